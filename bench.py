@@ -5,14 +5,19 @@ One "step" = one full DGPPO training iteration on the workload of BASELINE.json 
 4096 envs per GPU, T=128): stochastic rollout (collect) + deterministic rollout + value pre-passes + 2x GAE + advantage +
 all PPO minibatch updates (Vl, Vh, policy; clip + Adam), i.e. exactly what `algo.collect` + `algo.update` do per
 iteration (dgppo/trainer/trainer.py:131-137).  Counted work = B*T env-steps of the stochastic rollout per iteration
-(BASELINE.md §3).  Synthetic random scenes, random-init networks.
+(BASELINE.md §3).  Synthetic random scenes, random-init networks; every iteration starts from that seeded initial
+learner state (restore_learner in main) on its own scenes, so the last iteration's outputs are reproducible.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N>1: one rank per GPU.  Under `python -m torch.distributed.run --nproc-per-node N ...` the ranks come from the
         environment; a bare `python bench.py --gpus N` starts the N ranks itself (before touching the GPU).
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (raycast+graph kernel vs the HBM roofline, timed with HIP events
-inside this process), "cpu_baseline" (the CPU oracle timed on this box's host cores on a bounded sample), "phases".
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K iterations and reports what those iterations
+measured ("ms_per_step", "phases_ms_per_step", "mfma" flops).  --full adds the measurements that take runs of their own:
+"rollout_only_env_steps_per_s_per_gpu", "roofline" (raycast+graph kernel vs the HBM roofline, timed with HIP events inside
+this process), "cpu_baseline" (the CPU oracle timed on the host's cores on a bounded sample; --no-cpu-baseline drops
+it) and the offline MFMA-busy fraction.  --dump-outputs DIR writes what the last timed iteration computed (rank 0) as
+DIR/<name>.npy, see dump_outputs().
 """
 import argparse
 import json
@@ -68,11 +73,18 @@ def parse():
     p.add_argument("--obs", type=int, default=3)
     p.add_argument("--n-env", type=int, default=4096, help="envs PER GPU (weak scaling)")
     p.add_argument("--batch-size", type=int, default=16384)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also the rollout-only rate, the roofline loops, the CPU baseline and the offline MFMA-busy figure")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write what the last timed iteration computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     p.add_argument("--cpu-seconds", type=float, default=20.0)
     p.add_argument("--stall-seconds", type=float, default=420.0,
                    help="self-launched ranks (--gpus N without torchrun): stop the job when no rank has written anything for this long")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def roofline_env_kernel(cfg, device, B, iters=50):
@@ -166,6 +178,94 @@ def cpu_baseline(seconds_budget: float):
     return res
 
 
+DUMP_BYTES = 48 << 20          # budget of the sampled rollout arrays; parameters and scalars come on top (limit 64 MB)
+
+
+def dump_outputs(out_dir: str, eng, ro, det, info: dict) -> dict:
+    """What a caller of one iteration receives, after the last timed one: the stochastic and deterministic rollouts
+    (env-major records) of a fixed, seeded sample of envs, the updated flat parameters of the three networks and the logged
+    scalars.  float32 as computed (scalars float64).  -> {name: shape}"""
+    os.makedirs(out_dir, exist_ok=True)
+    fields = ("agent", "hits", "actions", "log_pis", "rewards", "costs")
+    rollouts = {"rollout": ro.finalize(), "det": det.finalize()}
+    tensors = [getattr(r, f) for r in rollouts.values() for f in fields if getattr(r, f, None) is not None]
+    B = ro.B
+    per_env = sum(t[0].numel() * t.element_size() for t in tensors)
+    S = max(1, min(B, 128, DUMP_BYTES // per_env))
+    idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(B, S, replace=False))).to(ro.rewards.device)
+    arrays = {}
+    for prefix, r in rollouts.items():
+        for f in fields:
+            t = getattr(r, f, None)
+            if t is not None:
+                arrays[f"{prefix}_{f}"] = t.index_select(0, idx).float().cpu().numpy()
+    for name, net in (("policy", eng.policy), ("Vl", eng.Vl), ("Vh", eng.Vh)):
+        arrays[f"{name}_params"] = net.params.float().cpu().numpy()
+    for k, v in info.items():
+        arrays["info_" + k.replace("/", "_")] = np.asarray(v, dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total / 2**20:.1f} MB (limit 64 MB)")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"dumped {len(arrays)} arrays ({total / 2**20:.1f} MB, {S} of {B} envs sampled) to {out_dir}")
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
+def full_measurements(args, out, eng, cfg, device, rank, B, T, world):
+    """--full: what a plain run leaves out — measurements that take runs of their own, after the timed iterations (the
+    rollout-only loop rewrites the engine's rollout records, so it comes after --dump-outputs)."""
+    from dgppo_amd import dist as D
+    log("timing the rollout alone and the raycast+graph kernel")
+    # the stochastic rollout alone (collect), timed after the training loop: env-steps/s of the rollout path by itself
+    seeds = torch.from_numpy(D.shard_seeds(rank, B, 10_000)).to(device)
+    eng.rollout(seeds, True, noise_seed=1)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    for r in range(3):
+        eng.rollout(seeds, True, noise_seed=2 + r)
+    torch.cuda.synchronize()
+    rollout_only = B * T * 3 / (time.perf_counter() - t1)
+    rl = roofline_env_kernel(cfg, device, B) if cfg.is_lidar and cfg.n_obs > 0 else None
+    rl_big = roofline_env_kernel(cfg, device, 4 * B, iters=30) if rl is not None else None
+    log(f"roofline kernel: {rl}")
+    out["rollout_only_env_steps_per_s_per_gpu"] = rollout_only
+    nnc = os.path.join(ROOT, "profiles", "r03_nn_counters.json")
+    if os.path.exists(nnc):
+        # matrix-core busy fraction of the update phase from the committed counter passes (rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES
+        # GRBM_GUI_ACTIVE ..., tools/collect_profiles.sh): measured offline, like roofline.traffic
+        try:
+            out["mfma"]["mfma_busy"] = json.load(open(nnc))["update_mfma_busy_frac"]
+            out["mfma"]["mfma_busy_source"] = "profiles/r03_nn_counters.json: SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8) over the update phase (offline pass)"
+        except Exception:
+            pass
+    if rl is not None:
+        traffic, tsrc = None, None
+        for name in ("r03_env_step_traffic.json", "r02_env_step_traffic.json", "r01_env_step_traffic.json"):
+            tpath = os.path.join(ROOT, "profiles", name)
+            if os.path.exists(tpath) and B == 4096 and args.env == "LidarSpread" and args.num_agents == 8 and args.obs == 3:
+                # HBM bytes per launch from the committed PMC passes (FETCH_SIZE x2-corrected + WRITE_SIZE), see profiles/README.md
+                traffic, tsrc = json.load(open(tpath))["hbm_bytes_per_launch_api_fetch_x2"], f"profiles/{name} (rocprofv3 --pmc, offline)"
+                break
+        comp = dict(rl["compact"])
+        flop_ray = 30.0 * cfg.n_agents * cfg.n_rays * cfg.n_obs * 4          # SURVEY §8d F_ray
+        comp["valu_tflops"] = flop_ray * comp["env_steps_per_s"] / 1e12
+        comp["valu_frac_of_fp32_peak"] = comp["valu_tflops"] / FP32_PEAK_TFLOPS
+        out["roofline"] = {"bound": "hbm", "kernel": "lidar_wave_kernel (dynamics + raycast + top-k + reward/cost + GraphsTuple emit)",
+                           "achieved": rl["api"]["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": rl["api"]["gbs"] / HBM_PEAK_GBS,
+                           "traffic": traffic, "traffic_source": tsrc,
+                           "algorithmic_bytes_per_launch": rl["api"]["bytes_per_env_step"] * B, "bytes_per_env_step": rl["api"]["bytes_per_env_step"],
+                           "us_per_launch": rl["api"]["us_per_launch"], "kernel_env_steps_per_s": rl["api"]["env_steps_per_s"],
+                           "at_4x_envs": {"envs": 4 * B, "us_per_launch": rl_big["api"]["us_per_launch"], "achieved": rl_big["api"]["gbs"],
+                                          "frac": rl_big["api"]["gbs"] / HBM_PEAK_GBS},
+                           "compact": comp}
+    if not args.no_cpu_baseline and world == 1:
+        try:
+            out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
+        except Exception as ex:  # the baseline must never take the GPU number down with it
+            out["cpu_baseline"] = {"error": repr(ex)}
+
+
 def spawn_ranks(args) -> int:
     """`python bench.py --gpus N` with no torchrun environment: the parent starts the N ranks itself — BEFORE it makes any GPU
     call (it never initialises HIP) — supervises them (dgppo_amd/launch.py: per-rank logs, stop everything on the first
@@ -225,13 +325,28 @@ def main():
     eng.Vl.load_tree(init.init_value(0, cfg.node_dim, 1, hp.Vl_gnn_layers, 2))
     eng.Vh.load_tree(init.init_value(0, cfg.node_dim, 2, hp.Vh_gnn_layers, 3))
     eng.set_entropy_noise(12345)
+    # Every iteration starts from this seeded learner state (parameters + Adam state).  The gradient reductions sum in no
+    # fixed order, and PPO iterations chained onto each other amplify those last-bit differences into different
+    # trajectories within two iterations; an iteration from a fixed state gives outputs another run or build can be
+    # compared with (--dump-outputs).  The work per iteration is the same either way.
+    learner = [t for k, net in eng.nets.items() for t in (net.params, eng.opt[k].m, eng.opt[k].v, eng.opt[k].state)]
+    learner0 = [t.clone() for t in learner]
+
+    def restore_learner():
+        for t, t0 in zip(learner, learner0):
+            t.copy_(t0)
+        for net in eng.nets.values():
+            net.prepare()
+
     B = args.n_env
     rng = np.random.default_rng(1000)                # the same permutation on every rank (shared seed)
     ev = lambda: torch.cuda.Event(enable_timing=True)
     phases = {"collect+det_rollout": 0.0, "update": 0.0}
+    last = {}                                        # rollout records of the latest iteration, for --dump-outputs
 
     def iteration(it: int, timed: bool):
         seeds = torch.from_numpy(D.shard_seeds(rank, B, it)).to(device)
+        restore_learner()
         e = [ev() for _ in range(3)]
         e[0].record()
         # algo.collect and the det_rollout_fn inside algo.update: same parameters, independent -> two HIP streams
@@ -241,6 +356,7 @@ def main():
             torch.cuda.synchronize(); log("first rollouts done")
         info = eng.update(ro, det, it, rng.permutation(B))                    # rest of algo.update (+ info sync)
         e[2].record()
+        last["ro"], last["det"] = ro, det
         if timed:
             torch.cuda.synchronize()
             phases["collect+det_rollout"] += e[0].elapsed_time(e[1])
@@ -277,19 +393,8 @@ def main():
         return
     ms_per_step = dt * 1e3 / args.steps
     value = world * B * T * args.steps / dt
-    log(f"training timed: {ms_per_step:.1f} ms/iteration -> {value:.0f} env-steps/s; timing the raycast+graph kernel")
-    # the stochastic rollout alone (collect), timed after the training loop: env-steps/s of the rollout path by itself
-    seeds = torch.from_numpy(D.shard_seeds(rank, B, 10_000)).to(device)
-    eng.rollout(seeds, True, noise_seed=1)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for r in range(3):
-        eng.rollout(seeds, True, noise_seed=2 + r)
-    torch.cuda.synchronize()
-    rollout_only = B * T * 3 / (time.perf_counter() - t1)
-    rl = roofline_env_kernel(cfg, device, B) if cfg.is_lidar and cfg.n_obs > 0 else None
-    rl_big = roofline_env_kernel(cfg, device, 4 * B, iters=30) if rl is not None else None
-    log(f"roofline kernel: {rl}")
+    log(f"training timed: {ms_per_step:.1f} ms/iteration -> {value:.0f} env-steps/s")
+    dumped = dump_outputs(args.dump_outputs, eng, last["ro"], last["det"], info) if args.dump_outputs else None
     sm = np.sort(np.asarray(step_ms))
     out = {
         "metric": "env-steps/sec whole node, LidarSpread n=8 4096 envs, 1/2/4/8 GPUs",
@@ -305,7 +410,6 @@ def main():
                               "note": "rank-0 wall time per iteration (each ends with the host sync of the logged scalars)"},
         "phases_ms_per_step": {k: v / args.steps for k, v in phases.items()},
         "update_host_ms_last_step": getattr(eng, "host_ms", None),
-        "rollout_only_env_steps_per_s_per_gpu": rollout_only,
         "mfma": {"flops_executed_per_step": flops_per_step, "unit": "flop (fp32, 2 per multiply-add, unpadded operand shapes)",
                  "tflops": flops_per_step / (ms_per_step * 1e-3) / 1e12, "peak_tflops": FP32_PEAK_TFLOPS,
                  "util": flops_per_step / (ms_per_step * 1e-3) / 1e12 / FP32_PEAK_TFLOPS,
@@ -317,43 +421,13 @@ def main():
                   "device": torch.cuda.get_device_name(device)},
         "last_info": {k: info[k] for k in ("policy/loss", "Vl/loss", "Vh/loss_Vh", "eval/safe_data")},
     }
-    nnc = os.path.join(ROOT, "profiles", "r03_nn_counters.json")
-    if os.path.exists(nnc):
-        # matrix-core busy fraction of the update phase from the committed counter passes (rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES
-        # GRBM_GUI_ACTIVE ..., tools/collect_profiles.sh): measured offline, like roofline.traffic
-        try:
-            out["mfma"]["mfma_busy"] = json.load(open(nnc))["update_mfma_busy_frac"]
-            out["mfma"]["mfma_busy_source"] = "profiles/r03_nn_counters.json: SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8) over the update phase (offline pass)"
-        except Exception:
-            pass
     if world > 1:
         out["multi_gpu"] = {"rccl_version": D.rccl_version(), "devices_visible": n_dev, "backend": backend,
                             "allreduce_selfcheck": "passed"}
-    if rl is not None:
-        traffic, tsrc = None, None
-        for name in ("r03_env_step_traffic.json", "r02_env_step_traffic.json", "r01_env_step_traffic.json"):
-            tpath = os.path.join(ROOT, "profiles", name)
-            if os.path.exists(tpath) and B == 4096 and args.env == "LidarSpread" and args.num_agents == 8 and args.obs == 3:
-                # HBM bytes per launch from the committed PMC passes (FETCH_SIZE x2-corrected + WRITE_SIZE), see profiles/README.md
-                traffic, tsrc = json.load(open(tpath))["hbm_bytes_per_launch_api_fetch_x2"], f"profiles/{name} (rocprofv3 --pmc, offline)"
-                break
-        comp = dict(rl["compact"])
-        flop_ray = 30.0 * cfg.n_agents * cfg.n_rays * cfg.n_obs * 4          # SURVEY §8d F_ray
-        comp["valu_tflops"] = flop_ray * comp["env_steps_per_s"] / 1e12
-        comp["valu_frac_of_fp32_peak"] = comp["valu_tflops"] / FP32_PEAK_TFLOPS
-        out["roofline"] = {"bound": "hbm", "kernel": "lidar_wave_kernel (dynamics + raycast + top-k + reward/cost + GraphsTuple emit)",
-                           "achieved": rl["api"]["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": rl["api"]["gbs"] / HBM_PEAK_GBS,
-                           "traffic": traffic, "traffic_source": tsrc,
-                           "algorithmic_bytes_per_launch": rl["api"]["bytes_per_env_step"] * B, "bytes_per_env_step": rl["api"]["bytes_per_env_step"],
-                           "us_per_launch": rl["api"]["us_per_launch"], "kernel_env_steps_per_s": rl["api"]["env_steps_per_s"],
-                           "at_4x_envs": {"envs": 4 * B, "us_per_launch": rl_big["api"]["us_per_launch"], "achieved": rl_big["api"]["gbs"],
-                                          "frac": rl_big["api"]["gbs"] / HBM_PEAK_GBS},
-                           "compact": comp}
-    if not args.no_cpu_baseline and world == 1:
-        try:
-            out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
-        except Exception as ex:  # the baseline must never take the GPU number down with it
-            out["cpu_baseline"] = {"error": repr(ex)}
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+    if args.full:
+        full_measurements(args, out, eng, cfg, device, rank, B, T, world)
     print(json.dumps(out), flush=True)
     close_comm()
     D.shutdown(world)

@@ -32,8 +32,8 @@ run nn_mfma 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS
 run nn_lds 600 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY --output-format csv -d $OUT/nn_lds -- python3 tools/prof_update_only.py
 unset MS REPS
 # ---- the whole benchmark under the tracer, then un-profiled reference numbers of the same build
-run bench_kt 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_kt -- python3 bench.py --steps 2 --warmup 2 --no-cpu-baseline
-run bench_plain 900 python3 bench.py
+run bench_kt 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_kt -- python3 bench.py --steps 2 --warmup 2 --full --no-cpu-baseline
+run bench_plain 900 python3 bench.py --full
 export DGPPO_HIP_LIB=$GRAFT_REPO_ROOT/dgppo_amd/csrc/libdgppo_hip_stamps.so
 run stamps 300 python3 tools/stamps_wave.py
 unset DGPPO_HIP_LIB

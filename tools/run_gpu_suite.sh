@@ -14,7 +14,7 @@ fi
 echo "tests rc=$rc"; tail -25 $O/gpu_tests.log | cut -c1-300
 if [ $rc -ge 124 ]; then echo "test run timed out / was killed: stopping"; exit $rc; fi
 [ "${SKIP_BENCH:-0}" = "1" ] && exit $rc
-timeout -k 10 400 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_quick.json 2> $O/bench_quick.err; brc=$?
+timeout -k 10 400 python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $O/bench_quick.json 2> $O/bench_quick.err; brc=$?
 echo "bench rc=$brc"; python3 - <<'PY'
 import json
 try:
