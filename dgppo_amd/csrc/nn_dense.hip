@@ -361,8 +361,7 @@ __global__ void __launch_bounds__(256) dense_smallk_kernel(DenseArgs a) {
 
 static bool dense_smallk_ok(const DenseArgs& a) {
   const long nq = (a.N + 3) / 4;                    // the multiply-high row index is exact while items * nq < 2^32
-  return a.K <= DSK_MAXK && a.N <= 192 && (long)a.M * nq * nq < (1l << 32) && !getenv("DGPPO_DENSE_NO_SMALLK") &&
-         !getenv("DGPPO_DENSE_NO_SMALLK_FWD");
+  return a.K <= DSK_MAXK && a.N <= 192 && (long)a.M * nq * nq < (1l << 32);
 }
 static void launch_dense_smallk(const DenseArgs& a, hipStream_t s) {
   const long items = (long)a.M * ((a.N + 3) / 4);
@@ -806,8 +805,7 @@ __global__ void __launch_bounds__(256) dense_bwd_w_smallk_kernel(DenseBwdWArgs a
 }
 
 static bool launch_bwd_w_smallk(DenseBwdWArgs a, hipStream_t s) {
-  if (a.K > 16 || a.N > 64 || (a.N & 3) || (a.ldy & 3) || (reinterpret_cast<uintptr_t>(a.dY) & 15) || a.M < 4096 ||
-      getenv("DGPPO_DENSE_NO_SMALLK") || getenv("DGPPO_DENSE_NO_SMALLK_BWD"))
+  if (a.K > 16 || a.N > 64 || (a.N & 3) || (a.ldy & 3) || (reinterpret_cast<uintptr_t>(a.dY) & 15) || a.M < 4096)
     return false;
   const int stride = ((a.K * a.N + a.N + 63) / 64) * 64;
   const long max_slabs = a.part ? (long)(a.ws_bytes / (sizeof(float) * stride)) : 0;

@@ -9,7 +9,6 @@
 //   losses                               dgppo/algo/informarl.py:374,428-438 ; dgppo/algo/dgppo.py:310
 //   backward = jax.grad of the above     dgppo/algo/informarl.py:377,440 ; dgppo/algo/dgppo.py:316
 #include "common.h"
-#include <stdlib.h>
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
@@ -146,9 +145,8 @@ extern "C" int32_t dgppo_ln_relu_bwd(const float* x, const float* y, const float
   if (M == 0) return 0;
   DGPPO_REQUIRE(x && y && stats && gamma && dy && dx && dgamma && dbeta, "ln_relu_bwd: NULL operand");
   // every workgroup ends with 128 float atomics on the same two cache lines (dgamma / dbeta): those serialise in L2, so the
-  // grid is kept at what the streaming part needs (DGPPO_LN_BWD_GRID: tuning override)
-  static const int cap = getenv("DGPPO_LN_BWD_GRID") ? atoi(getenv("DGPPO_LN_BWD_GRID")) : 256;
-  const int grid = min(cdiv(M, 16), cap);
+  // grid is kept at what the streaming part needs
+  const int grid = min(cdiv(M, 16), 256);
   hipLaunchKernelGGL(ln_relu_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, y, stats, gamma, dy, dx, dgamma,
                      dbeta, M);
   DGPPO_LAUNCH_CHECK();

@@ -640,7 +640,7 @@ extern "C" int32_t dgppo_mlp_gi_fwd(const float* X, int32_t ldx, const float* W1
   MlpGiArgs a{X, ldx, M, W1, b1, g1, be1, W2, b2, g2, be2, Wi, bi, p1, y1, st1, p2, y2, st2, gi};
   // rows per wave, weights in LDS (one 16-wave workgroup per CU): needs 16-byte addressable input rows
   if ((ldx & 3) == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W1) | reinterpret_cast<uintptr_t>(W2) |
-                          reinterpret_cast<uintptr_t>(Wi)) & 15) == 0 && !getenv("DGPPO_MLP_GI_TILED")) {
+                          reinterpret_cast<uintptr_t>(Wi)) & 15) == 0) {
     static thread_local int cus = 0;
     if (cus == 0) {
       int dev = 0;
@@ -1014,8 +1014,7 @@ extern "C" int32_t dgppo_gru1_head_fwd(const float* gi, const float* Wh, const f
   if (M == 0) return 0;
   GruHeadArgs a{gi, Wh, bhn, h0, W1, b1, W2, b2, hs, hprev, gates, u, out, M, n_out};
   // inference (nothing saved): rows per wave, weights in LDS
-  if (!hprev && !gates && !u && ((reinterpret_cast<uintptr_t>(Wh) | reinterpret_cast<uintptr_t>(W1) | reinterpret_cast<uintptr_t>(h0)) & 15) == 0 &&
-      !getenv("DGPPO_GRU1_TILED")) {
+  if (!hprev && !gates && !u && ((reinterpret_cast<uintptr_t>(Wh) | reinterpret_cast<uintptr_t>(W1) | reinterpret_cast<uintptr_t>(h0)) & 15) == 0) {
     static thread_local int cus = 0;
     if (cus == 0) {
       int dev = 0;

@@ -11,8 +11,6 @@
 // so this file only does: graph features, logits against RAW sender features, masked softmax, aggregation of raw
 // features, and the matching backward.  const(i,h) (the key bias) cancels in the softmax.
 #include "common.h"
-#include <stdlib.h>
-#include <type_traits>
 
 struct Topo {
   int n, ng, gs, os, per, lidar, spread;  // per = k (LiDAR) or n_obs (MPE)
@@ -853,9 +851,10 @@ static bool launch_attn_slot8_sj(const AttnArgs& a, int SJ, int grid, hipStream_
 #undef DGPPO_SJ
 }
 // H = 3 heads (the reference's GraphTransformer default, dgppo/nn/gnn.py:81), n <= 32 agents, S <= 64 slots
-static bool launch_attn_slot8(const AttnArgs& a, int grid, hipStream_t s, bool bwd) {
-  if (a.H != 3 || a.H > 8) return false;
-  const int NPA = (a.t.n + 7) / 8, SJ = (a.t.S + 7) / 8;
+static bool attn_slot8_shape(const Topo& t, int F, int H) { return F == 8 && H == 3 && t.n <= 32 && t.S <= 64; }
+static bool launch_attn_slot8(const AttnArgs& a, hipStream_t s, bool bwd) {
+  if (!attn_slot8_shape(a.t, a.F, a.H)) return false;
+  const int grid = (a.G + 3) / 4, NPA = (a.t.n + 7) / 8, SJ = (a.t.S + 7) / 8;
   switch (NPA) {
     case 1: return launch_attn_slot8_sj<3, 1>(a, SJ, grid, s, bwd);
     case 2: return launch_attn_slot8_sj<3, 2>(a, SJ, grid, s, bwd);
@@ -865,517 +864,21 @@ static bool launch_attn_slot8(const AttnArgs& a, int grid, hipStream_t s, bool b
   }
 }
 
-// ---- one wave per graph --------------------------------------------------------------------------------------------
-// For the graph sizes DGPPO uses (n*H <= 32 query rows, <= 96 nodes) a whole graph fits one wave: there is no
-// workgroup barrier anywhere, the 4 waves of a workgroup run 4 independent graphs and other waves fill the stalls.
-//   * MFMA fragments come straight from global memory in fragment layout.  The sum over features may visit k in any
-//     order as long as A and B agree, so lane (li, lq) takes the F/4 CONTIGUOUS features lq*F/4 .. of row li: a few
-//     16-byte loads per lane instead of strided 4-byte ones.
-//   * only the logit tile lives in LDS: L = Qt Xs^T is written there, the 8 lanes that own an (agent, head) pair read
-//     its logits, and overwrite the row with P in place (DS operations of one wave are ordered), then Zx = P Xs reads
-//     P as the A operand while the B operand (node rows, already in L2) is loaded directly in fragment layout.
-#ifndef DGPPO_ATTN_BWD_WPE
-#define DGPPO_ATTN_BWD_WPE 3
-#endif
-#define ATW_RT 2      // row tiles (n*H <= 32)
-#define ATW_BX 48     // registers for the node fragments of the logit GEMM: CT * F/4 <= 48
-#define ATW_BZ 48     // registers for the node fragments of the aggregation GEMM: 4*CT * ceil(F/16) <= 48
-// CT = ceil(Ns/16) node tiles, NP = ceil(n*H/8) softmax passes of 8 (agent, head) pairs, SJ = ceil(S/8) slots per softmax
-// lane: compile-time, so the kernel is straight-line code and the per-slot mask / edge features can be prefetched into
-// registers.
-template <int F, int CT, int NP, int SJ>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) attn_fwd_wave_kernel(AttnArgs a) {
-  extern __shared__ float sm[];
-  constexpr int FQ = F / 4, FT = (F + 15) / 16, KZ = CT * 4, Ll = CT * 16 + 1, RT = (NP + 1) / 2;   // RT query-row tiles
-  static_assert(CT * FQ <= ATW_BX && KZ * FT <= ATW_BZ && RT <= ATW_RT, "fragments exceed the register budget");
-  const Topo& t = a.t;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lq = lane >> 4;
-  // wave-uniform by construction; readfirstlane tells the compiler, so the per-graph base pointers live in SGPRs and the
-  // loads use scalar-base + 32-bit-offset addressing instead of 64-bit vector address arithmetic
-  const int g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-  if (g >= a.G) return;                                        // no barriers below: a wave may leave on its own
-  const int n = t.n, S = t.S, Ns = t.Ns, H = a.H, nH = n * H, Kp = a.Kp;
-  const int Wd = F + 4, kc = F + H * Wd;
-  const int hmagic = (65536 + H - 1) / H;                      // row / H == (row * hmagic) >> 16 for row * H < 65536
-  float* s_L = sm + wave * (RT * 16 * Ll);
-  ASTAMP(0);
-  const float* Xa = a.Xa + (size_t)g * n * F;
-  const float* Xo = a.Xo + (size_t)g * (Ns - n) * F - (size_t)n * F;   // indexed by node id (>= n)
-  const float* qt = a.qt + (size_t)g * nH * F;
-  float* zc = a.zcat + (size_t)g * n * Kp;
-  auto xrow = [&](int node) -> const float* {                  // rows past Ns are clamped: they only meet zeros of P
-    node = node < Ns ? node : Ns - 1;
-    return (node < n ? Xa : Xo) + (size_t)node * F;
-  };
-  // ---- fragments of the logit GEMM (rows past n*H clamped: those rows of L are cleared before they are used) ----
-  float aq[RT][FQ], bx[CT][FQ];
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    int row = rt * 16 + li;
-    row = row < nH ? row : nH - 1;
-    const float* p = qt + (size_t)row * F + lq * FQ;
-#pragma unroll
-    for (int u = 0; u < FQ; ++u) aq[rt][u] = p[u];
-  }
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct) {
-    const float* p = xrow(ct * 16 + li) + lq * FQ;
-#pragma unroll
-    for (int u = 0; u < FQ; ++u) bx[ct][u] = p[u];
-  }
-  // ---- everything else the wave will need from global memory, issued behind the fragments: the x_i rows that are
-  //      copied into zcat, and per softmax lane (8 lanes per (agent, head) pair, NP passes of 8 pairs) the mask and
-  //      edge features of its SJ slots ----
-  const int sub = lane & 7;
-  float4 xcopy = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (lane < n * FQ) xcopy = reinterpret_cast<const float4*>(Xa)[lane];
-  float mkv[NP][SJ];
-  int pi[NP], ph[NP];
-  {
-    const float* mk = a.emask + (size_t)g * n * S;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      int pair = (lane >> 3) + 8 * p;
-      pair = pair < nH ? pair : nH - 1;
-      pi[p] = (pair * hmagic) >> 16;
-      ph[p] = pair - pi[p] * H;
-#pragma unroll
-      for (int j = 0; j < SJ; ++j) {
-        int sl = sub + 8 * j;
-        sl = sl < S ? sl : S - 1;
-        mkv[p][j] = mk[pi[p] * S + sl];
-      }
-    }
-  }
-  // node fragments of the aggregation GEMM and the edge features of this lane's slots.  Narrow layers (F = 8) have the
-  // registers to request them together with the logit fragments — ONE global-memory round trip per graph; for F = 32
-  // that would cost the third wave per SIMD (measured: 122 vs 113 us), so there they are requested after the logit GEMM,
-  // when its fragments are dead, and land while the softmax runs.
-  constexpr bool EARLY = (F <= 8);
-  float bz[KZ][FT];
-  float4 efv[NP][SJ];
-  auto load_late_operands = [&]() {
-#pragma unroll
-    for (int k4 = 0; k4 < KZ; ++k4) {
-      const float* p = xrow(k4 * 4 + lq);
-#pragma unroll
-      for (int ft = 0; ft < FT; ++ft) { const int col = ft * 16 + li; bz[k4][ft] = p[col < F ? col : F - 1]; }
-    }
-    const float* ef = a.efeat + (size_t)g * n * S * 4;
-#pragma unroll
-    for (int p = 0; p < NP; ++p)
-#pragma unroll
-      for (int j = 0; j < SJ; ++j) {
-        int sl = sub + 8 * j;
-        sl = sl < S ? sl : S - 1;
-        efv[p][j] = reinterpret_cast<const float4*>(ef)[pi[p] * S + sl];
-      }
-  };
-  if constexpr (EARLY) { load_late_operands(); __builtin_amdgcn_sched_barrier(0); }
-  ASTAMP(1);
-  // ---- L = Qt Xs^T, one row tile at a time, its column tiles interleaved (independent accumulators) ----
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    f32x4g acc[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) acc[ct] = f32x4g{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < FQ; ++u)
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(aq[rt][u], bx[ct][u], acc[ct], 0, 0, 0);
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s_L[(rt * 16 + lq * 4 + r) * Ll + ct * 16 + li] = acc[ct][r];
-  }
-  ASTAMP(2);
-  if constexpr (!EARLY) { __builtin_amdgcn_sched_barrier(0); load_late_operands(); }
-  // the parts of zcat that are plain copies: x_i, the constant column, zero padding
-  if (lane < n * FQ) *reinterpret_cast<float4*>(zc + (lane / FQ) * Kp + 4 * (lane % FQ)) = xcopy;
-  for (int idx = lane + 64; idx < n * FQ; idx += 64)
-    *reinterpret_cast<float4*>(zc + (idx / FQ) * Kp + 4 * (idx % FQ)) = reinterpret_cast<const float4*>(Xa)[idx];
-  {
-    const int wpad = Kp - kc;                                  // >= 1: the constant column, then zeros
-    for (int i = lane; i < n; i += 64)
-      for (int c = 0; c < wpad; ++c) zc[i * Kp + kc + c] = (c == 0) ? 1.0f : 0.0f;
-  }
-  ASTAMP(3);
-  // ---- gather + softmax + edge aggregation + scatter of P ----
-  {
-    float* at = a.attn + (size_t)g * n * S * H;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const int pair = (lane >> 3) + 8 * p;
-      const bool live = pair < nH;
-      const int i = pi[p], h = ph[p];
-      float* Lrow = s_L + (live ? pair : 0) * Ll;
-      float l[SJ];
-      int nd[SJ];
-      float mx = -INFINITY;
-#pragma unroll
-      for (int j = 0; j < SJ; ++j) {
-        const int sl = sub + 8 * j;
-        const bool ok = live && sl < S;
-        nd[j] = ok ? sender_node(t, i, sl) : 0;
-        const float lv = Lrow[nd[j]];
-        l[j] = (ok && mkv[p][j] != 0.0f) ? lv : -INFINITY;
-        mx = fmaxf(mx, l[j]);
-      }
-      mx = grp8_max(mx);
-      float den = 0.0f;
-#pragma unroll
-      for (int j = 0; j < SJ; ++j) {
-        const float ev = (l[j] == -INFINITY) ? 0.0f : __expf(l[j] - mx)   /* v_exp_f32: rel. error ~1e-7 on weights <= 1 */;
-        l[j] = ev;
-        den += ev;
-      }
-      den = grp8_sum(den);
-      const float inv = (den > 0.0f) ? 1.0f / den : 0.0f;
-      if (live) {
-#pragma unroll
-        for (int c = 0; c < CT * 2; ++c) Lrow[sub + 8 * c] = 0.0f;   // own row: logits -> zeros -> P
-      }
-      float z0 = 0.f, z1 = 0.f, z2 = 0.f, z3 = 0.f;
-#pragma unroll
-      for (int j = 0; j < SJ; ++j) {
-        const int sl = sub + 8 * j;
-        if (live && sl < S) {
-          const float av = l[j] * inv;
-          if (a.attn != nullptr) at[(i * S + sl) * H + h] = av;
-          if (av != 0.0f) {   // masked slots may carry 5e5 / NaN edge features: skip, never multiply
-            Lrow[nd[j]] = av;
-            const float4 e = efv[p][j];
-            z0 = fmaf(av, e.x, z0); z1 = fmaf(av, e.y, z1); z2 = fmaf(av, e.z, z2); z3 = fmaf(av, e.w, z3);
-          }
-        }
-      }
-      z0 = grp8_sum(z0); z1 = grp8_sum(z1); z2 = grp8_sum(z2); z3 = grp8_sum(z3);
-      if (live && sub == 0) *reinterpret_cast<float4*>(zc + i * Kp + F + h * Wd + F) = make_float4(z0, z1, z2, z3);
-    }
-  }
-  // rows of the last row tile past n*H still hold logits of clamped query rows: P must be zero there
-  for (int idx = nH * Ll + lane; idx < RT * 16 * Ll; idx += 64) s_L[idx] = 0.0f;
-  ASTAMP(4);
-  // ---- Zx = P Xs: all (row tile, feature tile) accumulators interleaved over the node k-steps ----
-  {
-    f32x4g acc[RT][FT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-      for (int ft = 0; ft < FT; ++ft) acc[rt][ft] = f32x4g{0.f, 0.f, 0.f, 0.f};
-    // columns of P past Ns are zero (cleared, never scattered to), so clamped node rows contribute nothing
-#pragma unroll
-    for (int k0 = 0; k0 < KZ; k0 += 8) {
-      float pa[8][RT];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-          if (k0 + u < KZ) pa[u][rt] = s_L[(rt * 16 + li) * Ll + 4 * (k0 + u) + lq];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-          for (int ft = 0; ft < FT; ++ft)
-            if (k0 + u < KZ) acc[rt][ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[u][rt], bz[k0 + u][ft], acc[rt][ft], 0, 0, 0);
-    }
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = rt * 16 + lq * 4 + r;
-        const int i = (row * hmagic) >> 16, h = row - i * H;
-#pragma unroll
-        for (int ft = 0; ft < FT; ++ft) {
-          const int col = ft * 16 + li;
-          if (row < nH && col < F) zc[i * Kp + F + h * Wd + col] = acc[rt][ft][r];
-        }
-      }
-  }
-  ASTAMP(5); ASTAMP(6);
-}
-
-// ---- backward, one wave per graph ----------------------------------------------------------------------------------
-// Same layout rules as attn_fwd_wave_kernel.  The wave's LDS tile [RT*16][Ll] is used three times in sequence:
-//   1. dA = dZx Xs^T (dense), read back at the slots by the 8 lanes that own an (agent, head) pair, which compute the
-//      softmax backward dl = a (dA + dze.e - sum a (dA + dze.e)) in registers;
-//   2. the tile is overwritten with P (own rows, in place) and dXs += P^T dZx runs on the matrix cores;
-//   3. the tile is overwritten with dL and dQt = dL Xs, dXs += dL^T Qt run.
-// DS operations of a wave execute in order, so none of these hand-overs needs a barrier.  The dXs accumulators
-// (CT x ceil(F/16) tiles) stay in registers across 2 and 3.
-template <int F, int CT, int NP, int SJ>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DGPPO_ATTN_BWD_WPE, 8))) attn_bwd_wave_kernel(AttnArgs a) {
-  extern __shared__ float sm[];
-  constexpr int FQ = F / 4, FT = (F + 15) / 16, KZ = CT * 4, Ll = CT * 16 + 1, RT = (NP + 1) / 2, KP = RT * 4;
-  const Topo& t = a.t;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lq = lane >> 4;
-  // wave-uniform by construction; readfirstlane tells the compiler, so the per-graph base pointers live in SGPRs and the
-  // loads use scalar-base + 32-bit-offset addressing instead of 64-bit vector address arithmetic
-  const int g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-  if (g >= a.G) return;
-  const int n = t.n, S = t.S, Ns = t.Ns, H = a.H, nH = n * H, Kp = a.Kp;
-  const int Wd = F + 4;
-  const int hmagic = (65536 + H - 1) / H;
-  float* s_T = sm + wave * (RT * 16 * Ll);
-  const float* Xa = a.Xa + (size_t)g * n * F;
-  const float* Xo = a.Xo + (size_t)g * (Ns - n) * F - (size_t)n * F;
-  const float* qt = a.qt + (size_t)g * nH * F;
-  const float* dzc = a.dzcat + (size_t)g * n * Kp;
-  const bool want_dx = a.dXa != nullptr;
-  auto xrow = [&](int node) -> const float* {
-    node = node < Ns ? node : Ns - 1;
-    return (node < n ? Xa : Xo) + (size_t)node * F;
-  };
-  auto dzrow = [&](int pair) -> const float* {                 // dZx row of an (agent, head) pair inside dzcat (clamped)
-    pair = pair < nH ? pair : nH - 1;
-    const int i = (pair * hmagic) >> 16, h = pair - i * H;
-    return dzc + i * Kp + F + h * Wd;
-  };
-  // ---- fragments of dA = dZx Xs^T (k-permuted: lane (li, lq) takes features lq*F/4 .. of its row) ----
-  float adz[RT][FQ], bx[CT][FQ];
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    const float* p = dzrow(rt * 16 + li) + lq * FQ;
-#pragma unroll
-    for (int u = 0; u < FQ; ++u) adz[rt][u] = p[u];
-  }
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct) {
-    const float* p = xrow(ct * 16 + li) + lq * FQ;
-#pragma unroll
-    for (int u = 0; u < FQ; ++u) bx[ct][u] = p[u];
-  }
-  // ---- per softmax lane: attention weights, edge features and the edge part of dZ for its slots ----
-  const int sub = lane & 7;
-  float av[NP][SJ], ed[NP][SJ];
-  int pi[NP], ph[NP];
-  {
-    const float* ef = a.efeat + (size_t)g * n * S * 4;
-    const float* at = a.attn + (size_t)g * n * S * H;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      int pair = (lane >> 3) + 8 * p;
-      const bool live = pair < nH;
-      pair = live ? pair : nH - 1;
-      pi[p] = (pair * hmagic) >> 16;
-      ph[p] = pair - pi[p] * H;
-      const float4 dze = *reinterpret_cast<const float4*>(dzc + pi[p] * Kp + F + ph[p] * Wd + F);
-#pragma unroll
-      for (int j = 0; j < SJ; ++j) {
-        int sl = sub + 8 * j;
-        const bool ok = live && sl < S;
-        sl = sl < S ? sl : S - 1;
-        const float w = at[(pi[p] * S + sl) * H + ph[p]];
-        av[p][j] = ok ? w : 0.0f;
-        const float4 e = reinterpret_cast<const float4*>(ef)[pi[p] * S + sl];
-        // masked slots (a == 0) may carry 5e5 / NaN edge features: never multiply them
-        ed[p][j] = (ok && w != 0.0f) ? fmaf(dze.x, e.x, fmaf(dze.y, e.y, fmaf(dze.z, e.z, dze.w * e.w))) : 0.0f;
-      }
-    }
-  }
-  // ---- dA (dense) -> LDS tile ----
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    f32x4g acc[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) acc[ct] = f32x4g{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < FQ; ++u)
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(adz[rt][u], bx[ct][u], acc[ct], 0, 0, 0);
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s_T[(rt * 16 + lq * 4 + r) * Ll + ct * 16 + li] = acc[ct][r];
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  // ---- fragments needed later, requested now: dZx and Qt as B operands (k = pair), Xs as B operand (k = node) ----
-  float bdz[KP][FT], bq[KP][FT], bz[KZ][FT];
-#pragma unroll
-  for (int k4 = 0; k4 < KP; ++k4) {
-    const int pair = k4 * 4 + lq;
-    const float* pz = dzrow(pair);
-    const float* pq = qt + (size_t)(pair < nH ? pair : nH - 1) * F;
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft) {
-      const int col = ft * 16 + li, cc = col < F ? col : F - 1;
-      bdz[k4][ft] = want_dx ? pz[cc] : 0.0f;
-      bq[k4][ft] = want_dx ? pq[cc] : 0.0f;
-    }
-  }
-#pragma unroll
-  for (int k4 = 0; k4 < KZ; ++k4) {
-    const float* p = xrow(k4 * 4 + lq);
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft) { const int col = ft * 16 + li; bz[k4][ft] = p[col < F ? col : F - 1]; }
-  }
-  // ---- softmax backward in registers; the tile becomes P ----
-  float dl[NP][SJ];
-  int nd[NP][SJ];
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-    const int pair = (lane >> 3) + 8 * p;
-    const bool live = pair < nH;
-    float* Trow = s_T + (live ? pair : 0) * Ll;
-    float dot = 0.0f;
-#pragma unroll
-    for (int j = 0; j < SJ; ++j) {
-      const int sl = sub + 8 * j;
-      nd[p][j] = (live && sl < S) ? sender_node(t, pi[p], sl) : 0;
-      const float dA = (av[p][j] != 0.0f) ? Trow[nd[p][j]] + ed[p][j] : 0.0f;
-      dl[p][j] = dA;
-      dot = fmaf(av[p][j], dA, dot);
-    }
-    dot = grp8_sum(dot);
-#pragma unroll
-    for (int j = 0; j < SJ; ++j) dl[p][j] = av[p][j] * (dl[p][j] - dot);
-    if (live) {
-#pragma unroll
-      for (int cc = 0; cc < CT * 2; ++cc) Trow[sub + 8 * cc] = 0.0f;
-#pragma unroll
-      for (int j = 0; j < SJ; ++j) if (av[p][j] != 0.0f) Trow[nd[p][j]] = av[p][j];
-    }
-  }
-  // rows past n*H hold dA of clamped rows: they must be zero in every later use of the tile
-  for (int idx = nH * Ll + lane; idx < RT * 16 * Ll; idx += 64) s_T[idx] = 0.0f;
-  // ---- dXs += P^T dZx ----
-  f32x4g dxacc[CT][FT];
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft) dxacc[ct][ft] = f32x4g{0.f, 0.f, 0.f, 0.f};
-  if (want_dx) {
-#pragma unroll
-    for (int k4 = 0; k4 < KP; ++k4) {
-      float pa[CT];
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) pa[ct] = s_T[(k4 * 4 + lq) * Ll + ct * 16 + li];
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int ft = 0; ft < FT; ++ft) dxacc[ct][ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[ct], bdz[k4][ft], dxacc[ct][ft], 0, 0, 0);
-    }
-  }
-  // ---- the tile becomes dL ----
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-    const int pair = (lane >> 3) + 8 * p;
-    if (pair < nH) {
-      float* Trow = s_T + pair * Ll;
-#pragma unroll
-      for (int cc = 0; cc < CT * 2; ++cc) Trow[sub + 8 * cc] = 0.0f;
-#pragma unroll
-      for (int j = 0; j < SJ; ++j) if (dl[p][j] != 0.0f) Trow[nd[p][j]] = dl[p][j];
-    }
-  }
-  // ---- dQt = dL Xs ----
-  {
-    f32x4g acc[RT][FT];
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-      for (int ft = 0; ft < FT; ++ft) acc[rt][ft] = f32x4g{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k0 = 0; k0 < KZ; k0 += 8) {
-      float pa[8][RT];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-          if (k0 + u < KZ) pa[u][rt] = s_T[(rt * 16 + li) * Ll + 4 * (k0 + u) + lq];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-          for (int ft = 0; ft < FT; ++ft)
-            if (k0 + u < KZ) acc[rt][ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[u][rt], bz[k0 + u][ft], acc[rt][ft], 0, 0, 0);
-    }
-    float* dq = a.dqt + (size_t)g * nH * F;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = rt * 16 + lq * 4 + r;
-#pragma unroll
-        for (int ft = 0; ft < FT; ++ft) {
-          const int col = ft * 16 + li;
-          if (row < nH && col < F) dq[row * F + col] = acc[rt][ft][r];
-        }
-      }
-  }
-  // ---- dXs += dL^T Qt, then the stores (+ the direct x_i part of dzcat for agents) ----
-  if (want_dx) {
-#pragma unroll
-    for (int k4 = 0; k4 < KP; ++k4) {
-      float pa[CT];
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) pa[ct] = s_T[(k4 * 4 + lq) * Ll + ct * 16 + li];
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int ft = 0; ft < FT; ++ft) dxacc[ct][ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(pa[ct], bq[k4][ft], dxacc[ct][ft], 0, 0, 0);
-    }
-    // Epilogue in two passes.  What every output element still needs from memory — the direct x_i part of dzcat for an agent
-    // row, the sign of the node's own feature for the ReLU mask of another row — is READ FOR ALL ELEMENTS FIRST and the stores
-    // follow.  Interleaved (load, use, store per element) the compiler must keep program order between a store and the next
-    // load (the pointers may alias) and `s_waitcnt vmcnt(0)` before each use also waits for every earlier STORE: 40 fully
-    // serialised memory round trips per graph, 60 % of the kernel's wave time (SQ_WAIT_ANY, profiles/r03_nn_counters.json).
-    float side[CT][FT][4];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int node = ct * 16 + lq * 4 + r;
-#pragma unroll
-        for (int ft = 0; ft < FT; ++ft) {
-          const int f = ft * 16 + li;
-          float sv = 1.0f;
-          if (node < Ns && f < F) {
-            if (node < n) sv = dzc[node * Kp + f];
-            else if (a.dXo != nullptr && a.relu_xo) sv = a.Xo[((size_t)g * (Ns - n) + (node - n)) * F + f];   // just read as a fragment: an L2 hit
-          }
-          side[ct][ft][r] = sv;
-        }
-      }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int node = ct * 16 + lq * 4 + r;
-#pragma unroll
-        for (int ft = 0; ft < FT; ++ft) {
-          const int f = ft * 16 + li;
-          if (node >= Ns || f >= F) continue;
-          if (node < n) a.dXa[((size_t)g * n + node) * F + f] = dxacc[ct][ft][r] + side[ct][ft][r];
-          else if (a.dXo != nullptr) {
-            const size_t o = ((size_t)g * (Ns - n) + (node - n)) * F + f;
-            float v = dxacc[ct][ft][r];
-            if (a.relu_xo) v = (side[ct][ft][r] > 0.0f) ? v : 0.0f;
-            a.dXo[o] = v;
-          }
-        }
-      }
-  }
-}
-
 // ---- F = 32, block-diagonal form (one wave per graph) -----------------------------------------------------------
-// The dense wave kernels above form the whole [n*H x nodes] logit tile although an agent only attends to the nodes every
-// agent sees (agents, goals: "shared") and to its OWN 8 LiDAR hit nodes: 4/5 of the tile's columns (LidarSpread n = 8: 64
-// of 80) are used by one agent in eight.  Here the wave is laid out as 8 lanes per AGENT (il = lane / 8, sub = lane & 7):
+// A dense [n*H x nodes] logit tile (the workgroup MFMA kernels) is mostly wasted work: an agent only attends to the nodes
+// every agent sees (agents, goals: "shared") and to its OWN 8 LiDAR hit nodes, so 4/5 of the tile's columns (LidarSpread
+// n = 8: 64 of 80) are used by one agent in eight.  Here the wave is laid out as 8 lanes per AGENT (il = lane / 8, sub = lane & 7):
 //   * lane (il, sub) owns, for every head, the slots  {shared node p * 8 + sub, p < PS}  and  {hit sub}  of agent il, i.e.
 //     all S slots of an agent live in its 8 lanes (PS + 1 registers per head) and the softmax is a register / DPP matter;
 //   * all products run on the matrix cores as v_mfma_f32_4x4x1 (16 independent 4x4 blocks, one k per instruction): block
 //     (il, g2 = bit 2 of the lane), A rows = the 4 heads of agent il, B columns = 4 nodes (logits, dA) or 4 feature quads
 //     (aggregation, dQt).  A block only ever multiplies what its agent needs: 96 + 96 small MFMAs (1.5 k SIMD cycles) per
-//     graph forward instead of 160 16x16x4 tiles (5.1 k), 2.7 k instead of 10.2 k backward;
+//     graph forward instead of the dense tile's 160 16x16x4 tiles (5.1 k), 2.7 k instead of 10.2 k backward;
 //   * every global row is read ONCE, as coalesced 16-byte pieces, into a padded LDS image (shared rows, the 64 hit rows of
-//     the agent batch, query / dZ rows) from which all operand layouts are read; the dense kernels re-read the node rows
-//     from global memory per layout (2.4x the algorithmic bytes, profiles/r03_nn_counters.json).
+//     the agent batch, query / dZ rows) from which all operand layouts are read (a dense one-wave form that re-read the
+//     node rows from global memory per layout moved 2.4x the algorithmic bytes, profiles/r03_nn_counters.json).
 // More than 8 agents: batches of 8 agents run one after the other over the same staged shared rows.
-// Requirements (else the dense kernels above): F = 32, H <= 4, LiDAR hits 8 per agent (or no private nodes at all), at most
+// Requirements (attn_bd_shape): F = 32, H <= 4, LiDAR hits 8 per agent (or no private nodes at all), at most
 // 32 shared nodes.  Same arithmetic as gnn.py:85-117 up to the summation order.
 #define ABD_XL 36                      // LDS row stride of a staged 32-float row (16-byte aligned, conflict-free b128 row reads)
 #define ABD_DZL 40                     // the staged dZ rows carry the 4 edge-feature gradients behind the 32 features
@@ -2329,9 +1832,11 @@ __global__ void __launch_bounds__(64) attn_bwd_bd_kernel(AttnArgs a) {
   }
 }
 
-// the block-diagonal kernels apply when the private nodes are exactly 8 LiDAR hits per agent (or there are none)
+// the block-diagonal kernels apply when the private nodes are exactly 8 LiDAR hits per agent (or there are none), there are at
+// most 32 shared nodes (PS <= 4 groups of 8) and at most 16 agents (AB = ceil(n / 8) <= 2 agent batches; the shared nodes
+// include the agents, so AB <= PS)
 static bool attn_bd_shape(const Topo& t, int F, int H, int& PS, bool& hits) {
-  if (F != 32 || H < 1 || H > 4 || getenv("DGPPO_ATTN_NO_BD")) return false;
+  if (F != 32 || H < 1 || H > 4 || t.n > 16) return false;
   const int n_priv = t.Ns - t.n - t.ng;
   hits = t.lidar && n_priv > 0;
   if (hits && (t.per != 8 || n_priv != t.n * 8)) return false;
@@ -2344,30 +1849,20 @@ static void launch_attn_bd_x(const AttnArgs& a, hipStream_t s, bool bwd) {
   using L = AbdLds<PS, HITS>;
   if (bwd) { hipLaunchKernelGGL((attn_bwd_bd_kernel<PS, HITS, AB, XOF>), dim3(a.G), dim3(64), sizeof(float) * L::BWD, s, a); return; }
   if constexpr (AB == 1) {
-    if (!getenv("DGPPO_ATTN_NO_PERSIST")) {
-      // persistent waves with the next graph's loads in flight: as many 2-wave workgroups as fit the chip (LDS-limited), unless
-      // the launch is small enough that every graph gets its own wave anyway
-      static thread_local int cap = 0;
-      if (cap == 0) {
-        int per_cu = 0, dev = 0, cus = 256;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&attn_fwd_bdp_kernel<PS, HITS, XOF>), 128,
-                                                         sizeof(float) * 2 * L::FWD) != hipSuccess || per_cu < 1) per_cu = 1;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            cus < 1) cus = 256;
-        cap = per_cu * cus;
-      }
-      const int wgs = (a.G + 1) / 2;
-      if (const char* force = getenv("DGPPO_ATTN_PERSIST_WGS")) {     // tests: walk several graphs per wave on a tiny launch
-        const int fw = atoi(force);
-        if (fw > 0) {
-          hipLaunchKernelGGL((attn_fwd_bdp_kernel<PS, HITS, XOF>), dim3(fw < wgs ? fw : wgs), dim3(128), sizeof(float) * 2 * L::FWD, s, a);
-          return;
-        }
-      }
-      if (wgs > 2 * cap) {        // (smaller launches: one graph per wave in the leaner kernel below — more waves per CU)
-        hipLaunchKernelGGL((attn_fwd_bdp_kernel<PS, HITS, XOF>), dim3(cap), dim3(128), sizeof(float) * 2 * L::FWD, s, a);
-        return;
-      }
+    // persistent waves with the next graph's loads in flight: as many 2-wave workgroups as fit the chip (LDS-limited), unless
+    // the launch is small enough that every graph gets its own wave anyway
+    static thread_local int cap = 0;
+    if (cap == 0) {
+      int per_cu = 0, dev = 0, cus = 256;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&attn_fwd_bdp_kernel<PS, HITS, XOF>), 128,
+                                                       sizeof(float) * 2 * L::FWD) != hipSuccess || per_cu < 1) per_cu = 1;
+      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+          cus < 1) cus = 256;
+      cap = per_cu * cus;
+    }
+    if ((a.G + 1) / 2 > 2 * cap) {   // (smaller launches: one graph per wave in the leaner kernel below — more waves per CU)
+      hipLaunchKernelGGL((attn_fwd_bdp_kernel<PS, HITS, XOF>), dim3(cap), dim3(128), sizeof(float) * 2 * L::FWD, s, a);
+      return;
     }
   }
   hipLaunchKernelGGL((attn_fwd_bd_kernel<PS, HITS, AB, XOF>), dim3((a.G + 1) / 2), dim3(128), sizeof(float) * 2 * L::FWD, s, a);
@@ -2381,50 +1876,13 @@ static bool launch_attn_bd(const AttnArgs& a, hipStream_t s, bool bwd) {
   int PS = 0;
   bool hits = false;
   if (!attn_bd_shape(a.t, a.F, a.H, PS, hits)) return false;
-  const int AB = (a.t.n + 7) / 8;                   // agent batches; the shared nodes include the agents, so AB <= (PS + 1) / 2 <= 2
+  const int AB = (a.t.n + 7) / 8;
   switch ((PS * 2 + (hits ? 1 : 0)) * 4 + AB) {
 #define DGPPO_BD(P, HT, B) case ((P) * 2 + (HT)) * 4 + (B): launch_attn_bd_one<P, (HT) != 0, B>(a, s, bwd); return true;
-    DGPPO_BD(1, 0, 1) DGPPO_BD(1, 1, 1) DGPPO_BD(2, 0, 1) DGPPO_BD(2, 1, 1)
+    DGPPO_BD(1, 0, 1) DGPPO_BD(1, 1, 1) DGPPO_BD(2, 0, 1) DGPPO_BD(2, 1, 1) DGPPO_BD(2, 0, 2) DGPPO_BD(2, 1, 2)
     DGPPO_BD(3, 0, 1) DGPPO_BD(3, 1, 1) DGPPO_BD(3, 0, 2) DGPPO_BD(3, 1, 2)
     DGPPO_BD(4, 0, 1) DGPPO_BD(4, 1, 1) DGPPO_BD(4, 0, 2) DGPPO_BD(4, 1, 2)
 #undef DGPPO_BD
-    default: return false;
-  }
-}
-
-// dispatch over the compile-time tile counts; returns false if the shape has no instantiation
-template <int F, int CT, int NP>
-static bool launch_attn_wave_sj(const AttnArgs& a, int SJ, int grid, hipStream_t s, bool bwd) {
-  const size_t smem = sizeof(float) * 4 * ((NP + 1) / 2) * 16 * (CT * 16 + 1);
-#define DGPPO_SJ(J)                                                                                              \
-  case J:                                                                                                        \
-    if (bwd) hipLaunchKernelGGL((attn_bwd_wave_kernel<F, CT, NP, J>), dim3(grid), dim3(256), smem, s, a);        \
-    else hipLaunchKernelGGL((attn_fwd_wave_kernel<F, CT, NP, J>), dim3(grid), dim3(256), smem, s, a);            \
-    return true;
-  switch (SJ) {
-    DGPPO_SJ(1) DGPPO_SJ(2) DGPPO_SJ(3) DGPPO_SJ(4)
-    default: return false;
-  }
-#undef DGPPO_SJ
-}
-template <int F, int CT>
-static bool launch_attn_wave_np(const AttnArgs& a, int NP, int SJ, int grid, hipStream_t s, bool bwd) {
-  switch (NP) {
-    case 1: return launch_attn_wave_sj<F, CT, 1>(a, SJ, grid, s, bwd);
-    case 2: return launch_attn_wave_sj<F, CT, 2>(a, SJ, grid, s, bwd);
-    case 3: return launch_attn_wave_sj<F, CT, 3>(a, SJ, grid, s, bwd);
-    case 4: return launch_attn_wave_sj<F, CT, 4>(a, SJ, grid, s, bwd);
-    default: return false;
-  }
-}
-template <int F>
-static bool launch_attn_wave(const AttnArgs& a, int CT, int NP, int SJ, int grid, hipStream_t s, bool bwd = false) {
-  constexpr int FQ = F / 4, FT = (F + 15) / 16;
-  constexpr int CTMAX = (ATW_BX / FQ) < (ATW_BZ / (4 * FT)) ? (ATW_BX / FQ) : (ATW_BZ / (4 * FT));
-  switch (CT) {
-#define DGPPO_CASE(C) case C: if constexpr (C <= CTMAX) return launch_attn_wave_np<F, C>(a, NP, SJ, grid, s, bwd); else return false;
-    DGPPO_CASE(1) DGPPO_CASE(2) DGPPO_CASE(3) DGPPO_CASE(4) DGPPO_CASE(5) DGPPO_CASE(6)
-#undef DGPPO_CASE
     default: return false;
   }
 }
@@ -2586,6 +2044,22 @@ static int32_t attn_check(const dgppo_env_cfg* cfg, int F, int H, int Kp, int G,
   return 0;
 }
 
+// The attention kernel families, chosen by shape alone; the first one whose conditions hold runs:
+//   SLOT8  F = 8, H = 3, n <= 32, S <= 64 (attn_slot8_shape); the backward writes no input gradient (first layer only)
+//   BD     F = 32 block-diagonal topologies (attn_bd_shape)
+//   MFMA   one workgroup per graph on the matrix cores: F % 4 == 0, S <= 64, LDS image <= 64 KB; backward for F >= 16 only
+//   VALU   one workgroup per graph, every other shape (and the narrow backward, where it beats MFMA: measured)
+// The one-wave families (SLOT8, BD) store zcat rows in 16-byte pieces, hence Kp % 4 == 0.
+enum class AttnFamily { SLOT8, BD, MFMA, VALU };
+static AttnFamily attn_family(const Topo& t, int F, int H, int Kp, bool bwd, bool dXa) {
+  int PS = 0;
+  bool hits = false;
+  if ((Kp & 3) == 0 && attn_slot8_shape(t, F, H) && !(bwd && dXa)) return AttnFamily::SLOT8;
+  if ((Kp & 3) == 0 && attn_bd_shape(t, F, H, PS, hits)) return AttnFamily::BD;
+  if ((F & 3) == 0 && t.S <= 64 && attn_mfma_smem(attn_dims(t, F, H), bwd) <= 64 * 1024 && (!bwd || F >= 16)) return AttnFamily::MFMA;
+  return AttnFamily::VALU;
+}
+
 extern "C" int32_t dgppo_attn_fwd(const dgppo_env_cfg* cfg, int32_t F, int32_t H, int32_t Kp, const float* qt,
                                   const float* Xa, const float* Xo, const float* efeat, const float* emask, float* zcat,
                                   float* attn, int32_t G, void* stream) {
@@ -2597,29 +2071,20 @@ extern "C" int32_t dgppo_attn_fwd(const dgppo_env_cfg* cfg, int32_t F, int32_t H
   DGPPO_REQUIRE(a.t.Ns == a.t.n || Xo, "attn_fwd: Xo is NULL");
   a.qt = qt; a.Xa = Xa; a.Xo = Xo; a.efeat = efeat; a.emask = emask; a.zcat = zcat; a.attn = attn;
   const Topo& t = a.t;
+  const hipStream_t s = (hipStream_t)stream;
   const size_t smem = sizeof(float) * ((size_t)t.Ns * (F + 1) + (size_t)t.n * H * (F + 1) + (size_t)t.n * t.S * 5 +
                                        (size_t)t.n * t.S * H);
   DGPPO_REQUIRE(smem <= 64 * 1024, "attn_fwd: graph too large for LDS (%zu B)", smem);
-  const AttnDims d = attn_dims(t, F, H);
-  const size_t msmem = attn_mfma_smem(d, false);
-  const bool mfma_ok = (F & 3) == 0 && t.S <= 64 && msmem <= 64 * 1024 && !getenv("DGPPO_ATTN_VALU");
-  // one wave per graph when the shape has an instantiation (fragments within the register budget)
-  bool launched = false;
-  if (mfma_ok && (Kp & 3) == 0 && t.n * H * H < 65536 && !getenv("DGPPO_ATTN_BLOCK")) {
-    const int grid = (G + 3) / 4;
-    // instantiated for the widths the reference's defaults produce (node features padded to 8, msg_dim 32); other
-    // multiples of 4 take the workgroup-per-graph kernels below
-    // narrow first layer: slot-sparse VALU kernel (one memory round trip per graph); DGPPO_ATTN_DENSE8 forces the MFMA form
-    if (F == 8 && !getenv("DGPPO_ATTN_DENSE8")) launched = launch_attn_slot8(a, grid, (hipStream_t)stream, false);
-    if (!launched && F == 32) launched = launch_attn_bd(a, (hipStream_t)stream, false);
-    if (launched) {}
-    else if (F == 8) launched = launch_attn_wave<8>(a, d.CT, (d.nH + 7) / 8, (t.S + 7) / 8, grid, (hipStream_t)stream);
-    else if (F == 32) launched = launch_attn_wave<32>(a, d.CT, (d.nH + 7) / 8, (t.S + 7) / 8, grid, (hipStream_t)stream);
+  bool launched = true;
+  switch (attn_family(t, F, H, Kp, false, false)) {
+    case AttnFamily::SLOT8: launched = launch_attn_slot8(a, s, false); break;
+    case AttnFamily::BD: launched = launch_attn_bd(a, s, false); break;
+    case AttnFamily::MFMA:
+      hipLaunchKernelGGL(attn_fwd_kernel, dim3(G), dim3(256), attn_mfma_smem(attn_dims(t, F, H), false), s, a);
+      break;
+    case AttnFamily::VALU: hipLaunchKernelGGL(attn_fwd_valu_kernel, dim3(G), dim3(256), smem, s, a); break;
   }
-  if (!launched) {       // workgroup-per-graph fallbacks: MFMA for F % 4 == 0, plain VALU otherwise
-    if (mfma_ok) hipLaunchKernelGGL(attn_fwd_kernel, dim3(G), dim3(256), msmem, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(attn_fwd_valu_kernel, dim3(G), dim3(256), smem, (hipStream_t)stream, a);
-  }
+  DGPPO_REQUIRE(launched, "attn_fwd: dispatch failed");
   DGPPO_LAUNCH_CHECK();
   return 0;
 }
@@ -2633,40 +2098,29 @@ extern "C" int32_t dgppo_attn_bwd(const dgppo_env_cfg* cfg, int32_t F, int32_t H
   if (rc) return rc;
   if (G == 0) return 0;
   DGPPO_REQUIRE(dzcat && attn && qt && Xa && efeat && dqt, "attn_bwd: NULL operand");
-  a.relu_xo = 0;
   DGPPO_REQUIRE(a.t.Ns == a.t.n || Xo, "attn_bwd: Xo is NULL");
   DGPPO_REQUIRE(!(dXo && !dXa), "attn_bwd: dXo needs dXa");
   a.dzcat = dzcat; a.attn = (float*)attn; a.qt = qt; a.Xa = Xa; a.Xo = Xo; a.efeat = efeat; a.dqt = dqt; a.dXa = dXa; a.dXo = dXo;
   const Topo& t = a.t;
+  const hipStream_t s = (hipStream_t)stream;
   const size_t smem = sizeof(float) * ((size_t)t.Ns * (F + 1) + (size_t)t.n * H * (F + 1) + (size_t)t.n * t.S * 4 +
                                        2 * (size_t)t.n * t.S * H + (size_t)t.n * H * (F + 5));
   DGPPO_REQUIRE(smem <= 64 * 1024, "attn_bwd: graph too large for LDS (%zu B)", smem);
-  const AttnDims d = attn_dims(t, F, H);
-  const size_t msmem = attn_mfma_smem(d, true);
-  // one wave per graph when the shape has an instantiation (same conditions as the forward)
-  bool launched = false;
-  if ((F & 3) == 0 && t.S <= 64 && (Kp & 3) == 0 && t.n * H * H < 65536 && !getenv("DGPPO_ATTN_VALU") &&
-      !getenv("DGPPO_ATTN_BLOCK")) {
-    const int grid = (G + 3) / 4, NP = (d.nH + 7) / 8, SJ = (t.S + 7) / 8;
-    a.relu_xo = (relu_xo && dXo) ? 1 : 0;          // fused into the wave kernel's dXo store
-    if (F == 8 && !dXa && !getenv("DGPPO_ATTN_DENSE8")) launched = launch_attn_slot8(a, grid, (hipStream_t)stream, true);
-    if (!launched && F == 32) launched = launch_attn_bd(a, (hipStream_t)stream, true);
-    if (launched) {}
-    else if (F == 8) launched = launch_attn_wave<8>(a, d.CT, NP, SJ, grid, (hipStream_t)stream, true);
-    else if (F == 32) launched = launch_attn_wave<32>(a, d.CT, NP, SJ, grid, (hipStream_t)stream, true);
-    a.relu_xo = 0;
+  const AttnFamily fam = attn_family(t, F, H, Kp, true, dXa != nullptr);
+  a.relu_xo = (relu_xo && dXo && fam == AttnFamily::BD) ? 1 : 0;     // fused into the block-diagonal kernel's dXo store
+  bool launched = true;
+  switch (fam) {
+    case AttnFamily::SLOT8: launched = launch_attn_slot8(a, s, true); break;
+    case AttnFamily::BD: launched = launch_attn_bd(a, s, true); break;
+    case AttnFamily::MFMA:
+      hipLaunchKernelGGL(attn_bwd_kernel, dim3(G), dim3(256), attn_mfma_smem(attn_dims(t, F, H), true), s, a);
+      break;
+    case AttnFamily::VALU: hipLaunchKernelGGL(attn_bwd_valu_kernel, dim3(G), dim3(256), smem, s, a); break;
   }
-  if (!launched) {       // workgroup-per-graph fallbacks; among them the VALU kernel wins for narrow layers (measured)
-    if ((F & 3) == 0 && F >= 16 && t.S <= 64 && msmem <= 64 * 1024 && !getenv("DGPPO_ATTN_VALU"))
-      hipLaunchKernelGGL(attn_bwd_kernel, dim3(G), dim3(256), msmem, (hipStream_t)stream, a);
-    else
-      hipLaunchKernelGGL(attn_bwd_valu_kernel, dim3(G), dim3(256), smem, (hipStream_t)stream, a);
-    DGPPO_LAUNCH_CHECK();
-    if (relu_xo && dXo)    // the fallback kernels do not fuse the ReLU mask of the other nodes' gradient: separate pass
-      return dgppo_relu_bwd(dXo, Xo, (int64_t)G * (t.Ns - t.n) * F, stream);
-    return 0;
-  }
+  DGPPO_REQUIRE(launched, "attn_bwd: dispatch failed");
   DGPPO_LAUNCH_CHECK();
+  if (relu_xo && dXo && !a.relu_xo)    // the workgroup kernels do not fuse the ReLU mask of the other nodes' gradient: separate pass
+    return dgppo_relu_bwd(dXo, Xo, (int64_t)G * (t.Ns - t.n) * F, stream);
   return 0;
 }
 
@@ -2677,10 +2131,7 @@ extern "C" int32_t dgppo_attn_bwd(const dgppo_env_cfg* cfg, int32_t F, int32_t H
 // (gnn.py:85-117).  dgppo_attn_xo_supported tells the caller whether the topology has such a kernel; if not, materialise Xo
 // (dgppo_dense_fwd) and call dgppo_attn_fwd / dgppo_attn_bwd.
 static bool attn_xo_ok(const Topo& t, int F, int H, int Kp) {
-  int PS = 0;
-  bool hits = false;
-  return t.Ns > t.n && (Kp & 3) == 0 && t.S <= 64 && t.n * H * H < 65536 && !getenv("DGPPO_ATTN_VALU") && !getenv("DGPPO_ATTN_BLOCK") &&
-         !getenv("DGPPO_ATTN_NO_XO") && attn_bd_shape(t, F, H, PS, hits);
+  return t.Ns > t.n && attn_family(t, F, H, Kp, true, true) == AttnFamily::BD;
 }
 extern "C" int32_t dgppo_attn_xo_supported(const dgppo_env_cfg* cfg, int32_t F, int32_t H, int32_t Kp) {
   AttnArgs a{};

@@ -6,7 +6,6 @@ kernels); `layout` maps flax-style names to (offset, shape).  Torch
 from __future__ import annotations
 
 import math
-import os
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -391,7 +390,7 @@ class Net:
         def _alloc(n_floats):
             self._bwdw_floats = max(ws_floats, n_floats)
             return self.ws_arena.get(f"{tag}.bwdw_ws", self._bwdw_floats)
-        batch = K.BwdWBatch(self.device, _alloc) if (dout.is_cuda and os.environ.get("DGPPO_NO_BWDW_BATCH") is None) else None
+        batch = K.BwdWBatch(self.device, _alloc) if dout.is_cuda else None
         if batch is not None:
             batch.__enter__()
         try:
@@ -418,9 +417,8 @@ class Net:
         Ro = G * feats.n_other
         feat = act["feat"]
         # the MLP trunk + GRU input projection ran as the fused forward kernel (64-wide chain, one GRU layer): its backward chain
-        # is fused as well (DGPPO_NO_FUSED_TRUNK_BWD=1: the separate launches, for A/B runs and as the tests' second opinion)
-        fused_trunk = (self.rnn == "gru" and self.rnn_layers == 1 and self.kind != "Vhg" and dout.is_cuda
-                       and os.environ.get("DGPPO_NO_FUSED_TRUNK_BWD") is None)
+        # is fused as well (the separate launches remain for the other trunk / RNN options)
+        fused_trunk = self.rnn == "gru" and self.rnn_layers == 1 and self.kind != "Vhg" and dout.is_cuda
         dgi0 = None
         dhs = A.get(f"{tag}.dhs", Rh, HID)
         if self.kind == "policy":
@@ -520,7 +518,7 @@ class Net:
             dXo_l = A.get(f"{tag}.dXo{l}", Ro, fp) if (need_dx and Ro > 0) else None
             more_dXo = dXo_prev is not None and dXo_l is not None       # a dense term still accumulates into dXo_l (>= 3 layers)
             xf = act.get(f"xo_fused{l}")
-            if xf is not None and dXa_l is not None and not more_dXo and not os.environ.get("DGPPO_ATTN_XO_NO_DW"):
+            if xf is not None and dXa_l is not None and not more_dXo:
                 # the gradient of the recomputed rows never leaves the kernel: it goes straight into dWout_{l-1}[:8] / dbu_{l-1}
                 ws = A.get(f"{tag}.xo_ws", K.attn_xo_workspace_floats(G), 1).view(-1)
                 K.attn_bwd_xo_dw(cfg, fp, H_HEADS, kp, dz, act[f"attn{l}"], act[f"qt{l}"], act[f"Xa{l}"], xf[0], xf[1], xf[2],

@@ -368,3 +368,41 @@ def value_Vh(vp, graph, h, n_agents, global_info: bool = False):
 
 def graph_to_torch(g: Dict[str, np.ndarray]) -> Dict[str, Tensor]:
     return {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in g.items()}
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# kernel-level contract of dgppo_attn_fwd / dgppo_attn_bwd (the per-agent fixed-fan-in form of gnn.py:85-117, DESIGN "GNN
+# layer"): logits against the RAW sender rows, masked softmax over an agent's S slots, aggregation of raw rows + edge features
+# ----------------------------------------------------------------------------------------------------------------------
+def attn_sender_nodes(n: int, n_goals: int, goal_slots: int, obs_slots: int, lidar: bool, spread: bool) -> Tensor:
+    """[n, S] node id behind slot s of agent i: the n agents, then the goals (every goal for the Spread kinds, the agent's own
+    goal otherwise), then the obstacle nodes (the agent's own LiDAR hits, or every MPE obstacle).  Nodes are numbered agents,
+    goals, obstacle nodes."""
+    idx = []
+    for i in range(n):
+        row = list(range(n))
+        row += [n + g for g in range(goal_slots)] if spread else [n + i]
+        row += [n + n_goals + (i * obs_slots if lidar else 0) + m for m in range(obs_slots)]
+        idx.append(row)
+    return torch.tensor(idx, dtype=torch.int64)
+
+
+def attn_fixed_fan_in(senders: Tensor, qt: Tensor, Xa: Tensor, Xo: Optional[Tensor], efeat: Tensor, emask: Tensor,
+                      Kp: int) -> Tuple[Tensor, Tensor]:
+    """qt [G, n, H, F], Xa [G, n, F], Xo [G, Ns - n, F] or None, efeat [G, n, S, 4], emask [G, n, S] ->
+    zcat [G, n, Kp] = [x_i | per head: sum_s a x_s (F), sum_s a e_s (4) | 1 | 0-pad], attn [G, n, S, H].
+    a = softmax over the unmasked slots of qt_h . x_s (0 on masked slots); masked edge features (NaN allowed) never enter."""
+    G, n, H, Fw = qt.shape
+    X = Xa if Xo is None else torch.cat([Xa, Xo], 1)
+    xs = X[:, senders]                                                       # [G, n, S, F]
+    m = (emask != 0)[..., None]                                              # [G, n, S, 1]
+    logits = torch.einsum("gihf,gisf->gish", qt, xs)
+    mx = torch.where(m, logits, -torch.inf).amax(2, keepdim=True).detach()
+    ex = torch.where(m, torch.exp(torch.where(m, logits, mx) - mx.nan_to_num(neginf=0.0)), 0.0)
+    den = ex.sum(2, keepdim=True)
+    a = ex / torch.where(den > 0, den, 1.0)
+    e = torch.where(m, efeat, 0.0)
+    agg = torch.cat([torch.einsum("gish,gisf->gihf", a, xs), torch.einsum("gish,gisc->gihc", a, e)], -1)   # [G, n, H, F + 4]
+    pad = Kp - Fw - H * (Fw + 4)
+    const = torch.cat([torch.ones(G, n, 1, dtype=qt.dtype), torch.zeros(G, n, pad - 1, dtype=qt.dtype)], -1)
+    return torch.cat([Xa, agg.reshape(G, n, H * (Fw + 4)), const], -1), a

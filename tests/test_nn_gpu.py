@@ -100,14 +100,18 @@ def test_dense_kernels_random_shape_sweep(cuda):
             _close(db, db0 + dY.sum(0), 3e-6 * math.sqrt(M) + 1e-6, f"dense_bwd_w bias M={M} N={Nd}")
 
 
-@pytest.mark.parametrize("M,save,strided", [(1, True, False), (33, False, False), (1000, True, True), (40000, True, False)])
+@pytest.mark.parametrize("M,save,strided", [(1, True, False), (33, False, False), (1000, True, True), (40000, True, False),
+                                           (1000, False, "misaligned")])
 def test_mlp_gi_fused(cuda, M, save, strided):
     """fused Dense->LN->ReLU->Dense->LN->ReLU->Dense(192) against the plain torch fp32 composition (mlp.py:17-29,
-    rnn.py:14-30); ragged M (not a multiple of the 32-row tile), strided input, with and without the saved activations."""
+    rnn.py:14-30); ragged M (not a multiple of the 32-row tile), strided input, with and without the saved activations.
+    The strided view starts at column 8 of an 80-wide buffer, rows stay 16-byte aligned (rows-per-wave kernel); the misaligned
+    one starts at column 1, which only the 32-row-tile kernel takes."""
+    off = 1 if strided == "misaligned" else 8
     from dgppo_amd import ops_nn as K_
     g = torch.Generator().manual_seed(M)
     Xfull = torch.randn(M, 80, generator=g)
-    X = Xfull[:, 8:72] if strided else Xfull[:, :64].contiguous()
+    X = Xfull[:, off:off + 64] if strided else Xfull[:, :64].contiguous()
     P = {k: torch.randn(*shp, generator=g) * sc for k, shp, sc in (
         ("W1", (64, 64), 0.2), ("b1", (64,), 0.1), ("g1", (64,), 1.0), ("be1", (64,), 0.1), ("W2", (64, 64), 0.2),
         ("b2", (64,), 0.1), ("g2", (64,), 1.0), ("be2", (64,), 0.1), ("Wi", (64, 192), 0.2), ("bi", (192,), 0.1))}
@@ -126,7 +130,7 @@ def test_mlp_gi_fused(cuda, M, save, strided):
     y2 = torch.relu(o2)
     gi_want = y2 @ P["Wi"] + P["bi"]
     d = {k: v.to(cuda) for k, v in P.items()}
-    Xd = Xfull.to(cuda)[:, 8:72] if strided else X.to(cuda)
+    Xd = Xfull.to(cuda)[:, off:off + 64] if strided else X.to(cuda)
     gi = torch.full((M, 192), float("nan"), device=cuda)
     saves = None
     if save:
@@ -428,7 +432,9 @@ def _leafify(tree):
 
 
 @pytest.mark.parametrize("kind,n,n_obs", [(E.LIDAR_SPREAD, 8, 3), (E.MPE_TARGET, 3, 3), (E.LIDAR_BICYCLE_TARGET, 4, 2),
-                                           (E.MPE_SPREAD, 3, 0), (E.LIDAR_BICYCLE_TARGET, 16, 8)])   # last: config 5 size
+                                           (E.MPE_SPREAD, 3, 0), (E.LIDAR_BICYCLE_TARGET, 16, 8),   # config 5 size
+                                           (E.MPE_FORMATION, 12, 3),    # block-diagonal second layer with 2 shared-node groups x 2 agent batches
+                                           (E.LIDAR_SPREAD, 17, 3)])    # 34 shared nodes: materialised other-node rows
 def test_policy_forward_backward(cuda, kind, n, n_obs):
     from dgppo_amd import nets, ops_nn as K_
     n_env, T_ = 4, 16
@@ -554,118 +560,142 @@ def test_tree_roundtrip_and_param_counts(cuda):
             np.testing.assert_array_equal(leaves_a[k].numpy(), leaves_b[k])
 
 
-@pytest.mark.parametrize("F,Kp", [(8, 48), (32, 144), (16, 80)])
-def test_attention_kernel_families_agree(cuda, monkeypatch, F, Kp):
-    """dgppo_attn_fwd/bwd dispatch between the one-wave-per-graph kernels (default for F in {8, 32}), the workgroup-per-
-    graph MFMA kernels and the VALU kernels.  The default path is pinned to the oracle by the
-    network tests below; this pins every fallback to the default path on the same random inputs (masked slots, NaN edge
-    features behind the mask).  F = 16 has no wave instantiation: there the MFMA and VALU families are compared."""
-    from dgppo_amd import _native as N, ops_nn as K_
-    cfg = N.make_env_cfg(0, 8, 3)
-    n, S, H = 8, cfg.fan_in, 3
+def _attn_inputs(cfg, F, H, Kp, G, gen, p_masked, on=1):
+    """random operands of dgppo_attn_fwd / _bwd for G graphs of topology cfg: slots masked with probability p_masked except
+    the first `on`; masked slots carry NaN edge features."""
+    n, S = cfg.n_agents, cfg.fan_in
     n_other = cfg.num_nodes - 1 - n
-    G = 37
-    g = torch.Generator().manual_seed(F)
     R = G * n
-    qt = torch.randn(R, H * F, generator=g).to(cuda)
-    Xa = torch.randn(R, F, generator=g).to(cuda)
-    Xo = torch.randn(G * n_other, F, generator=g).to(cuda)
-    em = (torch.rand(R, S, generator=g) > 0.35).float()
-    em[:, :n] = 1.0
-    ef = torch.randn(R, S, 4, generator=g)
+    em = (torch.rand(R, S, generator=gen) > p_masked).float()
+    em[:, :on] = 1.0
+    ef = torch.randn(R, S, 4, generator=gen)
     ef[em == 0] = float("nan")                 # masked slots must never be multiplied
-    em, ef = em.to(cuda), ef.to(cuda)
-    dz = torch.randn(R, Kp, generator=g).to(cuda)
+    return dict(qt=torch.randn(R, H * F, generator=gen), Xa=torch.randn(R, F, generator=gen),
+                Xo=torch.randn(G * n_other, F, generator=gen) if n_other > 0 else None, ef=ef, em=em,
+                dz=torch.randn(R, Kp, generator=gen))
 
-    def run():
-        z = torch.full((R, Kp), float("nan"), device=cuda)
-        at = torch.full((R, S, H), float("nan"), device=cuda)
-        K_.attn_fwd(cfg, F, H, Kp, qt, Xa, Xo, ef, em, z, at, G)
-        dq = torch.full((R, H * F), float("nan"), device=cuda)
-        dXa = torch.full((R, F), float("nan"), device=cuda)
-        dXo = torch.full((G * n_other, F), float("nan"), device=cuda)
-        K_.attn_bwd(cfg, F, H, Kp, dz, at, qt, Xa, Xo, ef, dq, dXa, dXo, G)
+
+def _attn_reference(cfg, F, H, Kp, G, inp):
+    """float64 forward (oracle/nn_torch.py attn_fixed_fan_in) and its autograd backward, in the kernels' flat layouts."""
+    n, S = cfg.n_agents, cfg.fan_in
+    snd = T.attn_sender_nodes(n, cfg.n_goals, cfg.goal_slots, cfg.obs_slots, cfg.is_lidar, cfg.is_spread)
+    leaf = lambda t, *shp: t.double().reshape(*shp).requires_grad_()
+    qt, Xa = leaf(inp["qt"], G, n, H, F), leaf(inp["Xa"], G, n, F)
+    Xo = leaf(inp["Xo"], G, -1, F) if inp["Xo"] is not None else None
+    z, a = T.attn_fixed_fan_in(snd, qt, Xa, Xo, inp["ef"].double().reshape(G, n, S, 4), inp["em"].double().reshape(G, n, S), Kp)
+    (z * inp["dz"].double().reshape(G, n, Kp)).sum().backward()
+    out = dict(z=z.reshape(G * n, Kp), at=a.reshape(G * n, S, H), dq=qt.grad.reshape(G * n, H * F), dXa=Xa.grad.reshape(G * n, F))
+    if Xo is not None:
+        out["dXo"] = Xo.grad.reshape(-1, F)
+    return out
+
+
+def _attn_run(cfg, F, H, Kp, G, inp, dev):
+    """forward, backward with input gradients, the same backward with relu_xo, and the dqt-only backward (first-layer form)."""
+    n, S = cfg.n_agents, cfg.fan_in
+    R = G * n
+    d = {k: (v.to(dev) if v is not None else None) for k, v in inp.items()}
+    from dgppo_amd import ops_nn as K_
+    z = torch.full((R, Kp), float("nan"), device=dev)
+    at = torch.full((R, S, H), float("nan"), device=dev)
+    K_.attn_fwd(cfg, F, H, Kp, d["qt"], d["Xa"], d["Xo"], d["ef"], d["em"], z, at, G)
+    dq = torch.full((R, H * F), float("nan"), device=dev)
+    dXa = torch.full((R, F), float("nan"), device=dev)
+    dXo = torch.full_like(d["Xo"], float("nan")) if d["Xo"] is not None else None
+    K_.attn_bwd(cfg, F, H, Kp, d["dz"], at, d["qt"], d["Xa"], d["Xo"], d["ef"], dq, dXa, dXo, G)
+    out = dict(z=z, at=at, dq=dq, dXa=dXa, **({"dXo": dXo} if dXo is not None else {}))
+    if dXo is not None:
         # relu_xo: the same call with the ReLU backward of the other nodes' gradient fused in (dXo *= (Xo > 0))
         dq2, dXa2 = torch.empty_like(dq), torch.empty_like(dXa)
         dXo2 = torch.full_like(dXo, float("nan"))
-        K_.attn_bwd(cfg, F, H, Kp, dz, at, qt, Xa, Xo, ef, dq2, dXa2, dXo2, G, relu_xo=True)
-        # first-layer form: no input gradient requested (F = 8 takes the slot-sparse VALU kernel by default)
-        dq3 = torch.full((R, H * F), float("nan"), device=cuda)
-        K_.attn_bwd(cfg, F, H, Kp, dz, at, qt, Xa, Xo, ef, dq3, None, None, G)
+        K_.attn_bwd(cfg, F, H, Kp, d["dz"], at, d["qt"], d["Xa"], d["Xo"], d["ef"], dq2, dXa2, dXo2, G, relu_xo=True)
         torch.cuda.synchronize()
         assert torch.equal(dq2, dq) and torch.equal(dXa2, dXa)
-        assert torch.equal(dXo2, torch.where(Xo > 0, dXo, torch.zeros_like(dXo))), "relu_xo must equal masking afterwards"
-        return dict(z=z, at=at, dq=dq, dXa=dXa, dXo=dXo, dq_only=dq3)
+        assert torch.equal(dXo2, torch.where(d["Xo"] > 0, dXo, torch.zeros_like(dXo))), "relu_xo must equal masking afterwards"
+    # first-layer form: no input gradient requested (F = 8 takes the slot-sparse kernel)
+    dq3 = torch.full((R, H * F), float("nan"), device=dev)
+    K_.attn_bwd(cfg, F, H, Kp, d["dz"], at, d["qt"], d["Xa"], d["Xo"], d["ef"], dq3, None, None, G)
+    torch.cuda.synchronize()
+    out["dq_only"] = dq3
+    return out
 
-    families = {"default": {}, "block": {"DGPPO_ATTN_BLOCK": "1"}, "valu": {"DGPPO_ATTN_VALU": "1"},
-                "dense8": {"DGPPO_ATTN_DENSE8": "1"},      # F = 8: the matrix-core wave kernels instead of the slot-sparse ones
-                "wave": {"DGPPO_ATTN_NO_BD": "1"},         # F = 32: the dense one-wave-per-graph tiles instead of the block-diagonal form
-                "persist": {"DGPPO_ATTN_PERSIST_WGS": "3"}}  # F = 32 forward: persistent waves, 6 graphs each, next graph's loads in flight
-    outs = {}
-    for name, env in families.items():
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        outs[name] = run()
-        for k in env:
-            monkeypatch.delenv(k)
-    ref = outs["default"]
-    for k, v in ref.items():
-        assert torch.isfinite(v).all(), f"default path left non-finite values in {k}"
-    _close(ref["dq_only"], ref["dq"], 2e-5, "dqt-only backward vs full backward")
-    for name in ("block", "valu", "dense8", "wave", "persist"):
-        for k in ref:
-            _close(outs[name][k], ref[k], 2e-5, f"{name}.{k}")
+
+def _attn_check(got, want, name):
+    for k, v in got.items():
+        assert torch.isfinite(v).all(), f"{name}: non-finite values in {k}"
+        _close(v, want["dq" if k == "dq_only" else k], 2e-5, f"{name} {k}")
+
+
+@pytest.mark.parametrize("F,Kp", [(8, 48), (32, 144), (16, 80), (12, 64), (6, 40), (10, 56)])
+def test_attention_kernel_families_agree(cuda, F, Kp):
+    """dgppo_attn_fwd/bwd pick the kernel family from the shape alone (nn_graph.hip attn_family).  At LidarSpread n = 8:
+    F = 8 the slot-sparse kernels (the backward with input gradients: VALU), F = 32 the block-diagonal ones, F = 16 the
+    workgroup MFMA kernels, F = 12 MFMA forward + VALU backward, F = 6 / 10 the VALU kernels.  Every family is held to the
+    float64 reference on the same kind of inputs (masked slots, NaN edge features behind the mask)."""
+    from dgppo_amd import _native as N
+    cfg = N.make_env_cfg(0, 8, 3)
+    H, G = 3, 37
+    inp = _attn_inputs(cfg, F, H, Kp, G, torch.Generator().manual_seed(F), 0.35, on=cfg.n_agents)
+    _attn_check(_attn_run(cfg, F, H, Kp, G, inp, cuda), _attn_reference(cfg, F, H, Kp, G, inp), f"F={F}")
 
 
 @pytest.mark.parametrize("kind,n,n_obs", [(0, 2, 1), (0, 3, 0), (0, 5, 2), (0, 10, 3), (1, 6, 2), (3, 4, 3), (4, 6, 5), (2, 4, 2),
-                                           (0, 8, 5), (1, 10, 1)])
-def test_attention_wave_kernels_across_topologies(cuda, monkeypatch, kind, n, n_obs):
-    """the one-wave-per-graph kernels are compiled per (node tiles CT, softmax passes NP, slots per lane SJ): walk
-    different environment topologies (fan-in 2..35, 3..71 nodes) and compare forward and backward with the VALU
-    kernels, whose code does not depend on those parameters (shapes without a wave instantiation take a fallback on both
-    sides, which then simply must agree with itself)."""
+                                           (0, 8, 5), (1, 10, 1), (E.LIDAR_LINE, 10, 2), (E.MPE_FORMATION, 12, 3), (0, 17, 3),
+                                           (E.MPE_TARGET, 10, 13), (E.MPE_SPREAD, 17, 2)])
+def test_attention_wave_kernels_across_topologies(cuda, kind, n, n_obs):
+    """the one-wave-per-graph kernels are compiled per topology (slot-sparse: agent groups x slots per lane; block-diagonal:
+    shared-node groups PS x LiDAR hits x agent batches AB): walk environment topologies (fan-in 6..42, 6..170 nodes) with F = 8 and
+    F = 32 against the float64 reference.  F = 32 families: block-diagonal up to (LidarLine 10, 2) / (MPEFormation 12, 3)
+    (PS = 2, AB = 2), workgroup MFMA at (MPETarget 10, 13) (33 nodes > 32 shared) and (MPESpread 17, 2) (forward; VALU
+    backward), VALU at (LidarSpread 17, 3) (LDS image of the MFMA kernel > 64 KB)."""
+    from dgppo_amd import _native as N
+    cfg = N.make_env_cfg(kind, n, n_obs)
+    H, G = 3, 21
+    gen = torch.Generator().manual_seed(kind * 100 + n * 10 + n_obs)
+    for F, Kp in ((8, 48), (32, 144)):
+        inp = _attn_inputs(cfg, F, H, Kp, G, gen, 0.3)
+        _attn_check(_attn_run(cfg, F, H, Kp, G, inp, cuda), _attn_reference(cfg, F, H, Kp, G, inp), f"F={F}")
+
+
+@pytest.mark.parametrize("kind,n,n_obs", [(E.LIDAR_SPREAD, 8, 3), (E.MPE_SPREAD, 3, 3)])
+def test_attention_persistent_forward(cuda, kind, n, n_obs):
+    """n <= 8, F = 32: a forward launch of more than 2 * cap two-wave workgroups (cap = workgroups of the persistent kernel
+    that fit the chip at once) takes the persistent block-diagonal kernel, which walks several graphs per wave with the next
+    graph's loads in flight.  A CU holds at most 32 waves (MI355X), so cap <= 16 * CUs and G > 4 * 16 * CUs + 1 graphs
+    certainly take it (16 386 on 256 CUs); chunks of <= 512 graphs certainly do not.  Graphs are independent: both must agree
+    bit for bit, plain and with the recomputed other-node rows."""
     from dgppo_amd import _native as N, ops_nn as K_
     cfg = N.make_env_cfg(kind, n, n_obs)
-    S, H = cfg.fan_in, 3
+    F, Kp, H, S = 32, 144, 3, cfg.fan_in
     n_other = cfg.num_nodes - 1 - n
-    G = 21
-    gen = torch.Generator().manual_seed(kind * 100 + n * 10 + n_obs)
-    R = G * n
-    for F, Kp in ((8, 48), (32, 144)):
-        qt = torch.randn(R, H * F, generator=gen).to(cuda)
-        Xa = torch.randn(R, F, generator=gen).to(cuda)
-        Xo = torch.randn(max(G * n_other, 1), F, generator=gen).to(cuda)[:G * n_other]
-        em = (torch.rand(R, S, generator=gen) > 0.3).float()
-        em[:, 0] = 1.0
-        ef = torch.randn(R, S, 4, generator=gen)
-        ef[em == 0] = float("nan")
-        em, ef = em.to(cuda), ef.to(cuda)
-        dz = torch.randn(R, Kp, generator=gen).to(cuda)
+    assert K_.attn_xo_supported(cfg, F, H, Kp)
+    G = 4 * 16 * torch.cuda.get_device_properties(0).multi_processor_count + 2
+    gen = torch.Generator().manual_seed(n)
+    inp = _attn_inputs(cfg, F, H, Kp, G, gen, 0.3)
+    qt, Xa, Xo, ef, em = (inp[k].to(cuda) for k in ("qt", "Xa", "Xo", "ef", "em"))
+    raw = torch.randn(G * n_other, 8, generator=gen).to(cuda)
+    Wo, bo = (torch.randn(8, 32, generator=gen) * 0.5).to(cuda), (torch.randn(32, generator=gen) * 0.3).to(cuda)
 
-        def run():
-            z = torch.full((R, Kp), float("nan"), device=cuda)
-            at = torch.full((R, S, H), float("nan"), device=cuda)
-            K_.attn_fwd(cfg, F, H, Kp, qt, Xa, Xo if n_other > 0 else None, ef, em, z, at, G)
-            dq = torch.full((R, H * F), float("nan"), device=cuda)
-            dXa = torch.full((R, F), float("nan"), device=cuda)
-            dXo = torch.full((G * n_other, F), float("nan"), device=cuda) if n_other > 0 else None
-            K_.attn_bwd(cfg, F, H, Kp, dz, at, qt, Xa, Xo if n_other > 0 else None, ef, dq, dXa, dXo, G)
-            dq3 = torch.full((R, H * F), float("nan"), device=cuda)           # first-layer form (slot-sparse kernel for F = 8)
-            K_.attn_bwd(cfg, F, H, Kp, dz, at, qt, Xa, Xo if n_other > 0 else None, ef, dq3, None, None, G)
-            torch.cuda.synchronize()
-            return dict(z=z, at=at, dq=dq, dXa=dXa, dq_only=dq3, **({"dXo": dXo} if dXo is not None else {}))
+    def fwd(g0, g1, fused):
+        z = torch.full(((g1 - g0) * n, Kp), float("nan"), device=cuda)
+        at = torch.full(((g1 - g0) * n, S, H), float("nan"), device=cuda)
+        r, o = slice(g0 * n, g1 * n), slice(g0 * n_other, g1 * n_other)
+        if fused:
+            K_.attn_fwd_xo(cfg, F, H, Kp, qt[r], Xa[r], raw[o], Wo, bo, ef[r], em[r], z, at, g1 - g0)
+        else:
+            K_.attn_fwd(cfg, F, H, Kp, qt[r], Xa[r], Xo[o], ef[r], em[r], z, at, g1 - g0)
+        return z, at
 
-        got = run()
-        monkeypatch.setenv("DGPPO_ATTN_VALU", "1")
-        ref = run()
-        monkeypatch.delenv("DGPPO_ATTN_VALU")
-        for k in ref:
-            assert torch.isfinite(got[k]).all(), f"{k} not finite (F={F})"
-            _close(got[k], ref[k], 2e-5, f"F={F} {k}")
+    for fused in (False, True):
+        z, at = fwd(0, G, fused)
+        zc, atc = zip(*(fwd(g0, min(g0 + 512, G), fused) for g0 in range(0, G, 512)))
+        torch.cuda.synchronize()
+        assert torch.isfinite(z).all()
+        assert torch.equal(z, torch.cat(zc)) and torch.equal(at, torch.cat(atc)), f"persistent forward differs (fused={fused})"
 
 
 @pytest.mark.parametrize("kind,n,n_obs", [(0, 8, 3), (0, 3, 0), (0, 10, 3), (1, 6, 2), (3, 4, 3), (2, 16, 8)])
-def test_attention_with_recomputed_other_nodes(cuda, monkeypatch, kind, n, n_obs):
+def test_attention_with_recomputed_other_nodes(cuda, kind, n, n_obs):
     """dgppo_attn_fwd_xo / _bwd_xo recompute the sender rows of the nodes without incoming edges, relu(Xo_raw Wo + bo), inside
     the kernel (gnn.py:109-111 with aggr = 0 feeding gnn.py:85-117); they must agree with materialising those rows (torch) and
     calling dgppo_attn_fwd / _bwd, forward and backward, with and without the ReLU mask on dXo."""
@@ -709,12 +739,6 @@ def test_attention_with_recomputed_other_nodes(cuda, monkeypatch, kind, n, n_obs
         torch.cuda.synchronize()
         return dict(z=z, at=at, dq=dq, dXa=dXa, dXo=dXo)
 
-    monkeypatch.setenv("DGPPO_ATTN_PERSIST_WGS", "2")            # the persistent forward (4-5 graphs per wave) on the same inputs
-    pers = run(True, False)
-    monkeypatch.delenv("DGPPO_ATTN_PERSIST_WGS")
-    plain = run(True, False)
-    for k in plain:
-        assert torch.equal(pers[k], plain[k]), f"persistent forward differs in {k}"
     for relu_xo in (False, True):
         got, ref = run(True, relu_xo), run(False, relu_xo)
         for k in ref:
@@ -899,7 +923,7 @@ def test_policy_and_Vl_with_rnn_options(cuda, rnn_layers, lstm):
                                          (777, 16, 192, False), (3000, 7, 10, False), (1, 8, 24, False), (4097, 3, 5, True)])
 def test_dense_small_k_path(cuda, M, K, N, trans):
     """K <= 16 takes dense_smallk_kernel (W in LDS, a thread per four output columns): plain, bias + relu, accumulate into a
-    strided view, and the ReLU-mask epilogue, against torch fp32 — and against the tiled kernel (DGPPO_DENSE_NO_SMALLK)."""
+    strided view, and the ReLU-mask epilogue, against torch fp32."""
     from dgppo_amd import ops_nn as K_
     g = torch.Generator().manual_seed(M + 31 * K + N)
     X = torch.randn(M, K, generator=g)

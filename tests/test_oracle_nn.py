@@ -397,3 +397,38 @@ def test_lstm_cell_matches_torch_lstmcell():
     c1, h1 = T.lstm_cell(prnn["LSTMCell_5"], carry[:, 128:192], carry[:, 192:], h0)
     assert torch.equal(out, h1) and torch.equal(new, torch.cat([c0, h0, c1, h1], -1))
     assert T.carry_width({"params": {"RNN_0": prnn}}) == 256
+
+
+def test_attn_fixed_fan_in_matches_segment_softmax():
+    """the kernel-level attention reference equals the per-edge form (segment_softmax over the unmasked edges into each agent,
+    sums of a * [x_s | e]) on a LiDAR Target topology (own goal, own hits); NaN edge features behind the mask and an agent
+    with every slot masked (attention 0, aggregate 0) stay out of the result and its gradient."""
+    n, ng, gs, os_, F, H = 3, 3, 1, 2, 5, 2
+    snd = T.attn_sender_nodes(n, ng, gs, os_, lidar=True, spread=False)
+    assert snd.tolist() == [[0, 1, 2, 3, 6, 7], [0, 1, 2, 4, 8, 9], [0, 1, 2, 5, 10, 11]]
+    g = torch.Generator().manual_seed(0)
+    S = snd.shape[1]
+    qt = torch.randn(1, n, H, F, generator=g, dtype=torch.float64, requires_grad=True)
+    Xa = torch.randn(1, n, F, generator=g, dtype=torch.float64)
+    Xo = torch.randn(1, 9, F, generator=g, dtype=torch.float64)
+    em = (torch.rand(1, n, S, generator=g) > 0.4).double()
+    em[0, 0] = 1.0
+    em[0, 2] = 0.0
+    ef = torch.randn(1, n, S, 4, generator=g, dtype=torch.float64)
+    ef[em == 0] = float("nan")
+    Kp = F + H * (F + 4) + 3
+    z, a = T.attn_fixed_fan_in(snd, qt, Xa, Xo, ef, em, Kp)
+    X = torch.cat([Xa, Xo], 1)[0]
+    edges = [(i, s) for i in range(n) for s in range(S) if em[0, i, s] != 0]
+    recv = torch.tensor([i for i, _ in edges])
+    logits = torch.stack([(qt[0, i] * X[snd[i, s]]).sum(-1) for i, s in edges])
+    att = T.segment_softmax(logits, recv, n)
+    for i in range(n):
+        for h in range(H):
+            want = sum((att[k, h] * torch.cat([X[snd[i, s]], ef[0, i, s]]) for k, (j, s) in enumerate(edges) if j == i),
+                       torch.zeros(F + 4, dtype=torch.float64))
+            torch.testing.assert_close(z[0, i, F + h * (F + 4):F + (h + 1) * (F + 4)], want)
+    assert torch.equal(z[0, :, :F], Xa[0]) and (z[0, :, -3] == 1).all() and (z[0, :, -2:] == 0).all()
+    assert (a[0, 2] == 0).all() and torch.allclose(a[0, :2].sum(1), torch.ones(2, H, dtype=torch.float64))
+    z.sum().backward()
+    assert torch.isfinite(qt.grad).all() and (qt.grad[0, 2] == 0).all()
