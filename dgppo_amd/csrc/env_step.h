@@ -44,6 +44,55 @@ __device__ inline float clampf(float x, float lo, float hi) { return fminf(fmaxf
 // pre-step graph is NaN (ray parallel to an edge); states never are.
 __device__ inline float clampf_nan(float x, float lo, float hi) { return (x != x) ? x : fminf(fmaxf(x, lo), hi); }
 
+// The reference formulas every step kernel shares.  Each keeps the oracle's fp32 operation order.
+
+// agent_step_euler: lidar_bicycle_target.py:95-107, lidar_env/base.py:146-149.  u0, u1: the clipped action; y_limit bounds
+// the double integrator's y (area_size except MPECorridor / MPEConnectSpread: 2 A)
+template <int SD>
+__device__ inline void step_state(const float* x, float u0, float u1, const dgppo_env_cfg& c, float y_limit, float* nx) {
+  const float dt = c.dt, A = c.area_size;
+  if constexpr (SD == 5) {
+    const float theta = atan2f(x[3], x[2]);
+    const float theta_next = theta + x[4] * u0 * dt * 10.0f;
+    nx[0] = clampf(x[0] + x[4] * cosf(theta) * dt, 0.0f, A);
+    nx[1] = clampf(x[1] + x[4] * sinf(theta) * dt, 0.0f, A);
+    nx[2] = clampf(cosf(theta_next), -1.0f, 1.0f);
+    nx[3] = clampf(sinf(theta_next), -1.0f, 1.0f);
+    nx[SD - 1] = clampf(x[SD - 1] + u1 * dt * 10.0f, -0.5f, 0.5f);
+  } else {
+    const float vl = c.vel_limit;
+    nx[0] = clampf(x[2] * dt + x[0], 0.0f, A);
+    nx[1] = clampf(x[3] * dt + x[1], 0.0f, y_limit);
+    nx[2] = clampf((u0 * 10.0f) * dt + x[2], -vl, vl);
+    nx[3] = clampf((u1 * 10.0f) * dt + x[3], -vl, vl);
+  }
+}
+
+// get_cost (lidar_env/base.py:180-207, mpe/base.py:164-191): a margin m becomes m -/+ 0.5 before the clip, which each
+// caller applies (MPE clips only from below)
+__device__ inline float cost_value(float m) { return (m <= 0.0f) ? m - 0.5f : m + 0.5f; }
+
+// get_reward (lidar_spread.py:35-52 and its siblings) from the three sums in index order: distances to the ng reward
+// goals, goals not reached, squared action norms of the n agents
+__device__ inline float reward_from_sums(float s1, float s2, float s3, int ng, int n) {
+  float r = 0.0f;
+  r = r - (s1 / (float)ng) * 0.01f;
+  r = r - (s2 / (float)ng) * 0.001f;
+  r = r - (s3 / (float)n) * 0.0001f;
+  return r;
+}
+
+// one segment test of obstacle.py:97-105 taken literally: det = sign(det0) * clip(|det0|, 1e-7, 1e7), then
+// v * (na / det) + (1 - v) * 1e6 with v = (both quotients in [0, 1]).  The kernels' fast paths decide validity without the
+// divisions and fall back to this for det0 == 0 (x / 0 -> 0 * inf = NaN) and NaN
+__device__ inline float segment_alpha_literal(float det0, float na, float nb) {
+  const float sgn = (det0 > 0.0f) ? 1.0f : ((det0 < 0.0f) ? -1.0f : det0);
+  const float det = sgn * fminf(fmaxf(fabsf(det0), 1e-7f), 1e7f);
+  const float aq = na / det, bq = nb / det;
+  const float v = ((aq <= 1.0f) && (aq >= 0.0f) && (bq <= 1.0f) && (bq >= 0.0f)) ? 1.0f : 0.0f;
+  return v * aq + (1.0f - v) * 1e6f;
+}
+
 // Rectangle.inside with radius r (obstacle.py:62-72); rec = 16-float record
 __device__ inline bool rect_inside(const float* rec, float px, float py, float r) {
   float rel_x = px - rec[0];
@@ -61,6 +110,7 @@ __device__ inline bool rect_inside(const float* rec, float px, float py, float r
 
 #define MISS_BITS 0x49742400u  // bits of 1e6f
 
-// wave-per-env LiDAR kernel (env_wave.hip): returns true when it has an instantiation for this configuration and has
-// enqueued the launch; false -> the caller falls back to the workgroup-per-env kernels
-bool launch_lidar_wave(const StepArgs& a, hipStream_t s);
+// wave-per-env LiDAR kernel (env_wave.hip): whether its instantiation list holds this (state_dim, spread, n_agents,
+// n_obs), and the launch of that instance (step_family in env_step.hip decides when it runs)
+bool lidar_wave_has_instance(const dgppo_env_cfg& c);
+void launch_lidar_wave(const StepArgs& a, hipStream_t s);

@@ -13,7 +13,6 @@
 // Built with -ffp-contract=off: every fp32 operation is a single IEEE operation in the same order as
 // oracle/env_np.py, so states, rewards, costs, features and therefore all masks/indices are bit-identical.
 #include "env_step.h"
-#include <stdlib.h>
 
 template <int SD>
 __global__ void env_step_kernel(StepArgs a) {
@@ -68,22 +67,7 @@ __global__ void env_step_kernel(StepArgs a) {
     float* nx = s_next + i * SD;
     if (do_dyn) {
       const float u0 = s_act[i * 2], u1 = s_act[i * 2 + 1];
-      const float dt = c.dt, A = c.area_size;
-      if constexpr (SD == 5) {  // lidar_bicycle_target.py:95-107
-        float theta = atan2f(x[3], x[2]);
-        float theta_next = theta + x[4] * u0 * dt * 10.0f;
-        nx[0] = clampf(x[0] + x[4] * cosf(theta) * dt, 0.0f, A);
-        nx[1] = clampf(x[1] + x[4] * sinf(theta) * dt, 0.0f, A);
-        nx[2] = clampf(cosf(theta_next), -1.0f, 1.0f);
-        nx[3] = clampf(sinf(theta_next), -1.0f, 1.0f);
-        nx[SD - 1] = clampf(x[SD - 1] + u1 * dt * 10.0f, -0.5f, 0.5f);
-      } else {        // lidar_env/base.py:146-149
-        const float vl = c.vel_limit;
-        nx[0] = clampf(x[2] * dt + x[0], 0.0f, A);
-        nx[1] = clampf(x[3] * dt + x[1], 0.0f, c.y_limit);       // = A except MPECorridor / MPEConnectSpread (2 A)
-        nx[2] = clampf((u0 * 10.0f) * dt + x[2], -vl, vl);
-        nx[3] = clampf((u1 * 10.0f) * dt + x[3], -vl, vl);
-      }
+      step_state<SD>(x, u0, u1, c, c.y_limit, nx);
       // action penalty term: (||a||)^2
       float an = sqrtf(u0 * u0 + u1 * u1);
       s_an2[i] = an * an;
@@ -162,8 +146,7 @@ __global__ void env_step_kernel(StepArgs a) {
           for (int m = 1; m < oc; ++m) mo = nanmin(mo, s_pair[n_aa + i * oc + m]);
           obs_cost = (lidar ? c.car_radius : c.car_plus_obs) - mo;
         }
-        float c0 = (agent_cost <= 0.0f) ? agent_cost - 0.5f : agent_cost + 0.5f;
-        float c1 = (obs_cost <= 0.0f) ? obs_cost - 0.5f : obs_cost + 0.5f;
+        float c0 = cost_value(agent_cost), c1 = cost_value(obs_cost);
         if (lidar || c.kind == DGPPO_ENV_MPE_CONNECT_SPREAD) { c0 = clampf_nan(c0, -1.0f, 1.0f); c1 = clampf_nan(c1, -1.0f, 1.0f); }
         else { c0 = fmaxf(c0, -1.0f); c1 = fmaxf(c1, -1.0f); }   // mpe/base.py:189 clips only from below
         a.cost[((size_t)b * n + i) * c.n_cost] = c0;
@@ -195,8 +178,7 @@ __global__ void env_step_kernel(StepArgs a) {
       const float v = s_md[j] - c.connect_radius;
       w = (w != w || v != v) ? __builtin_nanf("") : fmaxf(w, v);
     }
-    float c2 = (w <= 0.0f) ? w - 0.5f : w + 0.5f;
-    a.cost[((size_t)b * n + tid) * 3 + 2] = clampf_nan(c2, -1.0f, 1.0f);
+    a.cost[((size_t)b * n + tid) * 3 + 2] = clampf_nan(cost_value(w), -1.0f, 1.0f);
   }
   if (do_dyn && tid == 0) {
     float s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
@@ -206,11 +188,7 @@ __global__ void env_step_kernel(StepArgs a) {
       s2 = (g == 0) ? ind : s2 + ind;
     }
     for (int i = 0; i < n; ++i) s3 = (i == 0) ? s_an2[0] : s3 + s_an2[i];
-    float r = 0.0f;
-    r = r - (s1 / (float)nrg) * 0.01f;
-    r = r - (s2 / (float)nrg) * 0.001f;
-    r = r - (s3 / (float)n) * 0.0001f;
-    a.reward[b] = r;
+    a.reward[b] = reward_from_sums(s1, s2, s3, nrg, n);
   }
 
   // ---- phase 2: ray fan x rectangles x 4 segments (thread per (agent, ray)) ------------------
@@ -258,11 +236,7 @@ __global__ void env_step_kernel(StepArgs a) {
             al = 1e6f;
             if (va && vb) al = na / det + 0.0f;   // v*alpha + (1-v)*1e6 with v = 1: alpha + 0 (turns -0 into +0)
           } else {  // literal path: det = sign(det0) * clip(|det0|) = 0 (or NaN)
-            const float sgn = (det0 > 0.0f) ? 1.0f : ((det0 < 0.0f) ? -1.0f : det0);
-            const float det = sgn * fminf(fmaxf(fabsf(det0), 1e-7f), 1e7f);
-            const float aq = na / det, bq = nb / det;
-            const float v = ((aq <= 1.0f) && (aq >= 0.0f) && (bq <= 1.0f) && (bq >= 0.0f)) ? 1.0f : 0.0f;
-            al = v * aq + (1.0f - v) * 1e6f;
+            al = segment_alpha_literal(det0, na, nb);
           }
           ao = (m == 0) ? al : nanmin(ao, al);
         }
@@ -409,16 +383,6 @@ __global__ void env_step_kernel(StepArgs a) {
 //   * stable top-k from the agent's 32 keys held in registers (one LDS round trip instead of 32 dependent ones);
 //   * node / state rows are composed in LDS and streamed out with unit-stride stores; edges as float4.
 // =====================================================================================================================
-#ifdef DGPPO_STAMPS
-__device__ unsigned long long g_stamps[32];
-#define STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
-extern "C" int32_t dgppo_debug_stamps(unsigned long long* out) {
-  return (int32_t)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 32);
-}
-#else
-#define STAMP(i)
-#endif
-
 // x / d for 0 <= x < 2^16 and 1 <= d < 2^16 with rcp = ceil(2^32 / d): one v_mul_hi_u32 instead of the ~35-instruction
 // integer division sequence (exact: the error term x * (rcp*d - 2^32) stays below 2^32).
 __device__ inline int fdiv(int x, uint32_t rcp) { return (int)__umulhi((uint32_t)x, rcp); }
@@ -428,7 +392,7 @@ static inline uint32_t fdiv_rcp(int d) { return d <= 1 ? 0u : (uint32_t)((0x1000
 #define LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 template <int SD, bool SPREAD, int NT>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar_step_kernel(StepArgs a) {
-  // requires n_rays == 32 (one half-wave per agent) — the host falls back to env_step_kernel otherwise
+  // requires n_rays == 32 (one half-wave per agent): step_family picks it only then
   extern __shared__ float smem[];
   const dgppo_env_cfg& c = a.cfg;
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -467,14 +431,12 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
   const float sr = c.comm_radius;
   // this lane's ray, for the whole kernel (no tables in materialise-only mode)
   const float cr = do_sense ? a.ray_cos[tid & 31] : 0.0f, sn = do_sense ? a.ray_sin[tid & 31] : 0.0f;
-  STAMP(0);
   // ---- P0: stage inputs ----
   for (int i = tid; i < n * SD; i += nt) { s_agent[i] = a.agent[(size_t)b * n * SD + i]; s_goal[i] = a.goal[(size_t)b * n * SD + i]; }
   if (do_dyn) for (int i = tid; i < n * 2; i += nt) s_act[i] = clampf(a.action[(size_t)b * n * 2 + i], -1.0f, 1.0f);
   for (int i = tid; i < no * 16; i += nt) s_obst[i] = a.obst[(size_t)b * no * 16 + i];
   if (a.hits != nullptr) for (int i = tid; i < n * k * 2; i += nt) s_hpre[i] = a.hits[(size_t)b * n * k * 2 + i];
   LDS_BARRIER();   // threads exchange data through LDS only; __syncthreads() would also wait for the global stores
-  STAMP(1);
   // ---- P1a: per-segment constants, bounding circles, dynamics, features (disjoint lanes) ----
   if (do_sense) {
     for (int q = tid; q < no * 4; q += nt) {
@@ -489,22 +451,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
     float* nx = s_next + i * SD;
     if (do_dyn) {
       const float u0 = s_act[i * 2], u1 = s_act[i * 2 + 1];
-      const float dt = c.dt, A = c.area_size;
-      if constexpr (SD == 5) {
-        float theta = atan2f(x[3], x[2]);
-        float theta_next = theta + x[4] * u0 * dt * 10.0f;
-        nx[0] = clampf(x[0] + x[4] * cosf(theta) * dt, 0.0f, A);
-        nx[1] = clampf(x[1] + x[4] * sinf(theta) * dt, 0.0f, A);
-        nx[2] = clampf(cosf(theta_next), -1.0f, 1.0f);
-        nx[3] = clampf(sinf(theta_next), -1.0f, 1.0f);
-        nx[SD - 1] = clampf(x[SD - 1] + u1 * dt * 10.0f, -0.5f, 0.5f);
-      } else {
-        const float vl = c.vel_limit;
-        nx[0] = clampf(x[2] * dt + x[0], 0.0f, A);
-        nx[1] = clampf(x[3] * dt + x[1], 0.0f, A);
-        nx[2] = clampf((u0 * 10.0f) * dt + x[2], -vl, vl);
-        nx[3] = clampf((u1 * 10.0f) * dt + x[3], -vl, vl);
-      }
+      step_state<SD>(x, u0, u1, c, c.area_size, nx);
       const float an = sqrtf(u0 * u0 + u1 * u1);
       s_an2[i] = an * an;
     } else {
@@ -514,7 +461,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
   }
   if (tid >= GO && tid < GO + n) state2feat<SD>(s_goal + (tid - GO) * SD, s_fg + (tid - GO) * 4);
   LDS_BARRIER();   // threads exchange data through LDS only; __syncthreads() would also wait for the global stores
-  STAMP(2);
   // ---- P1b: distances (one sqrt per thread) and start-inside flags ----
   {
     const int n_aa = do_dyn ? n * n : 0, n_ao = do_dyn ? n * k : 0, n_ga = do_dyn ? (SPREAD ? n * n : n) : 0;
@@ -545,7 +491,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
     }
   }
   LDS_BARRIER();   // threads exchange data through LDS only; __syncthreads() would also wait for the global stores
-  STAMP(3);
   // ---- P1c: per-agent reductions (min is order independent), cost, reward terms ----
   if (do_dyn) {
     if (tid < n) {
@@ -557,8 +502,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
 #pragma unroll 8
       for (int m = 1; m < k; ++m) mo = nanmin(mo, s_pair[n * n + i * k + m]);
       const float agent_cost = c.two_car_radius - md, obs_cost = c.car_radius - mo;
-      const float c0 = (agent_cost <= 0.0f) ? agent_cost - 0.5f : agent_cost + 0.5f;
-      const float c1 = (obs_cost <= 0.0f) ? obs_cost - 0.5f : obs_cost + 0.5f;
+      const float c0 = cost_value(agent_cost), c1 = cost_value(obs_cost);
       reinterpret_cast<float2*>(a.cost)[(size_t)b * n + i] = make_float2(clampf_nan(c0, -1.0f, 1.0f), clampf_nan(c1, -1.0f, 1.0f));
     }
     if (tid >= GO && tid < GO + n) {
@@ -571,7 +515,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
       s_d2g[g] = d2g;
     }
   }
-  STAMP(4);
   // ---- P2: all n_obs*4 segment tests of (agent, this lane's ray) (reference arithmetic, obstacle.py:97-105).  Per
   //      obstacle the 4 segments are unrolled: one batch of LDS reads, validity without divisions (see the generic
   //      kernel), one division per segment only when some lane of the wave hits it.  det == 0 / NaN (ray parallel to an
@@ -629,11 +572,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
             const float4 asq = s_as[i * no * 4 + q];
             const float det0 = dx12 * sgq.w - dy12 * sgq.z;
             const float nb = ndy12 * asq.x + dx12 * asq.y;
-            const float sgn = (det0 > 0.0f) ? 1.0f : ((det0 < 0.0f) ? -1.0f : det0);
-            const float dz = sgn * fminf(fmaxf(fabsf(det0), 1e-7f), 1e7f);
-            const float aq = asq.z / dz, bq = nb / dz;
-            const float v = ((aq <= 1.0f) && (aq >= 0.0f) && (bq <= 1.0f) && (bq >= 0.0f)) ? 1.0f : 0.0f;
-            const float al = v * aq + (1.0f - v) * 1e6f;
+            const float al = segment_alpha_literal(det0, asq.z, nb);
             any_nan = any_nan || (al != al);
             lmin = fminf(lmin, al);
           }
@@ -646,7 +585,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
     }
   }
   LDS_BARRIER();   // threads exchange data through LDS only; __syncthreads() would also wait for the global stores
-  STAMP(5);
   if (do_dyn && tid == 0) {
     float s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
 #pragma unroll 8
@@ -654,13 +592,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
 #pragma unroll 8
     for (int g = 0; g < ng; ++g) { const float ind = (s_d2g[g] > c.dist2goal) ? 1.0f : 0.0f; s2 = (g == 0) ? ind : s2 + ind; }
     for (int i = 0; i < n; ++i) s3 = (i == 0) ? s_an2[0] : s3 + s_an2[i];
-    float r = 0.0f;
-    r = r - (s1 / (float)ng) * 0.01f;
-    r = r - (s2 / (float)ng) * 0.001f;
-    r = r - (s3 / (float)n) * 0.0001f;
-    a.reward[b] = r;
+    a.reward[b] = reward_from_sums(s1, s2, s3, ng, n);
   }
-  STAMP(6);
   // ---- P3: stable ascending top-k (env/utils.py:132-136): the agent's 32 keys in registers, one LDS round trip ----
   if (do_sense) {
     for (int base = 0; base < NR; base += nt) {
@@ -691,11 +624,9 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
     for (int i = tid; i < n * k * 2; i += nt) s_hnext[i] = s_hpre[i];
   }
   LDS_BARRIER();   // threads exchange data through LDS only; __syncthreads() would also wait for the global stores
-  STAMP(7);
   // ---- P4: compact outputs ----
   if (a.next_agent != nullptr) for (int i = tid; i < n * SD; i += nt) a.next_agent[(size_t)b * n * SD + i] = s_next[i];
   if (a.next_hits != nullptr) for (int i = tid; i < n * k * 2; i += nt) a.next_hits[(size_t)b * n * k * 2 + i] = s_hnext[i];
-  STAMP(8);
   if (!a.has_graph) return;
   // ---- P5: padded GraphsTuple: node / state rows composed in LDS, streamed out with unit stride ----
   const int n_on = n * k, N = 2 * n + n_on + 1, pad = N - 1;
@@ -776,7 +707,6 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
     float* states = a.g.states + (size_t)b * N * SD;
     for (int idx = tid; idx < N * SD; idx += nt) states[idx] = s_outs[idx];
   }
-  STAMP(9);
 }
 #undef DIVN
 #undef DIVK
@@ -809,6 +739,27 @@ static float sqrt_threshold(float c) {
   while (s > 0.0f && sqrtf(s) >= c) s = nextafterf(s, 0.0f);
   while (!(sqrtf(s) >= c)) s = nextafterf(s, INFINITY);
   return s;
+}
+
+enum StepFamily { FAMILY_WAVE, FAMILY_LIDAR_WG, FAMILY_GENERIC };
+
+// The kernel family of a step, materialise or sense-only launch; all three give the same outputs, bit for bit.  The first
+// that applies runs:
+//   WAVE      lidar_wave_kernel (env_wave.hip): base LiDAR kind, 32 rays, top-k 8, n_obs >= 1, eye_offset >= comm_radius
+//             (the diagonal of the agent-agent block is masked), 16-byte aligned operands (inputs are staged as float4;
+//             torch allocations are aligned, sliced views may not be) and (state_dim, spread, n_agents, n_obs) in its
+//             instantiation list;
+//   LIDAR_WG  lidar_step_kernel: base LiDAR kind, n_obs > 0, 32 rays, its LDS stage <= 60 KB;
+//   GENERIC   env_step_kernel: everything else.
+static StepFamily step_family(const StepArgs& a) {
+  const dgppo_env_cfg& c = a.cfg;
+  const bool lidar32 = cfg_is_lidar(c) && cfg_is_base_kind(c) && c.n_obs > 0 && c.n_rays == 32;
+  auto al16 = [](const void* p) { return p == nullptr || (((uintptr_t)p) & 15) == 0; };
+  const bool aligned = al16(a.agent) && al16(a.goal) && al16(a.obst) && al16(a.hits) && al16(a.next_agent) &&
+                       al16(a.next_hits) && al16(a.action) && (!a.has_graph || (al16(a.g.edges) && al16(a.g.states)));
+  if (lidar32 && c.top_k == 8 && c.eye_offset >= c.comm_radius && aligned && lidar_wave_has_instance(c)) return FAMILY_WAVE;
+  if (lidar32 && lidar_smem_bytes(c) <= 60 * 1024) return FAMILY_LIDAR_WG;
+  return FAMILY_GENERIC;
 }
 
 static int32_t launch_step(const dgppo_env_cfg* cfg, int mode, const float* agent, const float* action, const float* goal,
@@ -857,39 +808,30 @@ static int32_t launch_step(const dgppo_env_cfg* cfg, int mode, const float* agen
   a.thr2_lidar = sqrt_threshold(cfg->lidar_mask_radius);
   const size_t smem = step_smem_bytes(*cfg);
   DGPPO_REQUIRE(smem <= 64 * 1024, "env too large for the per-env LDS stage (%zu bytes)", smem);
-  int work = cfg->n_agents * (lidar ? cfg->n_rays : 1);
-  int E = cfg_num_edges(*cfg);
-  if (gout && E > work) work = E;
-  int threads = ((work + 63) / 64) * 64;
-  if (threads < 64) threads = 64;
-  if (threads > 512) threads = 512;
   hipStream_t s = (hipStream_t)stream;
-  const size_t fsmem = lidar ? lidar_smem_bytes(*cfg) : 0;
-  if (launch_lidar_wave(a, s)) {
-    // wave-per-env kernel for the benchmark topologies (env_wave.hip; same outputs bit for bit)
-  } else if (lidar && cfg_is_base_kind(*cfg) && cfg->n_obs > 0 && cfg->n_rays == 32 && fsmem <= 60 * 1024 &&
-             !getenv("DGPPO_GENERIC_ENV_KERNEL")) {
-    // specialised LiDAR kernel (same outputs bit for bit; see its header)
-    const bool spread = cfg_is_spread(*cfg);
-    const char* nt_env = getenv("DGPPO_ENV_BLOCK");
-    const int ntb = nt_env ? atoi(nt_env) : 128;
-    if (ntb == 128) {
+  switch (step_family(a)) {
+    case FAMILY_WAVE:
+      launch_lidar_wave(a, s);
+      break;
+    case FAMILY_LIDAR_WG: {
+      const size_t fsmem = lidar_smem_bytes(*cfg);
       if (cfg->state_dim == 5) hipLaunchKernelGGL((lidar_step_kernel<5, false, 128>), dim3(B), dim3(128), fsmem, s, a);
-      else if (spread) hipLaunchKernelGGL((lidar_step_kernel<4, true, 128>), dim3(B), dim3(128), fsmem, s, a);
+      else if (cfg_is_spread(*cfg)) hipLaunchKernelGGL((lidar_step_kernel<4, true, 128>), dim3(B), dim3(128), fsmem, s, a);
       else hipLaunchKernelGGL((lidar_step_kernel<4, false, 128>), dim3(B), dim3(128), fsmem, s, a);
-    } else if (ntb == 64) {
-      if (cfg->state_dim == 5) hipLaunchKernelGGL((lidar_step_kernel<5, false, 64>), dim3(B), dim3(64), fsmem, s, a);
-      else if (spread) hipLaunchKernelGGL((lidar_step_kernel<4, true, 64>), dim3(B), dim3(64), fsmem, s, a);
-      else hipLaunchKernelGGL((lidar_step_kernel<4, false, 64>), dim3(B), dim3(64), fsmem, s, a);
-    } else {
-      if (cfg->state_dim == 5) hipLaunchKernelGGL((lidar_step_kernel<5, false, 256>), dim3(B), dim3(256), fsmem, s, a);
-      else if (spread) hipLaunchKernelGGL((lidar_step_kernel<4, true, 256>), dim3(B), dim3(256), fsmem, s, a);
-      else hipLaunchKernelGGL((lidar_step_kernel<4, false, 256>), dim3(B), dim3(256), fsmem, s, a);
+      break;
     }
-  } else if (cfg->state_dim == 5)
-    hipLaunchKernelGGL(env_step_kernel<5>, dim3(B), dim3(threads), smem, s, a);
-  else
-    hipLaunchKernelGGL(env_step_kernel<4>, dim3(B), dim3(threads), smem, s, a);
+    case FAMILY_GENERIC: {
+      int work = cfg->n_agents * (lidar ? cfg->n_rays : 1);
+      const int E = cfg_num_edges(*cfg);
+      if (gout && E > work) work = E;
+      int threads = ((work + 63) / 64) * 64;
+      if (threads < 64) threads = 64;
+      if (threads > 512) threads = 512;
+      if (cfg->state_dim == 5) hipLaunchKernelGGL(env_step_kernel<5>, dim3(B), dim3(threads), smem, s, a);
+      else hipLaunchKernelGGL(env_step_kernel<4>, dim3(B), dim3(threads), smem, s, a);
+      break;
+    }
+  }
   DGPPO_LAUNCH_CHECK();
   return 0;
 }

@@ -41,7 +41,6 @@
 // ray origin — d . (c_o - p) < -(h_o + 0.05) — no segment of o is valid for this ray (both tests are evaluated in fp32
 // with errors < 1e-6 against a slack of 0.048; a NaN fails both comparisons and keeps the triple).
 #include "env_step.h"
-#include <stdlib.h>
 
 // minimum waves per SIMD the register allocator must leave room for (VGPR budget 512 / n, granule 8)
 #ifndef DGPPO_WAVE_WPE
@@ -277,22 +276,7 @@ __global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(G
       float nx[SD];
       if (do_dyn) {
         const float u0 = clampf(L.act[i * 2], -1.0f, 1.0f), u1 = clampf(L.act[i * 2 + 1], -1.0f, 1.0f);   // env/base.py:84-86
-        const float dt = c.dt, A = c.area_size;
-        if constexpr (SD == 5) {  // lidar_bicycle_target.py:95-107
-          const float theta = atan2f(x[3], x[2]);
-          const float theta_next = theta + x[4] * u0 * dt * 10.0f;
-          nx[0] = clampf(x[0] + x[4] * cosf(theta) * dt, 0.0f, A);
-          nx[1] = clampf(x[1] + x[4] * sinf(theta) * dt, 0.0f, A);
-          nx[2] = clampf(cosf(theta_next), -1.0f, 1.0f);
-          nx[3] = clampf(sinf(theta_next), -1.0f, 1.0f);
-          nx[SD - 1] = clampf(x[SD - 1] + u1 * dt * 10.0f, -0.5f, 0.5f);
-        } else {                  // lidar_env/base.py:146-149
-          const float vl = c.vel_limit;
-          nx[0] = clampf(x[2] * dt + x[0], 0.0f, A);
-          nx[1] = clampf(x[3] * dt + x[1], 0.0f, A);
-          nx[2] = clampf((u0 * 10.0f) * dt + x[2], -vl, vl);
-          nx[3] = clampf((u1 * 10.0f) * dt + x[3], -vl, vl);
-        }
+        step_state<SD>(x, u0, u1, c, c.area_size, nx);
         asq = u0 * u0 + u1 * u1;                  // (||a||)^2 = fl(sqrt(.))^2: the root is taken below with the distances
       } else {
 #pragma unroll
@@ -418,13 +402,9 @@ __global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(G
         const int kind = lane / NA, i = lane - kind * NA;
         if (kind == 0) {        // agent_cost = 2r - min(min_{j != i} dist, sqrt(0) + 1e6)   [jnp.min: NaN propagates]
           const float md = nanmin(rt, 1e6f);
-          const float agent_cost = c.two_car_radius - md;
-          const float c0 = (agent_cost <= 0.0f) ? agent_cost - 0.5f : agent_cost + 0.5f;
-          L.cost[i * 2] = clampf_nan(c0, -1.0f, 1.0f);
+          L.cost[i * 2] = clampf_nan(cost_value(c.two_car_radius - md), -1.0f, 1.0f);
         } else if (kind == 1) {
-          const float obs_cost = c.car_radius - rt;
-          const float c1 = (obs_cost <= 0.0f) ? obs_cost - 0.5f : obs_cost + 0.5f;
-          L.cost[i * 2 + 1] = clampf_nan(c1, -1.0f, 1.0f);
+          L.cost[i * 2 + 1] = clampf_nan(cost_value(c.car_radius - rt), -1.0f, 1.0f);
         } else if (kind == 2) {
           L.red[i] = rt;
           L.red[NA + i] = (rt > c.dist2goal) ? 1.0f : 0.0f;
@@ -446,13 +426,7 @@ __global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(G
       const float s1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 0));
       const float s2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 1));
       const float s3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 2));
-      if (lane == 0) {
-        float rw = 0.0f;
-        rw = rw - (s1 / (float)NA) * 0.01f;
-        rw = rw - (s2 / (float)NA) * 0.001f;
-        rw = rw - (s3 / (float)NA) * 0.0001f;
-        a.reward[b] = rw;
-      }
+      if (lane == 0) a.reward[b] = reward_from_sums(s1, s2, s3, NA, NA);
       if (lane < NA * 2) a.cost[(size_t)b * NA * 2 + lane] = L.cost[lane];
     }
     // ---- early outputs: everything that does not depend on the ray-cast leaves now, so that these stores drain while
@@ -635,11 +609,7 @@ __global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(G
               const float na = sgq.w * ax - sgq.z * ay;
               const float det0 = dx12 * sgq.w - dy12 * sgq.z;
               const float nb = ndy12 * ax + dx12 * ay;
-              const float sgn = (det0 > 0.0f) ? 1.0f : ((det0 < 0.0f) ? -1.0f : det0);
-              const float dz = sgn * fminf(fmaxf(fabsf(det0), 1e-7f), 1e7f);
-              const float aq = na / dz, bq = nb / dz;
-              const float v = ((aq <= 1.0f) && (aq >= 0.0f) && (bq <= 1.0f) && (bq >= 0.0f)) ? 1.0f : 0.0f;
-              const float al = v * aq + (1.0f - v) * 1e6f;
+              const float al = segment_alpha_literal(det0, na, nb);
               any_nan = any_nan || (al != al);
               lmin = fminf(lmin, al);
             }
@@ -935,7 +905,7 @@ DGPPO_PRAGMA(unroll DGPPO_WAVE_UNROLL_P3)
 }
 
 template <int SD, bool SPREAD, int NA, int NO>
-bool launch_inst(const StepArgs& a, hipStream_t s) {
+void launch_inst(const StepArgs& a, hipStream_t s) {
   constexpr size_t per_wave = sizeof(WaveLds<SD, SPREAD, NA, NO, true>);        // the larger of the two layouts
   // waves per workgroup: as many independent waves as keep several workgroups resident in the 160 KiB of a CU
   constexpr int WPB = (per_wave * 4 <= 40 * 1024) ? 4 : ((per_wave * 2 <= 52 * 1024) ? 2 : 1);
@@ -970,20 +940,33 @@ bool launch_inst(const StepArgs& a, hipStream_t s) {
   const int max_blocks = n_cu * per_cu;
   int blocks = (a.B + WPB - 1) / WPB;
   if (blocks > max_blocks) blocks = max_blocks;
-  const char* wpe = getenv("DGPPO_WAVE_ENVS");    // tuning knob: minimum envs per wave (fewer, longer-lived waves)
-  if (wpe && atoi(wpe) > 1) {
-    const int want = (a.B + WPB * atoi(wpe) - 1) / (WPB * atoi(wpe));
-    if (want >= 1 && want < blocks) blocks = want;
-  }
-  const char* gpe = getenv("DGPPO_WAVE_GRID_ENVS");   // tuning knob: exactly this many envs per wave, grid NOT capped at the resident set
-  if (gpe && atoi(gpe) >= 1) blocks = (a.B + WPB * atoi(gpe) - 1) / (WPB * atoi(gpe));
   const dim3 g(blocks), t(WPB * 64);
 #define LAUNCH(M_, G_) hipLaunchKernelGGL((lidar_wave_kernel<SD, SPREAD, NA, NO, WPB, M_, G_>), g, t, (G_) ? smem_g : smem_c, s, a)
   if (a.mode == MODE_STEP) { if (a.has_graph) LAUNCH(MODE_STEP, true); else LAUNCH(MODE_STEP, false); }
   else if (a.mode == MODE_SENSE) { if (a.has_graph) LAUNCH(MODE_SENSE, true); else LAUNCH(MODE_SENSE, false); }
   else LAUNCH(MODE_GRAPH, true);
 #undef LAUNCH
-  return true;
+}
+
+template <int SD_, bool SPREAD_, int NA_, int NO_>
+struct Inst { static constexpr int SD = SD_, NA = NA_, NO = NO_; static constexpr bool SPREAD = SPREAD_; };
+
+// The instantiation list, (state_dim, spread, n_agents, n_obs): calls f(Inst<...>{}) for the configuration's entry and
+// returns whether there is one
+template <class F>
+bool with_instance(const dgppo_env_cfg& c, F&& f) {
+  const bool spread = cfg_is_spread(c);
+  const int n = c.n_agents, no = c.n_obs, sd = c.state_dim;
+#define INST(SD_, SP_, NA_, NO_) if (sd == SD_ && spread == SP_ && n == NA_ && no == NO_) { f(Inst<SD_, SP_, NA_, NO_>{}); return true; }
+  INST(4, true, 8, 3);      // BASELINE configs 3 / 4: LidarSpread n = 8, obs = 3
+  INST(4, false, 8, 3);     // LidarTarget n = 8, obs = 3
+  INST(5, false, 16, 8);    // BASELINE config 5: LidarBicycleTarget n = 16, obs = 8
+  INST(4, true, 16, 8);
+  INST(4, true, 4, 2);
+  INST(4, false, 4, 2);
+  INST(5, false, 4, 3);
+#undef INST
+  return false;
 }
 
 }  // namespace
@@ -997,27 +980,11 @@ extern "C" int32_t dgppo_debug_wave_spans(unsigned long long* out) {
 }
 #endif
 
-bool launch_lidar_wave(const StepArgs& a, hipStream_t s) {
-  const dgppo_env_cfg& c = a.cfg;
-  if (!cfg_is_lidar(c) || !cfg_is_base_kind(c) || c.n_rays != 32 || c.top_k != 8 || c.n_obs < 1) return false;
-  if (getenv("DGPPO_NO_WAVE_ENV_KERNEL")) return false;
-  if (!(c.eye_offset >= c.comm_radius)) return false;          // the diagonal of the agent-agent block must be masked
-  // 16-byte staging loads need 16-byte aligned bases (torch allocations are; sliced views may not be)
-  auto al16 = [](const void* p) { return p == nullptr || (((uintptr_t)p) & 15) == 0; };
-  if (!(al16(a.agent) && al16(a.goal) && al16(a.obst) && al16(a.hits) && al16(a.next_agent) && al16(a.next_hits) &&
-        al16(a.action)))
-    return false;
-  if (a.has_graph && !(al16(a.g.edges) && al16(a.g.states))) return false;
-  const bool spread = cfg_is_spread(c);
-  const int n = c.n_agents, no = c.n_obs, sd = c.state_dim;
-#define TRY(SD_, SP_, NA_, NO_) if (sd == SD_ && spread == SP_ && n == NA_ && no == NO_) return launch_inst<SD_, SP_, NA_, NO_>(a, s)
-  TRY(4, true, 8, 3);      // BASELINE configs 3 / 4: LidarSpread n = 8, obs = 3
-  TRY(4, false, 8, 3);     // LidarTarget n = 8, obs = 3
-  TRY(5, false, 16, 8);    // BASELINE config 5: LidarBicycleTarget n = 16, obs = 8
-  TRY(4, true, 16, 8);
-  TRY(4, true, 4, 2);
-  TRY(4, false, 4, 2);
-  TRY(5, false, 4, 3);
-#undef TRY
-  return false;
+bool lidar_wave_has_instance(const dgppo_env_cfg& c) { return with_instance(c, [](auto) {}); }
+
+void launch_lidar_wave(const StepArgs& a, hipStream_t s) {
+  with_instance(a.cfg, [&](auto inst) {
+    using I = decltype(inst);
+    launch_inst<I::SD, I::SPREAD, I::NA, I::NO>(a, s);
+  });
 }

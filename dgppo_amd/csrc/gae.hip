@@ -5,7 +5,6 @@
 //   advantage block            dgppo/algo/dgppo.py:239-259 (per-env normalisation, CBF derivative, safe gate, schedule)
 // Layout (env-major): costs [B,T,n,nh], rewards [B,T], Vh [B,T+1,n,nh], Vl [B,T+1] -> Qh [B,T,n,nh], Ql [B,T].
 #include "common.h"
-#include <stdlib.h>
 
 // jnp.maximum / .max(-1) propagate NaN (algo/utils.py:39-44); v_max_f32 (fmaxf) returns the other operand.  Costs can be NaN
 // (a NaN LiDAR hit point, lidar_env/base.py:180-207), and the reference then gets NaN targets, NaN losses and a skipped
@@ -290,8 +289,11 @@ extern "C" int32_t dgppo_gae(const float* costs, const float* rewards, const flo
   if (B == 0) return 0;
   DGPPO_REQUIRE(costs && rewards && Vh && Vl && lam_pow && Qh && Ql, "gae: NULL operand");
   GaeArgs a{costs, rewards, Vh, Vl, lam_pow, Qh, Ql, B, T, n * nh, n, nh, gamma, one_minus_gamma, one_minus_lam};
-  // column-parallel kernel: lambda^-31 must stay in range (lambda = 1 - one_minus_lam >= 0.5) and the rows must fit the lanes
-  if (T <= 256 && one_minus_lam <= 0.5f && one_minus_lam >= 0.0f && !getenv("DGPPO_GAE_ROWS")) {
+  // The family is chosen by shape and lambda; the first that applies runs:
+  //   column-parallel gae_cols_kernel: T <= 256 and lambda >= 0.5 (lambda^-31 must stay in range; the rows must fit the lanes);
+  //   row-parallel gae_rows_kernel<8|16|32>: T + 1 <= 256, n * nh <= 32 and its LDS stage <= 64 KB;
+  //   generic gae_kernel: everything else.
+  if (T <= 256 && one_minus_lam <= 0.5f && one_minus_lam >= 0.0f) {
     hipStream_t st = (hipStream_t)stream;
     if (T <= 32) launch_gae_cols<8, 4>(a, st);
     else if (T <= 64) launch_gae_cols<16, 4>(a, st);

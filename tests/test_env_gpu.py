@@ -15,6 +15,8 @@ CASES = [
     ("MPESpread", 3, 3), ("MPETarget", 3, 0), ("MPETarget", 3, 3), ("MPESpread", 5, 2),
     # the remaining instantiations of the wave-per-env kernel (csrc/env_wave.hip)
     ("LidarTarget", 8, 3), ("LidarSpread", 4, 2), ("LidarSpread", 16, 8),
+    # no wave instance: the workgroup-per-env LiDAR kernel, Target topology
+    ("LidarTarget", 3, 1),
 ]
 
 
@@ -47,8 +49,20 @@ def _to(x, dev):
     return None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev)
 
 
-def _run_step(cfg, ocfg, agent, goal, obst, hits, action, dev, want_graph=True):
+def _misaligned(t):
+    """a copy of device tensor t placed one float past a 16-byte boundary: the wave-per-env kernel stages its inputs as
+    float4 and is not chosen for it (step_family, csrc/env_step.hip); the workgroup-per-env kernels read such inputs"""
+    buf = torch.empty(t.numel() + 1, device=t.device)
+    out = buf[1:].view(t.shape)
+    out.copy_(t)
+    assert out.data_ptr() % 16 == 4
+    return out
+
+
+def _step_dev(cfg, agent, goal, obst, hits, action, want_graph=True, misalign=False):
+    """env_step on device tensors, outputs left on the device; misalign: `agent` one float past a 16-byte boundary"""
     from dgppo_amd import ops_env as O
+    dev = agent.device
     B, n = agent.shape[:2]
     rc, rs = O.ray_tables(max(cfg.n_rays, 1), dev) if cfg.is_lidar else (None, None)
     nx = torch.empty(B, n, cfg.state_dim, device=dev)
@@ -56,13 +70,17 @@ def _run_step(cfg, ocfg, agent, goal, obst, hits, action, dev, want_graph=True):
     rew = torch.empty(B, device=dev)
     cost = torch.empty(B, n, cfg.n_cost, device=dev)
     g = O.alloc_graph(cfg, B, dev) if want_graph else None
-    O.env_step(cfg, _to(agent, dev), _to(action, dev), _to(goal, dev), _to(obst, dev), _to(hits, dev), rc, rs,
+    O.env_step(cfg, _misaligned(agent) if misalign else agent, action, goal, obst, hits, rc, rs,
                nx, nh, rew if action is not None else None, cost if action is not None else None, g)
+    return dict(next_agent=nx, next_hits=nh, reward=rew, cost=cost, graph=g)
+
+
+def _run_step(cfg, ocfg, agent, goal, obst, hits, action, dev, want_graph=True, misalign=False):
+    d = _step_dev(cfg, _to(agent, dev), _to(goal, dev), _to(obst, dev), _to(hits, dev), _to(action, dev), want_graph, misalign)
     torch.cuda.synchronize()
-    out = dict(next_agent=nx.cpu().numpy(), next_hits=None if nh is None else nh.cpu().numpy(),
-               reward=rew.cpu().numpy(), cost=cost.cpu().numpy())
-    if g is not None:
-        out["graph"] = {k: v.cpu().numpy() for k, v in g.items()}
+    out = {k: None if v is None else v.cpu().numpy() for k, v in d.items() if k != "graph"}
+    if d["graph"] is not None:
+        out["graph"] = {k: v.cpu().numpy() for k, v in d["graph"].items()}
     return out
 
 
@@ -71,6 +89,18 @@ def _assert_graph_equal(got, want):
         np.testing.assert_array_equal(got[k], want[k], err_msg=k)          # integer outputs: bit-exact
     for k in ("nodes", "edges", "states"):
         np.testing.assert_array_equal(got[k].view(np.uint32), want[k].view(np.uint32), err_msg=k)
+
+
+def _bits(t):
+    return t.view(torch.int32) if t.dtype == torch.float32 else t
+
+
+def _assert_dev_equal(got, want, keys, tag):
+    """every bit of the named outputs and of the graph, compared on the device"""
+    for k in keys:
+        assert torch.equal(_bits(got[k]), _bits(want[k])), f"{tag} {k}"
+    for k in want["graph"]:
+        assert torch.equal(_bits(got["graph"][k]), _bits(want["graph"][k])), f"{tag} graph {k}"
 
 
 @pytest.mark.parametrize("kind,n,n_obs", CASES)
@@ -255,22 +285,8 @@ def test_randn_moments_and_determinism(cuda):
     assert not torch.equal(x, y)
 
 
-def test_generic_kernel_path_matches_specialised(cuda, monkeypatch):
-    """LiDAR envs normally run the specialised n_rays == 32 kernel; the generic kernel (other ray counts, forced here with
-    DGPPO_GENERIC_ENV_KERNEL) must give the same bits, and so must a non-32 ray fan against the oracle."""
-    cfg, ocfg = _mk("LidarSpread", 8, 3)
-    B = 96
-    agent, goal, obst, action = _random_state(ocfg, B, seed=21)
-    tab = E.ray_table(32)
-    hits, _ = E.lidar_sense(ocfg, agent[..., :2], obst, *tab)
-    fast = _run_step(cfg, ocfg, agent, goal, obst, hits, action, cuda)
-    monkeypatch.setenv("DGPPO_GENERIC_ENV_KERNEL", "1")
-    gen = _run_step(cfg, ocfg, agent, goal, obst, hits, action, cuda)
-    monkeypatch.delenv("DGPPO_GENERIC_ENV_KERNEL")
-    for k in ("next_agent", "next_hits", "reward", "cost"):
-        np.testing.assert_array_equal(fast[k].view(np.uint32), gen[k].view(np.uint32), err_msg=k)
-    _assert_graph_equal(fast["graph"], gen["graph"])
-    # 16 rays, top-4: generic kernel vs oracle
+def test_generic_kernel_16_rays_matches_oracle(cuda):
+    """A LiDAR fan of 16 rays, top-4: only the generic kernel takes it (the specialised ones need 32 rays)."""
     from dgppo_amd import _native as N, ops_env as O
     cfg16 = N.make_env_cfg(0, 5, 2, n_rays=16, top_k=4)
     o16 = E.EnvCfg(0, n_agents=5, n_obs=2, n_rays=16, top_k=4)
@@ -309,41 +325,38 @@ def _adversarial_state(ocfg, B, seed):
 
 @pytest.mark.parametrize("kind,n,n_obs,B", [("LidarSpread", 8, 3, 1500), ("LidarTarget", 8, 3, 300),
                                             ("LidarBicycleTarget", 16, 8, 200), ("LidarSpread", 4, 2, 333)])
-def test_wave_kernel_equals_workgroup_kernel_and_oracle(cuda, monkeypatch, kind, n, n_obs, B):
+def test_wave_kernel_equals_workgroup_kernel_and_oracle(cuda, kind, n, n_obs, B):
     """csrc/env_wave.hip (wave-per-env, obstacle culling, ballot top-k, squared-distance minima and masks) against the
-    workgroup-per-env kernel of env_step.hip (forced with DGPPO_NO_WAVE_ENV_KERNEL) — every output, every bit, in all three
-    modes (step / sense-only / materialise), with persistent waves looping over several envs — and against the oracle."""
+    workgroup-per-env kernel of env_step.hip (reached with `agent` one float past a 16-byte boundary) — every output, every
+    bit, in all three modes (step / sense-only / materialise) — and against the oracle.  Then the same at
+    3 x 8 x 4 x CU-count envs, tiled from the same scenes: 8 is the wave kernel's maximum waves per SIMD, so every
+    persistent wave walks at least 3 environments."""
+    from dgppo_amd import ops_env as O
     cfg, ocfg = _mk(kind, n, n_obs)
     agent, goal, obst, action = _adversarial_state(ocfg, B, seed=5)
     tab = E.ray_table(32)
     hits, _ = E.lidar_sense(ocfg, agent[..., :2], obst, *tab)
     hits = hits.copy()
     hits[5, 0, 3, 0] = np.nan                                           # a NaN hit point in graph_t
-    for wave_envs in ("1", "3"):
-        monkeypatch.setenv("DGPPO_WAVE_ENVS", wave_envs)                # 3: every wave walks >= 3 environments
-        fast = _run_step(cfg, ocfg, agent, goal, obst, hits, action, cuda)
-        fast_sense = _run_step(cfg, ocfg, agent, goal, obst, None, None, cuda)
-        monkeypatch.setenv("DGPPO_NO_WAVE_ENV_KERNEL", "1")
-        ref = _run_step(cfg, ocfg, agent, goal, obst, hits, action, cuda)
-        ref_sense = _run_step(cfg, ocfg, agent, goal, obst, None, None, cuda)
-        monkeypatch.delenv("DGPPO_NO_WAVE_ENV_KERNEL")
-        for got, want, tag in ((fast, ref, "step"), (fast_sense, ref_sense, "sense")):
-            for k in ("next_agent", "next_hits") + (("reward", "cost") if tag == "step" else ()):
-                np.testing.assert_array_equal(got[k].view(np.uint32), want[k].view(np.uint32), err_msg=f"{tag} {k}")
-            _assert_graph_equal(got["graph"], want["graph"])
+    fast = _run_step(cfg, ocfg, agent, goal, obst, hits, action, cuda)
+    fast_sense = _run_step(cfg, ocfg, agent, goal, obst, None, None, cuda)
+    ref = _run_step(cfg, ocfg, agent, goal, obst, hits, action, cuda, misalign=True)
+    ref_sense = _run_step(cfg, ocfg, agent, goal, obst, None, None, cuda, misalign=True)
+    for got, want, tag in ((fast, ref, "step"), (fast_sense, ref_sense, "sense")):
+        for k in ("next_agent", "next_hits") + (("reward", "cost") if tag == "step" else ()):
+            np.testing.assert_array_equal(got[k].view(np.uint32), want[k].view(np.uint32), err_msg=f"{tag} {k}")
+        _assert_graph_equal(got["graph"], want["graph"])
     assert np.isnan(fast["cost"][5, 0, 1]) and np.isfinite(fast["cost"][6]).all()
     # materialise-only mode
-    from dgppo_amd import ops_env as O
     g1, g2 = O.alloc_graph(cfg, B, cuda), O.alloc_graph(cfg, B, cuda)
-    h = fast["next_hits"]
-    O.graph_materialize(cfg, _to(fast["next_agent"], cuda), _to(goal, cuda), _to(obst, cuda), _to(h, cuda), g1)
-    monkeypatch.setenv("DGPPO_NO_WAVE_ENV_KERNEL", "1")
-    O.graph_materialize(cfg, _to(fast["next_agent"], cuda), _to(goal, cuda), _to(obst, cuda), _to(h, cuda), g2)
-    monkeypatch.delenv("DGPPO_NO_WAVE_ENV_KERNEL")
+    nx, h = _to(fast["next_agent"], cuda), _to(fast["next_hits"], cuda)
+    O.graph_materialize(cfg, nx, _to(goal, cuda), _to(obst, cuda), h, g1)
+    O.graph_materialize(cfg, _misaligned(nx), _to(goal, cuda), _to(obst, cuda), h, g2)
     torch.cuda.synchronize()
     _assert_graph_equal({k: v.cpu().numpy() for k, v in g1.items()}, {k: v.cpu().numpy() for k, v in g2.items()})
     _assert_graph_equal({k: v.cpu().numpy() for k, v in g1.items()}, fast["graph"])
     # and the oracle (double integrator: bit-exact; the bicycle's dynamics are compared elsewhere within 1e-6)
+    want = None
     if not ocfg.is_bicycle:
         want = E.env_step(ocfg, agent, goal, obst, hits, action, tab)
         for k in ("next_agent", "next_hits", "reward", "cost"):
@@ -355,6 +368,32 @@ def test_wave_kernel_equals_workgroup_kernel_and_oracle(cuda, monkeypatch, kind,
         p = want["next_agent"][0, 0, :2]
         assert np.all(want["next_hits"][0, 0] == p), "agent inside an obstacle: all hit points collapse onto the agent"
         assert (np.abs(want["next_hits"]) > 1e5).any()
+
+    # ---- every wave walks >= 3 environments: the scenes tiled to 3 x (8 waves per SIMD x 4 SIMDs) per CU, compared on the device
+    Bw = 3 * 8 * 4 * torch.cuda.get_device_properties(cuda).multi_processor_count
+    idx = torch.arange(Bw, device=cuda) % B
+    tile = lambda x: None if x is None else _to(x, cuda)[idx].contiguous()
+    A, G, Ob, H, Ac = (tile(x) for x in (agent, goal, obst, hits, action))
+    for tag, h_in, act in (("step", H, Ac), ("sense", None, None)):
+        keys = ("next_agent", "next_hits") + (("reward", "cost") if tag == "step" else ())
+        w = _step_dev(cfg, A, G, Ob, h_in, act)
+        _assert_dev_equal(w, _step_dev(cfg, A, G, Ob, h_in, act, misalign=True), keys, f"{Bw} envs {tag}")
+        if tag == "step":
+            if want is not None:                         # the oracle's outputs tiled the same way
+                for k in keys:
+                    wk = tile(want[k])
+                    nan = torch.isnan(wk)
+                    assert torch.equal(torch.isnan(w[k]), nan), f"{Bw} envs oracle {k}"
+                    assert torch.equal(_bits(w[k])[~nan], _bits(wk)[~nan]), f"{Bw} envs oracle {k}"
+                for k, v in want["graph"].items():
+                    assert torch.equal(_bits(w["graph"][k]), _bits(tile(v))), f"{Bw} envs oracle graph {k}"
+            g1, g2 = O.alloc_graph(cfg, Bw, cuda), O.alloc_graph(cfg, Bw, cuda)
+            O.graph_materialize(cfg, w["next_agent"], G, Ob, w["next_hits"], g1)
+            O.graph_materialize(cfg, _misaligned(w["next_agent"]), G, Ob, w["next_hits"], g2)
+            _assert_dev_equal({"graph": g1}, {"graph": g2}, (), f"{Bw} envs materialise")
+            _assert_dev_equal({"graph": g1}, w, (), f"{Bw} envs materialise vs step")
+        del w
+    torch.cuda.synchronize()
 
 
 # ---- task variants -------------------------------------------------------------------------------------
