@@ -20,7 +20,9 @@ ABI_VERSION = 3
 OPT_STATE_FLOATS = 8 + 2 * 256     # DGPPO_OPT_STATE_FLOATS (include/dgppo_hip.h)
 
 ENV_KINDS = {"LidarSpread": 0, "LidarTarget": 1, "LidarBicycleTarget": 2, "MPESpread": 3, "MPETarget": 4,
-             "LidarLine": 5, "MPELine": 6, "MPEFormation": 7, "MPECorridor": 8, "MPEConnectSpread": 9}
+             "LidarLine": 5, "MPELine": 6, "MPEFormation": 7, "MPECorridor": 8, "MPEConnectSpread": 9,
+             "VMASReverseTransport": 10}
+VMAS_REVERSE_TRANSPORT = 10
 GOALS_NODES, GOALS_LINE, GOALS_LINE_INTERIOR, GOALS_CIRCLE = range(4)
 RECT_STRIDE = 16
 
@@ -39,6 +41,10 @@ class EnvCfg(C.Structure):
     ]
 
     # ---- derived sizes (mirror csrc/common.h) ----
+    @property
+    def is_vmas(self):
+        return self.kind == VMAS_REVERSE_TRANSPORT
+
     @property
     def is_lidar(self):
         return self.kind <= 2 or self.kind == 5
@@ -86,6 +92,8 @@ def make_env_cfg(kind: int, n_agents: int, n_obs: int, n_rays: int = 32, top_k: 
     """Thresholds are formed in Python doubles then rounded to fp32, exactly as the reference's weakly-typed
     Python floats are (e.g. `comm_radius - 1e-1`, dgppo/env/lidar_env/lidar_spread.py:88).  area_size / obs_radius default
     to the PARAMS of the kind (1.5 / 0.05; MPECorridor and MPEConnectSpread: area 1.0, obs_radius derived / 0.25)."""
+    if kind == VMAS_REVERSE_TRANSPORT:
+        return make_vmas_cfg(n_agents, dt)
     is_lidar = kind <= 2 or kind == 5
     corridor, connect = kind == 8, kind == 9
     if area_size is None:
@@ -124,6 +132,22 @@ def make_env_cfg(kind: int, n_agents: int, n_obs: int, n_rays: int = 32, top_k: 
         c.line_min_dist = n_agents * 5 * car_radius if (kind == 6 and n_agents <= 3) else (n_agents - 2) * 6 * car_radius
     else:
         c.line_min_dist = 0.0
+    return c
+
+
+def make_vmas_cfg(n_agents: int, dt: float = 0.03) -> EnvCfg:
+    """VMASReverseTransport (dgppo/env/vmas/vmas_reverse_transport.py:35-63).  Its constants are fixed by the kind and live in
+    csrc/env_vmas.hip; the graph holds the n agent nodes and the pad only (n_goals = n_obs = 0: N = n + 1, E = n * n).  dt is
+    env.dt, what DGPPO's CBF term divides by; the physics steps with the World's own 0.1.  The remaining fields are the
+    numbers the reference uses (area 1.6, agent radius 0.03, obstacle radius 0.15, comm radius 0.4, dist2goal 0.01)."""
+    c = EnvCfg()
+    c.kind, c.n_agents, c.n_goals, c.n_obs, c.n_rays, c.top_k = VMAS_REVERSE_TRANSPORT, n_agents, 0, 0, 0, 0
+    c.state_dim, c.node_dim = 4, 20
+    c.area_size, c.dt, c.car_radius, c.comm_radius, c.obs_radius, c.dist2goal = 1.6, dt, 0.03, 0.4, 0.15, 0.01
+    c.two_car_radius = 0.03 * 2
+    c.vel_limit, c.reset_min_dist = 1.0, 0.03 * 2
+    c.reward_goals, c.n_cost = GOALS_NODES, 2
+    c.obs_mask_radius, c.y_limit = 0.4, 1.6
     return c
 
 

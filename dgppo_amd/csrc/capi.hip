@@ -17,7 +17,15 @@ extern "C" const char* dgppo_last_error(void) { return g_err; }
 
 int32_t dgppo_validate_cfg(const dgppo_env_cfg* c) {
   DGPPO_REQUIRE(c != nullptr, "cfg is NULL");
-  DGPPO_REQUIRE(c->kind >= DGPPO_ENV_LIDAR_SPREAD && c->kind <= DGPPO_ENV_MPE_CONNECT_SPREAD, "unknown env kind %d", c->kind);
+  DGPPO_REQUIRE(c->kind >= DGPPO_ENV_LIDAR_SPREAD && c->kind <= DGPPO_ENV_VMAS_REVERSE_TRANSPORT, "unknown env kind %d", c->kind);
+  if (cfg_is_vmas(*c)) {        // agents only: no goal or obstacle nodes in the graph (vmas_reverse_transport.py:251-311)
+    DGPPO_REQUIRE(c->n_agents >= 1 && c->n_agents <= 16, "VMASReverseTransport: n_agents must be in [1,16] (got %d)", c->n_agents);
+    DGPPO_REQUIRE(c->n_goals == 0 && c->n_obs == 0 && c->n_rays == 0 && c->top_k == 0,
+                  "VMASReverseTransport: n_goals, n_obs, n_rays and top_k must be 0 (the graph has agent nodes only)");
+    DGPPO_REQUIRE(c->state_dim == 4 && c->node_dim == 20 && c->n_cost == 2 && c->reward_goals == DGPPO_GOALS_NODES,
+                  "VMASReverseTransport: state_dim 4, node_dim 20, n_cost 2 expected");
+    return 0;
+  }
   DGPPO_REQUIRE(c->n_agents >= 1 && c->n_agents <= 64, "n_agents must be in [1,64] (got %d)", c->n_agents);
   {
     const bool line = c->kind == DGPPO_ENV_LIDAR_LINE || c->kind == DGPPO_ENV_MPE_LINE;

@@ -63,7 +63,13 @@ __host__ __device__ inline int cfg_num_edges(const dgppo_env_cfg& c) {
 }
 __host__ __device__ inline int cfg_obst_stride(const dgppo_env_cfg& c) { return cfg_is_lidar(c) ? DGPPO_RECT_STRIDE : c.state_dim; }
 
+__host__ __device__ inline bool cfg_is_vmas(const dgppo_env_cfg& c) { return c.kind == DGPPO_ENV_VMAS_REVERSE_TRANSPORT; }
+
 int32_t dgppo_validate_cfg(const dgppo_env_cfg* cfg);
+// the entry points of the other kinds refuse the VMAS record (it has a body and a scene, no goal / obstacle rows)
+#define DGPPO_REFUSE_VMAS(cfg, what, instead)                                                                   \
+  DGPPO_REQUIRE(!((cfg) && cfg_is_vmas(*(cfg))), "%s does not take VMASReverseTransport (env kind 10): use %s", \
+                what, instead)
 
 // ---- Philox-4x32-10 (stream layout documented in oracle/env_np.py) ---------------------------
 struct Philox4 {

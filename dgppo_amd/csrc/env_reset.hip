@@ -384,6 +384,7 @@ extern "C" int32_t dgppo_env_reset_checked(const dgppo_env_cfg* cfg, const uint6
                                            float* obst, int32_t* n_failed, int32_t B, void* stream) {
   int32_t rc = dgppo_validate_cfg(cfg);
   if (rc) return rc;
+  DGPPO_REFUSE_VMAS(cfg, "dgppo_env_reset", "dgppo_vmas_reset_checked");
   {
     // feasibility of the rejection sampling (env/utils.py:139-244): n points with pairwise distance >= reset_min_dist in
     // [0, area] x [0, reset_side_y].  Random sequential placement of discs jams at ~0.547 coverage; beyond one half the loops

@@ -768,6 +768,8 @@ static int32_t launch_step(const dgppo_env_cfg* cfg, int mode, const float* agen
                            int32_t B, void* stream) {
   int32_t rc = dgppo_validate_cfg(cfg);
   if (rc) return rc;
+  if (mode == MODE_GRAPH) DGPPO_REFUSE_VMAS(cfg, "dgppo_graph_materialize", "dgppo_vmas_graph_materialize");
+  else DGPPO_REFUSE_VMAS(cfg, "dgppo_env_step", "dgppo_vmas_step");
   DGPPO_REQUIRE(B >= 0, "B must be >= 0 (got %d)", B);
   if (B == 0) return 0;
   const bool lidar = cfg_is_lidar(*cfg);

@@ -45,6 +45,16 @@ __device__ inline int slot_of(const Topo& t, int nd, int i) {
   return t.n + t.gs + q;
 }
 
+// The constant-one column of zcat carries sum_s a[i,s,h] b_v = b_v.  An agent without any unmasked sender slot has no
+// incoming edge (aggr = 0, gnn.py:109-111), so its column is 0.  Goal slots are never masked: only topologies without them
+// (VMASReverseTransport, agent slots only) have to look at the masks.
+__device__ inline float ones_col(const Topo& t, const float* mrow) {
+  if (t.gs > 0) return 1.0f;
+  for (int s = 0; s < t.S; ++s)
+    if (mrow[s] != 0.0f) return 1.0f;
+  return 0.0f;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // graph features: compact record -> agent/other node feature matrices, per-slot edge features and masks.
 // Same arithmetic (explicit _rn ops = no fma contraction) as env_step.hip phase 5, i.e. as
@@ -168,6 +178,7 @@ extern "C" int32_t dgppo_graph_feats(const dgppo_env_cfg* cfg, const float* agen
                                      float* Xo, float* efeat, float* emask, int32_t Fp, void* stream) {
   int32_t rc = dgppo_validate_cfg(cfg);
   if (rc) return rc;
+  DGPPO_REFUSE_VMAS(cfg, "dgppo_graph_feats", "dgppo_vmas_graph_feats");
   DGPPO_REQUIRE(n_env >= 0 && n_time >= 0, "graph_feats: negative counts");
   if (n_env == 0 || n_time == 0) return 0;
   DGPPO_REQUIRE(agent && goal && Xa && efeat && emask, "graph_feats: NULL operand");
@@ -303,7 +314,7 @@ __global__ void __launch_bounds__(256) attn_fwd_valu_kernel(AttnArgs a) {
   const int kc = F + H * W;  // index of the constant-one column (carries mean_h b_v)
   for (int idx = tid; idx < n * (a.Kp - kc); idx += nt) {
     const int i = idx / (a.Kp - kc), c = kc + idx - i * (a.Kp - kc);
-    a.zcat[((size_t)g * n + i) * a.Kp + c] = (c == kc) ? 1.0f : 0.0f;
+    a.zcat[((size_t)g * n + i) * a.Kp + c] = (c == kc) ? ones_col(a.t, a.emask + ((size_t)g * n + i) * a.t.S) : 0.0f;
   }
 }
 
@@ -617,7 +628,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
   const int kc = F + H * Wd;
   for (int idx = tid; idx < n * (a.Kp - kc); idx += 256) {
     const int i = idx / (a.Kp - kc), c = kc + idx - i * (a.Kp - kc);
-    zc[i * a.Kp + c] = (c == kc) ? 1.0f : 0.0f;
+    zc[i * a.Kp + c] = (c == kc) ? ones_col(t, a.emask + ((size_t)g * n + i) * S) : 0.0f;
   }
   ASTAMP(6);
 }
@@ -669,7 +680,7 @@ __global__ void __launch_bounds__(256) attn_fwd_slot8_kernel(AttnArgs a) {
   for (int idx = lane; idx < n * 2; idx += 64)
     *reinterpret_cast<float4*>(zc + (idx >> 1) * Kp + 4 * (idx & 1)) = reinterpret_cast<const float4*>(Xa)[idx];
   for (int i = lane; i < n; i += 64)
-    for (int c = kc; c < Kp; ++c) zc[i * Kp + c] = (c == kc) ? 1.0f : 0.0f;
+    for (int c = kc; c < Kp; ++c) zc[i * Kp + c] = (c == kc) ? ones_col(a.t, mk + i * S) : 0.0f;
 #pragma unroll
   for (int p = 0; p < NPA; ++p) {
     const int ia = grp + 8 * p;
@@ -1203,7 +1214,7 @@ __global__ void __launch_bounds__(128) attn_fwd_bd_kernel(AttnArgs a) {
   {
     const int wpad = Kp - kc;                                  // >= 1: the constant column, then zeros
     for (int i = lane; i < n; i += 64)
-      for (int cc = 0; cc < wpad; ++cc) zc[i * Kp + kc + cc] = (cc == 0) ? 1.0f : 0.0f;
+      for (int cc = 0; cc < wpad; ++cc) zc[i * Kp + kc + cc] = (cc == 0) ? ones_col(a.t, mk + i * S) : 0.0f;
   }
   ASTAMP(6);
 }
@@ -1407,7 +1418,7 @@ __global__ void __launch_bounds__(128) attn_fwd_bdp_kernel(AttnArgs a) {
     {
       const int wpad = Kp - kc;                                  // >= 1: the constant column, then zeros
       for (int ii = lane; ii < n; ii += 64)
-        for (int cc = 0; cc < wpad; ++cc) zc[ii * Kp + kc + cc] = (cc == 0) ? 1.0f : 0.0f;
+        for (int cc = 0; cc < wpad; ++cc) zc[ii * Kp + kc + cc] = (cc == 0) ? ones_col(a.t, a.emask + ((size_t)gg * n + ii) * a.t.S) : 0.0f;
     }
   };
   Regs cur;

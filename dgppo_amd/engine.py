@@ -59,9 +59,13 @@ class RolloutData:
         n, sd = cfg.n_agents, cfg.state_dim
         self.cfg, self.B, self.T, self.stochastic = cfg, B, T, stochastic
         self.has_hits = cfg.is_lidar and cfg.n_obs > 0
+        self.vmas = cfg.is_vmas
         z = lambda *s: torch.empty(*s, device=device)
         self.agent_tm = z(T + 1, B, n, sd)
         self.hits_tm = z(T + 1, B, n, cfg.top_k, 2) if self.has_hits else None
+        # VMASReverseTransport: the box (x, y, vx, vy) per step and the goal | 3 obstacle centres per env
+        self.body_tm = z(T + 1, B, 4) if self.vmas else None
+        self.scene = z(B, 8) if self.vmas else None
         self.goal = z(B, cfg.n_goals, sd)
         self.obst = z(B, cfg.n_obs, cfg.obst_stride) if cfg.n_obs > 0 else None
         self.action_tm = z(T, B, n, 2)
@@ -88,6 +92,7 @@ class RolloutData:
             return cur
         self.agent = tr("agent", self.agent_tm)                       # [B, T+1, n, sd]
         self.hits = tr("hits", self.hits_tm) if self.has_hits else None
+        self.body = tr("body", self.body_tm) if self.vmas else None       # [B, T+1, 4]
         self.actions = tr("actions", self.action_tm)                  # [B, T, n, 2]
         self.log_pis = tr("log_pis", self.log_pi_tm) if self.stochastic else None
         self._rnn_em = tr("_rnn_em", self.rnn_tm)                     # [B, T+1, n, 64]
@@ -198,13 +203,27 @@ class Engine:
         f.compute(agent_slab, n * sd, 0, goal, obst, hits_slab, n * cfg.top_k * 2, 0, None, B, 1)
         return f
 
+    def _feats_vmas(self, tag, agent_slab, body_slab, scene, B):
+        """VMASReverseTransport: graph features of B dense [B, n, 4] / [B, 4] states"""
+        f = nets.GraphFeats(self.cfg, B, self.arena, tag)
+        return f.compute_vmas(agent_slab, self.cfg.n_agents * 4, 0, body_slab, 4, 0, scene, None, B, 1)
+
+    def _feats_of_state(self, tag, st, B):
+        """graph features of a batched env state (BatchState, or VMASBatchState for VMASReverseTransport)"""
+        if self.cfg.is_vmas:
+            return self._feats_vmas(tag, st.agent, st.body, st.scene, B)
+        return self._feats_at(tag, st.agent, st.hits, st.goal, st.obst, B)
+
     def _rollout_steps(self, ro: RolloutData, eps, B: int, stochastic: bool):
         """the T env steps of a rollout: policy forward (GNN + GRU + head) and env.step, all on the current stream."""
         cfg, T, n = self.cfg, self.T, self.cfg.n_agents
         tag = "ro" if stochastic else "rod"    # separate scratch per kind: the two rollouts may run on different streams
         for t in range(T):
             hits_t = ro.hits_tm[t] if ro.has_hits else None
-            feats = self._feats_at(tag, ro.agent_tm[t], hits_t, ro.goal, ro.obst, B)
+            if ro.vmas:
+                feats = self._feats_vmas(tag, ro.agent_tm[t], ro.body_tm[t], ro.scene, B)
+            else:
+                feats = self._feats_at(tag, ro.agent_tm[t], hits_t, ro.goal, ro.obst, B)
             act = self.policy.forward(feats, n_seq=B * n, T=1, h0=ro.rnn_tm[t].view(B * n, self.HC), tag=tag,
                                       hs_out=ro.rnn_tm[t + 1].view(B * n, self.HC), train=False)
             a_t = ro.action_tm[t].view(B * n, 2)
@@ -212,6 +231,10 @@ class Engine:
                 K.policy_head(act["ms"], eps[t], None, a_t, ro.log_pi_tm[t].view(B * n), None, n, 0)
             else:
                 K.policy_head(act["ms"], None, None, a_t, None, None, n, 1)
+            if ro.vmas:
+                OE.vmas_step(cfg, ro.agent_tm[t], ro.body_tm[t], ro.scene, ro.action_tm[t], ro.agent_tm[t + 1],
+                             ro.body_tm[t + 1], ro.reward_tm[t], ro.cost_tm[t], None)
+                continue
             OE.env_step(cfg, ro.agent_tm[t], ro.action_tm[t], ro.goal, ro.obst, hits_t, self.ray_cos, self.ray_sin,
                         ro.agent_tm[t + 1], ro.hits_tm[t + 1] if ro.has_hits else None, ro.reward_tm[t], ro.cost_tm[t], None)
 
@@ -229,7 +252,10 @@ class Engine:
             ro._env_major = False
         else:
             ro = RolloutData(cfg, B, T, self.device, stochastic, self.HC)
-        OE.env_reset(cfg, seeds, ro.agent_tm[0], ro.goal, ro.obst, self.reset_failed)
+        if ro.vmas:
+            OE.vmas_reset(cfg, seeds, ro.agent_tm[0], ro.body_tm[0], ro.scene, self.reset_failed)
+        else:
+            OE.env_reset(cfg, seeds, ro.agent_tm[0], ro.goal, ro.obst, self.reset_failed)
         if ro.has_hits:
             OE.env_step(cfg, ro.agent_tm[0], None, ro.goal, ro.obst, None, self.ray_cos, self.ray_sin, None, ro.hits_tm[0],
                         None, None, None)
@@ -308,6 +334,10 @@ class Engine:
         n, sd, T1 = cfg.n_agents, cfg.state_dim, self.T + 1
         f = nets.GraphFeats(cfg, Eb * n_time, self.arena, tag)
         agent = ro.agent[e0:, t0] if env_ids is None else ro.agent[:, t0]
+        if ro.vmas:
+            body = ro.body[e0:, t0] if env_ids is None else ro.body[:, t0]
+            scene = ro.scene[e0:] if env_ids is None else ro.scene
+            return f.compute_vmas(agent, T1 * n * sd, n * sd, body, T1 * 4, 4, scene, env_ids, Eb, n_time)
         hits = None
         if ro.has_hits:
             hits = ro.hits[e0:, t0] if env_ids is None else ro.hits[:, t0]
@@ -385,9 +415,14 @@ class Engine:
         A = self.arena
         fin_cost = A.get("tg.fin_cost", B, n, nh)
         scratch_agent = torch.empty_like(fin_agent)
-        OE.env_step(cfg, fin_agent, torch.zeros(B, n, 2, device=dev), ro.goal, ro.obst, fin_hits, self.ray_cos, self.ray_sin,
-                    scratch_agent, torch.empty_like(fin_hits) if fin_hits is not None else None, torch.empty(B, device=dev),
-                    fin_cost, None)
+        if ro.vmas:
+            fin_body = ro.body[:, T].contiguous()
+            OE.vmas_step(cfg, fin_agent, fin_body, ro.scene, torch.zeros(B, n, 2, device=dev), scratch_agent,
+                         torch.empty_like(fin_body), torch.empty(B, device=dev), fin_cost, None)
+        else:
+            OE.env_step(cfg, fin_agent, torch.zeros(B, n, 2, device=dev), ro.goal, ro.obst, fin_hits, self.ray_cos,
+                        self.ray_sin, scratch_agent, torch.empty_like(fin_hits) if fin_hits is not None else None,
+                        torch.empty(B, device=dev), fin_cost, None)
         Vh = A.get("tg.Vh.crafted", B, T + 1, n, nh)
         Vh[:, :T].copy_(ro.costs)
         Vh[:, T].copy_(fin_cost)

@@ -4,13 +4,15 @@ from typing import Optional
 from . import envs as _envs
 from .base import MultiAgentEnv
 from .envs import LidarEnvState, MPEEnvState, Rectangle          # re-exported: users import them from dgppo.env
+from .vmas import VMASReverseTransport, VMASReverseTransportState
 
 DEFAULT_MAX_STEP = 128
 _BUILT = ("MPETarget", "MPESpread", "MPELine", "MPEFormation", "MPECorridor", "MPEConnectSpread", "LidarSpread",
           "LidarTarget", "LidarLine", "LidarBicycleTarget")
-# registered by the reference, outside the scope of this build (SURVEY §2 rows 20-21)
-_REFERENCE_ONLY = ("VMASReverseTransport", "VMASWheel")
+# registered by the reference, outside the scope of this build (SURVEY §2 row 21)
+_REFERENCE_ONLY = ("VMASWheel",)
 ENV = {name: getattr(_envs, name) for name in _BUILT}
+ENV["VMASReverseTransport"] = VMASReverseTransport
 globals().update(ENV)                                              # `from dgppo.env import LidarSpread` keeps working
 
 

@@ -182,6 +182,11 @@ class MultiAgentEnv(ABC):
         OE.graph_materialize(self.cfg, st.agent, st.goal, st.obst, st.hits, g)
         return self._graphs(st, g)
 
+    def record_state(self, ro, flat, rep) -> BatchState:
+        """the compact state of every (env, t) of an env-major rollout record: flat(x) merges the env and time axes of a
+        per-step field, rep(x) repeats a per-env field over time"""
+        return BatchState(flat(ro.agent), rep(ro.goal), rep(ro.obst), flat(ro.hits))
+
     def _env_states(self, st: BatchState):
         raise NotImplementedError
 

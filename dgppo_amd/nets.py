@@ -111,7 +111,7 @@ class GraphFeats:
         self.cfg, self.G = cfg, G
         n, S = cfg.n_agents, cfg.fan_in
         self.n_other = cfg.num_nodes - 1 - n
-        self.Fp = 8
+        self.Fp = input_width(cfg)
         self.Xa = arena.get(f"{tag}.Xa0", G * n, self.Fp)
         self.Xo = arena.get(f"{tag}.Xo0", max(G * self.n_other, 1), self.Fp)[:G * self.n_other]
         self.efeat = arena.get(f"{tag}.efeat", G * n, S, 4)
@@ -122,6 +122,19 @@ class GraphFeats:
         K.graph_feats(self.cfg, agent, agent_se, agent_st, goal, obst, hits, hits_se, hits_st, env_ids, n_env, n_time,
                       self.Xa, self.Xo if self.n_other > 0 else None, self.efeat, self.emask, self.Fp)
         return self
+
+    def compute_vmas(self, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time):
+        """VMASReverseTransport: agent / body records through strides (floats), scene [B, 8] (dgppo_vmas_graph_feats)"""
+        assert n_env * n_time == self.G
+        K.vmas_graph_feats(self.cfg, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time,
+                           self.Xa, self.efeat, self.emask, self.Fp)
+        return self
+
+
+def input_width(cfg: N.EnvCfg) -> int:
+    """padded width of the layer-0 node rows: 8 for the LiDAR / MPE kinds (node_dim <= 8), ceil4(node_dim) = 20 for
+    VMASReverseTransport"""
+    return _ceil4(cfg.node_dim) if cfg.is_vmas else 8
 
 
 class Net:
@@ -153,7 +166,7 @@ class Net:
         f = cfg.node_dim
         for l in range(gnn_layers):
             d = OUT_DIM if l == gnn_layers - 1 else MSG_DIM
-            fp = 8 if l == 0 else f
+            fp = input_width(cfg) if l == 0 else f
             kp = _ceil4(fp + H_HEADS * (fp + 4) + 1)
             self.dims.append((f, fp, d, kp))
             f = d

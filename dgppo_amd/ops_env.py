@@ -19,12 +19,17 @@ def ray_tables(n_rays: int, device) -> tuple[torch.Tensor, torch.Tensor]:
     return rc, rs
 
 
+def _graph_state_dim(cfg: N.EnvCfg) -> int:
+    """columns of GraphsTuple.states: VMASReverseTransport's nodes carry none (vmas_reverse_transport.py:308)"""
+    return 0 if cfg.is_vmas else cfg.state_dim
+
+
 def alloc_graph(cfg: N.EnvCfg, B: int, device) -> Dict[str, torch.Tensor]:
     Nn, E = cfg.num_nodes, cfg.num_edges
     return dict(
         nodes=torch.empty(B, Nn, cfg.node_dim, device=device),
         edges=torch.empty(B, E, 4, device=device),
-        states=torch.empty(B, Nn, cfg.state_dim, device=device),
+        states=torch.empty(B, Nn, _graph_state_dim(cfg), device=device),
         receivers=torch.empty(B, E, dtype=torch.int32, device=device),
         senders=torch.empty(B, E, dtype=torch.int32, device=device),
         node_type=torch.empty(B, Nn, dtype=torch.int32, device=device),
@@ -37,7 +42,7 @@ def _graph_out(cfg: N.EnvCfg, g: Dict[str, torch.Tensor], B: int) -> N.GraphOut:
     Nn, E = cfg.num_nodes, cfg.num_edges
     N.expect_shape(g["nodes"], (B, Nn, cfg.node_dim), "graph.nodes")
     N.expect_shape(g["edges"], (B, E, 4), "graph.edges")
-    N.expect_shape(g["states"], (B, Nn, cfg.state_dim), "graph.states")
+    N.expect_shape(g["states"], (B, Nn, _graph_state_dim(cfg)), "graph.states")
     N.expect_shape(g["receivers"], (B, E), "graph.receivers")
     N.expect_shape(g["senders"], (B, E), "graph.senders")
     N.expect_shape(g["node_type"], (B, Nn), "graph.node_type")
@@ -134,3 +139,53 @@ def randn(seed: int, offset: int, out: torch.Tensor):
     rc = N.lib().dgppo_randn(C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), C.c_uint64(offset), N.ptr(out, name="out"),
                              C.c_int64(out.numel()), N.stream_ptr())
     N.check(rc, "dgppo_randn")
+
+
+# ---- VMASReverseTransport (include/dgppo_hip.h dgppo_vmas_*): agent [B, n, 4], body [B, 4], scene [B, 8] ------------------
+def _check_vmas(cfg: N.EnvCfg, agent, body, scene, B):
+    if not cfg.is_vmas:
+        raise ValueError(f"env kind {cfg.kind} is not VMASReverseTransport")
+    N.expect_shape(agent, (B, cfg.n_agents, 4), "agent")
+    N.expect_shape(body, (B, 4), "body")
+    N.expect_shape(scene, (B, 8), "scene")
+
+
+def vmas_reset(cfg: N.EnvCfg, seeds: torch.Tensor, agent, body, scene, n_failed: torch.Tensor = None):
+    """dgppo_vmas_reset_checked; n_failed as in env_reset."""
+    B = seeds.shape[0]
+    _check_vmas(cfg, agent, body, scene, B)
+    if n_failed is not None:
+        N.expect_shape(n_failed, (1,), "n_failed")
+    rc = N.lib().dgppo_vmas_reset_checked(C.byref(cfg), N.ptr(seeds, torch.int64, "seeds"), N.ptr(agent, name="agent"),
+                                          N.ptr(body, name="body"), N.ptr(scene, name="scene"),
+                                          N.ptr(n_failed, torch.int32, "n_failed"), C.c_int32(B), N.stream_ptr())
+    N.check(rc, "dgppo_vmas_reset_checked")
+
+
+def vmas_step(cfg: N.EnvCfg, agent, body, scene, action, next_agent, next_body, reward, cost,
+              graph: Optional[Dict[str, torch.Tensor]] = None):
+    """dgppo_vmas_step: reward / cost of the pre-step state, the optional graph of the post-step state."""
+    B = agent.shape[0]
+    _check_vmas(cfg, agent, body, scene, B)
+    n = cfg.n_agents
+    N.expect_shape(action, (B, n, 2), "action")
+    N.expect_shape(next_agent, (B, n, 4), "next_agent")
+    N.expect_shape(next_body, (B, 4), "next_body")
+    N.expect_shape(reward, (B,), "reward")
+    N.expect_shape(cost, (B, n, 2), "cost")
+    go = _graph_out(cfg, graph, B) if graph is not None else None
+    rc = N.lib().dgppo_vmas_step(
+        C.byref(cfg), N.ptr(agent, name="agent"), N.ptr(body, name="body"), N.ptr(scene, name="scene"),
+        N.ptr(action, name="action"), N.ptr(next_agent, name="next_agent"), N.ptr(next_body, name="next_body"),
+        N.ptr(reward, name="reward"), N.ptr(cost, name="cost"), C.byref(go) if go is not None else None, C.c_int32(B),
+        N.stream_ptr())
+    N.check(rc, "dgppo_vmas_step")
+
+
+def vmas_graph_materialize(cfg: N.EnvCfg, agent, body, scene, graph: Dict[str, torch.Tensor]):
+    B = agent.shape[0]
+    _check_vmas(cfg, agent, body, scene, B)
+    go = _graph_out(cfg, graph, B)
+    rc = N.lib().dgppo_vmas_graph_materialize(C.byref(cfg), N.ptr(agent, name="agent"), N.ptr(body, name="body"),
+                                              N.ptr(scene, name="scene"), C.byref(go), C.c_int32(B), N.stream_ptr())
+    N.check(rc, "dgppo_vmas_graph_materialize")

@@ -256,6 +256,35 @@ def graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, goal, obst, hits, hits
     N.check(rc, "dgppo_graph_feats")
 
 
+def vmas_graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time,
+                     Xa, efeat, emask, Fp):
+    """dgppo_vmas_graph_feats: graph_feats for VMASReverseTransport (agent [.., n, 4] and body [.., 4] records addressed
+    through strides in floats, scene [B, 8] dense)."""
+    G = n_env * n_time
+    n = cfg.n_agents
+    N.expect_shape(Xa, (G * n, Fp), "Xa")
+    N.expect_shape(efeat, (G * n, n, 4), "efeat")
+    N.expect_shape(emask, (G * n, n), "emask")
+    for name, t_, se, st, inner in (("agent", agent, agent_se, agent_st, (n, 4)), ("body", body, body_se, body_st, (4,))):
+        if not (t_.is_cuda and t_.dtype == torch.float32):
+            raise ValueError(f"vmas_graph_feats: {name} must be a float32 CUDA tensor")
+        want, acc = [], 1
+        for d in reversed(inner):
+            want.append(acc)
+            acc *= d
+        if tuple(t_.shape[-len(inner):]) != tuple(inner) or list(t_.stride()[-len(inner):]) != want[::-1]:
+            raise ValueError(f"vmas_graph_feats: the trailing {inner} block of {name} must be dense (got shape "
+                             f"{tuple(t_.shape)}, strides {t_.stride()})")
+        avail = t_.untyped_storage().nbytes() // 4 - t_.storage_offset()
+        if env_ids is None and (n_env - 1) * se + (n_time - 1) * st + acc > avail:
+            raise ValueError(f"vmas_graph_feats: {name}: the strides reach beyond its storage")
+    rc = N.lib().dgppo_vmas_graph_feats(
+        C.byref(cfg), C.c_void_p(agent.data_ptr()), C.c_int64(agent_se), C.c_int64(agent_st), C.c_void_p(body.data_ptr()),
+        C.c_int64(body_se), C.c_int64(body_st), _p(scene, "scene"), _p(env_ids, "env_ids", torch.int32), C.c_int32(n_env),
+        C.c_int32(n_time), _p(Xa, "Xa"), _p(efeat, "efeat"), _p(emask, "emask"), C.c_int32(Fp), N.stream_ptr())
+    N.check(rc, "dgppo_vmas_graph_feats")
+
+
 def attn_fwd(cfg, F, H, Kp, qt, Xa, Xo, efeat, emask, zcat, attn, G):
     n, S = cfg.n_agents, cfg.fan_in
     N.expect_shape(qt, (G * n, H * F), "qt")

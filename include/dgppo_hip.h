@@ -42,7 +42,9 @@ enum {
   DGPPO_ENV_MPE_LINE = 6,             /* dgppo/env/mpe/mpe_line.py */
   DGPPO_ENV_MPE_FORMATION = 7,        /* dgppo/env/mpe/mpe_formation.py : 1 landmark node, goals on a circle */
   DGPPO_ENV_MPE_CORRIDOR = 8,         /* dgppo/env/mpe/mpe_corridor.py : two fixed discs, y limit 2 * area */
-  DGPPO_ENV_MPE_CONNECT_SPREAD = 9    /* dgppo/env/mpe/mpe_connect_spread.py : third (connectivity) cost */
+  DGPPO_ENV_MPE_CONNECT_SPREAD = 9,   /* dgppo/env/mpe/mpe_connect_spread.py : third (connectivity) cost */
+  /* contact physics (dgppo/env/vmas/): its own record and entry points (dgppo_vmas_*), see below */
+  DGPPO_ENV_VMAS_REVERSE_TRANSPORT = 10 /* dgppo/env/vmas/vmas_reverse_transport.py */
 };
 /* dgppo_env_cfg.reward_goals: how the n positions the reward measures against follow from the goal nodes */
 enum {
@@ -166,6 +168,49 @@ int32_t dgppo_env_reset(const dgppo_env_cfg* cfg, const uint64_t* seeds,
  * and before launching, densities at which the placement cannot succeed (negative return).                              */
 int32_t dgppo_env_reset_checked(const dgppo_env_cfg* cfg, const uint64_t* seeds, float* agent, float* goal, float* obst,
                                 int32_t* n_failed, int32_t B, void* stream);
+
+/* ---- VMASReverseTransport (dgppo/env/vmas/vmas_reverse_transport.py) ------------------------------------------
+ * n agents (discs of radius 0.03) push a hollow 0.6 x 0.6 box of mass 10 towards a goal past 3 disc obstacles.  The record
+ * differs from the other kinds, so the kind has its own entry points; dgppo_env_step / dgppo_env_reset* /
+ * dgppo_graph_materialize / dgppo_graph_feats refuse it.  cfg: make_env_cfg of kind 10 (n_goals = n_obs = 0: the graph has
+ * only the n agent nodes and the pad, N = n + 1, E = n * n), 1 <= n <= 16, state_dim 4, node_dim 20.
+ *   agent [B, n, 4]  (x, y, vx, vy)                       a_pos | a_vel             vmas_reverse_transport.py:23-29
+ *   body  [B, 4]     (x, y, vx, vy) of the box            box_pos | box_vel
+ *   scene [B, 8]     goal | o0 | o1 | o2 (fixed per episode)  goal_pos | o_pos
+ * Graph nodes (:251-311): [a_pos, a_vel, box_pos, box_vel, goal - box, in_contact, 3 unit vectors box->obstacle, 3
+ * distances], the obstacles stably sorted by distance; graph states have zero columns (nothing is written to gout->states,
+ * which may point to a 0-element buffer).                                                                              */
+
+/* Reset (:90-128, get_node_goal_rng env/utils.py:139-244 without goals).  Philox-4x32-10 keyed by seeds[b] as
+ * dgppo_env_reset; draw d gives two uniforms u0, u1 (words 0, 1 of counter (d, 0, 0, 0)):
+ *   d = 0          box angle (u0, [0, 2 pi)), goal angle noise (u1, [-30, 30) degrees)
+ *   d = 1, 2       obstacle angles: o0 = d1.u0, o1 = d1.u1, o2 = d2.u0 (d2.u1 unused)
+ *   d = 3 .. 2+n   agent velocities: agent i = d(3+i).(u0, u1) in [-0.01, 0.01)
+ *   d = 3+n ...    agent positions: one draw per candidate, rejection sampled in the 0.24 square (<= 1024 tries per
+ *                  agent, <= 64 restarts), then shifted by box - 0.2.
+ * Deviation: the goals that get_node_goal_rng samples next to the agents, and then discards, are not drawn.  n_failed as in
+ * dgppo_env_reset_checked (caller-zeroed device int32, may be NULL).  Densities the placement cannot meet (n > 15) are
+ * refused on the host.                                                                                                 */
+int32_t dgppo_vmas_reset_checked(const dgppo_env_cfg* cfg, const uint64_t* seeds, float* agent, float* body, float* scene,
+                                 int32_t* n_failed, int32_t B, void* stream);
+/* Step (:130-249, physax/world.py:78-163, 361-474, 492-505, physax/geometry.py:8-102): clip the action to [-1, 1], agent
+ * force 0.5 action, 4 world steps x 5 substeps of 0.02 with box-sphere contact forces (agents touch only the box, the box
+ * does not rotate), drag 0.25 at the first substep of each world step, positions clipped to +-1.2.  reward [B] and cost
+ * [B, n, 2] of the PRE-step state (:208-249); gout (optional) = the graph of the post-step state.                        */
+int32_t dgppo_vmas_step(const dgppo_env_cfg* cfg, const float* agent, const float* body, const float* scene,
+                        const float* action, float* next_agent, float* next_body, float* reward, float* cost,
+                        const dgppo_graph_out* gout, int32_t B, void* stream);
+/* GraphsTuple of a stored state (:251-311 get_graph + edge_blocks + to_padded).                                         */
+int32_t dgppo_vmas_graph_materialize(const dgppo_env_cfg* cfg, const float* agent, const float* body, const float* scene,
+                                     const dgppo_graph_out* gout, int32_t B, void* stream);
+/* The networks' view of the same graphs (dgppo_graph_feats for this kind): Xa [G*n, Fp] node rows (20 columns, zero padded
+ * to Fp >= 20), per-(agent, slot) edge features efeat [G*n, n, 4] (x_i - x_s) and masks emask [G*n, n] (0 on the self
+ * slot).  Graph g = e * n_time + t reads agent + env*agent_se + t*agent_st, body + env*body_se + t*body_st and
+ * scene + env*8 (env = env_ids ? env_ids[e] : e).                                                                        */
+int32_t dgppo_vmas_graph_feats(const dgppo_env_cfg* cfg, const float* agent, int64_t agent_se, int64_t agent_st,
+                               const float* body, int64_t body_se, int64_t body_st, const float* scene,
+                               const int32_t* env_ids, int32_t n_env, int32_t n_time, float* Xa, float* efeat, float* emask,
+                               int32_t Fp, void* stream);
 
 /* Standard-normal noise: Philox-4x32-10 + Box-Muller, out[i] for i<n_elem; replaces the
  * jax.random draw inside dist.sample(seed=key) (algo/module/policy.py:196-203).         */

@@ -1,0 +1,302 @@
+"""NumPy fp32 restatement of VMASReverseTransport (test infrastructure; not collected by pytest, never imported by dgppo_amd/).
+
+Follows (file:line relative to the reference repository):
+  dgppo/env/vmas/vmas_reverse_transport.py   state :23-29, constants :35-63, reset :90-128, step :130-206,
+                                             get_reward :208-221, get_cost :223-249, get_a_incontact :251-262,
+                                             get_graph :264-296, edge_blocks :298-311
+  dgppo/env/vmas/physax/world.py             step :78-105, _integrate_state_pos :107-135, _box_sphere_collision :361-474,
+                                             _get_constraint_forces :476-505, update_forcetorque (end of file)
+  dgppo/env/vmas/physax/geometry.py          get_closest_point_line :8-33, get_closest_point_box :36-49,
+                                             get_all_points_box :52-70, get_all_lines_box :73-94
+  dgppo/env/utils.py                         get_node_goal_rng :139-244 (agents only)
+  dgppo/utils/graph.py                       EdgeBlock.make_edges :35-44, GetGraph.to_padded :212-247
+
+Every operation is an fp32 operation in the order of csrc/env_vmas.hip (which is built without fma contraction).  Arrays are
+batched over a leading env axis B: agent [B, n, 4], body [B, 4] (box x, y, vx, vy), scene [B, 8] (goal | o0 | o1 | o2).
+The reset follows the Philox stream documented at dgppo_vmas_reset_checked in include/dgppo_hip.h; JAX's threefry draws of
+the reference cannot be reproduced.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from oracle.env_np import philox4x32, u01
+
+f32 = np.float32
+
+# ---- constants: Python doubles rounded once to fp32, as JAX treats weakly typed scalars ----
+AGENT_RADIUS = f32(0.03)
+HALF_SIDE = f32(0.6 / 2)                      # box_length / 2, geometry.py:77-78
+C90 = np.cos(f32(np.pi / 2))                  # geometry.py:71-72: cos(fp32(pi/2)) = -4.371139e-08
+S90 = np.sin(f32(np.pi / 2))
+DIST_MIN = f32(0.03 + 4 / 6e2)                # radius + Default.LINE_MIN_DIST (world.py:19, 460-463)
+MARGIN = f32(6e-3)                            # contact_margin (vmas_reverse_transport.py:143)
+MIN_DIST = f32(1e-6)                          # world.py:485
+COLLISION_FORCE = f32(500)
+SUB_DT = f32(0.1 / 5)                         # World dt 0.1, substeps 5
+DRAG_KEEP = f32(1 - 0.25)                     # Default.DRAG
+SEMIDIM = f32(1.2)
+BOX_MASS = f32(10.0)
+U_MULT = f32(0.5)
+CONTACT_THR = f32(0.6 - 1e-2)                 # get_a_incontact: package_width - eps
+TWO_AGENT_R = f32(0.03 * 2)
+OBS_R = f32(0.15)
+DIST2GOAL = f32(0.01)
+SUBSTEPS, FRAME_SKIP = 5, 4
+NODE_DIM, EDGE_DIM = 20, 4
+
+# reset (vmas_reverse_transport.py:90-128)
+TWO_PI = f32(2 * np.pi)
+PI = f32(np.pi)
+NOISE = f32(np.deg2rad(30))
+X0_R = f32(0.98 * (0.8 - 0.5 * 0.6))
+OBS_RING = f32(0.98 * (0.8 - 0.5 * 0.6) - 1.5 * 0.15)
+SIDE = f32(0.4 * 0.6)
+SHIFT = f32(0.2)
+MAX_ITER = 1024
+
+
+def norm2(dx, dy):
+    return np.sqrt((dx * dx + dy * dy).astype(f32)).astype(f32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# reset
+# ---------------------------------------------------------------------------------------------------------------------
+class _Stream:
+    def __init__(self, seed):
+        self.key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+        self.d = 0
+
+    def uniform2(self):
+        w = philox4x32((self.d, 0, 0, 0), self.key)
+        self.d += 1
+        return u01(w[0]), u01(w[1])
+
+
+def juniform(u, lo, hi):
+    """jax.random.uniform: max(minval, u * (maxval - minval) + minval)"""
+    lo, hi = f32(lo), f32(hi)
+    return np.maximum(lo, f32(f32(u * f32(hi - lo)) + lo))
+
+
+def reset_uniforms(seed: int, n: int):
+    """the uniforms of draws 0 .. 2 + n: box angle, goal noise, 3 obstacle angles, n agent velocities"""
+    st = _Stream(seed)
+    d0 = st.uniform2()
+    d1 = st.uniform2()
+    d2 = st.uniform2()
+    vel = [st.uniform2() for _ in range(n)]
+    return dict(box=d0[0], goal=d0[1], obs=(d1[0], d1[1], d2[0]), vel=vel), st
+
+
+def reset_single(seed: int, n: int, max_restarts: int = 64):
+    """-> agent [n, 4], body [4], scene [8], placed (bool)"""
+    u, st = reset_uniforms(seed, n)
+    th = juniform(u["box"], 0.0, TWO_PI)
+    gth = f32(f32(th + PI) + juniform(u["goal"], -NOISE, NOISE))
+    bx, by = f32(X0_R * np.cos(th)), f32(X0_R * np.sin(th))
+    scene = np.zeros(8, f32)
+    scene[0], scene[1] = X0_R * np.cos(gth), X0_R * np.sin(gth)
+    for k, uo in enumerate(u["obs"]):
+        oth = juniform(uo, 0.0, TWO_PI)
+        scene[2 + 2 * k], scene[3 + 2 * k] = OBS_RING * np.cos(oth), OBS_RING * np.sin(oth)
+    agent = np.zeros((n, 4), f32)
+    for i, (v0, v1) in enumerate(u["vel"]):
+        agent[i, 2], agent[i, 3] = juniform(v0, -0.01, 0.01), juniform(v1, -0.01, 0.01)
+    # get_node_goal_rng(key, 0.24, 2, n, 0.06) without the goals: zero rows of the work array count (env/utils.py:150-151)
+    placed = False
+    pos = np.zeros((n, 2), f32)
+    for _ in range(max_restarts):
+        pos = np.zeros((n, 2), f32)
+        failed = False
+        for i in range(n):
+            it = 0
+            while True:
+                u0, u1 = st.uniform2()
+                cand = np.array([juniform(u0, 0.0, SIDE), juniform(u1, 0.0, SIDE)], f32)
+                dmin = np.min(norm2(pos[:, 0] - cand[0], pos[:, 1] - cand[1]))
+                if (not (dmin <= TWO_AGENT_R)) or it >= MAX_ITER:
+                    break
+                it += 1
+            pos[i] = cand
+            if it >= MAX_ITER:
+                failed = True
+                break
+        if not failed:
+            placed = True
+            break
+    agent[:, 0] = (pos[:, 0] - SHIFT) + bx
+    agent[:, 1] = (pos[:, 1] - SHIFT) + by
+    return agent, np.array([bx, by, 0, 0], f32), scene, placed
+
+
+def reset(seeds, n: int):
+    out = [reset_single(int(s), n) for s in seeds]
+    return (np.stack([o[0] for o in out]), np.stack([o[1] for o in out]), np.stack([o[2] for o in out]),
+            int(sum(not o[3] for o in out)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# physics
+# ---------------------------------------------------------------------------------------------------------------------
+def _closest_on_line(lx, ly, rx, ry, px, py):
+    """get_closest_point_line (geometry.py:8-33); jnp.sign is 0 at 0"""
+    dx, dy = (lx - px).astype(f32), (ly - py).astype(f32)
+    dot = (f32(dx * rx) + f32(dy * ry)).astype(f32)
+    s = np.sign(dot).astype(f32)
+    dfc = np.minimum(np.abs(dot), HALF_SIDE)
+    sd = (s * dfc).astype(f32)
+    return (lx - sd * rx).astype(f32), (ly - sd * ry).astype(f32)
+
+
+def contact_force(px, py, bx, by):
+    """force on the agent at (px, py) from the hollow box at (bx, by) (any broadcastable shapes) -> fx, fy, active.
+    get_all_lines_box (geometry.py:73-94): sides 1, 2 at box +- (1, 0) * 0.3 along (C90, 1), sides 3, 4 at
+    box +- (C90, 1) * 0.3 along (1, 0); get_closest_point_box keeps the first of equal distances (strict <)."""
+    h1x, h1y = f32(1) * HALF_SIDE, f32(0) * HALF_SIDE
+    h2x, h2y = f32(C90 * HALF_SIDE), f32(S90 * HALF_SIDE)
+    lines = (((bx + h1x), (by + h1y), C90, S90), ((bx - h1x), (by - h1y), C90, S90),
+             ((bx + h2x), (by + h2y), f32(1), f32(0)), ((bx - h2x), (by - h2y), f32(1), f32(0)))
+    shape = np.broadcast(px, bx).shape
+    best = np.full(shape, np.inf, f32)
+    cx = np.full(shape, np.inf, f32)
+    cy = np.full(shape, np.inf, f32)
+    for lx, ly, rx, ry in lines:
+        qx, qy = _closest_on_line(np.asarray(lx, f32), np.asarray(ly, f32), rx, ry, px, py)
+        d = norm2((px - qx).astype(f32), (py - qy).astype(f32))
+        closer = d < best
+        cx, cy, best = np.where(closer, qx, cx), np.where(closer, qy, cy), np.where(closer, d, best)
+    dx, dy = (px - cx).astype(f32), (py - cy).astype(f32)
+    dist = norm2(dx, dy)
+    v = (((DIST_MIN - dist) * f32(1)) / MARGIN).astype(f32)
+    pen = ((np.maximum(f32(0), v) + np.log1p(np.exp(-np.abs(v)))) * MARGIN).astype(f32)   # logaddexp(0, v) * k
+    den = np.where(dist > 0, dist, f32(1e-8)).astype(f32)
+    fx = (((COLLISION_FORCE * dx) / den) * pen).astype(f32)
+    fy = (((COLLISION_FORCE * dy) / den) * pen).astype(f32)
+    off = (dist < MIN_DIST) | (dist > DIST_MIN)
+    fx, fy = np.where(off, f32(0), fx), np.where(off, f32(0), fy)
+    return fx.astype(f32), fy.astype(f32), ~off
+
+
+def physics(agent, body, action):
+    """4 World.step calls of 5 substeps (vmas_reverse_transport.py:150-192, world.py:78-135) -> next agent, next body,
+    contact [B] (a contact force acted in some substep)"""
+    agent, body = agent.astype(f32), body.astype(f32)
+    B, n = agent.shape[:2]
+    u = (np.clip(action.astype(f32), f32(-1), f32(1)) * U_MULT).astype(f32)
+    px, py, vx, vy = (agent[..., k].copy() for k in range(4))
+    bx, by, bvx, bvy = (body[:, k:k + 1].copy() for k in range(4))
+    contact = np.zeros(B, bool)
+    for _ in range(FRAME_SKIP):
+        for s in range(SUBSTEPS):
+            fx, fy, act = contact_force(px, py, bx, by)
+            contact |= act.any(axis=1)
+            Fbx, Fby = -fx[:, 0:1], -fy[:, 0:1]            # the box collects -f of each agent in agent order
+            for j in range(1, n):
+                Fbx, Fby = (Fbx + -fx[:, j:j + 1]).astype(f32), (Fby + -fy[:, j:j + 1]).astype(f32)
+            Fbx, Fby = (f32(0) + Fbx).astype(f32), (f32(0) + Fby).astype(f32)
+            Fax, Fay = (u[..., 0] + fx).astype(f32), (u[..., 1] + fy).astype(f32)
+            if s == 0:                                     # drag at the first substep of each world step
+                vx, vy = (vx * DRAG_KEEP).astype(f32), (vy * DRAG_KEEP).astype(f32)
+                bvx, bvy = (bvx * DRAG_KEEP).astype(f32), (bvy * DRAG_KEEP).astype(f32)
+            vx = (vx + (Fax / f32(1)) * SUB_DT).astype(f32)
+            vy = (vy + (Fay / f32(1)) * SUB_DT).astype(f32)
+            px = np.clip((px + vx * SUB_DT).astype(f32), -SEMIDIM, SEMIDIM)
+            py = np.clip((py + vy * SUB_DT).astype(f32), -SEMIDIM, SEMIDIM)
+            bvx = (bvx + (Fbx / BOX_MASS) * SUB_DT).astype(f32)
+            bvy = (bvy + (Fby / BOX_MASS) * SUB_DT).astype(f32)
+            bx = np.clip((bx + bvx * SUB_DT).astype(f32), -SEMIDIM, SEMIDIM)
+            by = np.clip((by + bvy * SUB_DT).astype(f32), -SEMIDIM, SEMIDIM)
+    nagent = np.stack([px, py, vx, vy], -1).astype(f32)
+    nbody = np.concatenate([bx, by, bvx, bvy], -1).astype(f32)
+    return nagent, nbody, contact
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# reward, cost, graph
+# ---------------------------------------------------------------------------------------------------------------------
+def get_reward(body, scene):
+    """vmas_reverse_transport.py:208-221 -> [B]"""
+    dg = norm2((scene[:, 0] - body[:, 0]).astype(f32), (scene[:, 1] - body[:, 1]).astype(f32))
+    r = ((-dg) * f32(0.01)).astype(f32)
+    return (r - np.where(dg > DIST2GOAL, f32(1), f32(0)) * f32(0.001)).astype(f32)
+
+
+def cost_margins(agent, body, scene):
+    """the two columns of get_cost before margin and clip (vmas_reverse_transport.py:223-245) -> [B, n, 2]"""
+    B, n = agent.shape[:2]
+    d = norm2((agent[:, :, None, 0] - agent[:, None, :, 0]).astype(f32), (agent[:, :, None, 1] - agent[:, None, :, 1]).astype(f32))
+    d = (d + np.eye(n, dtype=f32) * f32(1e6)).astype(f32)
+    mind = d.min(axis=2)
+    od = np.stack([norm2((body[:, 0] - scene[:, 2 + 2 * k]).astype(f32), (body[:, 1] - scene[:, 3 + 2 * k]).astype(f32))
+                   for k in range(3)], -1)
+    mino = od.min(axis=1)
+    c0 = (f32(4) * (TWO_AGENT_R - mind)).astype(f32)
+    c1 = np.broadcast_to((f32(2) * (OBS_R - mino)).astype(f32)[:, None], (B, n))
+    return np.stack([c0, c1], -1).astype(f32)
+
+
+def get_cost(agent, body, scene):
+    """vmas_reverse_transport.py:223-249 -> [B, n, 2]: margin +-0.5, clip to [-1, 1]"""
+    c = cost_margins(agent, body, scene)
+    c = np.where(c <= 0, c - f32(0.5), c + f32(0.5)).astype(f32)
+    return np.clip(c, f32(-1), f32(1)).astype(f32)
+
+
+def obstacle_order(body, scene):
+    """distances sqrt(|o - box|^2 + 1e-6) [B, 3] and the stable argsort of them (jnp.argsort is stable)"""
+    rx = np.stack([(scene[:, 2 + 2 * k] - body[:, 0]).astype(f32) for k in range(3)], -1)
+    ry = np.stack([(scene[:, 3 + 2 * k] - body[:, 1]).astype(f32) for k in range(3)], -1)
+    d = np.sqrt(((rx * rx + ry * ry).astype(f32) + f32(1e-6)).astype(f32)).astype(f32)
+    return rx, ry, d, np.argsort(d, axis=1, kind="stable")
+
+
+def node_feats(agent, body, scene):
+    """get_graph node features (vmas_reverse_transport.py:264-289) -> [B, n, 20]"""
+    B, n = agent.shape[:2]
+    X = np.zeros((B, n, NODE_DIM), f32)
+    X[..., 0:4] = agent
+    X[..., 4:8] = body[:, None, :]
+    X[..., 8] = (scene[:, 0] - body[:, 0])[:, None]
+    X[..., 9] = (scene[:, 1] - body[:, 1])[:, None]
+    rel = (agent[..., :2] - body[:, None, :2]).astype(f32)
+    X[..., 10] = np.any(np.abs(rel) > CONTACT_THR, axis=-1).astype(f32)    # the 0.59 threshold, as written (:258-262)
+    rx, ry, d, idx = obstacle_order(body, scene)
+    vx, vy = (rx / d).astype(f32), (ry / d).astype(f32)
+    for r in range(3):
+        k = idx[:, r]
+        X[..., 11 + 2 * r] = vx[np.arange(B), k][:, None]
+        X[..., 12 + 2 * r] = vy[np.arange(B), k][:, None]
+        X[..., 17 + r] = d[np.arange(B), k][:, None]
+    return X
+
+
+def edge_feats(agent):
+    """agent-agent EdgeBlock (vmas_reverse_transport.py:298-311): [B, n, n, 4] = state_i - state_j, mask = i != j"""
+    n = agent.shape[1]
+    return (agent[:, :, None, :] - agent[:, None, :, :]).astype(f32), ~np.eye(n, dtype=bool)
+
+
+def get_graph(agent, body, scene):
+    """padded GraphsTuple (graph.py:35-44, 212-247): N = n + 1 nodes, E = n^2 edges, states with zero columns"""
+    B, n = agent.shape[:2]
+    nodes = np.zeros((B, n + 1, NODE_DIM), f32)
+    nodes[:, :n] = node_feats(agent, body, scene)
+    ef, mask = edge_feats(agent)
+    ids = np.arange(n, dtype=np.int32)
+    recv = np.where(mask, ids[:, None], n).reshape(-1).astype(np.int32)
+    send = np.where(mask, ids[None, :], n).reshape(-1).astype(np.int32)
+    node_type = np.zeros(n + 1, np.int32)
+    node_type[n] = -1
+    return dict(nodes=nodes, edges=ef.reshape(B, n * n, 4), states=np.zeros((B, n + 1, 0), f32),
+                receivers=np.broadcast_to(recv, (B, n * n)).copy(), senders=np.broadcast_to(send, (B, n * n)).copy(),
+                node_type=np.broadcast_to(node_type, (B, n + 1)).copy(), n_node=np.full(B, n + 1, np.int32),
+                n_edge=np.full(B, n * n, np.int32))
+
+
+def env_step(agent, body, scene, action):
+    """VMASReverseTransport.step (:130-206): reward and cost of the pre-step state, the graph of the post-step state"""
+    nagent, nbody, contact = physics(agent, body, action)
+    return dict(next_agent=nagent, next_body=nbody, reward=get_reward(body, scene), cost=get_cost(agent, body, scene),
+                graph=get_graph(nagent, nbody, scene), contact=contact)
