@@ -31,8 +31,8 @@ class _LazyGraphs:
         if self._g is None:
             ro, T, off = self._ro.finalize(), self._ro.T, self._off
             B = ro.B
-            flat = lambda x: None if x is None else x[:, off:off + T].reshape((B * T,) + x.shape[2:]).contiguous()
-            rep = lambda x: None if x is None else x.repeat_interleave(T, dim=0)
+            flat = lambda x: x[:, off:off + T].reshape((B * T,) + x.shape[2:]).contiguous()
+            rep = lambda x: x.repeat_interleave(T, dim=0)
             g = self._env.graph_batch(self._env.record_state(ro, flat, rep))
             unf = lambda x: x.view((B, T) + x.shape[1:]) if torch.is_tensor(x) else x
             es = g.env_states
@@ -175,7 +175,7 @@ class DGPPO(Algorithm):
         env, cfg = self._env, self._env.cfg
         st = env._state_of(graph)
         n = cfg.n_agents
-        feats = self.engine._feats_of_state("one", st, 1)
+        feats = self.engine._feats("one", st, 1)
         h0 = self._pack_carry(rnn_state)
         hs = torch.empty(n, self.engine.HC, device=self.device)
         act = self.engine.policy.forward(feats, n_seq=n, T=1, h0=h0, tag="one", hs_out=hs, train=False)

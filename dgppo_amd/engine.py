@@ -56,24 +56,30 @@ class RolloutData:
     """Compact rollout record (SURVEY §7 'compact rollout storage'): time-major while collecting, env-major afterwards."""
 
     def __init__(self, cfg: N.EnvCfg, B: int, T: int, device, stochastic: bool, carry_dim: int = nets.HID):
-        n, sd = cfg.n_agents, cfg.state_dim
+        n = cfg.n_agents
         self.cfg, self.B, self.T, self.stochastic = cfg, B, T, stochastic
-        self.has_hits = cfg.is_lidar and cfg.n_obs > 0
-        self.vmas = cfg.is_vmas
         z = lambda *s: torch.empty(*s, device=device)
-        self.agent_tm = z(T + 1, B, n, sd)
-        self.hits_tm = z(T + 1, B, n, cfg.top_k, 2) if self.has_hits else None
-        # VMASReverseTransport: the box (x, y, vx, vy) per step and the goal | 3 obstacle centres per env
-        self.body_tm = z(T + 1, B, 4) if self.vmas else None
-        self.scene = z(B, 8) if self.vmas else None
-        self.goal = z(B, cfg.n_goals, sd)
-        self.obst = z(B, cfg.n_obs, cfg.obst_stride) if cfg.n_obs > 0 else None
+        # the env state (ops_env.record_fields): step_tm / step hold the per-step fields time-major [T+1, B, ...] / env-major
+        # [B, T+1, ...] (after finalize()), env the per-env ones [B, ...].  Each is also an attribute (agent_tm, hits_tm,
+        # body_tm; agent, hits, body; goal, obst, scene), None where the kind has no such field.
+        step, env = OE.record_fields(cfg)
+        self.step_tm = {k: z(T + 1, B, *shape) for k, shape in step.items()}
+        self.env = {k: z(B, *shape) for k, shape in env.items()}
+        self.step: Dict[str, torch.Tensor] = {}
+        for k in OE.STEP_FIELDS:
+            setattr(self, k + "_tm", self.step_tm.get(k))
+            setattr(self, k, None)
+        for k in OE.ENV_FIELDS:
+            setattr(self, k, self.env.get(k))
         self.action_tm = z(T, B, n, 2)
         self.log_pi_tm = z(T, B, n) if stochastic else None
         self.rnn_tm = z(T + 1, B, n, carry_dim)          # packed actor carry [h_0 | h_1 | ...] of the stacked cells
         self.reward_tm = z(T, B)
         self.cost_tm = z(T, B, n, cfg.n_cost)
         self._env_major = False
+        # the env state of every step of the time-major record (views, made once: the rollout loop is bound by its host side)
+        views = {k: v.unbind(0) for k, v in self.step_tm.items()}
+        self.states_tm = [OE.State({k: v[t] for k, v in views.items()}, self.env) for t in range(T + 1)]
 
     def finalize(self):
         """time-major -> env-major copies (pure data movement).  The env-major buffers are allocated once per record and
@@ -90,9 +96,9 @@ class RolloutData:
                 cur = torch.empty(want, device=x.device, dtype=x.dtype)
             cur.copy_(x.transpose(0, 1))
             return cur
-        self.agent = tr("agent", self.agent_tm)                       # [B, T+1, n, sd]
-        self.hits = tr("hits", self.hits_tm) if self.has_hits else None
-        self.body = tr("body", self.body_tm) if self.vmas else None       # [B, T+1, 4]
+        for k, v in self.step_tm.items():                             # agent [B, T+1, n, sd], hits [B, T+1, n, k, 2], ...
+            self.step[k] = tr(k, v)
+            setattr(self, k, self.step[k])
         self.actions = tr("actions", self.action_tm)                  # [B, T, n, 2]
         self.log_pis = tr("log_pis", self.log_pi_tm) if self.stochastic else None
         self._rnn_em = tr("_rnn_em", self.rnn_tm)                     # [B, T+1, n, 64]
@@ -172,7 +178,6 @@ class Engine:
         assert self.world >= 1 and (allreduce is not None or self.world == 1), "world > 1 needs an allreduce"
         assert 0 <= self.rank < self.world, f"rank {rank} outside world {world}"
         self.prepass_graphs = int(os.environ.get("DGPPO_PREPASS_GRAPHS", prepass_graphs))      # tuning override
-        self.ray_cos, self.ray_sin = (OE.ray_tables(cfg.n_rays, device) if cfg.is_lidar else (None, None))
         self.lam_pow = OA.lam_pow_table(hyper.gae_lambda, T, device)
         # the constant entropy noise of SURVEY A.7 (distribution.py:40: seed drawn once at trace time)
         self.eps_hat = torch.zeros(cfg.n_agents, 2, device=device)
@@ -195,35 +200,18 @@ class Engine:
     # ------------------------------------------------------------------------------------------------------------------
     # rollout
     # ------------------------------------------------------------------------------------------------------------------
-    def _feats_at(self, tag, agent_slab, hits_slab, goal, obst, B):
-        """graph features of B dense [B, n, sd] states."""
-        cfg = self.cfg
-        f = nets.GraphFeats(cfg, B, self.arena, tag)
-        n, sd = cfg.n_agents, cfg.state_dim
-        f.compute(agent_slab, n * sd, 0, goal, obst, hits_slab, n * cfg.top_k * 2, 0, None, B, 1)
-        return f
-
-    def _feats_vmas(self, tag, agent_slab, body_slab, scene, B):
-        """VMASReverseTransport: graph features of B dense [B, n, 4] / [B, 4] states"""
-        f = nets.GraphFeats(self.cfg, B, self.arena, tag)
-        return f.compute_vmas(agent_slab, self.cfg.n_agents * 4, 0, body_slab, 4, 0, scene, None, B, 1)
-
-    def _feats_of_state(self, tag, st, B):
-        """graph features of a batched env state (BatchState, or VMASBatchState for VMASReverseTransport)"""
-        if self.cfg.is_vmas:
-            return self._feats_vmas(tag, st.agent, st.body, st.scene, B)
-        return self._feats_at(tag, st.agent, st.hits, st.goal, st.obst, B)
+    def _feats(self, tag, st: OE.State, n_env, n_time=1, slots=1, env_ids=None):
+        """graph features of n_env x n_time states: dense [n_env, ...] states, or (slots = T + 1) the env-major record from
+        st's first (env, step) on, of the envs env_ids if given"""
+        f = nets.GraphFeats(self.cfg, n_env * n_time, self.arena, tag)
+        return f.compute_record(st.step, slots, st.env, env_ids, n_env, n_time)
 
     def _rollout_steps(self, ro: RolloutData, eps, B: int, stochastic: bool):
         """the T env steps of a rollout: policy forward (GNN + GRU + head) and env.step, all on the current stream."""
         cfg, T, n = self.cfg, self.T, self.cfg.n_agents
         tag = "ro" if stochastic else "rod"    # separate scratch per kind: the two rollouts may run on different streams
         for t in range(T):
-            hits_t = ro.hits_tm[t] if ro.has_hits else None
-            if ro.vmas:
-                feats = self._feats_vmas(tag, ro.agent_tm[t], ro.body_tm[t], ro.scene, B)
-            else:
-                feats = self._feats_at(tag, ro.agent_tm[t], hits_t, ro.goal, ro.obst, B)
+            feats = self._feats(tag, ro.states_tm[t], B)
             act = self.policy.forward(feats, n_seq=B * n, T=1, h0=ro.rnn_tm[t].view(B * n, self.HC), tag=tag,
                                       hs_out=ro.rnn_tm[t + 1].view(B * n, self.HC), train=False)
             a_t = ro.action_tm[t].view(B * n, 2)
@@ -231,12 +219,7 @@ class Engine:
                 K.policy_head(act["ms"], eps[t], None, a_t, ro.log_pi_tm[t].view(B * n), None, n, 0)
             else:
                 K.policy_head(act["ms"], None, None, a_t, None, None, n, 1)
-            if ro.vmas:
-                OE.vmas_step(cfg, ro.agent_tm[t], ro.body_tm[t], ro.scene, ro.action_tm[t], ro.agent_tm[t + 1],
-                             ro.body_tm[t + 1], ro.reward_tm[t], ro.cost_tm[t], None)
-                continue
-            OE.env_step(cfg, ro.agent_tm[t], ro.action_tm[t], ro.goal, ro.obst, hits_t, self.ray_cos, self.ray_sin,
-                        ro.agent_tm[t + 1], ro.hits_tm[t + 1] if ro.has_hits else None, ro.reward_tm[t], ro.cost_tm[t], None)
+            OE.step(cfg, ro.states_tm[t], ro.action_tm[t], ro.states_tm[t + 1], ro.reward_tm[t], ro.cost_tm[t])
 
     def rollout(self, seeds: torch.Tensor, stochastic: bool, noise_seed: int = 0) -> RolloutData:
         cfg, T = self.cfg, self.T
@@ -252,13 +235,7 @@ class Engine:
             ro._env_major = False
         else:
             ro = RolloutData(cfg, B, T, self.device, stochastic, self.HC)
-        if ro.vmas:
-            OE.vmas_reset(cfg, seeds, ro.agent_tm[0], ro.body_tm[0], ro.scene, self.reset_failed)
-        else:
-            OE.env_reset(cfg, seeds, ro.agent_tm[0], ro.goal, ro.obst, self.reset_failed)
-        if ro.has_hits:
-            OE.env_step(cfg, ro.agent_tm[0], None, ro.goal, ro.obst, None, self.ray_cos, self.ray_sin, None, ro.hits_tm[0],
-                        None, None, None)
+        OE.reset(cfg, seeds, ro.states_tm[0], self.reset_failed)         # with the sense pass that fills hits_tm[0]
         ro.rnn_tm[0].zero_()                                   # init_rnn_state = zeros (informarl.py:115-124)
         eps = None
         if stochastic:
@@ -330,23 +307,10 @@ class Engine:
     # value pre-passes (dgppo.py:204-229, 262-264)
     # ------------------------------------------------------------------------------------------------------------------
     def _block_feats(self, tag, ro: RolloutData, e0, Eb, t0, n_time, env_ids=None):
-        cfg = self.cfg
-        n, sd, T1 = cfg.n_agents, cfg.state_dim, self.T + 1
-        f = nets.GraphFeats(cfg, Eb * n_time, self.arena, tag)
-        agent = ro.agent[e0:, t0] if env_ids is None else ro.agent[:, t0]
-        if ro.vmas:
-            body = ro.body[e0:, t0] if env_ids is None else ro.body[:, t0]
-            scene = ro.scene[e0:] if env_ids is None else ro.scene
-            return f.compute_vmas(agent, T1 * n * sd, n * sd, body, T1 * 4, 4, scene, env_ids, Eb, n_time)
-        hits = None
-        if ro.has_hits:
-            hits = ro.hits[e0:, t0] if env_ids is None else ro.hits[:, t0]
-        goal = ro.goal[e0:] if env_ids is None else ro.goal
-        obst = None
-        if ro.obst is not None:
-            obst = ro.obst[e0:] if env_ids is None else ro.obst
-        f.compute(agent, T1 * n * sd, n * sd, goal, obst, hits, T1 * n * cfg.top_k * 2, n * cfg.top_k * 2, env_ids, Eb, n_time)
-        return f
+        """features of steps t0 .. t0 + n_time - 1 of Eb envs of the env-major record: envs e0 .. e0 + Eb - 1, or env_ids"""
+        envs = slice(e0, None) if env_ids is None else slice(None)
+        st = OE.State({k: v[envs, t0] for k, v in ro.step.items()}, {k: v[envs] for k, v in ro.env.items()})
+        return self._feats(tag, st, Eb, n_time, self.T + 1, env_ids)
 
     def values_prepass(self, ro: RolloutData, want_Vl: bool, want_Vh: bool = True):
         """-> Vl [B,T+1] (or None), Vh [B,T+1,n,nh] of one rollout, with the reference's carry conventions."""
@@ -410,19 +374,10 @@ class Engine:
         cfg, T, B, hp = self.cfg, self.T, ro.B, self.hp
         n, nh, dev = cfg.n_agents, self.n_cost, self.device
         Vl, _ = self.values_prepass(ro, want_Vl=True, want_Vh=False)
-        fin_agent = ro.agent[:, T].contiguous()
-        fin_hits = ro.hits[:, T].contiguous() if ro.has_hits else None
+        fin = OE.State({k: v[:, T].contiguous() for k, v in ro.step.items()}, ro.env)
         A = self.arena
         fin_cost = A.get("tg.fin_cost", B, n, nh)
-        scratch_agent = torch.empty_like(fin_agent)
-        if ro.vmas:
-            fin_body = ro.body[:, T].contiguous()
-            OE.vmas_step(cfg, fin_agent, fin_body, ro.scene, torch.zeros(B, n, 2, device=dev), scratch_agent,
-                         torch.empty_like(fin_body), torch.empty(B, device=dev), fin_cost, None)
-        else:
-            OE.env_step(cfg, fin_agent, torch.zeros(B, n, 2, device=dev), ro.goal, ro.obst, fin_hits, self.ray_cos,
-                        self.ray_sin, scratch_agent, torch.empty_like(fin_hits) if fin_hits is not None else None,
-                        torch.empty(B, device=dev), fin_cost, None)
+        OE.step(cfg, fin, torch.zeros(B, n, 2, device=dev), fin.like(), torch.empty(B, device=dev), fin_cost)
         Vh = A.get("tg.Vh.crafted", B, T + 1, n, nh)
         Vh[:, :T].copy_(ro.costs)
         Vh[:, T].copy_(fin_cost)

@@ -22,14 +22,6 @@ class StepResult(NamedTuple):
     info: dict
 
 
-class BatchState(NamedTuple):
-    """compact batched env state (device tensors)."""
-    agent: torch.Tensor            # [B, n, sd]
-    goal: torch.Tensor             # [B, n, sd]
-    obst: Optional[torch.Tensor]   # LiDAR: [B, n_obs, 16] rectangle records; MPE: [B, n_obs, sd]
-    hits: Optional[torch.Tensor]   # LiDAR: [B, n, k, 2]
-
-
 class MultiAgentEnv(ABC):
     PARAMS: dict = {}
     KIND: str = ""
@@ -51,7 +43,6 @@ class MultiAgentEnv(ABC):
         p["n_obs"] = self.cfg.n_obs
         if not self.cfg.is_lidar:
             p["obs_radius"] = float(np.float32(self.cfg.obs_radius)) if "obs_radius" not in p else p["obs_radius"]
-        self._ray = None
 
     # ---- reference attribute surface ----
     @property
@@ -125,72 +116,47 @@ class MultiAgentEnv(ABC):
         return torch.clamp(action, -1.0, 1.0)
 
     # ---- batched interface (what the engine uses) ----
-    def _rays(self):
-        if self._ray is None and self.cfg.is_lidar:
-            self._ray = OE.ray_tables(self.cfg.n_rays, self.device)
-        return self._ray if self._ray is not None else (None, None)
-
-    @property
-    def _has_hits(self):
-        return self.cfg.is_lidar and self.cfg.n_obs > 0
-
     def reset_batch(self, seeds, want_graph: bool = False):
-        """seeds: int64 tensor / array [B] -> BatchState (and the GraphsTuple batch if asked)."""
+        """seeds: int64 tensor / array [B] -> ops_env.State (and the GraphsTuple batch if asked)."""
         cfg, dev = self.cfg, self.device
         seeds = torch.as_tensor(np.asarray(seeds, dtype=np.int64) if not torch.is_tensor(seeds) else seeds).to(dev)
         B = int(seeds.shape[0])
-        n, sd = cfg.n_agents, cfg.state_dim
-        agent = torch.empty(B, n, sd, device=dev)
-        goal = torch.empty(B, cfg.n_goals, sd, device=dev)
-        obst = torch.empty(B, cfg.n_obs, cfg.obst_stride, device=dev) if cfg.n_obs > 0 else None
+        st = OE.State.empty(cfg, B, dev)
         n_failed = torch.zeros(1, dtype=torch.int32, device=dev)
-        OE.env_reset(cfg, seeds, agent, goal, obst, n_failed)
+        g = OE.alloc_graph(cfg, B, dev) if want_graph else None
+        OE.reset(cfg, seeds, st, n_failed, g)
         if int(n_failed.item()):       # the API path may sync: an invalid scene never leaves reset()
             raise RuntimeError(f"env reset: {int(n_failed.item())} of {B} scenes could not be placed within the kernels' "
                                f"rejection-loop bounds (too many agents / obstacles for the area?)")
-        hits, g = None, None
-        rc, rs = self._rays()
-        if self._has_hits or want_graph:
-            hits = torch.empty(B, n, cfg.top_k, 2, device=dev) if self._has_hits else None
-            g = OE.alloc_graph(cfg, B, dev) if want_graph else None
-            if self._has_hits:
-                OE.env_step(cfg, agent, None, goal, obst, None, rc, rs, None, hits, None, None, g)
-            else:
-                OE.graph_materialize(cfg, agent, goal, obst, None, g)
-        st = BatchState(agent, goal, obst, hits)
         return (st, self._graphs(st, g)) if want_graph else st
 
-    def step_batch(self, st: BatchState, action: torch.Tensor, want_graph: bool = False):
-        """-> (next BatchState, reward [B], cost [B,n,2][, GraphsTuple batch])."""
+    def step_batch(self, st: OE.State, action: torch.Tensor, want_graph: bool = False):
+        """-> (next State, reward [B] and cost [B, n, n_cost] of the pre-step state[, GraphsTuple batch of the next state])."""
         cfg, dev = self.cfg, self.device
         B = st.agent.shape[0]
-        n = cfg.n_agents
-        nx = torch.empty_like(st.agent)
-        nh = torch.empty_like(st.hits) if st.hits is not None else None
+        nst = st.like()
         rew = torch.empty(B, device=dev)
-        cost = torch.empty(B, n, cfg.n_cost, device=dev)
+        cost = torch.empty(B, cfg.n_agents, cfg.n_cost, device=dev)
         g = OE.alloc_graph(cfg, B, dev) if want_graph else None
-        rc, rs = self._rays()
-        OE.env_step(cfg, st.agent, action.contiguous(), st.goal, st.obst, st.hits, rc, rs, nx, nh, rew, cost, g)
-        nst = BatchState(nx, st.goal, st.obst, nh)
+        OE.step(cfg, st, action.contiguous(), nst, rew, cost, g)
         if want_graph:
             return nst, rew, cost, self._graphs(nst, g)
         return nst, rew, cost
 
-    def graph_batch(self, st: BatchState) -> GraphsTuple:
+    def graph_batch(self, st: OE.State) -> GraphsTuple:
         g = OE.alloc_graph(self.cfg, st.agent.shape[0], self.device)
-        OE.graph_materialize(self.cfg, st.agent, st.goal, st.obst, st.hits, g)
+        OE.materialize(self.cfg, st, g)
         return self._graphs(st, g)
 
-    def record_state(self, ro, flat, rep) -> BatchState:
+    def record_state(self, ro, flat, rep) -> OE.State:
         """the compact state of every (env, t) of an env-major rollout record: flat(x) merges the env and time axes of a
         per-step field, rep(x) repeats a per-env field over time"""
-        return BatchState(flat(ro.agent), rep(ro.goal), rep(ro.obst), flat(ro.hits))
+        return OE.State({k: flat(v) for k, v in ro.step.items()}, {k: rep(v) for k, v in ro.env.items()})
 
-    def _env_states(self, st: BatchState):
+    def _env_states(self, st: OE.State):
         raise NotImplementedError
 
-    def _graphs(self, st: BatchState, g: dict) -> GraphsTuple:
+    def _graphs(self, st: OE.State, g: dict) -> GraphsTuple:
         return GraphsTuple(g["n_node"], g["n_edge"], g["nodes"], g["edges"], g["states"], g["receivers"], g["senders"],
                            g["node_type"], self._env_states(st), None)
 
@@ -208,7 +174,7 @@ class MultiAgentEnv(ABC):
         _, g = self.reset_batch(np.array([seed], dtype=np.int64), want_graph=True)
         return self._squeeze(g)
 
-    def _state_of(self, graph: GraphsTuple) -> BatchState:
+    def _state_of(self, graph: GraphsTuple) -> OE.State:
         raise NotImplementedError
 
     def step(self, graph: GraphsTuple, action, get_eval_info: bool = False) -> StepResult:
@@ -222,7 +188,7 @@ class MultiAgentEnv(ABC):
         zero = torch.zeros(1, self.num_agents, 2, device=self.device)
         return self.step_batch(st, zero)[2][0]                # cost is a function of the pre-step graph only
 
-    def _batch_of_env_state(self, env_state, lidar_data) -> BatchState:
+    def _batch_of_env_state(self, env_state, lidar_data) -> OE.State:
         raise NotImplementedError
 
     def get_graph(self, env_state, lidar_data=None) -> GraphsTuple:
@@ -231,11 +197,8 @@ class MultiAgentEnv(ABC):
         env with obstacles `lidar_data` are the top-k hit points, [n, k, 2] (or merged [n * k, 2]) as `get_lidar_vmap`
         returns them; when omitted they are sensed from the state first."""
         st = self._batch_of_env_state(env_state, lidar_data)
-        if self._has_hits and st.hits is None:
-            hits = torch.empty(1, self.num_agents, self.cfg.top_k, 2, device=self.device)
-            rc, rs = self._rays()
-            OE.env_step(self.cfg, st.agent, None, st.goal, st.obst, None, rc, rs, None, hits, None, None, None)
-            st = BatchState(st.agent, st.goal, st.obst, hits)
+        if st.hits is None and "hits" in OE.record_fields(self.cfg)[0]:
+            OE.sense(self.cfg, st)
         return self._squeeze(self.graph_batch(st))
 
     def render_video(self, rollout, video_path, Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100, **kwargs):

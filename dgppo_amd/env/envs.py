@@ -7,7 +7,8 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from .base import BatchState, MultiAgentEnv
+from .base import MultiAgentEnv
+from ..ops_env import State
 from ..utils.graph import GraphsTuple
 
 
@@ -60,10 +61,10 @@ class _LidarEnv(MultiAgentEnv):
     PARAMS = {"car_radius": 0.05, "comm_radius": 0.5, "n_rays": 32, "obs_len_range": [0.1, 0.3], "n_obs": 3,
               "default_area_size": 1.5, "dist2goal": 0.01, "top_k_rays": 8}
 
-    def _env_states(self, st: BatchState):
+    def _env_states(self, st: State):
         return LidarEnvState(st.agent, st.goal, _rect_from_records(st.obst) if st.obst is not None else None)
 
-    def _state_of(self, graph: GraphsTuple) -> BatchState:
+    def _state_of(self, graph: GraphsTuple) -> State:
         n, k = self.num_agents, self.cfg.top_k
         es = graph.env_states
         states = graph.states
@@ -74,10 +75,10 @@ class _LidarEnv(MultiAgentEnv):
         if self.cfg.n_obs > 0:
             obst = _records_from_rect(es.obstacle).reshape(1, self.cfg.n_obs, 16).contiguous()
             hits = states[..., n + ng:n + ng + n * k, :2].reshape(1, n, k, 2).contiguous()
-        return BatchState(agent, goal, obst, hits)
+        return State(dict(agent=agent, hits=hits), dict(goal=goal, obst=obst))
 
 
-    def _batch_of_env_state(self, env_state: LidarEnvState, lidar_data) -> BatchState:
+    def _batch_of_env_state(self, env_state: LidarEnvState, lidar_data) -> State:
         n, ng, sd, dev = self.num_agents, self.cfg.n_goals, self.state_dim, self.device
         f = lambda x, *shape: torch.as_tensor(x, dtype=torch.float32, device=dev).reshape(*shape).contiguous()
         obst = hits = None
@@ -86,7 +87,7 @@ class _LidarEnv(MultiAgentEnv):
                                                   for v in env_state.obstacle])).reshape(1, self.cfg.n_obs, 16).contiguous()
             if lidar_data is not None:
                 hits = f(lidar_data, 1, n, self.cfg.top_k, 2)
-        return BatchState(f(env_state.agent, 1, n, sd), f(env_state.goal, 1, ng, sd), obst, hits)
+        return State(dict(agent=f(env_state.agent, 1, n, sd), hits=hits), dict(goal=f(env_state.goal, 1, ng, sd), obst=obst))
 
 
 class LidarSpread(_LidarEnv):
@@ -109,24 +110,24 @@ class _MPE(MultiAgentEnv):
     PARAMS = {"car_radius": 0.05, "comm_radius": 0.5, "n_obs": 3, "obs_radius": 0.05, "default_area_size": 1.5,
               "dist2goal": 0.01}
 
-    def _env_states(self, st: BatchState):
+    def _env_states(self, st: State):
         return MPEEnvState(st.agent, st.goal, st.obst)
 
-    def _state_of(self, graph: GraphsTuple) -> BatchState:
+    def _state_of(self, graph: GraphsTuple) -> State:
         n = self.num_agents
         states = graph.states
         ng = self.cfg.n_goals
         agent = states[..., :n, :].reshape(1, n, 4).contiguous()
         goal = states[..., n:n + ng, :].reshape(1, ng, 4).contiguous()
         obst = states[..., n + ng:n + ng + self.cfg.n_obs, :].reshape(1, self.cfg.n_obs, 4).contiguous() if self.cfg.n_obs > 0 else None
-        return BatchState(agent, goal, obst, None)
+        return State(dict(agent=agent), dict(goal=goal, obst=obst))
 
 
-    def _batch_of_env_state(self, env_state: MPEEnvState, lidar_data=None) -> BatchState:
+    def _batch_of_env_state(self, env_state: MPEEnvState, lidar_data=None) -> State:
         n, ng, dev = self.num_agents, self.cfg.n_goals, self.device
         f = lambda x, *shape: torch.as_tensor(x, dtype=torch.float32, device=dev).reshape(*shape).contiguous()
         obst = f(env_state.obs, 1, self.cfg.n_obs, 4) if self.cfg.n_obs > 0 else None
-        return BatchState(f(env_state.agent, 1, n, 4), f(env_state.goal, 1, ng, 4), obst, None)
+        return State(dict(agent=f(env_state.agent, 1, n, 4)), dict(goal=f(env_state.goal, 1, ng, 4), obst=obst))
 
 
 class MPESpread(_MPE):

@@ -13,7 +13,7 @@ import torch
 from .. import _native as N
 from .. import ops_env as OE
 from ..utils.graph import GraphsTuple
-from .base import MultiAgentEnv, StepResult
+from .base import MultiAgentEnv
 
 
 class VMASReverseTransportState(NamedTuple):
@@ -26,14 +26,6 @@ class VMASReverseTransportState(NamedTuple):
     o_pos: torch.Tensor
 
 
-class VMASBatchState(NamedTuple):
-    """compact batched record (device tensors): agent [B, n, 4], body [B, 4] (box x, y, vx, vy), scene [B, 8]
-    (goal | o0 | o1 | o2, fixed per episode)"""
-    agent: torch.Tensor
-    body: torch.Tensor
-    scene: torch.Tensor
-
-
 class VMASReverseTransport(MultiAgentEnv):
     AGENT = 0
     KIND = "VMASReverseTransport"
@@ -41,7 +33,8 @@ class VMASReverseTransport(MultiAgentEnv):
 
     def __init__(self, num_agents: int, area_size: Optional[float] = None, max_step: int = 64, dt: float = 0.1,
                  params: Optional[dict] = None, device: Optional[torch.device] = None):
-        # :45-63: the arena, the package and the obstacles are fixed by the task, whatever the caller passes
+        # :45-63: the arena, the package and the obstacles are fixed by the task, whatever the caller passes.  Not through
+        # MultiAgentEnv.__init__: that reads car_radius, n_obs, ... of PARAMS and writes to it, and this task's has neither
         self.half_width = 0.8
         self.agent_radius = 0.03
         self._params = dict(self.PARAMS) if params is None else params
@@ -59,7 +52,6 @@ class VMASReverseTransport(MultiAgentEnv):
             raise ValueError(f"VMASReverseTransport supports 1 to 16 agents (got {num_agents})")
         self.cfg = N.make_vmas_cfg(num_agents, dt)
         self.num_goals = 0
-        self._ray = None
 
     # ---- reference attribute surface (:65-88, 313-320) ----
     @property
@@ -92,80 +84,28 @@ class VMASReverseTransport(MultiAgentEnv):
     def action_lim(self):
         return -torch.ones(2), torch.ones(2)
 
-    # ---- batched interface (what the engine uses) ----
-    def reset_batch(self, seeds, want_graph: bool = False):
-        cfg, dev = self.cfg, self.device
-        seeds = torch.as_tensor(np.asarray(seeds, dtype=np.int64) if not torch.is_tensor(seeds) else seeds).to(dev)
-        B = int(seeds.shape[0])
-        agent = torch.empty(B, cfg.n_agents, 4, device=dev)
-        body = torch.empty(B, 4, device=dev)
-        scene = torch.empty(B, 8, device=dev)
-        n_failed = torch.zeros(1, dtype=torch.int32, device=dev)
-        OE.vmas_reset(cfg, seeds, agent, body, scene, n_failed)
-        if int(n_failed.item()):
-            raise RuntimeError(f"env reset: {int(n_failed.item())} of {B} scenes could not be placed within the kernel's "
-                               f"rejection-loop bounds")
-        st = VMASBatchState(agent, body, scene)
-        return (st, self.graph_batch(st)) if want_graph else st
-
-    def step_batch(self, st: VMASBatchState, action: torch.Tensor, want_graph: bool = False):
-        """-> (next state, reward [B] and cost [B, n, 2] of the pre-step state[, graph of the next state])"""
-        cfg, dev = self.cfg, self.device
-        B = st.agent.shape[0]
-        nx, nb = torch.empty_like(st.agent), torch.empty_like(st.body)
-        rew = torch.empty(B, device=dev)
-        cost = torch.empty(B, cfg.n_agents, 2, device=dev)
-        g = OE.alloc_graph(cfg, B, dev) if want_graph else None
-        OE.vmas_step(cfg, st.agent, st.body, st.scene, action.contiguous(), nx, nb, rew, cost, g)
-        nst = VMASBatchState(nx, nb, st.scene)
-        if want_graph:
-            return nst, rew, cost, self._graphs(nst, g)
-        return nst, rew, cost
-
-    def graph_batch(self, st: VMASBatchState) -> GraphsTuple:
-        g = OE.alloc_graph(self.cfg, st.agent.shape[0], self.device)
-        OE.vmas_graph_materialize(self.cfg, st.agent, st.body, st.scene, g)
-        return self._graphs(st, g)
-
-    def record_state(self, ro, flat, rep) -> VMASBatchState:
-        """the compact state of every (env, t) of an env-major rollout record (see MultiAgentEnv.record_state)"""
-        return VMASBatchState(flat(ro.agent), flat(ro.body), rep(ro.scene))
-
-    def _env_states(self, st: VMASBatchState):
+    # ---- the compact state: agent [B, n, 4], body [B, 4] (box x, y, vx, vy), scene [B, 8] (goal | o0 | o1 | o2) ----
+    def _env_states(self, st: OE.State):
         o = st.scene[..., 2:8].reshape(st.scene.shape[:-1] + (3, 2))
         return VMASReverseTransportState(st.body[..., 0:2], st.body[..., 2:4], st.agent[..., 0:2], st.agent[..., 2:4],
                                          st.scene[..., 0:2], o)
 
     # ---- reference single-graph interface = B = 1 view ----
-    def _state_of(self, graph: GraphsTuple) -> VMASBatchState:
+    def _state_of(self, graph: GraphsTuple) -> OE.State:
         return self._batch_of_env_state(graph.env_states)
 
-    def _batch_of_env_state(self, es: VMASReverseTransportState, lidar_data=None) -> VMASBatchState:
+    def _batch_of_env_state(self, es: VMASReverseTransportState, lidar_data=None) -> OE.State:
         f = lambda x: torch.as_tensor(x, dtype=torch.float32, device=self.device)
         n = self.num_agents
         agent = torch.cat([f(es.a_pos).reshape(n, 2), f(es.a_vel).reshape(n, 2)], -1).reshape(1, n, 4).contiguous()
         body = torch.cat([f(es.box_pos).reshape(2), f(es.box_vel).reshape(2)]).reshape(1, 4).contiguous()
         scene = torch.cat([f(es.goal_pos).reshape(2), f(es.o_pos).reshape(6)]).reshape(1, 8).contiguous()
-        return VMASBatchState(agent, body, scene)
-
-    def step(self, graph: GraphsTuple, action, get_eval_info: bool = False) -> StepResult:
-        st = self._state_of(graph)
-        action = torch.as_tensor(action, dtype=torch.float32, device=self.device).reshape(1, self.num_agents, 2)
-        nst, rew, cost, g = self.step_batch(st, action, want_graph=True)
-        return StepResult(self._squeeze(g), rew[0], cost[0], torch.tensor(False), {})
-
-    def get_cost(self, graph: GraphsTuple):
-        st = self._state_of(graph)
-        zero = torch.zeros(1, self.num_agents, 2, device=self.device)
-        return self.step_batch(st, zero)[2][0]                # cost and reward depend on the pre-step state only
+        return OE.State(dict(agent=agent, body=body), dict(scene=scene))
 
     def get_reward(self, graph: GraphsTuple, action=None):
         st = self._state_of(graph)
         zero = torch.zeros(1, self.num_agents, 2, device=self.device)
         return self.step_batch(st, zero)[1][0]
-
-    def get_graph(self, env_state: VMASReverseTransportState, lidar_data=None) -> GraphsTuple:
-        return self._squeeze(self.graph_batch(self._batch_of_env_state(env_state)))
 
     # ---- rendering (:321-431) ----
     def render_video(self, rollout, video_path, Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,

@@ -123,6 +123,20 @@ class GraphFeats:
                       self.Xa, self.Xo if self.n_other > 0 else None, self.efeat, self.emask, self.Fp)
         return self
 
+    def compute_record(self, step, slots: int, env, env_ids, n_env, n_time):
+        """features of n_env x n_time states of a record (ops_env.record_fields): `step` holds the per-step fields as base
+        tensors whose storage keeps `slots` time slots per env (T + 1 in the env-major rollout record, 1 for a dense [B, ...]
+        slab), `env` the per-env fields.  A field of trailing size I has the env stride slots * I and the time stride I (0
+        for a slab: both kernels use it as t * stride only)."""
+        cfg, n = self.cfg, self.cfg.n_agents
+        se, st = slots, int(slots > 1)               # env and time stride in units of I
+        if cfg.is_vmas:
+            return self.compute_vmas(step["agent"], se * n * 4, st * n * 4, step["body"], se * 4, st * 4, env["scene"], env_ids,
+                                     n_env, n_time)
+        ia, ih = n * cfg.state_dim, n * cfg.top_k * 2
+        return self.compute(step["agent"], se * ia, st * ia, env["goal"], env.get("obst"), step.get("hits"), se * ih, st * ih,
+                            env_ids, n_env, n_time)
+
     def compute_vmas(self, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time):
         """VMASReverseTransport: agent / body records through strides (floats), scene [B, 8] (dgppo_vmas_graph_feats)"""
         assert n_env * n_time == self.G

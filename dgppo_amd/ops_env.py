@@ -11,12 +11,72 @@ import torch
 from . import _native as N
 
 
+STEP_FIELDS, ENV_FIELDS = ("agent", "hits", "body"), ("goal", "obst", "scene")     # every name record_fields can give
+
+
+def record_fields(cfg: N.EnvCfg) -> tuple[Dict[str, tuple], Dict[str, tuple]]:
+    """The compact record of an env kind: name -> trailing shape of the fields kept per (env, step) and of those kept per env.
+    LiDAR / MPE: agent states (+ the top-k LiDAR hit points) per step, goals (+ obstacle records) per env;
+    VMASReverseTransport: agents and the box (x, y, vx, vy) per step, scene = goal | 3 obstacle centres per env."""
+    n, sd = cfg.n_agents, cfg.state_dim
+    if cfg.is_vmas:
+        return {"agent": (n, 4), "body": (4,)}, {"scene": (8,)}
+    step, env = {"agent": (n, sd)}, {"goal": (cfg.n_goals, sd)}
+    if cfg.is_lidar and cfg.n_obs > 0:
+        step["hits"] = (n, cfg.top_k, 2)
+    if cfg.n_obs > 0:
+        env["obst"] = (cfg.n_obs, cfg.obst_stride)
+    return step, env
+
+
+class State:
+    """Compact env state of any kind (device tensors with some leading batch shape): `step` and `env` hold the fields
+    record_fields names, also readable as attributes (st.agent, st.hits, st.body, ...).  A field that is not held reads as
+    None: obst / hits of a kind without obstacles, hits before sensing."""
+
+    def __init__(self, step: Dict[str, torch.Tensor], env: Dict[str, torch.Tensor]):
+        self.step = {k: v for k, v in step.items() if v is not None}
+        self.env = {k: v for k, v in env.items() if v is not None}
+
+    def __getattr__(self, name):
+        if name in STEP_FIELDS:
+            return self.step.get(name)
+        if name in ENV_FIELDS:
+            return self.env.get(name)
+        raise AttributeError(name)
+
+    @classmethod
+    def empty(cls, cfg: N.EnvCfg, B: int, device) -> "State":
+        step, env = record_fields(cfg)
+        z = lambda shapes: {k: torch.empty(B, *s, device=device) for k, s in shapes.items()}
+        return cls(z(step), z(env))
+
+    def like(self) -> "State":
+        """uninitialised per-step fields of the same shapes next to the same per-env fields: where a step writes to"""
+        return State({k: torch.empty_like(v) for k, v in self.step.items()}, self.env)
+
+
 def ray_tables(n_rays: int, device) -> tuple[torch.Tensor, torch.Tensor]:
     """cos/sin(linspace(-pi, pi-2pi/R, R)) in fp32 (dgppo/env/utils.py:51)."""
     thetas = np.linspace(-np.pi, np.pi - 2 * np.pi / n_rays, n_rays).astype(np.float32)
     rc = torch.from_numpy(np.cos(thetas).astype(np.float32)).to(device)
     rs = torch.from_numpy(np.sin(thetas).astype(np.float32)).to(device)
     return rc, rs
+
+
+_RAYS: Dict[tuple, tuple] = {}
+
+
+def _rays(cfg: N.EnvCfg, device):
+    """the ray tables of a LiDAR kind, built once per (n_rays, device).  Building them copies from the host, which a HIP-graph
+    capture does not allow: the first call has to be an eager one.  Engine.rollout sees to that: its reset and sense pass run
+    outside the captured region, and the step loop runs eagerly once before it is captured."""
+    if not cfg.is_lidar:
+        return None, None
+    key = (cfg.n_rays, device)
+    if key not in _RAYS:
+        _RAYS[key] = ray_tables(cfg.n_rays, device)
+    return _RAYS[key]
 
 
 def _graph_state_dim(cfg: N.EnvCfg) -> int:
@@ -60,24 +120,25 @@ def _graph_out(cfg: N.EnvCfg, g: Dict[str, torch.Tensor], B: int) -> N.GraphOut:
     return go
 
 
-def _check_state(cfg: N.EnvCfg, agent, goal, obst, hits, B):
-    n, sd = cfg.n_agents, cfg.state_dim
-    N.expect_shape(agent, (B, n, sd), "agent")
-    N.expect_shape(goal, (B, cfg.n_goals, sd), "goal")
-    if cfg.n_obs > 0:
-        if obst is None:
-            raise ValueError("obst is required when n_obs > 0")
-        N.expect_shape(obst, (B, cfg.n_obs, cfg.obst_stride), "obst")
-    if hits is not None:
-        N.expect_shape(hits, (B, n, cfg.top_k, 2), "hits")
+def _check_state(cfg: N.EnvCfg, B: int, **given):
+    """every field of the kind's record is given and has its shape, but for hits: they may be missing (before sensing), and
+    the callers check the ones they get"""
+    for fields in record_fields(cfg):
+        for name, shape in fields.items():
+            if given.get(name) is not None:
+                N.expect_shape(given[name], (B,) + shape, name)
+            elif name != "hits":
+                raise ValueError(f"{name} is required by env kind {cfg.kind}")
 
 
 def env_step(cfg: N.EnvCfg, agent, action, goal, obst, hits, ray_cos, ray_sin,
              next_agent, next_hits, reward, cost, graph: Optional[Dict[str, torch.Tensor]] = None):
     """dgppo_env_step.  action=None -> sense-only (graph of the given state)."""
     B = agent.shape[0]
-    _check_state(cfg, agent, goal, obst, hits, B)
+    _check_state(cfg, B, agent=agent, goal=goal, obst=obst)
     n = cfg.n_agents
+    if hits is not None:
+        N.expect_shape(hits, (B, n, cfg.top_k, 2), "hits")
     if action is not None:
         N.expect_shape(action, (B, n, 2), "action")
         N.expect_shape(reward, (B,), "reward")
@@ -100,7 +161,9 @@ def env_step(cfg: N.EnvCfg, agent, action, goal, obst, hits, ray_cos, ray_sin,
 
 def graph_materialize(cfg: N.EnvCfg, agent, goal, obst, hits, graph: Dict[str, torch.Tensor]):
     B = agent.shape[0]
-    _check_state(cfg, agent, goal, obst, hits, B)
+    _check_state(cfg, B, agent=agent, goal=goal, obst=obst)
+    if hits is not None:
+        N.expect_shape(hits, (B, cfg.n_agents, cfg.top_k, 2), "hits")
     go = _graph_out(cfg, graph, B)
     rc = N.lib().dgppo_graph_materialize(
         C.byref(cfg), N.ptr(agent, name="agent"), N.ptr(goal, name="goal"), N.ptr(obst, name="obst"),
@@ -112,11 +175,7 @@ def env_reset(cfg: N.EnvCfg, seeds: torch.Tensor, agent, goal, obst, n_failed: t
     """n_failed: optional int32 device counter (caller-zeroed), += 1 per env whose bounded rejection loops ran out — read it at
     the next host sync and do not use the batch when it is non-zero (dgppo_env_reset_checked)."""
     B = seeds.shape[0]
-    n, sd = cfg.n_agents, cfg.state_dim
-    N.expect_shape(agent, (B, n, sd), "agent")
-    N.expect_shape(goal, (B, cfg.n_goals, sd), "goal")
-    if cfg.n_obs > 0:
-        N.expect_shape(obst, (B, cfg.n_obs, cfg.obst_stride), "obst")
+    _check_state(cfg, B, agent=agent, goal=goal, obst=obst)
     if n_failed is not None:
         N.expect_shape(n_failed, (1,), "n_failed")
     rc = N.lib().dgppo_env_reset_checked(C.byref(cfg), N.ptr(seeds, torch.int64, "seeds"), N.ptr(agent, name="agent"),
@@ -145,9 +204,7 @@ def randn(seed: int, offset: int, out: torch.Tensor):
 def _check_vmas(cfg: N.EnvCfg, agent, body, scene, B):
     if not cfg.is_vmas:
         raise ValueError(f"env kind {cfg.kind} is not VMASReverseTransport")
-    N.expect_shape(agent, (B, cfg.n_agents, 4), "agent")
-    N.expect_shape(body, (B, 4), "body")
-    N.expect_shape(scene, (B, 8), "scene")
+    _check_state(cfg, B, agent=agent, body=body, scene=scene)
 
 
 def vmas_reset(cfg: N.EnvCfg, seeds: torch.Tensor, agent, body, scene, n_failed: torch.Tensor = None):
@@ -189,3 +246,44 @@ def vmas_graph_materialize(cfg: N.EnvCfg, agent, body, scene, graph: Dict[str, t
     rc = N.lib().dgppo_vmas_graph_materialize(C.byref(cfg), N.ptr(agent, name="agent"), N.ptr(body, name="body"),
                                               N.ptr(scene, name="scene"), C.byref(go), C.c_int32(B), N.stream_ptr())
     N.check(rc, "dgppo_vmas_graph_materialize")
+
+
+# ---- the operations over a State of any kind: the only place that knows which entry points serve which kind ---------------
+def sense(cfg: N.EnvCfg, st: State, graph: Optional[Dict[str, torch.Tensor]] = None):
+    """fills st.hits (allocated here if the state has none yet) from the rest of the state: the sense-only dgppo_env_step,
+    which also writes the graph of the state if asked"""
+    s, e = st.step, st.env
+    if "hits" not in s:
+        s["hits"] = torch.empty(s["agent"].shape[:-2] + record_fields(cfg)[0]["hits"], device=s["agent"].device)
+    rc, rs = _rays(cfg, s["agent"].device)
+    env_step(cfg, s["agent"], None, e["goal"], e.get("obst"), None, rc, rs, None, s["hits"], None, None, graph)
+
+
+def reset(cfg: N.EnvCfg, seeds: torch.Tensor, st: State, n_failed: torch.Tensor = None,
+          graph: Optional[Dict[str, torch.Tensor]] = None):
+    """the episode start of seeds [B] into st (State.empty), sensed where the record has hits; n_failed as in env_reset"""
+    if cfg.is_vmas:
+        vmas_reset(cfg, seeds, st.agent, st.body, st.scene, n_failed)
+    else:
+        env_reset(cfg, seeds, st.agent, st.goal, st.obst, n_failed)
+    if "hits" in st.step:
+        sense(cfg, st, graph)
+    elif graph is not None:
+        materialize(cfg, st, graph)
+
+
+def step(cfg: N.EnvCfg, st: State, action, nst: State, reward, cost, graph: Optional[Dict[str, torch.Tensor]] = None):
+    """one env step from st into the per-step fields of nst (st.like()): reward [B] and cost [B, n, n_cost] of the pre-step
+    state, the optional graph of the post-step state"""
+    s, e, ns = st.step, st.env, nst.step         # the dicts: cheaper than attributes, and this runs in every rollout step
+    if cfg.is_vmas:
+        return vmas_step(cfg, s["agent"], s["body"], e["scene"], action, ns["agent"], ns["body"], reward, cost, graph)
+    rc, rs = _rays(cfg, s["agent"].device)
+    env_step(cfg, s["agent"], action, e["goal"], e.get("obst"), s.get("hits"), rc, rs, ns["agent"], ns.get("hits"), reward,
+             cost, graph)
+
+
+def materialize(cfg: N.EnvCfg, st: State, graph: Dict[str, torch.Tensor]):
+    if cfg.is_vmas:
+        return vmas_graph_materialize(cfg, st.agent, st.body, st.scene, graph)
+    graph_materialize(cfg, st.agent, st.goal, st.obst, st.hits, graph)

@@ -218,6 +218,24 @@ def dense_bwd_w(X, dY, dW, db=None):
     N.check(rc, "dgppo_dense_bwd_w")
 
 
+def _check_strided(fn: str, name: str, t_, se: int, st: int, inner: tuple, env_ids, n_env: int, n_time: int):
+    """a record field the feature kernels address as data_ptr + env * se + time * st, in floats (a view's own outer strides are
+    ignored): the innermost record must be dense fp32 CUDA storage, and the storage must reach the last (env, time) the call
+    touches"""
+    if not (t_.is_cuda and t_.dtype == torch.float32):
+        raise ValueError(f"{fn}: {name} must be a float32 CUDA tensor")
+    want, acc = [], 1
+    for d in reversed(inner):
+        want.append(acc)
+        acc *= d
+    if tuple(t_.shape[-len(inner):]) != tuple(inner) or list(t_.stride()[-len(inner):]) != want[::-1]:
+        raise ValueError(f"{fn}: the trailing {inner} block of {name} must be dense (got shape {tuple(t_.shape)}, "
+                         f"strides {t_.stride()})")
+    avail = t_.untyped_storage().nbytes() // 4 - t_.storage_offset()
+    if env_ids is None and (n_env - 1) * se + (n_time - 1) * st + acc > avail:
+        raise ValueError(f"{fn}: {name}: the strides reach beyond its storage")
+
+
 def graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, goal, obst, hits, hits_se, hits_st, env_ids, n_env, n_time,
                 Xa, Xo, efeat, emask, Fp):
     """agent/hits are base tensors (any shape); strides are in floats."""
@@ -229,24 +247,9 @@ def graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, goal, obst, hits, hits
         N.expect_shape(Xo, (G * n_other, Fp), "Xo")
     N.expect_shape(efeat, (G * n, S, 4), "efeat")
     N.expect_shape(emask, (G * n, S), "emask")
-    # the records are addressed as data_ptr + env * se + time * st (a view's own outer strides are ignored): the innermost
-    # record must be dense fp32 CUDA storage, and the storage must reach the last (env, time) the call touches
-    for name, t_, se, st, inner in (("agent", agent, agent_se, agent_st, (n, cfg.state_dim)),
-                                    ("hits", hits, hits_se, hits_st, (n, cfg.top_k, 2))):
-        if t_ is None:
-            continue
-        if not (t_.is_cuda and t_.dtype == torch.float32):
-            raise ValueError(f"graph_feats: {name} must be a float32 CUDA tensor")
-        want, acc = [], 1
-        for d in reversed(inner):
-            want.append(acc)
-            acc *= d
-        if tuple(t_.shape[-len(inner):]) != tuple(inner) or list(t_.stride()[-len(inner):]) != want[::-1]:
-            raise ValueError(f"graph_feats: the trailing {inner} block of {name} must be dense (got shape {tuple(t_.shape)}, "
-                             f"strides {t_.stride()})")
-        avail = t_.untyped_storage().nbytes() // 4 - t_.storage_offset()
-        if env_ids is None and (n_env - 1) * se + (n_time - 1) * st + acc > avail:
-            raise ValueError(f"graph_feats: {name}: the strides reach beyond its storage")
+    _check_strided("graph_feats", "agent", agent, agent_se, agent_st, (n, cfg.state_dim), env_ids, n_env, n_time)
+    if hits is not None:
+        _check_strided("graph_feats", "hits", hits, hits_se, hits_st, (n, cfg.top_k, 2), env_ids, n_env, n_time)
     rc = N.lib().dgppo_graph_feats(
         C.byref(cfg), C.c_void_p(agent.data_ptr()), C.c_int64(agent_se), C.c_int64(agent_st), _p(goal, "goal"),
         _p(obst, "obst") if (obst is not None and not cfg.is_lidar) else C.c_void_p(0),
@@ -265,19 +268,8 @@ def vmas_graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, body, body_se, bo
     N.expect_shape(Xa, (G * n, Fp), "Xa")
     N.expect_shape(efeat, (G * n, n, 4), "efeat")
     N.expect_shape(emask, (G * n, n), "emask")
-    for name, t_, se, st, inner in (("agent", agent, agent_se, agent_st, (n, 4)), ("body", body, body_se, body_st, (4,))):
-        if not (t_.is_cuda and t_.dtype == torch.float32):
-            raise ValueError(f"vmas_graph_feats: {name} must be a float32 CUDA tensor")
-        want, acc = [], 1
-        for d in reversed(inner):
-            want.append(acc)
-            acc *= d
-        if tuple(t_.shape[-len(inner):]) != tuple(inner) or list(t_.stride()[-len(inner):]) != want[::-1]:
-            raise ValueError(f"vmas_graph_feats: the trailing {inner} block of {name} must be dense (got shape "
-                             f"{tuple(t_.shape)}, strides {t_.stride()})")
-        avail = t_.untyped_storage().nbytes() // 4 - t_.storage_offset()
-        if env_ids is None and (n_env - 1) * se + (n_time - 1) * st + acc > avail:
-            raise ValueError(f"vmas_graph_feats: {name}: the strides reach beyond its storage")
+    _check_strided("vmas_graph_feats", "agent", agent, agent_se, agent_st, (n, 4), env_ids, n_env, n_time)
+    _check_strided("vmas_graph_feats", "body", body, body_se, body_st, (4,), env_ids, n_env, n_time)
     rc = N.lib().dgppo_vmas_graph_feats(
         C.byref(cfg), C.c_void_p(agent.data_ptr()), C.c_int64(agent_se), C.c_int64(agent_st), C.c_void_p(body.data_ptr()),
         C.c_int64(body_se), C.c_int64(body_st), _p(scene, "scene"), _p(env_ids, "env_ids", torch.int32), C.c_int32(n_env),

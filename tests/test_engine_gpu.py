@@ -729,7 +729,7 @@ def test_baseline_configs_full_iterations_keep_their_invariants(cuda, kind, n, n
             cf = c[torch.isfinite(c)]                                      # a NaN cost needs a NaN hit point (parallel ray): rare, legal
             assert float(cf.min()) >= -1.0 and (not ocfg.is_lidar or float(cf.max()) <= 1.0)
             assert int(torch.isnan(c).sum()) <= c.numel() // 1000
-            if r.has_hits:
+            if r.hits is not None:
                 d = (r.hits - ag[..., None, :2]).norm(dim=-1)
                 d = d[torch.isfinite(d)]
                 # a ray either hits within the sensing radius or misses: alpha = 1e6 puts the "hit" 5e5 away (kept unclamped
