@@ -42,3 +42,20 @@ class Algorithm(abc.ABC):
     @abc.abstractmethod
     def load(self, load_dir: str, step: int):
         """read {load_dir}/{step}/*.pkl"""
+
+    # -- the whole training state (weights, optimisers, generators): what a stopped run continues from -------------
+    @abc.abstractmethod
+    def state_dict(self) -> dict:
+        """nested dict with str keys and numpy-array / int / float leaves"""
+
+    @abc.abstractmethod
+    def load_state_dict(self, d: dict) -> None:
+        """restore a constructed algo from state_dict()'s tree; ValueError if it belongs to another configuration"""
+
+    @abc.abstractmethod
+    def save_state(self, path: str):
+        """write state_dict() to one file, atomically"""
+
+    @abc.abstractmethod
+    def load_state(self, path: str):
+        """load_state_dict() of a file written by save_state()"""

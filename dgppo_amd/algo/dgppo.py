@@ -277,3 +277,27 @@ class DGPPO(Algorithm):
         for fname, key in (("actor.pkl", "policy"), ("Vl.pkl", "Vl"), ("Vh.pkl", "Vh")):
             with open(os.path.join(path, fname), "rb") as f:   # weights-only unpickler: nothing in the file is executed
                 self.engine.nets[key].load_tree(CK.load_tree(f))
+
+    # ---- the whole training state, to continue a stopped run (not in the reference; InforMARL, InforMARLLagr and HCBFCRPO
+    # inherit it): the engine's buffers and every generator that decides a later batch, stored as numbers ----
+    def state_dict(self) -> dict:
+        return {"engine": self.engine.state_dict(), "rng": CK.generator_state(self._rng),
+                "perm_rng": CK.generator_state(self._perm_rng), "np_random": CK.global_numpy_state()}
+
+    def load_state_dict(self, d: dict) -> None:
+        """on a constructed algo: overrides what construction drew (the entropy noise and the global np.random it came from)"""
+        for k in ("engine", "rng", "perm_rng", "np_random"):
+            if k not in d:
+                raise ValueError(f"algo state has no '{k}' entry")
+        self.engine.load_state_dict(d["engine"])             # ValueError before anything changes if it does not fit
+        CK.set_generator_state(self._rng, d["rng"])
+        CK.set_generator_state(self._perm_rng, d["perm_rng"])
+        CK.set_global_numpy_state(d["np_random"])
+        self._pending_det = None                             # rollouts of the parameters that were just replaced
+        self._last_rollouts = {}
+
+    def save_state(self, path: str):
+        CK.save_state(self.state_dict(), path)
+
+    def load_state(self, path: str):
+        self.load_state_dict(CK.load_state(path))

@@ -21,6 +21,7 @@ from . import nets
 from . import ops_algo as OA
 from . import ops_env as OE
 from . import ops_nn as K
+from .utils import checkpoint as CK
 
 
 @dataclasses.dataclass
@@ -196,6 +197,68 @@ class Engine:
 
     def set_entropy_noise(self, seed: int):
         OE.randn(seed, 0, self.eps_hat.view(-1))
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # the whole training state (resuming a stopped run): parameters, optimiser moments, entropy noise, multipliers
+    # ------------------------------------------------------------------------------------------------------------------
+    _CFG_IDENTITY = ("kind", "n_agents", "n_obs", "n_rays", "top_k", "node_dim", "n_cost")
+
+    def _identity(self) -> dict:
+        """what a state dict must agree on with the engine it is loaded into, in the order it is compared.  Strings are
+        uint8 arrays (the weights-only reader of utils/checkpoint.py takes no str leaves)."""
+        ident = {"algo": CK.encode_str(self.algo)}
+        ident.update({f"cfg.{k}": int(getattr(self.cfg, k)) for k in self._CFG_IDENTITY})
+        for f in dataclasses.fields(Hyper):
+            v = getattr(self.hp, f.name)
+            ident[f"hyper.{f.name}"] = int(v) if isinstance(v, (bool, int)) else float(v)
+        ident["T"], ident["world"] = int(self.T), int(self.world)
+        ident.update({f"size.{k}": int(net.layout.size) for k, net in self.nets.items()})
+        return ident
+
+    def _state_tensors(self) -> Dict[str, torch.Tensor]:
+        """every device buffer of the state, by its path in the state dict"""
+        t = {}
+        for k, net in self.nets.items():
+            opt = self.opt[k]
+            t.update({f"{k}/params": net.params, f"{k}/m": opt.m, f"{k}/v": opt.v, f"{k}/state": opt.state})
+        t["eps_hat"] = self.eps_hat
+        if self.algo == "informarl_lagr":
+            t["lagr"] = self.lagr
+        return t
+
+    def state_dict(self) -> dict:
+        """nested dict (str keys; numpy arrays, ints and floats as leaves) of everything an update reads and writes"""
+        out = {"identity": self._identity()}
+        for path, x in self._state_tensors().items():
+            node = out
+            *dirs, leaf = path.split("/")
+            for d in dirs:
+                node = node.setdefault(d, {})
+            node[leaf] = x.detach().cpu().numpy().copy()
+        return out
+
+    def load_state_dict(self, d: dict) -> None:
+        """ValueError naming the first identity field that differs, before any buffer is touched; then copies INTO the
+        existing tensors — captured HIP graphs hold their addresses and read the loaded values on their next replay."""
+        mine, theirs = self._identity(), d.get("identity", {})
+        show = lambda v: repr(CK.decode_str(v)) if isinstance(v, np.ndarray) else repr(v)
+        for k, v in mine.items():
+            if k not in theirs:
+                raise ValueError(f"state dict does not fit this engine: it has no identity field '{k}'")
+            if not np.array_equal(np.asarray(v), np.asarray(theirs[k])):
+                raise ValueError(f"state dict does not fit this engine: '{k}' is {show(theirs[k])} there, {show(v)} here")
+        src = {}
+        for path, x in self._state_tensors().items():
+            node = d
+            for part in path.split("/"):
+                node = node.get(part) if isinstance(node, dict) else None
+            if not isinstance(node, np.ndarray) or node.dtype != np.float32 or node.shape != tuple(x.shape):
+                raise ValueError(f"state dict does not fit this engine: '{path}' is not a float32 array of shape {tuple(x.shape)}")
+            src[path] = node
+        for path, x in self._state_tensors().items():
+            x.copy_(torch.from_numpy(src[path]).to(self.device))
+        for net in self.nets.values():
+            net.prepare()                       # the prepared GNN weights follow the parameters
 
     # ------------------------------------------------------------------------------------------------------------------
     # rollout

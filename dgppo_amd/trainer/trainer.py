@@ -5,7 +5,11 @@ Data-parallel runs (one process per GPU): `rank` / `world` are two 
 reference's.  `n_env_train` stays the GLOBAL number of training environments: every rank draws the same global key array
 and rolls out its contiguous share of it, the algo (built with the same `allreduce` / `world` / `rank`) exchanges
 gradients once per minibatch, and evaluation, checkpoints and logging happen on rank 0 only — the parameters are
-bit-identical on every rank, so nothing is lost."""
+bit-identical on every rank, so nothing is lost.
+
+Stopped runs (not in the reference): with every weights save rank 0 also writes the whole training state to
+`{log_dir}/resume/{step}.pkl`; `Trainer(..., resume=True)` loads the newest one on every rank and the loop goes on from that
+step ("Resuming a stopped run")."""
 from __future__ import annotations
 
 import json
@@ -14,6 +18,16 @@ from time import time
 
 import numpy as np
 import torch
+
+from ..utils import checkpoint as CK
+
+KEEP_STATES = 2          # state files kept under {log_dir}/resume: the newest and the one before it
+
+
+def no_state_error(run_dir: str) -> FileNotFoundError:
+    return FileNotFoundError(f"{run_dir}: no training state to resume from (resume/flags.yaml and resume/{{step}}.pkl). Runs "
+                             f"written before full-state checkpoints existed hold weights only (models/{{step}}/*.pkl): "
+                             f"they can be tested, not continued.")
 
 
 class _Logger:
@@ -38,7 +52,7 @@ class _Logger:
 
 class Trainer:
     def __init__(self, env, env_test, algo, gamma: float, n_env_train: int, n_env_test: int, log_dir: str, seed: int,
-                 params: dict, save_log: bool = True, rank: int = 0, world: int = 1):
+                 params: dict, save_log: bool = True, rank: int = 0, world: int = 1, resume: bool = False):
         self.env, self.env_test, self.algo, self.gamma = env, env_test, algo, gamma
         self.n_env_train, self.n_env_test, self.log_dir, self.seed = n_env_train, n_env_test, log_dir, seed
         self.rank, self.world = int(rank), int(world)
@@ -53,6 +67,11 @@ class Trainer:
             os.makedirs(log_dir, exist_ok=True)
             self.model_dir = os.path.join(log_dir, "models")
             os.makedirs(self.model_dir, exist_ok=True)
+        # the full training state, {log_dir}/resume/{step}.pkl next to models/: written by rank 0 with every weights save,
+        # read by every rank of a resumed run
+        self.resume_dir = os.path.join(log_dir, "resume")
+        if save_log:
+            os.makedirs(self.resume_dir, exist_ok=True)
         self.logger = _Logger(log_dir, params["run_name"], env.__class__.__name__, save_log) if self.rank == 0 else None
         self.save_log = save_log
         self.steps = params["training_steps"]
@@ -61,6 +80,50 @@ class Trainer:
         self.save_interval = params["save_interval"]
         self.update_steps = 0
         self.key = np.random.default_rng([seed, 7])
+        self.start_step = 0
+        if resume:
+            self._resume()
+
+    # ---- the state at step s is the state BEFORE iteration s: the loop saves it after eval and the weights save, before it
+    # draws the keys of iteration s, so a resumed run repeats the evaluation and the save of step s and goes on from there ----
+    def state_dict(self, step: int) -> dict:
+        return {"algo": self.algo.state_dict(),
+                "trainer": {"key": CK.generator_state(self.key), "step": int(step), "update_steps": int(self.update_steps)}}
+
+    def _save_state(self, step: int):
+        CK.save_state(self.state_dict(step), os.path.join(self.resume_dir, f"{step}.pkl"))
+        for old in CK.state_steps(self.resume_dir)[:-KEEP_STATES]:
+            os.remove(os.path.join(self.resume_dir, f"{old}.pkl"))
+
+    def _resume(self):
+        """every rank loads the newest state (the ranks' generators are identical by construction, so rank 0's file serves
+        all); rank 0 drops the metrics records the stopped run wrote at or after that step"""
+        s = CK.latest_state(self.resume_dir)
+        if s is None:
+            raise no_state_error(self.log_dir)
+        tree = CK.load_state(os.path.join(self.resume_dir, f"{s}.pkl"))
+        tr = tree["trainer"]
+        if int(tr["step"]) != s:
+            raise ValueError(f"{self.resume_dir}/{s}.pkl holds the state of step {int(tr['step'])}")
+        self.algo.load_state_dict(tree["algo"])
+        CK.set_generator_state(self.key, tr["key"])
+        self.start_step, self.update_steps = s, int(tr["update_steps"])
+        path = self.logger.path if self.logger is not None else None
+        if path is not None and os.path.exists(path):
+            def before(ln):                      # a line torn by the stop does not parse: it goes too
+                try:
+                    return json.loads(ln)["step"] < s
+                except (ValueError, KeyError, TypeError):
+                    return False
+            with open(path) as f:
+                kept = [ln for ln in f if before(ln)]
+            with open(path + ".tmp", "w") as f:
+                f.writelines(kept)
+                f.flush()
+                os.fsync(f.fileno())
+            os.replace(path + ".tmp", path)
+        if self.rank == 0:
+            print(f"> resuming {self.log_dir} at step {s}", flush=True)
 
     @staticmethod
     def _check_params(params: dict) -> bool:
@@ -86,7 +149,7 @@ class Trainer:
         start_time = time()
         assert self.n_env_test <= 1000, "n_env_test must be less than or equal to 1_000"
         test_keys = np.random.default_rng([self.seed, 11]).integers(1, 2 ** 62, size=1000)[:self.n_env_test]
-        for step in range(0, self.steps + 1):
+        for step in range(self.start_step, self.steps + 1):
             if step % self.eval_interval == 0 and self.rank == 0:
                 ev = self.evaluate(test_keys)
                 rmin, rmax = ev.pop("_reward_min"), ev.pop("_reward_max")
@@ -96,6 +159,7 @@ class Trainer:
                 self.logger.log(ev, step=self.update_steps)
             if self.save_log and step % self.save_interval == 0:
                 self.algo.save(os.path.join(self.model_dir), step)
+                self._save_state(step)
             keys = self.key.integers(1, 2 ** 62, size=self.n_env_train)        # the global batch, identical on every rank
             share = self.n_env_train // self.world
             rollouts = self.algo.collect(None, keys[self.rank * share:(self.rank + 1) * share])

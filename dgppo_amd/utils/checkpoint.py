@@ -15,8 +15,9 @@ from __future__ import annotations
 
 import collections
 import io
+import os
 import pickle
-from typing import Any, BinaryIO
+from typing import Any, BinaryIO, List, Optional
 
 import numpy as np
 
@@ -106,3 +107,76 @@ def save_tree(tree, f: BinaryIO) -> None:
     """the reference's on-disk format: pickle of the nested dict with numpy leaves."""
     _check_tree(tree)
     pickle.dump(tree, f)
+
+
+# ---- the full training state: one tree per file, written atomically ({log_dir}/resume/{step}.pkl) ----
+# It goes through the same writer and reader as the weights: dicts with string keys, numpy arrays, ints and floats.
+# Generators are stored as the numbers that define them, strings as uint8 arrays.
+
+def encode_str(s: str) -> np.ndarray:
+    return np.frombuffer(s.encode("utf-8"), dtype=np.uint8).copy()
+
+
+def decode_str(a) -> str:
+    return np.asarray(a, dtype=np.uint8).tobytes().decode("utf-8", "replace")
+
+
+def generator_state(gen: np.random.Generator) -> dict:
+    """a PCG64 `np.random.Generator` -> its two 128-bit integers and the buffered half draw, as plain ints"""
+    st = gen.bit_generator.state
+    if st["bit_generator"] != "PCG64":
+        raise TypeError(f"only PCG64 generators are checkpointed, not {st['bit_generator']}")
+    return {"state": int(st["state"]["state"]), "inc": int(st["state"]["inc"]), "has_uint32": int(st["has_uint32"]),
+            "uinteger": int(st["uinteger"])}
+
+
+def set_generator_state(gen: np.random.Generator, d: dict) -> None:
+    gen.bit_generator.state = {"bit_generator": "PCG64", "state": {"state": int(d["state"]), "inc": int(d["inc"])},
+                               "has_uint32": int(d["has_uint32"]), "uinteger": int(d["uinteger"])}
+
+
+def global_numpy_state() -> dict:
+    """the process-global `np.random` (MT19937): key uint32[624], position and the cached gaussian"""
+    name, key, pos, has_gauss, cached = np.random.get_state()
+    assert name == "MT19937", name
+    return {"key": np.asarray(key, dtype=np.uint32).copy(), "pos": int(pos), "has_gauss": int(has_gauss),
+            "cached_gaussian": float(cached)}
+
+
+def set_global_numpy_state(d: dict) -> None:
+    key = np.asarray(d["key"], dtype=np.uint32)
+    if key.shape != (624,):
+        raise ValueError(f"MT19937 key has shape {key.shape}, expected (624,)")
+    np.random.set_state(("MT19937", key, int(d["pos"]), int(d["has_gauss"]), float(d["cached_gaussian"])))
+
+
+def save_state(tree, path: str) -> None:
+    """write `path` through `path + ".tmp"`: flush, fsync, rename.  A process killed while writing leaves the previous
+    file as it was and at most a `.tmp` next to it."""
+    _check_tree(tree)                    # refuse before a file is opened
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        save_tree(tree, f)
+        f.flush()
+        os.fsync(f.fileno())
+    os.replace(tmp, path)
+
+
+def load_state(path: str):
+    with open(path, "rb") as f:
+        return load_tree(f)
+
+
+def state_steps(dir: str) -> List[int]:
+    """the N of every `{dir}/{N}.pkl`, ascending; `.tmp` files and every other name are ignored"""
+    try:
+        names = os.listdir(dir)
+    except (FileNotFoundError, NotADirectoryError):
+        return []
+    return sorted(int(nm[:-4]) for nm in names if nm.endswith(".pkl") and nm[:-4].isascii() and nm[:-4].isdigit())
+
+
+def latest_state(dir: str) -> Optional[int]:
+    """the largest N for which `{dir}/{N}.pkl` exists, or None"""
+    steps = state_steps(dir)
+    return steps[-1] if steps else None

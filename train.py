@@ -11,7 +11,7 @@ import yaml
 
 from dgppo.algo import make_algo
 from dgppo.env import make_env
-from dgppo.trainer.trainer import Trainer
+from dgppo.trainer.trainer import Trainer, no_state_error
 from dgppo.trainer.utils import is_connected
 
 # (flags, kind, default)   kind: a type -> typed option, "flag" -> store_true, "req:<type>" -> required option
@@ -32,7 +32,11 @@ FLAGS = [
     (("--eval-epi",), "int", 1), (("--save-interval",), "int", 50),
     # not in the reference (it is single-device): data-parallel training, one process per GPU
     (("--gpus",), "int", 1),
+    # continue the stopped run in RUN_DIR from its newest full-state checkpoint; every other flag as in the stopped run
+    (("--resume",), "str", None),
 ]
+# flags a resumed run may give differently: where it logs and what it is called play no part in the computation
+_RESUME_FREE = ("resume", "log_dir", "name", "debug")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -45,6 +49,44 @@ def build_parser() -> argparse.ArgumentParser:
         else:
             ap.add_argument(*names, type=_T[kind], default=default)
     return ap
+
+
+def _dest(names) -> str:
+    return names[-1].lstrip("-").replace("-", "_")
+
+
+def _flags_to_store(a) -> dict:
+    """what config.yaml and resume/flags.yaml record of the command line: everything but --resume"""
+    return {k: v for k, v in vars(a).items() if k != "resume"}
+
+
+def check_resume_flags(a, stored: dict) -> None:
+    """the shares, the minibatch order and the schedules depend on the flags (--gpus and --steps included), so a resumed run
+    must repeat those of the stopped one (`stored`: its resume/flags.yaml).  SystemExit naming every flag that differs."""
+    diff = []
+    for names, _, _ in FLAGS:
+        k = _dest(names)
+        if k in _RESUME_FREE:
+            continue
+        if k not in stored:
+            diff.append(f"{names[-1]} (not recorded by the stopped run)")
+        elif stored[k] != getattr(a, k):
+            diff.append(f"{names[-1]} ({stored[k]!r} in the stopped run, {getattr(a, k)!r} now)")
+    if diff:
+        raise SystemExit("train.py --resume: these flags differ from the stopped run's: " + ", ".join(diff))
+
+
+def check_resume(a) -> None:
+    """needs no GPU: called before any rank is started"""
+    if a.resume is None:
+        return
+    if a.debug:
+        raise SystemExit("train.py: --resume cannot be combined with --debug (a debug run writes nothing)")
+    path = os.path.join(a.resume, "resume", "flags.yaml")
+    if not os.path.isfile(path):
+        raise no_state_error(a.resume)
+    with open(path) as f:
+        check_resume_flags(a, yaml.safe_load(f) or {})
 
 
 def _unique_run_dir(root: str, seed: int):
@@ -123,24 +165,33 @@ def train(a):
     write = not a.debug and rank == 0                # one writer (rank 0); the other ranks never touch the log directory
     if write:
         os.makedirs(root, exist_ok=True)
-    log_dir, stamp, tag = _unique_run_dir(root, a.seed)
-    run_name = f"{a.algo}_seed{a.seed:03}_{stamp}_{tag}"
-    if a.name is not None:
-        run_name = f"{run_name}_{a.name}_seed{a.seed:03}_{stamp}_{tag}"
+    if a.resume is not None:                         # the stopped run's directory, nothing new beside it
+        log_dir = a.resume
+        run_name = f"{a.algo}_{os.path.basename(os.path.normpath(log_dir))}"
+    else:
+        log_dir, stamp, tag = _unique_run_dir(root, a.seed)
+        run_name = f"{a.algo}_seed{a.seed:03}_{stamp}_{tag}"
+        if a.name is not None:
+            run_name = f"{run_name}_{a.name}_seed{a.seed:03}_{stamp}_{tag}"
     schedule = {"run_name": run_name, "training_steps": a.steps, "eval_interval": a.eval_interval, "eval_epi": a.eval_epi,
                 "save_interval": a.save_interval}
     trainer = Trainer(env=env, env_test=env_test, algo=algo, gamma=0.99, log_dir=log_dir, n_env_train=a.n_env_train,
-                      n_env_test=a.n_env_test, seed=a.seed, params=schedule, save_log=write, rank=rank, world=world)
-    if write:   # plain mappings (the reference dumps the argparse.Namespace object itself; test.py reads both)
+                      n_env_test=a.n_env_test, seed=a.seed, params=schedule, save_log=write, rank=rank, world=world,
+                      resume=a.resume is not None)
+    if write and a.resume is None:   # plain mappings (the reference dumps the argparse.Namespace object itself; test.py reads both)
         with open(f"{log_dir}/config.yaml", "w") as f:
-            yaml.safe_dump(vars(a), f)
+            yaml.safe_dump(_flags_to_store(a), f)
             yaml.safe_dump(algo.config, f)
+        # the flags alone, for --resume to compare with: config.yaml is one mapping in which algo.config's keys win
+        with open(f"{trainer.resume_dir}/flags.yaml", "w") as f:
+            yaml.safe_dump(_flags_to_store(a), f)
     trainer.train()
     close()
 
 
 def main():
     a = build_parser().parse_args()
+    check_resume(a)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher environment: start the ranks ourselves, before this process touches the GPU, and supervise them
         # (per-rank logs, everything stops on the first failure — dgppo_amd/launch.py)
