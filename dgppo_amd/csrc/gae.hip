@@ -365,8 +365,8 @@ __global__ void adv_kernel(AdvArgs a) {
     for (int h = 0; a.Vh != nullptr && h < nh; ++h) {       // Vh == NULL: plain normalised advantage (InforMARL)
       const float v0 = Vh[((size_t)t * n + ag) * nh + h], v1 = Vh[((size_t)(t + 1) * n + ag) * nh + h];
       const float deriv = (v1 - v0) * a.inv_dt + a.alpha * v0;
-      const float ac = fmaxf(deriv + a.cbf_eps, 0.0f);
-      amax = (h == 0) ? ac : fmaxf(amax, ac);
+      const float ac = nanmax(deriv + a.cbf_eps, 0.0f);      // jnp.maximum(...).max(-1) (dgppo.py:247-256): a NaN value
+      amax = (h == 0) ? ac : nanmax(amax, ac);                // gives a NaN advantage, not the other operand
       safe = safe && (deriv <= 0.0f);
     }
     const float A = (safe ? al : 0.0f) + amax * a.cbf_weight;
@@ -401,7 +401,7 @@ __global__ void shaped_reward_kernel(const float* __restrict__ reward, const flo
   float tot = 0.0f;
   for (int i = 0; i < n; ++i) {                    // .sum(axis=-1).sum(axis=-1): components first, then agents
     float si = 0.0f;
-    for (int h = 0; h < nh; ++h) si += fmaxf(c[i * nh + h], 0.0f);
+    for (int h = 0; h < nh; ++h) si += nanmax(c[i * nh + h], 0.0f);   // jnp.maximum: a NaN cost gives a NaN stage cost
     tot += si;
   }
   out[r] = reward[r] - w * tot;
@@ -560,7 +560,7 @@ extern "C" int32_t dgppo_lagr_apply(float* lagr, float* sums, int32_t count, int
 // (jnp.clip(rollout.costs, a_min=0), informarl_lagr.py:213)
 __global__ void relu_fwd_kernel(const float* __restrict__ x, float* __restrict__ out, long count) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) out[i] = fmaxf(x[i], 0.0f);
+  if (i < count) out[i] = nanmax(x[i], 0.0f);   // jnp.clip keeps a NaN cost
 }
 
 extern "C" int32_t dgppo_relu_fwd(const float* x, float* out, int64_t count, void* stream) {

@@ -516,18 +516,21 @@ extern "C" int32_t dgppo_gru_bwd(const float* dhs, const float* Wh, const float*
 #define LOG2_F 0.6931471805599453f
 
 __device__ inline float softplusf_(float x) { return (x > 20.0f) ? x : log1pf(expf(x)); }
-// log Phi(z): erfc for the bulk, asymptotic series for the far left tail (tfp special_math.log_ndtr)
+// log Phi(z): erfc for the bulk, asymptotic series for the far left tail (tfp special_math.log_ndtr).  The series
+// Phi(z) ~ phi(z) / (-z) * (1 - 1/z^2 + 3/z^4 - 15/z^6) is cut after its fourth term, so its relative error is the fifth,
+// 105 / z^8: 1.05e-6 at z = -10 but 2.7e-4 at z = -5.  It therefore starts at z <= -10; down to there the erfc form is
+// still made of normal fp32 numbers (erfcf(10 / sqrt 2) = 1.5e-23, expf(-50) = 1.9e-22).
+#define NDTR_SERIES_BELOW (-10.0f)
+__device__ inline float ndtr_tail_series(float z2) { return 1.0f - 1.0f / z2 + 3.0f / (z2 * z2) - 15.0f / (z2 * z2 * z2); }
 __device__ inline float log_ndtrf_(float z) {
-  if (z > -5.0f) return logf(0.5f * erfcf(-z * 0.70710678118654752f));
+  if (z > NDTR_SERIES_BELOW) return logf(0.5f * erfcf(-z * 0.70710678118654752f));
   const float z2 = z * z;
-  const float series = 1.0f - 1.0f / z2 + 3.0f / (z2 * z2) - 15.0f / (z2 * z2 * z2);
-  return -0.5f * z2 - logf(-z) - HALF_LOG_2PI + logf(series);
+  return -0.5f * z2 - logf(-z) - HALF_LOG_2PI + logf(ndtr_tail_series(z2));
 }
-// d/dz log Phi(z) = phi(z) / Phi(z)
+// d/dz log Phi(z) = phi(z) / Phi(z); in the tail -z / series, with the terms of the value
 __device__ inline float dlog_ndtrf_(float z) {
-  if (z > -5.0f) return 0.3989422804014327f * expf(-0.5f * z * z) / (0.5f * erfcf(-z * 0.70710678118654752f));
-  const float z2 = z * z;
-  return -z / (1.0f - 1.0f / z2 + 3.0f / (z2 * z2));
+  if (z > NDTR_SERIES_BELOW) return 0.3989422804014327f * expf(-0.5f * z * z) / (0.5f * erfcf(-z * 0.70710678118654752f));
+  return -z / ndtr_tail_series(z * z);
 }
 __device__ inline float tanh_fldj(float x) { return 2.0f * (LOG2_F - x - softplusf_(-2.0f * x)); }
 
@@ -678,11 +681,11 @@ extern "C" int32_t dgppo_policy_head(const float* ms, const float* eps, const fl
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) value_loss_kernel(const float* __restrict__ v, const float* __restrict__ target,
                                                          float* __restrict__ dv, float* __restrict__ stats, int count,
-                                                         float inv_count) {
+                                                         float count_f) {
   float l[1] = {0.0f};
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
     const float d = v[i] - target[i];
-    dv[i] = d * inv_count;
+    dv[i] = d / count_f;   // correctly rounded; d * (1 / count) strays up to 1.5 ulp from the quotient (1.43 seen at count = 255)
     l[0] += 0.5f * d * d;
   }
   block_atomic_sums<1>(l, stats);
@@ -695,7 +698,7 @@ extern "C" int32_t dgppo_value_loss(const float* v, const float* target, float* 
   DGPPO_REQUIRE(v && target && dv && stats, "value_loss: NULL operand");
   const int blocks = cdiv(count, 256);
   hipLaunchKernelGGL(value_loss_kernel, dim3(blocks < 256 ? blocks : 256), dim3(256), 0, (hipStream_t)stream, v, target, dv,
-                     stats, count, 1.0f / (float)count);
+                     stats, count, (float)count);
   DGPPO_LAUNCH_CHECK();
   return 0;
 }

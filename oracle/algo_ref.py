@@ -101,16 +101,29 @@ def cost_weight_schedule(cost_weight, step, train_steps, enabled=False):
     return w
 
 
+def shaped_reward(rewards, costs, cost_weight):
+    """The T_l argument of dgppo/algo/informarl.py:329, negated: r' = reward - w * max(cost, 0).sum(-1).sum(-1), so that
+    l = -r'.  costs [..., n, nh], rewards [...] -> [...], in the dtype of the inputs (float64 in, float64 out); np.maximum
+    propagates a NaN cost like jnp.maximum."""
+    return rewards - cost_weight * np.maximum(costs, 0.0).sum(axis=-1).sum(axis=-1)
+
+
+def informarl_advantage(Ql, Vl, n):
+    """dgppo/algo/informarl.py:334-336: -(Ql - Vl) standardised per env over T (population std, + 1e-8), one copy per
+    agent.  Ql [B,T], Vl [B,T+1] -> [B,T,n], in the dtype of the inputs."""
+    Al = Ql - Vl[:, :-1]
+    Al = (Al - Al.mean(axis=1, keepdims=True)) / (Al.std(axis=1, keepdims=True) + 1e-8)
+    return -np.repeat(Al[:, :, None], n, axis=-1)
+
+
 def informarl_targets(costs, rewards, Vl, gamma, lam, cost_weight):
     """dgppo/algo/informarl.py:323-336.  costs [B,T,n,nh], rewards [B,T], Vl [B,T+1] -> Ql [B,T], A [B,T,n]."""
     B, T, n, nh = costs.shape
     Vh = np.repeat(np.repeat(Vl[:, :, None, None], n, axis=-2), nh, axis=-1).astype(f32)
-    l = (-rewards + f32(cost_weight) * np.maximum(costs, 0.0).sum(axis=-1).sum(axis=-1)).astype(f32)
+    l = (-shaped_reward(rewards, costs, f32(cost_weight))).astype(f32)
     out = [compute_dec_ocp_gae(costs[b], l[b], Vh[b], Vl[b], gamma, lam) for b in range(B)]
     Ql = np.stack([o[1] for o in out])
-    Al = Ql - Vl[:, :-1]
-    Al = (Al - Al.mean(axis=1, keepdims=True)) / (Al.std(axis=1, keepdims=True) + 1e-8)
-    return Ql.astype(f32), (-np.repeat(Al[:, :, None], n, axis=-1)).astype(f32)
+    return Ql.astype(f32), informarl_advantage(Ql, Vl, n).astype(f32)
 
 
 def advantage_lagr(Ql, Vl, Qh, Vh, lagr):

@@ -196,6 +196,19 @@ def lstm_cell(p, c, h, x):
     return new_c, o * torch.tanh(new_c)
 
 
+def lstm_scan(p, c0, h0, xs):
+    """One LSTM layer of RNN (dgppo/nn/rnn.py:22-24) scanned over a chunk, as the update scans the policy over T
+    (dgppo/algo/informarl.py:409-424).  xs [n_grp, T, n_inner, f_in], c0 / h0 [n_grp, n_inner, hid] -> (hs, cs), each
+    [n_grp, T, n_inner, hid]: the output and the cell state after every step.  Runs in the dtype of its arguments."""
+    c, h = c0, h0
+    hs, cs = [], []
+    for tau in range(xs.shape[1]):
+        c, h = lstm_cell(p, c, h, xs[:, tau])
+        hs.append(h)
+        cs.append(c)
+    return torch.stack(hs, 1), torch.stack(cs, 1)
+
+
 def rnn_apply(p_rnn, h, x):
     """RNN (dgppo/nn/rnn.py:14-30) with GRU cells.  p_rnn = the params of 'RNN_0' ({'GRUCell_{2l+1}': ...}: every layer
     instantiates the cell class once for the isinstance probe and once for use) or None (--no-rnn: the net

@@ -144,3 +144,41 @@ def test_lagrangian_advantage_and_multiplier_known_answers():
     # clipped at zero, and the ratio scales the advantage term
     got = A.lagr_update(np.array([[0.01]], np.float32), lp + np.log(2.0).astype(np.float32), lp, Vh_T * 0, -np.abs(Ah_T), 0.9, 1.0)
     assert got[0, 0] == 0.0
+
+
+def test_shaped_reward_known_answers():
+    """informarl.py:329, negated: r' = r - w * (sum over agents and components of the positive parts of the costs)."""
+    cost = np.array([[[0.5, -1.0], [2.0, 0.25]], [[-3.0, -0.5], [-0.0, 0.0]]])          # [rows = 2, n = 2, nh = 2]
+    rew = np.array([-1.0, 4.0])
+    np.testing.assert_array_equal(A.shaped_reward(rew, cost, 2.0), [-1.0 - 2.0 * 2.75, 4.0])
+    np.testing.assert_array_equal(A.shaped_reward(rew, cost, 0.0), rew)
+    assert A.shaped_reward(rew, cost, 2.0).dtype == np.float64
+    assert A.shaped_reward(rew.astype(np.float32), cost.astype(np.float32), np.float32(2.0)).dtype == np.float32
+    # a NaN cost marks its own row only, also a negative-side one times weight 0 (jnp.maximum propagates, 0 * NaN = NaN)
+    cost[1, 0, 1] = np.nan
+    for w in (2.0, 0.0):
+        got = A.shaped_reward(rew, cost, w)
+        assert np.isnan(got[1]) and got[0] == -1.0 - w * 2.75
+    # informarl_targets feeds l = -r' to the GAE: with lambda = 0, Ql = l + gamma * Vl[t + 1]
+    r = np.random.default_rng(0)
+    costs = r.normal(size=(2, 5, 3, 2)).astype(np.float32)
+    rewards = r.normal(size=(2, 5)).astype(np.float32)
+    Vl = r.normal(size=(2, 6)).astype(np.float32)
+    Ql, _ = A.informarl_targets(costs, rewards, Vl, 0.9, 0.0, 0.7)
+    np.testing.assert_allclose(Ql, -A.shaped_reward(rewards.astype(np.float64), costs.astype(np.float64), 0.7) + 0.9 * Vl[:, 1:],
+                               rtol=1e-5, atol=1e-5)
+
+
+def test_informarl_advantage_known_answers():
+    """informarl.py:334-336: Al = Ql - Vl = [1, 3] -> standardised [-1, 1] -> negated, one copy per agent; a constant series
+    (T = 1 included) gives exactly 0; it is the advantage that informarl_targets returns."""
+    Ql = np.array([[2.0, 5.0]]); Vl = np.array([[1.0, 2.0, 9.0]])
+    got = A.informarl_advantage(Ql, Vl, 3)
+    assert got.shape == (1, 2, 3)
+    np.testing.assert_allclose(got[0], [[1.0] * 3, [-1.0] * 3], atol=1e-7)
+    assert not A.informarl_advantage(np.array([[4.0]]), np.array([[1.5, 0.0]]), 2).any()
+    r = np.random.default_rng(1)
+    costs = r.normal(size=(2, 6, 3, 2)).astype(np.float32) - 50.0
+    rewards = r.normal(size=(2, 6)).astype(np.float32); Vl = r.normal(size=(2, 7)).astype(np.float32)
+    Ql, adv = A.informarl_targets(costs, rewards, Vl, 0.99, 0.95, 0.7)
+    np.testing.assert_array_equal(adv, A.informarl_advantage(Ql, Vl, 3).astype(np.float32))

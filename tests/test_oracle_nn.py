@@ -399,6 +399,44 @@ def test_lstm_cell_matches_torch_lstmcell():
     assert T.carry_width({"params": {"RNN_0": prnn}}) == 256
 
 
+def test_lstm_scan_known_answers():
+    """lstm_scan (rnn.py:22-24 scanned over a chunk).  (1) closed form: with all kernels zero and only the g-gate's hidden
+    bias b set, i = f = o = 1/2 and g = tanh(b), so c_t = c_{t-1} / 2 + tanh(b) / 2 and h_t = tanh(c_t) / 2 whatever the
+    input.  (2) against torch.nn.LSTM over the same sequences, float64, with a non-zero initial carry; the layout is
+    [n_grp, T, n_inner, 64] and sequences do not mix."""
+    g = _gen(21)
+    p = T.tree_map(lambda t: torch.zeros_like(t, dtype=torch.float64), T.init_lstm(g, 64, 64))
+    b = 0.7
+    p["hg"]["bias"] += b
+    c0 = torch.randn(2, 3, 64, generator=g, dtype=torch.float64)
+    hs, cs = T.lstm_scan(p, c0, torch.randn(2, 3, 64, generator=g, dtype=torch.float64),
+                         torch.randn(2, 5, 3, 64, generator=g, dtype=torch.float64))
+    assert hs.shape == cs.shape == (2, 5, 3, 64)
+    c = c0
+    for t in range(5):
+        c = 0.5 * c + 0.5 * math.tanh(b)
+        assert torch.allclose(cs[:, t], c, atol=1e-14, rtol=0) and torch.allclose(hs[:, t], 0.5 * torch.tanh(c), atol=1e-14, rtol=0)
+    p = T.tree_map(lambda t: t.double(), T.init_lstm(g, 64, 64))
+    for k in ("hi", "hf", "hg", "ho"):
+        p[k]["bias"] = 0.3 * torch.randn(64, generator=g, dtype=torch.float64)
+    lstm = torch.nn.LSTM(64, 64, batch_first=True).double()
+    with torch.no_grad():
+        lstm.weight_ih_l0.copy_(torch.cat([p["i" + q]["kernel"].T for q in "ifgo"], 0))
+        lstm.weight_hh_l0.copy_(torch.cat([p["h" + q]["kernel"].T for q in "ifgo"], 0))
+        lstm.bias_ih_l0.zero_()
+        lstm.bias_hh_l0.copy_(torch.cat([p["h" + q]["bias"] for q in "ifgo"]))
+    n_grp, T_, n_inner = 3, 7, 2
+    xs = torch.randn(n_grp, T_, n_inner, 64, generator=g, dtype=torch.float64)
+    c0, h0 = (torch.randn(n_grp, n_inner, 64, generator=g, dtype=torch.float64) for _ in range(2))
+    hs, cs = T.lstm_scan(p, c0, h0, xs)
+    seq = xs.permute(0, 2, 1, 3).reshape(n_grp * n_inner, T_, 64)                # one batch row per sequence
+    with torch.no_grad():
+        out, (hT, cT) = lstm(seq, (h0.reshape(1, -1, 64), c0.reshape(1, -1, 64)))
+    assert torch.allclose(hs.permute(0, 2, 1, 3).reshape(n_grp * n_inner, T_, 64), out, atol=1e-12, rtol=0)
+    assert torch.allclose(cs[:, -1].reshape(-1, 64), cT[0], atol=1e-12, rtol=0)
+    assert hs.dtype == torch.float64
+
+
 def test_attn_fixed_fan_in_matches_segment_softmax():
     """the kernel-level attention reference equals the per-edge form (segment_softmax over the unmasked edges into each agent,
     sums of a * [x_s | e]) on a LiDAR Target topology (own goal, own hits); NaN edge features behind the mask and an agent
