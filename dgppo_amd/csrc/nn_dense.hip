@@ -414,10 +414,14 @@ struct DenseBwdWArgs {
 // slab of the caller's workspace and dense_bwd_w_reduce_kernel folds the slabs into dW/db — with hundreds of workgroups
 // finishing together, atomicAdd on the same K*N addresses serialises (measured: 137 us vs 10 us for K=64, N=4).  Only
 // launches of <= 4 workgroups (or a NULL / too small workspace) use atomicAdd directly.
+// NG > 1: a workgroup is NG such 4-wave groups (256 * NG threads, one workgroup per CU), each with its own row chunk of
+// rows_per_block rows and its own pair of LDS tile buffers; they walk their chunks in step (the barrier is the workgroup's),
+// add their accumulators through the tile LDS once the chunks are done, and group 0 writes the workgroup's ONE slab: a
+// CU that kept NG resident workgroups busy wrote NG slabs for the second stage to read back.
 #define BW_ROWS 32
-template <int NT, int KT>
-__global__ void __launch_bounds__(256) dense_bwd_w_kernel(DenseBwdWArgs a) {
-  extern __shared__ float sm[];
+template <int NT, int KT, int NG>
+__global__ void __launch_bounds__(256 * NG) dense_bwd_w_kernel(DenseBwdWArgs a) {
+  extern __shared__ float sm_wg[];
   constexpr int KTW = (KT + 3) / 4;
   // row strides = 16 mod 32 floats: the four slab rows of a fragment read hit disjoint bank halves
   constexpr int Kl = (KT & 1) ? KT * 16 : KT * 16 + 16;
@@ -426,10 +430,16 @@ __global__ void __launch_bounds__(256) dense_bwd_w_kernel(DenseBwdWArgs a) {
   constexpr int XQ = KT * 4, YQ = NT * 4;                      // float4 slots per padded row
   constexpr int PFX = (BW_ROWS * XQ + 255) / 256, PFY = (BW_ROWS * YQ + 255) / 256;
   const int K = a.K, N = a.N;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int grp = NG > 1 ? (int)(threadIdx.x >> 8) : 0;
+  const int tid = threadIdx.x & 255, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 15, lq = lane >> 4;
-  const int m_begin = blockIdx.x * a.rows_per_block;
+  float* sm = sm_wg + grp * 2 * BUF;
+  // group 0 holds the longest chunk of the workgroup: its tile count is everyone's trip count (rows past a group's own
+  // m_end are zeros in LDS), so that every wave meets every barrier
+  const int wg_begin = blockIdx.x * NG * a.rows_per_block;
+  const int m_begin = wg_begin + grp * a.rows_per_block;
   const int m_end = min(a.M, m_begin + a.rows_per_block);
+  const int n_tiles = (min(a.M - wg_begin, a.rows_per_block) + BW_ROWS - 1) / BW_ROWS;
   const bool vec = ((K & 3) == 0) && ((a.ldx & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.X) & 15) == 0) &&
                    ((N & 3) == 0) && ((a.ldy & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.dY) & 15) == 0);
   const int K4 = K >> 2, N4 = N >> 2;
@@ -522,7 +532,7 @@ __global__ void __launch_bounds__(256) dense_bwd_w_kernel(DenseBwdWArgs a) {
     commit(m_begin, 0);
     __syncthreads();
     int cur = 0;
-    for (int m0 = m_begin; m0 < m_end; m0 += BW_ROWS) {
+    for (int it = 0, m0 = m_begin; it < n_tiles; ++it, m0 += BW_ROWS) {
       fetch(m0 + BW_ROWS);                                     // past m_end on the last round: masked to zeros in commit
       __builtin_amdgcn_sched_barrier(0);
       compute(cur);
@@ -531,7 +541,7 @@ __global__ void __launch_bounds__(256) dense_bwd_w_kernel(DenseBwdWArgs a) {
       cur ^= 1;
     }
   } else {
-    for (int m0 = m_begin; m0 < m_end; m0 += BW_ROWS) {
+    for (int it = 0, m0 = m_begin; it < n_tiles; ++it, m0 += BW_ROWS) {
       stage_scalar(m0);
       __syncthreads();
       if (a.db != nullptr && tid < N) {
@@ -546,11 +556,51 @@ __global__ void __launch_bounds__(256) dense_bwd_w_kernel(DenseBwdWArgs a) {
     }
   }
 #undef DGPPO_LDS_BARRIER
+  if (NG > 1) {
+    // groups 1.. park their accumulators and column sums in their own (now idle) tile buffers, lane-major; group 0 adds them
+    constexpr int ACCF = KTW * NT * 4 * 256;
+    static_assert(NG == 1 || ACCF + PFY * 4 * 256 <= 2 * BUF, "dense_bwd_w: the group exchange does not fit the tile buffers");
+    __syncthreads();
+    if (grp > 0) {
+#pragma unroll
+      for (int i = 0; i < KTW; ++i)
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) sm[((i * NT + t) * 4 + r) * 256 + tid] = acc[i][t][r];
+      if (!vec) csum[0].x = colsum;
+#pragma unroll
+      for (int u = 0; u < PFY; ++u) {
+        sm[ACCF + (u * 4 + 0) * 256 + tid] = csum[u].x; sm[ACCF + (u * 4 + 1) * 256 + tid] = csum[u].y;
+        sm[ACCF + (u * 4 + 2) * 256 + tid] = csum[u].z; sm[ACCF + (u * 4 + 3) * 256 + tid] = csum[u].w;
+      }
+    }
+    __syncthreads();
+    if (grp == 0) {
+      for (int g = 1; g < NG; ++g) {
+        const float* o = sm_wg + g * 2 * BUF;
+#pragma unroll
+        for (int i = 0; i < KTW; ++i)
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][t][r] += o[((i * NT + t) * 4 + r) * 256 + tid];
+        if (!vec) colsum += o[ACCF + tid];
+        else {
+#pragma unroll
+          for (int u = 0; u < PFY; ++u) {
+            csum[u].x += o[ACCF + (u * 4 + 0) * 256 + tid]; csum[u].y += o[ACCF + (u * 4 + 1) * 256 + tid];
+            csum[u].z += o[ACCF + (u * 4 + 2) * 256 + tid]; csum[u].w += o[ACCF + (u * 4 + 3) * 256 + tid];
+          }
+        }
+      }
+    }
+  }
   float* slab = a.part ? a.part + (size_t)blockIdx.x * a.part_stride : nullptr;
 #pragma unroll
   for (int i = 0; i < KTW; ++i) {
     const int kt = wave + 4 * i;
-    if (kt >= KT) continue;
+    if (kt >= KT || grp != 0) continue;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int col = t * 16 + li;
@@ -582,12 +632,18 @@ __global__ void __launch_bounds__(256) dense_bwd_w_kernel(DenseBwdWArgs a) {
         for (int r = 0; r < BW_ROWS; ++r) cs += red[r * (YQ * 4) + tid];
       }
     }
-    if (tid < N) {
+    if (tid < N && grp == 0) {
       if (slab) slab[K * N + tid] = cs;
       else atomicAdd(a.db + tid, cs);
     }
   }
 }
+
+// Slabs summed by one thread of the second stage before its atomicAdd.  With one slab per CU (G = 256) 16 gives 16 splits:
+// 16 x E/256 workgroups (784 for a 64 x 192 gradient, 112 for 48 x 32) of four independent 4-deep load chains each, and
+// 16 atomicAdds per element (200 k for the largest gradient, far below the atomic rate).  32 would halve the workgroups
+// of the small gradients, which are latency- and not bandwidth-bound.
+#define REDUCE_SLABS_PER_SPLIT 16
 
 // Second stage: dW[k][n] += sum_g part[g][k*N + n], db[n] += sum_g part[g][K*N + n].  blockIdx.y splits the slabs so
 // that small outputs still fill the device; the splits meet in at most gridDim.y atomicAdds per element.
@@ -636,7 +692,7 @@ __global__ void __launch_bounds__(256) dense_bwd_w_reduce_batch_kernel(ReduceBat
   const int E = K * N + (d.db ? N : 0);
   if (e >= E) return;
   // the same split of the slabs over blockIdx.y as the single reduce kernel: splits meet in <= gridDim.y atomicAdds
-  const int splits = min((int)gridDim.y, max(1, (G + 31) / 32));
+  const int splits = min((int)gridDim.y, max(1, (G + REDUCE_SLABS_PER_SPLIT - 1) / REDUCE_SLABS_PER_SPLIT));
   if ((int)blockIdx.y >= splits) return;
   const int per = (G + splits - 1) / splits;
   const int g0 = blockIdx.y * per, g1 = min(G, g0 + per);
@@ -667,9 +723,33 @@ static void reduce_or_defer(hipStream_t s, const float* part, int stride, int gr
     return;
   }
   const int E = K * N + (db ? N : 0);
-  int splits = cdiv(grid, 32);
+  int splits = cdiv(grid, REDUCE_SLABS_PER_SPLIT);
   splits = splits < 1 ? 1 : (splits > 64 ? 64 : splits);
   hipLaunchKernelGGL(dense_bwd_w_reduce_kernel, dim3(cdiv(E, 256), splits), dim3(256), 0, s, part, stride, grid, dW, ldw, db, K, N);
+}
+
+static int device_cus() {
+  static thread_local int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  }
+  return cus;
+}
+
+// 4-wave groups per workgroup of the slab path: as many as fit a CU's 160 KB of LDS with their tile buffers (what the CU
+// would hold as separate workgroups), at most 4 (1024 threads); 1 where the tile buffers cannot carry the group exchange
+template <int NT, int KT>
+constexpr int bwd_w_groups() {
+  constexpr int KTW = (KT + 3) / 4;
+  constexpr int Kl = (KT & 1) ? KT * 16 : KT * 16 + 16;
+  constexpr int Nl = (NT & 1) ? NT * 16 : NT * 16 + 16;
+  constexpr int BUF2 = 2 * BW_ROWS * (Kl + Nl);
+  constexpr int PFY = (BW_ROWS * NT * 4 + 255) / 256;
+  constexpr int fit = (160 * 1024) / (BUF2 * 4);
+  constexpr bool xch = KTW * NT * 4 * 256 + PFY * 4 * 256 <= BUF2;
+  return (!xch || fit < 2) ? 1 : (fit > 4 ? 4 : fit);
 }
 
 template <int NT, int KT>
@@ -677,23 +757,25 @@ static void launch_bwd_w_kt(DenseBwdWArgs a, hipStream_t s) {
   constexpr int Kl = (KT & 1) ? KT * 16 : KT * 16 + 16;
   constexpr int Nl = (NT & 1) ? NT * 16 : NT * 16 + 16;
   constexpr size_t smem = 2 * sizeof(float) * BW_ROWS * (Kl + Nl);
-  static_assert(smem <= 160 * 1024, "dense_bwd_w tiles exceed the 160 KB LDS of a gfx950 CU");
-  static thread_local int cap = 0;      // resident workgroups on the device, queried once per instantiation
-  if (cap == 0) {
-    int per_cu = 0, dev = 0, cus = 256;
+  constexpr int NG = bwd_w_groups<NT, KT>();
+  static_assert(smem * NG <= 160 * 1024, "dense_bwd_w tiles exceed the 160 KB LDS of a gfx950 CU");
+  static thread_local bool opted = false;
+  if (!opted) {
     if (smem > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_w_kernel<NT, KT>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_w_kernel<NT, KT, 1>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(
-            &dense_bwd_w_kernel<NT, KT>), 256, smem) != hipSuccess || per_cu < 1) per_cu = 1;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-    cap = per_cu * cus;
+    if (NG > 1 && smem * NG > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_w_kernel<NT, KT, NG>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(smem * NG));
+    opted = true;
   }
-  // one resident wave of workgroups; rows per workgroup a multiple of the 32-row tile, at least two tiles
-  int rpb = cdiv(a.M, cap);
+  const int cus = device_cus();
+  // rows per 4-wave group: NG groups on every CU, a multiple of the 32-row tile, at least two tiles
+  int rpb = cdiv(a.M, NG * cus);
   rpb = ((rpb + BW_ROWS - 1) / BW_ROWS) * BW_ROWS;
   if (rpb < 2 * BW_ROWS) rpb = 2 * BW_ROWS;
+  // up to one group per CU the groups stay workgroups of their own (a slab per CU either way, and every CU gets rows)
+  const int ng = cdiv(a.M, rpb) > cus ? NG : 1;
   // partial slabs: stride rounded to 64 floats; shrink the grid if the scratch buffer cannot hold one slab per workgroup
   const int stride = ((a.K * a.N + a.N + 63) / 64) * 64;
   const size_t ws_bytes = a.ws_bytes;
@@ -701,13 +783,14 @@ static void launch_bwd_w_kt(DenseBwdWArgs a, hipStream_t s) {
   if (ws) {
     const long max_slabs = (long)(ws_bytes / (sizeof(float) * stride));
     if (max_slabs < 8) ws = nullptr;
-    else if (cdiv(a.M, rpb) > max_slabs) rpb = ((cdiv(a.M, (int)max_slabs) + BW_ROWS - 1) / BW_ROWS) * BW_ROWS;
+    else if (cdiv(a.M, rpb * ng) > max_slabs) rpb = ((cdiv(a.M, (int)max_slabs * ng) + BW_ROWS - 1) / BW_ROWS) * BW_ROWS;
   }
   a.rows_per_block = rpb;
   a.part = ws;
   a.part_stride = stride;
-  const int grid = cdiv(a.M, rpb);
-  hipLaunchKernelGGL((dense_bwd_w_kernel<NT, KT>), dim3(grid), dim3(256), smem, s, a);
+  const int grid = cdiv(a.M, rpb * ng);
+  if (NG > 1 && ng > 1) hipLaunchKernelGGL((dense_bwd_w_kernel<NT, KT, NG>), dim3(grid), dim3(256 * NG), smem * NG, s, a);
+  else hipLaunchKernelGGL((dense_bwd_w_kernel<NT, KT, 1>), dim3(grid), dim3(256), smem, s, a);
   if (ws) reduce_or_defer(s, ws, stride, grid, a.dW, a.ldw, a.db, a.K, a.N);
 }
 
@@ -854,6 +937,197 @@ int32_t dense_bwd_w_launch(DenseBwdWArgs a, hipStream_t s) {
   return 0;
 }
 
+// ---- GRU weight gradients in one pass ------------------------------------------------------------------------------------
+//   dWi[64,192] += x^T dgi               dbi[192] += colsum(dgi)
+//   dWh[64,192] += hprev^T [dgi[:, :128] | dhn]      dbhn[64] += colsum(dhn)      (hr / hz carry no bias)
+// The same tiling as dense_bwd_w_kernel: 32-row tiles [x | hprev] (128 wide) and [dgi | dhn] (256 wide) double-buffered in
+// LDS, the next tile's rows prefetched into registers while the current one is on the matrix cores, one LDS-only barrier per
+// tile.  One 8-wave workgroup per CU: waves 0-3 accumulate dWi (A = x), waves 4-7 dWh (A = hprev, B = the r / z columns of
+// dgi and dhn) from the SAME tiles, wave w of either half owning output rows 16w..16w+15 x all 12 column tiles.  Every input
+// row is read once (384 floats; the three dense_bwd_w calls this replaces read 576), and a CU writes one slab
+// [dWi | dbi | dWh | dbhn] for the common second stage.
+#define GW_AL 144          // [x | hprev] row: 128 + 16, stride = 16 (mod 32) as in dense_bwd_w_kernel
+#define GW_YL 272          // [dgi | dhn] row: 256 + 16
+#define GW_BUF (BW_ROWS * (GW_AL + GW_YL))
+#define GW_SLAB_WI 0
+#define GW_SLAB_BI (64 * 192)
+#define GW_SLAB_WH (64 * 192 + 192)
+#define GW_SLAB_BHN (2 * 64 * 192 + 192)
+#define GW_SLAB (2 * 64 * 192 + 192 + 64)     // 24832 floats, a multiple of 64
+struct GruBwdWArgs {
+  const float* x; int ldx;
+  const float* hprev; int ldh;
+  const float* dgi;       // [M,192] dense
+  const float* dhn;       // [M,64] dense
+  float* dWi; int ldwi;
+  float* dbi;
+  float* dWh; int ldwh;
+  float* dbhn;
+  int M, rows_per_block;
+  float* part;            // [grid][GW_SLAB] or NULL: atomicAdd straight into the outputs
+};
+
+__global__ void __launch_bounds__(512) gru_bwd_w_kernel(GruBwdWArgs a) {
+  extern __shared__ float sm[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) & 3, half = tid >> 8;
+  const int li = lane & 15, lq = lane >> 4;
+  const int m_begin = blockIdx.x * a.rows_per_block;
+  const int m_end = min(a.M, m_begin + a.rows_per_block);
+  f32x4 acc[12];
+#pragma unroll
+  for (int t = 0; t < 12; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // float4 slots of a tile: [x | hprev] 32 rows x 32 quads (2 per thread), [dgi | dhn] 32 rows x 64 quads (4 per thread);
+  // a thread's four [dgi | dhn] slots are the SAME column quad (512 = 8 rows x 64 quads), so one float4 carries its column sums
+  float4 pfa[2], pfy[4];
+  float4 csum = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int qa = tid & 31, ra = tid >> 5, qy = tid & 63, ry = tid >> 6;
+  auto fetch = [&](int m0) {            // rows clamped; masking happens in commit
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      int row = m0 + u * 16 + ra;
+      row = row < a.M ? row : a.M - 1;
+      const float* src = qa < 16 ? a.x + (size_t)row * a.ldx + 4 * qa : a.hprev + (size_t)row * a.ldh + 4 * (qa - 16);
+      pfa[u] = *reinterpret_cast<const float4*>(src);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      int row = m0 + u * 8 + ry;
+      row = row < a.M ? row : a.M - 1;
+      const float* src = qy < 48 ? a.dgi + (size_t)row * 192 + 4 * qy : a.dhn + (size_t)row * 64 + 4 * (qy - 48);
+      pfy[u] = *reinterpret_cast<const float4*>(src);
+    }
+  };
+  auto commit = [&](int m0, int b) {    // registers -> LDS buffer b; rows >= m_end become zeros
+    float* as = sm + b * GW_BUF;
+    float* ys = as + BW_ROWS * GW_AL;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int r = u * 16 + ra;
+      const float4 v = (m0 + r < m_end) ? pfa[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(as + r * GW_AL + 4 * qa) = v;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int r = u * 8 + ry;
+      const float4 v = (m0 + r < m_end) ? pfy[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(ys + r * GW_YL + 4 * qy) = v;
+      csum.x += v.x; csum.y += v.y; csum.z += v.z; csum.w += v.w;
+    }
+  };
+  auto compute = [&](int b) {
+    // A[i = k][kk = m] = [x | hprev][m][64 half + 16 wave + k], B[kk = m][j] = [dgi | dhn][m][column tile]
+    const float* as = sm + b * GW_BUF + lq * GW_AL + half * 64 + wave * 16 + li;
+    const float* ys = sm + b * GW_BUF + BW_ROWS * GW_AL + lq * GW_YL + li;
+    const float* yh = ys + (half ? 64 : 0);              // dWh's column tiles 8..11 are dhn: LDS columns 192..255
+#pragma unroll
+    for (int s4 = 0; s4 < BW_ROWS / 4; ++s4) {
+      float bv[12];
+#pragma unroll
+      for (int t = 0; t < 8; ++t) bv[t] = ys[s4 * 4 * GW_YL + t * 16];
+#pragma unroll
+      for (int t = 8; t < 12; ++t) bv[t] = yh[s4 * 4 * GW_YL + t * 16];
+      const float av = as[s4 * 4 * GW_AL];
+#pragma unroll
+      for (int t = 0; t < 12; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[t], acc[t], 0, 0, 0);
+    }
+  };
+  fetch(m_begin);
+  commit(m_begin, 0);
+  __syncthreads();
+  int cur = 0;
+  for (int m0 = m_begin; m0 < m_end; m0 += BW_ROWS) {
+    fetch(m0 + BW_ROWS);                                   // past m_end on the last round: masked to zeros in commit
+    __builtin_amdgcn_sched_barrier(0);
+    compute(cur);
+    commit(m0 + BW_ROWS, cur ^ 1);
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    cur ^= 1;
+  }
+  float* slab = a.part ? a.part + (size_t)blockIdx.x * GW_SLAB : nullptr;
+  {
+    float* out = half ? a.dWh : a.dWi;
+    const int ldo = half ? a.ldwh : a.ldwi;
+    float* sl = slab ? slab + (half ? GW_SLAB_WH : GW_SLAB_WI) : nullptr;
+#pragma unroll
+    for (int t = 0; t < 12; ++t) {
+      const int col = t * 16 + li;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int krow = wave * 16 + lq * 4 + r;
+        if (sl) sl[krow * 192 + col] = acc[t][r];
+        else atomicAdd(out + (size_t)krow * ldo + col, acc[t][r]);
+      }
+    }
+  }
+  // column sums: red[row slot 0..7][256 columns] through LDS (the tile buffers are idle now)
+  __syncthreads();
+  *reinterpret_cast<float4*>(sm + ry * 256 + 4 * qy) = csum;
+  __syncthreads();
+  if (tid < 256) {
+    float cs = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) cs += sm[r * 256 + tid];
+    if (tid < 192) {
+      if (slab) slab[GW_SLAB_BI + tid] = cs;
+      else atomicAdd(a.dbi + tid, cs);
+    } else {
+      if (slab) slab[GW_SLAB_BHN + tid - 192] = cs;
+      else atomicAdd(a.dbhn + tid - 192, cs);
+    }
+  }
+}
+
+extern "C" int64_t dgppo_gru_bwd_w_workspace_bytes(void) { return (int64_t)GW_SLAB * sizeof(float) * device_cus(); }
+
+extern "C" int32_t dgppo_gru_bwd_w(const float* x, int32_t ldx, const float* hprev, int32_t ldh, const float* dgi,
+                                   const float* dhn, float* dWi, int32_t ldwi, float* dbi, float* dWh, int32_t ldwh,
+                                   float* dbhn, int32_t M, float* workspace, int64_t workspace_bytes,
+                                   dgppo_reduce_desc* pending, void* stream) {
+  DGPPO_REQUIRE(M >= 0, "gru_bwd_w: bad M");
+  DGPPO_REQUIRE(x && hprev && dgi && dhn && dWi && dbi && dWh && dbhn, "gru_bwd_w: NULL operand");
+  DGPPO_REQUIRE(ldx >= 64 && ldh >= 64 && ldwi >= 192 && ldwh >= 192, "gru_bwd_w: leading dimensions too small");
+  DGPPO_REQUIRE((ldx & 3) == 0 && (ldh & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hprev) |
+                 reinterpret_cast<uintptr_t>(dgi) | reinterpret_cast<uintptr_t>(dhn)) & 15) == 0,
+                "gru_bwd_w: x, hprev, dgi, dhn must be 16-byte aligned with leading dimensions that are multiples of 4");
+  DGPPO_REQUIRE(workspace_bytes >= 0 && (workspace != nullptr || workspace_bytes == 0), "gru_bwd_w: bad workspace");
+  DGPPO_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "gru_bwd_w: workspace must be 16-byte aligned");
+  if (pending) pending[0].pending = pending[1].pending = pending[2].pending = 0;
+  if (M == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  constexpr size_t smem = 2 * sizeof(float) * GW_BUF;
+  static_assert(smem <= 160 * 1024, "gru_bwd_w tiles exceed the 160 KB LDS of a gfx950 CU");
+  static thread_local bool opted = false;
+  if (!opted) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_bwd_w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    opted = true;
+  }
+  // one workgroup per CU; rows per workgroup a multiple of the 32-row tile, at least two tiles
+  int rpb = cdiv(M, device_cus());
+  rpb = ((rpb + BW_ROWS - 1) / BW_ROWS) * BW_ROWS;
+  if (rpb < 2 * BW_ROWS) rpb = 2 * BW_ROWS;
+  float* ws = cdiv(M, rpb) > 4 ? workspace : nullptr;      // <= 4 workgroups: atomicAdd, as dense_bwd_w
+  if (ws) {
+    const long max_slabs = (long)(workspace_bytes / (sizeof(float) * GW_SLAB));
+    if (max_slabs < 8) ws = nullptr;
+    else if (cdiv(M, rpb) > max_slabs) rpb = ((cdiv(M, (int)max_slabs) + BW_ROWS - 1) / BW_ROWS) * BW_ROWS;
+  }
+  const int grid = cdiv(M, rpb);
+  GruBwdWArgs a{x, ldx, hprev, ldh, dgi, dhn, dWi, ldwi, dbi, dWh, ldwh, dbhn, M, rpb, ws};
+  hipLaunchKernelGGL(gru_bwd_w_kernel, dim3(grid), dim3(512), smem, s, a);
+  DGPPO_LAUNCH_CHECK();
+  if (!ws) return 0;
+  // second stage: dWi with its bias row, dWh without one, dbhn as a [1,64] matrix
+  dgppo_reduce_desc d[3];
+  d[0] = dgppo_reduce_desc{ws + GW_SLAB_WI, dWi, dbi, GW_SLAB, grid, ldwi, 64, 192, 1};
+  d[1] = dgppo_reduce_desc{ws + GW_SLAB_WH, dWh, nullptr, GW_SLAB, grid, ldwh, 64, 192, 1};
+  d[2] = dgppo_reduce_desc{ws + GW_SLAB_BHN, dbhn, nullptr, GW_SLAB, grid, 64, 1, 64, 1};
+  if (pending) {
+    pending[0] = d[0]; pending[1] = d[1]; pending[2] = d[2];
+    return 0;
+  }
+  return dgppo_dense_bwd_w_reduce_batch(d, 3, stream);
+}
+
 extern "C" int32_t dgppo_dense_fwd(const float* X, int32_t ldx, const float* W, int32_t ldw, const float* bias, float* Y,
                                    int32_t ldy, int32_t M, int32_t K, int32_t N, int32_t act, int32_t accumulate,
                                    int32_t trans_w, const float* relu_mask, int32_t ldm, void* stream) {
@@ -901,7 +1175,7 @@ extern "C" int32_t dgppo_dense_bwd_w_reduce_batch(const dgppo_reduce_desc* descs
       gmax = descs[i].slabs > gmax ? descs[i].slabs : gmax;
     }
     if (b.n == 0) continue;
-    int splits = cdiv(gmax, 32);
+    int splits = cdiv(gmax, REDUCE_SLABS_PER_SPLIT);
     splits = splits < 1 ? 1 : (splits > 64 ? 64 : splits);
     hipLaunchKernelGGL(dense_bwd_w_reduce_batch_kernel, dim3(cdiv(emax, 256), splits, b.n), dim3(256), 0, (hipStream_t)stream, b);
   }
@@ -909,8 +1183,8 @@ extern "C" int32_t dgppo_dense_bwd_w_reduce_batch(const dgppo_reduce_desc* descs
   return 0;
 }
 
-// one slab of K*N + N floats (rounded to 64) per resident workgroup; 1024 workgroups cover every instantiation's
-// residency (<= 4 per CU x 256 CUs)
+// one slab of K*N + N floats (rounded to 64) per workgroup: the MFMA kernels launch at most one per CU, the narrow-K
+// kernel up to 1024
 extern "C" int64_t dgppo_dense_bwd_w_workspace_bytes(int32_t K, int32_t N) {
   if (K < 1 || N < 1) return 0;
   const int64_t stride = (((int64_t)K * N + N + 63) / 64) * 64;

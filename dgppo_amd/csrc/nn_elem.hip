@@ -175,6 +175,7 @@ struct GruArgs {
   const float* dhs;     // [rows, 64] gradient w.r.t. every step's output
   float* dgi;           // [rows, 192]
   float* dgh;           // [rows, 192]  (da_r | da_z | d hn_lin) -> dWh = hprev^T dgh, dbhn = colsum(dgh[:,128:])
+  float* dhn;           // [rows, 64]   d hn_lin alone (the DHN_ONLY form: dgh's r / z columns are dgi's, not written twice)
   int n_seq, T, n_inner;
 };
 
@@ -332,8 +333,9 @@ __global__ void __launch_bounds__(256) gru_fwd_kernel(GruArgs a) {
 // MFMA output layout), so the carried dh lives in registers: dh_prev = dh * z + (dgh Wh^T), the product running on the
 // matrix cores with the Wh^T fragments (48 k-steps x 1 column tile) resident in registers.  dgh tiles are
 // double-buffered in LDS: one LDS-only barrier per step.  The saved gates / hprev / upstream gradient of step tau-1 are
-// requested while step tau's product runs.
-template <int RTW>
+// requested while step tau's product runs.  DHN_ONLY: the hidden-side gradient leaves as dhn [rows,64] instead of
+// dgh [rows,192] (whose r / z columns repeat dgi's); everything else, and every value written, is the same.
+template <int RTW, bool DHN_ONLY>
 __global__ void __launch_bounds__(256) gru_bwd_kernel(GruArgs a) {
   extern __shared__ float sm[];
   constexpr int RB = 16 * RTW;
@@ -402,8 +404,12 @@ __global__ void __launch_bounds__(256) gru_bwd_kernel(GruArgs a) {
             const size_t row = (size_t)(row0[rt][r] + tau * a.n_inner);
             float* o = a.dgi + row * 192 + c;
             o[0] = dar; o[64] = daz; o[128] = dan;
-            float* p = a.dgh + row * 192 + c;
-            p[0] = dar; p[64] = daz; p[128] = dhn;
+            if (DHN_ONLY) {
+              a.dhn[row * GRU_H + c] = dhn;
+            } else {
+              float* p = a.dgh + row * 192 + c;
+              p[0] = dar; p[64] = daz; p[128] = dhn;
+            }
           }
         }
       GRU_LDS_BARRIER();
@@ -478,30 +484,43 @@ extern "C" int32_t dgppo_gru_fwd(const float* gi, const float* Wh, const float* 
   return 0;
 }
 
+template <bool DHN_ONLY>
+static int32_t gru_bwd_launch(GruArgs a, hipStream_t stream) {
+  int32_t rc = gru_check(a);
+  if (rc) return rc;
+  if (a.n_seq == 0) return 0;
+  DGPPO_REQUIRE(a.dhs && a.Wh && a.hprev && a.gates && a.dgi && (DHN_ONLY ? a.dhn : a.dgh), "gru_bwd: NULL operand");
+  if (cdiv(a.n_seq, 32) >= 512) {
+    const size_t smem = sizeof(float) * 2 * 32 * GRU_WL;
+    static thread_local int cap = 0;
+    if (cap == 0) cap = gru_resident(reinterpret_cast<const void*>(&gru_bwd_kernel<2, DHN_ONLY>), smem);
+    const int tiles = cdiv(a.n_seq, 32);
+    hipLaunchKernelGGL((gru_bwd_kernel<2, DHN_ONLY>), dim3(tiles < cap ? tiles : cap), dim3(256), smem, stream, a);
+  } else {
+    const size_t smem = sizeof(float) * 2 * 16 * GRU_WL;
+    static thread_local int cap = 0;
+    if (cap == 0) cap = gru_resident(reinterpret_cast<const void*>(&gru_bwd_kernel<1, DHN_ONLY>), smem);
+    const int tiles = cdiv(a.n_seq, 16);
+    hipLaunchKernelGGL((gru_bwd_kernel<1, DHN_ONLY>), dim3(tiles < cap ? tiles : cap), dim3(256), smem, stream, a);
+  }
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int32_t dgppo_gru_bwd(const float* dhs, const float* Wh, const float* hprev, const float* gates, float* dgi,
                                  float* dgh, int32_t n_seq, int32_t T, int32_t n_inner, void* stream) {
   GruArgs a{};
   a.dhs = dhs; a.Wh = Wh; a.hprev = (float*)hprev; a.gates = (float*)gates; a.dgi = dgi; a.dgh = dgh;
   a.n_seq = n_seq; a.T = T; a.n_inner = n_inner;
-  int32_t rc = gru_check(a);
-  if (rc) return rc;
-  if (n_seq == 0) return 0;
-  DGPPO_REQUIRE(dhs && Wh && hprev && gates && dgi && dgh, "gru_bwd: NULL operand");
-  if (cdiv(n_seq, 32) >= 512) {
-    const size_t smem = sizeof(float) * 2 * 32 * GRU_WL;
-    static thread_local int cap = 0;
-    if (cap == 0) cap = gru_resident(reinterpret_cast<const void*>(&gru_bwd_kernel<2>), smem);
-    const int tiles = cdiv(n_seq, 32);
-    hipLaunchKernelGGL(gru_bwd_kernel<2>, dim3(tiles < cap ? tiles : cap), dim3(256), smem, (hipStream_t)stream, a);
-  } else {
-    const size_t smem = sizeof(float) * 2 * 16 * GRU_WL;
-    static thread_local int cap = 0;
-    if (cap == 0) cap = gru_resident(reinterpret_cast<const void*>(&gru_bwd_kernel<1>), smem);
-    const int tiles = cdiv(n_seq, 16);
-    hipLaunchKernelGGL(gru_bwd_kernel<1>, dim3(tiles < cap ? tiles : cap), dim3(256), smem, (hipStream_t)stream, a);
-  }
-  DGPPO_LAUNCH_CHECK();
-  return 0;
+  return gru_bwd_launch<false>(a, (hipStream_t)stream);
+}
+
+extern "C" int32_t dgppo_gru_bwd_dhn(const float* dhs, const float* Wh, const float* hprev, const float* gates, float* dgi,
+                                     float* dhn, int32_t n_seq, int32_t T, int32_t n_inner, void* stream) {
+  GruArgs a{};
+  a.dhs = dhs; a.Wh = Wh; a.hprev = (float*)hprev; a.gates = (float*)gates; a.dgi = dgi; a.dhn = dhn;
+  a.n_seq = n_seq; a.T = T; a.n_inner = n_inner;
+  return gru_bwd_launch<true>(a, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -321,7 +321,9 @@ class Net:
         simple = (self.rnn == "gru" and L == 1)           # the reference default: every fused kernel applies
         if simple:
             hs = hs_out if hs_out is not None else A.get(f"{tag}.hs", Rh, HID)
-            hprev = A.get(f"{tag}.hprev", Rh, HID) if train else None
+            # one step from a given carry: h before the step IS h0, which the backward reads in place of a saved copy
+            hprev_is_h0 = train and T == 1 and h0 is not None and self.kind != "policy"
+            hprev = A.get(f"{tag}.hprev", Rh, HID) if (train and not hprev_is_h0) else None
             gates = A.get(f"{tag}.gates", Rh, 4 * HID) if train else None
             feat = hs
             act["hs"], act["hprev"], act["gates"] = hs, hprev, gates
@@ -331,6 +333,8 @@ class Net:
         fused_tail = (simple and T == 1 and self.kind == "policy")
         if simple and not fused_tail:
             K.gru_fwd(gi, self.p("gru.Wh"), self.p("gru.bhn"), h0, hs, hprev, gates, n_seq, T, n_inner)
+            if hprev_is_h0:
+                act["hprev"] = h0
         if self.rnn == "none":
             # no cell: the MLP output is the feature and the carry passes through unchanged (policy.py:29-33)
             feat = act["y2"]
@@ -474,6 +478,19 @@ class Net:
             dy = dhs
         else:
             stack = act.get("stack") or [dict(x=None, gi=act["gi"], hs=act["hs"], hprev=act["hprev"], gates=act["gates"])]
+            if act.get("stack") is None and dout.is_cuda:
+                # one GRU layer: the backward scan leaves (dgi, dhn) and ONE kernel turns them into dWi, dbi, dWh, dbhn
+                st = stack[0]
+                dgi = A.get(f"{tag}.dgi0", Rh, 3 * HID)
+                dhn = A.get(f"{tag}.dhn0", Rh, HID)
+                K.gru_bwd_dhn(dhs, self.p("gru.Wh"), st["hprev"], st["gates"], dgi, dhn, n_seq, T, n_inner)
+                K.gru_bwd_w(act["y2"], st["hprev"], dgi, dhn, self.g("gru.Wi"), self.g("gru.bi"), self.g("gru.Wh"), self.g("gru.bhn"))
+                if fused_trunk:
+                    dgi0 = dgi
+                else:
+                    dhs = A.get(f"{tag}.dy", Rh, HID)
+                    K.dense_fwd(dgi, self.p("gru.Wi"), None, dhs, trans_w=True)
+                stack = []
             for l in range(len(stack) - 1, -1, -1):
                 st = stack[l]
                 pre = "gru" if l == 0 else f"gru{l}"

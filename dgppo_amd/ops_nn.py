@@ -419,6 +419,53 @@ def gru_bwd(dhs, Wh, hprev, gates, dgi, dgh, n_seq, T, n_inner):
     N.check(rc, "dgppo_gru_bwd")
 
 
+def gru_bwd_dhn(dhs, Wh, hprev, gates, dgi, dhn, n_seq, T, n_inner):
+    """gru_bwd without the duplicate r / z columns: dgi [rows,192] and dhn [rows,64] (= dgh[:, 128:]) for gru_bwd_w"""
+    rows = n_seq * T
+    N.expect_shape(dhs, (rows, 64), "dhs")
+    N.expect_shape(dgi, (rows, 192), "dgi")
+    N.expect_shape(dhn, (rows, 64), "dhn")
+    FLOPS[0] += 2.0 * rows * 64 * 192
+    rc = N.lib().dgppo_gru_bwd_dhn(_p(dhs), _p(Wh), _p(hprev), _p(gates), _p(dgi), _p(dhn), n_seq, T, n_inner, N.stream_ptr())
+    N.check(rc, "dgppo_gru_bwd_dhn")
+
+
+def gru_bwd_w(x, hprev, dgi, dhn, dWi, dbi, dWh, dbhn):
+    """dWi += x.T @ dgi ; dbi += dgi.sum(0) ; dWh += hprev.T @ [dgi[:, :128] | dhn] ; dbhn += dhn.sum(0) in one pass over the
+    rows (inside `with BwdWBatch(...)`: the slab reductions are deferred to the batch's flush, like dense_bwd_w's)"""
+    xp, ldx, M, Kx = _mat(x, "x")
+    hp, ldh, Mh, Kh = _mat(hprev, "hprev")
+    wip, ldwi, _, _ = _mat(dWi, "dWi")
+    whp, ldwh, _, _ = _mat(dWh, "dWh")
+    if Kx != 64 or (Mh, Kh) != (M, 64) or tuple(dWi.shape) != (64, 192) or tuple(dWh.shape) != (64, 192):
+        raise ValueError(f"gru_bwd_w: shape mismatch x{tuple(x.shape)} hprev{tuple(hprev.shape)} dWi{tuple(dWi.shape)} "
+                         f"dWh{tuple(dWh.shape)}")
+    N.expect_shape(dgi, (M, 192), "dgi"); N.expect_shape(dhn, (M, 64), "dhn")
+    N.expect_shape(dbi, (192,), "dbi"); N.expect_shape(dbhn, (64,), "dbhn")
+    FLOPS[0] += 2.0 * M * 64 * (128 + 64 + 192)      # the three dense_bwd_w calls this replaces
+    lib = N.lib()
+    lib.dgppo_gru_bwd_w_workspace_bytes.restype = C.c_int64
+    need = int(lib.dgppo_gru_bwd_w_workspace_bytes())
+    batch = BwdWBatch._active.get((x.device.index, torch.cuda.current_stream(x.device).cuda_stream)) if x.is_cuda else None
+    if batch is not None:
+        ws = batch.region(need)
+        d = (ReduceDesc * 3)()
+        pend = d
+    else:
+        key = (x.device.index, torch.cuda.current_stream(x.device).cuda_stream, "gru")
+        ws = _WS.get(key)
+        if ws is None or ws.numel() * 4 < need:
+            ws = _WS[key] = torch.empty(need // 4, dtype=torch.float32, device=x.device)
+        pend = None
+    rc = lib.dgppo_gru_bwd_w(xp, ldx, hp, ldh, _p(dgi, "dgi"), _p(dhn, "dhn"), wip, ldwi, _p(dbi, "dbi"), whp, ldwh,
+                             _p(dbhn, "dbhn"), M, _p(ws, "workspace"), C.c_int64(ws.numel() * 4), pend, N.stream_ptr())
+    N.check(rc, "dgppo_gru_bwd_w")
+    if batch is not None:
+        for i in range(3):
+            if d[i].pending:
+                batch.descs.append(ReduceDesc.from_buffer_copy(d[i]))
+
+
 def policy_head(ms, eps, action_in, action, log_pi, entropy, n_agents, mode, log_pi_old=None, adv=None, dms=None,
                 stats=None, clip_eps=0.25, coef_ent=0.01):
     rows = ms.shape[0]

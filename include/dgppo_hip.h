@@ -284,8 +284,8 @@ int32_t dgppo_gru1_head_fwd(const float* gi, const float* Wh, const float* bhn, 
                             float* u, float* out, int32_t M, int32_t n_out, void* stream);
 /* Scratch for dgppo_dense_bwd_w's two-stage reduction (per-workgroup partial sums, then one reduce kernel): the caller
  * owns it, like every other buffer (16-byte aligned device memory, reusable by consecutive calls on one stream).  The
- * returned size lets every resident workgroup keep its own slab; a smaller buffer shrinks the grid, NULL / 0 falls back
- * to atomicAdd into dW (correct, slower).  No reference counterpart (XLA owns its scratch allocations).      */
+ * returned size lets every workgroup keep its own slab (the MFMA kernels write one per CU, the narrow-K kernel up to
+ * 1024); a smaller buffer shrinks the grid, NULL / 0 falls back to atomicAdd into dW (correct, slower).  No reference counterpart (XLA owns its scratch allocations).      */
 int64_t dgppo_dense_bwd_w_workspace_bytes(int32_t K, int32_t N);
 
 /* Compact record -> per-graph dense features for the GNN: agent node rows Xa [G*n,Fp], other node rows
@@ -361,6 +361,21 @@ int32_t dgppo_gru_fwd(const float* gi, const float* Wh, const float* bhn, const 
 /* BPTT over the T steps of every sequence: dgi [rows,192], dgh [rows,192] (then dWh = hprev^T dgh).               */
 int32_t dgppo_gru_bwd(const float* dhs, const float* Wh, const float* hprev, const float* gates, float* dgi,
                       float* dgh, int32_t n_seq, int32_t T, int32_t n_inner, void* stream);
+/* The same BPTT without the duplicate: dgh's r / z columns ARE dgi's, so only its third block leaves the kernel, as
+ * dhn [rows,64] (= dgh[:,128:], bit for bit; dgi is bit for bit dgppo_gru_bwd's).  Feeds dgppo_gru_bwd_w.            */
+int32_t dgppo_gru_bwd_dhn(const float* dhs, const float* Wh, const float* hprev, const float* gates, float* dgi,
+                          float* dhn, int32_t n_seq, int32_t T, int32_t n_inner, void* stream);
+/* All weight gradients of one GRU layer from one pass over its rows (jax.grad of flax GRUCell, dgppo/nn/rnn.py:14-30):
+ * dWi [64,ldwi >= 192] += x^T dgi, dbi [192] += colsum(dgi), dWh [64,ldwh >= 192] += hprev^T [dgi[:,:128] | dhn],
+ * dbhn [64] += colsum(dhn) (the hr / hz Denses have no bias).  x [M,ldx], hprev [M,ldh]; dgi [M,192] and dhn [M,64] dense;
+ * all four 16-byte aligned, ldx / ldh multiples of 4.  workspace: dgppo_gru_bwd_w_workspace_bytes() bytes for one partial
+ * slab per CU (smaller: fewer, longer workgroups; NULL / 0 or M <= 256: atomicAdd into the outputs).  pending: NULL reduces
+ * the slabs now; otherwise [3] descriptors receive the owed reductions (pending = 0 where none is) for
+ * dgppo_dense_bwd_w_reduce_batch, under the contract of dgppo_dense_bwd_w_deferred.                                      */
+int64_t dgppo_gru_bwd_w_workspace_bytes(void);
+int32_t dgppo_gru_bwd_w(const float* x, int32_t ldx, const float* hprev, int32_t ldh, const float* dgi, const float* dhn,
+                        float* dWi, int32_t ldwi, float* dbi, float* dWh, int32_t ldwh, float* dbhn, int32_t M,
+                        float* workspace, int64_t workspace_bytes, dgppo_reduce_desc* pending, void* stream);
 
 /* LSTM scan (train.py --use-lstm; dgppo/nn/rnn.py:22-24 with flax nn.LSTMCell(64): i,f,o sigmoid, g tanh, c' = f c + i g,
  * h' = o tanh(c'), carry (c, h)).  zi [rows,256] = x [W_ii|W_if|W_ig|W_io] precomputed (flax's input Denses have no bias);

@@ -68,6 +68,25 @@ if which in ("all", "elem"):
     timeit("gru_bwd n_seq=8192 T=16", lambda: K.gru_bwd(hs, Wh, hp, gt, dgi, dgh, R // 16, 16, 8))
     h0 = torch.randn(32768, 64, device=dev); gi1 = torch.randn(32768, 192, device=dev); hs1 = torch.empty(32768, 64, device=dev)
     timeit("gru_fwd rollout n_seq=32768 T=1", lambda: K.gru_fwd(gi1, Wh, bh, h0, hs1, None, None, 32768, 1, 8))
+if which in ("all", "gruw"):
+    # the GRU backward's two forms and its weight gradients: one pass against the three dense_bwd_w calls it replaces
+    for M, T_ in ((R, 16), (R, 1), (16384, 16)):
+        Wh = torch.randn(64, 192, device=dev) * 0.1
+        x = torch.randn(M, 64, device=dev); hp = torch.randn(M, 64, device=dev); gt = torch.rand(M, 256, device=dev)
+        dhs = torch.randn(M, 64, device=dev)
+        dgi = torch.empty(M, 192, device=dev); dgh = torch.empty(M, 192, device=dev); dhn = torch.empty(M, 64, device=dev)
+        dWi = torch.zeros(64, 192, device=dev); dbi = torch.zeros(192, device=dev)
+        dWh = torch.zeros(64, 192, device=dev); dbhn = torch.zeros(64, device=dev)
+        timeit(f"gru_bwd (dgi, dgh) M={M} T={T_}", lambda: K.gru_bwd(dhs, Wh, hp, gt, dgi, dgh, M // T_, T_, 8), bytes_=4.0 * M * 832)
+        timeit(f"gru_bwd_dhn (dgi, dhn) M={M} T={T_}", lambda: K.gru_bwd_dhn(dhs, Wh, hp, gt, dgi, dhn, M // T_, T_, 8), bytes_=4.0 * M * 704)
+
+        def three():
+            K.dense_bwd_w(hp, dgh[:, :128], dWh[:, :128], None)
+            K.dense_bwd_w(hp, dgh[:, 128:], dWh[:, 128:], dbhn)
+            K.dense_bwd_w(x, dgi, dWi, dbi)
+        timeit(f"GRU weight gradients: 3 x dense_bwd_w M={M}", three, flops=2.0 * M * 64 * 384, bytes_=4.0 * M * 576)
+        timeit(f"GRU weight gradients: gru_bwd_w M={M}", lambda: K.gru_bwd_w(x, hp, dgi, dhn, dWi, dbi, dWh, dbhn),
+               flops=2.0 * M * 64 * 384, bytes_=4.0 * M * 384)
 if which in ("all", "attn"):
     cfg = N.make_env_cfg(0, 8, 3)
     for G in (16384, 4096):
