@@ -431,9 +431,11 @@ struct AdvLagrArgs {
 
 // informarl_lagr.py:219-235: Al = (Ql - Vl) standardised per env over T, negated; Ah = (Qh - Vh) standardised per
 // (env, agent, component) over T; A = -Al - mean_h(Ah * lagr[a, h]).  One workgroup per env; population std, + 1e-8.
+// The per-series arrays hold every admitted team: 64 agents x 3 costs (MPEConnectSpread) = 192 columns.
+#define ADV_LAGR_MAX_COLS 192
 __global__ void __launch_bounds__(256) adv_lagr_kernel(AdvLagrArgs a) {
   __shared__ float red[256];
-  __shared__ float s_mean[1 + 64], s_den[1 + 64];
+  __shared__ float s_mean[1 + ADV_LAGR_MAX_COLS], s_den[1 + ADV_LAGR_MAX_COLS];
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const int T = a.T, n = a.n, nh = a.nh, AH = n * nh;
   const float* Ql = a.Ql + (size_t)b * T;
@@ -477,7 +479,8 @@ __global__ void __launch_bounds__(256) adv_lagr_kernel(AdvLagrArgs a) {
 extern "C" int32_t dgppo_advantage_lagr(const float* Ql, const float* Vl, const float* Qh, const float* Vh,
                                         const float* lagr, float* adv, float* Ah, int32_t B, int32_t T, int32_t n,
                                         int32_t nh, void* stream) {
-  DGPPO_REQUIRE(B >= 0 && T >= 1 && n >= 1 && nh >= 1 && n * nh <= 64, "advantage_lagr: bad sizes (n * nh <= 64)");
+  DGPPO_REQUIRE(B >= 0 && T >= 1 && n >= 1 && nh >= 1 && (long)n * nh <= ADV_LAGR_MAX_COLS,
+                "advantage_lagr: bad sizes (n * nh <= 192)");
   if (B == 0) return 0;
   DGPPO_REQUIRE(Ql && Vl && Qh && Vh && lagr && adv && Ah, "advantage_lagr: NULL operand");
   AdvLagrArgs a{Ql, Vl, Qh, Vh, lagr, adv, Ah, B, T, n, nh};

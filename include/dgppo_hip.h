@@ -424,7 +424,8 @@ int32_t dgppo_advantage(const float* Ql, const float* Vl, const float* Vh, float
                         void* stream);
 /* InforMARL-Lagrangian advantage (dgppo/algo/informarl_lagr.py:219-235): Al = (Ql - Vl) standardised per env over T, Ah =
  * (Qh - Vh[:, :T]) standardised per (env, agent, component) over T (population std, + 1e-8), adv = -Al - mean_h(Ah *
- * lagr[a,h]).  Ql [B,T], Vl [B,T+1], Qh [B,T,n,nh], Vh [B,T+1,n,nh], lagr [n,nh] -> adv [B,T,n], Ah [B,T,n,nh].          */
+ * lagr[a,h]).  Ql [B,T], Vl [B,T+1], Qh [B,T,n,nh], Vh [B,T+1,n,nh], lagr [n,nh] -> adv [B,T,n], Ah [B,T,n,nh].
+ * n * nh <= 192 (64 agents x 3 costs, every admitted team); more columns are refused before anything is launched.        */
 int32_t dgppo_advantage_lagr(const float* Ql, const float* Vl, const float* Qh, const float* Vh, const float* lagr,
                              float* adv, float* Ah, int32_t B, int32_t T, int32_t n, int32_t nh, void* stream);
 /* update_lagr (informarl_lagr.py:286-309) on one minibatch of n_env envs: delta[a,h] = -mean_{env,t}(Vh (1 - gamma) +

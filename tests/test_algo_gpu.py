@@ -31,16 +31,20 @@ def test_gae(cuda, B, T, n, nh, lam):
     np.testing.assert_allclose(Ql.cpu().numpy(), Ql_w, rtol=0, atol=1e-5)
 
 
-@pytest.mark.parametrize("family", ["cols", "rows", "generic"])
+@pytest.mark.parametrize("family", ["cols", "rows", "generic", "generic above 64 KB"])
 def test_gae_propagates_nan_like_the_reference(cuda, family):
     """jnp.maximum / .max(-1) propagate NaN (algo/utils.py:39-44) and `mask * NaN` is NaN; v_max_f32 drops a NaN operand.
     A NaN cost (a NaN LiDAR hit point reaches get_cost), a NaN reward and a NaN value must mark exactly the entries the
     oracle marks: Qh[t' <= t, agent, all components] for a cost, Ql[t' <= t] for a reward, t' < t for an inserted value —
     and nothing else.  All three kernel families: column-parallel (lambda >= 0.5), row-parallel (lambda < 0.5), generic
-    (T > 256)."""
+    (T > 256) — and the generic kernel once more where it asks for more than 64 KB of dynamic LDS (lambda < 0.5 at 64
+    agents, T = 128: 4 * (129 * 128 + 129 + 2 * 128) = 67 588 bytes)."""
     from dgppo_amd import ops_algo as O
     B, T, n, nh = 6, (300 if family == "generic" else 40), 3, 2
     lam = 0.3 if family == "rows" else 0.95
+    if family == "generic above 64 KB":
+        T, n, lam = 128, 64, 0.3
+        assert n * nh > 32 and 4 * ((T + 1) * n * nh + (T + 1) + 2 * n * nh) > 64 * 1024
     r = np.random.default_rng(3)
     costs = r.uniform(-1, 1, size=(B, T, n, nh)).astype(np.float32)
     rew = (-r.uniform(0, 0.02, size=(B, T))).astype(np.float32)

@@ -502,10 +502,11 @@ def test_advantage_lagr_shapes(cuda, B, T_, n, nh):
     np.testing.assert_allclose(adv.cpu().numpy(), wA, atol=1e-5)
 
 
-def test_advantage_lagr_refuses_more_than_64_columns(cuda):
-    """n * nh = 65 exceeds the kernel's shared arrays: refused with a negative return before anything is launched"""
+def test_advantage_lagr_refuses_more_than_192_columns(cuda):
+    """n * nh = 193 exceeds the kernel's shared arrays (64 agents x 3 costs = 192 columns): refused with a negative return
+    before anything is launched"""
     from dgppo_amd import ops_algo as O
-    B, T_, n, nh = 1, 2, 13, 5
+    B, T_, n, nh = 1, 2, 193, 1
     _, Ql, Vl, Qh, Vh, lagr = _lagr_inputs(B, T_, n, nh, 1)
     d = lambda x: torch.from_numpy(x).to(cuda)
     adv = torch.full((B, T_, n), float("nan"), device=cuda); Ah = torch.full((B, T_, n, nh), float("nan"), device=cuda)
