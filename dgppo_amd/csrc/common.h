@@ -96,3 +96,7 @@ __host__ __device__ inline float u01_from_u32(uint32_t w) { return (float)(w >> 
 
 // NaN-propagating min (jnp.min semantics)
 __device__ inline float nanmin(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : fminf(a, b); }
+// NaN-propagating ReLU (jax.nn.relu / jnp.maximum(v, 0) semantics): fmaxf (v_max_f32) returns the non-NaN operand, so a NaN
+// pre-activation would leave as 0.  "not (v <= 0)" is true for a NaN: it passes; every other input, -Inf and +-0 included, gives
+// what fmaxf(v, 0.0f) gives (one compare and one select).
+__device__ inline float relu_nan(float v) { return !(v <= 0.0f) ? v : 0.0f; }

@@ -219,7 +219,7 @@ __global__ void __launch_bounds__(256) dense_fwd_kernel(DenseArgs a) {
           const int row = row0 + (rg * RTW + r) * 16 + lq * 4 + j;
           float v = acc[r][t][j] + bias[t];
           if constexpr (ACC) v += yold[r][t][j];
-          if (a.act == 1) v = fmaxf(v, 0.0f);
+          if (a.act == 1) v = relu_nan(v);
           if (a.mask != nullptr) v = (mk[r][t][j] > 0.0f) ? v : 0.0f;
           if (col < N && row < a.M) a.Y[(size_t)row * a.ldy + col] = v;
         }
@@ -340,7 +340,7 @@ __global__ void __launch_bounds__(256) dense_smallk_kernel(DenseArgs a) {
     float r[4] = {acc.x, acc.y, acc.z, acc.w};
     if (VECY) {
       if (a.accumulate) { const float4 o = *reinterpret_cast<const float4*>(y); r[0] += o.x; r[1] += o.y; r[2] += o.z; r[3] += o.w; }
-      if (a.act == 1) { r[0] = fmaxf(r[0], 0.f); r[1] = fmaxf(r[1], 0.f); r[2] = fmaxf(r[2], 0.f); r[3] = fmaxf(r[3], 0.f); }
+      if (a.act == 1) { r[0] = relu_nan(r[0]); r[1] = relu_nan(r[1]); r[2] = relu_nan(r[2]); r[3] = relu_nan(r[3]); }
       if (a.mask) {
         const float4 mk = *reinterpret_cast<const float4*>(a.mask + (size_t)row * a.ldm + c0);
         r[0] = mk.x > 0.f ? r[0] : 0.f; r[1] = mk.y > 0.f ? r[1] : 0.f; r[2] = mk.z > 0.f ? r[2] : 0.f; r[3] = mk.w > 0.f ? r[3] : 0.f;
@@ -351,7 +351,7 @@ __global__ void __launch_bounds__(256) dense_smallk_kernel(DenseArgs a) {
         if (c0 + u >= N) break;
         float v = r[u];
         if (a.accumulate) v += y[u];
-        if (a.act == 1) v = fmaxf(v, 0.f);
+        if (a.act == 1) v = relu_nan(v);
         if (a.mask) v = a.mask[(size_t)row * a.ldm + c0 + u] > 0.f ? v : 0.f;
         y[u] = v;
       }

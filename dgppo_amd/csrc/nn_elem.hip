@@ -9,6 +9,7 @@
 //   losses                               dgppo/algo/informarl.py:374,428-438 ; dgppo/algo/dgppo.py:310
 //   backward = jax.grad of the above     dgppo/algo/informarl.py:377,440 ; dgppo/algo/dgppo.py:316
 #include "common.h"
+#include "nn_ln.h"
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
@@ -63,13 +64,13 @@ __global__ void __launch_bounds__(256) ln_relu_fwd_kernel(const float* __restric
     const float4 v = reinterpret_cast<const float4*>(x)[(size_t)(ok ? row : M - 1) * 16 + li];
     const float mean = row16_sum((v.x + v.y) + (v.z + v.w)) * (1.0f / 64.0f);
     const float mean2 = row16_sum((v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w)) * (1.0f / 64.0f);
-    const float var = fmaxf(mean2 - mean * mean, 0.0f);
+    const float var = ln_fast_var(mean, mean2);
     const float rstd = rsqrtf(var + 1e-6f);
     float4 o;
-    o.x = fmaxf((v.x - mean) * rstd * g.x + b.x, 0.0f);
-    o.y = fmaxf((v.y - mean) * rstd * g.y + b.y, 0.0f);
-    o.z = fmaxf((v.z - mean) * rstd * g.z + b.z, 0.0f);
-    o.w = fmaxf((v.w - mean) * rstd * g.w + b.w, 0.0f);
+    o.x = relu_nan((v.x - mean) * rstd * g.x + b.x);
+    o.y = relu_nan((v.y - mean) * rstd * g.y + b.y);
+    o.z = relu_nan((v.z - mean) * rstd * g.z + b.z);
+    o.w = relu_nan((v.w - mean) * rstd * g.w + b.w);
     if (ok) {
       reinterpret_cast<float4*>(y)[(size_t)row * 16 + li] = o;
       if (stats != nullptr && li == 0) reinterpret_cast<float2*>(stats)[row] = make_float2(mean, rstd);

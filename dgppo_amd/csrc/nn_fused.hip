@@ -6,6 +6,7 @@
 //   GRUCell input projection  x W_i + b_i          dgppo/nn/rnn.py:14-30   (flax GRUCell: dense_i of the r|z|n gates)
 //   as composed by                                  dgppo/algo/module/policy.py:191-212, value.py:58-80
 #include "common.h"
+#include "nn_ln.h"
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 #define FZ_H 64            // hidden width of every layer in the chain
@@ -105,9 +106,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
         const float4 p0 = pa[rt][r], p1 = pb[rt][r];
         const float mean = ((p0.x + p0.z) + (p1.x + p1.z)) * (1.0f / 64.0f);
         const float mean2 = ((p0.y + p0.w) + (p1.y + p1.w)) * (1.0f / 64.0f);
-        const float var = fmaxf(mean2 - mean * mean, 0.0f);
+        const float var = ln_fast_var(mean, mean2);
         const float rstd = rsqrtf(var + 1e-6f);
-        const float y = fmaxf((v[rt][r] - mean) * rstd * g + e, 0.0f);
+        const float y = relu_nan((v[rt][r] - mean) * rstd * g + e);
         s_out[rl * FZ_HL + c] = y;
         const int row = row0 + rl;
         if (y_out != nullptr && row < a.M) {
@@ -307,7 +308,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES) mlp_gi_fwd_rw_kernel(MlpGiArgs 
     for (int r = 0; r < 4; ++r) {
       mean[r] = row16_sum(s[r]) * (1.0f / 64.0f);
       const float m2 = row16_sum(q[r]) * (1.0f / 64.0f);
-      rstd[r] = rsqrtf(fmaxf(m2 - mean[r] * mean[r], 0.0f) + 1e-6f);
+      rstd[r] = rsqrtf(ln_fast_var(mean[r], m2) + 1e-6f);
       const int row = row0 + lq * 4 + r;
       if (save && li == 0 && row < a.M) { st_out[(size_t)row * 2] = mean[r]; st_out[(size_t)row * 2 + 1] = rstd[r]; }
     }
@@ -316,7 +317,7 @@ __global__ void __launch_bounds__(64 * RW_WAVES) mlp_gi_fwd_rw_kernel(MlpGiArgs 
       const float g = par[64 + ct * 16 + li], e = par[128 + ct * 16 + li];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float y = fmaxf((acc[ct][r] - mean[r]) * rstd[r] * g + e, 0.0f);
+        const float y = relu_nan((acc[ct][r] - mean[r]) * rstd[r] * g + e);
         sY[(lq * 4 + r) * RW_YL + ct * 16 + li] = y;
         const int row = row0 + lq * 4 + r;
         if (save && row < a.M) y_out[(size_t)row * FZ_H + ct * 16 + li] = y;

@@ -560,6 +560,14 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(AttnArgs a) {
     if (s < S && s_m[i * S + s] != 0.0f) l = s_L[pair * Ll + sender_node(t, i, s)];
     s_a[idx] = l;
   }
+  // A private LiDAR-hit row whose one slot is masked reaches nobody.  Zx = P * Xs below would still meet it as 0 * x on the
+  // matrix cores, and a NaN hit point (NaN row) would poison every agent of the graph: zero the row (s_x is not read in this phase).
+  if (t.lidar && t.os > 0)
+    for (int q = tid >> 6; q < n * t.os; q += 4) {          // one wave per row, its lanes over the F columns
+      const int i = q / t.os;
+      if (s_m[i * S + n + t.gs + (q - i * t.os)] == 0.0f)
+        for (int f = tid & 63; f < F; f += 64) s_x[(n + t.ng + q) * Fl + f] = 0.0f;
+    }
   __syncthreads();
   ASTAMP(3);
   // ---- 8 lanes per (agent, head): softmax over the compact row (<= 8 slots per lane in registers, 3-step xor
@@ -981,7 +989,7 @@ __device__ inline void abd_xo_emit(const AbdXoRegs<GT>& x, float* XS, float* XH,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int o = t * 16 + lq * 4 + r;
-          if (o < n_shared_other) XS[(n + o) * ABD_XL + ct * 16 + li] = fmaxf(v[ct][r] + x.bo[ct], 0.0f);
+          if (o < n_shared_other) XS[(n + o) * ABD_XL + ct * 16 + li] = relu_nan(v[ct][r] + x.bo[ct]);
         }
     }
   }
@@ -995,7 +1003,7 @@ __device__ inline void abd_xo_emit(const AbdXoRegs<GT>& x, float* XS, float* XH,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int hr = t * 16 + lq * 4 + r;
-          XH[hr * ABD_XL + (hr >> 3) * 8 + ct * 16 + li] = fmaxf(v[ct][r] + x.bo[ct], 0.0f);
+          XH[hr * ABD_XL + (hr >> 3) * 8 + ct * 16 + li] = relu_nan(v[ct][r] + x.bo[ct]);
         }
     }
   }
@@ -1111,6 +1119,14 @@ __global__ void __launch_bounds__(128) attn_fwd_bd_kernel(AttnArgs a) {
     for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(QP + pin0 + (k * 8 + il) * ABD_XL + sub * 4) = vq[k];
 #pragma unroll
     for (int p = 0; p < NPR; ++p) mkv[p] = (slot[p] >= 0) ? mkv[p] : 0.0f;
+    if constexpr (HITS) {
+      // The lane's own hit row reaches nobody when its slot is masked, but Zx = P Xs would still meet it as 0 * x on the matrix
+      // cores (a NaN hit point: NaN row): the owner zeroes it.  DS operations of a wave execute in order: after the staging above.
+      if (mkv[PS] == 0.0f) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) *reinterpret_cast<float4*>(XH + lane * ABD_XL + il * 8 + k * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
     ASTAMP(2);
     // ---- logits: A = the query row of (agent il, head hA), B = the lane's own node rows ----
     f32x4g acc[NPR];
@@ -1320,6 +1336,14 @@ __global__ void __launch_bounds__(128) attn_fwd_bdp_kernel(AttnArgs a) {
     for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(QP + pin0 + (k * 8 + il) * ABD_XL + sub * 4) = R.vq[k];
 #pragma unroll
     for (int p = 0; p < NPR; ++p) R.mkv[p] = (slot[p] >= 0) ? R.mkv[p] : 0.0f;
+    if constexpr (HITS) {
+      // The lane's own hit row reaches nobody when its slot is masked, but Zx = P Xs would still meet it as 0 * x on the matrix
+      // cores (a NaN hit point: NaN row): the owner zeroes it.  DS operations of a wave execute in order: after the staging above.
+      if (R.mkv[PS] == 0.0f) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) *reinterpret_cast<float4*>(XH + lane * ABD_XL + il * 8 + k * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
   };
   auto compute = [&](int gg, const Regs& R) {
     float* zc = a.zcat + (size_t)gg * n * Kp;
@@ -1632,6 +1656,14 @@ __global__ void __launch_bounds__(64) attn_bwd_bd_kernel(AttnArgs a) {
     for (int p = 0; p < NPR; ++p)
 #pragma unroll
       for (int h = 0; h < 4; ++h) av[p][h] = (slot[p] >= 0 && h < H) ? av[p][h] : 0.0f;
+    if constexpr (HITS) {
+      // the lane's own hit row, if its slot carries no weight (a == 0 in every head: the saved weights are consulted, not the mask,
+      // so also an unmasked slot whose softmax weight underflowed), is zeroed before dQt = dL Xs meets it as 0 * x (see the forward)
+      if (av[PS][0] == 0.0f && av[PS][1] == 0.0f && av[PS][2] == 0.0f && av[PS][3] == 0.0f) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) *reinterpret_cast<float4*>(XH + lane * ABD_XL + il * 8 + k * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
     // ---- dA = dZx Xs^T at the lane's slots ----
     f32x4g acc[NPR];
 #pragma unroll
@@ -1983,6 +2015,16 @@ __global__ void __launch_bounds__(256) attn_bwd_kernel(AttnArgs a) {
     }
     s_c[idx] = dA;
   }
+  // a private LiDAR-hit row whose slot carries no weight (a == 0 in every head: the saved weights are consulted, not the mask, so
+  // also an unmasked slot whose softmax weight underflowed) is zeroed before dQt = dL * Xs meets it as 0 * x (see the forward)
+  if (t.lidar && t.os > 0)
+    for (int q = tid >> 6; q < n * t.os; q += 4) {          // one wave per row, its lanes over the F columns
+      const int i = q / t.os, s = n + t.gs + (q - i * t.os);
+      bool dead = true;
+      for (int h = 0; h < H; ++h) dead = dead && s_a[(i * H + h) * Sp + s] == 0.0f;
+      if (dead)
+        for (int f = tid & 63; f < F; f += 64) s_x[(n + t.ng + q) * Fl + f] = 0.0f;
+    }
   __syncthreads();
   // 8 lanes per (agent, head): softmax backward dl = a * (dA - sum_s a dA); then every lane helps clearing s_D
   for (int p0 = 0; p0 < nH; p0 += 32) {
