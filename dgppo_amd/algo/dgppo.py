@@ -15,7 +15,7 @@ from .. import engine as EN
 from .. import init as INIT
 from .. import nets
 from .. import ops_nn as K
-from ..trainer.data import Rollout
+from ..trainer.data import Landscape, Rollout
 from ..utils import checkpoint as CK
 from ..utils.graph import GraphsTuple
 from .base import Algorithm
@@ -244,6 +244,33 @@ class DGPPO(Algorithm):
             assert env.cfg.kind == self._env.cfg.kind and env.num_agents == self.n_agents
         ro = self.engine.rollout(self._seeds(keys), True, noise_seed=int(self._rng.integers(1, 2 ** 62)))
         return self._wrap(ro, env)
+
+    def vh_landscape(self, rollout: Rollout, index: int, agent: int, frames=None, nx: int = 64, ny: int = 64, xs=None,
+                     ys=None) -> Landscape:
+        """The learned constraint-value function of `agent` over a grid of positions, in frozen frames of episode `index` of a
+        rollout that collect_deterministic / collect_stochastic returned: in every frame the agent is moved to each grid
+        point (velocity kept, LiDAR cast again) and Vh evaluated with the carry of that step.  frames: frame numbers in
+        [0, T) (default: all); xs / ys: grid lines (default: linspace(0, area_size, nx / ny) in fp32).  Not in the reference:
+        it is the producer of what its renderer draws as viz_opts["cbf"] (dgppo/env/plot.py:348-372,437-447)."""
+        self.engine.require_landscape()
+        ro = getattr(self, "_last_rollouts", {}).get(id(rollout.actions))
+        if ro is None:
+            raise ValueError("vh_landscape() needs a Rollout produced by this algo's collect methods")
+        area = float(self._env.cfg.area_size)
+
+        def axis(v, m, name):
+            if v is None:
+                if int(m) < 1:
+                    raise ValueError(f"vh_landscape: {name}: the grid is empty")
+                v = np.linspace(0.0, area, int(m))
+            v = np.asarray(v, dtype=np.float32).reshape(-1)
+            if v.size == 0 or not np.isfinite(v).all():
+                raise ValueError(f"vh_landscape: {name} must be a non-empty array of finite coordinates")
+            return v
+        xs, ys = axis(xs, nx, "xs"), axis(ys, ny, "ys")
+        frames = np.arange(ro.T) if frames is None else np.asarray(frames, dtype=np.int64).reshape(-1)
+        Vh = self.engine.vh_landscape(ro, int(index), int(agent), frames, xs, ys)
+        return Landscape(xs, ys, Vh.cpu().numpy(), int(agent), frames.astype(np.int64))
 
     def update(self, rollout: Rollout, step: int) -> dict:
         ro = self._last_rollouts.pop(id(rollout.actions), None)

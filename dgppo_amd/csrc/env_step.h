@@ -108,6 +108,83 @@ __device__ inline bool rect_inside(const float* rec, float px, float py, float r
 }
 
 
+// ---- LiDAR ray cast of the generic kernels (env_step.hip's workgroup-per-env kernel, env_sweep.hip) -------------------------
+// per-segment constants of rectangle record `rec`, corner m: P[m] and the edge vector P[m-1] - P[m]
+__device__ inline void segment_consts(const float* rec, int m, float* out4) {
+  const int mm = (m + 3) & 3;
+  const float* P = rec + 8;
+  out4[0] = P[2 * m];
+  out4[1] = P[2 * m + 1];
+  out4[2] = P[2 * mm] - P[2 * m];          // x4 - x3
+  out4[3] = P[2 * mm + 1] - P[2 * m + 1];  // y4 - y3
+}
+
+// smallest alpha of the ray from (x1, y1) in direction (rc, rs), length sr, over the 4 * no segments of s_seg
+// (float4-aligned, segment_consts layout), before the start-inside factor.
+// Exactly the reference's arithmetic (obstacle.py:97-105), evaluated without the two IEEE divisions per test:
+//   valid = (0 <= num_a/det <= 1) && (0 <= num_b/det <= 1)  is decided from signs and magnitudes
+//     fl(q) >= 0  <=>  q >= 0   (no quotient of these operands can underflow to -0: |num| is 0 or >= ~1e-22, |det| <= 1e7)
+//     fl(q) <= 1  <=>  q <= 1   (num > det > 0 implies q >= 1 + 2^-24 + eps, which rounds above 1)
+//   and only a valid segment needs alpha = num_a/det (one correctly rounded division).  det == 0 (sign(det) = 0 ->
+//   x/0 -> 0*inf = NaN in the reference) takes the literal slow path so the NaN semantics are preserved bit for bit.
+__device__ inline float ray_min_alpha(float x1, float y1, float rc, float rs, float sr, const float* s_seg, int no) {
+  const float x2 = x1 + rc * sr;
+  const float y2 = y1 + rs * sr;
+  const float dx12 = x1 - x2, dy12 = y1 - y2;
+  float amin = 0.0f;
+  for (int o = 0; o < no; ++o) {
+    float ao = 0.0f;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const float4 sg = reinterpret_cast<const float4*>(s_seg)[o * 4 + m];
+      const float x3 = sg.x, y3 = sg.y, ex = sg.z, ey = sg.w;
+      const float det0 = dx12 * ey - dy12 * ex;
+      const float ax = x1 - x3, ay = y1 - y3;
+      const float na = ey * ax - ex * ay;
+      const float nb = (-dy12) * ax + dx12 * ay;
+      float al;
+      if (det0 != 0.0f && det0 == det0) {
+        const float det = copysignf(fminf(fmaxf(fabsf(det0), 1e-7f), 1e7f), det0);
+        const bool pos = det > 0.0f;
+        const bool va = (na == 0.0f || (na > 0.0f) == pos) && (pos ? (na <= det) : (na >= det));
+        const bool vb = (nb == 0.0f || (nb > 0.0f) == pos) && (pos ? (nb <= det) : (nb >= det));
+        al = 1e6f;
+        if (va && vb) al = na / det + 0.0f;   // v*alpha + (1-v)*1e6 with v = 1: alpha + 0 (turns -0 into +0)
+      } else {  // literal path: det = sign(det0) * clip(|det0|) = 0 (or NaN)
+        al = segment_alpha_literal(det0, na, nb);
+      }
+      ao = (m == 0) ? al : nanmin(ao, al);
+    }
+    amin = (o == 0) ? ao : nanmin(amin, ao);
+  }
+  return amin;
+}
+
+// stable ascending rank of ray r among the R alphas `al` (env/utils.py:132-136): NaNs sort last, ties in index order
+__device__ inline int ray_rank(const float* al, int R, int r) {
+  const float ar = al[r];
+  const bool nr = (ar != ar);
+  int rank = 0;
+  for (int j = 0; j < R; ++j) {
+    const float aj = al[j];
+    const bool nj = (aj != aj);
+    bool less;
+    if (nj || nr) less = (nj == nr) ? (j < r) : nr;
+    else less = (aj < ar) || (aj == ar && j < r);
+    rank += less ? 1 : 0;
+  }
+  return rank;
+}
+
+// hit point of a ray at alpha ar (env/utils.py:126-130)
+__device__ inline void ray_hit(float x1, float y1, float rc, float rs, float sr, float ar, float* out2) {
+  const float x2 = x1 + rc * sr;
+  const float y2 = y1 + rs * sr;
+  out2[0] = x1 + (x2 - x1) * ar;
+  out2[1] = y1 + (y2 - y1) * ar;
+}
+
+
 #define MISS_BITS 0x49742400u  // bits of 1e6f
 
 // wave-per-env LiDAR kernel (env_wave.hip): whether its instantiation list holds this (state_dim, spread, n_agents,

@@ -191,82 +191,24 @@ __global__ void env_step_kernel(StepArgs a) {
     a.reward[b] = reward_from_sums(s1, s2, s3, nrg, n);
   }
 
-  // ---- phase 2: ray fan x rectangles x 4 segments (thread per (agent, ray)) ------------------
-  // Exactly the reference's arithmetic (obstacle.py:97-105), evaluated without the two IEEE divisions per test:
-  //   valid = (0 <= num_a/det <= 1) && (0 <= num_b/det <= 1)  is decided from signs and magnitudes
-  //     fl(q) >= 0  <=>  q >= 0   (no quotient of these operands can underflow to -0: |num| is 0 or >= ~1e-22, |det| <= 1e7)
-  //     fl(q) <= 1  <=>  q <= 1   (num > det > 0 implies q >= 1 + 2^-24 + eps, which rounds above 1)
-  //   and only a valid segment needs alpha = num_a/det (one correctly rounded division).  det == 0 (sign(det) = 0 ->
-  //   x/0 -> 0*inf = NaN in the reference) takes the literal slow path so the NaN semantics are preserved bit for bit.
+  // ---- phase 2: ray fan x rectangles x 4 segments (thread per (agent, ray)); the arithmetic is ray_min_alpha's (env_step.h)
   if (do_sense) {
     const float sr = c.comm_radius;
-    // per-segment constants, once per env: P[m] and the edge vector P[m-1] - P[m]
-    for (int q = tid; q < no * 4; q += nt) {
-      const int o = q >> 2, m = q & 3, mm = (m + 3) & 3;
-      const float* P = s_obst + o * DGPPO_RECT_STRIDE + 8;
-      s_seg[q * 4 + 0] = P[2 * m];
-      s_seg[q * 4 + 1] = P[2 * m + 1];
-      s_seg[q * 4 + 2] = P[2 * mm] - P[2 * m];          // x4 - x3
-      s_seg[q * 4 + 3] = P[2 * mm + 1] - P[2 * m + 1];  // y4 - y3
-    }
+    // per-segment constants, once per env
+    for (int q = tid; q < no * 4; q += nt) segment_consts(s_obst + (q >> 2) * DGPPO_RECT_STRIDE, q & 3, s_seg + q * 4);
     __syncthreads();
     for (int idx = tid; idx < n * R; idx += nt) {
       const int i = idx / R, r = idx - i * R;
-      const float x1 = s_next[i * SD], y1 = s_next[i * SD + 1];
-      const float x2 = x1 + a.ray_cos[r] * sr;
-      const float y2 = y1 + a.ray_sin[r] * sr;
-      const float dx12 = x1 - x2, dy12 = y1 - y2;
-      float amin = 0.0f;
-      for (int o = 0; o < no; ++o) {
-        float ao = 0.0f;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const float4 sg = reinterpret_cast<const float4*>(s_seg)[o * 4 + m];
-          const float x3 = sg.x, y3 = sg.y, ex = sg.z, ey = sg.w;
-          const float det0 = dx12 * ey - dy12 * ex;
-          const float ax = x1 - x3, ay = y1 - y3;
-          const float na = ey * ax - ex * ay;
-          const float nb = (-dy12) * ax + dx12 * ay;
-          float al;
-          if (det0 != 0.0f && det0 == det0) {
-            const float det = copysignf(fminf(fmaxf(fabsf(det0), 1e-7f), 1e7f), det0);
-            const bool pos = det > 0.0f;
-            const bool va = (na == 0.0f || (na > 0.0f) == pos) && (pos ? (na <= det) : (na >= det));
-            const bool vb = (nb == 0.0f || (nb > 0.0f) == pos) && (pos ? (nb <= det) : (nb >= det));
-            al = 1e6f;
-            if (va && vb) al = na / det + 0.0f;   // v*alpha + (1-v)*1e6 with v = 1: alpha + 0 (turns -0 into +0)
-          } else {  // literal path: det = sign(det0) * clip(|det0|) = 0 (or NaN)
-            al = segment_alpha_literal(det0, na, nb);
-          }
-          ao = (m == 0) ? al : nanmin(ao, al);
-        }
-        amin = (o == 0) ? ao : nanmin(amin, ao);
-      }
-      amin = amin * (1.0f - s_isin[i]);
-      s_alpha[idx] = amin;
+      const float amin = ray_min_alpha(s_next[i * SD], s_next[i * SD + 1], a.ray_cos[r], a.ray_sin[r], sr, s_seg, no);
+      s_alpha[idx] = amin * (1.0f - s_isin[i]);
     }
     __syncthreads();
     // ---- phase 3: stable ascending top-k by rank counting (env/utils.py:132-136) --------------
     for (int idx = tid; idx < n * R; idx += nt) {
       const int i = idx / R, r = idx - i * R;
-      const float ar = s_alpha[idx];
-      const bool nr = (ar != ar);
-      int rank = 0;
-      for (int j = 0; j < R; ++j) {
-        const float aj = s_alpha[i * R + j];
-        const bool nj = (aj != aj);
-        bool less;
-        if (nj || nr) less = (nj == nr) ? (j < r) : nr;  // NaNs sort last, in index order
-        else less = (aj < ar) || (aj == ar && j < r);
-        rank += less ? 1 : 0;
-      }
-      if (rank < k) {
-        const float x1 = s_next[i * SD], y1 = s_next[i * SD + 1];
-        const float x2 = x1 + a.ray_cos[r] * sr;
-        const float y2 = y1 + a.ray_sin[r] * sr;
-        s_hnext[(i * k + rank) * 2] = x1 + (x2 - x1) * ar;
-        s_hnext[(i * k + rank) * 2 + 1] = y1 + (y2 - y1) * ar;
-      }
+      const int rank = ray_rank(s_alpha + i * R, R, r);
+      if (rank < k)
+        ray_hit(s_next[i * SD], s_next[i * SD + 1], a.ray_cos[r], a.ray_sin[r], sr, s_alpha[idx], s_hnext + (i * k + rank) * 2);
     }
     __syncthreads();
   } else if (lidar && no > 0) {

@@ -1,0 +1,248 @@
+// Vh landscape: the graph features of one frozen frame with ONE agent moved over a grid of positions — what the
+// reference's renderer consumes as viz_opts["cbf"] (dgppo/env/plot.py:348-372,437-447) and ships no producer for.
+//
+// Graph g = (f * ny + iy) * nx + ix is the graph of frame fid = frame_ids[f] in which agent `agent_id` stands at
+// (xs[ix], ys[iy]): its velocity (bicycle: heading and speed) is kept, its k LiDAR hit points are cast again from the new
+// position (get_lidar, env/utils.py:115-136: start-inside factor, det == 0 NaN rays, stable top-k), every other agent's hit
+// points are the recorded ones.  The outputs have the layout and arithmetic of dgppo_graph_feats (nn_graph.hip) for G graphs.
+//
+// Organisation: a workgroup stages the frame (states, goals, rectangle segments, recorded hits) in LDS once — per tile of
+// 64 grid points, a few hundred floats that stay in L2 across the tiles of a frame — and walks the tile, one wave per point: the wave casts the R rays of the moved agent, ranks them, and streams the graph's four
+// dense outputs with unit-stride stores (edge features as float4).  Consecutive points are consecutive graphs, so the four
+// waves of a pass write one contiguous range of each output.
+//
+// Built with -ffp-contract=off; the ray arithmetic is env_step.h's (shared with env_step.hip), the slot topology
+// graph_topo.h's (shared with nn_graph.hip).
+#include "env_step.h"
+#include "graph_topo.h"
+
+#define SWEEP_NT 256
+#define SWEEP_WAVES (SWEEP_NT / DGPPO_WAVE)
+#define SWEEP_TILE 64   // grid points per workgroup
+
+struct SweepArgs {
+  dgppo_env_cfg cfg;
+  Topo t;
+  const float* agent; long agent_st;
+  const float* goal;
+  const float* obst;
+  const float* hits; long hits_st;
+  const float* ray_cos;
+  const float* ray_sin;
+  const int32_t* frame_ids;
+  int agent_id, nx, nxy, tiles;
+  const float* xs;
+  const float* ys;
+  float* Xa;
+  float* Xo;
+  float* efeat;
+  float* emask;
+  float* hits_out;
+  int Fp;
+  uint32_t rcp_fp, rcp_S;   // ceil(2^32 / d): index divisions by Fp and S as one v_mul_hi_u32 (exact for idx < 2^16)
+};
+
+// orders the LDS accesses of ONE wave around it: its earlier writes are visible to its later reads
+__device__ inline void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ inline int sweep_div(int x, uint32_t rcp) { return (int)__umulhi((uint32_t)x, rcp); }
+
+template <int SD>
+__global__ void __launch_bounds__(SWEEP_NT) graph_feats_sweep_kernel(SweepArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const dgppo_env_cfg& c = a.cfg;
+  const Topo& t = a.t;
+  const int tid = threadIdx.x, lane = tid & (DGPPO_WAVE - 1), wave = tid / DGPPO_WAVE;
+  const int f = blockIdx.x / a.tiles, tile = blockIdx.x - f * a.tiles;
+  const int fid = a.frame_ids ? a.frame_ids[f] : f;
+  const int n = t.n, ng = t.ng, S = t.S, Fp = a.Fp, aid = a.agent_id;
+  const int n_on = t.Ns - n - ng;
+  const int no = c.n_obs, R = c.n_rays, k = c.top_k;
+  const bool cast = t.lidar && n_on > 0;
+  // LDS carve: every offset is a multiple of 4 floats
+  const int al4 = 3;
+  float* s_seg = sm;                                             // no*16 segment constants (LiDAR)
+  float* s_rec = s_seg + (cast ? no * 16 : 0);                   // no*16 rectangle records (LiDAR) | n_obs*SD (MPE)
+  float* s_ag = s_rec + (((t.lidar ? (cast ? no * 16 : 0) : n_on * SD) + al4) & ~al4);   // n*SD
+  float* s_go = s_ag + ((n * SD + al4) & ~al4);                  // ng*SD
+  float* s_fa = s_go + ((ng * SD + al4) & ~al4);                 // n*4   state2feat(agent), the moved agent's at its base position
+  float* s_fg = s_fa + n * 4;                                    // ng*4
+  float* s_hp = s_fg + ng * 4;                                   // n*k*2 recorded hits (LiDAR)
+  float* s_rc = s_hp + (cast ? ((n * k * 2 + al4) & ~al4) : 0);  // R
+  float* s_rs = s_rc + (cast ? ((R + al4) & ~al4) : 0);          // R
+  float* s_al = s_rs + (cast ? ((R + al4) & ~al4) : 0);          // waves * R   alphas of the wave's point
+  float* s_hit = s_al + (cast ? SWEEP_WAVES * ((R + al4) & ~al4) : 0);   // waves * k*2 hits of the moved agent
+  const int Rp = (R + al4) & ~al4, K2 = (k * 2 + al4) & ~al4;
+
+  // ---- the frame, once per workgroup ----
+  const float* ag = a.agent + (size_t)fid * a.agent_st;
+  for (int i = tid; i < n * SD; i += SWEEP_NT) s_ag[i] = ag[i];
+  for (int i = tid; i < ng * SD; i += SWEEP_NT) s_go[i] = a.goal[i];
+  if (cast) {
+    for (int i = tid; i < no * 16; i += SWEEP_NT) s_rec[i] = a.obst[i];
+    const float* hp = a.hits + (size_t)fid * a.hits_st;
+    for (int i = tid; i < n * k * 2; i += SWEEP_NT) s_hp[i] = hp[i];
+    for (int i = tid; i < R; i += SWEEP_NT) { s_rc[i] = a.ray_cos[i]; s_rs[i] = a.ray_sin[i]; }
+  } else if (!t.lidar) {
+    for (int i = tid; i < n_on * SD; i += SWEEP_NT) s_rec[i] = a.obst[i];
+  }
+  __syncthreads();
+  if (cast)
+    for (int q = tid; q < no * 4; q += SWEEP_NT) segment_consts(s_rec + (q >> 2) * DGPPO_RECT_STRIDE, q & 3, s_seg + q * 4);
+  for (int i = tid; i < n + ng; i += SWEEP_NT)
+    state2feat<SD>((i < n) ? s_ag + i * SD : s_go + (i - n) * SD, (i < n) ? s_fa + i * 4 : s_fg + (i - n) * 4);
+  __syncthreads();
+
+  const int q0 = tile * SWEEP_TILE, q1 = min(q0 + SWEEP_TILE, a.nxy);
+  float* w_al = s_al + wave * Rp;
+  float* w_hit = s_hit + wave * K2;
+  const float sr = c.comm_radius;
+  constexpr int ND = SD + 3;
+  // from here on the waves are independent: w_al / w_hit belong to one wave, whose LDS operations complete in issue order,
+  // so between its phases a wave-level fence (no reordering by the compiler, no workgroup barrier) is enough
+  for (int q = q0 + wave; q < q1; q += SWEEP_WAVES) {
+    const int iy = q / a.nx, ix = q - iy * a.nx;
+    const float px = a.xs[ix], py = a.ys[iy];
+    if (cast) {
+      {
+        // start inside a rectangle (env/utils.py:117, r = 0): all alphas become 0
+        bool in = false;
+        for (int o = lane; o < no; o += DGPPO_WAVE) in = in || rect_inside(s_rec + o * DGPPO_RECT_STRIDE, px, py, 0.0f);
+        const float is_in = (__ballot(in) != 0ull) ? 1.0f : 0.0f;
+        for (int r = lane; r < R; r += DGPPO_WAVE)
+          w_al[r] = ray_min_alpha(px, py, s_rc[r], s_rs[r], sr, s_seg, no) * (1.0f - is_in);
+      }
+      wave_sync();
+      for (int r = lane; r < R; r += DGPPO_WAVE) {
+        const int rank = ray_rank(w_al, R, r);
+        if (rank < k) ray_hit(px, py, s_rc[r], s_rs[r], sr, w_al[r], w_hit + rank * 2);
+      }
+      wave_sync();
+    }
+    const size_t g = (size_t)f * a.nxy + q;
+    // position and feature row of agent i in this graph
+    auto posx = [&](int i) { return (i == aid) ? px : s_ag[i * SD]; };
+    auto posy = [&](int i) { return (i == aid) ? py : s_ag[i * SD + 1]; };
+    auto feat = [&](int i, int d) { return (i == aid && d < 2) ? (d == 0 ? px : py) : s_fa[i * 4 + d]; };
+    // hit point m of agent i
+    auto hit = [&](int i, int m) { return (i == aid) ? w_hit + m * 2 : s_hp + (i * k + m) * 2; };
+
+    // node feature rows: [state | obs, goal, agent indicator], zero padded to Fp
+    float* xa = a.Xa + g * n * Fp;
+    for (int idx = lane; idx < n * Fp; idx += DGPPO_WAVE) {
+      const int nd = sweep_div(idx, a.rcp_fp), col = idx - nd * Fp;
+      float v = (col < SD) ? s_ag[nd * SD + col] : ((col == SD + 2) ? 1.0f : 0.0f);
+      if (nd == aid && col < 2) v = (col == 0) ? px : py;
+      if (col >= ND) v = 0.0f;
+      xa[idx] = v;
+    }
+    float* xo = a.Xo + g * (t.Ns - n) * Fp;
+    for (int idx = lane; idx < (t.Ns - n) * Fp; idx += DGPPO_WAVE) {
+      const int r = sweep_div(idx, a.rcp_fp), col = idx - r * Fp;
+      float v;
+      if (r < ng) v = (col < SD) ? s_go[r * SD + col] : ((col == SD + 1) ? 1.0f : 0.0f);
+      else {
+        const int qn = r - ng;
+        if (t.lidar) {
+          const int m = qn - aid * k;
+          const float* hp = (m >= 0 && m < k) ? w_hit + m * 2 : s_hp + qn * 2;
+          v = (col < 2) ? hp[col] : ((col == SD) ? 1.0f : 0.0f);
+        } else {
+          v = (col < SD) ? s_rec[qn * SD + col] : ((col == SD) ? 1.0f : 0.0f);
+        }
+      }
+      if (col >= ND) v = 0.0f;
+      xo[idx] = v;
+    }
+    // per-slot edge feature + mask (lidar_env/base.py:227-271, lidar_spread.py:57-96 and the MPE twins)
+    float4* ef = reinterpret_cast<float4*>(a.efeat) + g * n * S;
+    float* em = a.emask + g * n * S;
+    for (int idx = lane; idx < n * S; idx += DGPPO_WAVE) {
+      const int i = sweep_div(idx, a.rcp_S), s = idx - i * S;
+      float4 fe;
+      bool mask;
+      const float xi = posx(i), yi = posy(i);
+      if (s < n) {
+        fe = make_float4(feat(i, 0) - feat(s, 0), feat(i, 1) - feat(s, 1), feat(i, 2) - feat(s, 2), feat(i, 3) - feat(s, 3));
+        const float d = dist_rn(xi - posx(s), yi - posy(s)) + ((i == s) ? c.eye_offset : 0.0f);
+        mask = d < c.comm_radius;
+      } else if (s < n + t.gs) {
+        const float* fg = s_fg + (t.spread ? (s - n) : i) * 4;
+        fe = make_float4(feat(i, 0) - fg[0], feat(i, 1) - fg[1], feat(i, 2) - fg[2], feat(i, 3) - fg[3]);
+        mask = true;
+      } else {
+        const int m = s - n - t.gs;
+        if (t.lidar) {
+          const float* hp = hit(i, m);
+          const float lx = xi - hp[0], ly = yi - hp[1];
+          fe = make_float4(lx, ly, 0.0f, 0.0f);
+          mask = dist_rn(lx, ly) < c.lidar_mask_radius;
+        } else {
+          const float* xob = s_rec + m * SD;
+          const float dx = xi - xob[0], dy = yi - xob[1];
+          fe = make_float4(dx, dy, s_ag[i * SD + 2] - xob[2], s_ag[i * SD + 3] - xob[3]);
+          mask = dist_rn(dx, dy) < c.obs_mask_radius;
+        }
+      }
+      ef[idx] = fe;
+      em[idx] = mask ? 1.0f : 0.0f;
+    }
+    if (cast && a.hits_out != nullptr)
+      for (int i = lane; i < k * 2; i += DGPPO_WAVE) a.hits_out[g * k * 2 + i] = w_hit[i];
+    wave_sync();   // the next point's cast overwrites w_al / w_hit
+  }
+}
+
+extern "C" int32_t dgppo_graph_feats_sweep(const dgppo_env_cfg* cfg, const float* agent, int64_t agent_st, const float* goal,
+                                           const float* obst, const float* hits, int64_t hits_st, const float* ray_cos,
+                                           const float* ray_sin, const int32_t* frame_ids, int32_t n_frames, int32_t agent_id,
+                                           const float* xs, int32_t nx, const float* ys, int32_t ny, float* Xa, float* Xo,
+                                           float* efeat, float* emask, float* hits_out, int32_t Fp, void* stream) {
+  int32_t rc = dgppo_validate_cfg(cfg);
+  if (rc) return rc;
+  DGPPO_REFUSE_VMAS(cfg, "dgppo_graph_feats_sweep", "dgppo_vmas_graph_feats on a tiled record (there is no VMAS sweep)");
+  DGPPO_REQUIRE(agent_id >= 0 && agent_id < cfg->n_agents, "dgppo_graph_feats_sweep: agent_id %d outside [0, %d)", agent_id,
+                cfg->n_agents);
+  DGPPO_REQUIRE(nx >= 0 && ny >= 0 && n_frames >= 0, "dgppo_graph_feats_sweep: negative counts");
+  if (nx == 0 || ny == 0 || n_frames == 0) return 0;
+  DGPPO_REQUIRE(agent && goal && xs && ys && Xa && efeat && emask, "dgppo_graph_feats_sweep: NULL operand");
+  DGPPO_REQUIRE(Fp >= cfg->node_dim && Fp <= 32, "dgppo_graph_feats_sweep: Fp must be in [node_dim, 32]");
+  SweepArgs a;
+  a.cfg = *cfg; a.t = make_topo(*cfg);
+  const Topo& t = a.t;
+  const int n_on = t.Ns - t.n - t.ng;
+  DGPPO_REQUIRE(t.Ns == t.n || Xo, "dgppo_graph_feats_sweep: Xo is NULL");
+  if (n_on > 0) {
+    DGPPO_REQUIRE(obst, "dgppo_graph_feats_sweep: obst is NULL");
+    if (t.lidar) DGPPO_REQUIRE(hits && ray_cos && ray_sin, "dgppo_graph_feats_sweep: hits / ray_cos / ray_sin is NULL");
+  }
+  DGPPO_REQUIRE(((uintptr_t)efeat & 15) == 0, "dgppo_graph_feats_sweep: efeat must be 16-byte aligned");
+  DGPPO_REQUIRE(Fp >= 2 && t.S >= 2 && (long)t.Ns * Fp < 65536 && (long)t.n * t.S < 65536,
+                "dgppo_graph_feats_sweep: sizes out of range");
+  const long nxy = (long)nx * ny;
+  DGPPO_REQUIRE(nxy <= (1L << 24), "dgppo_graph_feats_sweep: grid too large (nx * ny <= 2^24)");
+  const long tiles = (nxy + SWEEP_TILE - 1) / SWEEP_TILE;
+  DGPPO_REQUIRE(tiles * n_frames < (1L << 31), "dgppo_graph_feats_sweep: too many graphs");
+  a.agent = agent; a.agent_st = agent_st; a.goal = goal; a.obst = obst; a.hits = hits; a.hits_st = hits_st;
+  a.ray_cos = ray_cos; a.ray_sin = ray_sin; a.frame_ids = frame_ids; a.agent_id = agent_id; a.nx = nx; a.nxy = (int)nxy;
+  a.tiles = (int)tiles; a.xs = xs; a.ys = ys; a.Xa = Xa; a.Xo = Xo; a.efeat = efeat; a.emask = emask; a.hits_out = hits_out;
+  a.Fp = Fp;
+  auto rcp = [](int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); };
+  a.rcp_fp = rcp(Fp); a.rcp_S = rcp(t.S);
+  const int SD = cfg->state_dim, no = cfg->n_obs, R = cfg->n_rays, k = cfg->top_k;
+  const bool cast = t.lidar && n_on > 0;
+  auto up4 = [](long v) { return (v + 3) & ~3L; };
+  long fl = up4(t.lidar ? (cast ? no * 16 : 0) : (long)n_on * SD) + up4((long)t.n * SD) + up4((long)t.ng * SD) + t.n * 4 + t.ng * 4;
+  if (cast) fl += no * 16 + up4((long)t.n * k * 2) + 2 * up4(R) + SWEEP_WAVES * (up4(R) + up4(k * 2));
+  DGPPO_REQUIRE(fl * 4 <= 64 * 1024, "dgppo_graph_feats_sweep: the frame does not fit the LDS (%ld bytes)", fl * 4);
+  const size_t smem = sizeof(float) * (size_t)fl;
+  const dim3 grid((unsigned)(tiles * n_frames));
+  if (SD == 5) hipLaunchKernelGGL(graph_feats_sweep_kernel<5>, grid, dim3(SWEEP_NT), smem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(graph_feats_sweep_kernel<4>, grid, dim3(SWEEP_NT), smem, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}

@@ -10,29 +10,8 @@
 //   sum_s a[i,s,h] (v_h(x_s) + e_h(edge_is)) = (sum_s a[i,s,h] [x_s ; edge_is]) [Wv_h ; We_h] + bv_h   (dense, outside)
 // so this file only does: graph features, logits against RAW sender features, masked softmax, aggregation of raw
 // features, and the matching backward.  const(i,h) (the key bias) cancels in the softmax.
-#include "common.h"
+#include "graph_topo.h"
 
-struct Topo {
-  int n, ng, gs, os, per, lidar, spread;  // per = k (LiDAR) or n_obs (MPE)
-  int S, Ns;                              // slots per agent, nodes without pad
-};
-
-static Topo make_topo(const dgppo_env_cfg& c) {
-  Topo t;
-  t.n = c.n_agents; t.ng = c.n_goals; t.gs = cfg_goal_slots(c); t.os = cfg_obs_slots(c);
-  t.lidar = cfg_is_lidar(c) ? 1 : 0; t.spread = cfg_is_spread(c) ? 1 : 0;
-  t.per = t.os;
-  t.S = t.n + t.gs + t.os;
-  t.Ns = t.n + t.ng + cfg_obs_nodes(c);
-  return t;
-}
-
-__device__ inline int sender_node(const Topo& t, int i, int s) {
-  if (s < t.n) return s;
-  if (s < t.n + t.gs) return t.spread ? t.n + (s - t.n) : t.n + i;
-  const int m = s - t.n - t.gs;
-  return t.lidar ? t.n + t.ng + i * t.per + m : t.n + t.ng + m;
-}
 // slot through which node nd sends to agent i (or -1)
 __device__ inline int slot_of(const Topo& t, int nd, int i) {
   if (nd < t.n) return nd;
@@ -76,8 +55,6 @@ struct FeatArgs {
   int Fp;
   uint32_t rcp_fp, rcp_S;   // ceil(2^32 / d): index divisions by Fp and S as one v_mul_hi_u32 (exact for idx < 2^16)
 };
-
-__device__ inline float dist_rn(float dx, float dy) { return __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy))); }
 
 template <int SD>
 __global__ void graph_feats_kernel(FeatArgs a) {

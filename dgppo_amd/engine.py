@@ -375,6 +375,11 @@ class Engine:
         st = OE.State({k: v[envs, t0] for k, v in ro.step.items()}, {k: v[envs] for k, v in ro.env.items()})
         return self._feats(tag, st, Eb, n_time, self.T + 1, env_ids)
 
+    def _vh_carry(self, ro: RolloutData, e0: int, Eb: int) -> torch.Tensor:
+        """[Eb, T, n, H]: the carry the constraint-value net reads for (env, t), t < T — layer 0 of the actor's stored carry
+        of that step (rnn.py:20: rnn_state[0]; pre-step in a stochastic record, post-step in a deterministic one)"""
+        return ro.rnn_states[e0:e0 + Eb][..., :nets.HID]
+
     def values_prepass(self, ro: RolloutData, want_Vl: bool, want_Vh: bool = True):
         """-> Vl [B,T+1] (or None), Vh [B,T+1,n,nh] of one rollout, with the reference's carry conventions."""
         cfg, T, B = self.cfg, self.T, ro.B
@@ -400,12 +405,84 @@ class Engine:
             hstar = self.arena.get("pre.hstar", Eb * n, HC)
             self.policy.forward(fin, n_seq=Eb * n, T=1, h0=h_last, tag="fin", hs_out=hstar, train=False)
             # the constraint-value net has ONE cell and reads layer 0 of the actor's packed carry (rnn.py:20: rnn_state[0])
-            h0_all[:, :T].copy_(ro.rnn_states[e0:e0 + Eb][..., :H])
+            h0_all[:, :T].copy_(self._vh_carry(ro, e0, Eb))
             h0_all[:, T].copy_(hstar.view(Eb, n, HC)[..., :H])
             act = self.Vh.forward(feats, n_seq=Eb * (T + 1) * n, T=1, h0=h0_all.view(-1, H) if self.hp.use_rnn else None,
                                   tag="pre", train=False)
             Vh_buf[e0:e0 + Eb].copy_(act["v"].view(Eb, T + 1, n, nh))
         return Vl_buf, Vh_buf
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # Vh landscape (the producer of the arrays dgppo/env/plot.py:348-372,437-447 draws; the reference ships none)
+    # ------------------------------------------------------------------------------------------------------------------
+    def require_landscape(self):
+        """ValueError unless vh_landscape serves this engine: DGPPO's constraint-value net on a LiDAR / MPE kind"""
+        if self.algo != "dgppo":
+            why = {"informarl_lagr": "its constraint-value net carries its own scan state, which needs a sequence pass first"}
+            raise ValueError(f"vh_landscape: algo '{self.algo}' is not supported: "
+                             + why.get(self.algo, "it has no constraint-value network"))
+        if self.cfg.is_vmas:
+            raise ValueError("vh_landscape: VMASReverseTransport is not supported")
+
+    def vh_landscape(self, ro: RolloutData, env_index: int, agent_id: int, frame_ids, xs, ys,
+                     events: Optional[list] = None) -> torch.Tensor:
+        """-> Vh [F, ny, nx, n, n_cost]: the constraint values of env `env_index` of the env-major record in frame
+        frame_ids[f] (a subset of [0, T)) with agent `agent_id` moved to (xs[ix], ys[iy]) and its LiDAR cast again there.
+        Every graph of frame t gets the carry values_prepass hands to Vh for (env, t).  Walked in sub-grids of at most
+        prepass_graphs graphs: whole frames, else rows of one frame, else pieces of one row.  events: a list that receives one
+        (start, features done, Vh done) triple of device events per sub-grid (tools/bench_landscape.py)."""
+        self.require_landscape()
+        cfg, T = self.cfg, self.T
+        n, nh, H = cfg.n_agents, self.n_cost, nets.HID
+        ro.finalize()
+        if not 0 <= int(env_index) < ro.B:
+            raise ValueError(f"vh_landscape: env_index {env_index} outside [0, {ro.B})")
+        if not 0 <= int(agent_id) < n:
+            raise ValueError(f"vh_landscape: agent_id {agent_id} outside [0, {n})")
+        frames = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        if frames.size == 0 or frames.min() < 0 or frames.max() >= T:
+            raise ValueError(f"vh_landscape: frame_ids must be a non-empty subset of [0, {T})")
+        xs, ys = K.sweep_axis(xs, "xs", self.device), K.sweep_axis(ys, "ys", self.device)
+        nx, ny, F = int(xs.numel()), int(ys.numel()), int(frames.size)
+        e = int(env_index)
+        step = {k: v[e] for k, v in ro.step.items()}
+        env = {k: v[e] for k, v in ro.env.items()}
+        rc, rs = OE._rays(cfg, self.device)
+        carry = self._vh_carry(ro, e, 1)[0] if self.hp.use_rnn else None            # [T, n, H]
+        out = torch.empty(F, ny, nx, n, nh, device=self.device)
+        ids_dev = torch.from_numpy(frames.astype(np.int32)).to(self.device)      # once per call; the sub-grids pass slices
+        cap = max(1, self.prepass_graphs)
+        fb = max(1, cap // (ny * nx))
+        yb = ny if cap >= ny * nx else max(1, cap // nx)
+        xb = nx if cap >= nx else cap
+        for f0 in range(0, F, fb):
+            f1 = min(F, f0 + fb)
+            fr = frames[f0:f1]
+            for y0 in range(0, ny, yb):
+                y1 = min(ny, y0 + yb)
+                for x0 in range(0, nx, xb):
+                    x1 = min(nx, x0 + xb)
+                    P = (y1 - y0) * (x1 - x0)
+                    Gb = (f1 - f0) * P
+                    feats = nets.GraphFeats(cfg, Gb, self.arena, "land")
+                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if events is not None else None
+                    if ev:
+                        ev[0].record()
+                    feats.compute_sweep(step, env, ids_dev[f0:f1], f1 - f0, agent_id, xs[x0:x1], ys[y0:y1], rc, rs,
+                                        frame_max=int(fr.max()))
+                    if ev:
+                        ev[1].record()
+                    h0 = None
+                    if carry is not None:
+                        h0 = self.arena.get("land.h0", Gb * n, H)
+                        for j, t in enumerate(fr):               # the carry of step t, for every grid point of that frame
+                            h0.view(f1 - f0, P, n, H)[j].copy_(carry[int(t)].unsqueeze(0).expand(P, n, H))
+                    act = self.Vh.forward(feats, n_seq=Gb * n, T=1, h0=h0, tag="land", train=False)
+                    out[f0:f1, y0:y1, x0:x1].copy_(act["v"].view(f1 - f0, y1 - y0, x1 - x0, n, nh))
+                    if ev:
+                        ev[2].record()
+                        events.append(tuple(ev))
+        return out
 
     # ------------------------------------------------------------------------------------------------------------------
     # update

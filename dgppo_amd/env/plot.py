@@ -81,7 +81,7 @@ class _Scene:
     """the artists of one figure; `draw(t)` moves them to frame t"""
 
     def __init__(self, ep: Episode, side_length: float, n_agent: int, n_goal: int, r: float, obs_r: float,
-                 cost_components: Sequence[str], Ta_is_unsafe, dpi: int):
+                 cost_components: Sequence[str], Ta_is_unsafe, dpi: int, landscape=None):
         import matplotlib
         matplotlib.use("Agg", force=False)
         import matplotlib.pyplot as plt
@@ -117,13 +117,50 @@ class _Scene:
         self.labels = [ax.text(pos0[i, 0], pos0[i, 1], f"{i}", size=20, color="k", ha="center", va="center", clip_on=True,
                                zorder=7) for i in range(n_agent)]
         self._plt = plt
+        # Vh landscape under the agents (dgppo/env/plot.py:348-372): one colour scale for the whole episode, centred at 0
+        self.landscape, self.contours, self.zero_line = landscape, None, None
+        if landscape is not None:
+            from matplotlib.colors import CenteredNorm
+            h = np.asarray(landscape.h(), dtype=np.float64)
+            self._h = h
+            self._frame_row = {int(t): k for k, t in enumerate(np.asarray(landscape.frames).reshape(-1))}
+            if h.shape[1] < 2 or h.shape[2] < 2:
+                print(f"(landscape grid {h.shape[2]} x {h.shape[1]}: contours need at least 2 lines each way, none are drawn)")
+            self._xy = np.meshgrid(np.asarray(landscape.xs, dtype=np.float64), np.asarray(landscape.ys, dtype=np.float64))
+            half = float(np.nanmax(np.abs(h))) if np.isfinite(h).any() else 1.0
+            self._norm = CenteredNorm(vcenter=0.0, halfrange=half if half > 0.0 else 1.0)
+            self._levels = np.linspace(-self._norm.halfrange, self._norm.halfrange, 15)
+            sm = plt.cm.ScalarMappable(norm=self._norm, cmap="RdBu_r")
+            self.fig.colorbar(sm, ax=ax, fraction=0.046, pad=0.04)
+            self.cbf_text = ax.text(0.5, 1.04, f"CBF for {int(landscape.agent)}", va="bottom", ha="center", **font)
 
     def artists(self):
+        extra = [a for a in (self.contours, self.zero_line, getattr(self, "cbf_text", None)) if a is not None]
         return [*self.agent_circles, *self.goal_circles, self.edges, self.cost_text, self.unsafe_text, self.step_text,
-                *self.labels]
+                *self.labels, *extra]
+
+    def _draw_landscape(self, t: int):
+        """the contours are rebuilt for every frame, as plot.py:437-447 does; a frame the landscape does not cover shows none"""
+        for a in (self.contours, self.zero_line):
+            if a is not None:
+                a.remove()
+        self.contours = self.zero_line = None
+        k = self._frame_row.get(int(t))
+        if k is None:
+            return
+        z = self._h[k]
+        if not np.isfinite(z).all() or z.shape[0] < 2 or z.shape[1] < 2:
+            return
+        X, Y = self._xy
+        self.contours = self.ax.contourf(X, Y, z, levels=self._levels, cmap="RdBu_r", norm=self._norm, alpha=0.5, zorder=2,
+                                         extend="both")
+        if z.min() < 0.0 <= z.max():                 # h >= 0 is unsafe (Landscape.h): a maximum of exactly 0 counts
+            self.zero_line = self.ax.contour(X, Y, z, levels=[0.0], colors="k", linewidths=2.0, zorder=4)
 
     def draw(self, t: int):
         ep, n = self.ep, self.n_agent
+        if self.landscape is not None:
+            self._draw_landscape(t)
         pos = ep.states[t, :, :2]
         for i, c in enumerate(self.agent_circles):
             c.set_center(tuple(pos[i]))
@@ -165,29 +202,30 @@ def _write(scene: _Scene, n_frames: int, video_path: pathlib.Path, fps: int = 33
 
 
 def _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_components, Ta_is_unsafe, viz_opts, dpi, n_goal,
-            index=None, max_frames=None, **kwargs) -> pathlib.Path:
+            index=None, max_frames=None, landscape=None, **kwargs) -> pathlib.Path:
     if dim != 2:
         raise NotImplementedError("only the planar environments of SURVEY §8 are rendered (dim == 2)")
     if viz_opts:
         raise NotImplementedError(f"viz_opts {sorted(viz_opts)}: CBF / Vh overlays are not built")
     ep = episode_from_rollout(rollout, index)
     n_goal = n_agent if n_goal is None else n_goal
-    scene = _Scene(ep, float(side_length), n_agent, n_goal, r, obs_r, cost_components, Ta_is_unsafe, dpi)
+    scene = _Scene(ep, float(side_length), n_agent, n_goal, r, obs_r, cost_components, Ta_is_unsafe, dpi, landscape)
     T = ep.states.shape[0] if max_frames is None else min(ep.states.shape[0], max_frames)
     return _write(scene, T, video_path)
 
 
 def render_lidar(rollout, video_path, side_length: float, dim: int, n_agent: int, n_rays: int, r: float,
                  cost_components: Tuple[str, ...], Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
-                 n_goal: Optional[int] = None, **kwargs) -> pathlib.Path:
-    """dgppo/env/plot.py:468 (LiDAR family: rectangle obstacles, `n_rays` hit nodes per agent)."""
+                 n_goal: Optional[int] = None, landscape=None, **kwargs) -> pathlib.Path:
+    """dgppo/env/plot.py:468 (LiDAR family: rectangle obstacles, `n_rays` hit nodes per agent).  landscape: a
+    trainer.data.Landscape of this episode, drawn as the reference draws viz_opts["cbf"] (plot.py:348-372,437-447)."""
     return _render(rollout, video_path, side_length, dim, n_agent, r, 0.0, cost_components, Ta_is_unsafe, viz_opts, dpi,
-                   n_goal, **kwargs)
+                   n_goal, landscape=landscape, **kwargs)
 
 
 def render_mpe(rollout, video_path, side_length: float, dim: int, n_agent: int, n_obs: int, r: float, obs_r: float,
                cost_components: Tuple[str, ...], Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
-               n_goal: Optional[int] = None, **kwargs) -> pathlib.Path:
-    """dgppo/env/plot.py:206 (MPE family: disc obstacles of radius obs_r)."""
+               n_goal: Optional[int] = None, landscape=None, **kwargs) -> pathlib.Path:
+    """dgppo/env/plot.py:206 (MPE family: disc obstacles of radius obs_r).  landscape: as in render_lidar."""
     return _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_components, Ta_is_unsafe, viz_opts, dpi,
-                   n_goal, **kwargs)
+                   n_goal, landscape=landscape, **kwargs)

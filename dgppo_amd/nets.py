@@ -137,6 +137,19 @@ class GraphFeats:
         return self.compute(step["agent"], se * ia, st * ia, env["goal"], env.get("obst"), step.get("hits"), se * ih, st * ih,
                             env_ids, n_env, n_time)
 
+    def compute_sweep(self, step, env, frame_ids, n_frames, agent_id, xs, ys, ray_cos=None, ray_sin=None, hits_out=None,
+                      frame_max=None):
+        """features of n_frames frames of ONE env of the env-major record with agent `agent_id` moved over the grid xs x ys
+        (dgppo_graph_feats_sweep; G = n_frames * ny * nx).  `step` holds that env's per-step fields [T + 1, ...] (frame f is
+        row frame_ids[f], or f without frame_ids), `env` its per-env rows; xs / ys are ops_nn.sweep_axis tensors."""
+        cfg, n = self.cfg, self.cfg.n_agents
+        if cfg.is_vmas:
+            raise ValueError("compute_sweep: VMASReverseTransport has no sweep entry point")
+        K.graph_feats_sweep(cfg, step["agent"], n * cfg.state_dim, env["goal"], env.get("obst"), step.get("hits"),
+                            n * cfg.top_k * 2, ray_cos, ray_sin, frame_ids, n_frames, agent_id, xs, ys, self.Xa,
+                            self.Xo if self.n_other > 0 else None, self.efeat, self.emask, self.Fp, hits_out, frame_max)
+        return self
+
     def compute_vmas(self, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time):
         """VMASReverseTransport: agent / body records through strides (floats), scene [B, 8] (dgppo_vmas_graph_feats)"""
         assert n_env * n_time == self.G

@@ -5,6 +5,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _native as N
@@ -257,6 +258,86 @@ def graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, goal, obst, hits, hits
         _p(env_ids, "env_ids", torch.int32), C.c_int32(n_env), C.c_int32(n_time), _p(Xa, "Xa"), _p(Xo, "Xo"),
         _p(efeat, "efeat"), _p(emask, "emask"), C.c_int32(Fp), N.stream_ptr())
     N.check(rc, "dgppo_graph_feats")
+
+
+def sweep_axis(x, name: str, device) -> torch.Tensor:
+    """one axis of a sweep grid as a dense fp32 device tensor: the coordinates are formed on the host (or given as a tensor)
+    and only copied, so host and device agree on every bit.  An empty axis or a non-finite coordinate is a ValueError."""
+    if torch.is_tensor(x):
+        t_ = x.to(device=device, dtype=torch.float32).contiguous()
+        ok = t_.ndim == 1 and t_.numel() > 0 and bool(torch.isfinite(t_).all())
+    else:
+        a = np.ascontiguousarray(np.asarray(x, dtype=np.float32))
+        ok = a.ndim == 1 and a.size > 0 and bool(np.isfinite(a).all())
+        t_ = torch.from_numpy(a).to(device) if ok else None
+    if not ok:
+        raise ValueError(f"graph_feats_sweep: {name} must be a non-empty 1-D array of finite coordinates")
+    return t_
+
+
+def graph_feats_sweep(cfg: N.EnvCfg, agent, agent_st, goal, obst, hits, hits_st, ray_cos, ray_sin, frame_ids, n_frames,
+                      agent_id, xs, ys, Xa, Xo, efeat, emask, Fp, hits_out=None, frame_max=None):
+    """dgppo_graph_feats_sweep: the features of n_frames frames of ONE env (agent / hits: base tensors read at
+    frame * stride, in floats; goal / obst: that env's rows) with agent `agent_id` moved over the grid xs [nx] x ys [ny]
+    (sweep_axis tensors).  frame_ids: a host sequence of frame numbers (copied to the device here), an int32 device tensor
+    with frame_max = its largest entry (nothing is copied), or None (0 .. n_frames-1).
+    Every refusal is raised before anything is launched."""
+    n, S = cfg.n_agents, cfg.fan_in
+    if not 0 <= int(agent_id) < n:
+        raise ValueError(f"graph_feats_sweep: agent_id {agent_id} outside [0, {n})")
+    for name, t_ in (("xs", xs), ("ys", ys)):
+        if not (torch.is_tensor(t_) and t_.is_cuda and t_.dtype == torch.float32 and t_.ndim == 1 and t_.is_contiguous()):
+            raise ValueError(f"graph_feats_sweep: {name} must be a dense 1-D float32 CUDA tensor (sweep_axis)")
+        if t_.numel() == 0:
+            raise ValueError(f"graph_feats_sweep: {name} is empty")
+    nx, ny = int(xs.numel()), int(ys.numel())
+    ids_dev = None
+    if torch.is_tensor(frame_ids):                       # already on the device: the caller vouches for the largest frame
+        if frame_max is None or n_frames < 1 or tuple(frame_ids.shape) != (n_frames,):
+            raise ValueError("graph_feats_sweep: a device frame_ids needs its shape (n_frames,) and frame_max")
+        ids_dev, last = frame_ids, int(frame_max)
+    elif frame_ids is not None:
+        ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        if ids.size != n_frames or n_frames == 0 or ids.min() < 0:
+            raise ValueError("graph_feats_sweep: frame_ids must hold n_frames >= 1 frame numbers >= 0")
+        last = int(ids.max())
+    else:
+        if n_frames < 1:
+            raise ValueError("graph_feats_sweep: n_frames must be >= 1")
+        last = n_frames - 1
+    G = n_frames * ny * nx
+    n_other = cfg.num_nodes - 1 - n
+    N.expect_shape(Xa, (G * n, Fp), "Xa")
+    if n_other > 0:
+        N.expect_shape(Xo, (G * n_other, Fp), "Xo")
+    N.expect_shape(efeat, (G * n, S, 4), "efeat")
+    N.expect_shape(emask, (G * n, S), "emask")
+    _check_strided("graph_feats_sweep", "agent", agent, 0, agent_st, (n, cfg.state_dim), None, 1, last + 1)
+    N.expect_shape(goal, (cfg.n_goals, cfg.state_dim), "goal")
+    cast = cfg.is_lidar and cfg.n_obs > 0
+    if cfg.n_obs > 0:
+        if obst is None:
+            raise ValueError("graph_feats_sweep: obst is required when n_obs > 0")
+        N.expect_shape(obst, (cfg.n_obs, cfg.obst_stride), "obst")
+    if cast:
+        if hits is None:
+            raise ValueError("graph_feats_sweep: hits is required for a LiDAR kind with obstacles")
+        _check_strided("graph_feats_sweep", "hits", hits, 0, hits_st, (n, cfg.top_k, 2), None, 1, last + 1)
+        N.expect_shape(ray_cos, (cfg.n_rays,), "ray_cos")
+        N.expect_shape(ray_sin, (cfg.n_rays,), "ray_sin")
+        if hits_out is not None:
+            N.expect_shape(hits_out, (G, cfg.top_k, 2), "hits_out")
+    if frame_ids is not None and ids_dev is None:
+        ids_dev = torch.from_numpy(ids.astype(np.int32)).to(agent.device)
+    null = C.c_void_p(0)
+    rc = N.lib().dgppo_graph_feats_sweep(
+        C.byref(cfg), C.c_void_p(agent.data_ptr()), C.c_int64(agent_st), _p(goal, "goal"),
+        _p(obst, "obst") if cfg.n_obs > 0 else null, C.c_void_p(hits.data_ptr()) if cast else null, C.c_int64(hits_st),
+        _p(ray_cos, "ray_cos") if cast else null, _p(ray_sin, "ray_sin") if cast else null,
+        _p(ids_dev, "frame_ids", torch.int32), C.c_int32(n_frames), C.c_int32(int(agent_id)), _p(xs, "xs"), C.c_int32(nx),
+        _p(ys, "ys"), C.c_int32(ny), _p(Xa, "Xa"), _p(Xo, "Xo") if n_other > 0 else null, _p(efeat, "efeat"), _p(emask, "emask"),
+        _p(hits_out, "hits_out") if (cast and hits_out is not None) else null, C.c_int32(Fp), N.stream_ptr())
+    N.check(rc, "dgppo_graph_feats_sweep")
 
 
 def vmas_graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time,

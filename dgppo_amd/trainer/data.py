@@ -4,6 +4,9 @@ records and materialises GraphsTuples with a HIP kernel only when s
 from __future__ import annotations
 
 import collections
+from typing import NamedTuple
+
+import numpy as np
 
 _FIELDS = ("graph", "actions", "rnn_states", "rewards", "costs", "dones", "log_pis", "next_graph")
 
@@ -20,3 +23,18 @@ class Rollout(collections.namedtuple("Rollout", _FIELDS)):
     time_horizon = property(lambda self: self._dim("rewards", 1), doc="steps per environment T")
     num_agents = property(lambda self: self._dim("costs", 2), doc="agents per environment")
     n_data = property(lambda self: self._dim("rewards", 0) * self._dim("rewards", 1), doc="B * T")
+
+
+class Landscape(NamedTuple):
+    """The constraint-value function of one agent swept over a grid of positions in frozen frames of an episode
+    (`DGPPO.vh_landscape`): what the reference's renderer draws as the "CBF" contours (dgppo/env/plot.py:348-372)."""
+    xs: np.ndarray        # [nx] fp32 grid lines
+    ys: np.ndarray        # [ny]
+    Vh: np.ndarray        # [F, ny, nx, n, n_cost]: Vh of every agent with `agent` standing at (xs[ix], ys[iy]) in frame frames[f]
+    agent: int            # the swept agent
+    frames: np.ndarray    # [F] frame numbers of the episode
+
+    def h(self) -> np.ndarray:
+        """[F, ny, nx]: the swept agent's largest Vh component.  >= 0 exactly where the net calls that agent unsafe — the rule
+        test.py applies to the costs (any component >= 0)."""
+        return np.asarray(self.Vh)[:, :, :, int(self.agent), :].max(axis=-1)

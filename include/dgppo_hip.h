@@ -297,6 +297,21 @@ int32_t dgppo_graph_feats(const dgppo_env_cfg* cfg, const float* agent, int64_t 
                           const int32_t* env_ids, int32_t n_env, int32_t n_time, float* Xa, float* Xo, float* efeat,
                           float* emask, int32_t Fp, void* stream);
 
+/* The same features for a Vh landscape: frame f (fid = frame_ids ? frame_ids[f] : f, read at agent + fid*agent_st and
+ * hits + fid*hits_st) of ONE environment, with agent `agent_id` moved to every point of the grid xs [nx] x ys [ny].  Graph
+ * g = (f*ny + iy)*nx + ix holds that agent at (xs[ix], ys[iy]) with its velocity (bicycle: heading and speed) kept; in the
+ * LiDAR kinds its k hit points are cast again from there against this env's rectangles (get_lidar, env/utils.py:115-136,
+ * lidar_env/base.py:126-140: start-inside factor, det == 0 NaN rays, stable top-k) while the other agents keep the recorded
+ * ones; every output has dgppo_graph_feats' layout and arithmetic (get_graph, lidar_env/base.py:227-271) for the
+ * G = n_frames*ny*nx graphs.  hits_out [G, k, 2] (may be NULL) receives the moved agent's hits.  goal / obst are this
+ * env's rows (obst: LiDAR [n_obs,16] rectangles, MPE [n_obs, sd]).  This is the producer of the arrays the reference's
+ * renderer draws as viz_opts["cbf"] (dgppo/env/plot.py:348-372,437-447); the reference ships none.                      */
+int32_t dgppo_graph_feats_sweep(const dgppo_env_cfg* cfg, const float* agent, int64_t agent_st, const float* goal,
+                                const float* obst, const float* hits, int64_t hits_st, const float* ray_cos,
+                                const float* ray_sin, const int32_t* frame_ids, int32_t n_frames, int32_t agent_id,
+                                const float* xs, int32_t nx, const float* ys, int32_t ny, float* Xa, float* Xo,
+                                float* efeat, float* emask, float* hits_out, int32_t Fp, void* stream);
+
 /* GraphTransformer attention in fixed-fan-in form (dgppo/nn/gnn.py:85-117; jraph.segment_softmax/segment_sum):
  * qt [G*n,H*F] = x_i Mcat + cvec (a Dense), logits = qt . x_sender, masked softmax over the S slots of each agent,
  * zcat [G*n,Kp] = [x_i | per head: sum a x_s (F), sum a e (4) | 1 | 0...], attn [G*n,S,H] saved for backward (NULL in

@@ -4,7 +4,9 @@
 (or `--stochastic`) policy, print per-episode reward / cost / safe rate and the aggregate, optionally append
 `test_log.csv`.  All episodes run as ONE batched rollout on the GPU (the reference loops over episodes on the host).
 Unless `--no-video`, every episode is rendered to `{path}/videos/{step}/` (test.py:150-159; `.gif` when no ffmpeg binary
-is available for `.mp4`)."""
+is available for `.mp4`).  `--landscape AGENT` (not a flag of the reference) also sweeps that agent over a
+`--landscape-grid`-squared grid in every frame of every episode, writes the learned constraint values to
+`{path}/videos/{step}/{stamp}_{name}_landscape.npz` and draws them as contours in the animation."""
 import argparse
 import datetime
 import os
@@ -56,7 +58,7 @@ def test(args):
     if args.log:
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(EV.csv_line(env, args.epi, agg))
-    if not args.no_video:
+    if not args.no_video or args.landscape is not None:
         videos_dir = pathlib.Path(args.path) / "videos" / f"{step}"
         videos_dir.mkdir(exist_ok=True, parents=True)
         stamp = datetime.datetime.now().strftime("%m%d-%H%M")
@@ -64,7 +66,16 @@ def test(args):
         for i in range(len(keys)):
             name = (f"n{num_agents}_epi{i:02}_reward{stats['reward'][i]:.3f}_cost{stats['cost'][i]:.3f}"
                     f"_sr{stats['safe_rate'][i] * 100:.0f}")
-            out = env.render_video(ro, videos_dir / f"{stamp}_{name}.mp4", unsafe[i], {}, dpi=args.dpi, index=i)
+            extra = {}
+            if args.landscape is not None:
+                land = algo.vh_landscape(ro, i, args.landscape, nx=args.landscape_grid, ny=args.landscape_grid)
+                out = videos_dir / f"{stamp}_{name}_landscape.npz"
+                np.savez(out, xs=land.xs, ys=land.ys, Vh=land.Vh, agent=land.agent, frames=land.frames)
+                print(f"landscape: {out}")
+                extra["landscape"] = land
+            if args.no_video:
+                continue
+            out = env.render_video(ro, videos_dir / f"{stamp}_{name}.mp4", unsafe[i], {}, dpi=args.dpi, index=i, **extra)
             print(f"video: {out}")
     return agg
 
@@ -76,10 +87,12 @@ FLAGS = [
     (("--debug",), "flag", False), (("--cpu",), "flag", False), (("--max-step",), "int", None), (("--log",), "flag", False),
     (("-n", "--num-agents"), "int", None), (("--seed",), "int", 1234), (("--env",), "str", None), (("--offset",), "int", 0),
     (("--dpi",), "int", 100),
+    # not the reference's flags: the Vh landscape of one agent (DGPPO.vh_landscape) over an N x N grid, per episode
+    (("--landscape",), "int", None), (("--landscape-grid",), "int", 64),
 ]
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     types = {"int": int, "str": str}
     ap = argparse.ArgumentParser(description=__doc__)
     for names, kind, default in FLAGS:
@@ -89,7 +102,11 @@ def main(argv=None):
             ap.add_argument(*names, type=types[kind[4:]], required=True)
         else:
             ap.add_argument(*names, type=types[kind], default=default)
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     if args.cpu:
         raise SystemExit("--cpu: this build has no CPU product path (the HIP library is required)")
     return test(args)
