@@ -4,7 +4,7 @@
 // Graph g = (f * ny + iy) * nx + ix is the graph of frame fid = frame_ids[f] in which agent `agent_id` stands at
 // (xs[ix], ys[iy]): its velocity (bicycle: heading and speed) is kept, its k LiDAR hit points are cast again from the new
 // position (get_lidar, env/utils.py:115-136: start-inside factor, det == 0 NaN rays, stable top-k), every other agent's hit
-// points are the recorded ones.  The outputs have the layout and arithmetic of dgppo_graph_feats (nn_graph.hip) for G graphs.
+// points are the recorded ones.  The outputs have the layout and arithmetic of dgppo_graph_feats (graph_feats.hip) for G graphs.
 //
 // Organisation: a workgroup stages the frame (states, goals, rectangle segments, recorded hits) in LDS once — per tile of
 // 64 grid points, a few hundred floats that stay in L2 across the tiles of a frame — and walks the tile, one wave per point: the wave casts the R rays of the moved agent, ranks them, and streams the graph's four
@@ -12,7 +12,7 @@
 // waves of a pass write one contiguous range of each output.
 //
 // Built with -ffp-contract=off; the ray arithmetic is env_step.h's (shared with env_step.hip), the slot topology
-// graph_topo.h's (shared with nn_graph.hip).
+// graph_topo.h's (shared with graph_feats.hip).
 #include "env_step.h"
 #include "graph_topo.h"
 

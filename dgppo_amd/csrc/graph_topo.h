@@ -1,4 +1,4 @@
-// Slot topology of the per-agent fixed-fan-in graph, shared between nn_graph.hip (features, attention) and env_sweep.hip
+// Slot topology of the per-agent fixed-fan-in graph, shared between graph_feats.hip (features), the attention kernels (nn_attn.h) and env_sweep.hip
 // (features of a swept agent): both address the same (agent, slot) layout through these definitions.
 #pragma once
 #include "common.h"

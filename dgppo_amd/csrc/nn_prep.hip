@@ -1,4 +1,4 @@
-// Weight preparation for the fixed-fan-in GNN layer (see nn_graph.hip) and its adjoint.
+// Weight preparation for the fixed-fan-in GNN layer (see nn_attn.h) and its adjoint.
 // From the reference's GraphTransformer parameters (dgppo/nn/gnn.py:86-110; flax names Dense_0..4 = q,k,v,e,u):
 //   Mcat[f, h*Fp+g] = 1/sqrt(D) * sum_d Wq[f,hD+d] Wk[g,hD+d]      cvec[h*Fp+g] = 1/sqrt(D) * sum_d bq[hD+d] Wk[g,hD+d]
 //   Wout = [ Wu ; per head (Wv_h ; We_h)/H ; mean_h bv_h ; 0 ]       (rows padded to Kp)

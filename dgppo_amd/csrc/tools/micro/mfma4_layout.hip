@@ -1,5 +1,5 @@
 // Prints the operand layout of v_mfma_f32_4x4x1_16B_f32 on this device: which A lane and which B lane feed register r of the
-// D value held by each lane.  (The block-diagonal attention kernels in csrc/nn_graph.hip assume: block = lane / 4, A row =
+// D value held by each lane.  (The block-diagonal attention kernels in csrc/attn_bd.hip assume: block = lane / 4, A row =
 // lane % 4, B column = lane % 4, D[row r][col lane % 4] in register r of the lane.)
 //   hipcc --offload-arch=gfx950 -O2 -o mfma4_layout tools/micro/mfma4_layout.hip && ./mfma4_layout
 #include <hip/hip_runtime.h>

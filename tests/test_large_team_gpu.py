@@ -1,4 +1,4 @@
-"""Teams of up to 64 agents on the GPU: the tiled attention kernels (nn_graph.hip, family TILED) against the float64
+"""Teams of up to 64 agents on the GPU: the tiled attention kernels (attn_tiled.hip, family TILED) against the float64
 oracle at the smallest shapes that leave the whole-graph families, forward determinism, and the engine / rollout / API
 paths at team sizes whose attention layers are tiled."""
 import os
@@ -20,7 +20,7 @@ LDS_IMAGE = 64 * 1024
 
 # ---- kernel level ---------------------------------------------------------------------------------------------------------
 def _image_bytes(cfg, F, H, bwd):
-    """the whole-graph LDS image of dgppo_attn_fwd / dgppo_attn_bwd (nn_graph.hip attn_image_bytes): above 64 KB the call
+    """the whole-graph LDS image of dgppo_attn_fwd / dgppo_attn_bwd (attn.hip attn_image_bytes): above 64 KB the call
     takes the tiled family (before this family existed it was refused: "graph too large for LDS")"""
     n, S, Ns = cfg.n_agents, cfg.fan_in, cfg.num_nodes - 1
     if bwd:

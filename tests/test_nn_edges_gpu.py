@@ -1,4 +1,4 @@
-"""The network kernels (nn_dense.hip, nn_elem.hip, nn_fused.hip, nn_graph.hip, nn_prep.hip) at non-finite and edge inputs:
+"""The network kernels (nn_dense.hip, nn_elem.hip, nn_fused.hip, graph_feats.hip, attn*.hip, nn_prep.hip) at non-finite and edge inputs:
 NaN / +-Inf through every ReLU as jax.nn.relu passes them, NaN sender rows behind masked slots, LayerNorm+ReLU at partial
 waves / both grid-stride loops / constant and cancelling rows, the GRU gates at saturation, and dgppo_gnn_prep / _unprep
 against their header formulas.  Every oracle is a float64 torch evaluation (oracle/nn_torch.py or a few lines here)."""

@@ -628,7 +628,7 @@ def _attn_check(got, want, name):
 
 @pytest.mark.parametrize("F,Kp", [(8, 48), (32, 144), (16, 80), (12, 64), (6, 40), (10, 56)])
 def test_attention_kernel_families_agree(cuda, F, Kp):
-    """dgppo_attn_fwd/bwd pick the kernel family from the shape alone (nn_graph.hip attn_family).  At LidarSpread n = 8:
+    """dgppo_attn_fwd/bwd pick the kernel family from the shape alone (attn.hip attn_family).  At LidarSpread n = 8:
     F = 8 the slot-sparse kernels (the backward with input gradients: VALU), F = 32 the block-diagonal ones, F = 16 the
     workgroup MFMA kernels, F = 12 MFMA forward + VALU backward, F = 6 / 10 the VALU kernels.  Every family is held to the
     float64 reference on the same kind of inputs (masked slots, NaN edge features behind the mask)."""
@@ -657,13 +657,17 @@ def test_attention_wave_kernels_across_topologies(cuda, kind, n, n_obs):
         _attn_check(_attn_run(cfg, F, H, Kp, G, inp, cuda), _attn_reference(cfg, F, H, Kp, G, inp), f"F={F}")
 
 
-@pytest.mark.parametrize("kind,n,n_obs", [(E.LIDAR_SPREAD, 8, 3), (E.MPE_SPREAD, 3, 3)])
+@pytest.mark.parametrize("kind,n,n_obs", [(E.LIDAR_SPREAD, 8, 3), (E.MPE_SPREAD, 3, 3), (E.LIDAR_SPREAD, 2, 1), (E.MPE_SPREAD, 8, 3),
+                                          (E.MPE_SPREAD, 8, 10), (E.LIDAR_SPREAD, 3, 0)])
 def test_attention_persistent_forward(cuda, kind, n, n_obs):
     """n <= 8, F = 32: a forward launch of more than 2 * cap two-wave workgroups (cap = workgroups of the persistent kernel
     that fit the chip at once) takes the persistent block-diagonal kernel, which walks several graphs per wave with the next
     graph's loads in flight.  A CU holds at most 32 waves (MI355X), so cap <= 16 * CUs and G > 4 * 16 * CUs + 1 graphs
     certainly take it (16 386 on 256 CUs); chunks of <= 512 graphs certainly do not.  Graphs are independent: both must agree
-    bit for bit, plain and with the recomputed other-node rows."""
+    bit for bit, plain and with the recomputed other-node rows.  The two forwards are instantiated per PS = ceil(shared nodes / 8)
+    (attn_bd_shape in attn_bd.hip: agents + goals when the private nodes are LiDAR hits, every node otherwise) with and without
+    hits; the cases are PS 2 with hits (16 shared nodes), PS 2 (9), PS 1 with hits (4), PS 3 (19), PS 4 (26), PS 1 (6): every
+    (PS, hits) pair an environment of n <= 8 agents reaches (with hits the shared nodes are agents + goals <= 16: PS <= 2)."""
     from dgppo_amd import _native as N, ops_nn as K_
     cfg = N.make_env_cfg(kind, n, n_obs)
     F, Kp, H, S = 32, 144, 3, cfg.fan_in

@@ -1,4 +1,4 @@
-"""Developer micro-benchmark of the attention kernels at large team sizes (the tiled family of nn_graph.hip), for a
+"""Developer micro-benchmark of the attention kernels at large team sizes (the tiled family, attn_tiled.hip), for a
 `rocprofv3 --kernel-trace --stats` run of its own:
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 tools/bench_attn_large.py [manifest.json]
 Launches, in this order and each `WARM + REPS` times: forward and backward at LidarSpread n = 32 (obs 3) for F = 8 (backward:

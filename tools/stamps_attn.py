@@ -1,5 +1,5 @@
 """Developer tool: per-phase s_memtime stamps of attn_fwd_bd_kernel (wave 0 of workgroup 0, under a full 16 384-graph launch).
-Build: hipcc ... -DDGPPO_STAMPS -c nn_graph.hip, link as libdgppo_hip_attnstamps.so; run with DGPPO_HIP_LIB pointing at it."""
+Build: hipcc ... -DDGPPO_STAMPS -c attn_bd.hip, link as libdgppo_hip_attnstamps.so; run with DGPPO_HIP_LIB pointing at it."""
 import ctypes as C, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
