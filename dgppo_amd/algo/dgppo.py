@@ -15,7 +15,7 @@ from .. import engine as EN
 from .. import init as INIT
 from .. import nets
 from .. import ops_nn as K
-from ..trainer.data import Landscape, Rollout
+from ..trainer.data import CostLandscape, Landscape, Rollout
 from ..utils import checkpoint as CK
 from ..utils.graph import GraphsTuple
 from .base import Algorithm
@@ -64,6 +64,18 @@ def _check_rnn_options(use_rnn: bool, use_lstm: bool, rnn_layers: int):
 
 def _n_cells(use_rnn: bool, rnn_layers: int) -> int:
     return rnn_layers if use_rnn else 0
+
+
+def _grid_axis(what: str, name: str, v, m: int, area: float) -> np.ndarray:
+    """one axis of a landscape grid in fp32: the given lines, or linspace(0, area, m)"""
+    if v is None:
+        if int(m) < 1:
+            raise ValueError(f"{what}: {name}: the grid is empty")
+        v = np.linspace(0.0, area, int(m))
+    v = np.asarray(v, dtype=np.float32).reshape(-1)
+    if v.size == 0 or not np.isfinite(v).all():
+        raise ValueError(f"{what}: {name} must be a non-empty array of finite coordinates")
+    return v
 
 
 class DGPPO(Algorithm):
@@ -257,20 +269,25 @@ class DGPPO(Algorithm):
         if ro is None:
             raise ValueError("vh_landscape() needs a Rollout produced by this algo's collect methods")
         area = float(self._env.cfg.area_size)
-
-        def axis(v, m, name):
-            if v is None:
-                if int(m) < 1:
-                    raise ValueError(f"vh_landscape: {name}: the grid is empty")
-                v = np.linspace(0.0, area, int(m))
-            v = np.asarray(v, dtype=np.float32).reshape(-1)
-            if v.size == 0 or not np.isfinite(v).all():
-                raise ValueError(f"vh_landscape: {name} must be a non-empty array of finite coordinates")
-            return v
-        xs, ys = axis(xs, nx, "xs"), axis(ys, ny, "ys")
+        xs, ys = _grid_axis("vh_landscape", "xs", xs, nx, area), _grid_axis("vh_landscape", "ys", ys, ny, area)
         frames = np.arange(ro.T) if frames is None else np.asarray(frames, dtype=np.int64).reshape(-1)
         Vh = self.engine.vh_landscape(ro, int(index), int(agent), frames, xs, ys)
         return Landscape(xs, ys, Vh.cpu().numpy(), int(agent), frames.astype(np.int64))
+
+    def cost_landscape(self, rollout: Rollout, index: int, agent: int, frames=None, nx: int = 64, ny: int = 64, xs=None,
+                       ys=None) -> CostLandscape:
+        """The environment's own cost h = get_cost over the grid vh_landscape sweeps (same arguments and defaults): in every
+        frame `agent` is moved to each grid point (LiDAR cast again) and the cost of every agent evaluated.  It is what the
+        learned Vh is supposed to bound (Vh >= h), and it needs no network: every algorithm has it (for HCBFCRPO it is the
+        hand-crafted CBF itself)."""
+        ro = getattr(self, "_last_rollouts", {}).get(id(rollout.actions))
+        if ro is None:
+            raise ValueError("cost_landscape() needs a Rollout produced by this algo's collect methods")
+        area = float(self._env.cfg.area_size)
+        xs, ys = _grid_axis("cost_landscape", "xs", xs, nx, area), _grid_axis("cost_landscape", "ys", ys, ny, area)
+        frames = np.arange(ro.T) if frames is None else np.asarray(frames, dtype=np.int64).reshape(-1)
+        cost = self.engine.cost_landscape(ro, int(index), int(agent), frames, xs, ys)
+        return CostLandscape(xs, ys, cost.cpu().numpy(), int(agent), frames.astype(np.int64))
 
     def update(self, rollout: Rollout, step: int) -> dict:
         ro = self._last_rollouts.pop(id(rollout.actions), None)

@@ -246,3 +246,253 @@ extern "C" int32_t dgppo_graph_feats_sweep(const dgppo_env_cfg* cfg, const float
   DGPPO_LAUNCH_CHECK();
   return 0;
 }
+
+
+// ---- cost landscape ------------------------------------------------------------------------------------------------------------
+// The environment's own cost h = get_cost (lidar_env/base.py:180-207, mpe/base.py:164-191, mpe_connect_spread.py:115-134) of
+// ALL n agents in the graphs of the sweep above: what the learned Vh is supposed to bound, at the same swept positions.
+//
+// Per frame almost everything is invariant: every unmoved agent's nearest unmoved neighbour (with the 1e6 diagonal term) and its
+// obstacle margin distance (recorded hits / discs).  A workgroup stages those once (s_md, s_mo); min is order independent and
+// returns one of its operands, so "min over the staged part, then the moved agent's distance" has the oracle's bits.
+// Phase 1 computes what depends on the point — the moved agent's nearest neighbour and obstacle distance (and the connectivity
+// term) — into LDS, phase 2 streams the tile's n * n_cost words per point, one lane per word, unit stride over the whole tile.
+// Phase 1 has two shapes: with a cast (LiDAR kinds with obstacles) a group of 32 lanes casts the R <= 32 rays of one point (two
+// points per wave; 64 lanes when R > 32); without one (MPE, or no obstacles) a lane per point.
+#define COST_NT 256
+#define COST_WAVES (COST_NT / DGPPO_WAVE)
+#define COST_TILE_CAST 64    // grid points per workgroup: 8 groups of 32 lanes walk 8 points a pass
+#define COST_TILE_LANE 256   // a lane per point
+#define COST_GROUPS (COST_NT / 32)
+
+struct CostSweepArgs {
+  dgppo_env_cfg cfg;
+  const float* agent; long agent_st;
+  const float* obst;
+  const float* hits; long hits_st;
+  const float* ray_cos;
+  const float* ray_sin;
+  const int32_t* frame_ids;
+  int agent_id, nx, nxy, tiles;
+  const float* xs;
+  const float* ys;
+  float* cost;
+  float* hits_out;
+  uint32_t rcp_W, rcp_nc;   // ceil(2^32 / d) for d = n * n_cost and n_cost (exact for idx < 2^16)
+};
+
+// sqrt(dx^2 + dy^2) as get_cost forms it, every operation correctly rounded: this file is built with -ffp-contract=off and
+// sqrtf is the IEEE square root, as in env_step.hip.  (graph_topo.h's dist_rn goes through __fsqrt_rn, which the HIP headers
+// map to the native, not correctly rounded, square root unless OCML_BASIC_ROUNDED_OPERATIONS is defined: one ulp off the oracle
+// in these outputs on the MI355X.  Elsewhere it only feeds mask comparisons.)
+__device__ inline float dist_cost(float dx, float dy) { return sqrtf(dx * dx + dy * dy); }
+// NaN-propagating max (jnp.max semantics)
+__device__ inline float nanmax(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : fmaxf(a, b); }
+// nanmin over the aligned group of `width` lanes (a power of two <= 64) this lane belongs to
+__device__ inline float group_nanmin(float v, int width) {
+  for (int off = width >> 1; off > 0; off >>= 1) v = nanmin(v, __shfl_xor(v, off));
+  return v;
+}
+
+template <bool CAST>
+__global__ void __launch_bounds__(COST_NT) cost_sweep_kernel(CostSweepArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const dgppo_env_cfg& c = a.cfg;
+  constexpr int TILE = CAST ? COST_TILE_CAST : COST_TILE_LANE;
+  const int tid = threadIdx.x, lane = tid & (DGPPO_WAVE - 1), wave = tid / DGPPO_WAVE;
+  const int f = blockIdx.x / a.tiles, tile = blockIdx.x - f * a.tiles;
+  const int fid = a.frame_ids ? a.frame_ids[f] : f;
+  const int n = c.n_agents, SD = c.state_dim, aid = a.agent_id, nc = c.n_cost;
+  const int no = c.n_obs, R = c.n_rays, k = c.top_k;
+  const bool lidar = cfg_is_lidar(c);
+  const float inf = __builtin_inff();
+  // LDS carve: every offset is a multiple of 4 floats
+  const int n4 = (n + 3) & ~3, Rp = (R + 3) & ~3, K2 = (k * 2 + 3) & ~3;
+  float* s_x = sm;                 // n   positions of the frame
+  float* s_y = s_x + n4;
+  float* s_md = s_y + n4;          // n   nearest unmoved neighbour of every unmoved agent (1e6 diagonal included)
+  float* s_mo = s_md + n4;         // n   nearest recorded hit / disc of every unmoved agent
+  float* s_px = s_mo + n4;         // TILE  the tile's points and what phase 1 found for the moved agent there
+  float* s_py = s_px + TILE;
+  float* s_pmd = s_py + TILE;
+  float* s_pmo = s_pmd + TILE;
+  float* s_pw = s_pmo + TILE;      //       connectivity term (n_cost == 3)
+  float* s_ob = s_pw + TILE;       // no*2 disc centres (MPE) | no*16 segment constants (cast)
+  float* s_rec = s_ob + no * 16;   // cast only from here: no*16 rectangle records
+  float* s_rc = s_rec + no * 16;   // R
+  float* s_rs = s_rc + Rp;         // R
+  float* s_al = s_rs + Rp;         // groups * R    alphas of the group's point
+  float* s_hit = s_al + COST_GROUPS * Rp;   // groups * k*2  hits of the moved agent
+
+  // ---- the frame, once per workgroup ----
+  const float* ag = a.agent + (size_t)fid * a.agent_st;
+  for (int i = tid; i < n; i += COST_NT) { s_x[i] = ag[i * SD]; s_y[i] = ag[i * SD + 1]; }
+  if (CAST) {
+    for (int i = tid; i < no * 16; i += COST_NT) s_rec[i] = a.obst[i];
+    for (int i = tid; i < R; i += COST_NT) { s_rc[i] = a.ray_cos[i]; s_rs[i] = a.ray_sin[i]; }
+  } else if (!lidar) {
+    for (int i = tid; i < no; i += COST_NT) { s_ob[i * 2] = a.obst[i * SD]; s_ob[i * 2 + 1] = a.obst[i * SD + 1]; }
+  }
+  __syncthreads();
+  if (CAST)
+    for (int q = tid; q < no * 4; q += COST_NT) segment_consts(s_rec + (q >> 2) * DGPPO_RECT_STRIDE, q & 3, s_ob + q * 4);
+  if (no > 0)
+    for (int j = tid; j < n; j += COST_NT) {
+      if (j == aid) continue;                        // the moved agent's own terms depend on the point: phase 1
+      float mo;
+      if (lidar) {
+        const float* hp = a.hits + (size_t)fid * a.hits_st + (size_t)j * k * 2;
+        mo = dist_cost(hp[0] - s_x[j], hp[1] - s_y[j]);
+        for (int m = 1; m < k; ++m) mo = nanmin(mo, dist_cost(hp[m * 2] - s_x[j], hp[m * 2 + 1] - s_y[j]));
+      } else {
+        mo = dist_cost(s_x[j] - s_ob[0], s_y[j] - s_ob[1]);
+        for (int m = 1; m < no; ++m) mo = nanmin(mo, dist_cost(s_x[j] - s_ob[m * 2], s_y[j] - s_ob[m * 2 + 1]));
+      }
+      s_mo[j] = mo;
+    }
+  for (int j = wave; j < n; j += COST_WAVES) {     // a wave per agent, a lane per neighbour
+    if (j == aid) continue;
+    float v = inf;
+    for (int i = lane; i < n; i += DGPPO_WAVE)
+      if (i != aid) {
+        const float d = dist_cost(s_x[j] - s_x[i], s_y[j] - s_y[i]);
+        v = nanmin(v, (i == j) ? d + 1e6f : d);
+      }
+    v = group_nanmin(v, DGPPO_WAVE);
+    if (lane == 0) s_md[j] = v;
+  }
+  __syncthreads();
+
+  const int q0 = tile * TILE, q1 = min(q0 + TILE, a.nxy);
+  // ---- phase 1: the moved agent at every point of the tile ----
+  if (CAST) {
+    const float sr = c.comm_radius;
+    const int LP = (R <= 32) ? 32 : DGPPO_WAVE, PW = DGPPO_WAVE / LP;      // lanes per point, points per wave
+    const int sub = lane / LP, sl = lane - sub * LP;
+    const uint64_t gmask = (LP == DGPPO_WAVE) ? ~0ull : (0xffffffffull << (32 * sub));
+    float* w_al = s_al + (wave * PW + sub) * Rp;
+    float* w_hit = s_hit + (wave * PW + sub) * K2;
+    // w_al / w_hit belong to one group of one wave, whose LDS operations complete in issue order: wave-level fences suffice.
+    // A group past the end of the tile repeats the last point (the wave stays convergent) and stores nothing
+    for (int base = q0 + wave * PW; base < q1; base += COST_WAVES * PW) {
+      const bool act = base + sub < q1;
+      const int q = act ? base + sub : q1 - 1;
+      const int iy = q / a.nx, ix = q - iy * a.nx;
+      const float px = a.xs[ix], py = a.ys[iy];
+      {
+        // start inside a rectangle (env/utils.py:117, r = 0): all alphas become 0
+        bool in = false;
+        for (int o = sl; o < no; o += LP) in = in || rect_inside(s_rec + o * DGPPO_RECT_STRIDE, px, py, 0.0f);
+        const float is_in = ((__ballot(in) & gmask) != 0ull) ? 1.0f : 0.0f;
+        for (int r = sl; r < R; r += LP) w_al[r] = ray_min_alpha(px, py, s_rc[r], s_rs[r], sr, s_ob, no) * (1.0f - is_in);
+      }
+      wave_sync();
+      for (int r = sl; r < R; r += LP) {
+        const int rank = ray_rank(w_al, R, r);
+        if (rank < k) ray_hit(px, py, s_rc[r], s_rs[r], sr, w_al[r], w_hit + rank * 2);
+      }
+      wave_sync();
+      float mo = inf, md = inf;
+      for (int m = sl; m < k; m += LP) mo = nanmin(mo, dist_cost(w_hit[m * 2] - px, w_hit[m * 2 + 1] - py));
+      for (int j = sl; j < n; j += LP) {
+        const float d = dist_cost(px - ((j == aid) ? px : s_x[j]), py - ((j == aid) ? py : s_y[j]));
+        md = nanmin(md, (j == aid) ? d + 1e6f : d);
+      }
+      mo = group_nanmin(mo, LP);
+      md = group_nanmin(md, LP);
+      if (act) {
+        if (sl == 0) { s_px[q - q0] = px; s_py[q - q0] = py; s_pmd[q - q0] = md; s_pmo[q - q0] = mo; }
+        if (a.hits_out != nullptr) {
+          float* ho = a.hits_out + ((size_t)f * a.nxy + q) * k * 2;
+          for (int i = sl; i < k * 2; i += LP) ho[i] = w_hit[i];
+        }
+      }
+      wave_sync();   // the next point's cast overwrites w_al / w_hit
+    }
+  } else {
+    for (int q = q0 + tid; q < q1; q += COST_NT) {
+      const int iy = q / a.nx, ix = q - iy * a.nx;
+      const float px = a.xs[ix], py = a.ys[iy];
+      float md = inf, w = -inf, mo = 0.0f;
+      for (int j = 0; j < n; ++j) {
+        const float d = dist_cost(px - ((j == aid) ? px : s_x[j]), py - ((j == aid) ? py : s_y[j]));
+        md = nanmin(md, (j == aid) ? d + 1e6f : d);
+        if (nc == 3 && j != aid) w = nanmax(w, nanmin(s_md[j], d) - c.connect_radius);
+      }
+      if (nc == 3) w = nanmax(w, md - c.connect_radius);
+      if (!lidar && no > 0) {
+        mo = dist_cost(px - s_ob[0], py - s_ob[1]);
+        for (int m = 1; m < no; ++m) mo = nanmin(mo, dist_cost(px - s_ob[m * 2], py - s_ob[m * 2 + 1]));
+      }
+      s_px[q - q0] = px; s_py[q - q0] = py; s_pmd[q - q0] = md; s_pmo[q - q0] = mo; s_pw[q - q0] = w;
+    }
+  }
+  __syncthreads();
+
+  // ---- phase 2: the tile's words, a lane per word ----
+  const int W = n * nc, words = (q1 - q0) * W;
+  const bool clip_hi = lidar || c.kind == DGPPO_ENV_MPE_CONNECT_SPREAD;   // mpe/base.py:189 clips only from below
+  const float r_obs = lidar ? c.car_radius : c.car_plus_obs;
+  float* out = a.cost + ((size_t)f * a.nxy + q0) * W;
+  for (int idx = tid; idx < words; idx += COST_NT) {
+    const int p = sweep_div(idx, a.rcp_W), rem = idx - p * W;
+    const int j = sweep_div(rem, a.rcp_nc), cc = rem - j * nc;
+    float m;
+    if (cc == 0) {
+      const float md = (j == aid) ? s_pmd[p] : nanmin(s_md[j], dist_cost(s_px[p] - s_x[j], s_py[p] - s_y[j]));
+      m = c.two_car_radius - md;
+    } else if (cc == 1) {
+      m = (no == 0) ? 0.0f : r_obs - ((j == aid) ? s_pmo[p] : s_mo[j]);
+    } else {
+      m = s_pw[p];
+    }
+    const float v = cost_value(m);
+    out[idx] = clip_hi ? clampf_nan(v, -1.0f, 1.0f) : ((v != v) ? v : fmaxf(v, -1.0f));
+  }
+}
+
+extern "C" int32_t dgppo_cost_sweep(const dgppo_env_cfg* cfg, const float* agent, int64_t agent_st, const float* obst,
+                                    const float* hits, int64_t hits_st, const float* ray_cos, const float* ray_sin,
+                                    const int32_t* frame_ids, int32_t n_frames, int32_t agent_id, const float* xs, int32_t nx,
+                                    const float* ys, int32_t ny, float* cost, float* hits_out, void* stream) {
+  int32_t rc = dgppo_validate_cfg(cfg);
+  if (rc) return rc;
+  DGPPO_REFUSE_VMAS(cfg, "dgppo_cost_sweep", "dgppo_vmas_step on a tiled record (there is no VMAS sweep)");
+  DGPPO_REQUIRE(agent_id >= 0 && agent_id < cfg->n_agents, "dgppo_cost_sweep: agent_id %d outside [0, %d)", agent_id,
+                cfg->n_agents);
+  DGPPO_REQUIRE(nx >= 0 && ny >= 0 && n_frames >= 0, "dgppo_cost_sweep: negative counts");
+  if (nx == 0 || ny == 0 || n_frames == 0) return 0;
+  DGPPO_REQUIRE(agent && xs && ys && cost, "dgppo_cost_sweep: NULL operand");
+  const int n = cfg->n_agents, no = cfg->n_obs, R = cfg->n_rays, k = cfg->top_k, nc = cfg->n_cost;
+  const bool lidar = cfg_is_lidar(*cfg), cast = lidar && no > 0;
+  if (no > 0) {
+    DGPPO_REQUIRE(obst, "dgppo_cost_sweep: obst is NULL");
+    if (lidar) DGPPO_REQUIRE(hits && ray_cos && ray_sin, "dgppo_cost_sweep: hits / ray_cos / ray_sin is NULL");
+  }
+  DGPPO_REQUIRE(nc >= 2 && !(cast && nc != 2), "dgppo_cost_sweep: n_cost must be 2 (3 for a kind without a cast)");
+  const int tile = cast ? COST_TILE_CAST : COST_TILE_LANE;
+  DGPPO_REQUIRE((long)tile * n * nc < 65536, "dgppo_cost_sweep: sizes out of range");
+  const long nxy = (long)nx * ny;
+  DGPPO_REQUIRE(nxy <= (1L << 24), "dgppo_cost_sweep: grid too large (nx * ny <= 2^24)");
+  const long tiles = (nxy + tile - 1) / tile;
+  // gridDim.x * blockDim.x has to stay below 2^32
+  DGPPO_REQUIRE(tiles * n_frames * COST_NT < (1L << 32), "dgppo_cost_sweep: too many grid points (%ld workgroups of %d threads)",
+                tiles * n_frames, COST_NT);
+  CostSweepArgs a;
+  a.cfg = *cfg;
+  a.agent = agent; a.agent_st = agent_st; a.obst = obst; a.hits = hits; a.hits_st = hits_st; a.ray_cos = ray_cos;
+  a.ray_sin = ray_sin; a.frame_ids = frame_ids; a.agent_id = agent_id; a.nx = nx; a.nxy = (int)nxy; a.tiles = (int)tiles;
+  a.xs = xs; a.ys = ys; a.cost = cost; a.hits_out = cast ? hits_out : nullptr;
+  auto rcp = [](int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); };
+  a.rcp_W = rcp(n * nc); a.rcp_nc = rcp(nc);
+  auto up4 = [](long v) { return (v + 3) & ~3L; };
+  long fl = 4 * up4(n) + 5 * tile + (long)no * 16;
+  if (cast) fl += (long)no * 16 + 2 * up4(R) + COST_GROUPS * (up4(R) + up4(k * 2));
+  DGPPO_REQUIRE(fl * 4 <= 64 * 1024, "dgppo_cost_sweep: the frame does not fit the LDS (%ld bytes)", fl * 4);
+  const size_t smem = sizeof(float) * (size_t)fl;
+  const dim3 grid((unsigned)(tiles * n_frames));
+  if (cast) hipLaunchKernelGGL(cost_sweep_kernel<true>, grid, dim3(COST_NT), smem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(cost_sweep_kernel<false>, grid, dim3(COST_NT), smem, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}

@@ -484,6 +484,35 @@ class Engine:
                         events.append(tuple(ev))
         return out
 
+    def cost_landscape(self, ro: RolloutData, env_index: int, agent_id: int, frame_ids, xs, ys) -> torch.Tensor:
+        """-> cost [F, ny, nx, n, n_cost]: the environment's own cost (get_cost) of every agent of env `env_index` of the
+        env-major record in frame frame_ids[f] (a subset of [0, T)) with agent `agent_id` moved to (xs[ix], ys[iy]) and its
+        LiDAR cast again there: what the learned Vh of vh_landscape is supposed to bound, at the same swept positions.  It
+        needs no network and no carry, so every algo and --no-rnn engines have it; one dgppo_cost_sweep launch writes the
+        result in place."""
+        cfg, T = self.cfg, self.T
+        if cfg.is_vmas:
+            raise ValueError("cost_landscape: VMASReverseTransport is not supported")
+        n = cfg.n_agents
+        ro.finalize()
+        if not 0 <= int(env_index) < ro.B:
+            raise ValueError(f"cost_landscape: env_index {env_index} outside [0, {ro.B})")
+        if not 0 <= int(agent_id) < n:
+            raise ValueError(f"cost_landscape: agent_id {agent_id} outside [0, {n})")
+        frames = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        if frames.size == 0 or frames.min() < 0 or frames.max() >= T:
+            raise ValueError(f"cost_landscape: frame_ids must be a non-empty subset of [0, {T})")
+        xs, ys = K.sweep_axis(xs, "xs", self.device), K.sweep_axis(ys, "ys", self.device)
+        nx, ny, F = int(xs.numel()), int(ys.numel()), int(frames.size)
+        e = int(env_index)
+        step = {k: v[e] for k, v in ro.step.items()}
+        env = {k: v[e] for k, v in ro.env.items()}
+        rc, rs = OE._rays(cfg, self.device)
+        out = torch.empty(F, ny, nx, n, self.n_cost, device=self.device)
+        K.cost_sweep(cfg, step["agent"], n * cfg.state_dim, env.get("obst"), step.get("hits"), n * cfg.top_k * 2, rc, rs,
+                     frames, F, int(agent_id), xs, ys, out.view(F * ny * nx, n, self.n_cost))
+        return out
+
     # ------------------------------------------------------------------------------------------------------------------
     # update
     # ------------------------------------------------------------------------------------------------------------------

@@ -81,7 +81,14 @@ class _Scene:
     """the artists of one figure; `draw(t)` moves them to frame t"""
 
     def __init__(self, ep: Episode, side_length: float, n_agent: int, n_goal: int, r: float, obs_r: float,
-                 cost_components: Sequence[str], Ta_is_unsafe, dpi: int, landscape=None):
+                 cost_components: Sequence[str], Ta_is_unsafe, dpi: int, landscape=None, cost_landscape=None):
+        if landscape is not None and cost_landscape is not None:
+            if int(landscape.agent) != int(cost_landscape.agent):
+                raise ValueError(f"landscape is swept for agent {int(landscape.agent)}, cost_landscape for agent "
+                                 f"{int(cost_landscape.agent)}")
+            if not (np.array_equal(np.asarray(landscape.xs), np.asarray(cost_landscape.xs))
+                    and np.array_equal(np.asarray(landscape.ys), np.asarray(cost_landscape.ys))):
+                raise ValueError("landscape and cost_landscape are swept over different grids")
         import matplotlib
         matplotlib.use("Agg", force=False)
         import matplotlib.pyplot as plt
@@ -117,49 +124,63 @@ class _Scene:
         self.labels = [ax.text(pos0[i, 0], pos0[i, 1], f"{i}", size=20, color="k", ha="center", va="center", clip_on=True,
                                zorder=7) for i in range(n_agent)]
         self._plt = plt
-        # Vh landscape under the agents (dgppo/env/plot.py:348-372): one colour scale for the whole episode, centred at 0
-        self.landscape, self.contours, self.zero_line = landscape, None, None
-        if landscape is not None:
+        # Vh landscape under the agents (dgppo/env/plot.py:348-372): one colour scale for the whole episode, centred at 0.
+        # The true cost (trainer.data.CostLandscape) is drawn the same way when it comes alone; next to a Vh landscape it
+        # only adds its own zero contour, dashed, so the learned and the true unsafe sets can be compared frame by frame
+        self.landscape, self.cost_landscape = landscape, cost_landscape
+        self.contours = self.zero_line = self.cost_zero_line = None
+        self._cost_h = None
+        filled = landscape if landscape is not None else cost_landscape
+        if filled is not None:
             from matplotlib.colors import CenteredNorm
-            h = np.asarray(landscape.h(), dtype=np.float64)
+            if landscape is not None and cost_landscape is not None:
+                self._cost_h = np.asarray(cost_landscape.h(), dtype=np.float64)
+                self._cost_row = {int(t): k for k, t in enumerate(np.asarray(cost_landscape.frames).reshape(-1))}
+            h = np.asarray(filled.h(), dtype=np.float64)
             self._h = h
-            self._frame_row = {int(t): k for k, t in enumerate(np.asarray(landscape.frames).reshape(-1))}
+            self._frame_row = {int(t): k for k, t in enumerate(np.asarray(filled.frames).reshape(-1))}
             if h.shape[1] < 2 or h.shape[2] < 2:
                 print(f"(landscape grid {h.shape[2]} x {h.shape[1]}: contours need at least 2 lines each way, none are drawn)")
-            self._xy = np.meshgrid(np.asarray(landscape.xs, dtype=np.float64), np.asarray(landscape.ys, dtype=np.float64))
+            self._xy = np.meshgrid(np.asarray(filled.xs, dtype=np.float64), np.asarray(filled.ys, dtype=np.float64))
             half = float(np.nanmax(np.abs(h))) if np.isfinite(h).any() else 1.0
             self._norm = CenteredNorm(vcenter=0.0, halfrange=half if half > 0.0 else 1.0)
             self._levels = np.linspace(-self._norm.halfrange, self._norm.halfrange, 15)
             sm = plt.cm.ScalarMappable(norm=self._norm, cmap="RdBu_r")
             self.fig.colorbar(sm, ax=ax, fraction=0.046, pad=0.04)
-            self.cbf_text = ax.text(0.5, 1.04, f"CBF for {int(landscape.agent)}", va="bottom", ha="center", **font)
+            self.cbf_text = ax.text(0.5, 1.04, f"{'CBF' if landscape is not None else 'Cost'} for {int(filled.agent)}",
+                                    va="bottom", ha="center", **font)
 
     def artists(self):
-        extra = [a for a in (self.contours, self.zero_line, getattr(self, "cbf_text", None)) if a is not None]
+        extra = [a for a in (self.contours, self.zero_line, self.cost_zero_line, getattr(self, "cbf_text", None))
+                 if a is not None]
         return [*self.agent_circles, *self.goal_circles, self.edges, self.cost_text, self.unsafe_text, self.step_text,
                 *self.labels, *extra]
 
     def _draw_landscape(self, t: int):
         """the contours are rebuilt for every frame, as plot.py:437-447 does; a frame the landscape does not cover shows none"""
-        for a in (self.contours, self.zero_line):
+        for a in (self.contours, self.zero_line, self.cost_zero_line):
             if a is not None:
                 a.remove()
-        self.contours = self.zero_line = None
-        k = self._frame_row.get(int(t))
-        if k is None:
-            return
-        z = self._h[k]
-        if not np.isfinite(z).all() or z.shape[0] < 2 or z.shape[1] < 2:
-            return
+        self.contours = self.zero_line = self.cost_zero_line = None
         X, Y = self._xy
-        self.contours = self.ax.contourf(X, Y, z, levels=self._levels, cmap="RdBu_r", norm=self._norm, alpha=0.5, zorder=2,
-                                         extend="both")
-        if z.min() < 0.0 <= z.max():                 # h >= 0 is unsafe (Landscape.h): a maximum of exactly 0 counts
-            self.zero_line = self.ax.contour(X, Y, z, levels=[0.0], colors="k", linewidths=2.0, zorder=4)
+        drawable = lambda z: np.isfinite(z).all() and z.shape[0] >= 2 and z.shape[1] >= 2
+        k = self._frame_row.get(int(t))
+        if k is not None and drawable(self._h[k]):
+            z = self._h[k]
+            self.contours = self.ax.contourf(X, Y, z, levels=self._levels, cmap="RdBu_r", norm=self._norm, alpha=0.5, zorder=2,
+                                             extend="both")
+            if z.min() < 0.0 <= z.max():             # h >= 0 is unsafe (Landscape.h): a maximum of exactly 0 counts
+                self.zero_line = self.ax.contour(X, Y, z, levels=[0.0], colors="k", linewidths=2.0, zorder=4)
+        k = self._cost_row.get(int(t)) if self._cost_h is not None else None
+        if k is not None and drawable(self._cost_h[k]):
+            z = self._cost_h[k]
+            if z.min() < 0.0 <= z.max():             # the true unsafe set's boundary, dashed
+                self.cost_zero_line = self.ax.contour(X, Y, z, levels=[0.0], colors="k", linewidths=2.0, linestyles="dashed",
+                                                      zorder=4)
 
     def draw(self, t: int):
         ep, n = self.ep, self.n_agent
-        if self.landscape is not None:
+        if self.landscape is not None or self.cost_landscape is not None:
             self._draw_landscape(t)
         pos = ep.states[t, :, :2]
         for i, c in enumerate(self.agent_circles):
@@ -202,30 +223,33 @@ def _write(scene: _Scene, n_frames: int, video_path: pathlib.Path, fps: int = 33
 
 
 def _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_components, Ta_is_unsafe, viz_opts, dpi, n_goal,
-            index=None, max_frames=None, landscape=None, **kwargs) -> pathlib.Path:
+            index=None, max_frames=None, landscape=None, cost_landscape=None, **kwargs) -> pathlib.Path:
     if dim != 2:
         raise NotImplementedError("only the planar environments of SURVEY §8 are rendered (dim == 2)")
     if viz_opts:
         raise NotImplementedError(f"viz_opts {sorted(viz_opts)}: CBF / Vh overlays are not built")
     ep = episode_from_rollout(rollout, index)
     n_goal = n_agent if n_goal is None else n_goal
-    scene = _Scene(ep, float(side_length), n_agent, n_goal, r, obs_r, cost_components, Ta_is_unsafe, dpi, landscape)
+    scene = _Scene(ep, float(side_length), n_agent, n_goal, r, obs_r, cost_components, Ta_is_unsafe, dpi, landscape,
+                   cost_landscape)
     T = ep.states.shape[0] if max_frames is None else min(ep.states.shape[0], max_frames)
     return _write(scene, T, video_path)
 
 
 def render_lidar(rollout, video_path, side_length: float, dim: int, n_agent: int, n_rays: int, r: float,
                  cost_components: Tuple[str, ...], Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
-                 n_goal: Optional[int] = None, landscape=None, **kwargs) -> pathlib.Path:
+                 n_goal: Optional[int] = None, landscape=None, cost_landscape=None, **kwargs) -> pathlib.Path:
     """dgppo/env/plot.py:468 (LiDAR family: rectangle obstacles, `n_rays` hit nodes per agent).  landscape: a
-    trainer.data.Landscape of this episode, drawn as the reference draws viz_opts["cbf"] (plot.py:348-372,437-447)."""
+    trainer.data.Landscape of this episode, drawn as the reference draws viz_opts["cbf"] (plot.py:348-372,437-447).
+    cost_landscape: a trainer.data.CostLandscape, drawn the same way when alone ("Cost for k"), as a dashed zero contour over
+    the Vh contours when both are given."""
     return _render(rollout, video_path, side_length, dim, n_agent, r, 0.0, cost_components, Ta_is_unsafe, viz_opts, dpi,
-                   n_goal, landscape=landscape, **kwargs)
+                   n_goal, landscape=landscape, cost_landscape=cost_landscape, **kwargs)
 
 
 def render_mpe(rollout, video_path, side_length: float, dim: int, n_agent: int, n_obs: int, r: float, obs_r: float,
                cost_components: Tuple[str, ...], Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
-               n_goal: Optional[int] = None, landscape=None, **kwargs) -> pathlib.Path:
-    """dgppo/env/plot.py:206 (MPE family: disc obstacles of radius obs_r).  landscape: as in render_lidar."""
+               n_goal: Optional[int] = None, landscape=None, cost_landscape=None, **kwargs) -> pathlib.Path:
+    """dgppo/env/plot.py:206 (MPE family: disc obstacles of radius obs_r).  landscape / cost_landscape: as in render_lidar."""
     return _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_components, Ta_is_unsafe, viz_opts, dpi,
-                   n_goal, landscape=landscape, **kwargs)
+                   n_goal, landscape=landscape, cost_landscape=cost_landscape, **kwargs)

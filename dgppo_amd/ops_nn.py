@@ -275,6 +275,54 @@ def sweep_axis(x, name: str, device) -> torch.Tensor:
     return t_
 
 
+def _sweep_grid(fn: str, cfg: N.EnvCfg, frame_ids, n_frames, agent_id, xs, ys, frame_max):
+    """the grid and frame arguments the two sweep bindings share -> nx, ny, the host frame numbers still to be copied (or
+    None), the device frame numbers given (or None), the largest frame read"""
+    n = cfg.n_agents
+    if not 0 <= int(agent_id) < n:
+        raise ValueError(f"{fn}: agent_id {agent_id} outside [0, {n})")
+    for name, t_ in (("xs", xs), ("ys", ys)):
+        if not (torch.is_tensor(t_) and t_.is_cuda and t_.dtype == torch.float32 and t_.ndim == 1 and t_.is_contiguous()):
+            raise ValueError(f"{fn}: {name} must be a dense 1-D float32 CUDA tensor (sweep_axis)")
+        if t_.numel() == 0:
+            raise ValueError(f"{fn}: {name} is empty")
+    ids = ids_dev = None
+    if torch.is_tensor(frame_ids):                       # already on the device: the caller vouches for the largest frame
+        if frame_max is None or n_frames < 1 or tuple(frame_ids.shape) != (n_frames,):
+            raise ValueError(f"{fn}: a device frame_ids needs its shape (n_frames,) and frame_max")
+        ids_dev, last = frame_ids, int(frame_max)
+    elif frame_ids is not None:
+        ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        if ids.size != n_frames or n_frames == 0 or ids.min() < 0:
+            raise ValueError(f"{fn}: frame_ids must hold n_frames >= 1 frame numbers >= 0")
+        last = int(ids.max())
+    else:
+        if n_frames < 1:
+            raise ValueError(f"{fn}: n_frames must be >= 1")
+        last = n_frames - 1
+    return int(xs.numel()), int(ys.numel()), ids, ids_dev, last
+
+
+def _sweep_record(fn: str, cfg: N.EnvCfg, agent, agent_st, obst, hits, hits_st, ray_cos, ray_sin, last, hits_out, G) -> bool:
+    """the record operands the two sweep bindings share; -> whether the kind casts rays (a LiDAR kind with obstacles)"""
+    n = cfg.n_agents
+    _check_strided(fn, "agent", agent, 0, agent_st, (n, cfg.state_dim), None, 1, last + 1)
+    cast = cfg.is_lidar and cfg.n_obs > 0
+    if cfg.n_obs > 0:
+        if obst is None:
+            raise ValueError(f"{fn}: obst is required when n_obs > 0")
+        N.expect_shape(obst, (cfg.n_obs, cfg.obst_stride), "obst")
+    if cast:
+        if hits is None:
+            raise ValueError(f"{fn}: hits is required for a LiDAR kind with obstacles")
+        _check_strided(fn, "hits", hits, 0, hits_st, (n, cfg.top_k, 2), None, 1, last + 1)
+        N.expect_shape(ray_cos, (cfg.n_rays,), "ray_cos")
+        N.expect_shape(ray_sin, (cfg.n_rays,), "ray_sin")
+        if hits_out is not None:
+            N.expect_shape(hits_out, (G, cfg.top_k, 2), "hits_out")
+    return cast
+
+
 def graph_feats_sweep(cfg: N.EnvCfg, agent, agent_st, goal, obst, hits, hits_st, ray_cos, ray_sin, frame_ids, n_frames,
                       agent_id, xs, ys, Xa, Xo, efeat, emask, Fp, hits_out=None, frame_max=None):
     """dgppo_graph_feats_sweep: the features of n_frames frames of ONE env (agent / hits: base tensors read at
@@ -282,29 +330,9 @@ def graph_feats_sweep(cfg: N.EnvCfg, agent, agent_st, goal, obst, hits, hits_st,
     (sweep_axis tensors).  frame_ids: a host sequence of frame numbers (copied to the device here), an int32 device tensor
     with frame_max = its largest entry (nothing is copied), or None (0 .. n_frames-1).
     Every refusal is raised before anything is launched."""
+    fn = "graph_feats_sweep"
     n, S = cfg.n_agents, cfg.fan_in
-    if not 0 <= int(agent_id) < n:
-        raise ValueError(f"graph_feats_sweep: agent_id {agent_id} outside [0, {n})")
-    for name, t_ in (("xs", xs), ("ys", ys)):
-        if not (torch.is_tensor(t_) and t_.is_cuda and t_.dtype == torch.float32 and t_.ndim == 1 and t_.is_contiguous()):
-            raise ValueError(f"graph_feats_sweep: {name} must be a dense 1-D float32 CUDA tensor (sweep_axis)")
-        if t_.numel() == 0:
-            raise ValueError(f"graph_feats_sweep: {name} is empty")
-    nx, ny = int(xs.numel()), int(ys.numel())
-    ids_dev = None
-    if torch.is_tensor(frame_ids):                       # already on the device: the caller vouches for the largest frame
-        if frame_max is None or n_frames < 1 or tuple(frame_ids.shape) != (n_frames,):
-            raise ValueError("graph_feats_sweep: a device frame_ids needs its shape (n_frames,) and frame_max")
-        ids_dev, last = frame_ids, int(frame_max)
-    elif frame_ids is not None:
-        ids = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
-        if ids.size != n_frames or n_frames == 0 or ids.min() < 0:
-            raise ValueError("graph_feats_sweep: frame_ids must hold n_frames >= 1 frame numbers >= 0")
-        last = int(ids.max())
-    else:
-        if n_frames < 1:
-            raise ValueError("graph_feats_sweep: n_frames must be >= 1")
-        last = n_frames - 1
+    nx, ny, ids, ids_dev, last = _sweep_grid(fn, cfg, frame_ids, n_frames, agent_id, xs, ys, frame_max)
     G = n_frames * ny * nx
     n_other = cfg.num_nodes - 1 - n
     N.expect_shape(Xa, (G * n, Fp), "Xa")
@@ -312,22 +340,9 @@ def graph_feats_sweep(cfg: N.EnvCfg, agent, agent_st, goal, obst, hits, hits_st,
         N.expect_shape(Xo, (G * n_other, Fp), "Xo")
     N.expect_shape(efeat, (G * n, S, 4), "efeat")
     N.expect_shape(emask, (G * n, S), "emask")
-    _check_strided("graph_feats_sweep", "agent", agent, 0, agent_st, (n, cfg.state_dim), None, 1, last + 1)
     N.expect_shape(goal, (cfg.n_goals, cfg.state_dim), "goal")
-    cast = cfg.is_lidar and cfg.n_obs > 0
-    if cfg.n_obs > 0:
-        if obst is None:
-            raise ValueError("graph_feats_sweep: obst is required when n_obs > 0")
-        N.expect_shape(obst, (cfg.n_obs, cfg.obst_stride), "obst")
-    if cast:
-        if hits is None:
-            raise ValueError("graph_feats_sweep: hits is required for a LiDAR kind with obstacles")
-        _check_strided("graph_feats_sweep", "hits", hits, 0, hits_st, (n, cfg.top_k, 2), None, 1, last + 1)
-        N.expect_shape(ray_cos, (cfg.n_rays,), "ray_cos")
-        N.expect_shape(ray_sin, (cfg.n_rays,), "ray_sin")
-        if hits_out is not None:
-            N.expect_shape(hits_out, (G, cfg.top_k, 2), "hits_out")
-    if frame_ids is not None and ids_dev is None:
+    cast = _sweep_record(fn, cfg, agent, agent_st, obst, hits, hits_st, ray_cos, ray_sin, last, hits_out, G)
+    if ids is not None:
         ids_dev = torch.from_numpy(ids.astype(np.int32)).to(agent.device)
     null = C.c_void_p(0)
     rc = N.lib().dgppo_graph_feats_sweep(
@@ -338,6 +353,33 @@ def graph_feats_sweep(cfg: N.EnvCfg, agent, agent_st, goal, obst, hits, hits_st,
         _p(ys, "ys"), C.c_int32(ny), _p(Xa, "Xa"), _p(Xo, "Xo") if n_other > 0 else null, _p(efeat, "efeat"), _p(emask, "emask"),
         _p(hits_out, "hits_out") if (cast and hits_out is not None) else null, C.c_int32(Fp), N.stream_ptr())
     N.check(rc, "dgppo_graph_feats_sweep")
+
+
+def cost_sweep(cfg: N.EnvCfg, agent, agent_st, obst, hits, hits_st, ray_cos, ray_sin, frame_ids, n_frames, agent_id, xs, ys,
+               cost, hits_out=None, frame_max=None):
+    """dgppo_cost_sweep: the environment's cost [G, n, n_cost] of all agents over the sweep graph_feats_sweep describes
+    (same operands without the goals, same frame_ids conventions, xs / ys: sweep_axis tensors; G = n_frames * ny * nx).
+    hits_out [G, k, 2] is for the kinds that cast rays (LiDAR with obstacles); with any other kind it is a ValueError.
+    Every refusal is raised before anything is launched."""
+    fn = "cost_sweep"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no sweep entry point")
+    if hits_out is not None and not (cfg.is_lidar and cfg.n_obs > 0):
+        raise ValueError(f"{fn}: hits_out needs a LiDAR kind with obstacles (nothing is cast here)")
+    nx, ny, ids, ids_dev, last = _sweep_grid(fn, cfg, frame_ids, n_frames, agent_id, xs, ys, frame_max)
+    G = n_frames * ny * nx
+    N.expect_shape(cost, (G, cfg.n_agents, cfg.n_cost), "cost")
+    cast = _sweep_record(fn, cfg, agent, agent_st, obst, hits, hits_st, ray_cos, ray_sin, last, hits_out, G)
+    if ids is not None:
+        ids_dev = torch.from_numpy(ids.astype(np.int32)).to(agent.device)
+    null = C.c_void_p(0)
+    rc = N.lib().dgppo_cost_sweep(
+        C.byref(cfg), C.c_void_p(agent.data_ptr()), C.c_int64(agent_st), _p(obst, "obst") if cfg.n_obs > 0 else null,
+        C.c_void_p(hits.data_ptr()) if cast else null, C.c_int64(hits_st), _p(ray_cos, "ray_cos") if cast else null,
+        _p(ray_sin, "ray_sin") if cast else null, _p(ids_dev, "frame_ids", torch.int32), C.c_int32(n_frames),
+        C.c_int32(int(agent_id)), _p(xs, "xs"), C.c_int32(nx), _p(ys, "ys"), C.c_int32(ny), _p(cost, "cost"),
+        _p(hits_out, "hits_out") if cast and hits_out is not None else null, N.stream_ptr())
+    N.check(rc, "dgppo_cost_sweep")
 
 
 def vmas_graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time,

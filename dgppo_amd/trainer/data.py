@@ -38,3 +38,18 @@ class Landscape(NamedTuple):
         """[F, ny, nx]: the swept agent's largest Vh component.  >= 0 exactly where the net calls that agent unsafe — the rule
         test.py applies to the costs (any component >= 0)."""
         return np.asarray(self.Vh)[:, :, :, int(self.agent), :].max(axis=-1)
+
+
+class CostLandscape(NamedTuple):
+    """The environment's own cost of one agent swept over a grid of positions in frozen frames of an episode
+    (`DGPPO.cost_landscape`): the ground truth the learned `Landscape` is supposed to bound, at the same swept positions."""
+    xs: np.ndarray        # [nx] fp32 grid lines
+    ys: np.ndarray        # [ny]
+    cost: np.ndarray      # [F, ny, nx, n, n_cost]: get_cost of every agent with `agent` standing at (xs[ix], ys[iy]) in frame frames[f]
+    agent: int            # the swept agent
+    frames: np.ndarray    # [F] frame numbers of the episode
+
+    def h(self) -> np.ndarray:
+        """[F, ny, nx]: the swept agent's largest cost component.  >= 0 exactly where test.py's unsafe rule fires for that
+        agent (any component >= 0)."""
+        return np.asarray(self.cost)[:, :, :, int(self.agent), :].max(axis=-1)

@@ -74,3 +74,25 @@ def latest_step(model_path: str) -> int:
     if not steps:
         raise FileNotFoundError(f"no checkpoints under {model_path}")
     return max(steps)
+
+
+def landscape_agreement(land, cost) -> Dict[str, np.ndarray]:
+    """How the learned landscape (trainer.data.Landscape) agrees with the true one (CostLandscape) of the same agent, grid
+    and frames.  Vh >= h should hold, so the unsafe set of the net should cover the true one.  Per frame [F], over the points
+    where both h() are finite: `points`, `unsafe` (true h >= 0), `missed` (true h >= 0 where the net says h < 0: a truly
+    unsafe point called safe), `conservative` (true h < 0 where the net says h >= 0); `nan` counts the other points.
+    missed_frac = missed.sum() / max(unsafe.sum(), 1), conservative_frac likewise over the truly safe points."""
+    same = (int(land.agent) == int(cost.agent)
+            and np.array_equal(np.asarray(land.xs), np.asarray(cost.xs)) and np.array_equal(np.asarray(land.ys), np.asarray(cost.ys))
+            and np.array_equal(np.asarray(land.frames).reshape(-1), np.asarray(cost.frames).reshape(-1)))
+    if not same:
+        raise ValueError("landscape_agreement: the two landscapes differ in xs, ys, agent or frames")
+    hv, hc = np.asarray(land.h()), np.asarray(cost.h())
+    ok = np.isfinite(hv) & np.isfinite(hc)
+    count = lambda m: (m & ok).sum(axis=(1, 2)).astype(np.int64)
+    points, unsafe = count(ok), count(hc >= 0.0)
+    missed, conservative = count((hc >= 0.0) & (hv < 0.0)), count((hc < 0.0) & (hv >= 0.0))
+    safe = points - unsafe
+    return dict(points=points, unsafe=unsafe, missed=missed, conservative=conservative, nan=(~ok).sum(axis=(1, 2)).astype(np.int64),
+                missed_frac=float(missed.sum() / max(int(unsafe.sum()), 1)),
+                conservative_frac=float(conservative.sum() / max(int(safe.sum()), 1)))

@@ -312,6 +312,20 @@ int32_t dgppo_graph_feats_sweep(const dgppo_env_cfg* cfg, const float* agent, in
                                 const float* xs, int32_t nx, const float* ys, int32_t ny, float* Xa, float* Xo,
                                 float* efeat, float* emask, float* hits_out, int32_t Fp, void* stream);
 
+/* The environment's own cost over the same sweep: cost [G, n, n_cost] = get_cost (lidar_env/base.py:180-207,
+ * mpe/base.py:164-191, mpe_connect_spread.py:115-134) of ALL n agents in graph g = (f*ny + iy)*nx + ix, i.e. frame fid of ONE
+ * environment with agent `agent_id` at (xs[ix], ys[iy]).  Operands as in dgppo_graph_feats_sweep (no goals are needed): in the
+ * LiDAR kinds the moved agent's k hits are cast again from the new position, every other agent's are the recorded ones; the
+ * MPE kinds use the disc obstacles.  Margins 2r - min_j d_ij (1e6 on the diagonal), r - min hit distance / r + obs_r - min disc
+ * distance (exactly 0 when n_obs == 0) and, for n_cost == 3, the NaN-propagating largest nearest-neighbour distance minus
+ * connect_radius; then -/+ 0.5 and the clip (both sides for the LiDAR kinds and MPEConnectSpread, from below otherwise).  A NaN
+ * stays a NaN.  hits_out [G, k, 2] (may be NULL) receives the moved agent's hits.  This is the ground truth the learned Vh of
+ * the landscape is supposed to bound (Vh >= h); the reference ships no producer for either.                               */
+int32_t dgppo_cost_sweep(const dgppo_env_cfg* cfg, const float* agent, int64_t agent_st, const float* obst, const float* hits,
+                         int64_t hits_st, const float* ray_cos, const float* ray_sin, const int32_t* frame_ids,
+                         int32_t n_frames, int32_t agent_id, const float* xs, int32_t nx, const float* ys, int32_t ny,
+                         float* cost, float* hits_out, void* stream);
+
 /* GraphTransformer attention in fixed-fan-in form (dgppo/nn/gnn.py:85-117; jraph.segment_softmax/segment_sum):
  * qt [G*n,H*F] = x_i Mcat + cvec (a Dense), logits = qt . x_sender, masked softmax over the S slots of each agent,
  * zcat [G*n,Kp] = [x_i | per head: sum a x_s (F), sum a e (4) | 1 | 0...], attn [G*n,S,H] saved for backward (NULL in

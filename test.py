@@ -6,7 +6,10 @@
 Unless `--no-video`, every episode is rendered to `{path}/videos/{step}/` (test.py:150-159; `.gif` when no ffmpeg binary
 is available for `.mp4`).  `--landscape AGENT` (not a flag of the reference) also sweeps that agent over a
 `--landscape-grid`-squared grid in every frame of every episode, writes the learned constraint values to
-`{path}/videos/{step}/{stamp}_{name}_landscape.npz` and draws them as contours in the animation."""
+`{path}/videos/{step}/{stamp}_{name}_landscape.npz` and draws them as contours in the animation.  `--cost-landscape AGENT`
+does the same with the environment's own cost (`{stamp}_{name}_cost.npz`; every algorithm has it); with both flags for the
+same agent the animation shows the learned contours with the true zero line dashed, and a line per episode says how much of
+the truly unsafe set the net misses."""
 import argparse
 import datetime
 import os
@@ -58,7 +61,7 @@ def test(args):
     if args.log:
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(EV.csv_line(env, args.epi, agg))
-    if not args.no_video or args.landscape is not None:
+    if not args.no_video or args.landscape is not None or args.cost_landscape is not None:
         videos_dir = pathlib.Path(args.path) / "videos" / f"{step}"
         videos_dir.mkdir(exist_ok=True, parents=True)
         stamp = datetime.datetime.now().strftime("%m%d-%H%M")
@@ -73,6 +76,18 @@ def test(args):
                 np.savez(out, xs=land.xs, ys=land.ys, Vh=land.Vh, agent=land.agent, frames=land.frames)
                 print(f"landscape: {out}")
                 extra["landscape"] = land
+            if args.cost_landscape is not None:
+                cost = algo.cost_landscape(ro, i, args.cost_landscape, nx=args.landscape_grid, ny=args.landscape_grid)
+                more = {}
+                if args.landscape == args.cost_landscape:
+                    more = EV.landscape_agreement(extra["landscape"], cost)
+                    print(f"epi: {i}, agent {cost.agent}: the learned Vh misses {more['missed_frac'] * 100:.3f}% of the truly "
+                          f"unsafe points (missed_frac), calls {more['conservative_frac'] * 100:.3f}% of the safe ones unsafe "
+                          f"(conservative_frac)")
+                out = videos_dir / f"{stamp}_{name}_cost.npz"
+                np.savez(out, xs=cost.xs, ys=cost.ys, cost=cost.cost, agent=cost.agent, frames=cost.frames, **more)
+                print(f"cost landscape: {out}")
+                extra["cost_landscape"] = cost
             if args.no_video:
                 continue
             out = env.render_video(ro, videos_dir / f"{stamp}_{name}.mp4", unsafe[i], {}, dpi=args.dpi, index=i, **extra)
@@ -90,12 +105,14 @@ FLAGS = [
     # not the reference's flags: the Vh landscape of one agent (DGPPO.vh_landscape) over an N x N grid, per episode
     (("--landscape",), "int", None), (("--landscape-grid",), "int", 64),
 ]
+# the true-cost landscape of one agent (DGPPO.cost_landscape) over the --landscape-grid grid, per episode
+COST_FLAGS = [(("--cost-landscape",), "int", None)]
 
 
 def build_parser() -> argparse.ArgumentParser:
     types = {"int": int, "str": str}
     ap = argparse.ArgumentParser(description=__doc__)
-    for names, kind, default in FLAGS:
+    for names, kind, default in FLAGS + COST_FLAGS:
         if kind == "flag":
             ap.add_argument(*names, action="store_true", default=False)
         elif kind.startswith("req:"):
