@@ -105,9 +105,10 @@ def targets(trees, ocfg, ro, det, hp, cbf_weight):
     return dict(Vl=Vl, Vh=Vh, Vh_det=Vh_det, Ql=Ql, Qh=Qh, Qh_det=Qh_det, adv=adv, safe=safe)
 
 
-def minibatch_losses(trees, ocfg, ro, det, tg, idx, hp, eps_hat):
+def minibatch_losses(trees, ocfg, ro, det, tg, idx, hp, eps_hat, detail=None):
     """losses + autograd gradients of the three networks for the minibatch `idx` (env indices).
-    trees must have requires_grad leaves."""
+    trees must have requires_grad leaves.  detail: a dict that receives the per-row log pi, ratio and clip decision
+    ([Eb,T,n] each) behind the policy scalars."""
     n = ocfg.n_agents
     rs = hp["rnn_step"]
     B, T1 = ro["agent"].shape[:2]
@@ -154,6 +155,8 @@ def minibatch_losses(trees, ocfg, ro, det, tg, idx, hp, eps_hat):
     l2 = -torch.clamp(rho, 1 - hp["clip_eps"], 1 + hp["clip_eps"]) * Aadv
     loss_pol = torch.maximum(l1, l2).mean() - hp["coef_ent"] * ent.mean()
     loss_pol.backward()
+    if detail is not None:
+        detail.update(lp=lp.detach(), rho=rho.detach(), clipped=(l2 > l1).detach())
     out.update({"policy/loss": float(loss_pol.detach()), "policy/clip_frac": float((l2 > l1).float().mean()),
                 "policy/entropy": float(ent.mean().detach()), "policy/total_variation_dist": float(0.5 * (rho - 1).abs().mean().detach())})
     return out
@@ -185,10 +188,10 @@ def targets_lagr(trees, ocfg, ro, hp, lagr):
     return dict(Vl=Vl, Vh=Vh, Ql=Ql, Qh=Qh, adv=adv, Ah=Ah)
 
 
-def minibatch_losses_lagr(trees, ocfg, ro, tg, idx, hp, eps_hat):
+def minibatch_losses_lagr(trees, ocfg, ro, tg, idx, hp, eps_hat, detail=None):
     """Vl / policy losses as InforMARL, plus update_Vh of the Lagrangian baseline: chunks of rnn_step with zero initial
     carry against Qh (informarl_lagr.py:252-284).  trees must have requires_grad leaves."""
-    out = minibatch_losses({"policy": trees["policy"], "Vl": trees["Vl"]}, ocfg, ro, None, tg, idx, hp, eps_hat)
+    out = minibatch_losses({"policy": trees["policy"], "Vl": trees["Vl"]}, ocfg, ro, None, tg, idx, hp, eps_hat, detail)
     n, rs = ocfg.n_agents, hp["rnn_step"]
     B, T1 = ro["agent"].shape[:2]
     Tn = T1 - 1

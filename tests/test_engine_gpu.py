@@ -21,13 +21,14 @@ def _np_rollout(ro):
                 log_pis=c(ro.log_pis), rnn_states=c(ro.rnn_states.contiguous()), rewards=c(ro.rewards), costs=c(ro.costs))
 
 
-def _setup(kind_name, n, n_obs, B, T_, cuda, batch_size, rnn_step, use_rnn=True, rnn_layers=1, use_lstm=False, **engine_kw):
+def _setup(kind_name, n, n_obs, B, T_, cuda, batch_size, rnn_step, use_rnn=True, rnn_layers=1, use_lstm=False, hyper_kw=None,
+           **engine_kw):
     from dgppo_amd import _native as N, engine as EN, init
     kind = N.ENV_KINDS[kind_name]
     cfg = N.make_env_cfg(kind, n, n_obs)
     ocfg = E.EnvCfg(kind, n_agents=n, n_obs=n_obs)
     hp = EN.Hyper(batch_size=batch_size, rnn_step=rnn_step, train_steps=100, use_rnn=use_rnn, rnn_layers=rnn_layers,
-                  use_lstm=use_lstm)
+                  use_lstm=use_lstm, **(hyper_kw or {}))
     eng = EN.Engine(cfg, hp, cuda, T=T_, **engine_kw)
     nc = rnn_layers if use_rnn else 0
     trees = {"policy": init.init_policy(0, cfg.node_dim, 2, 2, nc, use_lstm),
@@ -87,14 +88,62 @@ def _check_advantage(tg, wt, dt, alpha, cbf_eps, w, label=""):
     return int(flipped.sum())
 
 
-def _check_first_minibatch_grads(leaf, grads, names, tol=5e-5):
+def _check_minibatch_grads(leaf, grads, names, tol=5e-5, label=""):
+    """per leaf: |device gradient - autograd gradient of the oracle tree `leaf`| <= tol x the network's largest oracle
+    gradient entry (at least 1e-3).  -> {name: per-entry bound, number of entries, float64 norm of the oracle gradient}"""
+    out = {}
     for name in names:
         w = dict(T.tree_leaves(T.tree_map(lambda t: t.grad if t.grad is not None else torch.zeros_like(t), leaf[name])))
         gt = dict(T.tree_leaves(T.tree_map(lambda a: torch.from_numpy(np.ascontiguousarray(a)), grads[name])))
         scale = max(float(v.abs().max()) for v in w.values())
         for k in w:
             err = float((gt[k].double() - w[k].double()).abs().max())
-            assert err <= tol * max(scale, 1e-3), f"{name} grad {k}: err {err:.3e} scale {scale:.3e}"
+            assert err <= tol * max(scale, 1e-3), f"{label}{name} grad {k}: err {err:.3e} scale {scale:.3e}"
+        out[name] = dict(bound=tol * max(scale, 1e-3), count=sum(v.numel() for v in w.values()),
+                         norm=float(np.sqrt(sum(float((v.double() ** 2).sum()) for v in w.values()))))
+    return out
+
+
+_check_first_minibatch_grads = _check_minibatch_grads        # the name its first users import
+
+
+def _check_rollout_stepwise(eng, ocfg, trees, seeds, stochastic, noise_seed, n_obs):
+    """one rollout of `eng`: every stored quantity re-derived by the oracle policy `trees["policy"]` from the same noise.
+    -> the finalized record"""
+    B, T_, n = int(seeds.shape[0]), eng.T, ocfg.n_agents
+    ro = eng.rollout(seeds, stochastic, noise_seed=noise_seed).finalize()
+    r = _np_rollout(ro)
+    wa, wg, wo = E.env_reset(ocfg, [int(s) for s in seeds.cpu().numpy()])
+    np.testing.assert_array_equal(r["agent"][:, 0], wa)
+    np.testing.assert_array_equal(r["goal"], wg)
+    if wo is not None and r["obst"] is not None:   # trig-derived rectangle fields differ by <= 1 ulp (device cos/sin):
+        np.testing.assert_allclose(r["obst"], wo, atol=1e-6)
+        wo = r["obst"]                       # continue with the device's own records
+    tab = E.ray_table(32)
+    hits = E.lidar_sense(ocfg, wa[..., :2], wo, *tab)[0] if (ocfg.is_lidar and n_obs > 0) else None
+    eps = eng.arena.get("ro.eps", T_, B * n, 2).cpu().numpy().reshape(T_, B, n, 2) if stochastic else None
+    h = torch.zeros(B, n, 64)
+    agent = wa
+    for t in range(T_):
+        g = T.graph_to_torch(E.get_graph(ocfg, agent, wg, wo, hits))
+        with torch.no_grad():
+            if stochastic:
+                a, lp, h_new = T.policy_sample(trees["policy"], g, h, n, torch.from_numpy(eps[t]))
+                _close(r["log_pis"][:, t], lp.numpy(), "log_pi")
+            else:
+                a, h_new = T.policy_mode(trees["policy"], g, h, n)
+        np.testing.assert_allclose(r["actions"][:, t], a.numpy(), atol=1e-5)
+        stored = h if stochastic else h_new                     # SURVEY A.13 item 13
+        np.testing.assert_allclose(r["rnn_states"][:, t], stored.numpy(), atol=1e-5)
+        # feed the DEVICE action to the oracle env so trajectories cannot drift apart
+        out = E.env_step(ocfg, r["agent"][:, t], wg, wo, r["hits"][:, t] if hits is not None else None, r["actions"][:, t], tab)
+        np.testing.assert_array_equal(r["agent"][:, t + 1], out["next_agent"])
+        np.testing.assert_array_equal(r["rewards"][:, t], out["reward"])
+        np.testing.assert_array_equal(r["costs"][:, t], out["cost"])
+        agent, hits, h = out["next_agent"], out["next_hits"], h_new
+        if hits is not None:
+            np.testing.assert_array_equal(r["hits"][:, t + 1], hits)
+    return ro
 
 
 @pytest.mark.parametrize("kind,n,n_obs", [("LidarSpread", 3, 2), ("MPETarget", 3, 0)])
@@ -104,38 +153,7 @@ def test_rollout_matches_oracle_stepwise(cuda, kind, n, n_obs):
     cfg, ocfg, hp, eng, trees = _setup(kind, n, n_obs, B, T_, cuda, 16, 4)
     seeds = torch.arange(1, B + 1, dtype=torch.int64, device=cuda) * 104729
     for stochastic in (True, False):
-        ro = eng.rollout(seeds, stochastic, noise_seed=5).finalize()
-        r = _np_rollout(ro)
-        wa, wg, wo = E.env_reset(ocfg, [int(s) for s in seeds.cpu().numpy()])
-        np.testing.assert_array_equal(r["agent"][:, 0], wa)
-        np.testing.assert_array_equal(r["goal"], wg)
-        if wo is not None and r["obst"] is not None:   # trig-derived rectangle fields differ by <= 1 ulp (device cos/sin):
-            np.testing.assert_allclose(r["obst"], wo, atol=1e-6)
-            wo = r["obst"]                       # continue with the device's own records
-        tab = E.ray_table(32)
-        hits = E.lidar_sense(ocfg, wa[..., :2], wo, *tab)[0] if (ocfg.is_lidar and n_obs > 0) else None
-        eps = eng.arena.get("ro.eps", T_, B * n, 2).cpu().numpy().reshape(T_, B, n, 2) if stochastic else None
-        h = torch.zeros(B, n, 64)
-        agent = wa
-        for t in range(T_):
-            g = T.graph_to_torch(E.get_graph(ocfg, agent, wg, wo, hits))
-            with torch.no_grad():
-                if stochastic:
-                    a, lp, h_new = T.policy_sample(trees["policy"], g, h, n, torch.from_numpy(eps[t]))
-                    _close(r["log_pis"][:, t], lp.numpy(), "log_pi")
-                else:
-                    a, h_new = T.policy_mode(trees["policy"], g, h, n)
-            np.testing.assert_allclose(r["actions"][:, t], a.numpy(), atol=1e-5)
-            stored = h if stochastic else h_new
-            np.testing.assert_allclose(r["rnn_states"][:, t], stored.numpy(), atol=1e-5)
-            # feed the DEVICE action to the oracle env so trajectories cannot drift apart
-            out = E.env_step(ocfg, r["agent"][:, t], wg, wo, r["hits"][:, t] if hits is not None else None, r["actions"][:, t], tab)
-            np.testing.assert_array_equal(r["agent"][:, t + 1], out["next_agent"])
-            np.testing.assert_array_equal(r["rewards"][:, t], out["reward"])
-            np.testing.assert_array_equal(r["costs"][:, t], out["cost"])
-            agent, hits, h = out["next_agent"], out["next_hits"], h_new
-            if hits is not None:
-                np.testing.assert_array_equal(r["hits"][:, t + 1], hits)
+        _check_rollout_stepwise(eng, ocfg, trees, seeds, stochastic, 5, n_obs)
 
 
 @pytest.mark.parametrize("kind,n,n_obs", [("LidarSpread", 3, 2), ("MPESpread", 3, 3),
