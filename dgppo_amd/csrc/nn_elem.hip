@@ -178,6 +178,8 @@ struct GruArgs {
   float* dgh;           // [rows, 192]  (da_r | da_z | d hn_lin) -> dWh = hprev^T dgh, dbhn = colsum(dgh[:,128:])
   float* dhn;           // [rows, 64]   d hn_lin alone (the DHN_ONLY form: dgh's r / z columns are dgi's, not written twice)
   int n_seq, T, n_inner;
+  int h0_rpb;           // > 0: h0 is blocked — sequence s at h0 + (s / h0_rpb) * h0_bstride + (s % h0_rpb) * 64 (dgppo_gru_fwd_h0_blocks)
+  long h0_bstride;
 };
 
 __device__ inline size_t gru_row(const GruArgs& a, int s, int tau) {
@@ -223,7 +225,11 @@ __global__ void __launch_bounds__(256) gru_fwd_kernel(GruArgs a) {
       int s = tile * RB + r;
       s = s < a.n_seq ? s : a.n_seq - 1;
       float4 v = z4;
-      if (a.h0 != nullptr) v = reinterpret_cast<const float4*>(a.h0 + (size_t)s * GRU_H)[q];
+      if (a.h0 != nullptr) {
+        const float* hp = a.h0 + (size_t)s * GRU_H;
+        if (a.h0_rpb > 0) { const int b = s / a.h0_rpb; hp = a.h0 + (size_t)b * a.h0_bstride + (size_t)(s - b * a.h0_rpb) * GRU_H; }
+        v = reinterpret_cast<const float4*>(hp)[q];
+      }
       hpf[u][0] = v.x; hpf[u][1] = v.y; hpf[u][2] = v.z; hpf[u][3] = v.w;
     }
   };
@@ -458,31 +464,50 @@ static int32_t gru_check(const GruArgs& a) {
   return 0;
 }
 
-extern "C" int32_t dgppo_gru_fwd(const float* gi, const float* Wh, const float* bhn, const float* h0, float* hs,
-                                 float* hprev, float* gates, int32_t n_seq, int32_t T, int32_t n_inner, void* stream) {
-  GruArgs a{};
-  a.gi = gi; a.Wh = Wh; a.bhn = bhn; a.h0 = h0; a.hs = hs; a.hprev = hprev; a.gates = gates;
-  a.n_seq = n_seq; a.T = T; a.n_inner = n_inner;
+static int32_t gru_fwd_launch(GruArgs a, hipStream_t stream) {
   int32_t rc = gru_check(a);
   if (rc) return rc;
+  const int n_seq = a.n_seq;
   if (n_seq == 0) return 0;
-  DGPPO_REQUIRE(gi && Wh && bhn && hs, "gru_fwd: NULL operand");
+  DGPPO_REQUIRE(a.gi && a.Wh && a.bhn && a.hs, "gru_fwd: NULL operand");
   // 32-sequence tiles when there are enough of them to fill the device, otherwise 16 (half the MFMA chain per step)
   if (cdiv(n_seq, 32) >= 512) {
     const size_t smem = sizeof(float) * 2 * 32 * GRU_HL;
     static thread_local int cap = 0;
     if (cap == 0) cap = gru_resident(reinterpret_cast<const void*>(&gru_fwd_kernel<2>), smem);
     const int tiles = cdiv(n_seq, 32);
-    hipLaunchKernelGGL(gru_fwd_kernel<2>, dim3(tiles < cap ? tiles : cap), dim3(256), smem, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(gru_fwd_kernel<2>, dim3(tiles < cap ? tiles : cap), dim3(256), smem, stream, a);
   } else {
     const size_t smem = sizeof(float) * 2 * 16 * GRU_HL;
     static thread_local int cap = 0;
     if (cap == 0) cap = gru_resident(reinterpret_cast<const void*>(&gru_fwd_kernel<1>), smem);
     const int tiles = cdiv(n_seq, 16);
-    hipLaunchKernelGGL(gru_fwd_kernel<1>, dim3(tiles < cap ? tiles : cap), dim3(256), smem, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(gru_fwd_kernel<1>, dim3(tiles < cap ? tiles : cap), dim3(256), smem, stream, a);
   }
   DGPPO_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int32_t dgppo_gru_fwd(const float* gi, const float* Wh, const float* bhn, const float* h0, float* hs,
+                                 float* hprev, float* gates, int32_t n_seq, int32_t T, int32_t n_inner, void* stream) {
+  GruArgs a{};
+  a.gi = gi; a.Wh = Wh; a.bhn = bhn; a.h0 = h0; a.hs = hs; a.hprev = hprev; a.gates = gates;
+  a.n_seq = n_seq; a.T = T; a.n_inner = n_inner;
+  return gru_fwd_launch(a, (hipStream_t)stream);
+}
+
+extern "C" int32_t dgppo_gru_fwd_h0_blocks(const float* gi, const float* Wh, const float* bhn, const float* h0,
+                                           int32_t rows_per_block, int64_t block_stride, float* hs, float* hprev,
+                                           float* gates, int32_t n_seq, int32_t T, int32_t n_inner, void* stream) {
+  GruArgs a{};
+  a.gi = gi; a.Wh = Wh; a.bhn = bhn; a.h0 = h0; a.hs = hs; a.hprev = hprev; a.gates = gates;
+  a.n_seq = n_seq; a.T = T; a.n_inner = n_inner;
+  DGPPO_REQUIRE(h0 != nullptr && ((uintptr_t)h0 & 15) == 0, "gru_fwd_h0_blocks: h0 must be a 16-byte aligned pointer");
+  DGPPO_REQUIRE(rows_per_block >= 1, "gru_fwd_h0_blocks: rows_per_block must be >= 1 (got %d)", rows_per_block);
+  DGPPO_REQUIRE(block_stride >= (int64_t)rows_per_block * GRU_H && block_stride % 4 == 0,
+                "gru_fwd_h0_blocks: block_stride must be a multiple of 4 and >= rows_per_block * 64");
+  a.h0_rpb = rows_per_block; a.h0_bstride = (long)block_stride;
+  return gru_fwd_launch(a, (hipStream_t)stream);
 }
 
 template <bool DHN_ONLY>

@@ -102,9 +102,17 @@ class RolloutData:
             setattr(self, k, self.step[k])
         self.actions = tr("actions", self.action_tm)                  # [B, T, n, 2]
         self.log_pis = tr("log_pis", self.log_pi_tm) if self.stochastic else None
-        self._rnn_em = tr("_rnn_em", self.rnn_tm)                     # [B, T+1, n, 64]
+        # [B, T+2, n, HC]: slots 0..T are the carries of rnn_tm; the spare slot lets the value pre-pass put the final carry
+        # next to the stored ones and read all T+1 of an env in place (Engine.values_prepass)
+        T, x = self.T, self.rnn_tm
+        want = (x.shape[1], T + 2) + tuple(x.shape[2:])
+        cur = getattr(self, "_rnn_em", None)
+        if cur is None or tuple(cur.shape) != want:
+            cur = torch.empty(want, device=x.device, dtype=x.dtype)
+        cur[:, :T + 1].copy_(x.transpose(0, 1))
+        self._rnn_em = cur
         # stored carry of step t: pre-step (rollout, trainer/utils.py:46-51) or post-step (test_rollout, :71-77)
-        self.rnn_states = self._rnn_em[:, :self.T] if self.stochastic else self._rnn_em[:, 1:]
+        self.rnn_states = self._rnn_em[:, :T] if self.stochastic else self._rnn_em[:, 1:T + 1]
         self.rewards = tr("rewards", self.reward_tm)                  # [B, T]
         self.costs = tr("costs", self.cost_tm)                        # [B, T, n, n_cost]
         self._env_major = True
@@ -401,14 +409,24 @@ class Engine:
             HC = self.HC
             h_last = self.arena.get("pre.hlast", Eb * n, HC)
             h_last.view(Eb, n, HC).copy_(ro.rnn_states[e0:e0 + Eb, T - 1])
-            h0_all = self.arena.get("pre.h0all", Eb, T + 1, n, H)
             hstar = self.arena.get("pre.hstar", Eb * n, HC)
             self.policy.forward(fin, n_seq=Eb * n, T=1, h0=h_last, tag="fin", hs_out=hstar, train=False)
             # the constraint-value net has ONE cell and reads layer 0 of the actor's packed carry (rnn.py:20: rnn_state[0])
-            h0_all[:, :T].copy_(self._vh_carry(ro, e0, Eb))
-            h0_all[:, T].copy_(hstar.view(Eb, n, HC)[..., :H])
-            act = self.Vh.forward(feats, n_seq=Eb * (T + 1) * n, T=1, h0=h0_all.view(-1, H) if self.hp.use_rnn else None,
-                                  tag="pre", train=False)
+            if not self.hp.use_rnn:
+                h0 = None
+            elif HC == H:
+                # the T stored carries of an env already lie side by side in the env-major record: the final carry goes into
+                # the slot behind them (slot T of a stochastic record, the spare slot T+1 of a deterministic one — nothing
+                # else reads either) and the kernel reads all T+1 in place, one block per env.  h_last reads the slot before.
+                s0 = 0 if ro.stochastic else 1
+                ro._rnn_em[e0:e0 + Eb, s0 + T].copy_(hstar.view(Eb, n, H))
+                h0 = K.H0Blocks(ro._rnn_em[e0, s0], (T + 1) * n, (T + 2) * n * H, Eb)
+            else:                                          # stacked actor cells: layer 0 of the packed carry, gathered
+                h0_all = self.arena.get("pre.h0all", Eb, T + 1, n, H)
+                h0_all[:, :T].copy_(self._vh_carry(ro, e0, Eb))
+                h0_all[:, T].copy_(hstar.view(Eb, n, HC)[..., :H])
+                h0 = h0_all.view(-1, H)
+            act = self.Vh.forward(feats, n_seq=Eb * (T + 1) * n, T=1, h0=h0, tag="pre", train=False)
             Vh_buf[e0:e0 + Eb].copy_(act["v"].view(Eb, T + 1, n, nh))
         return Vl_buf, Vh_buf
 
@@ -652,7 +670,9 @@ class Engine:
               self.targets_hcbfcrpo(ro, step) if self.algo == "hcbfcrpo" else
               self.targets_lagr(ro, step) if lagr else self.targets(ro, det, step))
         th.append(_time.perf_counter())
-        idx_all = torch.from_numpy(np.ascontiguousarray(perm.astype(np.int64))).to(self.device)
+        perm = np.asarray(perm)
+        assert perm.size == 0 or (0 <= int(perm.min()) and int(perm.max()) < B), "perm holds env ids outside [0, B)"
+        idx_all = torch.from_numpy(np.ascontiguousarray(perm.astype(np.int32))).to(self.device)   # int32 once per update
         n_mb = B // Eb
         G = Eb * T
         R = G * n
@@ -660,7 +680,6 @@ class Engine:
         reduce = self.allreduce is not None
         A = self.arena
         # static inputs of one minibatch step: the env ids of the minibatch and everything gathered by them
-        mb_idx = A.get("mb.idx", Eb, dtype=torch.int64)
         mb_idx32 = A.get("mb.idx32", Eb, dtype=torch.int32)
         Ql_mb = A.get("mb.Ql", Eb, T)
         act_mb = A.get("mb.act", Eb, T, n, 2)
@@ -691,29 +710,28 @@ class Engine:
         def body_pre():
             """device work of ONE minibatch up to the gradient exchange (dgppo.py:276-289): gathers and the three forward /
             backward passes (with the optimiser steps when there is no exchange) — reads the minibatch's env ids from
-            mb_idx / mb_idx32."""
+            mb_idx32."""
             main = torch.cuda.current_stream(self.device) if is_cuda else None
             side = self._net_streams() if (self.multi_stream and main is not None) else None
             self.stats[:3].zero_()
             # everything the three updates read is produced on the main stream first
             feats = ctx["feats"] = self._block_feats("mb", ro, 0, Eb, 0, T, env_ids=mb_idx32)
-            torch.index_select(tg["Ql"], 0, mb_idx, out=Ql_mb)
+            pairs = [(tg["Ql"], Ql_mb)]
             if self.algo == "dgppo":
                 feats_det = self._block_feats("mbd", det, 0, Eb, 0, T, env_ids=mb_idx32)
+                full = None
                 if self.HC == H:
-                    torch.index_select(det.rnn_states, 0, mb_idx, out=h0_det)
+                    pairs.append((det.rnn_states, h0_det))
                 else:                                          # stacked cells: gather the packed carry, keep layer 0
                     full = A.get("mb.h0_det_full", Eb, T, n, self.HC)
-                    torch.index_select(det.rnn_states, 0, mb_idx, out=full)
-                    h0_det.copy_(full[..., :H])
-                torch.index_select(tg["Qh_det"], 0, mb_idx, out=Qh_det_mb)
+                    pairs.append((det.rnn_states, full))
+                pairs.append((tg["Qh_det"], Qh_det_mb))
             if lagr:
-                torch.index_select(tg["Qh"], 0, mb_idx, out=Qh_mb)
-                torch.index_select(tg["Vh"], 0, mb_idx, out=Vh_mb)
-                torch.index_select(tg["Ah"], 0, mb_idx, out=Ah_mb)
-            torch.index_select(ro.actions, 0, mb_idx, out=act_mb)
-            torch.index_select(ro.log_pis, 0, mb_idx, out=lp_old_mb)
-            torch.index_select(tg["adv"], 0, mb_idx, out=adv_mb)
+                pairs += [(tg["Qh"], Qh_mb), (tg["Vh"], Vh_mb), (tg["Ah"], Ah_mb)]
+            pairs += [(ro.actions, act_mb), (ro.log_pis, lp_old_mb), (tg["adv"], adv_mb)]
+            K.gather_rows(pairs, mb_idx32)                     # every per-env input of the minibatch in one launch
+            if self.algo == "dgppo" and full is not None:
+                h0_det.copy_(full[..., :H])
 
             def update_Vl():      # informarl.py:357-385: chunks of rnn_step with zero initial carry
                 act = self.Vl.forward(feats, n_seq=Eb * C, T=hp.rnn_step, h0=None, tag="tr")
@@ -798,22 +816,21 @@ class Engine:
 
         # The minibatch step is ~400 launches of 10-100 us kernels: issuing them from Python costs about as much host time
         # as they take on the device.  With use_graphs the step is captured once into a HIP graph (all its operands live in
-        # persistent buffers; only mb_idx changes) and replayed for every further minibatch and iteration.  Not with a
+        # persistent buffers; only mb_idx32 changes) and replayed for every further minibatch and iteration.  Not with a
         # gradient hook (a Python callback).  With a gradient exchange the step is TWO graphs — everything before the
         # collective, and the optimiser steps after it — with the collective issued eagerly between the replays, so that no
         # communication library call is ever recorded into a graph.
         slot = None
         if self.use_graphs and is_cuda and self.grad_hook is None:
             key = (self.algo, B, Eb, ro.agent.data_ptr(), det.agent.data_ptr() if det is not None else 0,
-                   tg["adv"].data_ptr(), tg["Ql"].data_ptr(), mb_idx.data_ptr(), self._update_generation())
+                   tg["adv"].data_ptr(), tg["Ql"].data_ptr(), mb_idx32.data_ptr(), self._update_generation())
             slot = self._upd_graph
             if slot.get("key") != key:
                 slot.clear()
                 slot["key"] = key
         for mb in range(n_mb):
             self._mb = mb
-            mb_idx.copy_(idx_all[mb * Eb:(mb + 1) * Eb])
-            mb_idx32.copy_(mb_idx)
+            mb_idx32.copy_(idx_all[mb * Eb:(mb + 1) * Eb])
             if slot is not None and slot.get("graph") is not None:
                 slot["graph"].replay()
                 if reduce:

@@ -326,7 +326,11 @@ class Net:
                          self.p("mlp.b2"), self.p("mlp.g2"), self.p("mlp.be2"), self.p("gru.Wi"), self.p("gru.bi"), gi, saves)
         assert n_seq * T == Rh, (n_seq, T, Rh)
         L, CD = self.rnn_layers, self.carry_dim
-        if h0 is not None:
+        h0_blocks = isinstance(h0, K.H0Blocks)      # the carry read in place from a blocked record (value pre-pass)
+        if h0_blocks:
+            assert self.rnn == "gru" and L == 1 and T == 1 and not train and self.kind != "policy", \
+                "a blocked h0 serves the one-cell GRU value nets' T = 1 inference pass"
+        elif h0 is not None:
             assert tuple(h0.shape) == (n_seq, CD), (tuple(h0.shape), n_seq, CD)
         if hs_out is not None:
             assert tuple(hs_out.shape) == (Rh, CD), (tuple(hs_out.shape), Rh, CD)
@@ -345,7 +349,10 @@ class Net:
         # (261 vs 350 us at 524 288 rows), so those keep the separate kernels.
         fused_tail = (simple and T == 1 and self.kind == "policy")
         if simple and not fused_tail:
-            K.gru_fwd(gi, self.p("gru.Wh"), self.p("gru.bhn"), h0, hs, hprev, gates, n_seq, T, n_inner)
+            if h0_blocks:
+                K.gru_fwd_h0_blocks(gi, self.p("gru.Wh"), self.p("gru.bhn"), h0, hs, hprev, gates, n_seq, T, n_inner)
+            else:
+                K.gru_fwd(gi, self.p("gru.Wh"), self.p("gru.bhn"), h0, hs, hprev, gates, n_seq, T, n_inner)
             if hprev_is_h0:
                 act["hprev"] = h0
         if self.rnn == "none":

@@ -532,6 +532,68 @@ def gru_fwd(gi, Wh, bhn, h0, hs, hprev, gates, n_seq, T, n_inner):
     N.check(rc, "dgppo_gru_fwd")
 
 
+class H0Blocks:
+    """initial GRU carry read in place from a blocked buffer (dgppo_gru_fwd_h0_blocks): sequence s lives at
+    base + (s // rows_per_block) * block_stride + (s % rows_per_block) * 64 floats.  `base` is any float32 CUDA view whose
+    first element is that of block 0 (it keeps the storage alive); n_blocks bounds what the kernel may touch."""
+
+    def __init__(self, base: torch.Tensor, rows_per_block: int, block_stride: int, n_blocks: int):
+        assert base.dtype == torch.float32 and base.is_cuda
+        st = base.untyped_storage()
+        last = base.storage_offset() + (n_blocks - 1) * block_stride + rows_per_block * 64
+        assert n_blocks >= 1 and last * 4 <= st.nbytes(), "H0Blocks: the blocks leave the storage of base"
+        self.base, self.rows_per_block, self.block_stride, self.n_blocks = base, int(rows_per_block), int(block_stride), int(n_blocks)
+
+    @property
+    def n_seq(self) -> int:
+        return self.n_blocks * self.rows_per_block
+
+
+def gru_fwd_h0_blocks(gi, Wh, bhn, h0: H0Blocks, hs, hprev, gates, n_seq, T, n_inner):
+    rows = n_seq * T
+    N.expect_shape(gi, (rows, 192), "gi")
+    N.expect_shape(hs, (rows, 64), "hs")
+    N.expect_shape(Wh, (64, 192), "Wh")
+    if n_seq > h0.n_seq:
+        raise ValueError(f"h0: {h0.n_blocks} blocks of {h0.rows_per_block} rows hold fewer than n_seq = {n_seq} carries")
+    FLOPS[0] += 2.0 * rows * 64 * 192
+    rc = N.lib().dgppo_gru_fwd_h0_blocks(_p(gi), _p(Wh), _p(bhn), C.c_void_p(h0.base.data_ptr()), h0.rows_per_block,
+                                         C.c_int64(h0.block_stride), _p(hs), _p(hprev), _p(gates), n_seq, T, n_inner,
+                                         N.stream_ptr())
+    N.check(rc, "dgppo_gru_fwd_h0_blocks")
+
+
+class GatherDesc(C.Structure):
+    """struct dgppo_gather_desc"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64), ("src_stride", C.c_int64)]
+
+
+GATHER_MAX = 8      # DGPPO_GATHER_MAX
+
+
+def gather_rows(pairs, ids):
+    """dst[e] = src[ids[e]] for every (src, dst) of `pairs` (at most GATHER_MAX) in ONE launch: torch.index_select along
+    dim 0 of each.  src may be a view along dim 0 / dim 1 (its rows dense, any row stride); dst contiguous; ids int32."""
+    if ids.dtype != torch.int32 or not ids.is_cuda or not ids.is_contiguous():
+        raise TypeError("ids must be a contiguous int32 CUDA tensor")
+    n_ids = int(ids.numel())
+    if len(pairs) > GATHER_MAX:
+        raise ValueError(f"gather_rows takes at most {GATHER_MAX} tensors per launch, got {len(pairs)}")
+    descs = (GatherDesc * max(len(pairs), 1))()
+    for k, (src, dst) in enumerate(pairs):
+        if not (src.is_cuda and dst.is_cuda):
+            raise RuntimeError("gather_rows: tensors must live on the GPU (the HIP path has no CPU fallback)")
+        if src.dtype != dst.dtype or tuple(dst.shape) != (n_ids,) + tuple(src.shape[1:]):
+            raise ValueError(f"gather_rows: pair {k}: dst {tuple(dst.shape)} {dst.dtype} does not fit src {tuple(src.shape)} "
+                             f"{src.dtype} gathered by {n_ids} ids")
+        if not dst.is_contiguous() or (src.shape[0] > 0 and not src[0].is_contiguous()):
+            raise ValueError(f"gather_rows: pair {k}: dst and the rows of src must be contiguous")
+        row = (src[0].numel() if src.shape[0] > 0 else 0) * src.element_size()
+        descs[k] = GatherDesc(src.data_ptr(), dst.data_ptr(), row, src.stride(0) * src.element_size())
+    rc = N.lib().dgppo_gather_rows(descs, len(pairs), C.c_void_p(ids.data_ptr()), n_ids, N.stream_ptr())
+    N.check(rc, "dgppo_gather_rows")
+
+
 def gru_bwd(dhs, Wh, hprev, gates, dgi, dgh, n_seq, T, n_inner):
     rows = n_seq * T
     N.expect_shape(dhs, (rows, 64), "dhs")

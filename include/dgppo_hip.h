@@ -288,6 +288,19 @@ int32_t dgppo_gru1_head_fwd(const float* gi, const float* Wh, const float* bhn, 
  * 1024); a smaller buffer shrinks the grid, NULL / 0 falls back to atomicAdd into dW (correct, slower).  No reference counterpart (XLA owns its scratch allocations).      */
 int64_t dgppo_dense_bwd_w_workspace_bytes(int32_t K, int32_t N);
 
+/* Row gather shared by up to DGPPO_GATHER_MAX tensors: dst_k[e] = src_k[ids[e]] for e < n_ids, every k in ONE launch (the
+ * minibatch prelude: torch.index_select along dim 0 of each tensor).  Row ids[e] of tensor k starts at
+ * src + ids[e] * src_stride (bytes; a view along dim 1 has src_stride > row_bytes); dst rows are dense.  row_bytes and
+ * src_stride are multiples of 4 (refused otherwise); 16-byte accesses when both, and both pointers, are multiples of 16,
+ * dwords otherwise.  descs is a HOST array.  ids are not range-checked.                                            */
+#define DGPPO_GATHER_MAX 8
+typedef struct dgppo_gather_desc {
+  const void* src;
+  void* dst;
+  int64_t row_bytes, src_stride;
+} dgppo_gather_desc;
+int32_t dgppo_gather_rows(const dgppo_gather_desc* descs, int32_t n_desc, const int32_t* ids, int32_t n_ids, void* stream);
+
 /* Compact record -> per-graph dense features for the GNN: agent node rows Xa [G*n,Fp], other node rows
  * Xo [G*(Ns-n),Fp], per-(agent,slot) edge features [G*n,S,4] and masks [G*n,S] (1/0).  Graph g = e*n_time + t reads
  * agent + env*agent_se + t*agent_st (env = env_ids ? env_ids[e] : e), likewise hits.  Same arithmetic as
@@ -388,6 +401,13 @@ int32_t dgppo_ln_relu_bwd(const float* x, const float* y, const float* stats, co
  * hs [rows,64]; hprev [rows,64] and gates [rows,256] are saved for the backward when non-NULL.                      */
 int32_t dgppo_gru_fwd(const float* gi, const float* Wh, const float* bhn, const float* h0, float* hs, float* hprev,
                       float* gates, int32_t n_seq, int32_t T, int32_t n_inner, void* stream);
+/* The same scan with h0 read in place from a blocked buffer: the carry of sequence s lives at
+ * h0 + (s / rows_per_block) * block_stride + (s % rows_per_block) * 64 (floats; block_stride a multiple of 4, h0 16-byte
+ * aligned and not NULL).  With block_stride == rows_per_block * 64 this is dgppo_gru_fwd.  The Vh pre-pass reads the
+ * env-major carry record [B, T+2, n, 64] this way: rows_per_block = (T+1)*n, block_stride = (T+2)*n*64.                */
+int32_t dgppo_gru_fwd_h0_blocks(const float* gi, const float* Wh, const float* bhn, const float* h0,
+                                int32_t rows_per_block, int64_t block_stride, float* hs, float* hprev, float* gates,
+                                int32_t n_seq, int32_t T, int32_t n_inner, void* stream);
 /* BPTT over the T steps of every sequence: dgi [rows,192], dgh [rows,192] (then dWh = hprev^T dgh).               */
 int32_t dgppo_gru_bwd(const float* dhs, const float* Wh, const float* hprev, const float* gates, float* dgi,
                       float* dgh, int32_t n_seq, int32_t T, int32_t n_inner, void* stream);
