@@ -379,8 +379,9 @@ __global__ void __launch_bounds__(64 * RW_WAVES) mlp_gi_fwd_rw_kernel(MlpGiArgs 
 //   dx = dpre1 W1^T  (optionally masked by relu'(mask): the chain's input is a ReLU output for the per-agent networks)
 // (jax.grad through MLP + GRUCell input Dense, dgppo/nn/mlp.py:17-29, dgppo/nn/rnn.py:14-30, as taken by
 // dgppo/algo/informarl.py:377,440 and dgppo/algo/dgppo.py:316.)  It replaces five launches (dense^T, ln_relu_bwd, dense^T,
-// ln_relu_bwd, dense^T) and the two round trips of dy2 / dy1 through HBM; dpre2 / dpre1 are still written because the
-// weight gradients dW2 = y1^T dpre2, dW1 = x^T dpre1 (dgppo_dense_bwd_w) read them.  LayerNorm parameter gradients
+// ln_relu_bwd, dense^T) and the two round trips of dy2 / dy1 through HBM; dgppo_mlp_gi_bwd writes dpre2 / dpre1 for the
+// weight gradients dW2 = y1^T dpre2, dW1 = x^T dpre1 (dgppo_dense_bwd_w), dgppo_mlp_gi_bwd_w forms them itself (WG below).
+// LayerNorm parameter gradients
 // (dgamma = sum dl xhat, dbeta = sum dl) are accumulated per workgroup and added with one atomic per column.
 // Same tiling as the forward: wave w owns columns 16w..16w+15 of every 64-wide result; W^T fragments (48 + 16 + 16
 // registers) stay resident; 32-row tiles; the dgi tile (192 wide) is staged in LDS, the next one prefetched in registers.
@@ -391,7 +392,17 @@ struct MlpGiBwdArgs {
   const float* mask; int ldm;
   float *dpre2, *dpre1, *dx; int lddx;
   float *dg2, *db2, *dg1, *db1;
+  // weight gradients (mlp_gi_bwd_kernel<true> only): x [M, ldx] is the chain's input; part [grid][TW_SLAB] or NULL: atomicAdd
+  const float* x; int ldx;
+  float* part;
+  float* dW2; int ldw2; float* dbias2;
+  float* dW1; int ldw1; float* dbias1;
 };
+// one partial slab of a workgroup: [dW2 64x64 | dbias2 64 | dW1 64x64 | dbias1 64], each half in the [K*N | N] form of a
+// dgppo_reduce_desc with a bias
+#define TW_HALF (FZ_H * FZ_H + FZ_H)
+#define TW_SLAB (2 * TW_HALF)
+#define TW_MIN_TILES 4     // tiles a workgroup walks at least when it writes a slab (see dgppo_mlp_gi_bwd_w)
 #define FZ_GL 194          // LDS row stride of the dgi tile: = 2 (mod 32)
 #ifndef FZ_BWD_RT
 #define FZ_BWD_RT 1         // row tiles (of 16 rows) per wave in the backward chain
@@ -400,6 +411,16 @@ struct MlpGiBwdArgs {
 #define FZ_BWD_WPE 2
 #endif
 
+// WG: the weight gradients of the two Dense layers as well, dW2 += y1^T dpre2, dW1 += x^T dpre1 and their bias sums, so that
+// dpre2 / dpre1 need not go through HBM (they are written only where given).  Wave w owns the 16 output columns it already
+// holds dpre for: its dpre values in the C/D layout (row 4 lq + r, column c) ARE the B operand of k-step r if that step
+// contracts over rows {4 lq + r : lq = 0..3}; the A operand reads the same rows of the full 64-wide y1 / x tile from LDS,
+// where the four waves put the columns they loaded anyway.  16 MFMAs and 16 accumulator registers per matrix and tile, all
+// independent of the dy chain; one slab per workgroup for the common second stage (dgppo_dense_bwd_w_reduce_batch).
+// Register budget: <true> compiles to 254 of the 256 VGPRs that two waves per SIMD allow (no AGPRs, no scratch; <false> 210).
+// There is no headroom: anything more that is live across the tile loop spills, so check -Rpass-analysis=kernel-resource-usage
+// after every edit of the chain.
+template <bool WG>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD_WPE, 8))) mlp_gi_bwd_kernel(MlpGiBwdArgs a) {
   // 16-row tiles (ONE row tile per wave, the forward has two): the W^T fragments take 80 registers, every per-row quantity of
   // the two LayerNorm backward passes is live next to them, and two row tiles spill
@@ -409,6 +430,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
   float* s_d2 = s_g + BRB * FZ_GL;            // [RB][HL]  dpre2
   float* s_d1 = s_d2 + BRB * FZ_HL;           // [RB][HL]  dpre1
   float* s_red = s_d1 + BRB * FZ_HL;          // [RB][8]   per-row (sum dxhat, sum dxhat xhat) of each of the 4 waves
+  float* s_y1 = s_red + BRB * 8;              // [RB][HL]  y1 rows (WG only; rows >= M are zeros)
+  float* s_x = s_y1 + BRB * FZ_HL;            // [RB][HL]  x rows  (WG only)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lq = lane >> 4;
   const int c = w * 16 + li;
   // B operands of X W^T: B[k][n] = W[n][k]; lane (li, lq) holds k = 4 kk + lq of output column n = c
@@ -419,6 +442,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
   for (int kk = 0; kk < 16; ++kk) { w2[kk] = a.W2[c * FZ_H + kk * 4 + lq]; w1[kk] = a.W1[c * FZ_H + kk * 4 + lq]; }
   const float g2 = a.g2[c], g1 = a.g1[c];
   float dgs[2] = {0.f, 0.f}, dbs[2] = {0.f, 0.f};     // this lane's partial sums of dgamma / dbeta: [layer 2, layer 1], column c
+  float dcs[2] = {0.f, 0.f};                          // ... and of the Dense bias gradients (column sums of dpre2, dpre1)
+  f32x4 aw2[4], aw1[4];                               // dW2 / dW1 rows 16 kt + 4 lq + r, column c
+  if constexpr (WG) {
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt) aw2[kt] = aw1[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
   const int n_tiles = (a.M + BRB - 1) / BRB;
   constexpr int GSL = BRB * 48 / 256;       // float4 slots of a dgi tile per lane
   float4 gpf[GSL];
@@ -440,8 +469,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
     }
   };
   // LayerNorm + ReLU backward for this lane's 8 elements (2 row tiles x 4 rows, column c).  v: dy in, dpre out.
+  // mid() runs between the two barriers: LDS writes made there are visible after the second one
   auto ln_relu_bwd = [&](float (&v)[BRT][4], const float (&pv)[BRT][4], const float (&yv)[BRT][4], const float2 (&st)[BRT][4], float g,
-                         float& dg_acc, float& db_acc, float* s_out, float* d_out, int row0) {
+                         float& dg_acc, float& db_acc, float& dc_acc, float* s_out, float* d_out, int row0, auto&& mid) {
     float xh[BRT][4], dxh[BRT][4];
 #pragma unroll
     for (int rt = 0; rt < BRT; ++rt)
@@ -462,6 +492,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
         v[rt][r] = ms.y;                                  // keep rstd for the second half
       }
     FZ_LDS_BARRIER();
+    mid();
 #pragma unroll
     for (int rt = 0; rt < BRT; ++rt)
 #pragma unroll
@@ -474,7 +505,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
         v[rt][r] = dp;
         s_out[rl * FZ_HL + c] = dp;
         const int row = row0 + rl;
-        if (row < a.M) d_out[(size_t)row * FZ_H + c] = dp;
+        if constexpr (WG) {
+          const bool ok = row < a.M;
+          if (ok) dc_acc += dp;                           // rows >= M contribute exactly zero, whatever the clamped row holds
+          if (ok && d_out != nullptr) d_out[(size_t)row * FZ_H + c] = dp;
+        } else {
+          if (row < a.M) d_out[(size_t)row * FZ_H + c] = dp;
+        }
       }
     FZ_LDS_BARRIER();
   };
@@ -498,6 +535,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
         o[rt][r] = src[(size_t)row * ld + c];
       }
   };
+  // acc[kt] += A^T dpre over the tile's 16 rows: A = s_a (y1 or x rows, zeros past M), B = this lane's dpre values
+  auto wgrad = [&](f32x4 (&acc)[4], const float* s_a, const float (&v)[BRT][4], int row0) {
+    static_assert(BRT == 1, "the weight-gradient contraction is written for one row tile per wave");
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float bv = (row0 + lq * 4 + r < a.M) ? v[0][r] : 0.0f;
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+        acc[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(s_a[(lq * 4 + r) * FZ_HL + kt * 16 + li], bv, acc[kt], 0, 0, 0);
+    }
+  };
   // the next tile's dgi rows are requested while the current tile computes (3 float4 per lane with 16-row tiles) and committed
   // to LDS once every read of the current tile is retired (after the first barrier pair of the first LayerNorm backward)
   int tile = blockIdx.x;
@@ -510,11 +558,23 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
     if (more) fetch(nxt);
     // everything this tile reads from global memory is requested here, before the first GEMM: a load issued where it is
     // needed costs a full memory round trip per LayerNorm stage (measured: 155 -> 139 -> see profiles/README.md)
-    float pv2[BRT][4], yv2[BRT][4], pv1[BRT][4], yv1[BRT][4], mk[BRT][4];
+    float pv2[BRT][4], yv2[BRT][4], pv1[BRT][4], yv1[BRT][4], mk[BRT][4], xv[BRT][4];
     float2 sv2[BRT][4], sv1[BRT][4];
     load8(a.p2, FZ_H, row0, pv2); load8(a.y2, FZ_H, row0, yv2); load_st(a.st2, row0, sv2);
     load8(a.p1, FZ_H, row0, pv1); load8(a.y1, FZ_H, row0, yv1); load_st(a.st1, row0, sv1);
-    if (a.mask != nullptr) load8(a.mask, a.ldm, row0, mk);
+    if constexpr (WG) {
+      load8(a.x, a.ldx, row0, xv);
+      if (a.mask != nullptr) {                     // the per-agent networks mask by their own input: one load serves both
+        if (a.mask == a.x && a.ldm == a.ldx) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) mk[0][r] = xv[0][r];
+        } else {
+          load8(a.mask, a.ldm, row0, mk);
+        }
+      }
+    } else {
+      if (a.mask != nullptr) load8(a.mask, a.ldm, row0, mk);
+    }
     __builtin_amdgcn_sched_barrier(0);
     f32x4 acc[BRT];
     float v[BRT][4];
@@ -539,7 +599,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[rt][r] = acc[rt][r];
     // (the barriers inside ln_relu_bwd retire every read of s_g: the next tile's rows may be committed after it)
-    ln_relu_bwd(v, pv2, yv2, sv2, g2, dgs[0], dbs[0], s_d2, a.dpre2, row0);
+    // (s_y1 / s_x of the previous tile are read until its end: they are rewritten behind the first barrier of this tile)
+    ln_relu_bwd(v, pv2, yv2, sv2, g2, dgs[0], dbs[0], dcs[0], s_d2, a.dpre2, row0, [&]() {
+      if constexpr (WG) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int rl = lq * 4 + r;
+          const bool ok = row0 + rl < a.M;
+          s_y1[rl * FZ_HL + c] = ok ? yv1[0][r] : 0.0f;
+          s_x[rl * FZ_HL + c] = ok ? xv[0][r] : 0.0f;
+        }
+      }
+    });
     if (more) commit();
     // ---- dy1 = dpre2 W2^T ----
     {
@@ -554,12 +625,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
       for (int kk = 0; kk < 16; ++kk)
 #pragma unroll
         for (int rt = 0; rt < BRT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[rt][kk], w2[kk], acc[rt], 0, 0, 0);
+      if constexpr (WG) wgrad(aw2, s_y1, v, row0);          // v still holds dpre2: independent MFMAs next to the dependent chain
     }
 #pragma unroll
     for (int rt = 0; rt < BRT; ++rt)
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[rt][r] = acc[rt][r];
-    ln_relu_bwd(v, pv1, yv1, sv1, g1, dgs[1], dbs[1], s_d1, a.dpre1, row0);
+    ln_relu_bwd(v, pv1, yv1, sv1, g1, dgs[1], dbs[1], dcs[1], s_d1, a.dpre1, row0, []() {});
     // ---- dx = dpre1 W1^T ----
     {
       float areg[BRT][16];
@@ -573,6 +645,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
       for (int kk = 0; kk < 16; ++kk)
 #pragma unroll
         for (int rt = 0; rt < BRT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[rt][kk], w1[kk], acc[rt], 0, 0, 0);
+      if constexpr (WG) wgrad(aw1, s_x, v, row0);
     }
 #pragma unroll
     for (int rt = 0; rt < BRT; ++rt)
@@ -587,17 +660,64 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
   }
   // ---- LayerNorm parameter gradients: sum the 4 row groups of each column in LDS, one atomic per column and workgroup ----
   __syncthreads();
-  float* red = sm;                                // [4 values][4 lq][64 columns]
+  float* red = sm;                                // [4 (+ 2) values][4 lq][64 columns]
   red[(0 * 4 + lq) * 64 + c] = dgs[0]; red[(1 * 4 + lq) * 64 + c] = dbs[0];
   red[(2 * 4 + lq) * 64 + c] = dgs[1]; red[(3 * 4 + lq) * 64 + c] = dbs[1];
+  if constexpr (WG) { red[(4 * 4 + lq) * 64 + c] = dcs[0]; red[(5 * 4 + lq) * 64 + c] = dcs[1]; }
   __syncthreads();
+  auto colsum = [&](int which, int col) {
+    return (red[(which * 4 + 0) * 64 + col] + red[(which * 4 + 1) * 64 + col]) +
+           (red[(which * 4 + 2) * 64 + col] + red[(which * 4 + 3) * 64 + col]);
+  };
   {
     const int which = tid >> 6, col = tid & 63;
-    const float tot = (red[(which * 4 + 0) * 64 + col] + red[(which * 4 + 1) * 64 + col]) +
-                      (red[(which * 4 + 2) * 64 + col] + red[(which * 4 + 3) * 64 + col]);
     float* dst = which == 0 ? a.dg2 : (which == 1 ? a.db2 : (which == 2 ? a.dg1 : a.db1));
-    atomicAdd(dst + col, tot);
+    atomicAdd(dst + col, colsum(which, col));
   }
+  if constexpr (WG) {
+    float* slab = a.part ? a.part + (size_t)blockIdx.x * TW_SLAB : nullptr;
+    if (tid < 128) {                              // Dense bias gradients: layer 2, layer 1
+      const int l = tid >> 6, col = tid & 63;
+      const float tot = colsum(4 + l, col);
+      if (slab) slab[l * TW_HALF + FZ_H * FZ_H + col] = tot;
+      else atomicAdd((l == 0 ? a.dbias2 : a.dbias1) + col, tot);
+    }
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int krow = kt * 16 + lq * 4 + r;
+        if (slab) {
+          slab[krow * FZ_H + c] = aw2[kt][r];
+          slab[TW_HALF + krow * FZ_H + c] = aw1[kt][r];
+        } else {
+          atomicAdd(a.dW2 + (size_t)krow * a.ldw2 + c, aw2[kt][r]);
+          atomicAdd(a.dW1 + (size_t)krow * a.ldw1 + c, aw1[kt][r]);
+        }
+      }
+  }
+}
+
+// grid cap of the persistent backward chain kernel: every workgroup the device can hold at once
+template <bool WG>
+static int mlp_gi_bwd_cap(size_t smem) {
+  static thread_local int cap = 0;
+  if (cap == 0) {
+    int per_cu = 0, dev = 0, cus = 256;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&mlp_gi_bwd_kernel<WG>), 256, smem) !=
+            hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+    cap = per_cu * cus;
+  }
+  return cap;
+}
+template <bool WG>
+constexpr size_t mlp_gi_bwd_smem() {
+  constexpr int BRB = 16 * FZ_BWD_RT;
+  // the final reduction of the LayerNorm (and bias) gradients reuses the tile buffers
+  constexpr size_t smem_t = sizeof(float) * (BRB * FZ_GL + (WG ? 4 : 2) * BRB * FZ_HL + BRB * 8), smem_r = sizeof(float) * (WG ? 24 : 16) * 64;
+  return smem_t > smem_r ? smem_t : smem_r;
 }
 
 extern "C" int32_t dgppo_mlp_gi_bwd(const float* dgi, const float* Wi, const float* W2, const float* W1, const float* g2,
@@ -610,23 +730,62 @@ extern "C" int32_t dgppo_mlp_gi_bwd(const float* dgi, const float* Wi, const flo
                 dg1 && db1, "mlp_gi_bwd: NULL operand");
   DGPPO_REQUIRE((reinterpret_cast<uintptr_t>(dgi) & 15) == 0, "mlp_gi_bwd: dgi must be 16-byte aligned");
   if (M == 0) return 0;
-  MlpGiBwdArgs a{dgi, M, Wi, W2, W1, g2, g1, p2, y2, st2, p1, y1, st1, relu_mask, ldm, dpre2, dpre1, dx, lddx, dg2, db2, dg1, db1};
-  constexpr int BRB = 16 * FZ_BWD_RT;
-  const size_t smem_t = sizeof(float) * (BRB * FZ_GL + 2 * BRB * FZ_HL + BRB * 8), smem_r = sizeof(float) * 16 * 64;
-  const size_t smem = smem_t > smem_r ? smem_t : smem_r;   // the final reduction of the LayerNorm gradients reuses the buffer
-  static thread_local int cap = 0;
-  if (cap == 0) {
-    int per_cu = 0, dev = 0, cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&mlp_gi_bwd_kernel), 256, smem) !=
-            hipSuccess || per_cu < 1) per_cu = 1;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-    cap = per_cu * cus;
-  }
-  const int tiles = (M + BRB - 1) / BRB;
-  hipLaunchKernelGGL(mlp_gi_bwd_kernel, dim3(tiles < cap ? tiles : cap), dim3(256), smem, (hipStream_t)stream, a);
+  MlpGiBwdArgs a{dgi, M, Wi, W2, W1, g2, g1, p2, y2, st2, p1, y1, st1, relu_mask, ldm, dpre2, dpre1, dx, lddx, dg2, db2, dg1, db1,
+                 nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr};
+  constexpr size_t smem = mlp_gi_bwd_smem<false>();
+  const int cap = mlp_gi_bwd_cap<false>(smem);
+  const int tiles = (M + 16 * FZ_BWD_RT - 1) / (16 * FZ_BWD_RT);
+  hipLaunchKernelGGL(mlp_gi_bwd_kernel<false>, dim3(tiles < cap ? tiles : cap), dim3(256), smem, (hipStream_t)stream, a);
   DGPPO_LAUNCH_CHECK();
   return 0;
+}
+
+// ---- the same chain with the trunk's weight gradients (mlp_gi_bwd_kernel<true>) ----------------------------------------------
+// One slab per workgroup.  The grid is the device's capacity (2 workgroups per CU) as long as every workgroup walks at least
+// TW_MIN_TILES tiles: below that the slab a workgroup writes (33 KB) outweighs the rows it reads (7.4 KB per tile), so fewer
+// workgroups walk more tiles (16 384 rows with the batched reduce: 44 us at 1 or 2 tiles, 39 at 4, 51 at 8); at <= 4 workgroups
+// the sums go straight into the outputs with atomicAdd, as in dense_bwd_w.
+extern "C" int64_t dgppo_mlp_gi_bwd_w_workspace_bytes(void) {
+  return (int64_t)TW_SLAB * sizeof(float) * mlp_gi_bwd_cap<true>(mlp_gi_bwd_smem<true>());
+}
+
+extern "C" int32_t dgppo_mlp_gi_bwd_w(const float* dgi, const float* Wi, const float* W2, const float* W1, const float* g2,
+                                      const float* g1, const float* p2, const float* y2, const float* st2, const float* p1,
+                                      const float* y1, const float* st1, const float* x, int32_t ldx, const float* relu_mask,
+                                      int32_t ldm, float* dpre2, float* dpre1, float* dx, int32_t lddx, float* dg2, float* db2,
+                                      float* dg1, float* db1, float* dW2, int32_t ldw2, float* dbias2, float* dW1, int32_t ldw1,
+                                      float* dbias1, int32_t M, float* workspace, int64_t workspace_bytes,
+                                      dgppo_reduce_desc* pending, void* stream) {
+  DGPPO_REQUIRE(M >= 0 && lddx >= FZ_H && ldx >= FZ_H && (relu_mask == nullptr || ldm >= FZ_H) && ldw2 >= FZ_H && ldw1 >= FZ_H,
+                "mlp_gi_bwd_w: bad shape M=%d lddx=%d ldx=%d ldm=%d ldw2=%d ldw1=%d", M, lddx, ldx, ldm, ldw2, ldw1);
+  DGPPO_REQUIRE(workspace_bytes >= 0 && (workspace != nullptr || workspace_bytes == 0), "mlp_gi_bwd_w: bad workspace");
+  DGPPO_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "mlp_gi_bwd_w: workspace must be 16-byte aligned");
+  if (pending) pending[0].pending = pending[1].pending = 0;
+  if (M == 0) return 0;                            // (the row operands of an empty call may be NULL)
+  DGPPO_REQUIRE(dgi && Wi && W2 && W1 && g2 && g1 && p2 && y2 && st2 && p1 && y1 && st1 && x && dx && dg2 && db2 && dg1 && db1 &&
+                dW2 && dbias2 && dW1 && dbias1, "mlp_gi_bwd_w: NULL operand");
+  DGPPO_REQUIRE((reinterpret_cast<uintptr_t>(dgi) & 15) == 0, "mlp_gi_bwd_w: dgi must be 16-byte aligned");
+  constexpr size_t smem = mlp_gi_bwd_smem<true>();
+  const int tiles = (M + 16 * FZ_BWD_RT - 1) / (16 * FZ_BWD_RT);
+  int grid = mlp_gi_bwd_cap<true>(smem);
+  if (grid > tiles / TW_MIN_TILES) grid = tiles / TW_MIN_TILES;
+  const long max_slabs = (long)(workspace_bytes / (sizeof(float) * TW_SLAB));
+  float* ws = (grid > 4 && max_slabs >= 8) ? workspace : nullptr;
+  if (ws && grid > max_slabs) grid = (int)max_slabs;
+  if (!ws) grid = tiles < 4 ? tiles : 4;
+  MlpGiBwdArgs a{dgi, M, Wi, W2, W1, g2, g1, p2, y2, st2, p1, y1, st1, relu_mask, ldm, dpre2, dpre1, dx, lddx, dg2, db2, dg1, db1,
+                 x, ldx, ws, dW2, ldw2, dbias2, dW1, ldw1, dbias1};
+  hipLaunchKernelGGL(mlp_gi_bwd_kernel<true>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  if (!ws) return 0;
+  dgppo_reduce_desc d[2];
+  d[0] = dgppo_reduce_desc{ws, dW2, dbias2, TW_SLAB, grid, ldw2, FZ_H, FZ_H, 1};
+  d[1] = dgppo_reduce_desc{ws + TW_HALF, dW1, dbias1, TW_SLAB, grid, ldw1, FZ_H, FZ_H, 1};
+  if (pending) {
+    pending[0] = d[0]; pending[1] = d[1];
+    return 0;
+  }
+  return dgppo_dense_bwd_w_reduce_batch(d, 2, stream);
 }
 
 extern "C" int32_t dgppo_mlp_gi_fwd(const float* X, int32_t ldx, const float* W1, const float* b1, const float* g1,
@@ -1054,4 +1213,295 @@ extern "C" int32_t dgppo_gru1_head_fwd(const float* gi, const float* Wh, const f
   else hipLaunchKernelGGL(gru1_head_fwd_kernel<false>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
   DGPPO_LAUNCH_CHECK();
   return 0;
+}
+
+// ---- backward of the output head in ONE pass over the rows ---------------------------------------------------------------------
+//   two layers (policy: u = feat Ws + bs, out = u Wms + bms, dgppo/algo/module/policy.py:62-74):
+//     dW2 += u^T dout, db2 += colsum dout, du = dout W2^T (never leaves the CU), dW1 += feat^T du, db1 += colsum du, dhs = du W1^T
+//   one layer (values: out = feat Wo + bo, dgppo/algo/module/value.py:41,76):
+//     dW1 += feat^T dout, db1 += colsum dout, dhs = dout W1^T
+// It replaces dense_bwd_w, dense_smallk, dense_bwd_w, dense_fwd (two layers) or dense_bwd_w, dense_smallk (one) and the round trip
+// of du.  One 8-wave workgroup per CU; every WAVE walks 16-row tiles of its own with a wave-private LDS image (feat | u | du rows),
+// so there is no workgroup barrier in the loop; the next tile's rows are requested while the current one computes.  n_out <= 16:
+// the narrow matrix is one zero-padded 16-wide column tile.  As in mlp_gi_bwd_kernel<true>, du in the C/D layout is the B operand
+// of dW1 with the contraction rows permuted; dW2 contracts in natural row order (dout read from global memory in either layout:
+// 16 x n_out floats per tile).  At the end the eight waves' accumulators meet in wave 0 through LDS (three halving rounds) and the
+// workgroup writes ONE partial slab [narrow dW | its bias | pad | dW1 64x64 | db1] for the common second stage.
+#define HB_HL 68                          // LDS row stride: 16-byte rows; A-fragment reads at most 2-way
+#define HB_WAVES 8
+#define HB_TILE (16 * HB_HL)
+#define HB_BIG 1088                       // offset of [dW1 | db1] in a two-layer slab (>= 64 * 16 + 16, a multiple of 64)
+#define HB_SLAB_ONE HB_BIG
+#define HB_SLAB_TWO (HB_BIG + FZ_H * FZ_H + FZ_H)
+struct HeadBwdArgs {
+  const float* feat; int ldf;
+  const float* u;                         // [M,64], two layers only
+  const float* dout; int n_out;           // [M,n_out]
+  const float *W1, *W2;                   // two layers: W1 [64,64], W2 [64,n_out]; one: W1 [64,n_out], W2 NULL
+  float* dhs;                             // [M,64]
+  float* dW1; int ldw1; float* db1;
+  float* dW2; int ldw2; float* db2;
+  float* part;                            // [grid][slab] or NULL: atomicAdd straight into the outputs
+  int M;
+};
+
+template <bool TWO>
+__global__ void __launch_bounds__(64 * HB_WAVES) head_bwd_kernel(HeadBwdArgs a) {
+  extern __shared__ float sm[];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lq = lane >> 4;
+  float* s_f = sm + w * 3 * HB_TILE;      // feat rows (zeros past M)
+  float* s_u = s_f + HB_TILE;             // u rows
+  float* s_du = s_u + HB_TILE;            // du rows
+  const int n_out = a.n_out, ks = (n_out + 3) >> 2;
+  const float* Wn = TWO ? a.W2 : a.W1;    // the narrow matrix [64, n_out]
+  // B operand of dout Wn^T: B[k][n] = Wn[n][k]; lane (li, lq) holds k = 4 kk + lq of output column 16 t + li (zero-padded)
+  float wn[4][4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const int k = kk * 4 + lq;
+      wn[t][kk] = k < n_out ? Wn[(t * 16 + li) * n_out + k] : 0.0f;
+    }
+  // W1 (two layers) sits in LDS once per workgroup: B operand of du W1^T, B[k][n] = W1[n][k] read as s_w1[n][k]
+  float* s_w1 = sm + HB_WAVES * 3 * HB_TILE;
+  if constexpr (TWO) {
+    for (int i = tid; i < FZ_H * FZ_H; i += 64 * HB_WAVES) s_w1[(i >> 6) * HB_HL + (i & 63)] = a.W1[i];   // (a parameter slice: any alignment)
+    __syncthreads();
+  }
+  f32x4 an[4];                            // narrow dW rows 16 kt + 4 lq + r, column li
+  f32x4 aw1[TWO ? 4 : 1][TWO ? 4 : 1];    // dW1 rows 16 kt + 4 lq + r, column 16 t + li
+  float cs_n = 0.0f, cs_u[4] = {0.f, 0.f, 0.f, 0.f};   // column sums: dout column li (over this lane's rows), du column 16 t + li
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt) an[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (TWO) {
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) aw1[kt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const int n_tiles = (a.M + 15) >> 4, stride = gridDim.x * HB_WAVES;
+  float4 pf[TWO ? 8 : 4];                 // the next tile's feat (and u) rows: 16 rows x 16 float4 each, 4 per lane
+  auto fetch = [&](int tile) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int idx = s * 64 + lane, r = idx >> 4, q = idx & 15;
+      int row = tile * 16 + r;
+      row = row < a.M ? row : a.M - 1;
+      pf[s] = *reinterpret_cast<const float4*>(a.feat + (size_t)row * a.ldf + 4 * q);
+      if constexpr (TWO) pf[4 + s] = *reinterpret_cast<const float4*>(a.u + (size_t)row * FZ_H + 4 * q);
+    }
+  };
+  auto commit = [&](int tile) {           // rows >= M become zeros
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int idx = s * 64 + lane, r = idx >> 4, q = idx & 15;
+      const float m = tile * 16 + r < a.M ? 1.0f : 0.0f;
+      auto pick = [&](const float4& v) { return make_float4(m != 0.f ? v.x : 0.f, m != 0.f ? v.y : 0.f, m != 0.f ? v.z : 0.f, m != 0.f ? v.w : 0.f); };
+      *reinterpret_cast<float4*>(s_f + r * HB_HL + 4 * q) = pick(pf[s]);
+      if constexpr (TWO) *reinterpret_cast<float4*>(s_u + r * HB_HL + 4 * q) = pick(pf[4 + s]);
+    }
+  };
+  int tile = blockIdx.x * HB_WAVES + w;
+  fetch(tile);                            // (rows are clamped: a fetch past the last tile reads row M - 1 and is never committed)
+  for (; tile < n_tiles; tile += stride) {
+    const int row0 = tile * 16;
+    commit(tile);
+    fetch(tile + stride);
+    // dout in both operand layouts, zero outside [M, n_out]
+    float a_d[4], b_d[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      const int ra = row0 + li, ka = kk * 4 + lq;              // A[row li][k = 4 kk + lq]
+      a_d[kk] = (ra < a.M && ka < n_out) ? a.dout[(size_t)ra * n_out + ka] : 0.0f;
+      const int rb = row0 + kk * 4 + lq;                         // B[k = row 4 kk + lq][column li]
+      b_d[kk] = (rb < a.M && li < n_out) ? a.dout[(size_t)rb * n_out + li] : 0.0f;
+      cs_n += b_d[kk];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // g = dout Wn^T [16, 64]: du (two layers) or dhs (one)
+    f32x4 g[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) g[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_d[0], wn[t][0], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    if (ks > 1) {                                                // wave-uniform: the k-steps beyond n_out are all zeros
+#pragma unroll
+      for (int kk = 1; kk < 4; ++kk)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) g[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a_d[kk], wn[t][kk], g[t], 0, 0, 0);
+    }
+    // narrow weight gradient: (u or feat)^T dout, contraction rows in natural order
+    const float* s_a = TWO ? s_u : s_f;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+        an[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(s_a[(s * 4 + lq) * HB_HL + kt * 16 + li], b_d[s], an[kt], 0, 0, 0);
+    if constexpr (TWO) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          s_du[(lq * 4 + r) * HB_HL + t * 16 + li] = g[t][r];
+          cs_u[t] += g[t][r];
+        }
+      // dW1 += feat^T du: step r contracts over rows {4 lq + r}, where this lane's du values are the B operand
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+          const float av = s_f[(lq * 4 + r) * HB_HL + kt * 16 + li];
+#pragma unroll
+          for (int t = 0; t < 4; ++t) aw1[kt][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, g[t][r], aw1[kt][t], 0, 0, 0);
+        }
+      // dhs = du W1^T: du as the A operand from the wave's own LDS rows (written above by this wave: no barrier)
+      float ad[16];
+#pragma unroll
+      for (int kk = 0; kk < 16; ++kk) ad[kk] = s_du[li * HB_HL + kk * 4 + lq];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        g[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < 16; ++kk)
+          g[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(ad[kk], s_w1[(t * 16 + li) * HB_HL + kk * 4 + lq], g[t], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = row0 + lq * 4 + r;
+        if (row < a.M) a.dhs[(size_t)row * FZ_H + t * 16 + li] = g[t][r];
+      }
+    // (the next commit overwrites s_f / s_u / s_du of THIS wave only, after its own reads above)
+  }
+  // ---- the eight waves' accumulators meet in wave 0: three halving rounds through lane-major LDS images (slot j of lane l at
+  // [j][l]: conflict-free, and the same lane of every wave holds the same element), then wave 0 writes the slab from registers
+  constexpr int NV = TWO ? 85 : 17;       // values per lane: narrow dW 16, (dW1 64,) dout column sum 1, (du column sums 4)
+  auto each = [&](auto&& f) {             // value = f(slot, value) over this lane's values, the same order in every wave
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) an[kt][r] = f(kt * 4 + r, an[kt][r]);
+    cs_n = f(16, cs_n);
+    if constexpr (TWO) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) cs_u[t] = f(17 + t, cs_u[t]);
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) aw1[kt][t][r] = f(21 + (kt * 4 + t) * 4 + r, aw1[kt][t][r]);
+    }
+  };
+  __syncthreads();                        // every wave is done with its tile images
+#pragma unroll
+  for (int half = HB_WAVES / 2; half >= 1; half >>= 1) {
+    if (w >= half && w < 2 * half) each([&](int j, float v) { sm[((w - half) * NV + j) * 64 + lane] = v; return v; });
+    __syncthreads();
+    if (w < half) each([&](int j, float v) { return v + sm[(w * NV + j) * 64 + lane]; });
+    __syncthreads();
+  }
+  if (w != 0) return;
+  // column sums: add the four row groups (lanes li, li + 16, li + 32, li + 48)
+  cs_n += __shfl_xor(cs_n, 16); cs_n += __shfl_xor(cs_n, 32);
+  if constexpr (TWO) {
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { cs_u[t] += __shfl_xor(cs_u[t], 16); cs_u[t] += __shfl_xor(cs_u[t], 32); }
+  }
+  constexpr int SLAB = TWO ? HB_SLAB_TWO : HB_SLAB_ONE;
+  const int nb = FZ_H * n_out;            // the narrow dW is dense [64, n_out] in the slab, its bias follows
+  float* slab = a.part ? a.part + (size_t)blockIdx.x * SLAB : nullptr;
+  float* dWn = TWO ? a.dW2 : a.dW1;
+  float* dbn = TWO ? a.db2 : a.db1;
+  const int ldn = TWO ? a.ldw2 : a.ldw1;
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int krow = kt * 16 + lq * 4 + r;
+      if (li < n_out) {
+        if (slab) slab[krow * n_out + li] = an[kt][r];
+        else atomicAdd(dWn + (size_t)krow * ldn + li, an[kt][r]);
+      }
+      if constexpr (TWO) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          if (slab) slab[HB_BIG + krow * FZ_H + t * 16 + li] = aw1[kt][t][r];
+          else atomicAdd(a.dW1 + (size_t)krow * a.ldw1 + t * 16 + li, aw1[kt][t][r]);
+        }
+      }
+    }
+  if (lq == 0) {
+    if (li < n_out) {
+      if (slab) slab[nb + li] = cs_n;
+      else atomicAdd(dbn + li, cs_n);
+    }
+    if constexpr (TWO) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        if (slab) slab[HB_BIG + FZ_H * FZ_H + t * 16 + li] = cs_u[t];
+        else atomicAdd(a.db1 + t * 16 + li, cs_u[t]);
+      }
+    }
+  }
+}
+
+static int head_bwd_cus() {
+  static thread_local int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  }
+  return cus;
+}
+
+extern "C" int64_t dgppo_head_bwd_workspace_bytes(void) { return (int64_t)HB_SLAB_TWO * sizeof(float) * head_bwd_cus(); }
+
+extern "C" int32_t dgppo_head_bwd(const float* feat, int32_t ldf, const float* u, const float* dout, const float* W1,
+                                  const float* W2, float* dhs, float* dW1, int32_t ldw1, float* db1, float* dW2, int32_t ldw2,
+                                  float* db2, int32_t M, int32_t n_out, float* workspace, int64_t workspace_bytes,
+                                  dgppo_reduce_desc* pending, void* stream) {
+  const bool two = W2 != nullptr;
+  DGPPO_REQUIRE(M >= 0 && n_out >= 1 && n_out <= 16 && ldf >= FZ_H && ldw1 >= (two ? FZ_H : n_out) && (!two || ldw2 >= n_out),
+                "head_bwd: bad shape M=%d n_out=%d ldf=%d ldw1=%d ldw2=%d", M, n_out, ldf, ldw1, ldw2);
+  DGPPO_REQUIRE(workspace_bytes >= 0 && (workspace != nullptr || workspace_bytes == 0), "head_bwd: bad workspace");
+  DGPPO_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "head_bwd: workspace must be 16-byte aligned");
+  if (pending) pending[0].pending = pending[1].pending = 0;
+  if (M == 0) return 0;                            // (the row operands of an empty call may be NULL)
+  DGPPO_REQUIRE(feat && dout && W1 && dhs && dW1 && db1 && (!two || (u && dW2 && db2)), "head_bwd: NULL operand");
+  DGPPO_REQUIRE((ldf & 3) == 0 && ((reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(u) |
+                 reinterpret_cast<uintptr_t>(dout) | reinterpret_cast<uintptr_t>(dhs)) & 15) == 0,
+                "head_bwd: feat, u, dout, dhs must be 16-byte aligned, the leading dimension of feat a multiple of 4");
+  const int slab = two ? HB_SLAB_TWO : HB_SLAB_ONE;
+  constexpr size_t smem = sizeof(float) * (HB_WAVES * 3 * HB_TILE + FZ_H * HB_HL);
+  static_assert(sizeof(float) * HB_WAVES * 3 * HB_TILE >= sizeof(float) * (HB_WAVES / 2) * 85 * 64 && smem <= 160 * 1024, "head_bwd: LDS image");
+  static thread_local bool opted = false;
+  if (!opted) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&head_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&head_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    opted = true;
+  }
+  // one workgroup per CU, a tile per wave and round; <= 4 workgroups (or no room for 8 slabs) add atomically, as dense_bwd_w
+  const int tiles = (M + 15) / 16;
+  int grid = (tiles + HB_WAVES - 1) / HB_WAVES;
+  if (grid > head_bwd_cus()) grid = head_bwd_cus();
+  const long max_slabs = (long)(workspace_bytes / (sizeof(float) * slab));
+  float* ws = (grid > 4 && max_slabs >= 8) ? workspace : nullptr;
+  if (ws && grid > max_slabs) grid = (int)max_slabs;
+  HeadBwdArgs a{feat, ldf, u, dout, n_out, W1, W2, dhs, dW1, ldw1, db1, dW2, ldw2, db2, ws, M};
+  if (two) hipLaunchKernelGGL(head_bwd_kernel<true>, dim3(grid), dim3(64 * HB_WAVES), smem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(head_bwd_kernel<false>, dim3(grid), dim3(64 * HB_WAVES), smem, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  if (!ws) return 0;
+  dgppo_reduce_desc d[2];
+  d[0] = dgppo_reduce_desc{ws, two ? dW2 : dW1, two ? db2 : db1, slab, grid, two ? ldw2 : ldw1, FZ_H, n_out, 1};
+  d[1] = dgppo_reduce_desc{ws + HB_BIG, dW1, db1, slab, grid, ldw1, FZ_H, FZ_H, two ? 1 : 0};
+  if (pending) {
+    pending[0] = d[0];
+    if (two) pending[1] = d[1];
+    return 0;
+  }
+  return dgppo_dense_bwd_w_reduce_batch(d, two ? 2 : 1, stream);
 }

@@ -472,7 +472,14 @@ class Net:
         fused_trunk = self.rnn == "gru" and self.rnn_layers == 1 and self.kind != "Vhg" and dout.is_cuda
         dgi0 = None
         dhs = A.get(f"{tag}.dhs", Rh, HID)
-        if self.kind == "policy":
+        if dout.is_cuda:
+            # the head's backward in ONE pass over the rows (dgppo_head_bwd): du never leaves the CU
+            if self.kind == "policy":
+                K.head_bwd(feat, act["u"], dout, self.p("head.Ws"), self.p("head.Wms"), dhs, self.g("head.Ws"), self.g("head.bs"),
+                           self.g("head.Wms"), self.g("head.bms"))
+            else:
+                K.head_bwd(feat, None, dout, self.p("head.Wo"), None, dhs, self.g("head.Wo"), self.g("head.bo"))
+        elif self.kind == "policy":
             K.dense_bwd_w(act["u"], dout, self.g("head.Wms"), self.g("head.bms"))
             du = A.get(f"{tag}.du", Rh, HID)
             K.dense_fwd(dout, self.p("head.Wms"), None, du, trans_w=True)
@@ -532,16 +539,14 @@ class Net:
         x_in = {1: act["mlp_in"], 2: act["y1"]}
         top = act[f"Xa{self.gnn_layers}"]          # output of the last GNN layer (a ReLU output): masks the gradient entering it
         if fused_trunk:
-            # dgi -> (Wi^T) -> LN+ReLU' -> (W2^T) -> LN+ReLU' -> (W1^T) -> dx in ONE launch (dgppo_mlp_gi_bwd): five launches and two
-            # [Rh, 64] round trips through HBM less per network; the two weight gradients read the dpre buffers it writes
-            dpre2, dpre1 = A.get(f"{tag}.dpre2", Rh, HID), A.get(f"{tag}.dpre1", Rh, HID)
+            # dgi -> (Wi^T) -> LN+ReLU' -> (W2^T) -> LN+ReLU' -> (W1^T) -> dx in ONE launch (dgppo_mlp_gi_bwd_w), which also forms the
+            # two weight gradients dW2 = y1^T dpre2, dW1 = x^T dpre1 from the tiles it holds: dpre2 / dpre1 never reach HBM
             dy = A.get(f"{tag}.dyy1", Rh, HID)
-            K.mlp_gi_bwd(dgi0, self.p("gru.Wi"), self.p("mlp.W2"), self.p("mlp.W1"), self.p("mlp.g2"), self.p("mlp.g1"),
-                         act["p2"], act["y2"], act["st2"], act["p1"], act["y1"], act["st1"],
-                         top if self.kind in ("policy", "Vh") else None, dpre2, dpre1, dy,
-                         self.g("mlp.g2"), self.g("mlp.be2"), self.g("mlp.g1"), self.g("mlp.be1"))
-            K.dense_bwd_w(x_in[2], dpre2, self.g("mlp.W2"), self.g("mlp.b2"))
-            K.dense_bwd_w(x_in[1], dpre1, self.g("mlp.W1"), self.g("mlp.b1"))
+            K.mlp_gi_bwd_w(dgi0, self.p("gru.Wi"), self.p("mlp.W2"), self.p("mlp.W1"), self.p("mlp.g2"), self.p("mlp.g1"),
+                           act["p2"], act["y2"], act["st2"], act["p1"], act["y1"], act["st1"], x_in[1],
+                           top if self.kind in ("policy", "Vh") else None, dy,
+                           self.g("mlp.g2"), self.g("mlp.be2"), self.g("mlp.g1"), self.g("mlp.be1"),
+                           self.g("mlp.W2"), self.g("mlp.b2"), self.g("mlp.W1"), self.g("mlp.b1"))
         for i in (() if fused_trunk else (2, 1)):
             dpre = A.get(f"{tag}.dpre{i}", Rh, HID)
             K.ln_relu_bwd(act[f"p{i}"], act[f"y{i}"], act[f"st{i}"], self.p(f"mlp.g{i}"), dy, dpre, self.g(f"mlp.g{i}"),

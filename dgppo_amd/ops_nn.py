@@ -651,6 +651,114 @@ def gru_bwd_w(x, hprev, dgi, dhn, dWi, dbi, dWh, dbhn):
                 batch.descs.append(ReduceDesc.from_buffer_copy(d[i]))
 
 
+_WS_BYTES: dict = {}   # (query name, device index) -> bytes: constant per device, asked once
+
+
+def _workspace_bytes(query: str, device) -> int:
+    key = (query, device.index)
+    if key not in _WS_BYTES:
+        fn = getattr(N.lib(), query)
+        fn.restype = C.c_int64
+        _WS_BYTES[key] = int(fn())
+    return _WS_BYTES[key]
+
+
+def mlp_gi_bwd_w(dgi, Wi, W2, W1, g2, g1, p2, y2, st2, p1, y1, st1, x, relu_mask, dx, dg2, db2, dg1, db1, dW2, dbias2, dW1,
+                 dbias1, dpre2=None, dpre1=None):
+    """mlp_gi_bwd and the trunk's weight gradients in one kernel (dgppo_mlp_gi_bwd_w): dW2 += y1.T @ dpre2, dbias2 += dpre2.sum(0),
+    dW1 += x.T @ dpre1, dbias1 += dpre1.sum(0); x [M,64] is the chain's input (a row-strided view, or the relu_mask tensor).
+    dpre2 / dpre1 are written only where given.  Inside `with BwdWBatch(...)` the slab reductions are deferred to its flush."""
+    M = dgi.shape[0]
+    N.expect_shape(dgi, (M, 192), "dgi")
+    for t, shp, nm in ((Wi, (64, 192), "Wi"), (W2, (64, 64), "W2"), (W1, (64, 64), "W1"), (g2, (64,), "g2"), (g1, (64,), "g1"),
+                       (p2, (M, 64), "p2"), (y2, (M, 64), "y2"), (st2, (M, 2), "st2"), (p1, (M, 64), "p1"), (y1, (M, 64), "y1"),
+                       (st1, (M, 2), "st1"), (dx, (M, 64), "dx"), (dg2, (64,), "dg2"), (db2, (64,), "db2"), (dg1, (64,), "dg1"),
+                       (db1, (64,), "db1"), (dbias2, (64,), "dbias2"), (dbias1, (64,), "dbias1")):
+        N.expect_shape(t, shp, nm)
+    for t, nm in ((dpre2, "dpre2"), (dpre1, "dpre1")):
+        if t is not None:
+            N.expect_shape(t, (M, 64), nm)
+    xp, ldx, Mx, Kx = _mat(x, "x")
+    w2p, ldw2, _, _ = _mat(dW2, "dW2")
+    w1p, ldw1, _, _ = _mat(dW1, "dW1")
+    if (Mx, Kx) != (M, 64) or tuple(dW2.shape) != (64, 64) or tuple(dW1.shape) != (64, 64):
+        raise ValueError(f"mlp_gi_bwd_w: shape mismatch x{tuple(x.shape)} dW2{tuple(dW2.shape)} dW1{tuple(dW1.shape)}")
+    mp, ldm = C.c_void_p(0), 0
+    if relu_mask is not None:
+        mp, ldm, Mm, Km = _mat(relu_mask, "relu_mask")
+        if (Mm, Km) != (M, 64):
+            raise ValueError(f"mlp_gi_bwd_w: relu_mask must be [M, 64], got {tuple(relu_mask.shape)}")
+    FLOPS[0] += 2.0 * M * (64 * 64 * 2 + 64 * 192) + 2 * 2.0 * M * 64 * 64      # the chain + the two dense_bwd_w calls it replaces
+    lib = N.lib()
+    need = _workspace_bytes("dgppo_mlp_gi_bwd_w_workspace_bytes", dgi.device)
+    batch = BwdWBatch._active.get((dgi.device.index, torch.cuda.current_stream(dgi.device).cuda_stream))
+    d = (ReduceDesc * 2)()
+    if batch is not None:
+        ws = batch.region(need)
+    else:
+        key = (dgi.device.index, torch.cuda.current_stream(dgi.device).cuda_stream, "trunk")
+        ws = _WS.get(key)
+        if ws is None or ws.numel() * 4 < need:
+            ws = _WS[key] = torch.empty(need // 4, dtype=torch.float32, device=dgi.device)
+    rc = lib.dgppo_mlp_gi_bwd_w(_p(dgi), _p(Wi), _p(W2), _p(W1), _p(g2), _p(g1), _p(p2), _p(y2), _p(st2), _p(p1), _p(y1), _p(st1),
+                                xp, ldx, mp, ldm, _p(dpre2), _p(dpre1), _p(dx), 64, _p(dg2), _p(db2), _p(dg1), _p(db1),
+                                w2p, ldw2, _p(dbias2), w1p, ldw1, _p(dbias1), M, _p(ws, "workspace"), C.c_int64(ws.numel() * 4),
+                                d if batch is not None else None, N.stream_ptr())
+    N.check(rc, "dgppo_mlp_gi_bwd_w")
+    if batch is not None:
+        for i in range(2):
+            if d[i].pending:
+                batch.descs.append(ReduceDesc.from_buffer_copy(d[i]))
+
+
+def head_bwd(feat, u, dout, W1, W2, dhs, dW1, db1, dW2=None, db2=None):
+    """backward of the output head in one kernel (dgppo_head_bwd).  Two layers (policy; u, W2, dW2, db2 given): dW2 += u.T @ dout,
+    db2 += dout.sum(0), du = dout @ W2.T, dW1 += feat.T @ du, db1 += du.sum(0), dhs = du @ W1.T.  One layer (values):
+    dW1 += feat.T @ dout, db1 += dout.sum(0), dhs = dout @ W1.T.  feat may be a row-strided view.  Inside `with BwdWBatch(...)`
+    the slab reductions are deferred to its flush."""
+    fp, ldf, M, Kf = _mat(feat, "feat")
+    n_out = int(dout.shape[1]) if dout.dim() == 2 else -1
+    two = W2 is not None
+    if Kf != 64 or not 1 <= n_out <= 16:
+        raise ValueError(f"head_bwd: feat must be [M, 64] and dout [M, n_out <= 16], got {tuple(feat.shape)} {tuple(dout.shape)}")
+    N.expect_shape(dout, (M, n_out), "dout"); N.expect_shape(dhs, (M, 64), "dhs")
+    if two:
+        N.expect_shape(u, (M, 64), "u"); N.expect_shape(W1, (64, 64), "W1"); N.expect_shape(W2, (64, n_out), "W2")
+        N.expect_shape(db1, (64,), "db1"); N.expect_shape(db2, (n_out,), "db2")
+        if tuple(dW1.shape) != (64, 64) or tuple(dW2.shape) != (64, n_out):
+            raise ValueError(f"head_bwd: shape mismatch dW1{tuple(dW1.shape)} dW2{tuple(dW2.shape)}")
+        w2p, ldw2, _, _ = _mat(dW2, "dW2")
+        FLOPS[0] += 2.0 * M * (2 * 64 * n_out + 2 * 64 * 64)       # the four launches it replaces
+    else:
+        if u is not None or dW2 is not None or db2 is not None:
+            raise ValueError("head_bwd: u, dW2, db2 belong to the two-layer form (W2 given)")
+        N.expect_shape(W1, (64, n_out), "W1"); N.expect_shape(db1, (n_out,), "db1")
+        if tuple(dW1.shape) != (64, n_out):
+            raise ValueError(f"head_bwd: shape mismatch dW1{tuple(dW1.shape)}")
+        w2p, ldw2 = C.c_void_p(0), 0
+        FLOPS[0] += 2.0 * M * 2 * 64 * n_out
+    w1p, ldw1, _, _ = _mat(dW1, "dW1")
+    lib = N.lib()
+    need = _workspace_bytes("dgppo_head_bwd_workspace_bytes", feat.device)
+    batch = BwdWBatch._active.get((feat.device.index, torch.cuda.current_stream(feat.device).cuda_stream))
+    d = (ReduceDesc * 2)()
+    if batch is not None:
+        ws = batch.region(need)
+    else:
+        key = (feat.device.index, torch.cuda.current_stream(feat.device).cuda_stream, "head")
+        ws = _WS.get(key)
+        if ws is None or ws.numel() * 4 < need:
+            ws = _WS[key] = torch.empty(need // 4, dtype=torch.float32, device=feat.device)
+    rc = lib.dgppo_head_bwd(fp, ldf, _p(u, "u"), _p(dout, "dout"), _p(W1, "W1"), _p(W2, "W2"), _p(dhs, "dhs"), w1p, ldw1,
+                            _p(db1, "db1"), w2p, ldw2, _p(db2, "db2"), M, n_out, _p(ws, "workspace"), C.c_int64(ws.numel() * 4),
+                            d if batch is not None else None, N.stream_ptr())
+    N.check(rc, "dgppo_head_bwd")
+    if batch is not None:
+        for i in range(2):
+            if d[i].pending:
+                batch.descs.append(ReduceDesc.from_buffer_copy(d[i]))
+
+
 def policy_head(ms, eps, action_in, action, log_pi, entropy, n_agents, mode, log_pi_old=None, adv=None, dms=None,
                 stats=None, clip_eps=0.25, coef_ent=0.01):
     rows = ms.shape[0]

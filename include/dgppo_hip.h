@@ -274,6 +274,36 @@ int32_t dgppo_dense_bwd_w_deferred(const float* X, int32_t ldx, const float* dY,
                                    float* db, int32_t M, int32_t K, int32_t N, float* workspace, int64_t workspace_bytes,
                                    dgppo_reduce_desc* pending, void* stream);
 int32_t dgppo_dense_bwd_w_reduce_batch(const dgppo_reduce_desc* descs, int32_t n, void* stream);
+/* dgppo_mlp_gi_bwd together with the weight gradients of the chain's two Dense layers, from the same pass over the rows:
+ * dW2 [64, ldw2] += y1^T dpre2, dbias2 [64] += colsum(dpre2), dW1 [64, ldw1] += x^T dpre1, dbias1 [64] += colsum(dpre1), where
+ * x [M, ldx] is the chain's input (it may be the relu_mask tensor itself).  dpre2 / dpre1 may be NULL: then they never leave
+ * the CU.  dx (and dpre* where given) are bit for bit those of dgppo_mlp_gi_bwd; dg* / db* are the same sums, but both
+ * entry points add per-workgroup partial sums with atomicAdd in arrival order, and this one may split the rows over fewer
+ * workgroups, so they agree only to the rounding of a reordered fp32 sum.  Rows >= M of a ragged tile contribute exactly
+ * zero.  workspace: dgppo_mlp_gi_bwd_w_workspace_bytes() bytes for one partial slab [dW2 | dbias2 | dW1 | dbias1] per
+ * workgroup; a smaller one shrinks the grid, and one with room for fewer than 8 slabs (or NULL) makes the call add atomically
+ * from at most 4 workgroups whatever M is: correct, but slow at many rows.  Few rows always add atomically.
+ * pending == NULL: the slabs are reduced at once.  Otherwise pending[0..1] receive the two owed reductions (pending = 0 where
+ * none is owed) for dgppo_dense_bwd_w_reduce_batch, under the rules of dgppo_dense_bwd_w_deferred.  M == 0 touches nothing. */
+int64_t dgppo_mlp_gi_bwd_w_workspace_bytes(void);
+int32_t dgppo_mlp_gi_bwd_w(const float* dgi, const float* Wi, const float* W2, const float* W1, const float* g2,
+                           const float* g1, const float* p2, const float* y2, const float* st2, const float* p1,
+                           const float* y1, const float* st1, const float* x, int32_t ldx, const float* relu_mask,
+                           int32_t ldm, float* dpre2, float* dpre1, float* dx, int32_t lddx, float* dg2, float* db2,
+                           float* dg1, float* db1, float* dW2, int32_t ldw2, float* dbias2, float* dW1, int32_t ldw1,
+                           float* dbias1, int32_t M, float* workspace, int64_t workspace_bytes, dgppo_reduce_desc* pending,
+                           void* stream);
+/* Backward of the output head in one pass over the rows (jax.grad through PolicyNet.head Dense -> TanhNormal Dense,
+ * dgppo/algo/module/policy.py:62-74, or the value Dense, dgppo/algo/module/value.py:41,76).  Two layers (W2 != NULL; the shapes
+ * of dgppo_gru1_head_fwd: W1 [64,64], W2 [64,n_out]): dW2 [64, ldw2] += u^T dout, db2 [n_out] += colsum(dout), du = dout W2^T
+ * (kept on the CU), dW1 [64, ldw1] += feat^T du, db1 [64] += colsum(du), dhs [M,64] = du W1^T.  One layer (W2 = u = dW2 = db2 =
+ * NULL, W1 [64,n_out]): dW1 [64, ldw1] += feat^T dout, db1 [n_out] += colsum(dout), dhs = dout W1^T.  feat [M, ldf >= 64],
+ * u [M,64], dout [M,n_out], n_out <= 16; feat, u, dout, dhs 16-byte aligned and ldf a multiple of 4, else the call is refused.
+ * workspace / pending: as dgppo_mlp_gi_bwd_w (dgppo_head_bwd_workspace_bytes(); pending[0..1], the second only for two layers). */
+int64_t dgppo_head_bwd_workspace_bytes(void);
+int32_t dgppo_head_bwd(const float* feat, int32_t ldf, const float* u, const float* dout, const float* W1, const float* W2,
+                       float* dhs, float* dW1, int32_t ldw1, float* db1, float* dW2, int32_t ldw2, float* db2, int32_t M,
+                       int32_t n_out, float* workspace, int64_t workspace_bytes, dgppo_reduce_desc* pending, void* stream);
 /* One GRU step (T = 1) fused with the output Dense layer(s) on the same rows — the tail of a rollout step:
  * h' = GRUCell(gi, h0) (dgppo/nn/rnn.py:14-30, gi = x W_i + b_i from dgppo_mlp_gi_fwd), then either the policy head
  * u = h' W1 + b1 [64], out = u W2 + b2 (PolicyNet.head Dense -> TanhNormal Dense, dgppo/algo/module/policy.py:62-74; pass

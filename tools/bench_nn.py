@@ -136,6 +136,64 @@ if which in ("all", "fusedbwd"):
             K.ln_relu_bwd(A[0], A[1], A[2], P[4], dy, o[1], pg[2], pg[3])
             K.dense_fwd(o[1], P[2], None, o[2], trans_w=True, relu_mask=mask)
         timeit(f"mlp bwd chain unfused (5 launches) M={M}", unfused)
+if which in ("all", "trunkw"):
+    # the trunk backward with its two weight gradients: mlp_gi_bwd + 2 x dense_bwd_w (dpre2 / dpre1 through HBM) against the one
+    # mlp_gi_bwd_w launch; either way inside a BwdWBatch, so the time includes one batched slab-reduce launch.  Three repeats,
+    # alternating; `vl` is the pooled-rows form (separate x, no mask)
+    for M, vl in ((131072, False), (16384, True), (16384, False)):
+        P = [torch.randn(*s_, device=dev) * 0.1 for s_ in ((64, 192), (64, 64), (64, 64), (64,), (64,))]
+        dgi = torch.randn(M, 192, device=dev)
+        A = [torch.randn(M, w, device=dev) for w in (64, 64, 2, 64, 64, 2)]
+        x = torch.randn(M, 64, device=dev)
+        mask = None if vl else x
+        o = [torch.empty(M, 64, device=dev) for _ in range(3)]
+        pg = [torch.zeros(64, device=dev) for _ in range(4)]
+        dW = [torch.zeros(64, 64, device=dev), torch.zeros(64, device=dev), torch.zeros(64, 64, device=dev), torch.zeros(64, device=dev)]
+        wsbuf = torch.empty(16 << 20, device=dev)
+
+        def parent():
+            with K.BwdWBatch(dev, lambda n: wsbuf):
+                K.mlp_gi_bwd(dgi, P[0], P[1], P[2], P[3], P[4], A[3], A[4], A[5], A[0], A[1], A[2], mask, o[0], o[1], o[2], *pg)
+                K.dense_bwd_w(A[1], o[0], dW[0], dW[1])
+                K.dense_bwd_w(x, o[1], dW[2], dW[3])
+
+        def fused():
+            with K.BwdWBatch(dev, lambda n: wsbuf):
+                K.mlp_gi_bwd_w(dgi, P[0], P[1], P[2], P[3], P[4], A[3], A[4], A[5], A[0], A[1], A[2], x, mask, o[2], *pg, *dW)
+        for rep in range(3):
+            timeit(f"trunk bwd: mlp_gi_bwd + 2 dense_bwd_w M={M} vl={int(vl)}", parent, iters=50)
+            timeit(f"trunk bwd: mlp_gi_bwd_w M={M} vl={int(vl)}", fused, iters=50)
+if which in ("all", "headb"):
+    # the head backward: dense_bwd_w, dense_fwd^T, dense_bwd_w, dense_fwd^T (policy, n_out = 4) or the first two (values,
+    # n_out = 1 / 2) against the one head_bwd launch; inside a BwdWBatch as above.  Three repeats, alternating
+    for M, n_out, two in ((131072, 4, True), (131072, 2, False), (16384, 4, True), (16384, 1, False)):
+        feat = torch.randn(M, 64, device=dev); u = torch.randn(M, 64, device=dev); dout = torch.randn(M, n_out, device=dev)
+        W1 = torch.randn(64, 64 if two else n_out, device=dev) * 0.1; W2 = torch.randn(64, n_out, device=dev) * 0.1
+        dW1 = torch.zeros_like(W1); db1 = torch.zeros(W1.shape[1], device=dev)
+        dW2 = torch.zeros_like(W2); db2 = torch.zeros(n_out, device=dev)
+        du = torch.empty(M, 64, device=dev); dhs = torch.empty(M, 64, device=dev)
+        wsbuf = torch.empty(16 << 20, device=dev)
+
+        def parent():
+            with K.BwdWBatch(dev, lambda n: wsbuf):
+                if two:
+                    K.dense_bwd_w(u, dout, dW2, db2)
+                    K.dense_fwd(dout, W2, None, du, trans_w=True)
+                    K.dense_bwd_w(feat, du, dW1, db1)
+                    K.dense_fwd(du, W1, None, dhs, trans_w=True)
+                else:
+                    K.dense_bwd_w(feat, dout, dW1, db1)
+                    K.dense_fwd(dout, W1, None, dhs, trans_w=True)
+
+        def fused():
+            with K.BwdWBatch(dev, lambda n: wsbuf):
+                if two:
+                    K.head_bwd(feat, u, dout, W1, W2, dhs, dW1, db1, dW2, db2)
+                else:
+                    K.head_bwd(feat, None, dout, W1, None, dhs, dW1, db1)
+        for rep in range(3):
+            timeit(f"head bwd: {4 if two else 2} launches M={M} n_out={n_out}", parent, iters=50, bytes_=4.0 * M * (196 if two else 129))
+            timeit(f"head bwd: head_bwd M={M} n_out={n_out}", fused, iters=50, bytes_=4.0 * M * (196 if two else 129))
 if which in ("all", "tail"):
     for M, two, train in ((32768, True, False), (131072, False, True), (524288, False, False)):
         gi = torch.randn(M, 192, device=dev); h0 = torch.randn(M, 64, device=dev)
