@@ -16,14 +16,16 @@ static int32_t attn_check(const dgppo_env_cfg* cfg, int F, int H, int Kp, int G,
 // The attention kernel families, chosen by shape alone; the first one whose conditions hold runs:
 //   SLOT8  F = 8, H = 3, n <= 32, S <= 64 (attn_slot8_shape); the backward writes no input gradient (first layer only)
 //   BD     F = 32 block-diagonal topologies (attn_bd_shape)
-//   MFMA   one workgroup per graph on the matrix cores: F % 4 == 0, S <= 64, LDS image <= 64 KB; backward for F >= 16 only
+//   MFMA   one workgroup per graph on the matrix cores: F % 4 == 0, Kp % 4 == 0, S <= 64, LDS image <= 64 KB; backward for
+//          F >= 16 only
 //   VALU   one workgroup per graph, every other shape (and the narrow backward, where it beats MFMA: measured)
 // Before any of them:
 //   TILED  one workgroup per graph, receivers in tiles: every shape whose whole-graph image (attn_image_bytes, the VALU family's)
 //          exceeds 64 KB, i.e. teams above ~17-35 agents depending on the kind (such calls were refused before this family
 //          existed, so every other shape keeps its family); forward and backward cross that line at different n, the attn /
 //          zcat layouts are the contract between the families
-// The one-wave families (SLOT8, BD) store zcat rows in 16-byte pieces, hence Kp % 4 == 0.
+// SLOT8, BD and MFMA move zcat / dzcat rows in 16-byte pieces, hence Kp % 4 == 0: any other width takes the VALU (or TILED)
+// kernels, which address single floats.
 enum class AttnFamily { SLOT8, BD, MFMA, VALU, TILED };
 size_t attn_image_bytes(const Topo& t, int F, int H, bool bwd) {
   if (bwd)
@@ -37,7 +39,7 @@ static AttnFamily attn_family(const Topo& t, int F, int H, int Kp, bool bwd, boo
   if (attn_image_bytes(t, F, H, bwd) > 64 * 1024) return AttnFamily::TILED;
   if ((Kp & 3) == 0 && attn_slot8_shape(t, F, H) && !(bwd && dXa)) return AttnFamily::SLOT8;
   if ((Kp & 3) == 0 && attn_bd_shape(t, F, H, PS, hits)) return AttnFamily::BD;
-  if ((F & 3) == 0 && t.S <= 64 && attn_mfma_smem(t, F, H, bwd) <= 64 * 1024 && (!bwd || F >= 16)) return AttnFamily::MFMA;
+  if ((F & 3) == 0 && (Kp & 3) == 0 && t.S <= 64 && attn_mfma_smem(t, F, H, bwd) <= 64 * 1024 && (!bwd || F >= 16)) return AttnFamily::MFMA;
   return AttnFamily::VALU;
 }
 

@@ -373,7 +373,11 @@ int32_t dgppo_cost_sweep(const dgppo_env_cfg* cfg, const float* agent, int64_t a
  * qt [G*n,H*F] = x_i Mcat + cvec (a Dense), logits = qt . x_sender, masked softmax over the S slots of each agent,
  * zcat [G*n,Kp] = [x_i | per head: sum a x_s (F), sum a e (4) | 1 | 0...], attn [G*n,S,H] saved for backward (NULL in
  * inference: the weights are not written).  Any team size dgppo_validate_cfg admits (n <= 64): graphs whose whole image
- * does not fit 64 KB of LDS are walked in receiver tiles (F % 4 == 0, 8 <= F <= 64 there).  Bit-reproducible run to run.  */
+ * does not fit 64 KB of LDS are walked in receiver tiles (F % 4 == 0, 8 <= F <= 64 there).  Bit-reproducible run to run.
+ * An agent without any unmasked slot receives nothing (aggr = 0, gnn.py:109-111): its attention weights are 0, its aggregates
+ * are 0 and its constant column is 0 instead of 1, so that the value bias does not reach it either.  In topologies with goal
+ * slots the caller must leave at least the goal slots of every agent unmasked (the environments never mask them): the
+ * constant column is then written as 1 without looking at the masks.                                                      */
 int32_t dgppo_attn_fwd(const dgppo_env_cfg* cfg, int32_t F, int32_t H, int32_t Kp, const float* qt, const float* Xa,
                        const float* Xo, const float* efeat, const float* emask, float* zcat, float* attn, int32_t G,
                        void* stream);

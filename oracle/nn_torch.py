@@ -403,8 +403,10 @@ def attn_sender_nodes(n: int, n_goals: int, goal_slots: int, obs_slots: int, lid
 def attn_fixed_fan_in(senders: Tensor, qt: Tensor, Xa: Tensor, Xo: Optional[Tensor], efeat: Tensor, emask: Tensor,
                       Kp: int) -> Tuple[Tensor, Tensor]:
     """qt [G, n, H, F], Xa [G, n, F], Xo [G, Ns - n, F] or None, efeat [G, n, S, 4], emask [G, n, S] ->
-    zcat [G, n, Kp] = [x_i | per head: sum_s a x_s (F), sum_s a e_s (4) | 1 | 0-pad], attn [G, n, S, H].
-    a = softmax over the unmasked slots of qt_h . x_s (0 on masked slots); masked edge features (NaN allowed) never enter."""
+    zcat [G, n, Kp] = [x_i | per head: sum_s a x_s (F), sum_s a e_s (4) | c | 0-pad], attn [G, n, S, H].
+    a = softmax over the unmasked slots of qt_h . x_s (0 on masked slots); masked edge features (NaN allowed) never enter.
+    c carries the value bias, sum_s a b_v: 1 for an agent with an unmasked slot, 0 for an agent without any (no incoming edge,
+    aggr = 0 in gnn.py:109-111: attention 0, aggregate 0 and no bias either)."""
     G, n, H, Fw = qt.shape
     X = Xa if Xo is None else torch.cat([Xa, Xo], 1)
     xs = X[:, senders]                                                       # [G, n, S, F]
@@ -417,5 +419,5 @@ def attn_fixed_fan_in(senders: Tensor, qt: Tensor, Xa: Tensor, Xo: Optional[Tens
     e = torch.where(m, efeat, 0.0)
     agg = torch.cat([torch.einsum("gish,gisf->gihf", a, xs), torch.einsum("gish,gisc->gihc", a, e)], -1)   # [G, n, H, F + 4]
     pad = Kp - Fw - H * (Fw + 4)
-    const = torch.cat([torch.ones(G, n, 1, dtype=qt.dtype), torch.zeros(G, n, pad - 1, dtype=qt.dtype)], -1)
+    const = torch.cat([m.any(2).to(qt.dtype), torch.zeros(G, n, pad - 1, dtype=qt.dtype)], -1)
     return torch.cat([Xa, agg.reshape(G, n, H * (Fw + 4)), const], -1), a

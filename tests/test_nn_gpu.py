@@ -560,34 +560,74 @@ def test_tree_roundtrip_and_param_counts(cuda):
             np.testing.assert_array_equal(leaves_a[k].numpy(), leaves_b[k])
 
 
-def _attn_inputs(cfg, F, H, Kp, G, gen, p_masked, on=1):
+def _attn_inputs(cfg, F, H, Kp, G, gen, p_masked, on=1, em=None, grid=None, xo=False):
     """random operands of dgppo_attn_fwd / _bwd for G graphs of topology cfg: slots masked with probability p_masked except
-    the first `on`; masked slots carry NaN edge features."""
+    the first `on`; masked slots carry NaN edge features.  em [G*n, S]: the caller's masks instead.  grid = q: exactly
+    representable operands (qt integers in [-q, q], node rows and edge features multiples of 1/4 in [-4, 4]; dz stays randn), so
+    that every logit is the same number in fp32 and float64 whatever the summation order.  xo: the operands of the _xo entry
+    points as well (Xo_raw [G*n_other, 8], Wo [8, 32], bo [32]; on the grid Wo in {-1/4, 0, 1/4} and bo in [-1, 1] keep the
+    recomputed rows at the scale of the others) with Xo = relu(Xo_raw Wo + bo) materialised in float64 from them."""
     n, S = cfg.n_agents, cfg.fan_in
     n_other = cfg.num_nodes - 1 - n
     R = G * n
-    em = (torch.rand(R, S, generator=gen) > p_masked).float()
-    em[:, :on] = 1.0
-    ef = torch.randn(R, S, 4, generator=gen)
+    if em is None:
+        em = (torch.rand(R, S, generator=gen) > p_masked).float()
+        em[:, :on] = 1.0
+    else:
+        em = em.reshape(R, S).float().clone()
+    quarters = lambda lo, hi, *shp: torch.randint(4 * lo, 4 * hi + 1, shp, generator=gen).float() / 4
+    ef = torch.randn(R, S, 4, generator=gen) if grid is None else quarters(-4, 4, R, S, 4)
     ef[em == 0] = float("nan")                 # masked slots must never be multiplied
-    return dict(qt=torch.randn(R, H * F, generator=gen), Xa=torch.randn(R, F, generator=gen),
-                Xo=torch.randn(G * n_other, F, generator=gen) if n_other > 0 else None, ef=ef, em=em,
-                dz=torch.randn(R, Kp, generator=gen))
+    if grid is None:
+        rnd = lambda *shp: torch.randn(*shp, generator=gen)
+        inp = dict(qt=rnd(R, H * F), Xa=rnd(R, F), Xo=rnd(G * n_other, F) if n_other > 0 and not xo else None)
+    else:
+        inp = dict(qt=torch.randint(-grid, grid + 1, (R, H * F), generator=gen).float(), Xa=quarters(-4, 4, R, F),
+                   Xo=quarters(-4, 4, G * n_other, F) if n_other > 0 and not xo else None)
+    if xo:
+        assert F == 32 and n_other > 0
+        if grid is None:
+            inp.update(Xo_raw=torch.randn(G * n_other, 8, generator=gen), Wo=torch.randn(8, 32, generator=gen) * 0.5,
+                       bo=torch.randn(32, generator=gen) * 0.3)
+        else:
+            inp.update(Xo_raw=quarters(-4, 4, G * n_other, 8), Wo=torch.randint(-1, 2, (8, 32), generator=gen).float() / 4,
+                       bo=quarters(-1, 1, 32))
+        _attn_materialise_xo(inp)
+    inp.update(ef=ef, em=em, dz=torch.randn(R, Kp, generator=gen))
+    return inp
+
+
+def _attn_materialise_xo(inp):
+    """Xo = relu(Xo_raw Wo + bo) in float64, rounded once to fp32 (on the grid operands it is exact)"""
+    inp["Xo"] = torch.relu(inp["Xo_raw"].double() @ inp["Wo"].double() + inp["bo"].double()).float()
 
 
 def _attn_reference(cfg, F, H, Kp, G, inp):
-    """float64 forward (oracle/nn_torch.py attn_fixed_fan_in) and its autograd backward, in the kernels' flat layouts."""
+    """float64 forward (oracle/nn_torch.py attn_fixed_fan_in) and its autograd backward, in the kernels' flat layouts; the
+    float64 logits [G*n, S, H] ride along.  With the operands of the _xo entry points (Xo_raw / Wo / bo) the other nodes' rows are
+    relu(Xo_raw Wo + bo) in float64 and the gradients behind them are added: dXo_relu = relu' dXo, dWo = Xo_raw^T dXo_relu, dbo."""
     n, S = cfg.n_agents, cfg.fan_in
     snd = T.attn_sender_nodes(n, cfg.n_goals, cfg.goal_slots, cfg.obs_slots, cfg.is_lidar, cfg.is_spread)
     leaf = lambda t, *shp: t.double().reshape(*shp).requires_grad_()
     qt, Xa = leaf(inp["qt"], G, n, H, F), leaf(inp["Xa"], G, n, F)
-    Xo = leaf(inp["Xo"], G, -1, F) if inp["Xo"] is not None else None
+    Xo = None
+    if inp.get("Xo_raw") is not None:
+        Xo = leaf(torch.relu(inp["Xo_raw"].double() @ inp["Wo"].double() + inp["bo"].double()), G, -1, F)
+    elif inp["Xo"] is not None:
+        Xo = leaf(inp["Xo"], G, -1, F)
     z, a = T.attn_fixed_fan_in(snd, qt, Xa, Xo, inp["ef"].double().reshape(G, n, S, 4), inp["em"].double().reshape(G, n, S), Kp)
     (z * inp["dz"].double().reshape(G, n, Kp)).sum().backward()
     out = dict(z=z.reshape(G * n, Kp), at=a.reshape(G * n, S, H), dq=qt.grad.reshape(G * n, H * F), dXa=Xa.grad.reshape(G * n, F))
+    with torch.no_grad():
+        X = Xa if Xo is None else torch.cat([Xa, Xo], 1)
+        out["logits"] = torch.einsum("gihf,gisf->gish", qt, X[:, snd]).reshape(G * n, S, H)
     if Xo is not None:
         out["dXo"] = Xo.grad.reshape(-1, F)
-    return out
+    if inp.get("Xo_raw") is not None:
+        out["dXo_relu"] = out["dXo"] * (Xo.detach().reshape(-1, F) > 0)
+        out["dWo"] = inp["Xo_raw"].double().t() @ out["dXo_relu"]
+        out["dbo"] = out["dXo_relu"].sum(0)
+    return {k: v.detach() for k, v in out.items()}
 
 
 def _attn_run(cfg, F, H, Kp, G, inp, dev):
@@ -620,10 +660,40 @@ def _attn_run(cfg, F, H, Kp, G, inp, dev):
     return out
 
 
+def _attn_run_xo(cfg, F, H, Kp, G, inp, dev):
+    """the three entry points that recompute the other nodes' rows from inp's Xo_raw / Wo / bo: dgppo_attn_fwd_xo (with and
+    without the saved weights), dgppo_attn_bwd_xo plain, with relu_xo and dqt-only, dgppo_attn_bwd_xo_dw into zeroed dWo / dbo
+    (rows [:8] of a wider gradient).  Keys are "<output>@xo...": _attn_check holds each to the reference's <output>."""
+    from dgppo_amd import ops_nn as K_
+    n, S = cfg.n_agents, cfg.fan_in
+    R, n_other = G * n, cfg.num_nodes - 1 - n
+    d = {k: (v.to(dev) if v is not None else None) for k, v in inp.items()}
+    nan = lambda *shp: torch.full(shp, float("nan"), device=dev)
+    z, at, z2 = nan(R, Kp), nan(R, S, H), nan(R, Kp)
+    K_.attn_fwd_xo(cfg, F, H, Kp, d["qt"], d["Xa"], d["Xo_raw"], d["Wo"], d["bo"], d["ef"], d["em"], z, at, G)
+    K_.attn_fwd_xo(cfg, F, H, Kp, d["qt"], d["Xa"], d["Xo_raw"], d["Wo"], d["bo"], d["ef"], d["em"], z2, None, G)   # inference form
+    out = {"z@xo": z, "at@xo": at}
+    for tag, relu_xo in (("dXo", False), ("dXo_relu", True)):
+        dq, dXa, dXo = nan(R, H * F), nan(R, F), nan(G * n_other, F)
+        K_.attn_bwd_xo(cfg, F, H, Kp, d["dz"], at, d["qt"], d["Xa"], d["Xo_raw"], d["Wo"], d["bo"], d["ef"], dq, dXa, dXo, G, relu_xo=relu_xo)
+        out.update({f"dq@xo {tag}": dq, f"dXa@xo {tag}": dXa, f"{tag}@xo": dXo})
+    dq3 = nan(R, H * F)
+    K_.attn_bwd_xo(cfg, F, H, Kp, d["dz"], at, d["qt"], d["Xa"], d["Xo_raw"], d["Wo"], d["bo"], d["ef"], dq3, None, None, G)
+    dq4, dXa4 = nan(R, H * F), nan(R, F)
+    dWfull, dbo = torch.zeros(Kp, 32, device=dev), torch.zeros(32, device=dev)
+    ws = torch.empty(K_.attn_xo_workspace_floats(G), device=dev)
+    K_.attn_bwd_xo_dw(cfg, F, H, Kp, d["dz"], at, d["qt"], d["Xa"], d["Xo_raw"], d["Wo"], d["bo"], d["ef"], dq4, dXa4, dWfull[:8], dbo, ws, G)
+    torch.cuda.synchronize()
+    assert torch.equal(z2, z), "the forward without saved weights differs"
+    assert float(dWfull[8:].abs().max()) == 0.0, "rows past 8 of the wider gradient were touched"
+    out.update({"dq@xo only": dq3, "dq@xo dw": dq4, "dXa@xo dw": dXa4, "dWo@xo": dWfull[:8], "dbo@xo": dbo})
+    return out
+
+
 def _attn_check(got, want, name):
     for k, v in got.items():
         assert torch.isfinite(v).all(), f"{name}: non-finite values in {k}"
-        _close(v, want["dq" if k == "dq_only" else k], 2e-5, f"{name} {k}")
+        _close(v, want["dq" if k == "dq_only" else k.split("@")[0]], 2e-5, f"{name} {k}")
 
 
 @pytest.mark.parametrize("F,Kp", [(8, 48), (32, 144), (16, 80), (12, 64), (6, 40), (10, 56)])

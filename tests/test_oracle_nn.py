@@ -440,7 +440,10 @@ def test_lstm_scan_known_answers():
 def test_attn_fixed_fan_in_matches_segment_softmax():
     """the kernel-level attention reference equals the per-edge form (segment_softmax over the unmasked edges into each agent,
     sums of a * [x_s | e]) on a LiDAR Target topology (own goal, own hits); NaN edge features behind the mask and an agent
-    with every slot masked (attention 0, aggregate 0) stay out of the result and its gradient."""
+    with every slot masked (attention 0, aggregate 0) stay out of the result and its gradient.  The column behind the
+    aggregates carries the value bias: the per-edge messages a * (v(x_s) + e) with v(x) = x W_v + b_v (gnn.py:85-111) are
+    composed from zcat as [sum a x_s | sum a e_s] [W_v ; W_e] + column * b_v, which holds for the fully masked agent (no edge,
+    message 0) only with a 0 there."""
     n, ng, gs, os_, F, H = 3, 3, 1, 2, 5, 2
     snd = T.attn_sender_nodes(n, ng, gs, os_, lidar=True, spread=False)
     assert snd.tolist() == [[0, 1, 2, 3, 6, 7], [0, 1, 2, 4, 8, 9], [0, 1, 2, 5, 10, 11]]
@@ -461,12 +464,20 @@ def test_attn_fixed_fan_in_matches_segment_softmax():
     recv = torch.tensor([i for i, _ in edges])
     logits = torch.stack([(qt[0, i] * X[snd[i, s]]).sum(-1) for i, s in edges])
     att = T.segment_softmax(logits, recv, n)
+    D = 3
+    Wv, We, bv = (torch.randn(*shp, generator=g, dtype=torch.float64) for shp in ((H, F, D), (H, 4, D), (H, D)))
     for i in range(n):
         for h in range(H):
-            want = sum((att[k, h] * torch.cat([X[snd[i, s]], ef[0, i, s]]) for k, (j, s) in enumerate(edges) if j == i),
-                       torch.zeros(F + 4, dtype=torch.float64))
-            torch.testing.assert_close(z[0, i, F + h * (F + 4):F + (h + 1) * (F + 4)], want)
-    assert torch.equal(z[0, :, :F], Xa[0]) and (z[0, :, -3] == 1).all() and (z[0, :, -2:] == 0).all()
+            mine = [(k, s) for k, (j, s) in enumerate(edges) if j == i]
+            want = sum((att[k, h] * torch.cat([X[snd[i, s]], ef[0, i, s]]) for k, s in mine), torch.zeros(F + 4, dtype=torch.float64))
+            agg = z[0, i, F + h * (F + 4):F + (h + 1) * (F + 4)]
+            torch.testing.assert_close(agg, want)
+            # the message of the per-edge form, value bias included, from zcat: the constant column is derived, not asserted
+            msg = sum((att[k, h] * (X[snd[i, s]] @ Wv[h] + bv[h] + ef[0, i, s] @ We[h]) for k, s in mine),
+                      torch.zeros(D, dtype=torch.float64))
+            torch.testing.assert_close(agg[:F] @ Wv[h] + agg[F:] @ We[h] + z[0, i, -3] * bv[h], msg)
+    assert torch.equal(z[0, :, :F], Xa[0]) and (z[0, :, -2:] == 0).all()
+    assert (z[0, :2, -3] == 1).all() and z[0, 2, -3] == 0 and (z[0, 2, F:] == 0).all()
     assert (a[0, 2] == 0).all() and torch.allclose(a[0, :2].sum(1), torch.ones(2, H, dtype=torch.float64))
     z.sum().backward()
     assert torch.isfinite(qt.grad).all() and (qt.grad[0, 2] == 0).all()
