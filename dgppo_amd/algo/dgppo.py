@@ -15,7 +15,7 @@ from .. import engine as EN
 from .. import init as INIT
 from .. import nets
 from .. import ops_nn as K
-from ..trainer.data import CostLandscape, Landscape, Rollout
+from ..trainer.data import ActionLandscape, CostLandscape, Landscape, Rollout
 from ..utils import checkpoint as CK
 from ..utils.graph import GraphsTuple
 from .base import Algorithm
@@ -66,12 +66,12 @@ def _n_cells(use_rnn: bool, rnn_layers: int) -> int:
     return rnn_layers if use_rnn else 0
 
 
-def _grid_axis(what: str, name: str, v, m: int, area: float) -> np.ndarray:
-    """one axis of a landscape grid in fp32: the given lines, or linspace(0, area, m)"""
+def _grid_axis(what: str, name: str, v, m: int, area: float, lo: float = 0.0) -> np.ndarray:
+    """one axis of a landscape grid in fp32: the given lines, or linspace(lo, area, m)"""
     if v is None:
         if int(m) < 1:
             raise ValueError(f"{what}: {name}: the grid is empty")
-        v = np.linspace(0.0, area, int(m))
+        v = np.linspace(lo, area, int(m))
     v = np.asarray(v, dtype=np.float32).reshape(-1)
     if v.size == 0 or not np.isfinite(v).all():
         raise ValueError(f"{what}: {name} must be a non-empty array of finite coordinates")
@@ -288,6 +288,26 @@ class DGPPO(Algorithm):
         frames = np.arange(ro.T) if frames is None else np.asarray(frames, dtype=np.int64).reshape(-1)
         cost = self.engine.cost_landscape(ro, int(index), int(agent), frames, xs, ys)
         return CostLandscape(xs, ys, cost.cpu().numpy(), int(agent), frames.astype(np.int64))
+
+    def action_landscape(self, rollout: Rollout, index: int, agent: int, frames=None, nu: int = 32, nv: int = 32, us=None,
+                         vs=None) -> ActionLandscape:
+        """The discrete control barrier condition the advantage is shaped by (dgppo.py:246-250), over a grid of actions of
+        `agent` in frames of episode `index` of a rollout that collect_deterministic / collect_stochastic returned: in every
+        frame t the agent's state is stepped with each grid action (everyone else keeps their recorded action), Vh is evaluated
+        on that next graph with the carry of step t + 1, and cbf = (Vh_next - Vh[t]) / dt + alpha * Vh[t].  frames: frame
+        numbers in [0, T) (default: all); us / vs: grid lines of the two action components (default: linspace(-1, 1, nu / nv) in
+        fp32).  Not in the reference."""
+        self.engine.require_landscape("action_landscape")
+        ro = getattr(self, "_last_rollouts", {}).get(id(rollout.actions))
+        if ro is None:
+            raise ValueError("action_landscape() needs a Rollout produced by this algo's collect methods")
+        us = _grid_axis("action_landscape", "us", us, nu, 1.0, lo=-1.0)
+        vs = _grid_axis("action_landscape", "vs", vs, nv, 1.0, lo=-1.0)
+        frames = np.arange(ro.T) if frames is None else np.asarray(frames, dtype=np.int64).reshape(-1)
+        cbf, Vh_next, Vh = self.engine.action_landscape(ro, int(index), int(agent), frames, us, vs)
+        actions = np.clip(ro.actions[int(index), :, int(agent)].cpu().numpy()[frames], -1.0, 1.0).astype(np.float32)
+        return ActionLandscape(us, vs, cbf.cpu().numpy(), Vh_next.cpu().numpy(), Vh.cpu().numpy(), actions, int(agent),
+                               frames.astype(np.int64), float(self.engine.hp.alpha), float(self.engine.cfg.dt))
 
     def update(self, rollout: Rollout, step: int) -> dict:
         ro = self._last_rollouts.pop(id(rollout.actions), None)

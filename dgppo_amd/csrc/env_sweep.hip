@@ -496,3 +496,211 @@ extern "C" int32_t dgppo_cost_sweep(const dgppo_env_cfg* cfg, const float* agent
   DGPPO_LAUNCH_CHECK();
   return 0;
 }
+
+
+// ---- CBF action landscape -----------------------------------------------------------------------------------------------------
+// The graph features behind the discrete barrier condition DGPPO's advantage is shaped by (dgppo/algo/dgppo.py:246-250):
+// cbf_deriv[t] = (Vh(graph[t+1]) - Vh(graph[t])) / dt + alpha * Vh(graph[t]), with ONE agent's action at step t swept over a grid.
+//
+// Graph g = (f * nv + iv) * nu + iu is the graph of frame fid + 1 (fid = frame_ids[f]) in which row `agent_id` is
+// agent_step_euler(row agent_id of frame fid, clip_action((us[iu], vs[iv]))) — step_state of env_step.h, the device code of the
+// step kernels, y_limit included; every other agent keeps its recorded next state, i.e. its recorded action.
+//
+// What changes with the action: in both dynamics the next POSITION does not depend on it (double integrator x + v dt, bicycle
+// x + v cos(theta) dt), so the LiDAR hits of frame fid + 1, every mask and every Xo row are the recorded ones and NO RAY IS CAST.
+// The velocity columns change (bicycle: cos(theta'), sin(theta'), v') and, through state2feat, every edge feature that touches
+// the agent.  The position is still taken from step_state's output: in a record the step kernels wrote, its bits are the record's.
+//
+// Organisation: the sweep above without its cast.  A workgroup stages frame fid + 1 (states, goals, discs, recorded hits) and
+// row agent_id of frame fid in LDS once per tile of 64 grid points and walks the tile, one wave per point: lane 0 steps the row
+// into the wave's LDS slot, then the wave streams the four dense outputs with unit-stride stores (edge features as float4).
+// The outputs have the layout and arithmetic of dgppo_graph_feats (graph_feats.hip) for G = n_frames * nv * nu graphs.
+#define ACT_TILE 64   // grid points per workgroup
+
+struct ActionSweepArgs {
+  dgppo_env_cfg cfg;
+  Topo t;
+  const float* agent; long agent_st;
+  const float* goal;
+  const float* obst;
+  const float* hits; long hits_st;
+  const int32_t* frame_ids;
+  int agent_id, nu, nuv, tiles;
+  const float* us;
+  const float* vs;
+  float* Xa;
+  float* Xo;
+  float* efeat;
+  float* emask;
+  int Fp;
+  uint32_t rcp_fp, rcp_S;   // ceil(2^32 / d): index divisions by Fp and S as one v_mul_hi_u32 (exact for idx < 2^16)
+};
+
+template <int SD>
+__global__ void __launch_bounds__(SWEEP_NT) graph_feats_action_sweep_kernel(ActionSweepArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const dgppo_env_cfg& c = a.cfg;
+  const Topo& t = a.t;
+  const int tid = threadIdx.x, lane = tid & (DGPPO_WAVE - 1), wave = tid / DGPPO_WAVE;
+  const int f = blockIdx.x / a.tiles, tile = blockIdx.x - f * a.tiles;
+  const int fid = a.frame_ids ? a.frame_ids[f] : f;
+  const int n = t.n, ng = t.ng, S = t.S, Fp = a.Fp, aid = a.agent_id;
+  const int n_on = t.Ns - n - ng;
+  const int k = c.top_k;
+  const bool rec_hits = t.lidar && n_on > 0;
+  // LDS carve: every offset is a multiple of 4 floats
+  const int al4 = 3;
+  float* s_rec = sm;                                                   // n_obs*SD discs (MPE)
+  float* s_ag = s_rec + ((t.lidar ? 0 : (n_on * SD + al4) & ~al4));    // n*SD   frame fid + 1
+  float* s_go = s_ag + ((n * SD + al4) & ~al4);                        // ng*SD
+  float* s_fa = s_go + ((ng * SD + al4) & ~al4);                       // n*4    state2feat(agent) of frame fid + 1
+  float* s_fg = s_fa + n * 4;                                          // ng*4
+  float* s_hp = s_fg + ng * 4;                                         // n*k*2  recorded hits of frame fid + 1 (LiDAR)
+  float* s_x0 = s_hp + (rec_hits ? ((n * k * 2 + al4) & ~al4) : 0);    // 8      row agent_id of frame fid
+  float* s_w = s_x0 + 8;                                               // waves * 12: the stepped row (8) and its features (4)
+
+  // ---- frame fid + 1 and the row to step, once per workgroup ----
+  const float* ag = a.agent + (size_t)(fid + 1) * a.agent_st;
+  for (int i = tid; i < n * SD; i += SWEEP_NT) s_ag[i] = ag[i];
+  for (int i = tid; i < ng * SD; i += SWEEP_NT) s_go[i] = a.goal[i];
+  if (rec_hits) {
+    const float* hp = a.hits + (size_t)(fid + 1) * a.hits_st;
+    for (int i = tid; i < n * k * 2; i += SWEEP_NT) s_hp[i] = hp[i];
+  } else if (!t.lidar) {
+    for (int i = tid; i < n_on * SD; i += SWEEP_NT) s_rec[i] = a.obst[i];
+  }
+  if (tid < SD) s_x0[tid] = a.agent[(size_t)fid * a.agent_st + aid * SD + tid];
+  __syncthreads();
+  for (int i = tid; i < n + ng; i += SWEEP_NT)
+    state2feat<SD>((i < n) ? s_ag + i * SD : s_go + (i - n) * SD, (i < n) ? s_fa + i * 4 : s_fg + (i - n) * 4);
+  __syncthreads();
+
+  const int q0 = tile * ACT_TILE, q1 = min(q0 + ACT_TILE, a.nuv);
+  float* w_st = s_w + wave * 12;
+  float* w_f = w_st + 8;
+  constexpr int ND = SD + 3;
+  // from here on the waves are independent: w_st / w_f belong to one wave, whose LDS operations complete in issue order,
+  // so between its phases a wave-level fence (no reordering by the compiler, no workgroup barrier) is enough
+  for (int q = q0 + wave; q < q1; q += SWEEP_WAVES) {
+    const int iv = q / a.nu, iu = q - iv * a.nu;
+    if (lane == 0) {
+      const float u0 = clampf(a.us[iu], -1.0f, 1.0f), u1 = clampf(a.vs[iv], -1.0f, 1.0f);   // clip_action, env/base.py:84-86
+      step_state<SD>(s_x0, u0, u1, c, c.y_limit, w_st);
+      state2feat<SD>(w_st, w_f);
+    }
+    wave_sync();
+    const size_t g = (size_t)f * a.nuv + q;
+    // state and feature row of agent i in this graph
+    auto st = [&](int i) { return (i == aid) ? w_st : s_ag + i * SD; };
+    auto ft = [&](int i) { return (i == aid) ? w_f : s_fa + i * 4; };
+
+    // node feature rows: [state | obs, goal, agent indicator], zero padded to Fp
+    float* xa = a.Xa + g * n * Fp;
+    for (int idx = lane; idx < n * Fp; idx += DGPPO_WAVE) {
+      const int nd = sweep_div(idx, a.rcp_fp), col = idx - nd * Fp;
+      float v = (col < SD) ? st(nd)[col] : ((col == SD + 2) ? 1.0f : 0.0f);
+      if (col >= ND) v = 0.0f;
+      xa[idx] = v;
+    }
+    float* xo = a.Xo + g * (t.Ns - n) * Fp;
+    for (int idx = lane; idx < (t.Ns - n) * Fp; idx += DGPPO_WAVE) {
+      const int r = sweep_div(idx, a.rcp_fp), col = idx - r * Fp;
+      float v;
+      if (r < ng) v = (col < SD) ? s_go[r * SD + col] : ((col == SD + 1) ? 1.0f : 0.0f);
+      else {
+        const int qn = r - ng;
+        if (t.lidar) v = (col < 2) ? s_hp[qn * 2 + col] : ((col == SD) ? 1.0f : 0.0f);
+        else v = (col < SD) ? s_rec[qn * SD + col] : ((col == SD) ? 1.0f : 0.0f);
+      }
+      if (col >= ND) v = 0.0f;
+      xo[idx] = v;
+    }
+    // per-slot edge feature + mask (lidar_env/base.py:227-271, lidar_spread.py:57-96 and the MPE twins)
+    float4* ef = reinterpret_cast<float4*>(a.efeat) + g * n * S;
+    float* em = a.emask + g * n * S;
+    for (int idx = lane; idx < n * S; idx += DGPPO_WAVE) {
+      const int i = sweep_div(idx, a.rcp_S), s = idx - i * S;
+      float4 fe;
+      bool mask;
+      const float* xi = st(i);
+      const float* fi = ft(i);
+      if (s < n) {
+        const float* xs_ = st(s);
+        const float* fs = ft(s);
+        fe = make_float4(fi[0] - fs[0], fi[1] - fs[1], fi[2] - fs[2], fi[3] - fs[3]);
+        const float d = dist_rn(xi[0] - xs_[0], xi[1] - xs_[1]) + ((i == s) ? c.eye_offset : 0.0f);
+        mask = d < c.comm_radius;
+      } else if (s < n + t.gs) {
+        const float* fg = s_fg + (t.spread ? (s - n) : i) * 4;
+        fe = make_float4(fi[0] - fg[0], fi[1] - fg[1], fi[2] - fg[2], fi[3] - fg[3]);
+        mask = true;
+      } else {
+        const int m = s - n - t.gs;
+        if (t.lidar) {
+          const float* hp = s_hp + (i * k + m) * 2;
+          const float lx = xi[0] - hp[0], ly = xi[1] - hp[1];
+          fe = make_float4(lx, ly, 0.0f, 0.0f);
+          mask = dist_rn(lx, ly) < c.lidar_mask_radius;
+        } else {
+          const float* xob = s_rec + m * SD;
+          const float dx = xi[0] - xob[0], dy = xi[1] - xob[1];
+          fe = make_float4(dx, dy, xi[2] - xob[2], xi[3] - xob[3]);
+          mask = dist_rn(dx, dy) < c.obs_mask_radius;
+        }
+      }
+      ef[idx] = fe;
+      em[idx] = mask ? 1.0f : 0.0f;
+    }
+    wave_sync();   // the next point's step overwrites w_st / w_f
+  }
+}
+
+extern "C" int32_t dgppo_graph_feats_action_sweep(const dgppo_env_cfg* cfg, const float* agent, int64_t agent_st,
+                                                  const float* goal, const float* obst, const float* hits, int64_t hits_st,
+                                                  const int32_t* frame_ids, int32_t n_frames, int32_t agent_id, const float* us,
+                                                  int32_t nu, const float* vs, int32_t nv, float* Xa, float* Xo, float* efeat,
+                                                  float* emask, int32_t Fp, void* stream) {
+  int32_t rc = dgppo_validate_cfg(cfg);
+  if (rc) return rc;
+  DGPPO_REFUSE_VMAS(cfg, "dgppo_graph_feats_action_sweep",
+                    "dgppo_vmas_step and dgppo_vmas_graph_feats on a tiled record (there is no VMAS sweep)");
+  DGPPO_REQUIRE(agent_id >= 0 && agent_id < cfg->n_agents, "dgppo_graph_feats_action_sweep: agent_id %d outside [0, %d)",
+                agent_id, cfg->n_agents);
+  DGPPO_REQUIRE(nu >= 0 && nv >= 0 && n_frames >= 0, "dgppo_graph_feats_action_sweep: negative counts");
+  if (nu == 0 || nv == 0 || n_frames == 0) return 0;
+  DGPPO_REQUIRE(agent && goal && us && vs && Xa && efeat && emask, "dgppo_graph_feats_action_sweep: NULL operand");
+  DGPPO_REQUIRE(Fp >= cfg->node_dim && Fp <= 32, "dgppo_graph_feats_action_sweep: Fp must be in [node_dim, 32]");
+  ActionSweepArgs a;
+  a.cfg = *cfg; a.t = make_topo(*cfg);
+  const Topo& t = a.t;
+  const int n_on = t.Ns - t.n - t.ng;
+  DGPPO_REQUIRE(t.Ns == t.n || Xo, "dgppo_graph_feats_action_sweep: Xo is NULL");
+  if (n_on > 0) {
+    if (t.lidar) DGPPO_REQUIRE(hits, "dgppo_graph_feats_action_sweep: hits is NULL");
+    else DGPPO_REQUIRE(obst, "dgppo_graph_feats_action_sweep: obst is NULL");
+  }
+  DGPPO_REQUIRE(((uintptr_t)efeat & 15) == 0, "dgppo_graph_feats_action_sweep: efeat must be 16-byte aligned");
+  DGPPO_REQUIRE(Fp >= 2 && t.S >= 2 && (long)t.Ns * Fp < 65536 && (long)t.n * t.S < 65536,
+                "dgppo_graph_feats_action_sweep: sizes out of range");
+  const long nuv = (long)nu * nv;
+  DGPPO_REQUIRE(nuv <= (1L << 24), "dgppo_graph_feats_action_sweep: grid too large (nu * nv <= 2^24)");
+  const long tiles = (nuv + ACT_TILE - 1) / ACT_TILE;
+  DGPPO_REQUIRE(tiles * n_frames < (1L << 31), "dgppo_graph_feats_action_sweep: too many graphs");
+  a.agent = agent; a.agent_st = agent_st; a.goal = goal; a.obst = obst; a.hits = hits; a.hits_st = hits_st;
+  a.frame_ids = frame_ids; a.agent_id = agent_id; a.nu = nu; a.nuv = (int)nuv; a.tiles = (int)tiles; a.us = us; a.vs = vs;
+  a.Xa = Xa; a.Xo = Xo; a.efeat = efeat; a.emask = emask; a.Fp = Fp;
+  auto rcp = [](int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); };
+  a.rcp_fp = rcp(Fp); a.rcp_S = rcp(t.S);
+  const int SD = cfg->state_dim, k = cfg->top_k;
+  auto up4 = [](long v) { return (v + 3) & ~3L; };
+  long fl = (t.lidar ? 0 : up4((long)n_on * SD)) + up4((long)t.n * SD) + up4((long)t.ng * SD) + t.n * 4 + t.ng * 4 + 8 +
+            SWEEP_WAVES * 12;
+  if (t.lidar && n_on > 0) fl += up4((long)t.n * k * 2);
+  DGPPO_REQUIRE(fl * 4 <= 64 * 1024, "dgppo_graph_feats_action_sweep: the frame does not fit the LDS (%ld bytes)", fl * 4);
+  const size_t smem = sizeof(float) * (size_t)fl;
+  const dim3 grid((unsigned)(tiles * n_frames));
+  if (SD == 5) hipLaunchKernelGGL(graph_feats_action_sweep_kernel<5>, grid, dim3(SWEEP_NT), smem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(graph_feats_action_sweep_kernel<4>, grid, dim3(SWEEP_NT), smem, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}

@@ -388,6 +388,17 @@ class Engine:
         of that step (rnn.py:20: rnn_state[0]; pre-step in a stochastic record, post-step in a deterministic one)"""
         return ro.rnn_states[e0:e0 + Eb][..., :nets.HID]
 
+    def _final_carry(self, ro: RolloutData, e0: int, Eb: int) -> torch.Tensor:
+        """[Eb * n, HC]: the actor's packed carry after the last step — its GRU on next_graph[-1] from rnn_states[-1]
+        (dgppo.py:222-226)"""
+        T, n, HC = self.T, self.cfg.n_agents, self.HC
+        fin = self._block_feats("fin", ro, e0, Eb, T, 1)
+        h_last = self.arena.get("pre.hlast", Eb * n, HC)
+        h_last.view(Eb, n, HC).copy_(ro.rnn_states[e0:e0 + Eb, T - 1])
+        hstar = self.arena.get("pre.hstar", Eb * n, HC)
+        self.policy.forward(fin, n_seq=Eb * n, T=1, h0=h_last, tag="fin", hs_out=hstar, train=False)
+        return hstar
+
     def values_prepass(self, ro: RolloutData, want_Vl: bool, want_Vh: bool = True):
         """-> Vl [B,T+1] (or None), Vh [B,T+1,n,nh] of one rollout, with the reference's carry conventions."""
         cfg, T, B = self.cfg, self.T, ro.B
@@ -404,13 +415,8 @@ class Engine:
                 Vl_buf[e0:e0 + Eb].copy_(act["v"].view(Eb, T + 1))
             if not want_Vh:
                 continue
-            # final carry: actor GRU on next_graph[-1] from rnn_states[-1] (dgppo.py:222-226)
-            fin = self._block_feats("fin", ro, e0, Eb, T, 1)
             HC = self.HC
-            h_last = self.arena.get("pre.hlast", Eb * n, HC)
-            h_last.view(Eb, n, HC).copy_(ro.rnn_states[e0:e0 + Eb, T - 1])
-            hstar = self.arena.get("pre.hstar", Eb * n, HC)
-            self.policy.forward(fin, n_seq=Eb * n, T=1, h0=h_last, tag="fin", hs_out=hstar, train=False)
+            hstar = self._final_carry(ro, e0, Eb)
             # the constraint-value net has ONE cell and reads layer 0 of the actor's packed carry (rnn.py:20: rnn_state[0])
             if not self.hp.use_rnn:
                 h0 = None
@@ -433,14 +439,15 @@ class Engine:
     # ------------------------------------------------------------------------------------------------------------------
     # Vh landscape (the producer of the arrays dgppo/env/plot.py:348-372,437-447 draws; the reference ships none)
     # ------------------------------------------------------------------------------------------------------------------
-    def require_landscape(self):
-        """ValueError unless vh_landscape serves this engine: DGPPO's constraint-value net on a LiDAR / MPE kind"""
+    def require_landscape(self, what: str = "vh_landscape"):
+        """ValueError unless vh_landscape / action_landscape serve this engine: DGPPO's constraint-value net on a LiDAR / MPE
+        kind"""
         if self.algo != "dgppo":
             why = {"informarl_lagr": "its constraint-value net carries its own scan state, which needs a sequence pass first"}
-            raise ValueError(f"vh_landscape: algo '{self.algo}' is not supported: "
+            raise ValueError(f"{what}: algo '{self.algo}' is not supported: "
                              + why.get(self.algo, "it has no constraint-value network"))
         if self.cfg.is_vmas:
-            raise ValueError("vh_landscape: VMASReverseTransport is not supported")
+            raise ValueError(f"{what}: VMASReverseTransport is not supported")
 
     def vh_landscape(self, ro: RolloutData, env_index: int, agent_id: int, frame_ids, xs, ys,
                      events: Optional[list] = None) -> torch.Tensor:
@@ -530,6 +537,78 @@ class Engine:
         K.cost_sweep(cfg, step["agent"], n * cfg.state_dim, env.get("obst"), step.get("hits"), n * cfg.top_k * 2, rc, rs,
                      frames, F, int(agent_id), xs, ys, out.view(F * ny * nx, n, self.n_cost))
         return out
+
+    def action_landscape(self, ro: RolloutData, env_index: int, agent_id: int, frame_ids, us, vs,
+                         events: Optional[list] = None):
+        """-> (cbf, Vh_next, Vh): the discrete barrier condition DGPPO's advantage is shaped by (dgppo.py:246-250) with the
+        action of agent `agent_id` at step t = frame_ids[f] (a subset of [0, T)) of env `env_index` swept over (us[iu], vs[iv]).
+        Vh_next [F, nv, nu, n, n_cost] is Vh of the graph of frame t + 1 in which that agent's row is agent_step_euler(its row
+        of frame t, clip_action((us[iu], vs[iv]))) and every other agent keeps its recorded next state, with the carry
+        values_prepass hands to Vh for (env, t + 1) (the final carry for t = T - 1; the carry does not depend on the swept
+        action); Vh [F, n, n_cost] is values_prepass' Vh[env, t]; cbf = (Vh_next - Vh) / dt + alpha * Vh, <= 0 where the net
+        admits the action.  Walked in sub-grids of at most prepass_graphs graphs, as vh_landscape is.  events: as there.
+        Vh comes from a values_prepass of the whole record (that is what makes it bit-equal to it), which rewrites the
+        pre-pass' persistent output buffers with the values they already hold for these parameters."""
+        self.require_landscape("action_landscape")
+        cfg, T = self.cfg, self.T
+        n, nh, H = cfg.n_agents, self.n_cost, nets.HID
+        ro.finalize()
+        if not 0 <= int(env_index) < ro.B:
+            raise ValueError(f"action_landscape: env_index {env_index} outside [0, {ro.B})")
+        if not 0 <= int(agent_id) < n:
+            raise ValueError(f"action_landscape: agent_id {agent_id} outside [0, {n})")
+        frames = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        if frames.size == 0 or frames.min() < 0 or frames.max() >= T:
+            raise ValueError(f"action_landscape: frame_ids must be a non-empty subset of [0, {T})")
+        us, vs = K.sweep_axis(us, "us", self.device), K.sweep_axis(vs, "vs", self.device)
+        nu, nv, F = int(us.numel()), int(vs.numel()), int(frames.size)
+        e = int(env_index)
+        ids_dev = torch.from_numpy(frames.astype(np.int32)).to(self.device)      # once per call; the sub-grids pass slices
+        _, Vh_all = self.values_prepass(ro, want_Vl=False)
+        Vh = Vh_all[e].index_select(0, ids_dev.long())                           # [F, n, nh]
+        carry = None
+        if self.hp.use_rnn:                                                      # [T, n, H]: the carry of the graph of frame t + 1
+            carry = torch.empty(T, n, H, device=self.device)
+            carry[:T - 1].copy_(self._vh_carry(ro, e, 1)[0, 1:])
+            if int(frames.max()) == T - 1:
+                carry[T - 1].copy_(self._final_carry(ro, e, 1).view(n, self.HC)[:, :H])
+        step = {k: v[e] for k, v in ro.step.items()}
+        env = {k: v[e] for k, v in ro.env.items()}
+        Vh_next = torch.empty(F, nv, nu, n, nh, device=self.device)
+        cap = max(1, self.prepass_graphs)
+        fb = max(1, cap // (nv * nu))
+        vb = nv if cap >= nv * nu else max(1, cap // nu)
+        ub = nu if cap >= nu else cap
+        for f0 in range(0, F, fb):
+            f1 = min(F, f0 + fb)
+            fr = frames[f0:f1]
+            for v0 in range(0, nv, vb):
+                v1 = min(nv, v0 + vb)
+                for u0 in range(0, nu, ub):
+                    u1 = min(nu, u0 + ub)
+                    P = (v1 - v0) * (u1 - u0)
+                    Gb = (f1 - f0) * P
+                    feats = nets.GraphFeats(cfg, Gb, self.arena, "act")
+                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if events is not None else None
+                    if ev:
+                        ev[0].record()
+                    feats.compute_action_sweep(step, env, ids_dev[f0:f1], f1 - f0, agent_id, us[u0:u1], vs[v0:v1],
+                                               frame_max=int(fr.max()))
+                    if ev:
+                        ev[1].record()
+                    h0 = None
+                    if carry is not None:
+                        h0 = self.arena.get("act.h0", Gb * n, H)
+                        for j, t in enumerate(fr):               # the carry of step t + 1, for every grid point of that frame
+                            h0.view(f1 - f0, P, n, H)[j].copy_(carry[int(t)].unsqueeze(0).expand(P, n, H))
+                    act = self.Vh.forward(feats, n_seq=Gb * n, T=1, h0=h0, tag="act", train=False)
+                    Vh_next[f0:f1, v0:v1, u0:u1].copy_(act["v"].view(f1 - f0, v1 - v0, u1 - u0, n, nh))
+                    if ev:
+                        ev[2].record()
+                        events.append(tuple(ev))
+        Vh_b = Vh.view(F, 1, 1, n, nh)
+        cbf = (Vh_next - Vh_b) / float(cfg.dt) + float(self.hp.alpha) * Vh_b
+        return cbf, Vh_next, Vh.clone()
 
     # ------------------------------------------------------------------------------------------------------------------
     # update

@@ -77,11 +77,29 @@ def unsafe_agents(ep: Episode, t: int, Ta_is_unsafe=None) -> np.ndarray:
     return np.flatnonzero((ep.costs[t] >= 0.0).any(axis=-1))
 
 
+def _centred_scale(h: np.ndarray):
+    """-> (norm, levels): one colour scale for a whole episode of contours, centred at 0 (15 levels)"""
+    from matplotlib.colors import CenteredNorm
+    half = float(np.nanmax(np.abs(h))) if np.isfinite(h).any() else 1.0
+    norm = CenteredNorm(vcenter=0.0, halfrange=half if half > 0.0 else 1.0)
+    return norm, np.linspace(-norm.halfrange, norm.halfrange, 15)
+
+
+def _drawable(z: np.ndarray) -> bool:
+    return bool(np.isfinite(z).all()) and z.shape[0] >= 2 and z.shape[1] >= 2
+
+
 class _Scene:
     """the artists of one figure; `draw(t)` moves them to frame t"""
 
     def __init__(self, ep: Episode, side_length: float, n_agent: int, n_goal: int, r: float, obs_r: float,
-                 cost_components: Sequence[str], Ta_is_unsafe, dpi: int, landscape=None, cost_landscape=None):
+                 cost_components: Sequence[str], Ta_is_unsafe, dpi: int, landscape=None, cost_landscape=None,
+                 action_landscape=None):
+        if action_landscape is not None:
+            for name, other in (("landscape", landscape), ("cost_landscape", cost_landscape)):
+                if other is not None and int(other.agent) != int(action_landscape.agent):
+                    raise ValueError(f"action_landscape is swept for agent {int(action_landscape.agent)}, {name} for agent "
+                                     f"{int(other.agent)}")
         if landscape is not None and cost_landscape is not None:
             if int(landscape.agent) != int(cost_landscape.agent):
                 raise ValueError(f"landscape is swept for agent {int(landscape.agent)}, cost_landscape for agent "
@@ -132,7 +150,6 @@ class _Scene:
         self._cost_h = None
         filled = landscape if landscape is not None else cost_landscape
         if filled is not None:
-            from matplotlib.colors import CenteredNorm
             if landscape is not None and cost_landscape is not None:
                 self._cost_h = np.asarray(cost_landscape.h(), dtype=np.float64)
                 self._cost_row = {int(t): k for k, t in enumerate(np.asarray(cost_landscape.frames).reshape(-1))}
@@ -142,16 +159,41 @@ class _Scene:
             if h.shape[1] < 2 or h.shape[2] < 2:
                 print(f"(landscape grid {h.shape[2]} x {h.shape[1]}: contours need at least 2 lines each way, none are drawn)")
             self._xy = np.meshgrid(np.asarray(filled.xs, dtype=np.float64), np.asarray(filled.ys, dtype=np.float64))
-            half = float(np.nanmax(np.abs(h))) if np.isfinite(h).any() else 1.0
-            self._norm = CenteredNorm(vcenter=0.0, halfrange=half if half > 0.0 else 1.0)
-            self._levels = np.linspace(-self._norm.halfrange, self._norm.halfrange, 15)
+            self._norm, self._levels = _centred_scale(h)
             sm = plt.cm.ScalarMappable(norm=self._norm, cmap="RdBu_r")
             self.fig.colorbar(sm, ax=ax, fraction=0.046, pad=0.04)
             self.cbf_text = ax.text(0.5, 1.04, f"{'CBF' if landscape is not None else 'Cost'} for {int(filled.agent)}",
                                     va="bottom", ha="center", **font)
 
+        # action landscape (trainer.data.ActionLandscape): an inset over the action square, the swept agent's largest cbf_deriv
+        # component as filled contours (<= 0: the net admits the action), the zero contour in black, the recorded action marked
+        self.action_landscape = action_landscape
+        self.act_ax = self.act_contours = self.act_zero_line = self.act_marker = None
+        if action_landscape is not None:
+            A = action_landscape
+            self._act_h = np.asarray(A.h(), dtype=np.float64)
+            self._act_row = {int(t): k for k, t in enumerate(np.asarray(A.frames).reshape(-1))}
+            self._act_taken = np.asarray(A.actions, dtype=np.float64).reshape(-1, 2)
+            us, vs = np.asarray(A.us, dtype=np.float64), np.asarray(A.vs, dtype=np.float64)
+            if self._act_h.shape[1] < 2 or self._act_h.shape[2] < 2:
+                print(f"(action grid {self._act_h.shape[2]} x {self._act_h.shape[1]}: contours need at least 2 lines each way, "
+                      f"none are drawn)")
+            self._act_uv = np.meshgrid(us, vs)
+            self._act_norm, self._act_levels = _centred_scale(self._act_h)
+            self.act_ax = ax.inset_axes([0.76, 0.02, 0.22, 0.22], zorder=8)
+            self.act_ax.set_xlim(min(-1.0, float(us.min())), max(1.0, float(us.max())))
+            self.act_ax.set_ylim(min(-1.0, float(vs.min())), max(1.0, float(vs.max())))
+            self.act_ax.set_aspect("equal")
+            self.act_ax.set_xticks([-1, 0, 1])
+            self.act_ax.set_yticks([-1, 0, 1])
+            self.act_ax.tick_params(labelsize=8)
+            self.act_ax.set_title(f"cbf_deriv of {int(A.agent)} over its action", fontsize=9)
+            self.act_marker, = self.act_ax.plot([], [], marker="x", color="k", markersize=8, markeredgewidth=2, linestyle="none",
+                                                zorder=5)
+            self.act_ax.set_visible(False)
+
     def artists(self):
-        extra = [a for a in (self.contours, self.zero_line, self.cost_zero_line, getattr(self, "cbf_text", None))
+        extra = [a for a in (self.contours, self.zero_line, self.cost_zero_line, getattr(self, "cbf_text", None), self.act_ax)
                  if a is not None]
         return [*self.agent_circles, *self.goal_circles, self.edges, self.cost_text, self.unsafe_text, self.step_text,
                 *self.labels, *extra]
@@ -163,25 +205,45 @@ class _Scene:
                 a.remove()
         self.contours = self.zero_line = self.cost_zero_line = None
         X, Y = self._xy
-        drawable = lambda z: np.isfinite(z).all() and z.shape[0] >= 2 and z.shape[1] >= 2
         k = self._frame_row.get(int(t))
-        if k is not None and drawable(self._h[k]):
+        if k is not None and _drawable(self._h[k]):
             z = self._h[k]
             self.contours = self.ax.contourf(X, Y, z, levels=self._levels, cmap="RdBu_r", norm=self._norm, alpha=0.5, zorder=2,
                                              extend="both")
             if z.min() < 0.0 <= z.max():             # h >= 0 is unsafe (Landscape.h): a maximum of exactly 0 counts
                 self.zero_line = self.ax.contour(X, Y, z, levels=[0.0], colors="k", linewidths=2.0, zorder=4)
         k = self._cost_row.get(int(t)) if self._cost_h is not None else None
-        if k is not None and drawable(self._cost_h[k]):
+        if k is not None and _drawable(self._cost_h[k]):
             z = self._cost_h[k]
             if z.min() < 0.0 <= z.max():             # the true unsafe set's boundary, dashed
                 self.cost_zero_line = self.ax.contour(X, Y, z, levels=[0.0], colors="k", linewidths=2.0, linestyles="dashed",
                                                       zorder=4)
 
+    def _draw_action_landscape(self, t: int):
+        """the inset of frame t, rebuilt like the contours above; a frame the action landscape does not hold shows no inset"""
+        for a in (self.act_contours, self.act_zero_line):
+            if a is not None:
+                a.remove()
+        self.act_contours = self.act_zero_line = None
+        k = self._act_row.get(int(t))
+        self.act_ax.set_visible(k is not None)
+        if k is None:
+            return
+        U, V = self._act_uv
+        z = self._act_h[k]
+        if _drawable(z):
+            self.act_contours = self.act_ax.contourf(U, V, z, levels=self._act_levels, cmap="RdBu_r", norm=self._act_norm,
+                                                     extend="both")
+            if z.min() <= 0.0 < z.max():             # cbf_deriv <= 0 is admitted: the boundary exists where the sign changes
+                self.act_zero_line = self.act_ax.contour(U, V, z, levels=[0.0], colors="k", linewidths=1.5)
+        self.act_marker.set_data([self._act_taken[k, 0]], [self._act_taken[k, 1]])
+
     def draw(self, t: int):
         ep, n = self.ep, self.n_agent
         if self.landscape is not None or self.cost_landscape is not None:
             self._draw_landscape(t)
+        if self.action_landscape is not None:
+            self._draw_action_landscape(t)
         pos = ep.states[t, :, :2]
         for i, c in enumerate(self.agent_circles):
             c.set_center(tuple(pos[i]))
@@ -223,7 +285,7 @@ def _write(scene: _Scene, n_frames: int, video_path: pathlib.Path, fps: int = 33
 
 
 def _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_components, Ta_is_unsafe, viz_opts, dpi, n_goal,
-            index=None, max_frames=None, landscape=None, cost_landscape=None, **kwargs) -> pathlib.Path:
+            index=None, max_frames=None, landscape=None, cost_landscape=None, action_landscape=None, **kwargs) -> pathlib.Path:
     if dim != 2:
         raise NotImplementedError("only the planar environments of SURVEY §8 are rendered (dim == 2)")
     if viz_opts:
@@ -231,25 +293,30 @@ def _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_compo
     ep = episode_from_rollout(rollout, index)
     n_goal = n_agent if n_goal is None else n_goal
     scene = _Scene(ep, float(side_length), n_agent, n_goal, r, obs_r, cost_components, Ta_is_unsafe, dpi, landscape,
-                   cost_landscape)
+                   cost_landscape, action_landscape)
     T = ep.states.shape[0] if max_frames is None else min(ep.states.shape[0], max_frames)
     return _write(scene, T, video_path)
 
 
 def render_lidar(rollout, video_path, side_length: float, dim: int, n_agent: int, n_rays: int, r: float,
                  cost_components: Tuple[str, ...], Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
-                 n_goal: Optional[int] = None, landscape=None, cost_landscape=None, **kwargs) -> pathlib.Path:
+                 n_goal: Optional[int] = None, landscape=None, cost_landscape=None, action_landscape=None,
+                 **kwargs) -> pathlib.Path:
     """dgppo/env/plot.py:468 (LiDAR family: rectangle obstacles, `n_rays` hit nodes per agent).  landscape: a
     trainer.data.Landscape of this episode, drawn as the reference draws viz_opts["cbf"] (plot.py:348-372,437-447).
     cost_landscape: a trainer.data.CostLandscape, drawn the same way when alone ("Cost for k"), as a dashed zero contour over
-    the Vh contours when both are given."""
+    the Vh contours when both are given.  action_landscape: a trainer.data.ActionLandscape, drawn in an inset over the action
+    square (filled contours of the swept agent's cbf_deriv, black zero contour, the recorded action marked); it combines with
+    the other two, for the same agent."""
     return _render(rollout, video_path, side_length, dim, n_agent, r, 0.0, cost_components, Ta_is_unsafe, viz_opts, dpi,
-                   n_goal, landscape=landscape, cost_landscape=cost_landscape, **kwargs)
+                   n_goal, landscape=landscape, cost_landscape=cost_landscape, action_landscape=action_landscape, **kwargs)
 
 
 def render_mpe(rollout, video_path, side_length: float, dim: int, n_agent: int, n_obs: int, r: float, obs_r: float,
                cost_components: Tuple[str, ...], Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
-               n_goal: Optional[int] = None, landscape=None, cost_landscape=None, **kwargs) -> pathlib.Path:
-    """dgppo/env/plot.py:206 (MPE family: disc obstacles of radius obs_r).  landscape / cost_landscape: as in render_lidar."""
+               n_goal: Optional[int] = None, landscape=None, cost_landscape=None, action_landscape=None,
+               **kwargs) -> pathlib.Path:
+    """dgppo/env/plot.py:206 (MPE family: disc obstacles of radius obs_r).  landscape / cost_landscape / action_landscape: as in
+    render_lidar."""
     return _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_components, Ta_is_unsafe, viz_opts, dpi,
-                   n_goal, landscape=landscape, cost_landscape=cost_landscape, **kwargs)
+                   n_goal, landscape=landscape, cost_landscape=cost_landscape, action_landscape=action_landscape, **kwargs)

@@ -150,6 +150,18 @@ class GraphFeats:
                             self.Xo if self.n_other > 0 else None, self.efeat, self.emask, self.Fp, hits_out, frame_max)
         return self
 
+    def compute_action_sweep(self, step, env, frame_ids, n_frames, agent_id, us, vs, frame_max=None):
+        """features of the graphs after the step of n_frames frames of ONE env of the env-major record with the action of agent
+        `agent_id` swept over us x vs (dgppo_graph_feats_action_sweep; G = n_frames * nv * nu): frame frame_ids[f] + 1 with that
+        agent's row stepped from frame frame_ids[f].  `step` / `env` as in compute_sweep; us / vs are ops_nn.sweep_axis tensors."""
+        cfg, n = self.cfg, self.cfg.n_agents
+        if cfg.is_vmas:
+            raise ValueError("compute_action_sweep: VMASReverseTransport has no sweep entry point")
+        K.graph_feats_action_sweep(cfg, step["agent"], n * cfg.state_dim, env["goal"], env.get("obst"), step.get("hits"),
+                                   n * cfg.top_k * 2, frame_ids, n_frames, agent_id, us, vs, self.Xa,
+                                   self.Xo if self.n_other > 0 else None, self.efeat, self.emask, self.Fp, frame_max)
+        return self
+
     def compute_vmas(self, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time):
         """VMASReverseTransport: agent / body records through strides (floats), scene [B, 8] (dgppo_vmas_graph_feats)"""
         assert n_env * n_time == self.G

@@ -275,13 +275,13 @@ def sweep_axis(x, name: str, device) -> torch.Tensor:
     return t_
 
 
-def _sweep_grid(fn: str, cfg: N.EnvCfg, frame_ids, n_frames, agent_id, xs, ys, frame_max):
-    """the grid and frame arguments the two sweep bindings share -> nx, ny, the host frame numbers still to be copied (or
+def _sweep_grid(fn: str, cfg: N.EnvCfg, frame_ids, n_frames, agent_id, xs, ys, frame_max, names=("xs", "ys")):
+    """the grid and frame arguments the sweep bindings share -> nx, ny, the host frame numbers still to be copied (or
     None), the device frame numbers given (or None), the largest frame read"""
     n = cfg.n_agents
     if not 0 <= int(agent_id) < n:
         raise ValueError(f"{fn}: agent_id {agent_id} outside [0, {n})")
-    for name, t_ in (("xs", xs), ("ys", ys)):
+    for name, t_ in zip(names, (xs, ys)):
         if not (torch.is_tensor(t_) and t_.is_cuda and t_.dtype == torch.float32 and t_.ndim == 1 and t_.is_contiguous()):
             raise ValueError(f"{fn}: {name} must be a dense 1-D float32 CUDA tensor (sweep_axis)")
         if t_.numel() == 0:
@@ -380,6 +380,53 @@ def cost_sweep(cfg: N.EnvCfg, agent, agent_st, obst, hits, hits_st, ray_cos, ray
         C.c_int32(int(agent_id)), _p(xs, "xs"), C.c_int32(nx), _p(ys, "ys"), C.c_int32(ny), _p(cost, "cost"),
         _p(hits_out, "hits_out") if cast and hits_out is not None else null, N.stream_ptr())
     N.check(rc, "dgppo_cost_sweep")
+
+
+ACTION_SWEEP_TILE = 64    # grid points per workgroup of dgppo_graph_feats_action_sweep (ACT_TILE, csrc/env_sweep.hip)
+
+
+def graph_feats_action_sweep(cfg: N.EnvCfg, agent, agent_st, goal, obst, hits, hits_st, frame_ids, n_frames, agent_id, us, vs,
+                             Xa, Xo, efeat, emask, Fp, frame_max=None):
+    """dgppo_graph_feats_action_sweep: the features of the graphs AFTER the step of n_frames frames of ONE env (agent / hits:
+    base tensors read at frame * stride, in floats; goal / obst: that env's rows) with the action of agent `agent_id` swept
+    over us [nu] x vs [nv] (sweep_axis tensors; clipped to [-1, 1] like every action): graph (f, iv, iu) is frame
+    frame_ids[f] + 1 with that agent's row stepped from frame frame_ids[f] by (us[iu], vs[iv]).  Nothing is cast: hits are the
+    recorded ones of frame + 1.  frame_ids as in graph_feats_sweep; frame + 1 must lie inside the record.
+    Every refusal is raised before anything is launched."""
+    fn = "graph_feats_action_sweep"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no sweep entry point")
+    n, S = cfg.n_agents, cfg.fan_in
+    nu, nv, ids, ids_dev, last = _sweep_grid(fn, cfg, frame_ids, n_frames, agent_id, us, vs, frame_max, ("us", "vs"))
+    G = n_frames * nv * nu
+    n_other = cfg.num_nodes - 1 - n
+    N.expect_shape(Xa, (G * n, Fp), "Xa")
+    if n_other > 0:
+        N.expect_shape(Xo, (G * n_other, Fp), "Xo")
+    N.expect_shape(efeat, (G * n, S, 4), "efeat")
+    N.expect_shape(emask, (G * n, S), "emask")
+    N.expect_shape(goal, (cfg.n_goals, cfg.state_dim), "goal")
+    # frames last and last + 1 are read
+    _check_strided(fn, "agent", agent, 0, agent_st, (n, cfg.state_dim), None, 1, last + 2)
+    rec_hits = cfg.is_lidar and cfg.n_obs > 0
+    discs = (not cfg.is_lidar) and cfg.n_obs > 0
+    if rec_hits:
+        if hits is None:
+            raise ValueError(f"{fn}: hits is required for a LiDAR kind with obstacles")
+        _check_strided(fn, "hits", hits, 0, hits_st, (n, cfg.top_k, 2), None, 1, last + 2)
+    if discs:
+        if obst is None:
+            raise ValueError(f"{fn}: obst is required when n_obs > 0")
+        N.expect_shape(obst, (cfg.n_obs, cfg.obst_stride), "obst")
+    if ids is not None:
+        ids_dev = torch.from_numpy(ids.astype(np.int32)).to(agent.device)
+    null = C.c_void_p(0)
+    rc = N.lib().dgppo_graph_feats_action_sweep(
+        C.byref(cfg), C.c_void_p(agent.data_ptr()), C.c_int64(agent_st), _p(goal, "goal"), _p(obst, "obst") if discs else null,
+        C.c_void_p(hits.data_ptr()) if rec_hits else null, C.c_int64(hits_st), _p(ids_dev, "frame_ids", torch.int32),
+        C.c_int32(n_frames), C.c_int32(int(agent_id)), _p(us, "us"), C.c_int32(nu), _p(vs, "vs"), C.c_int32(nv), _p(Xa, "Xa"),
+        _p(Xo, "Xo") if n_other > 0 else null, _p(efeat, "efeat"), _p(emask, "emask"), C.c_int32(Fp), N.stream_ptr())
+    N.check(rc, "dgppo_graph_feats_action_sweep")
 
 
 def vmas_graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time,

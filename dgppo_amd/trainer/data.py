@@ -53,3 +53,24 @@ class CostLandscape(NamedTuple):
         """[F, ny, nx]: the swept agent's largest cost component.  >= 0 exactly where test.py's unsafe rule fires for that
         agent (any component >= 0)."""
         return np.asarray(self.cost)[:, :, :, int(self.agent), :].max(axis=-1)
+
+
+class ActionLandscape(NamedTuple):
+    """The discrete control barrier condition of DGPPO (dgppo/algo/dgppo.py:246-250) with one agent's action swept over a grid
+    in frames of an episode (`DGPPO.action_landscape`): cbf = (Vh_next - Vh) / dt + alpha * Vh, where Vh_next is the learned
+    constraint value of the state one step ahead had `agent` taken (us[iu], vs[iv]) and everyone else their recorded action."""
+    us: np.ndarray        # [nu] fp32 grid lines of the first action component
+    vs: np.ndarray        # [nv] of the second
+    cbf: np.ndarray       # [F, nv, nu, n, n_cost]: cbf_deriv of every agent (a neighbour's value moves too)
+    Vh_next: np.ndarray   # [F, nv, nu, n, n_cost]: Vh of the graph after the step
+    Vh: np.ndarray        # [F, n, n_cost]: Vh of the recorded graph of frame frames[f]
+    actions: np.ndarray   # [F, 2]: the recorded action of `agent` in frame frames[f], clipped as the environment clips it
+    agent: int            # the agent whose action is swept
+    frames: np.ndarray    # [F] frame numbers of the episode
+    alpha: float
+    dt: float
+
+    def h(self) -> np.ndarray:
+        """[F, nv, nu]: the swept agent's largest cbf component.  <= 0 exactly where the net admits the action (every
+        component of cbf_deriv <= 0)."""
+        return np.asarray(self.cbf)[:, :, :, int(self.agent), :].max(axis=-1)

@@ -96,3 +96,33 @@ def landscape_agreement(land, cost) -> Dict[str, np.ndarray]:
     return dict(points=points, unsafe=unsafe, missed=missed, conservative=conservative, nan=(~ok).sum(axis=(1, 2)).astype(np.int64),
                 missed_frac=float(missed.sum() / max(int(unsafe.sum()), 1)),
                 conservative_frac=float(conservative.sum() / max(int(safe.sum()), 1)))
+
+
+def action_admissibility(A) -> Dict[str, np.ndarray]:
+    """What the learned barrier admits in an action landscape (trainer.data.ActionLandscape): a grid action is admitted where
+    A.h() <= 0, i.e. every component of the swept agent's cbf_deriv is <= 0; a NaN is not admitted.  Per frame [F]: `points`
+    (nv * nu), `admitted`, and `taken` — whether the action the agent actually took is admitted, decided from the record's own
+    values and not from the nearest grid point: cbf_deriv = (Vh[t + 1] - Vh[t]) / dt + alpha * Vh[t] with both values out of
+    A.Vh, so it is known (1 / 0) where A.frames also holds t + 1 and -1 elsewhere (always for the last frame of an episode,
+    whose successor values_prepass evaluates but the landscape does not keep).  `empty_frames`: the frame numbers with no
+    admitted action.  admissible_frac = admitted.sum() / points.sum(), empty_frac = len(empty_frames) / F,
+    taken_admitted_frac = (taken == 1).sum() / max((taken >= 0).sum(), 1)."""
+    h = np.asarray(A.h())
+    F = h.shape[0]
+    frames = np.asarray(A.frames).reshape(-1).astype(np.int64)
+    if frames.size != F:
+        raise ValueError(f"action_admissibility: {frames.size} frame numbers for {F} frames")
+    admitted = (h <= 0.0).sum(axis=(1, 2)).astype(np.int64)          # a NaN compares false
+    points = np.full(F, h.shape[1] * h.shape[2], dtype=np.int64)
+    Vh = np.asarray(A.Vh)[:, int(A.agent)]                            # [F, n_cost]
+    row = {int(t): k for k, t in enumerate(frames)}
+    taken = np.full(F, -1, dtype=np.int64)
+    for k, t in enumerate(frames):
+        nxt = row.get(int(t) + 1)
+        if nxt is not None:
+            cbf = (Vh[nxt] - Vh[k]) / np.float32(A.dt) + np.float32(A.alpha) * Vh[k]
+            taken[k] = int(bool((cbf <= 0.0).all()))
+    empty = frames[admitted == 0]
+    return dict(points=points, admitted=admitted, taken=taken, empty_frames=empty,
+                admissible_frac=float(admitted.sum() / max(int(points.sum()), 1)), empty_frac=float(empty.size / max(F, 1)),
+                taken_admitted_frac=float((taken == 1).sum() / max(int((taken >= 0).sum()), 1)))

@@ -369,6 +369,21 @@ int32_t dgppo_cost_sweep(const dgppo_env_cfg* cfg, const float* agent, int64_t a
                          int32_t n_frames, int32_t agent_id, const float* xs, int32_t nx, const float* ys, int32_t ny,
                          float* cost, float* hits_out, void* stream);
 
+/* The features behind the discrete control barrier condition (dgppo/algo/dgppo.py:246-250: cbf_deriv = (Vh(graph[t+1]) -
+ * Vh(graph[t])) / dt + alpha * Vh(graph[t])) with ONE agent's action swept: graph g = (f*nv + iv)*nu + iu is the graph of frame
+ * fid + 1 (fid = frame_ids ? frame_ids[f] : f) of ONE environment in which row `agent_id` is agent_step_euler(row agent_id of
+ * frame fid, clip_action((us[iu], vs[iv]))) (env/base.py:84-86, lidar_env/base.py:146-149, lidar_bicycle_target.py:95-107; the
+ * step kernels' own arithmetic, y_limit included) and every other agent keeps its recorded next state.  The next position does
+ * not depend on the action, so nothing is cast: hits (LiDAR kinds with obstacles; NULL otherwise) are the recorded ones of
+ * frame fid + 1, read at hits + (fid+1)*hits_st; agent is read at agent + fid*agent_st (the row) and + (fid+1)*agent_st (the
+ * frame), so fid + 1 must lie inside the record.  goal / obst are this env's rows; obst is read by the MPE kinds only
+ * ([n_obs, sd] discs; may be NULL for a LiDAR kind).  Outputs: dgppo_graph_feats' layout and arithmetic (get_graph,
+ * lidar_env/base.py:227-271) for the G = n_frames*nv*nu graphs.  The reference ships no producer for this.                   */
+int32_t dgppo_graph_feats_action_sweep(const dgppo_env_cfg* cfg, const float* agent, int64_t agent_st, const float* goal,
+                                       const float* obst, const float* hits, int64_t hits_st, const int32_t* frame_ids,
+                                       int32_t n_frames, int32_t agent_id, const float* us, int32_t nu, const float* vs,
+                                       int32_t nv, float* Xa, float* Xo, float* efeat, float* emask, int32_t Fp, void* stream);
+
 /* GraphTransformer attention in fixed-fan-in form (dgppo/nn/gnn.py:85-117; jraph.segment_softmax/segment_sum):
  * qt [G*n,H*F] = x_i Mcat + cvec (a Dense), logits = qt . x_sender, masked softmax over the S slots of each agent,
  * zcat [G*n,Kp] = [x_i | per head: sum a x_s (F), sum a e (4) | 1 | 0...], attn [G*n,S,H] saved for backward (NULL in

@@ -9,7 +9,11 @@ is available for `.mp4`).  `--landscape AGENT` (not a flag of the reference) als
 `{path}/videos/{step}/{stamp}_{name}_landscape.npz` and draws them as contours in the animation.  `--cost-landscape AGENT`
 does the same with the environment's own cost (`{stamp}_{name}_cost.npz`; every algorithm has it); with both flags for the
 same agent the animation shows the learned contours with the true zero line dashed, and a line per episode says how much of
-the truly unsafe set the net misses."""
+the truly unsafe set the net misses.  `--action-landscape AGENT` sweeps that agent's ACTION over the `--landscape-grid`-squared
+grid of [-1, 1]^2 in every frame and evaluates the discrete barrier condition the policy is trained under
+(`DGPPO.action_landscape`): `{stamp}_{name}_action.npz`, an inset in the animation, and a line per episode saying how much of
+the action square the learned barrier admits, in how many frames it admits nothing, and how often the action taken lies
+inside."""
 import argparse
 import datetime
 import os
@@ -38,7 +42,8 @@ def test(args):
         action_dim=env.action_dim, n_agents=env.num_agents, cost_weight=config.cost_weight,
         actor_gnn_layers=config.actor_gnn_layers, Vl_gnn_layers=config.Vl_gnn_layers,
         Vh_gnn_layers=getattr(config, "Vh_gnn_layers", 1), lr_actor=config.lr_actor, lr_Vl=config.lr_Vl, max_grad_norm=2.0,
-        seed=config.seed, use_rnn=config.use_rnn, rnn_layers=config.rnn_layers, use_lstm=config.use_lstm)
+        seed=config.seed, use_rnn=config.use_rnn, rnn_layers=config.rnn_layers, use_lstm=config.use_lstm,
+        alpha=getattr(config, "alpha", 10.0))
     algo.load(model_path, step)
 
     # episode seeds: the reference takes jr.split(PRNGKey(seed), 1000)[:epi][offset:] (test.py:90-93); RNG streams are not
@@ -61,7 +66,7 @@ def test(args):
     if args.log:
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(EV.csv_line(env, args.epi, agg))
-    if not args.no_video or args.landscape is not None or args.cost_landscape is not None:
+    if not args.no_video or args.landscape is not None or args.cost_landscape is not None or args.action_landscape is not None:
         videos_dir = pathlib.Path(args.path) / "videos" / f"{step}"
         videos_dir.mkdir(exist_ok=True, parents=True)
         stamp = datetime.datetime.now().strftime("%m%d-%H%M")
@@ -88,6 +93,17 @@ def test(args):
                 np.savez(out, xs=cost.xs, ys=cost.ys, cost=cost.cost, agent=cost.agent, frames=cost.frames, **more)
                 print(f"cost landscape: {out}")
                 extra["cost_landscape"] = cost
+            if args.action_landscape is not None:
+                A = algo.action_landscape(ro, i, args.action_landscape, nu=args.landscape_grid, nv=args.landscape_grid)
+                adm = EV.action_admissibility(A)
+                print(f"epi: {i}, agent {A.agent}: the learned barrier admits {adm['admissible_frac'] * 100:.3f}% of the action "
+                      f"grid (admissible_frac), nothing in {adm['empty_frac'] * 100:.3f}% of the frames (empty_frac), the action "
+                      f"taken in {adm['taken_admitted_frac'] * 100:.3f}% of them (taken_admitted_frac)")
+                out = videos_dir / f"{stamp}_{name}_action.npz"
+                np.savez(out, us=A.us, vs=A.vs, cbf=A.cbf, Vh_next=A.Vh_next, Vh=A.Vh, actions=A.actions, agent=A.agent,
+                         frames=A.frames, alpha=A.alpha, dt=A.dt, **adm)
+                print(f"action landscape: {out}")
+                extra["action_landscape"] = A
             if args.no_video:
                 continue
             out = env.render_video(ro, videos_dir / f"{stamp}_{name}.mp4", unsafe[i], {}, dpi=args.dpi, index=i, **extra)
@@ -107,12 +123,14 @@ FLAGS = [
 ]
 # the true-cost landscape of one agent (DGPPO.cost_landscape) over the --landscape-grid grid, per episode
 COST_FLAGS = [(("--cost-landscape",), "int", None)]
+# the barrier condition over one agent's actions (DGPPO.action_landscape), --landscape-grid squared, per episode
+ACTION_FLAGS = [(("--action-landscape",), "int", None)]
 
 
 def build_parser() -> argparse.ArgumentParser:
     types = {"int": int, "str": str}
     ap = argparse.ArgumentParser(description=__doc__)
-    for names, kind, default in FLAGS + COST_FLAGS:
+    for names, kind, default in FLAGS + COST_FLAGS + ACTION_FLAGS:
         if kind == "flag":
             ap.add_argument(*names, action="store_true", default=False)
         elif kind.startswith("req:"):
