@@ -39,10 +39,13 @@ __device__ inline void state2feat(const float* s, float* f) {
   }
 }
 
-__device__ inline float clampf(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
-// jnp.clip semantics: a NaN stays a NaN (fminf/fmaxf would return the bound).  Costs can be NaN when a hit point of the
-// pre-step graph is NaN (ray parallel to an edge); states never are.
+// jnp.clip semantics: a NaN stays a NaN (fminf / fmaxf alone would return the bound); every other input gets the bits of
+// fminf(fmaxf(x, lo), hi).  NaN reaches the costs through a NaN hit point of the pre-step graph (ray parallel to an edge,
+// SURVEY A.13 item 9), and the actions and states through a NaN policy output, which the reference carries through
+// clip_action (env/base.py:84-86) and clip_state into a visibly NaN rollout: every clip of the step kernels goes through here
 __device__ inline float clampf_nan(float x, float lo, float hi) { return (x != x) ? x : fminf(fmaxf(x, lo), hi); }
+// clip_action (env/base.py:84-86), shared by the three step kernels and the action sweep
+__device__ inline float clip_action(float u) { return clampf_nan(u, -1.0f, 1.0f); }
 
 // The reference formulas every step kernel shares.  Each keeps the oracle's fp32 operation order.
 
@@ -54,17 +57,17 @@ __device__ inline void step_state(const float* x, float u0, float u1, const dgpp
   if constexpr (SD == 5) {
     const float theta = atan2f(x[3], x[2]);
     const float theta_next = theta + x[4] * u0 * dt * 10.0f;
-    nx[0] = clampf(x[0] + x[4] * cosf(theta) * dt, 0.0f, A);
-    nx[1] = clampf(x[1] + x[4] * sinf(theta) * dt, 0.0f, A);
-    nx[2] = clampf(cosf(theta_next), -1.0f, 1.0f);
-    nx[3] = clampf(sinf(theta_next), -1.0f, 1.0f);
-    nx[SD - 1] = clampf(x[SD - 1] + u1 * dt * 10.0f, -0.5f, 0.5f);
+    nx[0] = clampf_nan(x[0] + x[4] * cosf(theta) * dt, 0.0f, A);
+    nx[1] = clampf_nan(x[1] + x[4] * sinf(theta) * dt, 0.0f, A);
+    nx[2] = clampf_nan(cosf(theta_next), -1.0f, 1.0f);
+    nx[3] = clampf_nan(sinf(theta_next), -1.0f, 1.0f);
+    nx[SD - 1] = clampf_nan(x[SD - 1] + u1 * dt * 10.0f, -0.5f, 0.5f);
   } else {
     const float vl = c.vel_limit;
-    nx[0] = clampf(x[2] * dt + x[0], 0.0f, A);
-    nx[1] = clampf(x[3] * dt + x[1], 0.0f, y_limit);
-    nx[2] = clampf((u0 * 10.0f) * dt + x[2], -vl, vl);
-    nx[3] = clampf((u1 * 10.0f) * dt + x[3], -vl, vl);
+    nx[0] = clampf_nan(x[2] * dt + x[0], 0.0f, A);
+    nx[1] = clampf_nan(x[3] * dt + x[1], 0.0f, y_limit);
+    nx[2] = clampf_nan((u0 * 10.0f) * dt + x[2], -vl, vl);
+    nx[3] = clampf_nan((u1 * 10.0f) * dt + x[3], -vl, vl);
   }
 }
 

@@ -54,7 +54,7 @@ __global__ void env_step_kernel(StepArgs a) {
   for (int i = tid; i < n * SD; i += nt) s_agent[i] = a.agent[(size_t)b * n * SD + i];
   for (int i = tid; i < ng * SD; i += nt) s_goal[i] = a.goal[(size_t)b * ng * SD + i];
   if (do_dyn)
-    for (int i = tid; i < n * 2; i += nt) s_act[i] = clampf(a.action[(size_t)b * n * 2 + i], -1.0f, 1.0f);  // env/base.py:84-86
+    for (int i = tid; i < n * 2; i += nt) s_act[i] = clip_action(a.action[(size_t)b * n * 2 + i]);  // env/base.py:84-86
   for (int i = tid; i < no * ostride; i += nt) s_obst[i] = a.obst[(size_t)b * no * ostride + i];
   if (a.hits != nullptr)
     for (int i = tid; i < n * kk * 2; i += nt) s_hpre[i] = a.hits[(size_t)b * n * kk * 2 + i];
@@ -375,7 +375,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
   const float cr = do_sense ? a.ray_cos[tid & 31] : 0.0f, sn = do_sense ? a.ray_sin[tid & 31] : 0.0f;
   // ---- P0: stage inputs ----
   for (int i = tid; i < n * SD; i += nt) { s_agent[i] = a.agent[(size_t)b * n * SD + i]; s_goal[i] = a.goal[(size_t)b * n * SD + i]; }
-  if (do_dyn) for (int i = tid; i < n * 2; i += nt) s_act[i] = clampf(a.action[(size_t)b * n * 2 + i], -1.0f, 1.0f);
+  if (do_dyn) for (int i = tid; i < n * 2; i += nt) s_act[i] = clip_action(a.action[(size_t)b * n * 2 + i]);
   for (int i = tid; i < no * 16; i += nt) s_obst[i] = a.obst[(size_t)b * no * 16 + i];
   if (a.hits != nullptr) for (int i = tid; i < n * k * 2; i += nt) s_hpre[i] = a.hits[(size_t)b * n * k * 2 + i];
   LDS_BARRIER();   // threads exchange data through LDS only; __syncthreads() would also wait for the global stores
@@ -494,7 +494,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(80))) lidar
             asm("v_max_f32 %0, %1, %2" : "=v"(mx) : "v"(naf[m]), "v"(nbf));
             // 0 <= q <= 1 for both quotients  <=>  0 <= min(na', nb') and max(na', nb') <= |det|   (-0 >= 0 holds, like -0/d >= 0)
             valid[m] = (mn >= 0.0f) && (mx <= adet[m]);
-            bad = bad || !(det0 != 0.0f);                                      // zero or NaN
+            bad = bad || !(fabsf(det0) > 0.0f);                                // zero or NaN (NaN != 0 would hold)
           }
 #pragma unroll
           for (int m = 0; m < 4; ++m) {

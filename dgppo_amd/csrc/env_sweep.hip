@@ -584,7 +584,7 @@ __global__ void __launch_bounds__(SWEEP_NT) graph_feats_action_sweep_kernel(Acti
   for (int q = q0 + wave; q < q1; q += SWEEP_WAVES) {
     const int iv = q / a.nu, iu = q - iv * a.nu;
     if (lane == 0) {
-      const float u0 = clampf(a.us[iu], -1.0f, 1.0f), u1 = clampf(a.vs[iv], -1.0f, 1.0f);   // clip_action, env/base.py:84-86
+      const float u0 = clip_action(a.us[iu]), u1 = clip_action(a.vs[iv]);   // clip_action, env/base.py:84-86
       step_state<SD>(s_x0, u0, u1, c, c.y_limit, w_st);
       state2feat<SD>(w_st, w_f);
     }

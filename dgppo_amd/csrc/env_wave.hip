@@ -275,7 +275,7 @@ __global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(G
       const float* x = L.agent + i * SD;
       float nx[SD];
       if (do_dyn) {
-        const float u0 = clampf(L.act[i * 2], -1.0f, 1.0f), u1 = clampf(L.act[i * 2 + 1], -1.0f, 1.0f);   // env/base.py:84-86
+        const float u0 = clip_action(L.act[i * 2]), u1 = clip_action(L.act[i * 2 + 1]);   // env/base.py:84-86
         step_state<SD>(x, u0, u1, c, c.area_size, nx);
         asq = u0 * u0 + u1 * u1;                  // (||a||)^2 = fl(sqrt(.))^2: the root is taken below with the distances
       } else {
@@ -572,8 +572,8 @@ __global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(G
             dprod = dprod * det0;
           }
           // det == 0 or NaN on any of the four segments (a product that underflows to 0 only sends the ray to the literal
-          // path below, which is always right)
-          const bool bad = !(dprod != 0.0f);
+          // path below, which is always right).  A NaN product (NaN position) must be caught too, and NaN != 0 holds
+          const bool bad = !(fabsf(dprod) > 0.0f);
           float amin = 1e6f;
           // one branch for the pass: when some lane hits some segment, the four correctly rounded divisions are issued
           // together (independent chains interleave)

@@ -213,6 +213,47 @@ def test_action_sweep_matches_oracle(cuda, kind, n, n_obs, area):
                     _same_words(v[:, 3, 3], v[:, 1, 2], f"{name} {tag}: (3, -2) vs (1, -1)")
 
 
+@pytest.mark.parametrize("kind,n,n_obs", [("LidarSpread", 3, 2), ("MPESpread", 3, 3)])
+def test_action_sweep_keeps_a_nan_action(cuda, kind, n, n_obs):
+    """a NaN grid value stays NaN through the sweep's clip_action, as in the oracle's (jnp.clip; fminf / fmaxf would turn it into
+    the action -1): NaN in the swept agent's velocity columns and in the edge features that subtract them, at exactly the
+    oracle's places, every other word bit-equal.  sweep_axis refuses non-finite coordinates, so the axes are handed to the
+    binding as plain device tensors."""
+    from dgppo_amd import ops_nn as K_
+    cfg, ocfg, agent, goal, obst, hits = _hand_scene(kind, n, n_obs, None)
+    frame_ids, aid, Fp = [1, 0], n - 1, 8
+    us, vs = np.array([0.0, np.nan, 1.0], f32), np.array([np.nan, 0.5], f32)
+    nu, nv, S, pad = len(us), len(vs), cfg.fan_in, cfg.num_nodes - 1
+    G, n_other = len(frame_ids) * nv * nu, cfg.num_nodes - 1 - n
+    ag, gr = _oracle_sweep(ocfg, agent, goal, obst, hits, frame_ids, aid, us, vs)
+    eos = _edge_of_slot(cfg)
+    on, edges = gr["receivers"][:, eos] != pad, gr["edges"][:, eos]
+    rows = np.zeros((G, pad, Fp), f32)
+    rows[..., :cfg.node_dim] = gr["nodes"][:, :pad]
+    swept = rows.reshape(len(frame_ids), nv, nu, pad, Fp)[:, :, :, aid]
+    assert np.isnan(swept[:, :, 1, 2]).all() and np.isnan(swept[:, 0, :, 3]).all() and np.isfinite(swept[:, 1, 0]).all()
+    assert np.isfinite(swept[..., :2]).all() and np.isnan(edges[on]).any()
+
+    def same(got, want, name):
+        nan = np.isnan(want)
+        np.testing.assert_array_equal(np.isnan(got), nan, err_msg=f"{name}: NaN positions")
+        _bits_equal(np.where(nan, f32(0), got), np.where(nan, f32(0), want), name)
+
+    Xa = torch.full((G * n, Fp), float("nan"), device=cuda)
+    Xo = torch.full((G * n_other, Fp), float("nan"), device=cuda)
+    ef = torch.full((G * n, S, 4), float("nan"), device=cuda)
+    em = torch.full((G * n, S), float("nan"), device=cuda)
+    k = ocfg.top_k
+    K_.graph_feats_action_sweep(cfg, _to(agent, cuda), n * ocfg.state_dim, _to(goal, cuda), _to(obst, cuda), _to(hits, cuda),
+                                0 if hits is None else n * k * 2, frame_ids, len(frame_ids), aid, _to(us, cuda), _to(vs, cuda),
+                                Xa, Xo, ef, em, Fp)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(em.cpu().numpy().reshape(G, n, S), on.astype(f32), err_msg="emask")
+    same(ef.cpu().numpy().reshape(G, n, S, 4)[on], np.ascontiguousarray(edges[on]), "efeat")
+    same(Xa.cpu().numpy().reshape(G, n, Fp), rows[:, :n], "Xa")
+    same(Xo.cpu().numpy().reshape(G, n_other, Fp), rows[:, n:], "Xo")
+
+
 # ---- 2. - 4. against the step kernel and the composition of the existing entry points -----------------------------------------------
 def _stepped(cfg, cuda, aid, acts, seed=4242):
     """P copies of one env (same seed), stepped once by ops_env.step with the same actions for everyone but agent `aid`, who
