@@ -15,7 +15,7 @@ from .. import engine as EN
 from .. import init as INIT
 from .. import nets
 from .. import ops_nn as K
-from ..trainer.data import ActionLandscape, CostLandscape, Landscape, Rollout
+from ..trainer.data import ActionLandscape, CostLandscape, Landscape, Rollout, ShieldLog
 from ..utils import checkpoint as CK
 from ..utils.graph import GraphsTuple
 from .base import Algorithm
@@ -256,6 +256,26 @@ class DGPPO(Algorithm):
             assert env.cfg.kind == self._env.cfg.kind and env.num_agents == self.n_agents
         ro = self.engine.rollout(self._seeds(keys), True, noise_seed=int(self._rng.integers(1, 2 ** 62)))
         return self._wrap(ro, env)
+
+    def collect_shielded(self, keys, env=None, grid: int = 8, us=None, vs=None, margin: float = 0.0):
+        """-> (Rollout, ShieldLog): deterministic test episodes in which every agent's action passes through the learned barrier
+        as a runtime filter (Engine.rollout_shielded): the policy's action is kept where cbf_deriv of the agent's own Vh
+        (dgppo.py:246-250) is <= -margin for it, otherwise replaced by the nearest admissible action of the grid us x vs
+        (default: linspace(-1, 1, grid) in fp32 on both axes), or by the least violating one where nothing is admissible.  The
+        Rollout is a deterministic one in every respect (landscapes, render_video); the log says what the shield did.  Not in
+        the reference."""
+        self.engine.require_landscape("collect_shielded")
+        if env is not None and env is not self._env:
+            assert env.cfg.kind == self._env.cfg.kind and env.num_agents == self.n_agents
+        us = _grid_axis("collect_shielded", "us", us, grid, 1.0, lo=-1.0)
+        vs = _grid_axis("collect_shielded", "vs", vs, grid, 1.0, lo=-1.0)
+        if not np.isfinite(float(margin)):
+            raise ValueError("collect_shielded: margin must be finite")
+        ro, log = self.engine.rollout_shielded(self._seeds(keys), us, vs, float(margin))
+        r = self._wrap(ro, env)
+        em = lambda x: x.transpose(0, 1).contiguous().cpu().numpy()
+        return r, ShieldLog(em(log["policy_action"]), ro.actions.cpu().numpy(), em(log["index"]), em(log["flag"]), em(log["h"]),
+                            em(log["Vh"]), us, vs, float(margin), float(self.engine.hp.alpha), float(self.engine.cfg.dt))
 
     def vh_landscape(self, rollout: Rollout, index: int, agent: int, frames=None, nx: int = 64, ny: int = 64, xs=None,
                      ys=None) -> Landscape:

@@ -704,3 +704,320 @@ extern "C" int32_t dgppo_graph_feats_action_sweep(const dgppo_env_cfg* cfg, cons
   DGPPO_LAUNCH_CHECK();
   return 0;
 }
+
+
+// ---- barrier shield: every agent's action swept at once ------------------------------------------------------------------------
+// The what-if graphs of one shielded step (Engine.rollout_shielded): for env e, agent i and candidate p, graph
+// g = (e * n + i) * P + p, P = 1 + nv * nu, is the graph of next_agent[e] — the state after the provisional step with the
+// policy's own actions — in which row i is agent_step_euler(row i of agent[e], clip_action(candidate p)) and every other agent
+// keeps its provisional next state.  Candidate 0 is the agent's own policy action a_pol[e, i], candidate 1 + iv * nu + iu is
+// (us[iu], vs[iv]).  This is dgppo_graph_feats_action_sweep's graph with the same arithmetic (step_state of env_step.h, nothing
+// is cast: the next position does not depend on the action, so next_hits are final), for all agents and environments in ONE
+// launch instead of B * n.
+//
+// Organisation: the action sweep's.  A workgroup serves one (e, i, tile of 64 candidates): it stages next_agent[e], the goals,
+// discs and next_hits of env e and row i of agent[e] in LDS once and walks the tile, one wave per candidate: lane 0 steps the
+// row into the wave's LDS slot, then the wave streams the four dense outputs with unit-stride stores (edge features as float4).
+struct TeamSweepArgs {
+  dgppo_env_cfg cfg;
+  Topo t;
+  const float* agent;        // [B, n, SD]   state t
+  const float* next_agent;   // [B, n, SD]   provisional state t + 1
+  const float* goal;         // [B, ng, SD]
+  const float* obst;         // [B, n_obs, SD] discs (MPE)
+  const float* next_hits;    // [B, n, k, 2] (LiDAR with obstacles)
+  const float* a_pol;        // [B, n, 2]
+  int nu, P, tiles;
+  const float* us;
+  const float* vs;
+  float* Xa;
+  float* Xo;
+  float* efeat;
+  float* emask;
+  int Fp;
+  uint32_t rcp_fp, rcp_S;   // ceil(2^32 / d): index divisions by Fp and S as one v_mul_hi_u32 (exact for idx < 2^16)
+};
+
+template <int SD>
+__global__ void __launch_bounds__(SWEEP_NT) graph_feats_team_action_sweep_kernel(TeamSweepArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const dgppo_env_cfg& c = a.cfg;
+  const Topo& t = a.t;
+  const int tid = threadIdx.x, lane = tid & (DGPPO_WAVE - 1), wave = tid / DGPPO_WAVE;
+  const int ei = blockIdx.x / a.tiles, tile = blockIdx.x - ei * a.tiles;   // ei = e * n + i
+  const int n = t.n, ng = t.ng, S = t.S, Fp = a.Fp;
+  const int e = ei / n, aid = ei - e * n;
+  const int n_on = t.Ns - n - ng;
+  const int k = c.top_k;
+  const bool rec_hits = t.lidar && n_on > 0;
+  // LDS carve: every offset is a multiple of 4 floats
+  const int al4 = 3;
+  float* s_rec = sm;                                                   // n_obs*SD discs (MPE)
+  float* s_ag = s_rec + ((t.lidar ? 0 : (n_on * SD + al4) & ~al4));    // n*SD   next_agent[e]
+  float* s_go = s_ag + ((n * SD + al4) & ~al4);                        // ng*SD
+  float* s_fa = s_go + ((ng * SD + al4) & ~al4);                       // n*4    state2feat(next_agent[e])
+  float* s_fg = s_fa + n * 4;                                          // ng*4
+  float* s_hp = s_fg + ng * 4;                                         // n*k*2  next_hits[e] (LiDAR)
+  float* s_x0 = s_hp + (rec_hits ? ((n * k * 2 + al4) & ~al4) : 0);    // 8      row aid of agent[e]
+  float* s_w = s_x0 + 8;                                               // waves * 12: the stepped row (8) and its features (4)
+
+  // ---- the provisional next frame of env e and the row to step, once per workgroup ----
+  const float* ag = a.next_agent + (size_t)e * n * SD;
+  for (int i = tid; i < n * SD; i += SWEEP_NT) s_ag[i] = ag[i];
+  const float* go = a.goal + (size_t)e * ng * SD;
+  for (int i = tid; i < ng * SD; i += SWEEP_NT) s_go[i] = go[i];
+  if (rec_hits) {
+    const float* hp = a.next_hits + (size_t)e * n * k * 2;
+    for (int i = tid; i < n * k * 2; i += SWEEP_NT) s_hp[i] = hp[i];
+  } else if (!t.lidar) {
+    const float* ob = a.obst + (size_t)e * n_on * SD;
+    for (int i = tid; i < n_on * SD; i += SWEEP_NT) s_rec[i] = ob[i];
+  }
+  if (tid < SD) s_x0[tid] = a.agent[(size_t)ei * SD + tid];
+  __syncthreads();
+  for (int i = tid; i < n + ng; i += SWEEP_NT)
+    state2feat<SD>((i < n) ? s_ag + i * SD : s_go + (i - n) * SD, (i < n) ? s_fa + i * 4 : s_fg + (i - n) * 4);
+  __syncthreads();
+
+  const int q0 = tile * ACT_TILE, q1 = min(q0 + ACT_TILE, a.P);
+  float* w_st = s_w + wave * 12;
+  float* w_f = w_st + 8;
+  constexpr int ND = SD + 3;
+  // from here on the waves are independent: w_st / w_f belong to one wave, whose LDS operations complete in issue order,
+  // so between its phases a wave-level fence (no reordering by the compiler, no workgroup barrier) is enough
+  for (int q = q0 + wave; q < q1; q += SWEEP_WAVES) {
+    if (lane == 0) {
+      float u0, u1;
+      if (q == 0) {
+        u0 = a.a_pol[(size_t)ei * 2]; u1 = a.a_pol[(size_t)ei * 2 + 1];
+      } else {
+        const int iv = (q - 1) / a.nu, iu = (q - 1) - iv * a.nu;
+        u0 = a.us[iu]; u1 = a.vs[iv];
+      }
+      step_state<SD>(s_x0, clip_action(u0), clip_action(u1), c, c.y_limit, w_st);   // clip_action, env/base.py:84-86
+      state2feat<SD>(w_st, w_f);
+    }
+    wave_sync();
+    const size_t g = (size_t)ei * a.P + q;
+    // state and feature row of agent i in this graph
+    auto st = [&](int i) { return (i == aid) ? w_st : s_ag + i * SD; };
+    auto ft = [&](int i) { return (i == aid) ? w_f : s_fa + i * 4; };
+
+    // node feature rows: [state | obs, goal, agent indicator], zero padded to Fp
+    float* xa = a.Xa + g * n * Fp;
+    for (int idx = lane; idx < n * Fp; idx += DGPPO_WAVE) {
+      const int nd = sweep_div(idx, a.rcp_fp), col = idx - nd * Fp;
+      float v = (col < SD) ? st(nd)[col] : ((col == SD + 2) ? 1.0f : 0.0f);
+      if (col >= ND) v = 0.0f;
+      xa[idx] = v;
+    }
+    float* xo = a.Xo + g * (t.Ns - n) * Fp;
+    for (int idx = lane; idx < (t.Ns - n) * Fp; idx += DGPPO_WAVE) {
+      const int r = sweep_div(idx, a.rcp_fp), col = idx - r * Fp;
+      float v;
+      if (r < ng) v = (col < SD) ? s_go[r * SD + col] : ((col == SD + 1) ? 1.0f : 0.0f);
+      else {
+        const int qn = r - ng;
+        if (t.lidar) v = (col < 2) ? s_hp[qn * 2 + col] : ((col == SD) ? 1.0f : 0.0f);
+        else v = (col < SD) ? s_rec[qn * SD + col] : ((col == SD) ? 1.0f : 0.0f);
+      }
+      if (col >= ND) v = 0.0f;
+      xo[idx] = v;
+    }
+    // per-slot edge feature + mask (lidar_env/base.py:227-271, lidar_spread.py:57-96 and the MPE twins)
+    float4* ef = reinterpret_cast<float4*>(a.efeat) + g * n * S;
+    float* em = a.emask + g * n * S;
+    for (int idx = lane; idx < n * S; idx += DGPPO_WAVE) {
+      const int i = sweep_div(idx, a.rcp_S), s = idx - i * S;
+      float4 fe;
+      bool mask;
+      const float* xi = st(i);
+      const float* fi = ft(i);
+      if (s < n) {
+        const float* xs_ = st(s);
+        const float* fs = ft(s);
+        fe = make_float4(fi[0] - fs[0], fi[1] - fs[1], fi[2] - fs[2], fi[3] - fs[3]);
+        const float d = dist_rn(xi[0] - xs_[0], xi[1] - xs_[1]) + ((i == s) ? c.eye_offset : 0.0f);
+        mask = d < c.comm_radius;
+      } else if (s < n + t.gs) {
+        const float* fg = s_fg + (t.spread ? (s - n) : i) * 4;
+        fe = make_float4(fi[0] - fg[0], fi[1] - fg[1], fi[2] - fg[2], fi[3] - fg[3]);
+        mask = true;
+      } else {
+        const int m = s - n - t.gs;
+        if (t.lidar) {
+          const float* hp = s_hp + (i * k + m) * 2;
+          const float lx = xi[0] - hp[0], ly = xi[1] - hp[1];
+          fe = make_float4(lx, ly, 0.0f, 0.0f);
+          mask = dist_rn(lx, ly) < c.lidar_mask_radius;
+        } else {
+          const float* xob = s_rec + m * SD;
+          const float dx = xi[0] - xob[0], dy = xi[1] - xob[1];
+          fe = make_float4(dx, dy, xi[2] - xob[2], xi[3] - xob[3]);
+          mask = dist_rn(dx, dy) < c.obs_mask_radius;
+        }
+      }
+      ef[idx] = fe;
+      em[idx] = mask ? 1.0f : 0.0f;
+    }
+    wave_sync();   // the next candidate's step overwrites w_st / w_f
+  }
+}
+
+extern "C" int32_t dgppo_graph_feats_team_action_sweep(const dgppo_env_cfg* cfg, const float* agent, const float* next_agent,
+                                                       const float* goal, const float* obst, const float* next_hits,
+                                                       const float* a_pol, int32_t n_env, const float* us, int32_t nu,
+                                                       const float* vs, int32_t nv, float* Xa, float* Xo, float* efeat,
+                                                       float* emask, int32_t Fp, void* stream) {
+  const char* fn = "dgppo_graph_feats_team_action_sweep";
+  int32_t rc = dgppo_validate_cfg(cfg);
+  if (rc) return rc;
+  DGPPO_REFUSE_VMAS(cfg, fn, "dgppo_vmas_step and dgppo_vmas_graph_feats on a tiled record (there is no VMAS sweep)");
+  DGPPO_REQUIRE(nu >= 1 && nv >= 1 && n_env >= 0, "%s: nu and nv must be >= 1 and n_env >= 0 (got %d, %d, %d)", fn, nu, nv, n_env);
+  if (n_env == 0) return 0;
+  DGPPO_REQUIRE(agent && next_agent && goal && a_pol && us && vs && Xa && efeat && emask, "%s: NULL operand", fn);
+  DGPPO_REQUIRE(Fp >= cfg->node_dim && Fp <= 32, "%s: Fp must be in [node_dim, 32]", fn);
+  TeamSweepArgs a;
+  a.cfg = *cfg; a.t = make_topo(*cfg);
+  const Topo& t = a.t;
+  const int n_on = t.Ns - t.n - t.ng;
+  DGPPO_REQUIRE(t.Ns == t.n || Xo, "%s: Xo is NULL", fn);
+  if (n_on > 0) {
+    if (t.lidar) DGPPO_REQUIRE(next_hits, "%s: next_hits is NULL", fn);
+    else DGPPO_REQUIRE(obst, "%s: obst is NULL", fn);
+  }
+  DGPPO_REQUIRE(((uintptr_t)efeat & 15) == 0, "%s: efeat must be 16-byte aligned", fn);
+  DGPPO_REQUIRE(Fp >= 2 && t.S >= 2 && (long)t.Ns * Fp < 65536 && (long)t.n * t.S < 65536, "%s: sizes out of range", fn);
+  const long nuv = (long)nu * nv;
+  DGPPO_REQUIRE(nuv < (1L << 24), "%s: grid too large (nu * nv < 2^24)", fn);
+  const long P = 1 + nuv;
+  const long tiles = (P + ACT_TILE - 1) / ACT_TILE;
+  DGPPO_REQUIRE(tiles * n_env * t.n < (1L << 31), "%s: too many graphs", fn);
+  a.agent = agent; a.next_agent = next_agent; a.goal = goal; a.obst = obst; a.next_hits = next_hits; a.a_pol = a_pol;
+  a.nu = nu; a.P = (int)P; a.tiles = (int)tiles; a.us = us; a.vs = vs;
+  a.Xa = Xa; a.Xo = Xo; a.efeat = efeat; a.emask = emask; a.Fp = Fp;
+  auto rcp = [](int d) { return (uint32_t)((0x100000000ull + (uint64_t)d - 1) / (uint64_t)d); };
+  a.rcp_fp = rcp(Fp); a.rcp_S = rcp(t.S);
+  const int SD = cfg->state_dim, k = cfg->top_k;
+  auto up4 = [](long v) { return (v + 3) & ~3L; };
+  long fl = (t.lidar ? 0 : up4((long)n_on * SD)) + up4((long)t.n * SD) + up4((long)t.ng * SD) + t.n * 4 + t.ng * 4 + 8 +
+            SWEEP_WAVES * 12;
+  if (t.lidar && n_on > 0) fl += up4((long)t.n * k * 2);
+  DGPPO_REQUIRE(fl * 4 <= 64 * 1024, "%s: the frame does not fit the LDS (%ld bytes)", fn, fl * 4);
+  const size_t smem = sizeof(float) * (size_t)fl;
+  const dim3 grid((unsigned)(tiles * n_env * t.n));
+  if (SD == 5) hipLaunchKernelGGL(graph_feats_team_action_sweep_kernel<5>, grid, dim3(SWEEP_NT), smem, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(graph_feats_team_action_sweep_kernel<4>, grid, dim3(SWEEP_NT), smem, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
+
+// ---- barrier shield: selection -------------------------------------------------------------------------------------------------
+// Per (env e, agent i), over the P = 1 + nv * nu candidates of the sweep above, on the agent's OWN row (the filter is
+// decentralised):  h[p] = max_c ((Vh_next[e, i, p, i, c] - Vh_t[e, i, c]) / dt + alpha * Vh_t[e, i, c])  — the discrete barrier
+// condition of dgppo/algo/dgppo.py:246-250, NaN-propagating max, fp32 without contraction.  A candidate is admissible iff
+// h <= -margin (a NaN never is).  Candidate 0 (the policy's action) is kept if admissible (flag 0); otherwise the admissible
+// candidate nearest to it, du * du + dv * dv on clipped actions, lowest index on ties (a NaN distance counts as +inf) (flag 1);
+// with nothing admissible the candidate with the smallest h, lowest index on ties, NaN skipped, candidate 0 if every h is NaN
+// (flag 2).  One wave per (e, i), lanes over the candidates, two (value, index) minima reduced with __shfl_xor.
+#define SHIELD_NT 256
+#define SHIELD_WAVES (SHIELD_NT / DGPPO_WAVE)
+
+struct ShieldArgs {
+  const float* Vh_next;   // [E, n, P, n, nh]
+  const float* Vh_t;      // [E, n, nh]
+  const float* a_pol;     // [E, n, 2]
+  const float* us;
+  const float* vs;
+  int rows, n, nh, nu, P;
+  float dt, alpha, margin;
+  float* action;          // [E, n, 2]
+  int32_t* index;         // [E, n]
+  int32_t* flag;          // [E, n]
+  float* h;               // [E, n, P] or NULL
+};
+
+// lexicographic (value, index) minimum over the wave
+__device__ inline void wave_argmin(float& v, int& i) {
+  for (int off = DGPPO_WAVE >> 1; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(v, off);
+    const int oi = __shfl_xor(i, off);
+    if (ov < v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
+}
+
+__global__ void __launch_bounds__(SHIELD_NT) shield_select_kernel(ShieldArgs a) {
+  const int lane = threadIdx.x & (DGPPO_WAVE - 1);
+  const long row = (long)blockIdx.x * SHIELD_WAVES + threadIdx.x / DGPPO_WAVE;   // row = e * n + i
+  if (row >= a.rows) return;                      // whole waves leave: no lane of a live wave is missing from the shuffles
+  const int i = (int)(row % a.n), nh = a.nh, P = a.P;
+  const float inf = __builtin_inff();
+  const float* vt = a.Vh_t + row * nh;
+  const float* vn = a.Vh_next + ((size_t)row * P * a.n + i) * nh;
+  const size_t vn_st = (size_t)a.n * nh;
+  const float a0 = clip_action(a.a_pol[row * 2]), a1 = clip_action(a.a_pol[row * 2 + 1]);
+  const float thr = -a.margin;
+  float bd = inf, bh = inf, h0 = 0.0f;
+  int bdi = 0x7fffffff, bhi = 0x7fffffff;
+  for (int p = lane; p < P; p += DGPPO_WAVE) {
+    float h = 0.0f;
+    for (int cc = 0; cc < nh; ++cc) {
+      const float v = vt[cc];
+      const float hc = (vn[p * vn_st + cc] - v) / a.dt + a.alpha * v;
+      h = (cc == 0) ? hc : nanmax(h, hc);
+    }
+    if (a.h != nullptr) a.h[(size_t)row * P + p] = h;
+    if (p == 0) h0 = h;
+    float cu = a0, cv = a1;
+    if (p > 0) {
+      const int iv = (p - 1) / a.nu, iu = (p - 1) - iv * a.nu;
+      cu = clip_action(a.us[iu]); cv = clip_action(a.vs[iv]);
+    }
+    if (h <= thr) {                               // admissible (false for a NaN)
+      const float du = cu - a0, dv = cv - a1;
+      float d = du * du + dv * dv;
+      if (d != d) d = inf;
+      if (d < bd || (d == bd && p < bdi)) { bd = d; bdi = p; }
+    }
+    if (h == h && (h < bh || (h == bh && p < bhi))) { bh = h; bhi = p; }
+  }
+  h0 = __shfl(h0, 0);
+  wave_argmin(bd, bdi);
+  wave_argmin(bh, bhi);
+  if (lane != 0) return;
+  int idx, fl;
+  if (h0 <= thr) { idx = 0; fl = 0; }
+  else if (bdi != 0x7fffffff) { idx = bdi; fl = 1; }
+  else { idx = (bhi != 0x7fffffff) ? bhi : 0; fl = 2; }
+  float cu = a0, cv = a1;
+  if (idx > 0) {
+    const int iv = (idx - 1) / a.nu, iu = (idx - 1) - iv * a.nu;
+    cu = clip_action(a.us[iu]); cv = clip_action(a.vs[iv]);
+  }
+  a.action[row * 2] = cu; a.action[row * 2 + 1] = cv;
+  a.index[row] = idx; a.flag[row] = fl;
+}
+
+extern "C" int32_t dgppo_shield_select(const float* Vh_next, const float* Vh_t, const float* a_pol, int32_t n_env,
+                                       int32_t n_agents, int32_t n_cost, const float* us, int32_t nu, const float* vs, int32_t nv,
+                                       float dt, float alpha, float margin, float* action, int32_t* index, int32_t* flag,
+                                       float* h, void* stream) {
+  const char* fn = "dgppo_shield_select";
+  DGPPO_REQUIRE(n_env >= 0 && n_agents >= 1 && n_cost >= 1, "%s: n_env >= 0, n_agents >= 1 and n_cost >= 1 are required", fn);
+  DGPPO_REQUIRE(nu >= 1 && nv >= 1, "%s: nu and nv must be >= 1 (got %d, %d)", fn, nu, nv);
+  DGPPO_REQUIRE((long)nu * nv < (1L << 24), "%s: grid too large (nu * nv < 2^24)", fn);
+  DGPPO_REQUIRE(dt > 0.0f && alpha == alpha && margin == margin, "%s: dt must be > 0, alpha and margin no NaN", fn);
+  if (n_env == 0) return 0;
+  DGPPO_REQUIRE(Vh_next && Vh_t && a_pol && us && vs && action && index && flag, "%s: NULL operand", fn);
+  const long rows = (long)n_env * n_agents;
+  DGPPO_REQUIRE(rows < (1L << 31) - SHIELD_WAVES, "%s: too many rows", fn);
+  ShieldArgs a;
+  a.Vh_next = Vh_next; a.Vh_t = Vh_t; a.a_pol = a_pol; a.us = us; a.vs = vs;
+  a.rows = (int)rows; a.n = n_agents; a.nh = n_cost; a.nu = nu; a.P = 1 + nu * nv;
+  a.dt = dt; a.alpha = alpha; a.margin = margin; a.action = action; a.index = index; a.flag = flag; a.h = h;
+  const dim3 grid((unsigned)((rows + SHIELD_WAVES - 1) / SHIELD_WAVES));
+  hipLaunchKernelGGL(shield_select_kernel, grid, dim3(SHIELD_NT), 0, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}

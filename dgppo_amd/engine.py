@@ -611,6 +611,103 @@ class Engine:
         return cbf, Vh_next, Vh.clone()
 
     # ------------------------------------------------------------------------------------------------------------------
+    # barrier shield: the deterministic rollout with every agent's action filtered through the learned barrier
+    # ------------------------------------------------------------------------------------------------------------------
+    def rollout_shielded(self, seeds: torch.Tensor, us, vs, margin: float = 0.0, events: Optional[list] = None):
+        """-> (RolloutData, log): a deterministic record (the conventions of rollout(seeds, False)) in which, at every step,
+        every agent's action is filtered through the barrier condition the policy is trained under (dgppo.py:246-250).  The
+        candidates of an agent are its own policy action (index 0) and the grid (us[iu], vs[iv]) (index 1 + iv * nu + iu).  Per
+        step: the policy forward gives a_pol and the post-step carry; Vh of the graph of state t with layer 0 of that carry is
+        Vh_t; a provisional step with a_pol gives the next state (its positions and hits are final: they do not depend on the
+        action) and one more policy forward on it the carry c' that Vh reads for frame t + 1; the what-if graphs of every
+        (env, agent, candidate) — the agent's row stepped by the candidate, everyone else as provisionally stepped — go through
+        Vh with layer 0 of c' (dgppo_graph_feats_team_action_sweep, walked in blocks of environments of at most prepass_graphs
+        graphs); dgppo_shield_select picks per agent, on its own row; the final step with the chosen actions overwrites state
+        t + 1.  Reward and cost belong to the pre-step state and keep their values.
+        log (time-major device tensors): policy_action [T, B, n, 2], index / flag [T, B, n] (int32; flag 0 kept, 1 replaced by an
+        admissible candidate, 2 nothing admissible), h [T, B, n, P], Vh [T, B, n, nh].  Eager launches; the record is a fresh one.
+        events: a list that receives one tuple of device events per step (tools/bench_shield.py): start, policy and Vh_t done,
+        provisional step and c' done, then (features, Vh forward, select) done per env block, the final step done."""
+        self.require_landscape("rollout_shielded")
+        cfg, T = self.cfg, self.T
+        n, nh, H, HC = cfg.n_agents, self.n_cost, nets.HID, self.HC
+        us, vs = K.sweep_axis(us, "us", self.device), K.sweep_axis(vs, "vs", self.device)
+        margin = float(margin)
+        if not np.isfinite(margin):
+            raise ValueError("rollout_shielded: margin must be finite")
+        nu, nv = int(us.numel()), int(vs.numel())
+        P = 1 + nu * nv
+        B = int(seeds.shape[0])
+        dev = self.device
+        ro = RolloutData(cfg, B, T, dev, False, HC)
+        OE.reset(cfg, seeds, ro.states_tm[0], self.reset_failed)
+        ro.rnn_tm[0].zero_()
+        log = dict(policy_action=torch.empty(T, B, n, 2, device=dev), index=torch.empty(T, B, n, dtype=torch.int32, device=dev),
+                   flag=torch.empty(T, B, n, dtype=torch.int32, device=dev), h=torch.empty(T, B, n, P, device=dev),
+                   Vh=torch.empty(T, B, n, nh, device=dev))
+        use_rnn = self.hp.use_rnn
+        block = max(1, min(B, max(1, self.prepass_graphs) // (n * P)))
+        dt, alpha = float(cfg.dt), float(self.hp.alpha)
+
+        def mark(ev):
+            if ev is not None:
+                ev.append(torch.cuda.Event(enable_timing=True))
+                ev[-1].record()
+        for t in range(T):
+            st, nst = ro.states_tm[t], ro.states_tm[t + 1]
+            ev = [] if events is not None else None
+            mark(ev)
+            # 1. policy forward: a_pol and h_{t+1}
+            feats = self._feats("sh", st, B)
+            h_next = ro.rnn_tm[t + 1].view(B * n, HC)
+            act = self.policy.forward(feats, n_seq=B * n, T=1, h0=ro.rnn_tm[t].view(B * n, HC), tag="sh", hs_out=h_next,
+                                      train=False)
+            a_pol = log["policy_action"][t]
+            K.policy_head(act["ms"], None, None, a_pol.view(B * n, 2), None, None, n, 1)
+            # 2. Vh_t with the carry a deterministic record hands it: layer 0 of h_{t+1}
+            h0 = None
+            if use_rnn:
+                h0 = h_next
+                if HC != H:
+                    h0 = self.arena.get("sh.h0", B * n, H)
+                    h0.copy_(h_next[:, :H])
+            v = self.Vh.forward(feats, n_seq=B * n, T=1, h0=h0, tag="sh", train=False)["v"]
+            Vh_t = log["Vh"][t]
+            Vh_t.copy_(v.view(B, n, nh))
+            mark(ev)
+            # 3. provisional step and the carry c' of frame t + 1
+            OE.step(cfg, st, a_pol, nst, ro.reward_tm[t], ro.cost_tm[t])
+            cl0 = None
+            if use_rnn:
+                cprime = self.arena.get("sh.cprime", B * n, HC)
+                self.policy.forward(self._feats("sh", nst, B), n_seq=B * n, T=1, h0=h_next, tag="sh", hs_out=cprime, train=False)
+                cl0 = cprime.view(B, n, HC)[..., :H]
+            mark(ev)
+            # 4. - 6. what-if graphs, Vh, selection: blocks of environments
+            for e0 in range(0, B, block):
+                Eb = min(block, B - e0)
+                sl = slice(e0, e0 + Eb)
+                Gb = Eb * n * P
+                cut = lambda s: OE.State({k: x[sl] for k, x in s.step.items()}, {k: x[sl] for k, x in s.env.items()})
+                wf = nets.GraphFeats(cfg, Gb, self.arena, "shw").compute_team_action_sweep(cut(st), cut(nst), a_pol[sl], us, vs)
+                mark(ev)
+                hw = None
+                if use_rnn:
+                    hw = self.arena.get("shw.h0", Gb * n, H)
+                    hw.view(Eb, n * P, n, H).copy_(cl0[sl].unsqueeze(1).expand(Eb, n * P, n, H))
+                vn = self.Vh.forward(wf, n_seq=Gb * n, T=1, h0=hw, tag="shw", train=False)["v"]
+                mark(ev)
+                K.shield_select(vn.view(Gb * n, nh), Vh_t[sl], a_pol[sl], us, vs, dt, alpha, margin, ro.action_tm[t][sl],
+                                log["index"][t][sl], log["flag"][t][sl], log["h"][t][sl])
+                mark(ev)
+            # 7. the step that counts
+            OE.step(cfg, st, ro.action_tm[t], nst, ro.reward_tm[t], ro.cost_tm[t])
+            mark(ev)
+            if ev is not None:
+                events.append(tuple(ev))
+        return ro, log
+
+    # ------------------------------------------------------------------------------------------------------------------
     # update
     # ------------------------------------------------------------------------------------------------------------------
     def cbf_weight_at(self, step: int) -> float:

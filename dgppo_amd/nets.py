@@ -162,6 +162,17 @@ class GraphFeats:
                                    self.Xo if self.n_other > 0 else None, self.efeat, self.emask, self.Fp, frame_max)
         return self
 
+    def compute_team_action_sweep(self, st, nst, a_pol, us, vs):
+        """features of the G = B * n * (1 + nv * nu) what-if graphs of one shielded step (dgppo_graph_feats_team_action_sweep):
+        `st` / `nst` are the dense states (ops_env.State, [B, ...] fields) before and after the provisional step, a_pol [B, n, 2]
+        the policy's actions; us / vs are ops_nn.sweep_axis tensors."""
+        if self.cfg.is_vmas:
+            raise ValueError("compute_team_action_sweep: VMASReverseTransport has no sweep entry point")
+        K.graph_feats_team_action_sweep(self.cfg, st.step["agent"], nst.step["agent"], st.env["goal"], st.env.get("obst"),
+                                        nst.step.get("hits"), a_pol, us, vs, self.Xa, self.Xo if self.n_other > 0 else None,
+                                        self.efeat, self.emask, self.Fp)
+        return self
+
     def compute_vmas(self, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time):
         """VMASReverseTransport: agent / body records through strides (floats), scene [B, 8] (dgppo_vmas_graph_feats)"""
         assert n_env * n_time == self.G

@@ -429,6 +429,100 @@ def graph_feats_action_sweep(cfg: N.EnvCfg, agent, agent_st, goal, obst, hits, h
     N.check(rc, "dgppo_graph_feats_action_sweep")
 
 
+def _dense(fn: str, name: str, t_, shape, dtype=torch.float32):
+    """a dense CUDA operand of exactly this shape"""
+    if not (torch.is_tensor(t_) and t_.is_cuda and t_.dtype == dtype and t_.is_contiguous()):
+        raise ValueError(f"{fn}: {name} must be a contiguous {dtype} CUDA tensor")
+    if tuple(t_.shape) != tuple(shape):
+        raise ValueError(f"{fn}: {name}: expected shape {tuple(shape)}, got {tuple(t_.shape)}")
+
+
+def _shield_axes(fn: str, us, vs):
+    for name, t_ in (("us", us), ("vs", vs)):
+        if not (torch.is_tensor(t_) and t_.is_cuda and t_.dtype == torch.float32 and t_.ndim == 1 and t_.is_contiguous()):
+            raise ValueError(f"{fn}: {name} must be a dense 1-D float32 CUDA tensor (sweep_axis)")
+        if t_.numel() == 0:
+            raise ValueError(f"{fn}: {name} is empty")
+    return int(us.numel()), int(vs.numel())
+
+
+def graph_feats_team_action_sweep(cfg: N.EnvCfg, agent, next_agent, goal, obst, next_hits, a_pol, us, vs, Xa, Xo, efeat, emask,
+                                  Fp):
+    """dgppo_graph_feats_team_action_sweep: the features of the G = B * n * P what-if graphs of one shielded step, P = 1 + nv * nu:
+    graph (e, i, p) is next_agent[e] with row i stepped from agent[e, i] by candidate p — a_pol[e, i] for p = 0, (us[iu], vs[iv])
+    for p = 1 + iv * nu + iu, clipped to [-1, 1] like every action.  All operands dense: agent / next_agent [B, n, sd], goal
+    [B, n_goals, sd], obst [B, n_obs, sd] (MPE kinds), next_hits [B, n, k, 2] (LiDAR kinds with obstacles), a_pol [B, n, 2].
+    Every refusal is raised before anything is launched."""
+    fn = "graph_feats_team_action_sweep"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no sweep entry point")
+    n, S, sd = cfg.n_agents, cfg.fan_in, cfg.state_dim
+    nu, nv = _shield_axes(fn, us, vs)
+    if not (torch.is_tensor(agent) and agent.ndim == 3):
+        raise ValueError(f"{fn}: agent must be a [B, n, state_dim] tensor")
+    B = int(agent.shape[0])
+    G = B * n * (1 + nu * nv)
+    n_other = cfg.num_nodes - 1 - n
+    _dense(fn, "agent", agent, (B, n, sd))
+    _dense(fn, "next_agent", next_agent, (B, n, sd))
+    _dense(fn, "goal", goal, (B, cfg.n_goals, sd))
+    _dense(fn, "a_pol", a_pol, (B, n, 2))
+    _dense(fn, "Xa", Xa, (G * n, Fp))
+    if n_other > 0:
+        _dense(fn, "Xo", Xo, (G * n_other, Fp))
+    _dense(fn, "efeat", efeat, (G * n, S, 4))
+    _dense(fn, "emask", emask, (G * n, S))
+    rec_hits = cfg.is_lidar and cfg.n_obs > 0
+    discs = (not cfg.is_lidar) and cfg.n_obs > 0
+    if rec_hits:
+        if next_hits is None:
+            raise ValueError(f"{fn}: next_hits is required for a LiDAR kind with obstacles")
+        _dense(fn, "next_hits", next_hits, (B, n, cfg.top_k, 2))
+    if discs:
+        if obst is None:
+            raise ValueError(f"{fn}: obst is required when n_obs > 0")
+        _dense(fn, "obst", obst, (B, cfg.n_obs, cfg.obst_stride))
+    null = C.c_void_p(0)
+    rc = N.lib().dgppo_graph_feats_team_action_sweep(
+        C.byref(cfg), _p(agent, "agent"), _p(next_agent, "next_agent"), _p(goal, "goal"), _p(obst, "obst") if discs else null,
+        _p(next_hits, "next_hits") if rec_hits else null, _p(a_pol, "a_pol"), C.c_int32(B), _p(us, "us"), C.c_int32(nu),
+        _p(vs, "vs"), C.c_int32(nv), _p(Xa, "Xa"), _p(Xo, "Xo") if n_other > 0 else null, _p(efeat, "efeat"), _p(emask, "emask"),
+        C.c_int32(Fp), N.stream_ptr())
+    N.check(rc, "dgppo_graph_feats_team_action_sweep")
+
+
+def shield_select(Vh_next, Vh_t, a_pol, us, vs, dt: float, alpha: float, margin: float, action, index, flag, h=None):
+    """dgppo_shield_select on a block of E environments: Vh_next [E * n * P * n, nh] (the Vh forward of the team sweep's graphs,
+    P = 1 + nv * nu), Vh_t [E, n, nh], a_pol [E, n, 2] -> action [E, n, 2], index / flag [E, n] int32 and, if given,
+    h [E, n, P].  The rule is stated next to the declaration in include/dgppo_hip.h."""
+    fn = "shield_select"
+    nu, nv = _shield_axes(fn, us, vs)
+    P = 1 + nu * nv
+    if not (torch.is_tensor(Vh_t) and Vh_t.ndim == 3):
+        raise ValueError(f"{fn}: Vh_t must be a [E, n, n_cost] tensor")
+    E, n, nh = (int(s) for s in Vh_t.shape)
+    if n < 1 or nh < 1:
+        raise ValueError(f"{fn}: Vh_t must have at least one agent and one cost component")
+    for name, v in (("dt", dt), ("alpha", alpha), ("margin", margin)):
+        if not np.isfinite(float(v)):
+            raise ValueError(f"{fn}: {name} must be finite")
+    if not float(dt) > 0.0:
+        raise ValueError(f"{fn}: dt must be > 0")
+    _dense(fn, "Vh_t", Vh_t, (E, n, nh))
+    _dense(fn, "Vh_next", Vh_next, (E * n * P * n, nh))
+    _dense(fn, "a_pol", a_pol, (E, n, 2))
+    _dense(fn, "action", action, (E, n, 2))
+    _dense(fn, "index", index, (E, n), torch.int32)
+    _dense(fn, "flag", flag, (E, n), torch.int32)
+    if h is not None:
+        _dense(fn, "h", h, (E, n, P))
+    rc = N.lib().dgppo_shield_select(
+        _p(Vh_next, "Vh_next"), _p(Vh_t, "Vh_t"), _p(a_pol, "a_pol"), C.c_int32(E), C.c_int32(n), C.c_int32(nh), _p(us, "us"),
+        C.c_int32(nu), _p(vs, "vs"), C.c_int32(nv), C.c_float(float(dt)), C.c_float(float(alpha)), C.c_float(float(margin)),
+        _p(action, "action"), _p(index, "index", torch.int32), _p(flag, "flag", torch.int32), _p(h, "h"), N.stream_ptr())
+    N.check(rc, "dgppo_shield_select")
+
+
 def vmas_graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time,
                      Xa, efeat, emask, Fp):
     """dgppo_vmas_graph_feats: graph_feats for VMASReverseTransport (agent [.., n, 4] and body [.., 4] records addressed

@@ -55,6 +55,23 @@ class CostLandscape(NamedTuple):
         return np.asarray(self.cost)[:, :, :, int(self.agent), :].max(axis=-1)
 
 
+class ShieldLog(NamedTuple):
+    """What the barrier shield did in the episodes of `DGPPO.collect_shielded`, env-major like the Rollout next to it.  The
+    candidates of an agent are its policy action (index 0) and the grid points (us[iu], vs[iv]) (index 1 + iv * nu + iu);
+    h = max_c ((Vh_next - Vh) / dt + alpha * Vh) on the agent's own row, admissible where h <= -margin."""
+    policy_action: np.ndarray   # [B, T, n, 2]: what the policy wanted
+    action: np.ndarray          # [B, T, n, 2]: what was executed (the Rollout's actions)
+    index: np.ndarray           # [B, T, n] int32: the candidate executed
+    flag: np.ndarray            # [B, T, n] int32: 0 kept, 1 replaced by an admissible candidate, 2 nothing admissible
+    h: np.ndarray               # [B, T, n, P]: the barrier value of every candidate, P = 1 + nv * nu
+    Vh: np.ndarray              # [B, T, n, n_cost]: Vh of the graph of step t
+    us: np.ndarray              # [nu] fp32 grid lines of the first action component
+    vs: np.ndarray              # [nv] of the second
+    margin: float
+    alpha: float
+    dt: float
+
+
 class ActionLandscape(NamedTuple):
     """The discrete control barrier condition of DGPPO (dgppo/algo/dgppo.py:246-250) with one agent's action swept over a grid
     in frames of an episode (`DGPPO.action_landscape`): cbf = (Vh_next - Vh) / dt + alpha * Vh, where Vh_next is the learned

@@ -126,3 +126,20 @@ def action_admissibility(A) -> Dict[str, np.ndarray]:
     return dict(points=points, admitted=admitted, taken=taken, empty_frames=empty,
                 admissible_frac=float(admitted.sum() / max(int(points.sum()), 1)), empty_frac=float(empty.size / max(F, 1)),
                 taken_admitted_frac=float((taken == 1).sum() / max(int((taken >= 0).sum()), 1)))
+
+
+def shield_stats(log) -> Dict[str, np.ndarray]:
+    """What the barrier shield did per episode (trainer.data.ShieldLog, arrays [B, T, n, ...]), each [B]:
+    `intervention_frac` — the share of (step, agent) pairs whose action was replaced (flag != 0), `infeasible_frac` — the share
+    in which the barrier admitted no candidate (flag == 2), `mean_deviation` — the mean over (step, agent) of the Euclidean
+    distance |a_shield - a_pol| between the executed action and the policy's, both clipped as the environment clips them."""
+    flag = np.asarray(log.flag)
+    if flag.ndim != 3:
+        raise ValueError(f"shield_stats: flag must be [B, T, n], got shape {flag.shape}")
+    a, p = np.asarray(log.action, dtype=np.float64), np.asarray(log.policy_action, dtype=np.float64)
+    if a.shape != flag.shape + (2,) or p.shape != a.shape:
+        raise ValueError(f"shield_stats: action {a.shape} / policy_action {p.shape} do not fit flag {flag.shape}")
+    B = flag.shape[0]
+    dev = np.sqrt(((np.clip(a, -1.0, 1.0) - np.clip(p, -1.0, 1.0)) ** 2).sum(axis=-1))
+    return dict(intervention_frac=(flag != 0).reshape(B, -1).mean(axis=1), infeasible_frac=(flag == 2).reshape(B, -1).mean(axis=1),
+                mean_deviation=dev.reshape(B, -1).mean(axis=1))

@@ -384,6 +384,31 @@ int32_t dgppo_graph_feats_action_sweep(const dgppo_env_cfg* cfg, const float* ag
                                        int32_t n_frames, int32_t agent_id, const float* us, int32_t nu, const float* vs,
                                        int32_t nv, float* Xa, float* Xo, float* efeat, float* emask, int32_t Fp, void* stream);
 
+/* The same what-if graphs for a barrier shield, for EVERY agent of n_env environments in one launch: graph
+ * g = (e*n + i)*P + p, P = 1 + nv*nu, is the graph of next_agent[e] (the state after a provisional step) in which row i is
+ * agent_step_euler(row i of agent[e], clip_action(candidate p)) (env/base.py:84-86, lidar_env/base.py:146-149,
+ * lidar_bicycle_target.py:95-107) and every other agent keeps its provisional next state; candidate 0 is a_pol[e, i], candidate
+ * 1 + iv*nu + iu is (us[iu], vs[iv]).  All operands are dense: agent / next_agent [n_env, n, sd], goal [n_env, n_goals, sd],
+ * obst [n_env, n_obs, sd] (MPE discs; may be NULL for a LiDAR kind), next_hits [n_env, n, k, 2] (LiDAR kinds with obstacles; NULL
+ * otherwise: nothing is cast, the next position does not depend on the action), a_pol [n_env, n, 2].  Outputs:
+ * dgppo_graph_feats' layout and arithmetic (get_graph, lidar_env/base.py:227-271) for the G = n_env*n*P graphs — what the
+ * constraint-value net reads to evaluate cbf_deriv (dgppo/algo/dgppo.py:246-250) per agent and candidate.  nu, nv >= 1.    */
+int32_t dgppo_graph_feats_team_action_sweep(const dgppo_env_cfg* cfg, const float* agent, const float* next_agent,
+                                            const float* goal, const float* obst, const float* next_hits, const float* a_pol,
+                                            int32_t n_env, const float* us, int32_t nu, const float* vs, int32_t nv, float* Xa,
+                                            float* Xo, float* efeat, float* emask, int32_t Fp, void* stream);
+
+/* The shield's choice among those candidates, per (env e, agent i) on the agent's own row: h[e, i, p] = max_c ((Vh_next[e, i, p,
+ * i, c] - Vh_t[e, i, c]) / dt + alpha * Vh_t[e, i, c]), the left-hand side of the barrier condition dgppo/algo/dgppo.py:246-250
+ * (NaN-propagating max).  Vh_next [n_env, n, P, n, n_cost], Vh_t [n_env, n, n_cost], a_pol [n_env, n, 2].  A candidate is
+ * admissible iff h <= -margin (never a NaN).  Candidate 0 is kept if admissible (flag 0); else the admissible candidate nearest
+ * to it — du*du + dv*dv in fp32 on clipped actions, lowest index on ties (flag 1); else the smallest h, lowest index on ties,
+ * NaN skipped, candidate 0 when every h is NaN (flag 2).  action [n_env, n, 2] is the chosen candidate clipped to [-1, 1],
+ * index / flag [n_env, n] int32, h [n_env, n, P] (may be NULL).  The reference ships no runtime filter.                     */
+int32_t dgppo_shield_select(const float* Vh_next, const float* Vh_t, const float* a_pol, int32_t n_env, int32_t n_agents,
+                            int32_t n_cost, const float* us, int32_t nu, const float* vs, int32_t nv, float dt, float alpha,
+                            float margin, float* action, int32_t* index, int32_t* flag, float* h, void* stream);
+
 /* GraphTransformer attention in fixed-fan-in form (dgppo/nn/gnn.py:85-117; jraph.segment_softmax/segment_sum):
  * qt [G*n,H*F] = x_i Mcat + cvec (a Dense), logits = qt . x_sender, masked softmax over the S slots of each agent,
  * zcat [G*n,Kp] = [x_i | per head: sum a x_s (F), sum a e (4) | 1 | 0...], attn [G*n,S,H] saved for backward (NULL in

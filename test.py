@@ -13,7 +13,10 @@ the truly unsafe set the net misses.  `--action-landscape AGENT` sweeps that age
 grid of [-1, 1]^2 in every frame and evaluates the discrete barrier condition the policy is trained under
 (`DGPPO.action_landscape`): `{stamp}_{name}_action.npz`, an inset in the animation, and a line per episode saying how much of
 the action square the learned barrier admits, in how many frames it admits nothing, and how often the action taken lies
-inside."""
+inside.  `--shield` runs the episodes with the learned barrier as a runtime filter (`DGPPO.collect_shielded`): every agent's
+action is kept where the barrier admits it and otherwise replaced by the nearest admissible action of a `--shield-grid`-squared
+grid of [-1, 1]^2 (`--shield-margin M`: admissible means cbf_deriv <= -M).  Every line and file then describes the shielded
+episodes; one more line per episode says how often the shield stepped in, and `{stamp}_{name}_shield.npz` holds its log."""
 import argparse
 import datetime
 import os
@@ -51,7 +54,10 @@ def test(args):
     keys = np.random.default_rng([args.seed, 13]).integers(1, 2 ** 62, size=1000)[:args.epi][args.offset:]
     if len(keys) == 0:
         raise SystemExit("no episodes to run (--epi / --offset)")
-    if args.stochastic:
+    shield_log = None
+    if args.shield:
+        ro, shield_log = algo.collect_shielded(keys, env=env, grid=args.shield_grid, margin=args.shield_margin)
+    elif args.stochastic:
         ro = algo.collect_stochastic(keys, env=env)
     else:
         ro = algo.collect_deterministic(keys, env=env)
@@ -63,10 +69,17 @@ def test(args):
     print(f"reward: {agg['reward']:.3f}, min/max reward: {agg['reward_min']:.3f}/{agg['reward_max']:.3f}, "
           f"cost: {agg['cost']:.3f}, min/max cost: {agg['cost_min']:.3f}/{agg['cost_max']:.3f}, "
           f"safe_rate: {agg['safe_mean'] * 100:.3f}%")
+    if shield_log is not None:
+        sh = EV.shield_stats(shield_log)
+        for i in range(len(keys)):
+            print(f"epi: {i}, shield: stepped in for {sh['intervention_frac'][i] * 100:.3f}% of the actions (intervention_frac), "
+                  f"found nothing admissible for {sh['infeasible_frac'][i] * 100:.3f}% (infeasible_frac), moved the action by "
+                  f"{sh['mean_deviation'][i]:.4f} on average (mean_deviation)")
     if args.log:
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(EV.csv_line(env, args.epi, agg))
-    if not args.no_video or args.landscape is not None or args.cost_landscape is not None or args.action_landscape is not None:
+    if (not args.no_video or args.landscape is not None or args.cost_landscape is not None or args.action_landscape is not None
+            or shield_log is not None):
         videos_dir = pathlib.Path(args.path) / "videos" / f"{step}"
         videos_dir.mkdir(exist_ok=True, parents=True)
         stamp = datetime.datetime.now().strftime("%m%d-%H%M")
@@ -75,6 +88,12 @@ def test(args):
             name = (f"n{num_agents}_epi{i:02}_reward{stats['reward'][i]:.3f}_cost{stats['cost'][i]:.3f}"
                     f"_sr{stats['safe_rate'][i] * 100:.0f}")
             extra = {}
+            if shield_log is not None:
+                out = videos_dir / f"{stamp}_{name}_shield.npz"
+                per_epi = {k: getattr(shield_log, k)[i] for k in ("policy_action", "action", "index", "flag", "h", "Vh")}
+                np.savez(out, us=shield_log.us, vs=shield_log.vs, margin=shield_log.margin, alpha=shield_log.alpha,
+                         dt=shield_log.dt, **per_epi, **{k: v[i] for k, v in sh.items()})
+                print(f"shield: {out}")
             if args.landscape is not None:
                 land = algo.vh_landscape(ro, i, args.landscape, nx=args.landscape_grid, ny=args.landscape_grid)
                 out = videos_dir / f"{stamp}_{name}_landscape.npz"
@@ -125,12 +144,15 @@ FLAGS = [
 COST_FLAGS = [(("--cost-landscape",), "int", None)]
 # the barrier condition over one agent's actions (DGPPO.action_landscape), --landscape-grid squared, per episode
 ACTION_FLAGS = [(("--action-landscape",), "int", None)]
+# the learned barrier as a runtime filter on every agent's action (DGPPO.collect_shielded): an N x N grid of replacement actions,
+# admissible where cbf_deriv <= -M
+SHIELD_FLAGS = [(("--shield",), "flag", False), (("--shield-grid",), "int", 8), (("--shield-margin",), "float", 0.0)]
 
 
 def build_parser() -> argparse.ArgumentParser:
-    types = {"int": int, "str": str}
+    types = {"int": int, "str": str, "float": float}
     ap = argparse.ArgumentParser(description=__doc__)
-    for names, kind, default in FLAGS + COST_FLAGS + ACTION_FLAGS:
+    for names, kind, default in FLAGS + COST_FLAGS + ACTION_FLAGS + SHIELD_FLAGS:
         if kind == "flag":
             ap.add_argument(*names, action="store_true", default=False)
         elif kind.startswith("req:"):
@@ -144,6 +166,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.cpu:
         raise SystemExit("--cpu: this build has no CPU product path (the HIP library is required)")
+    if args.shield and args.stochastic:
+        raise SystemExit("--shield --stochastic: the shield filters the deterministic policy; drop one of the two flags")
     return test(args)
 
 
