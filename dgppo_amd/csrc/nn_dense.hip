@@ -6,6 +6,7 @@
 // jax.grad of those (dgppo/algo/informarl.py:377,440; dgppo/algo/dgppo.py:316).
 // fp32-input MFMA is bit-for-bit a k-ordered fmaf chain (exact fp32, no reduced precision).
 #include "common.h"
+#include "nn_gru.h"
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 #ifdef DGPPO_STAMPS
@@ -402,6 +403,10 @@ struct DenseBwdWArgs {
   float* part;        // scratch for per-workgroup partials [grid][part_stride], or NULL: atomicAdd straight into dW/db
   int part_stride;    // >= K*N + N
   size_t ws_bytes;    // size of the caller's scratch buffer behind `part`
+  // dense_bwd_xw only (the DX kernels): the input gradient of the same Dense from the same pass
+  const float* W; int ldwp;   // [K,N] parameters
+  float* dX; int lddx;        // [M,K]: dX = dY W^T, or with acc_mask: dX = (X > 0) ? dX + dY W^T : 0
+  int acc_mask;
 };
 
 // A workgroup owns a contiguous chunk of rows and walks it in tiles of 32.  X[32,K] and dY[32,N] tiles live in LDS
@@ -418,8 +423,17 @@ struct DenseBwdWArgs {
 // rows_per_block rows and its own pair of LDS tile buffers; they walk their chunks in step (the barrier is the workgroup's),
 // add their accumulators through the tile LDS once the chunks are done, and group 0 writes the workgroup's ONE slab: a
 // CU that kept NG resident workgroups busy wrote NG slabs for the second stage to read back.
+// DX: the same pass also forms dX[32,K] = dY W^T of every tile (dgppo_dense_bwd_xw; K = KT*16 and N = NT*16 exactly, 16-byte
+// aligned operands: the launcher's condition).  The product runs per wave on its output column tiles x both
+// 16-row tiles, reduction over n - kt counted from the LAST wave (kt = 3 - w, 7 - w, ...), so that with KT = 9 the wave that
+// has three row tiles of dW has two column tiles of dX and the other way round: five products on the longest wave, not six.
+// W^T stays in registers for the whole launch (KTW * NT float4 per lane); the dY operand is
+// read from memory again in the MFMA A layout (lane (li, lq) = row li, the four columns 16s + 4lq ..: one float4 per 16
+// columns, the k-steps taking n in that order on both operands) - the rows were just fetched for the LDS tile, so these are
+// cache hits, and a column walk of the row-major LDS tile would be an 8-way bank conflict.  The ReLU mask of the `+=` form is
+// X itself: the LDS tile.
 #define BW_ROWS 32
-template <int NT, int KT, int NG>
+template <int NT, int KT, int NG, bool DX = false>
 __global__ void __launch_bounds__(256 * NG) dense_bwd_w_kernel(DenseBwdWArgs a) {
   extern __shared__ float sm_wg[];
   constexpr int KTW = (KT + 3) / 4;
@@ -451,6 +465,72 @@ __global__ void __launch_bounds__(256 * NG) dense_bwd_w_kernel(DenseBwdWArgs a) 
   float4 pfx[PFX], pfy[PFY], csum[PFY];
 #pragma unroll
   for (int u = 0; u < PFY; ++u) csum[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+  // DX: B[kk = lq][j = li] of k-step (s, e) = W[kt*16 + li][16 s + 4 lq + e]; A of the same step = dY[row li][16 s + 4 lq + e]
+  float4 wreg[DX ? KTW : 1][DX ? NT : 1], ya[DX ? 2 : 1][DX ? NT : 1];
+  if constexpr (DX) {
+#pragma unroll
+    for (int i = 0; i < KTW; ++i) {
+      int kt = (3 - wave) + 4 * i;
+      kt = kt < KT ? kt : KT - 1;
+#pragma unroll
+      for (int s = 0; s < NT; ++s)
+        wreg[i][s] = *reinterpret_cast<const float4*>(a.W + (size_t)(kt * 16 + li) * a.ldwp + 16 * s + 4 * lq);
+    }
+  }
+  auto fetch_a = [&](int m0) {          // DX: the dY rows of tile m0 in the A layout (rows clamped; stores are masked)
+    if constexpr (DX) {
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) {
+        int row = m0 + mt * 16 + li;
+        row = row < a.M ? row : a.M - 1;
+#pragma unroll
+        for (int s = 0; s < NT; ++s) ya[mt][s] = *reinterpret_cast<const float4*>(a.dY + (size_t)row * a.ldy + 16 * s + 4 * lq);
+      }
+    }
+  };
+  auto dx_tile = [&](int m0, int b) {   // DX: dX rows m0 .. m0+31 (C/D layout: col = li, row = lq * 4 + reg); b = the X tile's buffer
+    if constexpr (DX) {
+      const float* xs = sm + b * BUF;
+#pragma unroll
+      for (int i = 0; i < KTW; ++i) {
+        const int kt = (3 - wave) + 4 * i;
+        if (kt >= KT) continue;
+        const int col = kt * 16 + li;
+        float old[2][4];
+        if (a.acc_mask) {
+#pragma unroll
+          for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              int row = m0 + mt * 16 + lq * 4 + r;
+              row = row < m_end ? row : m_end - 1;
+              old[mt][r] = a.dX[(size_t)row * a.lddx + col];
+            }
+        }
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+          f32x4 dx = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int s = 0; s < NT; ++s) {
+            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[mt][s].x, wreg[i][s].x, dx, 0, 0, 0);
+            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[mt][s].y, wreg[i][s].y, dx, 0, 0, 0);
+            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[mt][s].z, wreg[i][s].z, dx, 0, 0, 0);
+            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[mt][s].w, wreg[i][s].w, dx, 0, 0, 0);
+          }
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const int rl = mt * 16 + lq * 4 + r;
+            float v = dx[r];
+            if (a.acc_mask) {
+              v += old[mt][r];
+              v = (xs[rl * Kl + col] > 0.0f) ? v : 0.0f;
+            }
+            if (m0 + rl < m_end) a.dX[(size_t)(m0 + rl) * a.lddx + col] = v;
+          }
+        }
+      }
+    }
+  };
 
   auto fetch = [&](int m0) {            // global -> registers (rows clamped; masking happens in commit)
 #pragma unroll
@@ -527,16 +607,19 @@ __global__ void __launch_bounds__(256 * NG) dense_bwd_w_kernel(DenseBwdWArgs a) 
   };
 #define DGPPO_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
   float colsum = 0.0f;                  // scalar path only
-  if (vec) {
+  // DX has no scalar path (it would form no dX): the host launches it only where bwd_w_vec() holds, which is `vec`
+  if (DX || vec) {
     fetch(m_begin);
     commit(m_begin, 0);
     __syncthreads();
     int cur = 0;
     for (int it = 0, m0 = m_begin; it < n_tiles; ++it, m0 += BW_ROWS) {
+      fetch_a(m0);
       fetch(m0 + BW_ROWS);                                     // past m_end on the last round: masked to zeros in commit
       __builtin_amdgcn_sched_barrier(0);
       compute(cur);
       commit(m0 + BW_ROWS, cur ^ 1);
+      dx_tile(m0, cur);                                        // reads X's tile (the mask) before the barrier frees it
       DGPPO_LDS_BARRIER();
       cur ^= 1;
     }
@@ -752,20 +835,22 @@ constexpr int bwd_w_groups() {
   return (!xch || fit < 2) ? 1 : (fit > 4 ? 4 : fit);
 }
 
-template <int NT, int KT>
+// NGX: group count given by the caller (the DX sites, kXwSites below); 0 = what the tile buffers allow
+template <int NT, int KT, bool DX = false, int NGX = 0>
 static void launch_bwd_w_kt(DenseBwdWArgs a, hipStream_t s) {
   constexpr int Kl = (KT & 1) ? KT * 16 : KT * 16 + 16;
   constexpr int Nl = (NT & 1) ? NT * 16 : NT * 16 + 16;
   constexpr size_t smem = 2 * sizeof(float) * BW_ROWS * (Kl + Nl);
-  constexpr int NG = bwd_w_groups<NT, KT>();
+  constexpr int NG = NGX > 0 ? NGX : bwd_w_groups<NT, KT>();
+  static_assert(NG <= bwd_w_groups<NT, KT>(), "dense_bwd_w: more groups than the tile buffers and their exchange allow");
   static_assert(smem * NG <= 160 * 1024, "dense_bwd_w tiles exceed the 160 KB LDS of a gfx950 CU");
   static thread_local bool opted = false;
   if (!opted) {
     if (smem > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_w_kernel<NT, KT, 1>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_w_kernel<NT, KT, 1, DX>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (NG > 1 && smem * NG > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_w_kernel<NT, KT, NG>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_w_kernel<NT, KT, NG, DX>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(smem * NG));
     opted = true;
   }
@@ -789,8 +874,8 @@ static void launch_bwd_w_kt(DenseBwdWArgs a, hipStream_t s) {
   a.part = ws;
   a.part_stride = stride;
   const int grid = cdiv(a.M, rpb * ng);
-  if (NG > 1 && ng > 1) hipLaunchKernelGGL((dense_bwd_w_kernel<NT, KT, NG>), dim3(grid), dim3(256 * NG), smem * NG, s, a);
-  else hipLaunchKernelGGL((dense_bwd_w_kernel<NT, KT, 1>), dim3(grid), dim3(256), smem, s, a);
+  if (NG > 1 && ng > 1) hipLaunchKernelGGL((dense_bwd_w_kernel<NT, KT, NG, DX>), dim3(grid), dim3(256 * NG), smem * NG, s, a);
+  else hipLaunchKernelGGL((dense_bwd_w_kernel<NT, KT, 1, DX>), dim3(grid), dim3(256), smem, s, a);
   if (ws) reduce_or_defer(s, ws, stride, grid, a.dW, a.ldw, a.db, a.K, a.N);
 }
 
@@ -937,6 +1022,57 @@ int32_t dense_bwd_w_launch(DenseBwdWArgs a, hipStream_t s) {
   return 0;
 }
 
+// ---- input and weight gradient of a Dense from one pass (dgppo_dense_bwd_xw) ---------------------------------------------
+// THE place that chooses between the fused kernel and the pair (dense_bwd_w, then dense_fwd with W^T): shape and alignment
+// only.  The shapes are GNN glue Denses of the networks, each moved here after a measured per-call gain at 131 072 rows
+// (profiles/README.md, round 7); everything else runs the pair, the `+=` site K = 32, N = 96 included (its KT = 2 gives two of
+// a group's four waves nothing to multiply: 56.8 us fused against 54.7 us for the pair).
+// The sites, in ONE table: shape, its tiles, and the groups per CU - at most 2, so that a lane keeps 256 registers for W^T and
+// the dY operand next to the accumulators; 48 x 32 needs 114 and keeps the 4 of dense_bwd_w (27.6 -> 25.4 us at 131 072 rows).
+struct XwSite { int K, N, NT, KT, NG; };
+constexpr XwSite kXwSites[] = {{144, 64, 4, 9, 2}, {48, 32, 2, 3, 4}, {48, 64, 4, 3, 2}};
+constexpr int kXwSiteCount = sizeof(kXwSites) / sizeof(kXwSites[0]);
+
+// what dense_bwd_w_kernel calls `vec`: the fused form exists only on the 16-byte staging path (its scalar path forms no dX)
+static bool bwd_w_vec(const DenseBwdWArgs& a) {
+  return (a.K & 3) == 0 && (a.ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(a.X) & 15) == 0 && (a.N & 3) == 0 && (a.ldy & 3) == 0 &&
+         (reinterpret_cast<uintptr_t>(a.dY) & 15) == 0;
+}
+
+static bool bwd_xw_fused(const DenseBwdWArgs& a) {
+  bool site = false;
+  for (int i = 0; i < kXwSiteCount; ++i) site = site || (a.K == kXwSites[i].K && a.N == kXwSites[i].N);
+  const uintptr_t p = reinterpret_cast<uintptr_t>(a.W) | reinterpret_cast<uintptr_t>(a.dX);
+  return site && a.N <= 192 && bwd_w_vec(a) && ((a.ldwp | a.lddx) & 3) == 0 && (p & 15) == 0;
+}
+
+template <int I>
+static void launch_xw_site(const DenseBwdWArgs& a, hipStream_t s) {
+  if constexpr (I < kXwSiteCount) {
+    constexpr XwSite S = kXwSites[I];
+    static_assert(S.K == S.KT * 16 && S.N == S.NT * 16, "dense_bwd_xw: a site is whole 16-wide tiles (W^T and dY fragments are unguarded)");
+    if (a.K == S.K && a.N == S.N) launch_bwd_w_kt<S.NT, S.KT, true, S.NG>(a, s);
+    else launch_xw_site<I + 1>(a, s);
+  }
+}
+
+static int32_t dense_bwd_xw_launch(DenseBwdWArgs a, hipStream_t s) {
+  DGPPO_REQUIRE(a.M >= 0 && a.K >= 1 && a.N >= 1, "dense_bwd_xw: bad shape");
+  DGPPO_REQUIRE(a.X && a.dY && a.dW && a.W && a.dX, "dense_bwd_xw: NULL operand");
+  DGPPO_REQUIRE(a.ldx >= a.K && a.ldy >= a.N && a.ldw >= a.N && a.ldwp >= a.N && a.lddx >= a.K,
+                "dense_bwd_xw: leading dimensions too small");
+  if (a.M == 0) return 0;
+  if (!bwd_xw_fused(a)) {
+    const int32_t rc = dense_bwd_w_launch(a, s);
+    if (rc) return rc;
+    DenseArgs f{a.dY, a.ldy, a.W, a.ldwp, nullptr, a.dX, a.lddx, a.M, a.N, a.K, 0, a.acc_mask, 1, a.acc_mask ? a.X : nullptr, a.ldx};
+    return dense_fwd_launch(f, s);
+  }
+  launch_xw_site<0>(a, s);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---- GRU weight gradients in one pass ------------------------------------------------------------------------------------
 //   dWi[64,192] += x^T dgi               dbi[192] += colsum(dgi)
 //   dWh[64,192] += hprev^T [dgi[:, :128] | dhn]      dbhn[64] += colsum(dhn)      (hr / hz carry no bias)
@@ -965,8 +1101,18 @@ struct GruBwdWArgs {
   float* dbhn;
   int M, rows_per_block;
   float* part;            // [grid][GW_SLAB] or NULL: atomicAdd straight into the outputs
+  // T1 only (hprev is h0; dgi / dhn above are unused): the gate gradients are formed here
+  const float* dhs;       // [M,64] dense
+  const float* gates;     // [M,256] dense (r | z | n | hn)
+  float* dgi_out;         // [M,192] dense
 };
 
+// T1: the one-step GRU backward inside the pass.  With T = 1 the scan (gru_bwd_kernel) is elementwise in (dhs, gates, h0), so
+// the [dgi | dhn] tile is formed on chip instead of being written by the scan and read back: thread (row tid/16, column quad
+// tid%16) loads d, h0, r, z, n, hn of its four columns once (six 16-byte loads), forms all four gradient quads with
+// gru_gate_grad (the scan's expressions: the same bits), stages them and stores dgi's three for the trunk's backward.  dhn
+// never reaches memory.  The MFMA loop, the slabs and the epilogue are the same code.
+template <bool T1>
 __global__ void __launch_bounds__(512) gru_bwd_w_kernel(GruBwdWArgs a) {
   extern __shared__ float sm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = (tid >> 6) & 3, half = tid >> 8;
@@ -978,9 +1124,13 @@ __global__ void __launch_bounds__(512) gru_bwd_w_kernel(GruBwdWArgs a) {
   for (int t = 0; t < 12; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
   // float4 slots of a tile: [x | hprev] 32 rows x 32 quads (2 per thread), [dgi | dhn] 32 rows x 64 quads (4 per thread);
   // a thread's four [dgi | dhn] slots are the SAME column quad (512 = 8 rows x 64 quads), so one float4 carries its column sums
-  float4 pfa[2], pfy[4];
-  float4 csum = make_float4(0.f, 0.f, 0.f, 0.f);
+  // T1: one (row, column quad) per thread; pfy = d, h0, r, z, n, hn and one column-sum quad per block of [dgi | dhn]
+  float4 pfa[2], pfy[T1 ? 6 : 4];
+  float4 csum[T1 ? 4 : 1];
+#pragma unroll
+  for (int u = 0; u < (T1 ? 4 : 1); ++u) csum[u] = make_float4(0.f, 0.f, 0.f, 0.f);
   const int qa = tid & 31, ra = tid >> 5, qy = tid & 63, ry = tid >> 6;
+  const int q1 = tid & 15, r1 = tid >> 4;
   auto fetch = [&](int m0) {            // rows clamped; masking happens in commit
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -989,12 +1139,22 @@ __global__ void __launch_bounds__(512) gru_bwd_w_kernel(GruBwdWArgs a) {
       const float* src = qa < 16 ? a.x + (size_t)row * a.ldx + 4 * qa : a.hprev + (size_t)row * a.ldh + 4 * (qa - 16);
       pfa[u] = *reinterpret_cast<const float4*>(src);
     }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      int row = m0 + u * 8 + ry;
+    if constexpr (T1) {
+      int row = m0 + r1;
       row = row < a.M ? row : a.M - 1;
-      const float* src = qy < 48 ? a.dgi + (size_t)row * 192 + 4 * qy : a.dhn + (size_t)row * 64 + 4 * (qy - 48);
-      pfy[u] = *reinterpret_cast<const float4*>(src);
+      pfy[0] = *reinterpret_cast<const float4*>(a.dhs + (size_t)row * 64 + 4 * q1);
+      pfy[1] = *reinterpret_cast<const float4*>(a.hprev + (size_t)row * a.ldh + 4 * q1);
+      const float* gs = a.gates + (size_t)row * 256 + 4 * q1;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) pfy[2 + g] = *reinterpret_cast<const float4*>(gs + 64 * g);
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        int row = m0 + u * 8 + ry;
+        row = row < a.M ? row : a.M - 1;
+        const float* src = qy < 48 ? a.dgi + (size_t)row * 192 + 4 * qy : a.dhn + (size_t)row * 64 + 4 * (qy - 48);
+        pfy[u] = *reinterpret_cast<const float4*>(src);
+      }
     }
   };
   auto commit = [&](int m0, int b) {    // registers -> LDS buffer b; rows >= m_end become zeros
@@ -1006,12 +1166,34 @@ __global__ void __launch_bounds__(512) gru_bwd_w_kernel(GruBwdWArgs a) {
       const float4 v = (m0 + r < m_end) ? pfa[u] : make_float4(0.f, 0.f, 0.f, 0.f);
       *reinterpret_cast<float4*>(as + r * GW_AL + 4 * qa) = v;
     }
+    if constexpr (T1) {
+      const bool in = m0 + r1 < m_end;
+      // the scan's d = dh + dhs with its zero-initialised dh
+      const GruGateGrad g0 = gru_gate_grad(gru_zero_carry(pfy[0].x), pfy[1].x, pfy[2].x, pfy[3].x, pfy[4].x, pfy[5].x);
+      const GruGateGrad g1 = gru_gate_grad(gru_zero_carry(pfy[0].y), pfy[1].y, pfy[2].y, pfy[3].y, pfy[4].y, pfy[5].y);
+      const GruGateGrad g2 = gru_gate_grad(gru_zero_carry(pfy[0].z), pfy[1].z, pfy[2].z, pfy[3].z, pfy[4].z, pfy[5].z);
+      const GruGateGrad g3 = gru_gate_grad(gru_zero_carry(pfy[0].w), pfy[1].w, pfy[2].w, pfy[3].w, pfy[4].w, pfy[5].w);
+      float4 v[4] = {make_float4(g0.dar, g1.dar, g2.dar, g3.dar), make_float4(g0.daz, g1.daz, g2.daz, g3.daz),
+                     make_float4(g0.dan, g1.dan, g2.dan, g3.dan), make_float4(g0.dhn, g1.dhn, g2.dhn, g3.dhn)};
+      if (in) {
+        float* o = a.dgi_out + (size_t)(m0 + r1) * 192 + 4 * q1;
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int r = u * 8 + ry;
-      const float4 v = (m0 + r < m_end) ? pfy[u] : make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(ys + r * GW_YL + 4 * qy) = v;
-      csum.x += v.x; csum.y += v.y; csum.z += v.z; csum.w += v.w;
+        for (int g = 0; g < 3; ++g) *reinterpret_cast<float4*>(o + 64 * g) = v[g];
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        if (!in) v[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(ys + r1 * GW_YL + 64 * g + 4 * q1) = v[g];
+        csum[g].x += v[g].x; csum[g].y += v[g].y; csum[g].z += v[g].z; csum[g].w += v[g].w;
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int r = u * 8 + ry;
+        const float4 v = (m0 + r < m_end) ? pfy[u] : make_float4(0.f, 0.f, 0.f, 0.f);
+        *reinterpret_cast<float4*>(ys + r * GW_YL + 4 * qy) = v;
+        csum[0].x += v.x; csum[0].y += v.y; csum[0].z += v.z; csum[0].w += v.w;
+      }
     }
   };
   auto compute = [&](int b) {
@@ -1059,14 +1241,19 @@ __global__ void __launch_bounds__(512) gru_bwd_w_kernel(GruBwdWArgs a) {
       }
     }
   }
-  // column sums: red[row slot 0..7][256 columns] through LDS (the tile buffers are idle now)
+  // column sums: red[row slot 0..7 (T1: 0..31)][256 columns] through LDS (the tile buffers are idle now)
   __syncthreads();
-  *reinterpret_cast<float4*>(sm + ry * 256 + 4 * qy) = csum;
+  if constexpr (T1) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) *reinterpret_cast<float4*>(sm + r1 * 256 + 64 * g + 4 * q1) = csum[g];
+  } else {
+    *reinterpret_cast<float4*>(sm + ry * 256 + 4 * qy) = csum[0];
+  }
   __syncthreads();
   if (tid < 256) {
     float cs = 0.0f;
 #pragma unroll
-    for (int r = 0; r < 8; ++r) cs += sm[r * 256 + tid];
+    for (int r = 0; r < (T1 ? 32 : 8); ++r) cs += sm[r * 256 + tid];
     if (tid < 192) {
       if (slab) slab[GW_SLAB_BI + tid] = cs;
       else atomicAdd(a.dbi + tid, cs);
@@ -1079,26 +1266,29 @@ __global__ void __launch_bounds__(512) gru_bwd_w_kernel(GruBwdWArgs a) {
 
 extern "C" int64_t dgppo_gru_bwd_w_workspace_bytes(void) { return (int64_t)GW_SLAB * sizeof(float) * device_cus(); }
 
-extern "C" int32_t dgppo_gru_bwd_w(const float* x, int32_t ldx, const float* hprev, int32_t ldh, const float* dgi,
-                                   const float* dhn, float* dWi, int32_t ldwi, float* dbi, float* dWh, int32_t ldwh,
-                                   float* dbhn, int32_t M, float* workspace, int64_t workspace_bytes,
-                                   dgppo_reduce_desc* pending, void* stream) {
+template <bool T1>
+static int32_t gru_bwd_w_launch(GruBwdWArgs a, float* workspace, int64_t workspace_bytes, dgppo_reduce_desc* pending,
+                                hipStream_t s) {
+  const int M = a.M;
   DGPPO_REQUIRE(M >= 0, "gru_bwd_w: bad M");
-  DGPPO_REQUIRE(x && hprev && dgi && dhn && dWi && dbi && dWh && dbhn, "gru_bwd_w: NULL operand");
-  DGPPO_REQUIRE(ldx >= 64 && ldh >= 64 && ldwi >= 192 && ldwh >= 192, "gru_bwd_w: leading dimensions too small");
-  DGPPO_REQUIRE((ldx & 3) == 0 && (ldh & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hprev) |
-                 reinterpret_cast<uintptr_t>(dgi) | reinterpret_cast<uintptr_t>(dhn)) & 15) == 0,
-                "gru_bwd_w: x, hprev, dgi, dhn must be 16-byte aligned with leading dimensions that are multiples of 4");
+  DGPPO_REQUIRE(a.x && a.hprev && a.dWi && a.dbi && a.dWh && a.dbhn, "gru_bwd_w: NULL operand");
+  DGPPO_REQUIRE(T1 ? (a.dhs && a.gates && a.dgi_out) : (a.dgi && a.dhn), "gru_bwd_w: NULL operand");
+  DGPPO_REQUIRE(a.ldx >= 64 && a.ldh >= 64 && a.ldwi >= 192 && a.ldwh >= 192, "gru_bwd_w: leading dimensions too small");
+  DGPPO_REQUIRE((a.ldx & 3) == 0 && (a.ldh & 3) == 0 &&
+                ((reinterpret_cast<uintptr_t>(a.x) | reinterpret_cast<uintptr_t>(a.hprev) | reinterpret_cast<uintptr_t>(a.dgi) |
+                  reinterpret_cast<uintptr_t>(a.dhn) | reinterpret_cast<uintptr_t>(a.dhs) | reinterpret_cast<uintptr_t>(a.gates) |
+                  reinterpret_cast<uintptr_t>(a.dgi_out)) & 15) == 0,
+                "gru_bwd_w: the row operands must be 16-byte aligned with leading dimensions that are multiples of 4");
   DGPPO_REQUIRE(workspace_bytes >= 0 && (workspace != nullptr || workspace_bytes == 0), "gru_bwd_w: bad workspace");
   DGPPO_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "gru_bwd_w: workspace must be 16-byte aligned");
   if (pending) pending[0].pending = pending[1].pending = pending[2].pending = 0;
   if (M == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
   constexpr size_t smem = 2 * sizeof(float) * GW_BUF;
   static_assert(smem <= 160 * 1024, "gru_bwd_w tiles exceed the 160 KB LDS of a gfx950 CU");
+  static_assert(32 * 256 <= 2 * GW_BUF, "gru_bwd_w: the column-sum exchange does not fit the tile buffers");
   static thread_local bool opted = false;
   if (!opted) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_bwd_w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gru_bwd_w_kernel<T1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     opted = true;
   }
   // one workgroup per CU; rows per workgroup a multiple of the 32-row tile, at least two tiles
@@ -1112,20 +1302,41 @@ extern "C" int32_t dgppo_gru_bwd_w(const float* x, int32_t ldx, const float* hpr
     else if (cdiv(M, rpb) > max_slabs) rpb = ((cdiv(M, (int)max_slabs) + BW_ROWS - 1) / BW_ROWS) * BW_ROWS;
   }
   const int grid = cdiv(M, rpb);
-  GruBwdWArgs a{x, ldx, hprev, ldh, dgi, dhn, dWi, ldwi, dbi, dWh, ldwh, dbhn, M, rpb, ws};
-  hipLaunchKernelGGL(gru_bwd_w_kernel, dim3(grid), dim3(512), smem, s, a);
+  a.rows_per_block = rpb;
+  a.part = ws;
+  hipLaunchKernelGGL(gru_bwd_w_kernel<T1>, dim3(grid), dim3(512), smem, s, a);
   DGPPO_LAUNCH_CHECK();
   if (!ws) return 0;
   // second stage: dWi with its bias row, dWh without one, dbhn as a [1,64] matrix
   dgppo_reduce_desc d[3];
-  d[0] = dgppo_reduce_desc{ws + GW_SLAB_WI, dWi, dbi, GW_SLAB, grid, ldwi, 64, 192, 1};
-  d[1] = dgppo_reduce_desc{ws + GW_SLAB_WH, dWh, nullptr, GW_SLAB, grid, ldwh, 64, 192, 1};
-  d[2] = dgppo_reduce_desc{ws + GW_SLAB_BHN, dbhn, nullptr, GW_SLAB, grid, 64, 1, 64, 1};
+  d[0] = dgppo_reduce_desc{ws + GW_SLAB_WI, a.dWi, a.dbi, GW_SLAB, grid, a.ldwi, 64, 192, 1};
+  d[1] = dgppo_reduce_desc{ws + GW_SLAB_WH, a.dWh, nullptr, GW_SLAB, grid, a.ldwh, 64, 192, 1};
+  d[2] = dgppo_reduce_desc{ws + GW_SLAB_BHN, a.dbhn, nullptr, GW_SLAB, grid, 64, 1, 64, 1};
   if (pending) {
     pending[0] = d[0]; pending[1] = d[1]; pending[2] = d[2];
     return 0;
   }
-  return dgppo_dense_bwd_w_reduce_batch(d, 3, stream);
+  return dgppo_dense_bwd_w_reduce_batch(d, 3, (void*)s);
+}
+
+extern "C" int32_t dgppo_gru_bwd_w(const float* x, int32_t ldx, const float* hprev, int32_t ldh, const float* dgi,
+                                   const float* dhn, float* dWi, int32_t ldwi, float* dbi, float* dWh, int32_t ldwh,
+                                   float* dbhn, int32_t M, float* workspace, int64_t workspace_bytes,
+                                   dgppo_reduce_desc* pending, void* stream) {
+  GruBwdWArgs a{};
+  a.x = x; a.ldx = ldx; a.hprev = hprev; a.ldh = ldh; a.dgi = dgi; a.dhn = dhn;
+  a.dWi = dWi; a.ldwi = ldwi; a.dbi = dbi; a.dWh = dWh; a.ldwh = ldwh; a.dbhn = dbhn; a.M = M;
+  return gru_bwd_w_launch<false>(a, workspace, workspace_bytes, pending, (hipStream_t)stream);
+}
+
+extern "C" int32_t dgppo_gru_bwd_w_t1(const float* x, int32_t ldx, const float* h0, int32_t ldh, const float* dhs,
+                                      const float* gates, float* dgi, float* dWi, int32_t ldwi, float* dbi, float* dWh,
+                                      int32_t ldwh, float* dbhn, int32_t M, float* workspace, int64_t workspace_bytes,
+                                      dgppo_reduce_desc* pending, void* stream) {
+  GruBwdWArgs a{};
+  a.x = x; a.ldx = ldx; a.hprev = h0; a.ldh = ldh; a.dhs = dhs; a.gates = gates; a.dgi_out = dgi;
+  a.dWi = dWi; a.ldwi = ldwi; a.dbi = dbi; a.dWh = dWh; a.ldwh = ldwh; a.dbhn = dbhn; a.M = M;
+  return gru_bwd_w_launch<true>(a, workspace, workspace_bytes, pending, (hipStream_t)stream);
 }
 
 extern "C" int32_t dgppo_dense_fwd(const float* X, int32_t ldx, const float* W, int32_t ldw, const float* bias, float* Y,
@@ -1155,6 +1366,21 @@ extern "C" int32_t dgppo_dense_bwd_w_deferred(const float* X, int32_t ldx, const
   DenseBwdWArgs a{X, ldx, dY, ldy, dW, ldw, db, M, K, N, 0, workspace, 0, (size_t)workspace_bytes};
   g_defer = pending;
   const int32_t rc = dense_bwd_w_launch(a, (hipStream_t)stream);
+  g_defer = nullptr;
+  return rc;
+}
+
+extern "C" int32_t dgppo_dense_bwd_xw(const float* X, int32_t ldx, const float* dY, int32_t ldy, const float* W, int32_t ldw,
+                                      float* dX, int32_t lddx, int32_t accumulate_mask, float* dW, int32_t lddw, float* db,
+                                      int32_t M, int32_t K, int32_t N, float* workspace, int64_t workspace_bytes,
+                                      dgppo_reduce_desc* pending, void* stream) {
+  DGPPO_REQUIRE(workspace_bytes >= 0 && (workspace != nullptr || workspace_bytes == 0), "dense_bwd_xw: bad workspace");
+  DGPPO_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "dense_bwd_xw: workspace must be 16-byte aligned");
+  if (pending) pending->pending = 0;
+  DenseBwdWArgs a{X, ldx, dY, ldy, dW, lddw, db, M, K, N, 0, workspace, 0, (size_t)workspace_bytes, W, ldw, dX, lddx,
+                  accumulate_mask ? 1 : 0};
+  g_defer = pending;
+  const int32_t rc = dense_bwd_xw_launch(a, (hipStream_t)stream);
   g_defer = nullptr;
   return rc;
 }

@@ -10,6 +10,7 @@
 //   backward = jax.grad of the above     dgppo/algo/informarl.py:377,440 ; dgppo/algo/dgppo.py:316
 #include "common.h"
 #include "nn_ln.h"
+#include "nn_gru.h"
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
@@ -341,7 +342,8 @@ __global__ void __launch_bounds__(256) gru_fwd_kernel(GruArgs a) {
 // matrix cores with the Wh^T fragments (48 k-steps x 1 column tile) resident in registers.  dgh tiles are
 // double-buffered in LDS: one LDS-only barrier per step.  The saved gates / hprev / upstream gradient of step tau-1 are
 // requested while step tau's product runs.  DHN_ONLY: the hidden-side gradient leaves as dhn [rows,64] instead of
-// dgh [rows,192] (whose r / z columns repeat dgi's); everything else, and every value written, is the same.
+// dgh [rows,192] (whose r / z columns repeat dgi's); everything else, and every value written, is the same.  The first step
+// (tau == 0, walked last) only forms its gate gradients: the product would feed a dh that nothing reads.
 template <int RTW, bool DHN_ONLY>
 __global__ void __launch_bounds__(256) gru_bwd_kernel(GruArgs a) {
   extern __shared__ float sm[];
@@ -397,16 +399,14 @@ __global__ void __launch_bounds__(256) gru_bwd_kernel(GruArgs a) {
         for (int r = 0; r < 4; ++r) {
           const int rl = rt * 16 + lq * 4 + r;
           const float d = ok[rt][r] ? dh[rt][r] + du[rt][r] : 0.0f;
-          const float dz = d * (hp[rt][r] - ng[rt][r]);
-          const float dn = d * (1.0f - zg[rt][r]);
-          const float dan = dn * (1.0f - ng[rt][r] * ng[rt][r]);
-          const float dhn = dan * rg[rt][r];
-          const float dar = dan * hn[rt][r] * rg[rt][r] * (1.0f - rg[rt][r]);
-          const float daz = dz * zg[rt][r] * (1.0f - zg[rt][r]);
+          const GruGateGrad gg = gru_gate_grad(d, hp[rt][r], rg[rt][r], zg[rt][r], ng[rt][r], hn[rt][r]);
+          const float dar = gg.dar, daz = gg.daz, dan = gg.dan, dhn = gg.dhn;
           dh[rt][r] = d * zg[rt][r];
-          s_g[rl * GRU_WL + c] = dar;
-          s_g[rl * GRU_WL + 64 + c] = daz;
-          s_g[rl * GRU_WL + 128 + c] = dhn;
+          if (tau > 0) {                      // the dgh image feeds phase B only
+            s_g[rl * GRU_WL + c] = dar;
+            s_g[rl * GRU_WL + 64 + c] = daz;
+            s_g[rl * GRU_WL + 128 + c] = dhn;
+          }
           if (ok[rt][r]) {
             const size_t row = (size_t)(row0[rt][r] + tau * a.n_inner);
             float* o = a.dgi + row * 192 + c;
@@ -419,8 +419,12 @@ __global__ void __launch_bounds__(256) gru_bwd_kernel(GruArgs a) {
             }
           }
         }
+      // dh after the first step has no reader (there is no dh0 output): no product, no dgh image and no barrier at
+      // tau == 0.  cur stays on the buffer this step left unwritten; the tile-end barrier below orders the next tile's
+      // first write after every read of this tile, whichever buffer that is.
+      if (tau == 0) break;
       GRU_LDS_BARRIER();
-      if (tau > 0) fetch(tau - 1);          // in flight during the product below
+      fetch(tau - 1);                       // in flight during the product below
       __builtin_amdgcn_sched_barrier(0);
       // phase B: dh_prev[row, c] += sum_k dgh[row, k] * Wh[c, k]
       f32x4 acc[RTW];

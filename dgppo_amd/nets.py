@@ -377,7 +377,7 @@ class Net:
             else:
                 K.gru_fwd(gi, self.p("gru.Wh"), self.p("gru.bhn"), h0, hs, hprev, gates, n_seq, T, n_inner)
             if hprev_is_h0:
-                act["hprev"] = h0
+                act["hprev"] = act["h0"] = h0
         if self.rnn == "none":
             # no cell: the MLP output is the feature and the carry passes through unchanged (policy.py:29-33)
             feat = act["y2"]
@@ -482,6 +482,12 @@ class Net:
                          gq("Wq"), gq("bq"), gq("Wk"), gq("Wv"), gq("bv"), gq("We"), gq("Wu"), f, fp, d, H_HEADS, kp)
         self.prep_grads.zero_()
 
+    @staticmethod
+    def _gru_t1_in_pass(act, T, row_operands) -> bool:
+        """gru_bwd_w_t1 applies: one step whose saved hprev IS the given h0, all row operands on the GPU and 16-byte aligned"""
+        return (T == 1 and act.get("h0") is not None and act["hprev"] is act["h0"]
+                and all(t.is_cuda and t.data_ptr() % 16 == 0 for t in row_operands))
+
     def _backward_body(self, act, dout: torch.Tensor, tag: str):
         cfg, A = self.cfg, self.arena
         G, Rh, n_inner, n_seq, T = act["G"], act["Rh"], act["n_inner"], act["n_seq"], act["T"]
@@ -532,9 +538,14 @@ class Net:
                 # one GRU layer: the backward scan leaves (dgi, dhn) and ONE kernel turns them into dWi, dbi, dWh, dbhn
                 st = stack[0]
                 dgi = A.get(f"{tag}.dgi0", Rh, 3 * HID)
-                dhn = A.get(f"{tag}.dhn0", Rh, HID)
-                K.gru_bwd_dhn(dhs, self.p("gru.Wh"), st["hprev"], st["gates"], dgi, dhn, n_seq, T, n_inner)
-                K.gru_bwd_w(act["y2"], st["hprev"], dgi, dhn, self.g("gru.Wi"), self.g("gru.bi"), self.g("gru.Wh"), self.g("gru.bhn"))
+                gW = (self.g("gru.Wi"), self.g("gru.bi"), self.g("gru.Wh"), self.g("gru.bhn"))
+                if self._gru_t1_in_pass(act, T, (act["y2"], st["hprev"], dhs, st["gates"], dgi)):
+                    # one step from h0: the scan is elementwise, so the weight-gradient pass forms the gate gradients itself
+                    K.gru_bwd_w_t1(act["y2"], st["hprev"], dhs, st["gates"], dgi, *gW)
+                else:
+                    dhn = A.get(f"{tag}.dhn0", Rh, HID)
+                    K.gru_bwd_dhn(dhs, self.p("gru.Wh"), st["hprev"], st["gates"], dgi, dhn, n_seq, T, n_inner)
+                    K.gru_bwd_w(act["y2"], st["hprev"], dgi, dhn, *gW)
                 if fused_trunk:
                     dgi0 = dgi
                 else:
@@ -598,9 +609,9 @@ class Net:
         dXo = None
         for l in range(self.gnn_layers - 1, -1, -1):
             f, fp, d, kp = self.dims[l]
-            K.dense_bwd_w(act[f"zcat{l}"], dXa, self.pg(f"gnn{l}.Wout"), self.g(f"gnn{l}.bu"))
+            # dWout / dbu and dz = dXa Wout^T from one pass over (zcat, dXa)
             dz = A.get(f"{tag}.dz{l}", R, kp)
-            K.dense_fwd(dXa, self.pp(f"gnn{l}.Wout"), None, dz, trans_w=True)
+            K.dense_bwd_xw(act[f"zcat{l}"], dXa, self.pp(f"gnn{l}.Wout"), dz, self.pg(f"gnn{l}.Wout"), self.g(f"gnn{l}.bu"))
             if dXo is not None:  # other nodes of layer l+1: relu(W_u x + b_u)
                 K.dense_bwd_w(act[f"Xo{l}"], dXo, self.pg(f"gnn{l}.Wout")[:fp], self.g(f"gnn{l}.bu"))
             dqt = A.get(f"{tag}.dqt{l}", R, H_HEADS * fp)
@@ -623,9 +634,13 @@ class Net:
                 K.attn_bwd(cfg, fp, H_HEADS, kp, dz, act[f"attn{l}"], act[f"qt{l}"], act[f"Xa{l}"],
                            act[f"Xo{l}"] if Ro > 0 else None, feats.efeat, dqt, dXa_l, dXo_l, G,
                            relu_xo=(dXo_l is not None and not more_dXo))
-            K.dense_bwd_w(act[f"Xa{l}"], dqt, self.pg(f"gnn{l}.Mcat"), self.pg(f"gnn{l}.cvec"))
             if need_dx:
-                K.dense_fwd(dqt, self.pp(f"gnn{l}.Mcat"), None, dXa_l, accumulate=True, trans_w=True, relu_mask=act[f"Xa{l}"])
+                # dMcat / dcvec and dXa_l = relu'(Xa) (dXa_l + dqt Mcat^T) from one pass: the mask IS the Dense's input
+                K.dense_bwd_xw(act[f"Xa{l}"], dqt, self.pp(f"gnn{l}.Mcat"), dXa_l, self.pg(f"gnn{l}.Mcat"), self.pg(f"gnn{l}.cvec"),
+                               accumulate_mask=True)
+            else:
+                K.dense_bwd_w(act[f"Xa{l}"], dqt, self.pg(f"gnn{l}.Mcat"), self.pg(f"gnn{l}.cvec"))
+            if need_dx:
                 if more_dXo:
                     K.dense_fwd(dXo_prev, self.pp(f"gnn{l}.Wout")[:fp], None, dXo_l, accumulate=True, trans_w=True,
                                 relu_mask=act[f"Xo{l}"])

@@ -219,6 +219,38 @@ def dense_bwd_w(X, dY, dW, db=None):
     N.check(rc, "dgppo_dense_bwd_w")
 
 
+def dense_bwd_xw(X, dY, W, dX, dW, db=None, accumulate_mask: bool = False):
+    """dense_bwd_w(X, dY, dW, db) and dense_fwd(dY, W, None, dX, trans_w=True) - with accumulate_mask: accumulate=True,
+    relu_mask=X - as ONE call: the library runs them as one pass over X and dY for the GNN glue shapes (dgppo_dense_bwd_xw in
+    the header) and as the pair otherwise."""
+    xp, ldx, M, K = _mat(X, "X")
+    yp, ldy, My, Ncol = _mat(dY, "dY")
+    pp, ldp, Kp, Np = _mat(W, "W")
+    dxp, lddx, Mx, Kx = _mat(dX, "dX")
+    wp, ldw, Kw, Nw = _mat(dW, "dW")
+    if My != M or (Kw, Nw) != (K, Ncol) or (Kp, Np) != (K, Ncol) or (Mx, Kx) != (M, K):
+        raise ValueError(f"dense_bwd_xw: shape mismatch X{tuple(X.shape)} dY{tuple(dY.shape)} W{tuple(W.shape)} "
+                         f"dX{tuple(dX.shape)} dW{tuple(dW.shape)}")
+    if db is not None:
+        N.expect_shape(db, (Ncol,), "db")
+    FLOPS[0] += 4.0 * M * K * Ncol
+    batch = BwdWBatch._active.get((X.device.index, torch.cuda.current_stream(X.device).cuda_stream))
+    lib = N.lib()
+    if batch is not None:
+        lib.dgppo_dense_bwd_w_workspace_bytes.restype = C.c_int64
+        ws = batch.region(min(int(lib.dgppo_dense_bwd_w_workspace_bytes(C.c_int32(K), C.c_int32(Ncol))), 64 << 20))
+        d = ReduceDesc()
+        pend = C.byref(d)
+    else:
+        ws = _bwd_w_workspace(X.device, K, Ncol)
+        pend = None
+    rc = lib.dgppo_dense_bwd_xw(xp, ldx, yp, ldy, pp, ldp, dxp, lddx, int(bool(accumulate_mask)), wp, ldw, _p(db, "db"), M, K,
+                                Ncol, _p(ws, "workspace"), C.c_int64(ws.numel() * 4), pend, N.stream_ptr())
+    N.check(rc, "dgppo_dense_bwd_xw")
+    if batch is not None and d.pending:
+        batch.descs.append(d)
+
+
 def _check_strided(fn: str, name: str, t_, se: int, st: int, inner: tuple, env_ids, n_env: int, n_time: int):
     """a record field the feature kernels address as data_ptr + env * se + time * st, in floats (a view's own outer strides are
     ignored): the innermost record must be dense fp32 CUDA storage, and the storage must reach the last (env, time) the call
@@ -740,7 +772,7 @@ def gru_bwd(dhs, Wh, hprev, gates, dgi, dgh, n_seq, T, n_inner):
     N.expect_shape(dhs, (rows, 64), "dhs")
     N.expect_shape(dgi, (rows, 192), "dgi")
     N.expect_shape(dgh, (rows, 192), "dgh")
-    FLOPS[0] += 2.0 * rows * 64 * 192
+    FLOPS[0] += 2.0 * n_seq * (T - 1) * 64 * 192        # the first step forms no dh: nothing reads it
     rc = N.lib().dgppo_gru_bwd(_p(dhs), _p(Wh), _p(hprev), _p(gates), _p(dgi), _p(dgh), n_seq, T, n_inner, N.stream_ptr())
     N.check(rc, "dgppo_gru_bwd")
 
@@ -751,27 +783,27 @@ def gru_bwd_dhn(dhs, Wh, hprev, gates, dgi, dhn, n_seq, T, n_inner):
     N.expect_shape(dhs, (rows, 64), "dhs")
     N.expect_shape(dgi, (rows, 192), "dgi")
     N.expect_shape(dhn, (rows, 64), "dhn")
-    FLOPS[0] += 2.0 * rows * 64 * 192
+    FLOPS[0] += 2.0 * n_seq * (T - 1) * 64 * 192
     rc = N.lib().dgppo_gru_bwd_dhn(_p(dhs), _p(Wh), _p(hprev), _p(gates), _p(dgi), _p(dhn), n_seq, T, n_inner, N.stream_ptr())
     N.check(rc, "dgppo_gru_bwd_dhn")
 
 
-def gru_bwd_w(x, hprev, dgi, dhn, dWi, dbi, dWh, dbhn):
-    """dWi += x.T @ dgi ; dbi += dgi.sum(0) ; dWh += hprev.T @ [dgi[:, :128] | dhn] ; dbhn += dhn.sum(0) in one pass over the
-    rows (inside `with BwdWBatch(...)`: the slab reductions are deferred to the batch's flush, like dense_bwd_w's)"""
+def _gru_bwd_w_call(name, x, hprev, rows_in, dgi, dWi, dbi, dWh, dbhn):
+    """the common part of gru_bwd_w / gru_bwd_w_t1: rows_in = the dense row operands between hprev and the outputs"""
     xp, ldx, M, Kx = _mat(x, "x")
     hp, ldh, Mh, Kh = _mat(hprev, "hprev")
     wip, ldwi, _, _ = _mat(dWi, "dWi")
     whp, ldwh, _, _ = _mat(dWh, "dWh")
     if Kx != 64 or (Mh, Kh) != (M, 64) or tuple(dWi.shape) != (64, 192) or tuple(dWh.shape) != (64, 192):
-        raise ValueError(f"gru_bwd_w: shape mismatch x{tuple(x.shape)} hprev{tuple(hprev.shape)} dWi{tuple(dWi.shape)} "
+        raise ValueError(f"{name}: shape mismatch x{tuple(x.shape)} hprev{tuple(hprev.shape)} dWi{tuple(dWi.shape)} "
                          f"dWh{tuple(dWh.shape)}")
-    N.expect_shape(dgi, (M, 192), "dgi"); N.expect_shape(dhn, (M, 64), "dhn")
+    for nm, (t, w) in rows_in.items():
+        N.expect_shape(t, (M, w), nm)
+    N.expect_shape(dgi, (M, 192), "dgi")
     N.expect_shape(dbi, (192,), "dbi"); N.expect_shape(dbhn, (64,), "dbhn")
     FLOPS[0] += 2.0 * M * 64 * (128 + 64 + 192)      # the three dense_bwd_w calls this replaces
     lib = N.lib()
-    lib.dgppo_gru_bwd_w_workspace_bytes.restype = C.c_int64
-    need = int(lib.dgppo_gru_bwd_w_workspace_bytes())
+    need = _workspace_bytes("dgppo_gru_bwd_w_workspace_bytes", x.device)
     batch = BwdWBatch._active.get((x.device.index, torch.cuda.current_stream(x.device).cuda_stream)) if x.is_cuda else None
     if batch is not None:
         ws = batch.region(need)
@@ -783,13 +815,30 @@ def gru_bwd_w(x, hprev, dgi, dhn, dWi, dbi, dWh, dbhn):
         if ws is None or ws.numel() * 4 < need:
             ws = _WS[key] = torch.empty(need // 4, dtype=torch.float32, device=x.device)
         pend = None
-    rc = lib.dgppo_gru_bwd_w(xp, ldx, hp, ldh, _p(dgi, "dgi"), _p(dhn, "dhn"), wip, ldwi, _p(dbi, "dbi"), whp, ldwh,
-                             _p(dbhn, "dbhn"), M, _p(ws, "workspace"), C.c_int64(ws.numel() * 4), pend, N.stream_ptr())
-    N.check(rc, "dgppo_gru_bwd_w")
+    mid = [_p(t, nm) for nm, (t, w) in rows_in.items()]
+    if name == "dgppo_gru_bwd_w":
+        mid = [_p(dgi, "dgi")] + mid               # (x, hprev, dgi, dhn, outputs)
+    else:
+        mid = mid + [_p(dgi, "dgi")]               # (x, h0, dhs, gates, dgi, outputs)
+    rc = getattr(lib, name)(xp, ldx, hp, ldh, *mid, wip, ldwi, _p(dbi, "dbi"), whp, ldwh, _p(dbhn, "dbhn"), M,
+                            _p(ws, "workspace"), C.c_int64(ws.numel() * 4), pend, N.stream_ptr())
+    N.check(rc, name)
     if batch is not None:
         for i in range(3):
             if d[i].pending:
                 batch.descs.append(ReduceDesc.from_buffer_copy(d[i]))
+
+
+def gru_bwd_w(x, hprev, dgi, dhn, dWi, dbi, dWh, dbhn):
+    """dWi += x.T @ dgi ; dbi += dgi.sum(0) ; dWh += hprev.T @ [dgi[:, :128] | dhn] ; dbhn += dhn.sum(0) in one pass over the
+    rows (inside `with BwdWBatch(...)`: the slab reductions are deferred to the batch's flush, like dense_bwd_w's)"""
+    _gru_bwd_w_call("dgppo_gru_bwd_w", x, hprev, {"dhn": (dhn, 64)}, dgi, dWi, dbi, dWh, dbhn)
+
+
+def gru_bwd_w_t1(x, h0, dhs, gates, dgi, dWi, dbi, dWh, dbhn):
+    """gru_bwd_dhn(T = 1, hprev = h0) and gru_bwd_w in one pass: writes dgi [M,192] (the bits gru_bwd_dhn writes) and
+    accumulates the four GRU gradients; dhn stays on chip.  The gate gradients are elementwise: no product is counted."""
+    _gru_bwd_w_call("dgppo_gru_bwd_w_t1", x, h0, {"dhs": (dhs, 64), "gates": (gates, 256)}, dgi, dWi, dbi, dWh, dbhn)
 
 
 _WS_BYTES: dict = {}   # (query name, device index) -> bytes: constant per device, asked once

@@ -274,6 +274,20 @@ int32_t dgppo_dense_bwd_w_deferred(const float* X, int32_t ldx, const float* dY,
                                    float* db, int32_t M, int32_t K, int32_t N, float* workspace, int64_t workspace_bytes,
                                    dgppo_reduce_desc* pending, void* stream);
 int32_t dgppo_dense_bwd_w_reduce_batch(const dgppo_reduce_desc* descs, int32_t n, void* stream);
+/* Both gradients of one Dense Y = X W from one call: dW [K, lddw] += X^T dY, db [N] += colsum(dY) (db may be NULL) as
+ * dgppo_dense_bwd_w, and the input gradient dX [M, lddx] = dY W^T (W [K, ldw]: the parameters), or with accumulate_mask != 0
+ * dX = (X > 0) ? dX + dY W^T : 0 - dgppo_dense_fwd's accumulate + relu_mask epilogue with X itself as the mask (the Dense's input
+ * is a ReLU output).  For the GNN glue shapes (K, N) in {(144, 64), (48, 32), (48, 64)} with X, dY, W, dX 16-byte
+ * aligned and ldx, ldy, ldw, lddx multiples of 4 this is ONE launch that brings X in once and dY twice (once for the tile of
+ * the weight gradient and once more in the operand layout of the input gradient: a cache hit by the measured fetch
+ * counters, profiles/README.md round 7); every other call runs
+ * dgppo_dense_bwd_w followed by dgppo_dense_fwd(trans_w) and gives their results.  The choice depends on nothing else.  The one
+ * pass sums dX over n in a different order than dgppo_dense_fwd (agreement to fp32 rounding of a reordered sum of N terms).
+ * dX must not overlap X, dY or W.  workspace as dgppo_dense_bwd_w; pending NULL reduces the slabs now, otherwise *pending
+ * receives the owed reduction under the rules of dgppo_dense_bwd_w_deferred.                                                 */
+int32_t dgppo_dense_bwd_xw(const float* X, int32_t ldx, const float* dY, int32_t ldy, const float* W, int32_t ldw, float* dX,
+                           int32_t lddx, int32_t accumulate_mask, float* dW, int32_t lddw, float* db, int32_t M, int32_t K,
+                           int32_t N, float* workspace, int64_t workspace_bytes, dgppo_reduce_desc* pending, void* stream);
 /* dgppo_mlp_gi_bwd together with the weight gradients of the chain's two Dense layers, from the same pass over the rows:
  * dW2 [64, ldw2] += y1^T dpre2, dbias2 [64] += colsum(dpre2), dW1 [64, ldw1] += x^T dpre1, dbias1 [64] += colsum(dpre1), where
  * x [M, ldx] is the chain's input (it may be the relu_mask tensor itself).  dpre2 / dpre1 may be NULL: then they never leave
@@ -500,6 +514,15 @@ int64_t dgppo_gru_bwd_w_workspace_bytes(void);
 int32_t dgppo_gru_bwd_w(const float* x, int32_t ldx, const float* hprev, int32_t ldh, const float* dgi, const float* dhn,
                         float* dWi, int32_t ldwi, float* dbi, float* dWh, int32_t ldwh, float* dbhn, int32_t M,
                         float* workspace, int64_t workspace_bytes, dgppo_reduce_desc* pending, void* stream);
+/* The same pass for a one-step GRU (T = 1, the state before the step is h0 [M,ldh]) with the BPTT inside it: the gate gradients
+ * are formed on chip from dhs [M,64], gates [M,256] (as dgppo_gru_fwd saved them) and h0, so neither dgppo_gru_bwd_dhn runs nor
+ * dhn exists in memory.  Writes dgi [M,192] (bit-equal to dgppo_gru_bwd_dhn at T = 1, -0.0 and NaN inputs included) for the
+ * layer below, and accumulates dWi, dbi, dWh, dbhn as dgppo_gru_bwd_w does from that dgi and the dhn of the same call
+ * (summation order differs from it in dbi / dbhn only; h0 is loaded twice per tile, as operand of dWh and for the gates).  x, h0, dhs, gates, dgi 16-byte aligned, ldx / ldh multiples of 4;
+ * workspace and pending as dgppo_gru_bwd_w.                                                                                     */
+int32_t dgppo_gru_bwd_w_t1(const float* x, int32_t ldx, const float* h0, int32_t ldh, const float* dhs, const float* gates,
+                           float* dgi, float* dWi, int32_t ldwi, float* dbi, float* dWh, int32_t ldwh, float* dbhn, int32_t M,
+                           float* workspace, int64_t workspace_bytes, dgppo_reduce_desc* pending, void* stream);
 
 /* LSTM scan (train.py --use-lstm; dgppo/nn/rnn.py:22-24 with flax nn.LSTMCell(64): i,f,o sigmoid, g tanh, c' = f c + i g,
  * h' = o tanh(c'), carry (c, h)).  zi [rows,256] = x [W_ii|W_if|W_ig|W_io] precomputed (flax's input Denses have no bias);

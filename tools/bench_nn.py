@@ -87,6 +87,51 @@ if which in ("all", "gruw"):
         timeit(f"GRU weight gradients: 3 x dense_bwd_w M={M}", three, flops=2.0 * M * 64 * 384, bytes_=4.0 * M * 576)
         timeit(f"GRU weight gradients: gru_bwd_w M={M}", lambda: K.gru_bwd_w(x, hp, dgi, dhn, dWi, dbi, dWh, dbhn),
                flops=2.0 * M * 64 * 384, bytes_=4.0 * M * 384)
+if which in ("all", "gruw1"):
+    # the one-step GRU backward (Vh: T = 1 from h0): scan + weight-gradient pass against the pass that forms the gate gradients
+    # itself; inside a BwdWBatch, so each time includes one batched slab-reduce launch.  Three repeats, alternating
+    M = R
+    Wh = torch.randn(64, 192, device=dev) * 0.1
+    x = torch.randn(M, 64, device=dev); h0 = torch.randn(M, 64, device=dev); gt = torch.rand(M, 256, device=dev)
+    dhs = torch.randn(M, 64, device=dev)
+    dgi = torch.empty(M, 192, device=dev); dhn = torch.empty(M, 64, device=dev)
+    dW = [torch.zeros(64, 192, device=dev), torch.zeros(192, device=dev), torch.zeros(64, 192, device=dev), torch.zeros(64, device=dev)]
+    wsbuf = torch.empty(16 << 20, device=dev)
+
+    def pair():
+        with K.BwdWBatch(dev, lambda n: wsbuf):
+            K.gru_bwd_dhn(dhs, Wh, h0, gt, dgi, dhn, M, 1, 8)
+            K.gru_bwd_w(x, h0, dgi, dhn, *dW)
+
+    def one():
+        with K.BwdWBatch(dev, lambda n: wsbuf):
+            K.gru_bwd_w_t1(x, h0, dhs, gt, dgi, *dW)
+    for rep in range(3):
+        timeit(f"GRU T=1 bwd: gru_bwd_dhn + gru_bwd_w M={M}", pair, iters=50, bytes_=4.0 * M * (384 + 256 + 256 + 384))
+        if hasattr(K, "gru_bwd_w_t1"):
+            timeit(f"GRU T=1 bwd: gru_bwd_w_t1 M={M}", one, iters=50, bytes_=4.0 * M * (64 + 64 + 64 + 256 + 192))
+if which in ("all", "xw"):
+    # both gradients of a GNN glue Dense: dense_bwd_w + dense_fwd(W^T) against the one dense_bwd_xw call, per site of
+    # Net._backward_body; inside a BwdWBatch (kernel plus its share of the batched reduce).  Three repeats, alternating
+    for Kd, Nd, accm in ((144, 64, False), (32, 96, True), (48, 32, False), (48, 64, False)):
+        M = R
+        X = torch.relu(torch.randn(M, Kd, device=dev)); dY = torch.randn(M, Nd, device=dev); W = torch.randn(Kd, Nd, device=dev) * 0.1
+        dX = torch.zeros(M, Kd, device=dev); dW = torch.zeros(Kd, Nd, device=dev); db = torch.zeros(Nd, device=dev)
+        wsbuf = torch.empty(16 << 20, device=dev)
+
+        def pair():
+            with K.BwdWBatch(dev, lambda n: wsbuf):
+                K.dense_bwd_w(X, dY, dW, db)
+                K.dense_fwd(dY, W, None, dX, accumulate=accm, trans_w=True, relu_mask=X if accm else None)
+
+        def one():
+            with K.BwdWBatch(dev, lambda n: wsbuf):
+                K.dense_bwd_xw(X, dY, W, dX, dW, db, accumulate_mask=accm)
+        nbytes = 4.0 * M * (Kd + Nd + Kd * (2 if accm else 1))
+        for rep in range(3):
+            timeit(f"dense bwd K={Kd} N={Nd}: dense_bwd_w + dense_fwd^T", pair, iters=50, bytes_=nbytes)
+            if hasattr(K, "dense_bwd_xw"):
+                timeit(f"dense bwd K={Kd} N={Nd}: dense_bwd_xw", one, iters=50, bytes_=nbytes)
 if which in ("all", "attn"):
     cfg = N.make_env_cfg(0, 8, 3)
     for G in (16384, 4096):
