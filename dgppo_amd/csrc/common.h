@@ -96,6 +96,9 @@ __host__ __device__ inline float u01_from_u32(uint32_t w) { return (float)(w >> 
 
 // NaN-propagating min (jnp.min semantics)
 __device__ inline float nanmin(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : fminf(a, b); }
+// jnp.clip semantics: a NaN stays a NaN (fminf / fmaxf alone would return the bound); every other input gets the bits of
+// fminf(fmaxf(x, lo), hi).  Every clip of the env step kernels (env_step.h, env_vmas.hip) goes through here.
+__device__ inline float clampf_nan(float x, float lo, float hi) { return (x != x) ? x : fminf(fmaxf(x, lo), hi); }
 // NaN-propagating ReLU (jax.nn.relu / jnp.maximum(v, 0) semantics): fmaxf (v_max_f32) returns the non-NaN operand, so a NaN
 // pre-activation would leave as 0.  "not (v <= 0)" is true for a NaN: it passes; every other input, -Inf and +-0 included, gives
 // what fmaxf(v, 0.0f) gives (one compare and one select).

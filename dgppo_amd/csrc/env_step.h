@@ -39,11 +39,10 @@ __device__ inline void state2feat(const float* s, float* f) {
   }
 }
 
-// jnp.clip semantics: a NaN stays a NaN (fminf / fmaxf alone would return the bound); every other input gets the bits of
-// fminf(fmaxf(x, lo), hi).  NaN reaches the costs through a NaN hit point of the pre-step graph (ray parallel to an edge,
-// SURVEY A.13 item 9), and the actions and states through a NaN policy output, which the reference carries through
-// clip_action (env/base.py:84-86) and clip_state into a visibly NaN rollout: every clip of the step kernels goes through here
-__device__ inline float clampf_nan(float x, float lo, float hi) { return (x != x) ? x : fminf(fmaxf(x, lo), hi); }
+// Every clip of the step kernels goes through clampf_nan (common.h: jnp.clip semantics, a NaN stays a NaN).  NaN reaches the
+// costs through a NaN hit point of the pre-step graph (ray parallel to an edge), and the actions and states
+// through a NaN policy output, which the reference carries through clip_action (env/base.py:84-86) and clip_state into a
+// visibly NaN rollout.
 // clip_action (env/base.py:84-86), shared by the three step kernels and the action sweep
 __device__ inline float clip_action(float u) { return clampf_nan(u, -1.0f, 1.0f); }
 

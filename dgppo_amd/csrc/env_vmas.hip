@@ -16,6 +16,11 @@
 // on each lane: no LDS and no barrier across the 20 substeps.  Built with -ffp-contract=off (Makefile EXACT_SRCS): each
 // fp32 operation below is one IEEE operation in the order of tests/vmas_np.py, so a step without contact matches that
 // restatement bit for bit; with contact the forces go through expf / log1pf (a few ulps).
+//
+// Non-finite inputs: the reference clips with jnp.clip and reduces with jnp.min, which keep a NaN, and jnp.argsort sorts NaN
+// last.  Every clip below goes through clampf_nan and both cost minima through nanmin (common.h), and the obstacle rank of
+// node_row puts NaN last, so a NaN action or state gives the reference's visibly NaN rollout and not a finite one; for every
+// non-NaN input these give the bits of fminf / fmaxf and of the plain comparison.
 #include "common.h"
 
 namespace {
@@ -100,12 +105,29 @@ __device__ inline void node_row(const float* a, const float* body, const float* 
     d[k] = sqrtf((rx * rx + ry * ry) + 1e-6f);
     vx[k] = rx / d[k]; vy[k] = ry / d[k];
   }
+  // stable argsort of 3 distances, NaN last (jnp.argsort; ray_rank of env_step.h): rank = #smaller + #equal before.  The ranks
+  // are a permutation of 0, 1, 2, so each slot below finds its obstacle and every column is written.
+  int rank[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {          // stable argsort of 3 distances: rank = #smaller + #equal before
+  for (int k = 0; k < 3; ++k) {
+    const bool nk = (d[k] != d[k]);
     int r = 0;
 #pragma unroll
-    for (int j = 0; j < 3; ++j) r += (d[j] < d[k] || (d[j] == d[k] && j < k)) ? 1 : 0;
-    out[11 + 2 * r] = vx[k]; out[12 + 2 * r] = vy[k]; out[17 + r] = d[k];
+    for (int j = 0; j < 3; ++j) {
+      const bool nj = (d[j] != d[j]);
+      bool less;
+      if (nj || nk) less = (nj == nk) ? (j < k) : nk;
+      else less = (d[j] < d[k]) || (d[j] == d[k] && j < k);
+      r += less ? 1 : 0;
+    }
+    rank[k] = r;
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const int k = (rank[0] == r) ? 0 : ((rank[1] == r) ? 1 : 2);
+    out[11 + 2 * r] = (k == 0) ? vx[0] : ((k == 1) ? vx[1] : vx[2]);
+    out[12 + 2 * r] = (k == 0) ? vy[0] : ((k == 1) ? vy[1] : vy[2]);
+    out[17 + r] = (k == 0) ? d[0] : ((k == 1) ? d[1] : d[2]);
   }
 }
 
@@ -164,8 +186,8 @@ __global__ __launch_bounds__(256) void vmas_step_kernel(VmasStepArgs a) {
     px = s[0]; py = s[1]; vx = s[2]; vy = s[3];
     if (a.action) {
       const float* u = a.action + ((size_t)b * n + i) * 2;
-      ux = fminf(fmaxf(u[0], -1.0f), 1.0f) * kUMult;        // clip_action, then u_multiplier (entity.py, world.py:296-309)
-      uy = fminf(fmaxf(u[1], -1.0f), 1.0f) * kUMult;
+      ux = clampf_nan(u[0], -1.0f, 1.0f) * kUMult;          // clip_action, then u_multiplier (entity.py, world.py:296-309)
+      uy = clampf_nan(u[1], -1.0f, 1.0f) * kUMult;
     }
   }
   if (env_ok) {
@@ -180,17 +202,17 @@ __global__ __launch_bounds__(256) void vmas_step_kernel(VmasStepArgs a) {
     for (int j = 0; j < n; ++j) {
       const float qx = __shfl(px, j, P), qy = __shfl(py, j, P);
       const float d = norm2f(px - qx, py - qy) + ((j == i) ? 1e6f : 0.0f);
-      mind = fminf(mind, d);
+      mind = nanmin(mind, d);                               // jnp.min: a NaN distance makes the margin NaN
     }
     float mino = 3.4e38f;
 #pragma unroll
-    for (int k = 0; k < 3; ++k) mino = fminf(mino, norm2f(bx - sc[2 + 2 * k], by - sc[3 + 2 * k]));
+    for (int k = 0; k < 3; ++k) mino = nanmin(mino, norm2f(bx - sc[2 + 2 * k], by - sc[3 + 2 * k]));
     if (live) {
       float c0 = 4.0f * (kTwoAgentR - mind), c1 = 2.0f * (kObsR - mino);
       c0 = (c0 <= 0.0f) ? c0 - 0.5f : c0 + 0.5f;
       c1 = (c1 <= 0.0f) ? c1 - 0.5f : c1 + 0.5f;
-      a.cost[((size_t)b * n + i) * 2] = fminf(fmaxf(c0, -1.0f), 1.0f);
-      a.cost[((size_t)b * n + i) * 2 + 1] = fminf(fmaxf(c1, -1.0f), 1.0f);
+      a.cost[((size_t)b * n + i) * 2] = clampf_nan(c0, -1.0f, 1.0f);
+      a.cost[((size_t)b * n + i) * 2 + 1] = clampf_nan(c1, -1.0f, 1.0f);
       if (i == 0) {
         const float dg = norm2f(sc[0] - bx, sc[1] - by);
         float r = -dg * 0.01f;
@@ -216,11 +238,11 @@ __global__ __launch_bounds__(256) void vmas_step_kernel(VmasStepArgs a) {
           bvx = bvx * kDragKeep; bvy = bvy * kDragKeep;
         }
         vx = vx + (Fax / 1.0f) * kSubDt; vy = vy + (Fay / 1.0f) * kSubDt;
-        px = fminf(fmaxf(px + vx * kSubDt, -kSemidim), kSemidim);
-        py = fminf(fmaxf(py + vy * kSubDt, -kSemidim), kSemidim);
+        px = clampf_nan(px + vx * kSubDt, -kSemidim, kSemidim);
+        py = clampf_nan(py + vy * kSubDt, -kSemidim, kSemidim);
         bvx = bvx + (Fbx / kBoxMass) * kSubDt; bvy = bvy + (Fby / kBoxMass) * kSubDt;
-        bx = fminf(fmaxf(bx + bvx * kSubDt, -kSemidim), kSemidim);
-        by = fminf(fmaxf(by + bvy * kSubDt, -kSemidim), kSemidim);
+        bx = clampf_nan(bx + bvx * kSubDt, -kSemidim, kSemidim);
+        by = clampf_nan(by + bvy * kSubDt, -kSemidim, kSemidim);
       }
     }
     if (live) {

@@ -90,8 +90,10 @@ def reset_uniforms(seed: int, n: int):
     return dict(box=d0[0], goal=d0[1], obs=(d1[0], d1[1], d2[0]), vel=vel), st
 
 
-def reset_single(seed: int, n: int, max_restarts: int = 64):
-    """-> agent [n, 4], body [4], scene [8], placed (bool)"""
+def reset_single(seed: int, n: int, max_restarts: int = 64, stats: dict = None):
+    """-> agent [n, 4], body [4], scene [8], placed (bool); a dict given as `stats` receives `restarts` (placements started
+    over after the 1024-iteration cut), `draws` (Philox counter at the end) and `pos` [n, 2] (the placement in the 0.24 square,
+    before it is shifted onto the box)"""
     u, st = reset_uniforms(seed, n)
     th = juniform(u["box"], 0.0, TWO_PI)
     gth = f32(f32(th + PI) + juniform(u["goal"], -NOISE, NOISE))
@@ -107,7 +109,9 @@ def reset_single(seed: int, n: int, max_restarts: int = 64):
     # get_node_goal_rng(key, 0.24, 2, n, 0.06) without the goals: zero rows of the work array count (env/utils.py:150-151)
     placed = False
     pos = np.zeros((n, 2), f32)
+    attempts = 0
     for _ in range(max_restarts):
+        attempts += 1
         pos = np.zeros((n, 2), f32)
         failed = False
         for i in range(n):
@@ -126,6 +130,8 @@ def reset_single(seed: int, n: int, max_restarts: int = 64):
         if not failed:
             placed = True
             break
+    if stats is not None:
+        stats["restarts"], stats["draws"], stats["pos"] = attempts - 1, st.d, pos.copy()
     agent[:, 0] = (pos[:, 0] - SHIFT) + bx
     agent[:, 1] = (pos[:, 1] - SHIFT) + by
     return agent, np.array([bx, by, 0, 0], f32), scene, placed
@@ -150,8 +156,9 @@ def _closest_on_line(lx, ly, rx, ry, px, py):
     return (lx - sd * rx).astype(f32), (ly - sd * ry).astype(f32)
 
 
-def contact_force(px, py, bx, by):
-    """force on the agent at (px, py) from the hollow box at (bx, by) (any broadcastable shapes) -> fx, fy, active.
+def contact_force(px, py, bx, by, with_dist=False):
+    """force on the agent at (px, py) from the hollow box at (bx, by) (any broadcastable shapes) -> fx, fy, active
+    (and, with_dist, the distance to the closest point of the box).
     get_all_lines_box (geometry.py:73-94): sides 1, 2 at box +- (1, 0) * 0.3 along (C90, 1), sides 3, 4 at
     box +- (C90, 1) * 0.3 along (1, 0); get_closest_point_box keeps the first of equal distances (strict <)."""
     h1x, h1y = f32(1) * HALF_SIDE, f32(0) * HALF_SIDE
@@ -176,22 +183,32 @@ def contact_force(px, py, bx, by):
     fy = (((COLLISION_FORCE * dy) / den) * pen).astype(f32)
     off = (dist < MIN_DIST) | (dist > DIST_MIN)
     fx, fy = np.where(off, f32(0), fx), np.where(off, f32(0), fy)
+    if with_dist:
+        return fx.astype(f32), fy.astype(f32), ~off, dist
     return fx.astype(f32), fy.astype(f32), ~off
 
 
-def physics(agent, body, action):
+def physics(agent, body, action, trace=False):
     """4 World.step calls of 5 substeps (vmas_reverse_transport.py:150-192, world.py:78-135) -> next agent, next body,
-    contact [B] (a contact force acted in some substep)"""
+    contact [B] (a contact force acted in some substep).  trace: additionally [B, 2] float64, the smallest |dist - DIST_MIN|
+    and the smallest |dist - MIN_DIST| over all agents and the substeps 1 .. 19 (NaN distances are skipped): how close the
+    step came to a force threshold after its first substep"""
     agent, body = agent.astype(f32), body.astype(f32)
     B, n = agent.shape[:2]
     u = (np.clip(action.astype(f32), f32(-1), f32(1)) * U_MULT).astype(f32)
     px, py, vx, vy = (agent[..., k].copy() for k in range(4))
     bx, by, bvx, bvy = (body[:, k:k + 1].copy() for k in range(4))
     contact = np.zeros(B, bool)
-    for _ in range(FRAME_SKIP):
+    near = np.full((B, 2), np.inf)
+    for w in range(FRAME_SKIP):
         for s in range(SUBSTEPS):
-            fx, fy, act = contact_force(px, py, bx, by)
+            fx, fy, act, dist = contact_force(px, py, bx, by, with_dist=True)
             contact |= act.any(axis=1)
+            if trace and (w, s) != (0, 0):
+                d64 = dist.astype(np.float64)
+                for c, thr in enumerate((DIST_MIN, MIN_DIST)):
+                    gap = np.where(np.isnan(d64), np.inf, np.abs(d64 - float(thr)))
+                    near[:, c] = np.minimum(near[:, c], gap.min(axis=1))
             Fbx, Fby = -fx[:, 0:1], -fy[:, 0:1]            # the box collects -f of each agent in agent order
             for j in range(1, n):
                 Fbx, Fby = (Fbx + -fx[:, j:j + 1]).astype(f32), (Fby + -fy[:, j:j + 1]).astype(f32)
@@ -210,6 +227,8 @@ def physics(agent, body, action):
             by = np.clip((by + bvy * SUB_DT).astype(f32), -SEMIDIM, SEMIDIM)
     nagent = np.stack([px, py, vx, vy], -1).astype(f32)
     nbody = np.concatenate([bx, by, bvx, bvy], -1).astype(f32)
+    if trace:
+        return nagent, nbody, contact, near
     return nagent, nbody, contact
 
 
