@@ -26,6 +26,21 @@ struct StepArgs {
   float thr2_comm, thr2_lidar;              // sqrt_threshold(comm_radius), sqrt_threshold(lidar_mask_radius) (wave kernel)
 };
 
+// What the act-step form of the wave kernel (env_wave.hip, dgppo_env_act_step_feats) takes beside StepArgs: the policy's
+// head output it samples the action from, and where the features and layer-0 queries of state t+1 go
+struct ActFeatArgs {
+  const float* ms;       // [B * n, 4]: mean0, mean1, std_trans0, std_trans1
+  const float* eps;      // [B * n, 2] noise (sample != 0)
+  float* action;         // [B, n, 2] out: what policy_head_kernel writes in modes 0 / 1
+  float* log_pi;         // [B, n] out (sample != 0)
+  int sample;            // 1: tanh(mean + std eps) and log pi; 0: tanh(mean)
+  float *Xa, *Xo, *efeat, *emask;   // GraphFeats layout at Fp = 8 of state t+1; Xa == NULL: not emitted
+  const float *Mcat, *cvec;         // [8, 24], [24]
+  float* qt0;                       // [B * n, 24] = Xa Mcat + cvec of state t+1; NULL: not emitted
+  int max_blocks;                   // > 0: cap of the persistent grid (tests: several rounds at a small batch)
+};
+struct NoActFeat {};
+
 // state2feat: lidar_bicycle_target.py:113-118 (identity for the double integrator)
 template <int SD>
 __device__ inline void state2feat(const float* s, float* f) {
@@ -193,3 +208,5 @@ __device__ inline void ray_hit(float x1, float y1, float rc, float rs, float sr,
 // n_obs), and the launch of that instance (step_family in env_step.hip decides when it runs)
 bool lidar_wave_has_instance(const dgppo_env_cfg& c);
 void launch_lidar_wave(const StepArgs& a, hipStream_t s);
+bool lidar_wave_has_act_instance(const dgppo_env_cfg& c);                             // ... and its act-step form
+void launch_lidar_wave_act(const StepArgs& a, const ActFeatArgs& f, hipStream_t s);   // MODE_STEP, compact record

@@ -790,6 +790,65 @@ extern "C" int32_t dgppo_env_step(const dgppo_env_cfg* cfg, const float* agent, 
                      gout, B, stream);
 }
 
+// ---- act-step: sample, step and emit the next features in one launch (env_wave.hip, FUSE form) --------------------------
+// what step_family asks of the wave kernel (alignment aside, which the entry point checks operand by operand), and the
+// widths its epilogues are written for: Fp = 8 node rows, H = 3 heads
+static bool act_step_ok(const dgppo_env_cfg& c, int Fp, int H) {
+  const bool lidar32 = cfg_is_lidar(c) && cfg_is_base_kind(c) && c.n_obs > 0 && c.n_rays == 32;
+  return lidar32 && c.top_k == 8 && c.eye_offset >= c.comm_radius && c.node_dim <= 8 && Fp == 8 && H == 3 && lidar_wave_has_act_instance(c);
+}
+
+extern "C" int32_t dgppo_env_act_step_feats_supported(const dgppo_env_cfg* cfg, int32_t Fp, int32_t H) {
+  if (!cfg || dgppo_validate_cfg(cfg) != 0 || cfg_is_vmas(*cfg)) return 0;
+  return act_step_ok(*cfg, Fp, H) ? 1 : 0;
+}
+
+extern "C" int32_t dgppo_env_act_step_feats(const dgppo_env_cfg* cfg, const float* agent, const float* goal, const float* obst,
+                                            const float* hits, const float* ray_cos, const float* ray_sin, const float* ms,
+                                            const float* eps, int32_t sample, float* action, float* log_pi, float* next_agent,
+                                            float* next_hits, float* reward, float* cost, float* Xa, float* Xo, float* efeat,
+                                            float* emask, int32_t Fp, const float* Mcat, const float* cvec, float* qt0, int32_t H,
+                                            int32_t max_blocks, int32_t B, void* stream) {
+  if (!cfg) { dgppo_set_error("cfg is NULL"); return -1; }
+  int32_t rc = dgppo_validate_cfg(cfg);
+  if (rc) return rc;
+  DGPPO_REFUSE_VMAS(cfg, "dgppo_env_act_step_feats", "dgppo_vmas_step");
+  DGPPO_REQUIRE(act_step_ok(*cfg, Fp, H), "env_act_step_feats: no kernel for this configuration, Fp=%d, H=%d (ask dgppo_env_act_step_feats_supported)", Fp, H);
+  DGPPO_REQUIRE(B >= 0 && max_blocks >= 0, "env_act_step_feats: B and max_blocks must be >= 0 (got %d, %d)", B, max_blocks);
+  if (B == 0) return 0;
+  DGPPO_REQUIRE(agent && goal && obst && hits && ray_cos && ray_sin, "env_act_step_feats: NULL state operand");
+  DGPPO_REQUIRE(ms && action && next_agent && next_hits && reward && cost, "env_act_step_feats: NULL operand");
+  DGPPO_REQUIRE(!sample || (eps && log_pi), "env_act_step_feats(sample): eps and log_pi must not be NULL");
+  DGPPO_REQUIRE(!Xa || (Xo && efeat && emask), "env_act_step_feats: Xa needs Xo, efeat and emask");
+  DGPPO_REQUIRE(!qt0 || (Mcat && cvec), "env_act_step_feats: qt0 needs Mcat and cvec");
+  auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+  DGPPO_REQUIRE(al16(agent) && al16(goal) && al16(obst) && al16(hits) && al16(next_agent) && al16(next_hits),
+                "env_act_step_feats: the record operands must be 16-byte aligned");
+  DGPPO_REQUIRE(al16(Xa) && al16(Xo) && al16(efeat) && al16(emask) && al16(qt0),
+                "env_act_step_feats: Xa, Xo, efeat, emask and qt0 must be 16-byte aligned");
+  DGPPO_REQUIRE((((uintptr_t)ms | (uintptr_t)eps | (uintptr_t)action | (uintptr_t)log_pi | (uintptr_t)Mcat | (uintptr_t)cvec) & 3) == 0,
+                "env_act_step_feats: operands must be 4-byte aligned");
+  StepArgs a;
+  a.cfg = *cfg;
+  a.agent = agent; a.action = nullptr; a.goal = goal; a.obst = obst; a.hits = hits;
+  a.ray_cos = ray_cos; a.ray_sin = ray_sin;
+  a.next_agent = next_agent; a.next_hits = next_hits; a.reward = reward; a.cost = cost;
+  a.has_graph = 0;
+  a.g = dgppo_graph_out{};
+  a.mode = MODE_STEP;
+  a.B = B;
+  a.rcp_n = fdiv_rcp(cfg->n_agents); a.rcp_k = fdiv_rcp(cfg->top_k); a.rcp_no = fdiv_rcp(cfg->n_obs);
+  a.rcp_no4 = fdiv_rcp(4 * cfg->n_obs);
+  a.thr2_comm = sqrt_threshold(cfg->comm_radius);
+  a.thr2_lidar = sqrt_threshold(cfg->lidar_mask_radius);
+  ActFeatArgs f;
+  f.ms = ms; f.eps = eps; f.action = action; f.log_pi = log_pi; f.sample = sample ? 1 : 0;
+  f.Xa = Xa; f.Xo = Xo; f.efeat = efeat; f.emask = emask; f.Mcat = Mcat; f.cvec = cvec; f.qt0 = qt0; f.max_blocks = max_blocks;
+  launch_lidar_wave_act(a, f, (hipStream_t)stream);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int32_t dgppo_graph_materialize(const dgppo_env_cfg* cfg, const float* agent, const float* goal,
                                            const float* obst, const float* hits, const dgppo_graph_out* gout, int32_t B,
                                            void* stream) {

@@ -41,6 +41,8 @@
 // ray origin — d . (c_o - p) < -(h_o + 0.05) — no segment of o is valid for this ray (both tests are evaluated in fp32
 // with errors < 1e-6 against a slack of 0.048; a NaN fails both comparisons and keeps the triple).
 #include "env_step.h"
+#include "nn_head.h"
+#include <type_traits>
 
 // minimum waves per SIMD the register allocator must leave room for (VGPR budget 512 / n, granule 8)
 #ifndef DGPPO_WAVE_WPE
@@ -140,6 +142,14 @@ struct alignas(16) WaveLds {
   float nodes[GRAPH ? ceil4(C::N * C::ND) : 4];
 };
 
+// the act-step form: the compact slab and, once per wave, the layer-0 query weights [FP, HF] | [HF]
+constexpr int ACT_FP = 8, ACT_H = 3, ACT_HF = ACT_H * ACT_FP;
+constexpr int ACT_MAX_NA = 8;
+template <int SD, bool SPREAD, int NA, int NO>
+struct alignas(16) WaveLdsAct : WaveLds<SD, SPREAD, NA, NO, false> {
+  float mc[ACT_FP * ACT_HF + ACT_HF];
+};
+
 __device__ inline float raw_min(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ inline float raw_max(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 
@@ -182,10 +192,15 @@ __device__ inline float group_min(float x) {
 
 // MODE / GRAPH are compile-time: the training rollout (MODE_STEP, compact), the API step (MODE_STEP + GraphsTuple), the
 // sense-only pass of reset and the materialise-only pass each get their own straight-line code
-template <int SD, bool SPREAD, int NA, int NO, int WPB, int MODE, bool GRAPH>
-__global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(GRAPH ? DGPPO_WAVE_WPE : DGPPO_WAVE_WPE_COMPACT, 8))) lidar_wave_kernel(StepArgs a) {
+// FUSE (MODE_STEP, compact): the act-step form.  The wave draws its env's action from the policy's head output before the
+// step (policy_head_kernel's arithmetic, nn_head.h) and, after it, emits the graph features of state t+1 (graph_feats_kernel's
+// arithmetic at Fp = 8) and their layer-0 queries qt0 = Xa Mcat + cvec (dense_smallk_kernel's fmaf chain) from the values it holds
+template <int SD, bool SPREAD, int NA, int NO, int WPB, int MODE, bool GRAPH, bool FUSE = false>
+__global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu((GRAPH || FUSE) ? DGPPO_WAVE_WPE : DGPPO_WAVE_WPE_COMPACT, 8)))
+lidar_wave_kernel(StepArgs a, std::conditional_t<FUSE, ActFeatArgs, NoActFeat> f) {
+  static_assert(!FUSE || (MODE == MODE_STEP && !GRAPH), "the act-step form is a compact step");
   using C = WC<SD, SPREAD, NA, NO>;
-  using LT = WaveLds<SD, SPREAD, NA, NO, GRAPH>;
+  using LT = std::conditional_t<FUSE, WaveLdsAct<SD, SPREAD, NA, NO>, WaveLds<SD, SPREAD, NA, NO, GRAPH>>;
   constexpr int K = C::K, ND = C::ND, N = C::N, PAD = C::PAD, NIT = C::NIT, GS = C::GS, E = C::E;
   extern __shared__ float4 smem4[];
   int lane = threadIdx.x & 63;
@@ -200,22 +215,22 @@ __global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(G
   constexpr bool do_sense = (MODE != MODE_GRAPH);
   constexpr bool has_graph = GRAPH;
   const float sr = c.comm_radius;
-  const int r = lane & 31;                      // this lane's ray, for the whole kernel
-  const int hi_half = lane >> 5;                // which of the two agents of a wave iteration
-  const float cr = do_sense ? a.ray_cos[r] : 0.0f, sn = do_sense ? a.ray_sin[r] : 0.0f;
-  const uint32_t below = (1u << r) - 1u;        // lanes of my half with a smaller ray index
+  const int r0 = lane & 31;                     // this lane's ray, for the whole kernel
+  const int hi_half0 = lane >> 5;               // which of the two agents of a wave iteration
+  const float cr0 = (do_sense && !FUSE) ? a.ray_cos[r0] : 0.0f, sn0 = (do_sense && !FUSE) ? a.ray_sin[r0] : 0.0f;
+  const uint32_t below0 = (1u << r0) - 1u;      // lanes of my half with a smaller ray index
 
   // ---- input staging plan: item q (a float4) of the concatenation agent | goal | obst | hits | act of one env ----
   constexpr int I_AG = NA * SD / 4, I_OB = NO * 4, I_HI = (MODE != MODE_SENSE) ? NA * K * 2 / 4 : 0,
-                I_AC = (MODE == MODE_STEP) ? NA * 2 / 4 : 0;
+                I_AC = (MODE == MODE_STEP && !FUSE) ? NA * 2 / 4 : 0;     // (the act-step form makes its own action)
   constexpr int IT = 2 * I_AG + I_OB + I_HI + I_AC, NSLOT = (IT + 63) / 64;
   static_assert(MODE != MODE_STEP || (NA * 2) % 4 == 0, "the action block is staged as float4");
   const char* gsrc[NSLOT];
   uint32_t gstride[NSLOT];
   float4 pf[NSLOT];
-#pragma unroll
-  for (int j = 0; j < NSLOT; ++j) {
-    const int q = j * 64 + lane;
+  struct StageSrc { const char* p; uint32_t stride; };     // (returned by value: an array element passed by reference ends up in scratch)
+  auto stage_src = [&](int ln, int j) -> StageSrc {
+    const int q = j * 64 + ln;
     const char* base = reinterpret_cast<const char*>(a.agent);
     uint32_t stride = NA * SD * 4;
     int q0 = 0;
@@ -223,9 +238,15 @@ __global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(G
     if (q >= 2 * I_AG) { base = reinterpret_cast<const char*>(a.obst); stride = NO * 64; q0 = 2 * I_AG; }
     if (I_HI > 0 && q >= 2 * I_AG + I_OB) { base = reinterpret_cast<const char*>(a.hits); stride = NA * K * 8; q0 = 2 * I_AG + I_OB; }
     if (I_AC > 0 && q >= 2 * I_AG + I_OB + I_HI) { base = reinterpret_cast<const char*>(a.action); stride = NA * 8; q0 = 2 * I_AG + I_OB + I_HI; }
-    gsrc[j] = base + (q - q0) * 16;
-    gstride[j] = stride;
+    return StageSrc{base + (q - q0) * 16, stride};
+  };
+#pragma unroll
+  for (int j = 0; j < NSLOT; ++j) {
+    const StageSrc ss = stage_src(lane, j);
+    gsrc[j] = ss.p;
+    gstride[j] = ss.stride;
   }
+  static_assert(!FUSE || (2 * NA <= 64 && ND <= ACT_FP), "one lane per action component; node rows fit Fp = 8");
   {
     const int b0 = blockIdx.x * WPB + wave;          // the first env's inputs fly while the images are initialised
     if (b0 < a.B) {
@@ -233,6 +254,10 @@ __global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(G
       for (int j = 0; j < NSLOT; ++j)
         if (j * 64 + lane < IT) pf[j] = *reinterpret_cast<const float4*>(gsrc[j] + (size_t)b0 * gstride[j]);
     }
+  }
+  if constexpr (FUSE) {                              // once per wave: the layer-0 query weights
+    if (f.qt0 != nullptr)
+      for (int i = lane; i < ACT_FP * ACT_HF + ACT_HF; i += 64) L.mc[i] = (i < ACT_FP * ACT_HF) ? f.Mcat[i] : f.cvec[i - ACT_FP * ACT_HF];
   }
   // ---- once per wave: the constant part of the node / state images (lidar_env/base.py:236-264, graph.py:214-218) ----
   if (has_graph)
@@ -248,22 +273,60 @@ __global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(G
     // unrolled) body is hoisted out of this loop and kept live — ~170 VGPRs, 3 waves per SIMD; recomputing them costs a
     // few dozen VALU instructions per env and keeps the kernel under 128
     asm volatile("" : "+v"(lane));
+    // The lane's own constants are kept across the envs, except in the act-step form: its head arithmetic needs the five
+    // registers (it fetches the ray's direction again, an L1 hit, and derives the rest from the opaque lane id)
+    const int r = FUSE ? (lane & 31) : r0;
+    const int hi_half = FUSE ? (lane >> 5) : hi_half0;
+    const float cr = FUSE ? a.ray_cos[lane & 31] : cr0, sn = FUSE ? a.ray_sin[lane & 31] : sn0;
+    const uint32_t below = FUSE ? ((1u << (lane & 31)) - 1u) : below0;
 #ifdef DGPPO_STAMPS
     const bool stamp_on = (b == 0);
     if ((threadIdx.x & 63) == 0 && gw < 8192 && b == gw) g_wspan[3 * gw + 1] = __builtin_amdgcn_s_memtime();
     if (blockIdx.x == 0 && threadIdx.x == 0 && stamp_on) g_wstamps[40] = __builtin_amdgcn_s_memrealtime();   // 100 MHz
 #endif
     PHASE("P0_stage", 0);
+    // act-step form: lane 2 i + d owns dimension d of agent i's action.  Its mean, std_trans and noise are requested here and
+    // not one env ahead: three more registers held across the whole body cost the kernel its fifth wave per SIMD
+    float h_mu = 0.0f, h_st = 0.0f, h_eps = 0.0f;
+    if constexpr (FUSE) {
+      if (lane < 2 * NA) {
+        const float* m = f.ms + ((size_t)b * NA + (lane >> 1)) * 4 + (lane & 1);
+        h_mu = m[0];
+        if (f.sample) { h_st = m[2]; h_eps = f.eps[(size_t)b * NA * 2 + lane]; }
+      }
+    }
     // ---- P0: the env's inputs arrive in registers (issued one env ahead), one ds_write_b128 per lane and slot ----
 #pragma unroll
     for (int j = 0; j < NSLOT; ++j)
       if (j * 64 + lane < IT) reinterpret_cast<float4*>(L.agent)[j * 64 + lane] = pf[j];
+    if constexpr (FUSE) {
+      // ---- the action (policy_head_kernel modes 0 / 1): one component per lane, log pi = lp_0 + lp_1 on the even lane ----
+      if (lane < 2 * NA) {
+        float act, lp = 0.0f;
+        if (f.sample) {
+          const float sd = tn_std(h_st);
+          act = tn_sample_dim(h_mu, sd, h_eps);
+          lp = tn_log_prob_dim(act, h_mu, sd);
+        } else {
+          act = tn_mode_dim(h_mu);
+        }
+        L.act[lane] = act;
+        f.action[(size_t)b * NA * 2 + lane] = act;
+        if (f.sample) {
+          const float lp1 = dpp<DPP_XOR1>(lp);       // both lanes of a pair are active
+          if ((lane & 1) == 0) f.log_pi[(size_t)b * NA + (lane >> 1)] = lp + lp1;
+        }
+      }
+    }
     {
       const int bn = b + gridDim.x * WPB;            // prefetch the next env of this wave while this one is processed
       if (bn < a.B) {
 #pragma unroll
-        for (int j = 0; j < NSLOT; ++j)
-          if (j * 64 + lane < IT) pf[j] = *reinterpret_cast<const float4*>(gsrc[j] + (size_t)bn * gstride[j]);
+        for (int j = 0; j < NSLOT; ++j) {
+          // (the act-step form works the plan out again from the opaque lane id: three registers fewer across the body)
+          const StageSrc ss = FUSE ? stage_src(lane, j) : StageSrc{gsrc[j], gstride[j]};
+          if (j * 64 + lane < IT) pf[j] = *reinterpret_cast<const float4*>(ss.p + (size_t)bn * ss.stride);
+        }
       }
     }
     WSYNC();
@@ -434,6 +497,50 @@ __global__ void __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(G
     if (a.next_agent != nullptr) {
       float4* o4 = reinterpret_cast<float4*>(a.next_agent + (size_t)b * NA * SD);
       for (int i = lane; i < NA * SD / 4; i += 64) o4[i] = reinterpret_cast<const float4*>(L.next)[i];
+    }
+    if constexpr (FUSE) {
+      // ---- act-step, early: what the next state alone decides.  Node rows [state | obs, goal, agent indicator | 0] of the
+      //      agents (Xa) and the goals (head of Xo), two 16-byte stores per row (graph_feats_kernel's vecX path) ----
+      if (f.Xa != nullptr) {
+#pragma unroll
+        for (int q0 = 0; q0 < 4 * NA; q0 += 64) {
+          const int q = q0 + lane;
+          if (q < 4 * NA) {
+            const int nd = q >> 1, col0 = (q & 1) * 4;
+            const bool is_goal = nd >= NA;
+            const float* src = is_goal ? L.goal + (nd - NA) * SD : L.next + nd * SD;
+            const int one = is_goal ? SD + 1 : SD + 2;
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const int col = col0 + k;
+              v[k] = (col < SD) ? src[col < SD ? col : 0] : ((col == one) ? 1.0f : 0.0f);
+            }
+            float* dst = is_goal ? f.Xo + ((size_t)b * (NA + NA * K) + (nd - NA)) * ACT_FP + col0
+                                 : f.Xa + ((size_t)b * NA + nd) * ACT_FP + col0;
+            *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+          }
+        }
+      }
+      // ---- qt0[row, c] = cvec[c] then fmaf over k ascending of (Xa[row, k], Mcat[k, c]): four columns per lane ----
+      if (f.qt0 != nullptr) {
+        constexpr int NQ = ACT_HF / 4;
+#pragma unroll
+        for (int q0 = 0; q0 < NA * NQ; q0 += 64) {
+          const int q = q0 + lane;
+          if (q < NA * NQ) {
+            const int row = q / NQ, c0 = (q - row * NQ) * 4;
+            float4 acc = *reinterpret_cast<const float4*>(L.mc + ACT_FP * ACT_HF + c0);
+#pragma unroll
+            for (int k = 0; k < ACT_FP; ++k) {
+              const float xv = (k < SD) ? L.next[row * SD + (k < SD ? k : 0)] : ((k == SD + 2) ? 1.0f : 0.0f);
+              const float4 w = *reinterpret_cast<const float4*>(L.mc + k * ACT_HF + c0);
+              acc.x = fmaf(xv, w.x, acc.x); acc.y = fmaf(xv, w.y, acc.y); acc.z = fmaf(xv, w.z, acc.z); acc.w = fmaf(xv, w.w, acc.w);
+            }
+            *reinterpret_cast<float4*>(f.qt0 + ((size_t)b * NA + row) * ACT_HF + c0) = acc;
+          }
+        }
+      }
     }
     if (has_graph) {                     // agent / goal rows of the images
       for (int q = lane; q < NA * SD; q += 64) {
@@ -847,6 +954,65 @@ DGPPO_PRAGMA(unroll DGPPO_WAVE_UNROLL_P3)
       float4* o4 = reinterpret_cast<float4*>(a.next_hits + (size_t)b * NA * K * 2);
       for (int i = lane; i < NA * K * 2 / 4; i += 64) o4[i] = reinterpret_cast<const float4*>(L.hits)[i];
     }
+    if constexpr (FUSE) {
+      // ---- act-step, late: the hit-node rows of Xo and the per-slot edge features and masks of graph_{t+1} ----
+      if (f.Xa != nullptr) {
+#pragma unroll
+        for (int q0 = 0; q0 < 2 * NA * K; q0 += 64) {
+          const int q = q0 + lane;
+          if (q < 2 * NA * K) {
+            const int h = q >> 1, col0 = (q & 1) * 4;
+            float v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const int col = col0 + k;
+              v[k] = (col < 2) ? L.hits[h * 2 + (col < 2 ? col : 0)] : ((col == SD) ? 1.0f : 0.0f);
+            }
+            *reinterpret_cast<float4*>(f.Xo + ((size_t)b * (NA + NA * K) + NA + h) * ACT_FP + col0) = make_float4(v[0], v[1], v[2], v[3]);
+          }
+        }
+        // Edge slots of agent i: the n agents, its goal slot(s), its k hits.  Single rounded differences; the masks
+        // fl(sqrt(s)) (+ eye_offset on the diagonal) < radius as s < sqrt_threshold(radius), like the GraphsTuple's edges
+        constexpr int S = NA + GS + K, NE = NA * S;
+        static_assert(NE % 4 == 0, "masks leave as float4");
+#pragma unroll
+        for (int base = 0; base < NE; base += 64) {
+          const int idx = base + lane;
+          bool mask = false;
+          if (idx < NE) {
+            const int i = idx / S, s = idx - i * S;
+            const float4 fi = reinterpret_cast<const float4*>(fa_ptr)[i];
+            const float px = L.next[i * SD], py = L.next[i * SD + 1];
+            float4 e;
+            if (s < NA) {
+              const float4 fj = reinterpret_cast<const float4*>(fa_ptr)[s];
+              e = make_float4(fi.x - fj.x, fi.y - fj.y, fi.z - fj.z, fi.w - fj.w);
+              const float dx = px - L.next[s * SD], dy = py - L.next[s * SD + 1];
+              mask = (i != s) && (dx * dx + dy * dy < a.thr2_comm);
+            } else if (s < NA + GS) {
+              const int gi = SPREAD ? (s - NA) : i;
+              const float4 fg = reinterpret_cast<const float4*>(fg_ptr)[gi];
+              e = make_float4(fi.x - fg.x, fi.y - fg.y, fi.z - fg.z, fi.w - fg.w);
+              mask = true;
+            } else {
+              const int m = s - NA - GS;
+              const float lx = px - L.hits[(i * K + m) * 2], ly = py - L.hits[(i * K + m) * 2 + 1];
+              e = make_float4(lx, ly, 0.0f, 0.0f);
+              mask = lx * lx + ly * ly < a.thr2_lidar;
+            }
+            reinterpret_cast<float4*>(f.efeat)[(size_t)b * NE + idx] = e;
+          }
+          const unsigned long long bits = __builtin_amdgcn_ballot_w64(mask);   // the 64 masks of this pass: lanes 0..15 write four each
+          const int i4 = base + 4 * lane;
+          if (lane < 16 && i4 < NE) {
+            const unsigned mb = (unsigned)(bits >> (4 * lane));
+            *reinterpret_cast<float4*>(f.emask + (size_t)b * NE + i4) =
+                make_float4((mb & 1u) ? 1.0f : 0.0f, (mb & 2u) ? 1.0f : 0.0f, (mb & 4u) ? 1.0f : 0.0f, (mb & 8u) ? 1.0f : 0.0f);
+          }
+        }
+      }
+      WSYNC();   // the next env overwrites next / hits only after these reads were issued
+    }
     if (!has_graph) continue;
     PHASE("P5_graph", 8);
     // ---- P5: padded GraphsTuple (lidar_env/base.py:227-271, lidar_spread.py:57-96, lidar_target.py:57-96, graph.py:35-44,212-247)
@@ -941,11 +1107,33 @@ void launch_inst(const StepArgs& a, hipStream_t s) {
   int blocks = (a.B + WPB - 1) / WPB;
   if (blocks > max_blocks) blocks = max_blocks;
   const dim3 g(blocks), t(WPB * 64);
-#define LAUNCH(M_, G_) hipLaunchKernelGGL((lidar_wave_kernel<SD, SPREAD, NA, NO, WPB, M_, G_>), g, t, (G_) ? smem_g : smem_c, s, a)
+#define LAUNCH(M_, G_) hipLaunchKernelGGL((lidar_wave_kernel<SD, SPREAD, NA, NO, WPB, M_, G_>), g, t, (G_) ? smem_g : smem_c, s, a, NoActFeat{})
   if (a.mode == MODE_STEP) { if (a.has_graph) LAUNCH(MODE_STEP, true); else LAUNCH(MODE_STEP, false); }
   else if (a.mode == MODE_SENSE) { if (a.has_graph) LAUNCH(MODE_SENSE, true); else LAUNCH(MODE_SENSE, false); }
   else LAUNCH(MODE_GRAPH, true);
 #undef LAUNCH
+}
+
+// the act-step form: same workgroup shape as the other forms, its own slab size and residency
+template <int SD, bool SPREAD, int NA, int NO>
+void launch_inst_act(const StepArgs& a, const ActFeatArgs& f, hipStream_t s) {
+  constexpr size_t per_wave_g = sizeof(WaveLds<SD, SPREAD, NA, NO, true>);
+  constexpr int WPB = (per_wave_g * 4 <= 40 * 1024) ? 4 : ((per_wave_g * 2 <= 52 * 1024) ? 2 : 1);
+  constexpr size_t smem = sizeof(WaveLdsAct<SD, SPREAD, NA, NO>) * WPB;
+  static_assert(smem <= 64 * 1024, "LDS slab too large");
+  auto kern = lidar_wave_kernel<SD, SPREAD, NA, NO, WPB, MODE_STEP, false, true>;
+  static int per_cu = 0, n_cu = 0;
+  if (per_cu == 0) {
+    int n = 0;
+    per_cu = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, WPB * 64, smem) == hipSuccess && n > 0) ? n : 1;
+    int dev = 0, v = 0;
+    n_cu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+  }
+  int max_blocks = n_cu * per_cu;
+  if (f.max_blocks > 0 && f.max_blocks < max_blocks) max_blocks = f.max_blocks;
+  int blocks = (a.B + WPB - 1) / WPB;
+  if (blocks > max_blocks) blocks = max_blocks;
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(WPB * 64), smem, s, a, f);
 }
 
 template <int SD_, bool SPREAD_, int NA_, int NO_>
@@ -981,6 +1169,15 @@ extern "C" int32_t dgppo_debug_wave_spans(unsigned long long* out) {
 #endif
 
 bool lidar_wave_has_instance(const dgppo_env_cfg& c) { return with_instance(c, [](auto) {}); }
+bool lidar_wave_has_act_instance(const dgppo_env_cfg& c) { return c.n_agents <= ACT_MAX_NA && lidar_wave_has_instance(c); }
+
+void launch_lidar_wave_act(const StepArgs& a, const ActFeatArgs& f, hipStream_t s) {
+  with_instance(a.cfg, [&](auto inst) {
+    using I = decltype(inst);
+    // (teams of 16 keep the four launches: like their other forms they need scratch at five waves per SIMD)
+    if constexpr (I::NA <= ACT_MAX_NA) launch_inst_act<I::SD, I::SPREAD, I::NA, I::NO>(a, f, s);
+  });
+}
 
 void launch_lidar_wave(const StepArgs& a, hipStream_t s) {
   with_instance(a.cfg, [&](auto inst) {

@@ -556,32 +556,9 @@ extern "C" int32_t dgppo_gru_bwd_dhn(const float* dhs, const float* Wh, const fl
 // ---------------------------------------------------------------------------------------------------------------------
 // tanh-Normal head (policy.py:62-74, distribution.py:10-46).  ms[row] = [mean0, mean1, std_trans0, std_trans1]
 // ---------------------------------------------------------------------------------------------------------------------
-#define STD_INIT_INV (-0.43275212956718856f)  // log(exp(0.5) - 1)
-#define STD_MIN 1e-5f
-#define THRESH 0.999f
-#define INV_THRESH 3.8002011672502f           // atanh(0.999)
-#define LOG_EPS (-6.907755278982137f)         // log(1 - 0.999)
-#define HALF_LOG_2PI 0.9189385332046727f
-#define LOG2_F 0.6931471805599453f
-
-__device__ inline float softplusf_(float x) { return (x > 20.0f) ? x : log1pf(expf(x)); }
-// log Phi(z): erfc for the bulk, asymptotic series for the far left tail (tfp special_math.log_ndtr).  The series
-// Phi(z) ~ phi(z) / (-z) * (1 - 1/z^2 + 3/z^4 - 15/z^6) is cut after its fourth term, so its relative error is the fifth,
-// 105 / z^8: 1.05e-6 at z = -10 but 2.7e-4 at z = -5.  It therefore starts at z <= -10; down to there the erfc form is
-// still made of normal fp32 numbers (erfcf(10 / sqrt 2) = 1.5e-23, expf(-50) = 1.9e-22).
-#define NDTR_SERIES_BELOW (-10.0f)
-__device__ inline float ndtr_tail_series(float z2) { return 1.0f - 1.0f / z2 + 3.0f / (z2 * z2) - 15.0f / (z2 * z2 * z2); }
-__device__ inline float log_ndtrf_(float z) {
-  if (z > NDTR_SERIES_BELOW) return logf(0.5f * erfcf(-z * 0.70710678118654752f));
-  const float z2 = z * z;
-  return -0.5f * z2 - logf(-z) - HALF_LOG_2PI + logf(ndtr_tail_series(z2));
-}
-// d/dz log Phi(z) = phi(z) / Phi(z); in the tail -z / series, with the terms of the value
-__device__ inline float dlog_ndtrf_(float z) {
-  if (z > NDTR_SERIES_BELOW) return 0.3989422804014327f * expf(-0.5f * z * z) / (0.5f * erfcf(-z * 0.70710678118654752f));
-  return -z / ndtr_tail_series(z * z);
-}
-__device__ inline float tanh_fldj(float x) { return 2.0f * (LOG2_F - x - softplusf_(-2.0f * x)); }
+// the per-dimension arithmetic (softplusf_, log_ndtrf_, tanh_fldj, tn_log_prob_dim, tn_std, tn_sample_dim, tn_mode_dim) is
+// shared with the act-step form of the wave-per-env kernel: nn_head.h
+#include "nn_head.h"
 
 struct HeadArgs {
   const float* ms;        // [rows, 4]
@@ -599,15 +576,6 @@ struct HeadArgs {
   float clip_eps, coef_ent, inv_count;
 };
 
-__device__ inline float tn_log_prob_dim(float act, float mu, float sd) {
-  const float ac = fminf(fmaxf(act, -THRESH), THRESH);
-  if (ac <= -THRESH) return log_ndtrf_((-INV_THRESH - mu) / sd) - LOG_EPS;
-  if (ac >= THRESH) return log_ndtrf_(-(INV_THRESH - mu) / sd) - LOG_EPS;
-  const float x = atanhf(ac);
-  const float z = (x - mu) / sd;
-  return -0.5f * z * z - logf(sd) - HALF_LOG_2PI - tanh_fldj(x);
-}
-
 __global__ void __launch_bounds__(256) policy_head_kernel(HeadArgs a) {
   float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};        // eval: sum loss, sum entropy, sum(l2 > l1), sum |ratio - 1|
   const int rows_pad = (a.rows + 255) & ~255;
@@ -618,17 +586,17 @@ __global__ void __launch_bounds__(256) policy_head_kernel(HeadArgs a) {
   const float mu[2] = {m.x, m.y};
   const float st[2] = {m.z, m.w};
   float sd[2];
-  for (int d = 0; d < 2; ++d) sd[d] = softplusf_(st[d] + STD_INIT_INV) + STD_MIN;
+  for (int d = 0; d < 2; ++d) sd[d] = tn_std(st[d]);
   if (a.mode == 1) {  // PPOPolicy.get_action: tanh(mean)
     if (valid) {
-      a.action[row * 2] = tanhf(mu[0]);
-      a.action[row * 2 + 1] = tanhf(mu[1]);
+      a.action[row * 2] = tn_mode_dim(mu[0]);
+      a.action[row * 2 + 1] = tn_mode_dim(mu[1]);
     }
     continue;
   }
   float act[2];
   if (a.mode == 0) {  // sample_action: tanh(mean + std * eps); log_prob recomputes atanh(clip(a)) like the reference
-    for (int d = 0; d < 2; ++d) act[d] = tanhf(mu[d] + sd[d] * a.eps[row * 2 + d]);
+    for (int d = 0; d < 2; ++d) act[d] = tn_sample_dim(mu[d], sd[d], a.eps[row * 2 + d]);
     if (valid) {
       a.action[row * 2] = act[0];
       a.action[row * 2 + 1] = act[1];

@@ -129,7 +129,8 @@ class OptState:
 class Engine:
     def __init__(self, cfg: N.EnvCfg, hyper: Hyper, device, T: int = 128,
                  allreduce: Optional[Callable[[torch.Tensor], None]] = None, world: int = 1, prepass_graphs: int = 1 << 20,
-                 use_graphs: bool = False, multi_stream: bool = False, algo: str = "dgppo", rank: int = 0):
+                 use_graphs: bool = False, multi_stream: bool = False, algo: str = "dgppo", rank: int = 0,
+                 fused_step: bool = True):
         self.cfg, self.hp, self.device, self.T = cfg, hyper, device, T
         assert algo in ("dgppo", "informarl", "hcbfcrpo", "informarl_lagr"), algo
         # "informarl" / "hcbfcrpo": no constraint-value network and no deterministic rollout (informarl.py, hcbfcrpo.py);
@@ -142,6 +143,9 @@ class Engine:
         # run the Vl / Vh / policy updates of a minibatch on three HIP streams (they are independent)
         self.multi_stream = multi_stream and os.environ.get("DGPPO_MULTI_STREAM", "1") != "0"
         self._side_streams = None
+        # one launch per rollout step for head sampling + env.step + the next step's features and layer-0 queries, where the
+        # C ABI has such a kernel for the configuration (dgppo_env_act_step_feats_supported); else the four launches
+        self.fused_step = bool(fused_step) and OE.act_step_feats_supported(cfg, nets.input_width(cfg), nets.H_HEADS)
         self._ro_cache: Dict[tuple, dict] = {}
         self._upd_graph: dict = {}
         self.n_cost = cfg.n_cost              # 2, or 3 with MPEConnectSpread's connectivity cost
@@ -281,6 +285,23 @@ class Engine:
         """the T env steps of a rollout: policy forward (GNN + GRU + head) and env.step, all on the current stream."""
         cfg, T, n = self.cfg, self.T, self.cfg.n_agents
         tag = "ro" if stochastic else "rod"    # separate scratch per kind: the two rollouts may run on different streams
+        if self.fused_step:
+            # features and queries of step 0 from the stand-alone kernels; every step's launch then leaves those of the next
+            # state in the same buffers, which the next forward reads
+            pol, R = self.policy, B * n
+            feats = self._feats(tag, ro.states_tm[0], B)
+            Mcat, cvec = pol.pp("gnn0.Mcat"), pol.pp("gnn0.cvec")
+            qt0 = pol.arena.get(f"{tag}.qt0", R, Mcat.shape[1])
+            K.dense_fwd(feats.Xa, Mcat, cvec, qt0)
+            for t in range(T):
+                act = pol.forward(feats, n_seq=R, T=1, h0=ro.rnn_tm[t].view(R, self.HC), tag=tag,
+                                  hs_out=ro.rnn_tm[t + 1].view(R, self.HC), train=False, qt0=qt0)
+                nxt = dict(Xa=feats.Xa, Xo=feats.Xo, efeat=feats.efeat, emask=feats.emask, Fp=feats.Fp, Mcat=Mcat, cvec=cvec,
+                           qt0=qt0, H=nets.H_HEADS) if t + 1 < T else {}      # nothing reads the features of the last state
+                OE.act_step_feats(cfg, ro.states_tm[t], act["ms"], eps[t] if stochastic else None, ro.action_tm[t],
+                                  ro.log_pi_tm[t] if stochastic else None, ro.states_tm[t + 1], ro.reward_tm[t], ro.cost_tm[t],
+                                  **nxt)
+            return
         for t in range(T):
             feats = self._feats(tag, ro.states_tm[t], B)
             act = self.policy.forward(feats, n_seq=B * n, T=1, h0=ro.rnn_tm[t].view(B * n, self.HC), tag=tag,

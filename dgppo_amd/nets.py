@@ -276,8 +276,10 @@ class Net:
 
     # ---- forward ---------------------------------------------------------------------------------------------------
     def forward(self, feats: GraphFeats, n_seq: int, T: int, h0: Optional[torch.Tensor], tag: str = "f",
-                hs_out: Optional[torch.Tensor] = None, train: bool = True):
+                hs_out: Optional[torch.Tensor] = None, train: bool = True, qt0: Optional[torch.Tensor] = None):
         """Trunk + GRU + output Dense(s).  Graphs are ordered (group, time): G = (n_seq / n_inner) * T.
+        qt0: the layer-0 queries Xa Mcat0 + cvec0 [G * n, H * Fp] where the caller already holds them (the one-launch rollout
+        step emits them with the features); the layer-0 Dense is then skipped.
         Returns a dict of activations (views into this net's arena, valid until the next forward with the same tag)."""
         cfg, G, A = self.cfg, feats.G, self.arena
         n = cfg.n_agents
@@ -287,8 +289,12 @@ class Net:
         Xa, Xo = feats.Xa, feats.Xo
         xo_fused = None
         for l, (f, fp, d, kp) in enumerate(self.dims):
-            qt = A.get(f"{tag}.qt{l}", R, H_HEADS * fp)
-            K.dense_fwd(Xa, self.pp(f"gnn{l}.Mcat"), self.pp(f"gnn{l}.cvec"), qt)
+            if l == 0 and qt0 is not None:
+                assert tuple(qt0.shape) == (R, H_HEADS * fp), (tuple(qt0.shape), R, H_HEADS * fp)
+                qt = qt0
+            else:
+                qt = A.get(f"{tag}.qt{l}", R, H_HEADS * fp)
+                K.dense_fwd(Xa, self.pp(f"gnn{l}.Mcat"), self.pp(f"gnn{l}.cvec"), qt)
             zcat = A.get(f"{tag}.zcat{l}", R, kp)
             attn = A.get(f"{tag}.attn{l}", R, cfg.fan_in, H_HEADS) if train else None    # only the backward reads the weights
             if xo_fused is not None:      # other nodes' rows recomputed in the kernel from the raw features (see below)

@@ -283,6 +283,52 @@ def step(cfg: N.EnvCfg, st: State, action, nst: State, reward, cost, graph: Opti
              cost, graph)
 
 
+def act_step_feats_supported(cfg: N.EnvCfg, Fp: int, H: int) -> bool:
+    """does the configuration have the one-launch rollout step (dgppo_env_act_step_feats) at node width Fp and H heads?"""
+    return bool(N.lib().dgppo_env_act_step_feats_supported(C.byref(cfg), C.c_int32(Fp), C.c_int32(H)))
+
+
+def act_step_feats(cfg: N.EnvCfg, st: State, ms, eps, action, log_pi, nst: State, reward, cost, Xa=None, Xo=None, efeat=None,
+                   emask=None, Fp: int = 8, Mcat=None, cvec=None, qt0=None, H: int = 3, max_blocks: int = 0):
+    """dgppo_env_act_step_feats: the action from the head output ms [B * n, 4] (eps [B * n, 2] given: sampled, with log_pi
+    [B, n]; eps None: tanh(mean)), the env step from st into nst with it, and — where given — the graph features Xa / Xo /
+    efeat / emask of the new state (GraphFeats buffers) and its layer-0 queries qt0 = Xa Mcat + cvec"""
+    s, e, ns = st.step, st.env, nst.step
+    agent = s["agent"]
+    B, n = agent.shape[0], cfg.n_agents
+    rc, rs = _rays(cfg, agent.device)
+    sample = eps is not None
+    N.expect_shape(ms, (B * n, 4), "ms")
+    N.expect_shape(action, (B, n, 2), "action")
+    N.expect_shape(ns["agent"], (B, n, cfg.state_dim), "next_agent")
+    N.expect_shape(ns["hits"], (B, n, cfg.top_k, 2), "next_hits")
+    N.expect_shape(reward, (B,), "reward")
+    N.expect_shape(cost, (B, n, cfg.n_cost), "cost")
+    if sample:
+        N.expect_shape(eps, (B * n, 2), "eps")
+        N.expect_shape(log_pi, (B, n), "log_pi")
+    if Xa is not None:
+        S = cfg.fan_in
+        N.expect_shape(Xa, (B * n, Fp), "Xa")
+        N.expect_shape(Xo, (B * (cfg.num_nodes - 1 - n), Fp), "Xo")
+        N.expect_shape(efeat, (B * n, S, 4), "efeat")
+        N.expect_shape(emask, (B * n, S), "emask")
+    if qt0 is not None:
+        N.expect_shape(Mcat, (Fp, H * Fp), "Mcat")
+        N.expect_shape(cvec, (H * Fp,), "cvec")
+        N.expect_shape(qt0, (B * n, H * Fp), "qt0")
+    rc_ = N.lib().dgppo_env_act_step_feats(
+        C.byref(cfg), N.ptr(agent, name="agent"), N.ptr(e["goal"], name="goal"), N.ptr(e.get("obst"), name="obst"),
+        N.ptr(s.get("hits"), name="hits"), N.ptr(rc, name="ray_cos"), N.ptr(rs, name="ray_sin"), N.ptr(ms, name="ms"),
+        N.ptr(eps, name="eps"), C.c_int32(1 if sample else 0), N.ptr(action, name="action"),
+        N.ptr(log_pi if sample else None, name="log_pi"), N.ptr(ns["agent"], name="next_agent"),
+        N.ptr(ns["hits"], name="next_hits"), N.ptr(reward, name="reward"), N.ptr(cost, name="cost"), N.ptr(Xa, name="Xa"),
+        N.ptr(Xo if Xa is not None else None, name="Xo"), N.ptr(efeat if Xa is not None else None, name="efeat"),
+        N.ptr(emask if Xa is not None else None, name="emask"), C.c_int32(Fp), N.ptr(Mcat, name="Mcat"),
+        N.ptr(cvec, name="cvec"), N.ptr(qt0, name="qt0"), C.c_int32(H), C.c_int32(max_blocks), C.c_int32(B), N.stream_ptr())
+    N.check(rc_, "dgppo_env_act_step_feats")
+
+
 def materialize(cfg: N.EnvCfg, st: State, graph: Dict[str, torch.Tensor]):
     if cfg.is_vmas:
         return vmas_graph_materialize(cfg, st.agent, st.body, st.scene, graph)

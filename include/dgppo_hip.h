@@ -147,6 +147,31 @@ int32_t dgppo_env_step(const dgppo_env_cfg* cfg,
                        float* next_agent, float* next_hits, float* reward, float* cost,
                        const dgppo_graph_out* gout, int32_t B, void* stream);
 
+/* One rollout step after the policy's forward, in one launch: draw the action from the head output (what
+ * dgppo_policy_head does in modes 0 / 1), step the env (what dgppo_env_step writes to the compact record), and emit the
+ * graph features of state t+1 (what dgppo_graph_feats gives for it at Fp = 8) and their layer-0 queries
+ * qt0 = Xa Mcat + cvec (what dgppo_dense_fwd gives) -- each bit for bit.
+ * dgppo_env_act_step_feats_supported: 1 if the configuration has such a kernel: a base LiDAR kind with 32 rays, top-k 8,
+ * n_obs >= 1, eye_offset >= comm_radius, n_agents <= 8 and (state_dim, n_agents, n_obs) among the wave-per-env instances, at Fp = 8 and
+ * H = 3; the entry point refuses everything else.
+ *   agent, goal, obst, hits, ray_cos, ray_sin       as dgppo_env_step (16-byte aligned)
+ *   ms         [B*n, 4]     head output: mean0, mean1, std_trans0, std_trans1
+ *   eps        [B*n, 2]     noise (sample != 0; else may be NULL)
+ *   sample     1: tanh(mean + std eps) and log pi; 0: tanh(mean)
+ *   action     [B, n, 2]    out
+ *   log_pi     [B, n]       out (sample != 0; else may be NULL)
+ *   next_agent, next_hits, reward, cost             out, as dgppo_env_step
+ *   Xa [B*n, 8], Xo [B*(n + n*k), 8], efeat [B*n, S, 4], emask [B*n, S]   out, of state t+1; Xa == NULL: not emitted
+ *   Mcat [8, 24], cvec [24], qt0 [B*n, 24]          qt0 out, of state t+1; qt0 == NULL: not emitted
+ *   max_blocks 0, or a cap of the persistent grid (tests)                                             */
+int32_t dgppo_env_act_step_feats_supported(const dgppo_env_cfg* cfg, int32_t Fp, int32_t H);
+int32_t dgppo_env_act_step_feats(const dgppo_env_cfg* cfg, const float* agent, const float* goal, const float* obst,
+                                 const float* hits, const float* ray_cos, const float* ray_sin, const float* ms,
+                                 const float* eps, int32_t sample, float* action, float* log_pi, float* next_agent,
+                                 float* next_hits, float* reward, float* cost, float* Xa, float* Xo, float* efeat,
+                                 float* emask, int32_t Fp, const float* Mcat, const float* cvec, float* qt0, int32_t H,
+                                 int32_t max_blocks, int32_t B, void* stream);
+
 /* Materialise the GraphsTuple of a stored compact record (lazy rollout.graph view):
  * same arithmetic as get_graph (lidar_env/base.py:227-271, mpe/base.py:211-241).     */
 int32_t dgppo_graph_materialize(const dgppo_env_cfg* cfg,
