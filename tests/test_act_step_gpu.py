@@ -21,7 +21,10 @@ from test_env_gpu import _mk, _to  # noqa: E402
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("ignore:The given NumPy array is not writable"),
               pytest.mark.filterwarnings("ignore:invalid value encountered")]
 f32 = np.float32
-INSTANCES = [("LidarSpread", 4, 2), ("LidarTarget", 8, 3), ("LidarBicycleTarget", 4, 3)]
+# every compiled instance of the act-step kernel (the INST list of csrc/env_wave.hip up to ACT_MAX_NA agents):
+# tests/test_act_step_instances_cpu.py holds this list to what dgppo_env_act_step_feats_supported answers
+INSTANCES = [("LidarSpread", 8, 3), ("LidarTarget", 8, 3), ("LidarSpread", 4, 2), ("LidarTarget", 4, 2),
+             ("LidarBicycleTarget", 4, 3)]
 FP, H = 8, 3
 GUARD = 64                 # sentinel floats either side of an output (a multiple of 4: the outputs stay 16-byte aligned)
 SENTINEL = 0x7FC0BEEF      # as a float: a quiet NaN with a payload no kernel produces
@@ -249,10 +252,12 @@ def test_unsupported_configurations_are_refused(cuda):
     odd, _ = _mk("LidarSpread", 3, 2)                                   # no wave-per-env instance for three agents
     mpe = N.make_env_cfg(N.ENV_KINDS["MPESpread"], 4, 2)
     vmas = N.make_env_cfg(N.ENV_KINDS["VMASReverseTransport"], 4, 0)
-    for cfg in (odd, mpe, vmas):
+    # the 16-agent wave instances keep the four launches (above ACT_MAX_NA): no act-step form is compiled for them
+    big = [_mk("LidarSpread", 16, 8)[0], _mk("LidarBicycleTarget", 16, 8)[0]]
+    for cfg in (odd, mpe, vmas, *big):
         assert not OE.act_step_feats_supported(cfg, FP, H)
     B = 2
-    for cfg, fp, h in ((odd, FP, H), (ok, 12, H), (ok, FP, 2)):
+    for cfg, fp, h in ((odd, FP, H), (ok, 12, H), (ok, FP, 2), (big[0], FP, H), (big[1], FP, H)):
         n = cfg.n_agents
         st = _random_state(cfg, B, cuda, 1)
         z = lambda *s: torch.zeros(*s, device=cuda)
@@ -271,16 +276,20 @@ def test_unsupported_configurations_are_refused(cuda):
     with pytest.raises(ValueError, match="16-byte aligned"):
         OE.act_step_feats(ok, st, z(B * n, 4), None, z(B, n, 2), None, st.like(), z(B), z(B, n, 2), off,
                           z(B * (ok.num_nodes - 1 - n), FP), z(B * n, ok.fan_in, 4), z(B * n, ok.fan_in), FP)
+    # and an engine asked for the fused step on them takes the four launches
+    from dgppo_amd import engine as EN
+    for cfg in big:
+        assert EN.Engine(cfg, EN.Hyper(batch_size=8, rnn_step=4, train_steps=10), cuda, T=4, fused_step=True).fused_step is False
 
 
 # ---- engine level --------------------------------------------------------------------------------------------------------
-def _engine(cfg, dev, fused, graphs):
+def _engine(cfg, dev, fused, graphs, B=37, T=4):
     from dgppo_amd import engine as EN, init
-    eng = EN.Engine(cfg, EN.Hyper(batch_size=37 * 4, rnn_step=4, train_steps=10), dev, T=4, use_graphs=graphs, multi_stream=graphs,
+    eng = EN.Engine(cfg, EN.Hyper(batch_size=B * T, rnn_step=T, train_steps=10), dev, T=T, use_graphs=graphs, multi_stream=graphs,
                     fused_step=fused)
     eng.policy.load_tree(init.init_policy(0, cfg.node_dim, 2, 2))
     eng.Vl.load_tree(init.init_value(0, cfg.node_dim, 1, 2, 2))
-    eng.Vh.load_tree(init.init_value(0, cfg.node_dim, 2, 1, 3))
+    eng.Vh.load_tree(init.init_value(0, cfg.node_dim, cfg.n_cost, 1, 3))
     eng.set_entropy_noise(1)
     return eng
 
@@ -295,16 +304,14 @@ def _record(ro):
     return out
 
 
-@pytest.mark.parametrize("graphs", [False, True], ids=["eager", "hipgraph"])
-def test_engine_rollouts_identical_with_and_without_the_fused_step(cuda, graphs):
-    """LidarSpread n = 4, B = 37, T = 4: every array of both records and both value pre-passes, fused_step on against off; with
-    HIP graphs the second call of each engine replays its captured loop"""
-    cfg, _ = _mk("LidarSpread", 4, 2)
-    B = 37
+def _fused_on_off_identical(cuda, kind, n, n_obs, B, T, graphs):
+    """every array of both records and both value pre-passes, fused_step on against off; with HIP graphs the second call of
+    each engine replays its captured loop"""
+    cfg, _ = _mk(kind, n, n_obs)
     sd = torch.arange(1, B + 1, dtype=torch.int64, device=cuda) * 7919
     res = {}
     for fused in (True, False):
-        eng = _engine(cfg, cuda, fused, graphs)
+        eng = _engine(cfg, cuda, fused, graphs, B, T)
         assert eng.fused_step == fused
         for it in range(2 if graphs else 1):
             ro, det = eng.rollout_pair(sd + it, sd + 5 + it, noise_seed=3 + it)
@@ -322,3 +329,33 @@ def test_engine_rollouts_identical_with_and_without_the_fused_step(cuda, graphs)
     assert res[True].keys() == res[False].keys()
     for k in res[False]:
         assert torch.equal(_bits(res[True][k]), _bits(res[False][k])), f"{k} differs between fused_step=True and False"
+
+
+@pytest.mark.parametrize("graphs", [False, True], ids=["eager", "hipgraph"])
+def test_engine_rollouts_identical_with_and_without_the_fused_step(cuda, graphs):
+    """LidarSpread n = 4, B = 37, T = 4"""
+    _fused_on_off_identical(cuda, "LidarSpread", 4, 2, 37, 4, graphs)
+
+
+def _more_than_one_pass(dev):
+    """a batch no grid of the act-step kernel covers in one pass.  The engine leaves the grid at its cap, CUs x resident
+    workgroups with one env per wave; 4 waves per workgroup and 8 workgroups per CU (32 waves, the most a CU holds of a
+    256-thread workgroup) bound every instance's cap from above.  The 37 envs on top give some waves a second env and
+    others none, and leave the last workgroup ragged (37 = 9 x 4 + 1)"""
+    return 4 * 8 * torch.cuda.get_device_properties(dev).multi_processor_count + 37
+
+
+@pytest.mark.parametrize("graphs", [False, True], ids=["eager", "hipgraph"])
+@pytest.mark.parametrize("kind,n,n_obs,B,T", [("LidarSpread", 8, 3, 37, 4),               # the benchmark's topology
+                                              ("LidarBicycleTarget", 4, 3, 37, 4),        # state_dim 5
+                                              ("LidarSpread", 4, 2, None, 3)],            # B = _more_than_one_pass
+                         ids=["spread8", "bicycle4", "spread4-two-passes"])
+def test_engine_fused_step_identical_at_more_shapes(cuda, kind, n, n_obs, B, T, graphs):
+    """the same comparison where the engine's loop differs from the kernel tests' own buffers: the instance bench.py times,
+    the five-word state, and a batch at which every persistent wave walks on to a second env inside the engine's loop — the
+    features and qt0 each step's launch leaves in place are then written and read env-strided, and the step at t = T - 1
+    passes no feature buffers"""
+    if B is None:
+        B = _more_than_one_pass(cuda)
+        assert B > 4 * 8 * torch.cuda.get_device_properties(cuda).multi_processor_count
+    _fused_on_off_identical(cuda, kind, n, n_obs, B, T, graphs)
