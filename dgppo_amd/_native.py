@@ -176,6 +176,14 @@ def lib() -> C.CDLL:
     v = l.dgppo_abi_version()
     if v != ABI_VERSION:
         raise RuntimeError(f"dgppo_amd: ABI mismatch: library {v}, python {ABI_VERSION}")
+    # the rollout landscape's entry points (csrc/env_sweep.hip) take floats by value and many pointers: declared, so that a
+    # plain Python number or None converts as the prototype says
+    p, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+    l.dgppo_env_sweep_fork.restype = i32
+    l.dgppo_env_sweep_fork.argtypes = [C.POINTER(EnvCfg), p, i64, p, p, p, i64, p, p, p, i32, i32, p, i32, p, i32, p, i64, i32,
+                                       p, p, p, p, p, p]
+    l.dgppo_constraint_return.restype = i32
+    l.dgppo_constraint_return.argtypes = [p, i64, i32, i32, i32, i32, f32, f32, p, p, p]
     _lib = l
     return l
 

@@ -15,7 +15,7 @@ from .. import engine as EN
 from .. import init as INIT
 from .. import nets
 from .. import ops_nn as K
-from ..trainer.data import ActionLandscape, CostLandscape, Landscape, Rollout, ShieldLog
+from ..trainer.data import ActionLandscape, CostLandscape, Landscape, Rollout, RolloutLandscape, ShieldLog
 from ..utils import checkpoint as CK
 from ..utils.graph import GraphsTuple
 from .base import Algorithm
@@ -308,6 +308,25 @@ class DGPPO(Algorithm):
         frames = np.arange(ro.T) if frames is None else np.asarray(frames, dtype=np.int64).reshape(-1)
         cost = self.engine.cost_landscape(ro, int(index), int(agent), frames, xs, ys)
         return CostLandscape(xs, ys, cost.cpu().numpy(), int(agent), frames.astype(np.int64))
+
+    def rollout_landscape(self, rollout: Rollout, index: int, agent: int, frames=None, nx: int = 64, ny: int = 64, xs=None,
+                          ys=None, horizon: int = 32) -> RolloutLandscape:
+        """What Vh is trained to predict, over the grid vh_landscape sweeps (same arguments and defaults): in every frame
+        `agent` is moved to each grid point (velocity kept, LiDAR cast again) and the deterministic policy rolled `horizon`
+        steps forward from there, with the actor's carry of that frame.  value is the discounted-to-max constraint return of
+        those steps (compute_dec_ocp_gae, dgppo/algo/utils.py:38-45, at gae_lambda = 1, started from the last cost instead of
+        a learned tail), worst the largest cost met: {worst >= 0} is the set of positions from which the policy becomes unsafe
+        within the horizon — what {Vh >= 0} is meant to cover, and what the instantaneous cost_landscape understates.  It
+        needs only the policy: every algorithm has it.  Not in the reference."""
+        ro = getattr(self, "_last_rollouts", {}).get(id(rollout.actions))
+        if ro is None:
+            raise ValueError("rollout_landscape() needs a Rollout produced by this algo's collect methods")
+        area = float(self._env.cfg.area_size)
+        xs, ys = _grid_axis("rollout_landscape", "xs", xs, nx, area), _grid_axis("rollout_landscape", "ys", ys, ny, area)
+        frames = np.arange(ro.T) if frames is None else np.asarray(frames, dtype=np.int64).reshape(-1)
+        value, worst = self.engine.rollout_landscape(ro, int(index), int(agent), frames, xs, ys, int(horizon))
+        return RolloutLandscape(xs, ys, value.cpu().numpy(), worst.cpu().numpy(), int(agent), frames.astype(np.int64),
+                                int(horizon), float(self.engine.hp.gamma))
 
     def action_landscape(self, rollout: Rollout, index: int, agent: int, frames=None, nu: int = 32, nv: int = 32, us=None,
                          vs=None) -> ActionLandscape:

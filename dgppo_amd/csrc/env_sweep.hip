@@ -13,6 +13,8 @@
 //
 // Built with -ffp-contract=off; the ray arithmetic is env_step.h's (shared with env_step.hip), the slot topology
 // graph_topo.h's (shared with graph_feats.hip).
+#include <string>
+
 #include "env_step.h"
 #include "graph_topo.h"
 
@@ -1018,6 +1020,249 @@ extern "C" int32_t dgppo_shield_select(const float* Vh_next, const float* Vh_t, 
   a.dt = dt; a.alpha = alpha; a.margin = margin; a.action = action; a.index = index; a.flag = flag; a.h = h;
   const dim3 grid((unsigned)((rows + SHIELD_WAVES - 1) / SHIELD_WAVES));
   hipLaunchKernelGGL(shield_select_kernel, grid, dim3(SHIELD_NT), 0, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
+
+// ---- rollout landscape: the what-if environments of a sweep as a dense env state ---------------------------------------------
+// Vh is fitted to Qh, the discounted-to-max constraint return of the policy's own future (compute_dec_ocp_gae,
+// dgppo/algo/utils.py:38-45), so its ground truth at a swept position is a policy rollout FROM that position.  The fork below
+// builds the start of those rollouts: env g = (f * ny + iy) * nx + ix is frame fid = frame_ids[f] with agent `agent_id` standing
+// at (xs[ix], ys[iy]) — the graph of dgppo_graph_feats_sweep above, written as the state the step kernels run on (agent rows,
+// goals, obstacle records, hit points, the actor's carry) instead of as its features.
+//
+// Organisation: the sweep's.  A workgroup stages the frame (states, goals, obstacle records, recorded hits) in LDS once per tile
+// of 64 grid points and walks the tile, one wave per point: the wave casts the R rays of the moved agent and ranks them
+// (env_step.h's ray arithmetic, as above), then streams the env's rows with unit-stride stores.  Consecutive points are
+// consecutive envs, so the four waves of a pass write one contiguous range of each output.  The carry rows are a plain copy
+// per point and go from global memory to global memory (n * HC floats that stay in L2 across a frame's tiles): the LDS
+// budget does not depend on HC.
+struct ForkArgs {
+  dgppo_env_cfg cfg;
+  const float* agent; long agent_st;
+  const float* goal;
+  const float* obst;
+  const float* hits; long hits_st;
+  const float* ray_cos;
+  const float* ray_sin;
+  const int32_t* frame_ids;
+  int agent_id, nx, nxy, tiles;
+  const float* xs;
+  const float* ys;
+  const float* carry; long carry_st;
+  int HC;
+  float* agent_out;
+  float* goal_out;
+  float* obst_out;
+  float* hits_out;
+  float* carry_out;
+};
+
+__global__ void __launch_bounds__(SWEEP_NT) env_sweep_fork_kernel(ForkArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const dgppo_env_cfg& c = a.cfg;
+  const int tid = threadIdx.x, lane = tid & (DGPPO_WAVE - 1), wave = tid / DGPPO_WAVE;
+  const int f = blockIdx.x / a.tiles, tile = blockIdx.x - f * a.tiles;
+  const int fid = a.frame_ids ? a.frame_ids[f] : f;
+  const int n = c.n_agents, ng = c.n_goals, SD = c.state_dim, aid = a.agent_id;
+  const int no = c.n_obs, R = c.n_rays, k = c.top_k;
+  const bool lidar = cfg_is_lidar(c), cast = lidar && no > 0;
+  const int OS = lidar ? DGPPO_RECT_STRIDE : SD;                 // floats per obstacle record
+  // LDS carve: every offset is a multiple of 4 floats
+  const int al4 = 3;
+  const int Rp = (R + al4) & ~al4, K2 = (k * 2 + al4) & ~al4;
+  float* s_seg = sm;                                             // no*16 segment constants (cast)
+  float* s_rec = s_seg + (cast ? no * 16 : 0);                   // no*OS obstacle records
+  float* s_ag = s_rec + ((no * OS + al4) & ~al4);                // n*SD
+  float* s_go = s_ag + ((n * SD + al4) & ~al4);                  // ng*SD
+  float* s_hp = s_go + ((ng * SD + al4) & ~al4);                 // n*k*2 recorded hits (cast)
+  float* s_rc = s_hp + (cast ? ((n * k * 2 + al4) & ~al4) : 0);  // R
+  float* s_rs = s_rc + (cast ? Rp : 0);                          // R
+  float* s_al = s_rs + (cast ? Rp : 0);                          // waves * R    alphas of the wave's point
+  float* s_hit = s_al + (cast ? SWEEP_WAVES * Rp : 0);           // waves * k*2  hits of the moved agent
+
+  // ---- the frame, once per workgroup ----
+  const float* ag = a.agent + (size_t)fid * a.agent_st;
+  for (int i = tid; i < n * SD; i += SWEEP_NT) s_ag[i] = ag[i];
+  for (int i = tid; i < ng * SD; i += SWEEP_NT) s_go[i] = a.goal[i];
+  for (int i = tid; i < no * OS; i += SWEEP_NT) s_rec[i] = a.obst[i];
+  if (cast) {
+    const float* hp = a.hits + (size_t)fid * a.hits_st;
+    for (int i = tid; i < n * k * 2; i += SWEEP_NT) s_hp[i] = hp[i];
+    for (int i = tid; i < R; i += SWEEP_NT) { s_rc[i] = a.ray_cos[i]; s_rs[i] = a.ray_sin[i]; }
+  }
+  __syncthreads();
+  if (cast)
+    for (int q = tid; q < no * 4; q += SWEEP_NT) segment_consts(s_rec + (q >> 2) * DGPPO_RECT_STRIDE, q & 3, s_seg + q * 4);
+  __syncthreads();
+
+  const int q0 = tile * SWEEP_TILE, q1 = min(q0 + SWEEP_TILE, a.nxy);
+  float* w_al = s_al + wave * Rp;
+  float* w_hit = s_hit + wave * K2;
+  const float sr = c.comm_radius;
+  const int hit0 = aid * k * 2, hit1 = hit0 + k * 2;            // the moved agent's words of a hits row
+  const float* cr = a.carry ? a.carry + (size_t)fid * a.carry_st : nullptr;
+  // from here on the waves are independent: w_al / w_hit belong to one wave, whose LDS operations complete in issue order,
+  // so between its phases a wave-level fence (no reordering by the compiler, no workgroup barrier) is enough
+  for (int q = q0 + wave; q < q1; q += SWEEP_WAVES) {
+    const int iy = q / a.nx, ix = q - iy * a.nx;
+    const float px = a.xs[ix], py = a.ys[iy];
+    if (cast) {
+      {
+        // start inside a rectangle (env/utils.py:117, r = 0): all alphas become 0
+        bool in = false;
+        for (int o = lane; o < no; o += DGPPO_WAVE) in = in || rect_inside(s_rec + o * DGPPO_RECT_STRIDE, px, py, 0.0f);
+        const float is_in = (__ballot(in) != 0ull) ? 1.0f : 0.0f;
+        for (int r = lane; r < R; r += DGPPO_WAVE)
+          w_al[r] = ray_min_alpha(px, py, s_rc[r], s_rs[r], sr, s_seg, no) * (1.0f - is_in);
+      }
+      wave_sync();
+      for (int r = lane; r < R; r += DGPPO_WAVE) {
+        const int rank = ray_rank(w_al, R, r);
+        if (rank < k) ray_hit(px, py, s_rc[r], s_rs[r], sr, w_al[r], w_hit + rank * 2);
+      }
+      wave_sync();
+    }
+    const size_t g = (size_t)f * a.nxy + q;
+    // agent rows: frame fid's, columns 0 and 1 of row agent_id replaced; every other column (velocity; the bicycle's heading
+    // and speed) kept
+    float* ao = a.agent_out + g * n * SD;
+    for (int i = lane; i < n * SD; i += DGPPO_WAVE) {
+      float v = s_ag[i];
+      if (i == aid * SD) v = px;
+      if (i == aid * SD + 1) v = py;
+      ao[i] = v;
+    }
+    // the step kernels index goals and obstacle records by env: every what-if env gets its own copy
+    float* go = a.goal_out + g * ng * SD;
+    for (int i = lane; i < ng * SD; i += DGPPO_WAVE) go[i] = s_go[i];
+    if (no > 0) {
+      float* oo = a.obst_out + g * no * OS;
+      for (int i = lane; i < no * OS; i += DGPPO_WAVE) oo[i] = s_rec[i];
+    }
+    if (cast) {
+      float* ho = a.hits_out + g * n * k * 2;
+      for (int i = lane; i < n * k * 2; i += DGPPO_WAVE) ho[i] = (i >= hit0 && i < hit1) ? w_hit[i - hit0] : s_hp[i];
+    }
+    if (cr != nullptr) {
+      float* co = a.carry_out + g * n * a.HC;
+      for (int i = lane; i < n * a.HC; i += DGPPO_WAVE) co[i] = cr[i];
+    }
+    wave_sync();   // the next point's cast overwrites w_al / w_hit
+  }
+}
+
+extern "C" int32_t dgppo_env_sweep_fork(const dgppo_env_cfg* cfg, const float* agent, int64_t agent_st, const float* goal,
+                                        const float* obst, const float* hits, int64_t hits_st, const float* ray_cos,
+                                        const float* ray_sin, const int32_t* frame_ids, int32_t n_frames, int32_t agent_id,
+                                        const float* xs, int32_t nx, const float* ys, int32_t ny, const float* carry,
+                                        int64_t carry_st, int32_t HC, float* agent_out, float* goal_out, float* obst_out,
+                                        float* hits_out, float* carry_out, void* stream) {
+  int32_t rc = dgppo_validate_cfg(cfg);
+  if (rc) {   // the configuration's own refusal, under this entry point's name
+    const std::string why = dgppo_last_error();
+    dgppo_set_error("dgppo_env_sweep_fork: %s", why.c_str());
+    return rc;
+  }
+  DGPPO_REFUSE_VMAS(cfg, "dgppo_env_sweep_fork", "dgppo_vmas_step on a tiled record (there is no VMAS sweep)");
+  DGPPO_REQUIRE(agent_id >= 0 && agent_id < cfg->n_agents, "dgppo_env_sweep_fork: agent_id %d outside [0, %d)", agent_id,
+                cfg->n_agents);
+  DGPPO_REQUIRE(nx >= 0 && ny >= 0 && n_frames >= 0, "dgppo_env_sweep_fork: negative counts");
+  if (nx == 0 || ny == 0 || n_frames == 0) return 0;
+  DGPPO_REQUIRE(agent && goal && xs && ys && agent_out && goal_out, "dgppo_env_sweep_fork: NULL operand");
+  const int n = cfg->n_agents, ng = cfg->n_goals, SD = cfg->state_dim, no = cfg->n_obs, R = cfg->n_rays, k = cfg->top_k;
+  const bool lidar = cfg_is_lidar(*cfg), cast = lidar && no > 0;
+  if (no > 0) {
+    DGPPO_REQUIRE(obst, "dgppo_env_sweep_fork: obst is NULL");
+    DGPPO_REQUIRE(obst_out, "dgppo_env_sweep_fork: obst_out is NULL");
+    if (cast) {
+      DGPPO_REQUIRE(hits && ray_cos && ray_sin, "dgppo_env_sweep_fork: hits / ray_cos / ray_sin is NULL");
+      DGPPO_REQUIRE(hits_out, "dgppo_env_sweep_fork: hits_out is NULL");
+    }
+  }
+  if (carry != nullptr) {
+    DGPPO_REQUIRE(carry_out, "dgppo_env_sweep_fork: carry_out is NULL");
+    DGPPO_REQUIRE(HC >= 1 && (long)n * HC < (1L << 31), "dgppo_env_sweep_fork: HC %d out of range", HC);
+  }
+  const int OS = lidar ? DGPPO_RECT_STRIDE : SD;
+  auto up4 = [](long v) { return (v + 3) & ~3L; };
+  long fl = up4((long)no * OS) + up4((long)n * SD) + up4((long)ng * SD);
+  if (cast) fl += (long)no * 16 + up4((long)n * k * 2) + 2 * up4(R) + SWEEP_WAVES * (up4(R) + up4(k * 2));
+  DGPPO_REQUIRE(fl * 4 <= 64 * 1024, "dgppo_env_sweep_fork: the frame does not fit the LDS (%ld bytes)", fl * 4);
+  const long nxy = (long)nx * ny;
+  DGPPO_REQUIRE(nxy <= (1L << 24), "dgppo_env_sweep_fork: grid too large (nx * ny <= 2^24)");
+  const long tiles = (nxy + SWEEP_TILE - 1) / SWEEP_TILE;
+  DGPPO_REQUIRE(tiles * n_frames < (1L << 31), "dgppo_env_sweep_fork: too many envs");
+  ForkArgs a;
+  a.cfg = *cfg;
+  a.agent = agent; a.agent_st = agent_st; a.goal = goal; a.obst = obst; a.hits = hits; a.hits_st = hits_st;
+  a.ray_cos = ray_cos; a.ray_sin = ray_sin; a.frame_ids = frame_ids; a.agent_id = agent_id; a.nx = nx; a.nxy = (int)nxy;
+  a.tiles = (int)tiles; a.xs = xs; a.ys = ys; a.carry = carry; a.carry_st = carry_st; a.HC = HC;
+  a.agent_out = agent_out; a.goal_out = goal_out; a.obst_out = obst_out; a.hits_out = hits_out; a.carry_out = carry_out;
+  const size_t smem = sizeof(float) * (size_t)fl;
+  const dim3 grid((unsigned)(tiles * n_frames));
+  hipLaunchKernelGGL(env_sweep_fork_kernel, grid, dim3(SWEEP_NT), smem, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
+
+// ---- rollout landscape: the costs of a K-step rollout folded into what Vh is trained on ------------------------------------------
+// compute_dec_ocp_gae's Vhs_row recursion (dgppo/algo/utils.py:38-45, discount_to_max) at gae_lambda = 1, per (env, agent) row:
+// V = h[K-1]; for k = K-2 .. 0: m = max_c h[k][c], V[c] = max(h[k][c], one_minus_gamma * m + gamma * V[c]) — one multiply, one
+// multiply and one add, in that order (this file is built with -ffp-contract=off).  The reference bootstraps with Vh of the state
+// after the last step; here the row starts from the last cost itself, so that the net under test stays out of its own ground
+// truth.  worst[c] = max_k h[k][c].  Every max propagates NaN (jnp.maximum / jnp.max).
+// A lane per row: the nh <= 3 words of a row are consecutive and rows are consecutive, so a wave reads one contiguous range per
+// step; NH is a template parameter, the row's values live in named registers.
+#define FOLD_NT 256
+
+template <int NH>
+__global__ void __launch_bounds__(FOLD_NT) constraint_return_kernel(const float* __restrict__ cost, long cost_st, int K, long rows,
+                                                                     float gamma, float omg, float* __restrict__ value,
+                                                                     float* __restrict__ worst) {
+  const long r = (long)blockIdx.x * FOLD_NT + threadIdx.x;
+  if (r >= rows) return;
+  const float* h = cost + (size_t)(K - 1) * cost_st + (size_t)r * NH;
+  float v0 = h[0], v1 = (NH > 1) ? h[1] : 0.0f, v2 = (NH > 2) ? h[2] : 0.0f;
+  float w0 = v0, w1 = v1, w2 = v2;
+  for (int k = K - 2; k >= 0; --k) {
+    h -= cost_st;
+    const float h0 = h[0], h1 = (NH > 1) ? h[1] : 0.0f, h2 = (NH > 2) ? h[2] : 0.0f;
+    float m = h0;
+    if (NH > 1) m = nanmax(m, h1);
+    if (NH > 2) m = nanmax(m, h2);
+    const float dm = omg * m;
+    v0 = nanmax(h0, dm + gamma * v0); w0 = nanmax(w0, h0);
+    if (NH > 1) { v1 = nanmax(h1, dm + gamma * v1); w1 = nanmax(w1, h1); }
+    if (NH > 2) { v2 = nanmax(h2, dm + gamma * v2); w2 = nanmax(w2, h2); }
+  }
+  float* vo = value + (size_t)r * NH;
+  float* wo = worst + (size_t)r * NH;
+  vo[0] = v0; wo[0] = w0;
+  if (NH > 1) { vo[1] = v1; wo[1] = w1; }
+  if (NH > 2) { vo[2] = v2; wo[2] = w2; }
+}
+
+extern "C" int32_t dgppo_constraint_return(const float* cost, int64_t cost_st, int32_t K, int32_t G, int32_t n_agents, int32_t nh,
+                                           float gamma, float one_minus_gamma, float* value, float* worst, void* stream) {
+  const char* fn = "dgppo_constraint_return";
+  DGPPO_REQUIRE(K >= 1, "%s: K must be >= 1 (got %d)", fn, K);
+  DGPPO_REQUIRE(nh >= 1 && nh <= 3, "%s: nh %d outside [1, 3]", fn, nh);
+  DGPPO_REQUIRE(G >= 0 && n_agents >= 0, "%s: negative counts", fn);
+  if (G == 0 || n_agents == 0) return 0;
+  DGPPO_REQUIRE(cost && value && worst, "%s: NULL operand", fn);
+  const long rows = (long)G * n_agents;
+  DGPPO_REQUIRE(K == 1 || cost_st >= rows * nh, "%s: the step stride %ld is shorter than a step (%ld floats)", fn, (long)cost_st,
+                rows * nh);
+  const long blocks = (rows + FOLD_NT - 1) / FOLD_NT;
+  DGPPO_REQUIRE(blocks < (1L << 31), "%s: too many rows", fn);
+  const dim3 grid((unsigned)blocks), block(FOLD_NT);
+  hipStream_t s = (hipStream_t)stream;
+  if (nh == 1) hipLaunchKernelGGL(constraint_return_kernel<1>, grid, block, 0, s, cost, (long)cost_st, K, rows, gamma, one_minus_gamma, value, worst);
+  else if (nh == 2) hipLaunchKernelGGL(constraint_return_kernel<2>, grid, block, 0, s, cost, (long)cost_st, K, rows, gamma, one_minus_gamma, value, worst);
+  else hipLaunchKernelGGL(constraint_return_kernel<3>, grid, block, 0, s, cost, (long)cost_st, K, rows, gamma, one_minus_gamma, value, worst);
   DGPPO_LAUNCH_CHECK();
   return 0;
 }

@@ -282,8 +282,10 @@ class Engine:
         return f.compute_record(st.step, slots, st.env, env_ids, n_env, n_time)
 
     def _rollout_steps(self, ro: RolloutData, eps, B: int, stochastic: bool):
-        """the T env steps of a rollout: policy forward (GNN + GRU + head) and env.step, all on the current stream."""
-        cfg, T, n = self.cfg, self.T, self.cfg.n_agents
+        """the ro.T env steps of a rollout from the state and carry in slot 0 of the record: policy forward (GNN + GRU + head)
+        and env.step, all on the current stream.  The step count is the record's (self.T in rollout(), the horizon in
+        rollout_landscape())."""
+        cfg, T, n = self.cfg, ro.T, self.cfg.n_agents
         tag = "ro" if stochastic else "rod"    # separate scratch per kind: the two rollouts may run on different streams
         if self.fused_step:
             # features and queries of step 0 from the stand-alone kernels; every step's launch then leaves those of the next
@@ -558,6 +560,89 @@ class Engine:
         K.cost_sweep(cfg, step["agent"], n * cfg.state_dim, env.get("obst"), step.get("hits"), n * cfg.top_k * 2, rc, rs,
                      frames, F, int(agent_id), xs, ys, out.view(F * ny * nx, n, self.n_cost))
         return out
+
+    def rollout_landscape(self, ro: RolloutData, env_index: int, agent_id: int, frame_ids, xs, ys, horizon: int,
+                          events: Optional[list] = None, records: Optional[list] = None):
+        """-> (value, worst), each [F, ny, nx, n, n_cost]: what Vh is trained to predict, measured.  Vh is fitted to the
+        discounted-to-max constraint return of the policy's own future (compute_dec_ocp_gae, dgppo/algo/utils.py:38-45), so
+        for every grid point the env of frame frame_ids[f] (a subset of [0, T)) of env `env_index` with agent `agent_id`
+        moved to (xs[ix], ys[iy]) is forked (dgppo_env_sweep_fork: LiDAR cast again, the actor's pre-step carry of that frame
+        — ro._rnn_em[e, t], valid in stochastic and deterministic records alike, all HC columns) and rolled `horizon` steps
+        forward with the deterministic policy, whatever kind the source record is (eager launches of _rollout_steps, so the
+        one-launch and the four-launch step both serve).  value folds the horizon's costs as the training target does at
+        gae_lambda = 1, started from the last cost instead of a learned tail (dgppo_constraint_return, hp.gamma); worst is
+        their maximum over the steps: >= 0 exactly where an agent becomes unsafe within the horizon.  The rollouts run past
+        the episode's end where t + horizon > T: there is no done flag in these environments.  It needs only the policy, so
+        every algo and --no-rnn engines have it.  Walked as vh_landscape walks its grid — whole frames, else rows of one
+        frame, else pieces of one row — in sub-grids of Gb envs with Gb * (horizon + 1) <= prepass_graphs.
+        events: a list that receives one (start, fork done, steps done, fold done) tuple of device events per sub-grid
+        (tools/bench_rollout_landscape.py).  records: a list that receives (f0, f1, y0, y1, x0, x1, finalized record) per
+        sub-grid (the tests re-derive every step of those)."""
+        cfg, T = self.cfg, self.T
+        if cfg.is_vmas:
+            raise ValueError("rollout_landscape: VMASReverseTransport is not supported")
+        n, nh, HC = cfg.n_agents, self.n_cost, self.HC
+        ro.finalize()
+        if not 0 <= int(env_index) < ro.B:
+            raise ValueError(f"rollout_landscape: env_index {env_index} outside [0, {ro.B})")
+        if not 0 <= int(agent_id) < n:
+            raise ValueError(f"rollout_landscape: agent_id {agent_id} outside [0, {n})")
+        frames = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        if frames.size == 0 or frames.min() < 0 or frames.max() >= T:
+            raise ValueError(f"rollout_landscape: frame_ids must be a non-empty subset of [0, {T})")
+        horizon = int(horizon)
+        if horizon < 1:
+            raise ValueError(f"rollout_landscape: horizon must be >= 1 (got {horizon})")
+        xs, ys = K.sweep_axis(xs, "xs", self.device), K.sweep_axis(ys, "ys", self.device)
+        nx, ny, F = int(xs.numel()), int(ys.numel()), int(frames.size)
+        e = int(env_index)
+        step = {k: v[e] for k, v in ro.step.items()}
+        env = {k: v[e] for k, v in ro.env.items()}
+        carry = ro._rnn_em[e] if self.hp.use_rnn else None                       # [T + 2, n, HC]: slot t = pre-step carry of t
+        value = torch.empty(F, ny, nx, n, nh, device=self.device)
+        worst = torch.empty(F, ny, nx, n, nh, device=self.device)
+        ids_dev = torch.from_numpy(frames.astype(np.int32)).to(self.device)      # once per call; the sub-grids pass slices
+        cap = max(1, self.prepass_graphs // (horizon + 1))
+        fb = max(1, cap // (ny * nx))
+        yb = ny if cap >= ny * nx else max(1, cap // nx)
+        xb = nx if cap >= nx else cap
+        recs: Dict[int, RolloutData] = {}            # one record per sub-grid size, unless the caller keeps the records
+        for f0 in range(0, F, fb):
+            f1 = min(F, f0 + fb)
+            fr = frames[f0:f1]
+            for y0 in range(0, ny, yb):
+                y1 = min(ny, y0 + yb)
+                for x0 in range(0, nx, xb):
+                    x1 = min(nx, x0 + xb)
+                    Gb = (f1 - f0) * (y1 - y0) * (x1 - x0)
+                    rec = recs.get(Gb) if records is None else None
+                    if rec is None:
+                        rec = recs[Gb] = RolloutData(cfg, Gb, horizon, self.device, False, HC)
+                    rec._env_major = False
+                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if events is not None else None
+                    if ev:
+                        ev[0].record()
+                    if carry is None:
+                        rec.rnn_tm[0].zero_()
+                    OE.sweep_fork(cfg, step, env, ids_dev[f0:f1], f1 - f0, int(agent_id), xs[x0:x1], ys[y0:y1], rec.states_tm[0],
+                                  carry, n * HC, rec.rnn_tm[0].view(Gb * n, HC) if carry is not None else None,
+                                  frame_max=int(fr.max()))
+                    if ev:
+                        ev[1].record()
+                    self._rollout_steps(rec, None, Gb, False)
+                    if ev:
+                        ev[2].record()
+                    val = self.arena.get("rl.value", Gb, n, nh)
+                    wor = self.arena.get("rl.worst", Gb, n, nh)
+                    OA.constraint_return(rec.cost_tm, self.hp.gamma, val, wor)
+                    value[f0:f1, y0:y1, x0:x1].copy_(val.view(f1 - f0, y1 - y0, x1 - x0, n, nh))
+                    worst[f0:f1, y0:y1, x0:x1].copy_(wor.view(f1 - f0, y1 - y0, x1 - x0, n, nh))
+                    if ev:
+                        ev[3].record()
+                        events.append(tuple(ev))
+                    if records is not None:
+                        records.append((f0, f1, y0, y1, x0, x1, rec.finalize()))
+        return value, worst
 
     def action_landscape(self, ro: RolloutData, env_index: int, agent_id: int, frame_ids, us, vs,
                          events: Optional[list] = None):

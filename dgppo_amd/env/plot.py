@@ -94,7 +94,17 @@ class _Scene:
 
     def __init__(self, ep: Episode, side_length: float, n_agent: int, n_goal: int, r: float, obs_r: float,
                  cost_components: Sequence[str], Ta_is_unsafe, dpi: int, landscape=None, cost_landscape=None,
-                 action_landscape=None):
+                 action_landscape=None, rollout_landscape=None):
+        if rollout_landscape is not None:
+            for name, other in (("landscape", landscape), ("cost_landscape", cost_landscape),
+                                ("action_landscape", action_landscape)):
+                if other is not None and int(other.agent) != int(rollout_landscape.agent):
+                    raise ValueError(f"rollout_landscape is swept for agent {int(rollout_landscape.agent)}, {name} for agent "
+                                     f"{int(other.agent)}")
+            for name, other in (("landscape", landscape), ("cost_landscape", cost_landscape)):
+                if other is not None and not (np.array_equal(np.asarray(other.xs), np.asarray(rollout_landscape.xs))
+                                              and np.array_equal(np.asarray(other.ys), np.asarray(rollout_landscape.ys))):
+                    raise ValueError(f"{name} and rollout_landscape are swept over different grids")
         if action_landscape is not None:
             for name, other in (("landscape", landscape), ("cost_landscape", cost_landscape)):
                 if other is not None and int(other.agent) != int(action_landscape.agent):
@@ -164,6 +174,18 @@ class _Scene:
             self.fig.colorbar(sm, ax=ax, fraction=0.046, pad=0.04)
             self.cbf_text = ax.text(0.5, 1.04, f"{'CBF' if landscape is not None else 'Cost'} for {int(filled.agent)}",
                                     va="bottom", ha="center", **font)
+        # rollout landscape (trainer.data.RolloutLandscape): the boundary of the set from which the policy becomes unsafe within
+        # the horizon — the zero contour of its h(), dotted, over whatever else is drawn
+        self.rollout_landscape = rollout_landscape
+        self.rollout_zero_line = None
+        if rollout_landscape is not None:
+            self._ro_h = np.asarray(rollout_landscape.h(), dtype=np.float64)
+            self._ro_row = {int(t): k for k, t in enumerate(np.asarray(rollout_landscape.frames).reshape(-1))}
+            self._ro_xy = np.meshgrid(np.asarray(rollout_landscape.xs, dtype=np.float64),
+                                      np.asarray(rollout_landscape.ys, dtype=np.float64))
+            if self._ro_h.shape[1] < 2 or self._ro_h.shape[2] < 2:
+                print(f"(rollout landscape grid {self._ro_h.shape[2]} x {self._ro_h.shape[1]}: contours need at least 2 lines each "
+                      f"way, none are drawn)")
 
         # action landscape (trainer.data.ActionLandscape): an inset over the action square, the swept agent's largest cbf_deriv
         # component as filled contours (<= 0: the net admits the action), the zero contour in black, the recorded action marked
@@ -193,8 +215,8 @@ class _Scene:
             self.act_ax.set_visible(False)
 
     def artists(self):
-        extra = [a for a in (self.contours, self.zero_line, self.cost_zero_line, getattr(self, "cbf_text", None), self.act_ax)
-                 if a is not None]
+        extra = [a for a in (self.contours, self.zero_line, self.cost_zero_line, self.rollout_zero_line,
+                             getattr(self, "cbf_text", None), self.act_ax) if a is not None]
         return [*self.agent_circles, *self.goal_circles, self.edges, self.cost_text, self.unsafe_text, self.step_text,
                 *self.labels, *extra]
 
@@ -219,6 +241,20 @@ class _Scene:
                 self.cost_zero_line = self.ax.contour(X, Y, z, levels=[0.0], colors="k", linewidths=2.0, linestyles="dashed",
                                                       zorder=4)
 
+    def _draw_rollout_landscape(self, t: int):
+        """the dotted zero contour of frame t, rebuilt like the contours above; a frame the rollout landscape does not hold, or
+        one whose slice holds a NaN or does not change sign, shows none"""
+        if self.rollout_zero_line is not None:
+            self.rollout_zero_line.remove()
+        self.rollout_zero_line = None
+        k = self._ro_row.get(int(t))
+        if k is not None and _drawable(self._ro_h[k]):
+            z = self._ro_h[k]
+            if z.min() < 0.0 <= z.max():             # h >= 0: unsafe within the horizon (RolloutLandscape.h)
+                X, Y = self._ro_xy
+                self.rollout_zero_line = self.ax.contour(X, Y, z, levels=[0.0], colors="k", linewidths=2.0, linestyles="dotted",
+                                                         zorder=4)
+
     def _draw_action_landscape(self, t: int):
         """the inset of frame t, rebuilt like the contours above; a frame the action landscape does not hold shows no inset"""
         for a in (self.act_contours, self.act_zero_line):
@@ -242,6 +278,8 @@ class _Scene:
         ep, n = self.ep, self.n_agent
         if self.landscape is not None or self.cost_landscape is not None:
             self._draw_landscape(t)
+        if self.rollout_landscape is not None:
+            self._draw_rollout_landscape(t)
         if self.action_landscape is not None:
             self._draw_action_landscape(t)
         pos = ep.states[t, :, :2]
@@ -285,7 +323,8 @@ def _write(scene: _Scene, n_frames: int, video_path: pathlib.Path, fps: int = 33
 
 
 def _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_components, Ta_is_unsafe, viz_opts, dpi, n_goal,
-            index=None, max_frames=None, landscape=None, cost_landscape=None, action_landscape=None, **kwargs) -> pathlib.Path:
+            index=None, max_frames=None, landscape=None, cost_landscape=None, action_landscape=None, rollout_landscape=None,
+            **kwargs) -> pathlib.Path:
     if dim != 2:
         raise NotImplementedError("only the planar environments of SURVEY §8 are rendered (dim == 2)")
     if viz_opts:
@@ -293,7 +332,7 @@ def _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_compo
     ep = episode_from_rollout(rollout, index)
     n_goal = n_agent if n_goal is None else n_goal
     scene = _Scene(ep, float(side_length), n_agent, n_goal, r, obs_r, cost_components, Ta_is_unsafe, dpi, landscape,
-                   cost_landscape, action_landscape)
+                   cost_landscape, action_landscape, rollout_landscape)
     T = ep.states.shape[0] if max_frames is None else min(ep.states.shape[0], max_frames)
     return _write(scene, T, video_path)
 
@@ -301,22 +340,26 @@ def _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_compo
 def render_lidar(rollout, video_path, side_length: float, dim: int, n_agent: int, n_rays: int, r: float,
                  cost_components: Tuple[str, ...], Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
                  n_goal: Optional[int] = None, landscape=None, cost_landscape=None, action_landscape=None,
-                 **kwargs) -> pathlib.Path:
+                 rollout_landscape=None, **kwargs) -> pathlib.Path:
     """dgppo/env/plot.py:468 (LiDAR family: rectangle obstacles, `n_rays` hit nodes per agent).  landscape: a
     trainer.data.Landscape of this episode, drawn as the reference draws viz_opts["cbf"] (plot.py:348-372,437-447).
     cost_landscape: a trainer.data.CostLandscape, drawn the same way when alone ("Cost for k"), as a dashed zero contour over
     the Vh contours when both are given.  action_landscape: a trainer.data.ActionLandscape, drawn in an inset over the action
     square (filled contours of the swept agent's cbf_deriv, black zero contour, the recorded action marked); it combines with
-    the other two, for the same agent."""
+    the other two, for the same agent.  rollout_landscape: a trainer.data.RolloutLandscape: the zero contour of its h() — the
+    boundary of the set from which the policy becomes unsafe within the horizon — dotted, over whatever else is drawn, for the
+    same agent and grid."""
     return _render(rollout, video_path, side_length, dim, n_agent, r, 0.0, cost_components, Ta_is_unsafe, viz_opts, dpi,
-                   n_goal, landscape=landscape, cost_landscape=cost_landscape, action_landscape=action_landscape, **kwargs)
+                   n_goal, landscape=landscape, cost_landscape=cost_landscape, action_landscape=action_landscape,
+                   rollout_landscape=rollout_landscape, **kwargs)
 
 
 def render_mpe(rollout, video_path, side_length: float, dim: int, n_agent: int, n_obs: int, r: float, obs_r: float,
                cost_components: Tuple[str, ...], Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
                n_goal: Optional[int] = None, landscape=None, cost_landscape=None, action_landscape=None,
-               **kwargs) -> pathlib.Path:
-    """dgppo/env/plot.py:206 (MPE family: disc obstacles of radius obs_r).  landscape / cost_landscape / action_landscape: as in
-    render_lidar."""
+               rollout_landscape=None, **kwargs) -> pathlib.Path:
+    """dgppo/env/plot.py:206 (MPE family: disc obstacles of radius obs_r).  landscape / cost_landscape / action_landscape /
+    rollout_landscape: as in render_lidar."""
     return _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_components, Ta_is_unsafe, viz_opts, dpi,
-                   n_goal, landscape=landscape, cost_landscape=cost_landscape, action_landscape=action_landscape, **kwargs)
+                   n_goal, landscape=landscape, cost_landscape=cost_landscape, action_landscape=action_landscape,
+                   rollout_landscape=rollout_landscape, **kwargs)

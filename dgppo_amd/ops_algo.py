@@ -27,6 +27,26 @@ def gae(costs, rewards, Vh, Vl, lam_pow, gamma: float, gae_lambda: float, Qh, Ql
     N.check(rc, "dgppo_gae")
 
 
+def constraint_return(cost_tm, gamma: float, value, worst):
+    """dgppo_constraint_return: the costs of a K-step rollout, time-major cost_tm [K, G, n, nh] (steps may be strided), folded
+    into the discounted-to-max constraint return Vh is trained on (compute_dec_ocp_gae's Vhs_row at gae_lambda = 1, started from
+    the last cost instead of a learned tail) -> value [G, n, nh], and worst [G, n, nh] = max over the steps.  gamma and
+    1 - gamma are formed in Python doubles and rounded to fp32, as gae() hands them over."""
+    if cost_tm.ndim != 4:
+        raise ValueError(f"constraint_return: cost_tm must be [K, G, n, nh], got {tuple(cost_tm.shape)}")
+    K_, G, n, nh = cost_tm.shape
+    if K_ < 1:
+        raise ValueError("constraint_return: K must be >= 1")
+    if not cost_tm[0].is_contiguous():
+        raise ValueError("constraint_return: every step of cost_tm must be dense")
+    N.expect_shape(value, (G, n, nh), "value")
+    N.expect_shape(worst, (G, n, nh), "worst")
+    rc = N.lib().dgppo_constraint_return(N.ptr(cost_tm[0], name="cost"), int(cost_tm.stride(0)), K_, G, n, nh, float(gamma),
+                                         float(1 - gamma), N.ptr(value, name="value"), N.ptr(worst, name="worst"),
+                                         N.stream_ptr())
+    N.check(rc, "dgppo_constraint_return")
+
+
 def shaped_reward(reward, cost, cost_weight: float, out):
     """out = reward - w * sum_{agents, components} max(cost, 0)   (InforMARL's stage cost, informarl.py:329)"""
     B, T, n, nh = cost.shape

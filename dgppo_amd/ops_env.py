@@ -329,6 +329,51 @@ def act_step_feats(cfg: N.EnvCfg, st: State, ms, eps, action, log_pi, nst: State
     N.check(rc_, "dgppo_env_act_step_feats")
 
 
+def sweep_fork(cfg: N.EnvCfg, step: Dict[str, torch.Tensor], env: Dict[str, torch.Tensor], frame_ids, n_frames: int,
+               agent_id: int, xs, ys, out: State, carry=None, carry_st: int = 0, carry_out=None, frame_max=None):
+    """dgppo_env_sweep_fork: the G = n_frames * ny * nx what-if envs of a sweep into `out` (State.empty(cfg, G, device)) — env
+    (f * ny + iy) * nx + ix is frame frame_ids[f] of ONE env with agent `agent_id` at (xs[ix], ys[iy]), its LiDAR cast again
+    there.  `step` holds that env's per-step fields [T + 1, ...], `env` its per-env rows (GraphFeats.compute_sweep's operands);
+    xs / ys are ops_nn.sweep_axis tensors; frame_ids as in ops_nn.graph_feats_sweep.  carry: a base tensor whose [n, HC] rows of
+    frame t start at t * carry_st floats, copied into carry_out [G * n, HC] for every grid point of the frame; None: no carry.
+    Every refusal is raised before anything is launched."""
+    from . import ops_nn as K                     # the grid and record checks the sweep bindings share
+    fn = "sweep_fork"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no sweep entry point")
+    n, sd, k = cfg.n_agents, cfg.state_dim, cfg.top_k
+    agent, hits, obst, goal = step["agent"], step.get("hits"), env.get("obst"), env["goal"]
+    nx, ny, ids, ids_dev, last = K._sweep_grid(fn, cfg, frame_ids, n_frames, agent_id, xs, ys, frame_max)
+    G = n_frames * ny * nx
+    rc, rs = _rays(cfg, agent.device)
+    cast = K._sweep_record(fn, cfg, agent, n * sd, obst, hits, n * k * 2, rc, rs, last, None, G)
+    N.expect_shape(goal, (cfg.n_goals, sd), "goal")
+    o_step, o_env = out.step, out.env
+    for fields, held in zip(record_fields(cfg), (o_step, o_env)):
+        for name, shape in fields.items():
+            if held.get(name) is None:
+                raise ValueError(f"{fn}: out has no {name}")
+            N.expect_shape(held[name], (G,) + shape, f"out.{name}")
+    HC = 0
+    if carry is not None:
+        if carry_out is None or carry_out.ndim != 2 or carry_out.shape[0] != G * n:
+            raise ValueError(f"{fn}: carry_out must be [G * n, HC] = [{G * n}, HC]")
+        HC = int(carry_out.shape[1])
+        K._check_strided(fn, "carry", carry, 0, int(carry_st), (n, HC), None, 1, last + 1)
+    if ids is not None:
+        ids_dev = torch.from_numpy(ids.astype(np.int32)).to(agent.device)
+    raw = lambda t_: C.c_void_p(t_.data_ptr())       # a view into the record: only its trailing block is dense (checked above)
+    rc_ = N.lib().dgppo_env_sweep_fork(
+        C.byref(cfg), raw(agent), n * sd, N.ptr(goal, name="goal"), N.ptr(obst, name="obst"), raw(hits) if cast else None,
+        n * k * 2, N.ptr(rc if cast else None, name="ray_cos"), N.ptr(rs if cast else None, name="ray_sin"),
+        N.ptr(ids_dev, torch.int32, "frame_ids"), n_frames, int(agent_id), N.ptr(xs, name="xs"), nx, N.ptr(ys, name="ys"), ny,
+        raw(carry) if carry is not None else None, int(carry_st), HC, N.ptr(o_step["agent"], name="out.agent"),
+        N.ptr(o_env["goal"], name="out.goal"), N.ptr(o_env.get("obst"), name="out.obst"),
+        N.ptr(o_step.get("hits") if cast else None, name="out.hits"),
+        N.ptr(carry_out if carry is not None else None, name="carry_out"), N.stream_ptr())
+    N.check(rc_, "dgppo_env_sweep_fork")
+
+
 def materialize(cfg: N.EnvCfg, st: State, graph: Dict[str, torch.Tensor]):
     if cfg.is_vmas:
         return vmas_graph_materialize(cfg, st.agent, st.body, st.scene, graph)

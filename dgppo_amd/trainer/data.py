@@ -55,6 +55,29 @@ class CostLandscape(NamedTuple):
         return np.asarray(self.cost)[:, :, :, int(self.agent), :].max(axis=-1)
 
 
+class RolloutLandscape(NamedTuple):
+    """What Vh is trained to predict, measured: from every grid point the policy is rolled `horizon` steps forward
+    (`DGPPO.rollout_landscape`) and the costs it meets are folded as the training target folds them (compute_dec_ocp_gae,
+    dgppo/algo/utils.py:38-45, at gae_lambda = 1 and started from the last cost instead of a learned tail)."""
+    xs: np.ndarray        # [nx] fp32 grid lines
+    ys: np.ndarray        # [ny]
+    value: np.ndarray     # [F, ny, nx, n, n_cost]: the discounted-to-max constraint return of the horizon from (xs[ix], ys[iy])
+    worst: np.ndarray     # [F, ny, nx, n, n_cost]: the largest cost met within the horizon
+    agent: int            # the swept agent
+    frames: np.ndarray    # [F] frame numbers of the episode
+    horizon: int          # steps rolled from every grid point
+    gamma: float
+
+    def h(self) -> np.ndarray:
+        """[F, ny, nx]: the swept agent's largest `worst` component.  >= 0 exactly where that agent becomes unsafe, by the rule
+        test.py applies to the costs (any component >= 0), within the horizon."""
+        return np.asarray(self.worst)[:, :, :, int(self.agent), :].max(axis=-1)
+
+    def v(self) -> np.ndarray:
+        """[F, ny, nx]: the swept agent's largest `value` component: what Landscape.h() is supposed to equal."""
+        return np.asarray(self.value)[:, :, :, int(self.agent), :].max(axis=-1)
+
+
 class ShieldLog(NamedTuple):
     """What the barrier shield did in the episodes of `DGPPO.collect_shielded`, env-major like the Rollout next to it.  The
     candidates of an agent are its policy action (index 0) and the grid points (us[iu], vs[iv]) (index 1 + iv * nu + iu);

@@ -98,6 +98,49 @@ def landscape_agreement(land, cost) -> Dict[str, np.ndarray]:
                 conservative_frac=float(conservative.sum() / max(int(safe.sum()), 1)))
 
 
+def rollout_agreement(rl, land=None, cost=None) -> Dict[str, np.ndarray]:
+    """How a RolloutLandscape (trainer.data) — the set of positions from which the policy becomes unsafe within the horizon —
+    compares with the learned Landscape and the instantaneous CostLandscape of the same agent, grid and frames.  A point is
+    `doomed` where rl.h() >= 0.  Per frame [F], each count over the points where its operands' h() are finite:
+    always `points`, `doomed` and doomed_frac = doomed.sum() / max(points.sum(), 1);
+    with `land`: `missed` (doomed where the net says h < 0: what a barrier exists to rule out), `conservative` (not doomed
+    within the horizon where the net says h >= 0), missed_frac = missed.sum() / max(the doomed points counted, 1),
+    conservative_frac likewise over the points not doomed, and value_error = the mean |Vh - value| over the finite entries of
+    the swept agent's row;
+    with `cost`: `latent` (safe now, cost h < 0, but doomed: the failures cost_landscape cannot show) and latent_frac =
+    latent.sum() / max(the currently safe points counted, 1)."""
+    for name, other in (("land", land), ("cost", cost)):
+        if other is None:
+            continue
+        same = (int(rl.agent) == int(other.agent)
+                and np.array_equal(np.asarray(rl.xs), np.asarray(other.xs)) and np.array_equal(np.asarray(rl.ys), np.asarray(other.ys))
+                and np.array_equal(np.asarray(rl.frames).reshape(-1), np.asarray(other.frames).reshape(-1)))
+        if not same:
+            raise ValueError(f"rollout_agreement: rl and {name} differ in xs, ys, agent or frames")
+    hr = np.asarray(rl.h())
+    fin = np.isfinite(hr)
+    count = lambda m: m.sum(axis=(1, 2)).astype(np.int64)
+    points, doomed = count(fin), count(fin & (hr >= 0.0))
+    out = dict(points=points, doomed=doomed, doomed_frac=float(doomed.sum() / max(int(points.sum()), 1)))
+    if land is not None:
+        hv = np.asarray(land.h())
+        ok = fin & np.isfinite(hv)
+        missed, conservative = count(ok & (hr >= 0.0) & (hv < 0.0)), count(ok & (hr < 0.0) & (hv >= 0.0))
+        n_doomed, n_free = int(count(ok & (hr >= 0.0)).sum()), int(count(ok & (hr < 0.0)).sum())
+        a = int(rl.agent)
+        d = np.abs(np.asarray(land.Vh, dtype=np.float64)[:, :, :, a] - np.asarray(rl.value, dtype=np.float64)[:, :, :, a])
+        d = d[np.isfinite(d)]
+        out.update(missed=missed, conservative=conservative, missed_frac=float(missed.sum() / max(n_doomed, 1)),
+                   conservative_frac=float(conservative.sum() / max(n_free, 1)),
+                   value_error=float(d.mean()) if d.size else float("nan"))
+    if cost is not None:
+        hc = np.asarray(cost.h())
+        ok = fin & np.isfinite(hc)
+        latent = count(ok & (hc < 0.0) & (hr >= 0.0))
+        out.update(latent=latent, latent_frac=float(latent.sum() / max(int(count(ok & (hc < 0.0)).sum()), 1)))
+    return out
+
+
 def action_admissibility(A) -> Dict[str, np.ndarray]:
     """What the learned barrier admits in an action landscape (trainer.data.ActionLandscape): a grid action is admitted where
     A.h() <= 0, i.e. every component of the swept agent's cbf_deriv is <= 0; a NaN is not admitted.  Per frame [F]: `points`

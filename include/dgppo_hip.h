@@ -448,6 +448,34 @@ int32_t dgppo_shield_select(const float* Vh_next, const float* Vh_t, const float
                             int32_t n_cost, const float* us, int32_t nu, const float* vs, int32_t nv, float dt, float alpha,
                             float margin, float* action, int32_t* index, int32_t* flag, float* h, void* stream);
 
+/* The what-if environments of the sweep above as a dense env state the step kernels run on, for a policy rollout FROM every
+ * swept position: Vh is fitted to the discounted-to-max constraint return of the policy's own future (compute_dec_ocp_gae,
+ * dgppo/algo/utils.py:38-45), which the instantaneous cost of dgppo_cost_sweep does not give.  Env g = (f*ny + iy)*nx + ix, G =
+ * n_frames*ny*nx, is frame fid (fid = frame_ids ? frame_ids[f] : f; operands as in dgppo_graph_feats_sweep) of ONE environment:
+ *   agent_out [G, n, sd]            frame fid's rows; columns 0, 1 of row agent_id become (xs[ix], ys[iy]), every other column
+ *                                   (velocity; the bicycle's heading and speed, lidar_bicycle_target.py:95-107) is kept;
+ *   goal_out  [G, n_goals, sd], obst_out [G, n_obs, 16 | sd]   copies: the step kernels index per-env fields by env;
+ *   hits_out  [G, n, k, 2]          (LiDAR kinds with obstacles; otherwise not written, may be NULL) the recorded hits, row
+ *                                   agent_id cast again from the new position (get_lidar, env/utils.py:115-136,
+ *                                   lidar_env/base.py:126-140: start-inside factor, det == 0 NaN rays, stable top-k);
+ *   carry_out [G*n, HC]             frame fid's rows of carry, read at carry + fid*carry_st ([n, HC] rows, the actor's packed
+ *                                   carry), the same for every grid point of the frame; carry may be NULL: nothing is written.
+ * The reference ships no way to start an episode anywhere but at reset (env/base.py reset).                                   */
+int32_t dgppo_env_sweep_fork(const dgppo_env_cfg* cfg, const float* agent, int64_t agent_st, const float* goal,
+                             const float* obst, const float* hits, int64_t hits_st, const float* ray_cos, const float* ray_sin,
+                             const int32_t* frame_ids, int32_t n_frames, int32_t agent_id, const float* xs, int32_t nx,
+                             const float* ys, int32_t ny, const float* carry, int64_t carry_st, int32_t HC, float* agent_out,
+                             float* goal_out, float* obst_out, float* hits_out, float* carry_out, void* stream);
+
+/* The costs of a K-step rollout, cost [K, G, n, nh] time-major with step stride cost_st (floats), folded into what Vh is
+ * trained on: compute_dec_ocp_gae's Vhs_row recursion (dgppo/algo/utils.py:38-45, discount_to_max=True) at gae_lambda = 1.  Per
+ * (g, agent): V = h[K-1]; for k = K-2 .. 0: m = max_c h[k][c], V[c] = max(h[k][c], one_minus_gamma*m + gamma*V[c]) (one multiply,
+ * one multiply and one add, in that order).  value [G, n, nh] = V, worst [G, n, nh] = max_k h[k][c].  Every max propagates NaN
+ * (jnp.maximum / jnp.max).  Unlike the reference, which bootstraps with Vh of the state after the last step, the row starts
+ * from the last cost itself: the net under test stays out of its own ground truth.  K >= 1, 1 <= nh <= 3.                    */
+int32_t dgppo_constraint_return(const float* cost, int64_t cost_st, int32_t K, int32_t G, int32_t n_agents, int32_t nh,
+                                float gamma, float one_minus_gamma, float* value, float* worst, void* stream);
+
 /* GraphTransformer attention in fixed-fan-in form (dgppo/nn/gnn.py:85-117; jraph.segment_softmax/segment_sum):
  * qt [G*n,H*F] = x_i Mcat + cvec (a Dense), logits = qt . x_sender, masked softmax over the S slots of each agent,
  * zcat [G*n,Kp] = [x_i | per head: sum a x_s (F), sum a e (4) | 1 | 0...], attn [G*n,S,H] saved for backward (NULL in

@@ -16,7 +16,15 @@ the action square the learned barrier admits, in how many frames it admits nothi
 inside.  `--shield` runs the episodes with the learned barrier as a runtime filter (`DGPPO.collect_shielded`): every agent's
 action is kept where the barrier admits it and otherwise replaced by the nearest admissible action of a `--shield-grid`-squared
 grid of [-1, 1]^2 (`--shield-margin M`: admissible means cbf_deriv <= -M).  Every line and file then describes the shielded
-episodes; one more line per episode says how often the shield stepped in, and `{stamp}_{name}_shield.npz` holds its log."""
+episodes; one more line per episode says how often the shield stepped in, and `{stamp}_{name}_shield.npz` holds its log.
+`--rollout-landscape AGENT` measures what the constraint values are trained to predict: from every point of the
+`--landscape-grid`-squared grid, in every frame, the deterministic policy is rolled `--rollout-horizon K` steps forward with
+that agent displaced there (`DGPPO.rollout_landscape`; every algorithm has it) and the costs it meets are folded as the
+training target folds them.  `{stamp}_{name}_rollout.npz` holds the folded value, the worst cost met and the statistics; a
+line per episode says how much of the grid is doomed (unsafe within the horizon) and, with `--landscape` / `--cost-landscape`
+for the same agent, how much of the doomed set the learned Vh misses and how much of it is still safe now (which the
+instantaneous cost cannot show); the animation shows the doomed set's boundary dotted.  With `--shield` the what-if rollouts
+follow the UNSHIELDED policy: they say what the policy alone would do from each point, not what the filter would make of it."""
 import argparse
 import datetime
 import os
@@ -79,7 +87,7 @@ def test(args):
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(EV.csv_line(env, args.epi, agg))
     if (not args.no_video or args.landscape is not None or args.cost_landscape is not None or args.action_landscape is not None
-            or shield_log is not None):
+            or args.rollout_landscape is not None or shield_log is not None):
         videos_dir = pathlib.Path(args.path) / "videos" / f"{step}"
         videos_dir.mkdir(exist_ok=True, parents=True)
         stamp = datetime.datetime.now().strftime("%m%d-%H%M")
@@ -123,6 +131,26 @@ def test(args):
                          frames=A.frames, alpha=A.alpha, dt=A.dt, **adm)
                 print(f"action landscape: {out}")
                 extra["action_landscape"] = A
+            if args.rollout_landscape is not None:
+                rl = algo.rollout_landscape(ro, i, args.rollout_landscape, nx=args.landscape_grid, ny=args.landscape_grid,
+                                            horizon=args.rollout_horizon)
+                same = lambda key, flag: extra.get(key) if flag == args.rollout_landscape else None
+                agree = EV.rollout_agreement(rl, land=same("landscape", args.landscape),
+                                             cost=same("cost_landscape", args.cost_landscape))
+                line = (f"epi: {i}, agent {rl.agent}: within {rl.horizon} steps the policy becomes unsafe from "
+                        f"{agree['doomed_frac'] * 100:.3f}% of the grid (doomed_frac)")
+                if "missed_frac" in agree:
+                    line += (f", the learned Vh misses {agree['missed_frac'] * 100:.3f}% of those points (missed_frac), calls "
+                             f"{agree['conservative_frac'] * 100:.3f}% of the others unsafe (conservative_frac) and is "
+                             f"{agree['value_error']:.4f} off the measured return on average (value_error)")
+                if "latent_frac" in agree:
+                    line += f", {agree['latent_frac'] * 100:.3f}% of the points safe now are doomed (latent_frac)"
+                print(line)
+                out = videos_dir / f"{stamp}_{name}_rollout.npz"
+                np.savez(out, xs=rl.xs, ys=rl.ys, value=rl.value, worst=rl.worst, agent=rl.agent, frames=rl.frames,
+                         horizon=rl.horizon, gamma=rl.gamma, **agree)
+                print(f"rollout landscape: {out}")
+                extra["rollout_landscape"] = rl
             if args.no_video:
                 continue
             out = env.render_video(ro, videos_dir / f"{stamp}_{name}.mp4", unsafe[i], {}, dpi=args.dpi, index=i, **extra)
@@ -147,12 +175,15 @@ ACTION_FLAGS = [(("--action-landscape",), "int", None)]
 # the learned barrier as a runtime filter on every agent's action (DGPPO.collect_shielded): an N x N grid of replacement actions,
 # admissible where cbf_deriv <= -M
 SHIELD_FLAGS = [(("--shield",), "flag", False), (("--shield-grid",), "int", 8), (("--shield-margin",), "float", 0.0)]
+# what Vh is trained to predict, measured (DGPPO.rollout_landscape): the policy rolled K steps forward from every point of the
+# --landscape-grid grid with one agent displaced there, per episode
+ROLLOUT_FLAGS = [(("--rollout-landscape",), "int", None), (("--rollout-horizon",), "int", 32)]
 
 
 def build_parser() -> argparse.ArgumentParser:
     types = {"int": int, "str": str, "float": float}
     ap = argparse.ArgumentParser(description=__doc__)
-    for names, kind, default in FLAGS + COST_FLAGS + ACTION_FLAGS + SHIELD_FLAGS:
+    for names, kind, default in FLAGS + COST_FLAGS + ACTION_FLAGS + SHIELD_FLAGS + ROLLOUT_FLAGS:
         if kind == "flag":
             ap.add_argument(*names, action="store_true", default=False)
         elif kind.startswith("req:"):
