@@ -14,7 +14,8 @@ static int32_t attn_check(const dgppo_env_cfg* cfg, int F, int H, int Kp, int G,
 }
 
 // The attention kernel families, chosen by shape alone; the first one whose conditions hold runs:
-//   SLOT8  F = 8, H = 3, n <= 32, S <= 64 (attn_slot8_shape); the backward writes no input gradient (first layer only)
+//   SLOT8  F = 8, H = 3, n <= 32, S <= 64 (attn_slot8_shape); the backward writes no input gradient (first layer only);
+//          the only family that can do without efeat and without saved weights (dgppo_attn_fwd_rows / _bwd_rows below)
 //   BD     F = 32 block-diagonal topologies (attn_bd_shape)
 //   MFMA   one workgroup per graph on the matrix cores: F % 4 == 0, Kp % 4 == 0, S <= 64, LDS image <= 64 KB; backward for
 //          F >= 16 only
@@ -156,6 +157,51 @@ extern "C" int32_t dgppo_attn_bwd_xo(const dgppo_env_cfg* cfg, int32_t F, int32_
   attn_set_bwd(a, dzcat, attn, qt, Xa, nullptr, efeat, dqt, dXa, dXo);
   a.relu_xo = (relu_xo && dXo) ? 1 : 0;
   return attn_launch(AttnFamily::BD, a, stream, true, "attn_bwd_xo");
+}
+
+// ---- the first layer without its redundant operands (slot-sparse kernels only) --------------------------------------------
+// On the kinds with a 4-float state the node rows carry the state verbatim in columns 0..3, and graph_feats.hip / the act-step
+// kernel form a slot's edge feature as the single rounded difference of those columns (z = w = 0 on a LiDAR hit slot).  The
+// slot-sparse kernels hold both rows in registers, so they subtract instead of reading efeat; and their backward forms the
+// weights again from qt and emask instead of reading what a training forward would have had to write.
+// dgppo_attn_rows_supported tells the caller whether (cfg, F, H) has these modes; every other family and shape refuses them here.
+static bool attn_rows_ok(const dgppo_env_cfg& c, const Topo& t, int F, int H, int Kp) {
+  return attn_slot8_rows_ok(c, t, F, H) && attn_family(t, F, H, Kp, false, false) == AttnFamily::SLOT8 &&
+         attn_family(t, F, H, Kp, true, false) == AttnFamily::SLOT8;
+}
+extern "C" int32_t dgppo_attn_rows_supported(const dgppo_env_cfg* cfg, int32_t F, int32_t H) {
+  AttnArgs a{};
+  const int Kp = (F + H * (F + 4) + 1 + 3) / 4 * 4;         // the width the callers pad zcat to; any Kp % 4 == 0 is taken
+  if (F < 1 || H < 1 || attn_check(cfg, F, H, Kp, 0, a)) return 0;
+  return attn_rows_ok(*cfg, a.t, F, H, Kp) ? 1 : 0;
+}
+extern "C" int32_t dgppo_attn_fwd_rows(const dgppo_env_cfg* cfg, int32_t F, int32_t H, int32_t Kp, const float* qt,
+                                       const float* Xa, const float* Xo, const float* emask, float* zcat, float* attn,
+                                       int32_t G, void* stream) {
+  AttnArgs a{};
+  int32_t rc = attn_check(cfg, F, H, Kp, G, a);
+  if (rc) return rc;
+  DGPPO_REQUIRE(attn_rows_ok(*cfg, a.t, F, H, Kp), "attn_fwd_rows: no such kernel for this configuration (ask dgppo_attn_rows_supported)");
+  if (G == 0) return 0;
+  DGPPO_REQUIRE(qt && Xa && emask && zcat, "attn_fwd_rows: NULL operand");
+  DGPPO_REQUIRE(a.t.Ns == a.t.n || Xo, "attn_fwd_rows: Xo is NULL");
+  attn_set_fwd(a, qt, Xa, Xo, nullptr, emask, zcat, attn);
+  return attn_launch(AttnFamily::SLOT8, a, stream, false, "attn_fwd_rows");
+}
+extern "C" int32_t dgppo_attn_bwd_rows(const dgppo_env_cfg* cfg, int32_t F, int32_t H, int32_t Kp, const float* dzcat,
+                                       const float* attn, const float* qt, const float* emask, const float* Xa, const float* Xo,
+                                       float* dqt, int32_t G, void* stream) {
+  AttnArgs a{};
+  int32_t rc = attn_check(cfg, F, H, Kp, G, a);
+  if (rc) return rc;
+  DGPPO_REQUIRE(attn_rows_ok(*cfg, a.t, F, H, Kp), "attn_bwd_rows: no such kernel for this configuration (ask dgppo_attn_rows_supported)");
+  if (G == 0) return 0;
+  DGPPO_REQUIRE(dzcat && Xa && dqt, "attn_bwd_rows: NULL operand");
+  DGPPO_REQUIRE(attn || (qt && emask), "attn_bwd_rows: without attn the weights need qt and emask");
+  DGPPO_REQUIRE(a.t.Ns == a.t.n || Xo, "attn_bwd_rows: Xo is NULL");
+  attn_set_bwd(a, dzcat, attn, qt, Xa, Xo, nullptr, dqt, nullptr, nullptr);
+  a.emask = emask;
+  return attn_launch(AttnFamily::SLOT8, a, stream, true, "attn_bwd_rows");
 }
 
 extern "C" int64_t dgppo_attn_xo_workspace_bytes(int32_t G) { return G < 0 ? 0 : (int64_t)G * ABD_DW_STRIDE * (int64_t)sizeof(float); }

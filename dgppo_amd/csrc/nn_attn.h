@@ -47,10 +47,10 @@ struct AttnArgs {
   const float* qt;       // [G*n, H*F]
   const float* Xa;       // [G*n, F]
   const float* Xo;       // [G*(Ns-n), F]
-  const float* efeat;    // [G*n, S, 4]
+  const float* efeat;    // [G*n, S, 4]   (slot-sparse kernels, dgppo_attn_fwd_rows / _bwd_rows: NULL = differences of the node rows)
   const float* emask;    // [G*n, S]
   float* zcat;           // [G*n, Kp]   = [x_i | per head: sum a x_s (F), sum a e (4) | 1 | 0-pad]
-  float* attn;           // [G*n, S, H]
+  float* attn;           // [G*n, S, H]   (slot-sparse backward, dgppo_attn_bwd_rows: NULL = formed again from qt and emask)
   // backward
   const float* dzcat;    // [G*n, Kp]
   float* dqt;            // [G*n, H*F]
@@ -119,6 +119,7 @@ size_t attn_image_bytes(const Topo& t, int F, int H, bool bwd);                /
 size_t attn_mfma_smem(const Topo& t, int F, int H, bool bwd);                  // attn_wg.hip
 void launch_attn_wg(const AttnArgs& a, hipStream_t s, bool bwd, bool mfma);
 bool attn_slot8_shape(const Topo& t, int F, int H);                            // attn_slot8.hip
+bool attn_slot8_rows_ok(const dgppo_env_cfg& c, const Topo& t, int F, int H);   // may efeat (and, backward, attn) be left out?
 bool launch_attn_slot8(const AttnArgs& a, hipStream_t s, bool bwd);
 bool attn_bd_shape(const Topo& t, int F, int H, int& PS, bool& hits);          // attn_bd.hip
 bool launch_attn_bd(const AttnArgs& a, hipStream_t s, bool bwd);

@@ -130,7 +130,7 @@ class Engine:
     def __init__(self, cfg: N.EnvCfg, hyper: Hyper, device, T: int = 128,
                  allreduce: Optional[Callable[[torch.Tensor], None]] = None, world: int = 1, prepass_graphs: int = 1 << 20,
                  use_graphs: bool = False, multi_stream: bool = False, algo: str = "dgppo", rank: int = 0,
-                 fused_step: bool = True):
+                 fused_step: bool = True, lean_attn0: bool = True):
         self.cfg, self.hp, self.device, self.T = cfg, hyper, device, T
         assert algo in ("dgppo", "informarl", "hcbfcrpo", "informarl_lagr"), algo
         # "informarl" / "hcbfcrpo": no constraint-value network and no deterministic rollout (informarl.py, hcbfcrpo.py);
@@ -146,6 +146,8 @@ class Engine:
         # one launch per rollout step for head sampling + env.step + the next step's features and layer-0 queries, where the
         # C ABI has such a kernel for the configuration (dgppo_env_act_step_feats_supported); else the four launches
         self.fused_step = bool(fused_step) and OE.act_step_feats_supported(cfg, nets.input_width(cfg), nets.H_HEADS)
+        # the first layer's attention without edge features and saved weights (nets.Net); False: the general entry points
+        self.lean_attn0 = bool(lean_attn0)
         self._ro_cache: Dict[tuple, dict] = {}
         self._upd_graph: dict = {}
         self.n_cost = cfg.n_cost              # 2, or 3 with MPEConnectSpread's connectivity cost
@@ -175,7 +177,7 @@ class Engine:
         self.flat_grads = torch.zeros(tot + 4 * 8, device=device)
         self.n_reduced = tot + 3 * 8
         self.stats = self.flat_grads[tot:tot + 32].view(4, 8)
-        built = {k: nets.Net(kind, cfg, layers, n_out, device, grads=self.flat_grads[o:o + sz], **rnn_kw(k))
+        built = {k: nets.Net(kind, cfg, layers, n_out, device, grads=self.flat_grads[o:o + sz], lean_attn0=self.lean_attn0, **rnn_kw(k))
                  for (k, kind, layers, n_out), o, sz in zip(spec, offs, sizes)}
         if algo == "informarl_lagr":
             self.lagr = torch.full((cfg.n_agents, self.n_cost), float(hyper.lagr_init), device=device)   # informarl_lagr.py:107
@@ -303,6 +305,7 @@ class Engine:
                 OE.act_step_feats(cfg, ro.states_tm[t], act["ms"], eps[t] if stochastic else None, ro.action_tm[t],
                                   ro.log_pi_tm[t] if stochastic else None, ro.states_tm[t + 1], ro.reward_tm[t], ro.cost_tm[t],
                                   **nxt)
+                feats.edges_from_rows = cfg.state_dim == 4     # the step's edges are differences of the rows it wrote, too
             return
         for t in range(T):
             feats = self._feats(tag, ro.states_tm[t], B)

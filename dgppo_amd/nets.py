@@ -116,11 +116,16 @@ class GraphFeats:
         self.Xo = arena.get(f"{tag}.Xo0", max(G * self.n_other, 1), self.Fp)[:G * self.n_other]
         self.efeat = arena.get(f"{tag}.efeat", G * n, S, 4)
         self.emask = arena.get(f"{tag}.emask", G * n, S)
+        # does efeat[i, s] hold, bit for bit, the difference of columns 0..3 of the receiver's and the sender's node row (two
+        # columns, then zeros, on a LiDAR hit slot)?  Every producer below says so for itself; the first-layer attention may
+        # then subtract the rows it holds instead of reading efeat (Net.forward, dgppo_attn_rows_supported)
+        self.edges_from_rows = False
 
     def compute(self, agent, agent_se, agent_st, goal, obst, hits, hits_se, hits_st, env_ids, n_env, n_time):
         assert n_env * n_time == self.G
         K.graph_feats(self.cfg, agent, agent_se, agent_st, goal, obst, hits, hits_se, hits_st, env_ids, n_env, n_time,
                       self.Xa, self.Xo if self.n_other > 0 else None, self.efeat, self.emask, self.Fp)
+        self.edges_from_rows = self.cfg.state_dim == 4      # (the bicycle's velocity columns are products of its 5-float state)
         return self
 
     def compute_record(self, step, slots: int, env, env_ids, n_env, n_time):
@@ -148,6 +153,7 @@ class GraphFeats:
         K.graph_feats_sweep(cfg, step["agent"], n * cfg.state_dim, env["goal"], env.get("obst"), step.get("hits"),
                             n * cfg.top_k * 2, ray_cos, ray_sin, frame_ids, n_frames, agent_id, xs, ys, self.Xa,
                             self.Xo if self.n_other > 0 else None, self.efeat, self.emask, self.Fp, hits_out, frame_max)
+        self.edges_from_rows = False
         return self
 
     def compute_action_sweep(self, step, env, frame_ids, n_frames, agent_id, us, vs, frame_max=None):
@@ -160,6 +166,7 @@ class GraphFeats:
         K.graph_feats_action_sweep(cfg, step["agent"], n * cfg.state_dim, env["goal"], env.get("obst"), step.get("hits"),
                                    n * cfg.top_k * 2, frame_ids, n_frames, agent_id, us, vs, self.Xa,
                                    self.Xo if self.n_other > 0 else None, self.efeat, self.emask, self.Fp, frame_max)
+        self.edges_from_rows = False
         return self
 
     def compute_team_action_sweep(self, st, nst, a_pol, us, vs):
@@ -171,6 +178,7 @@ class GraphFeats:
         K.graph_feats_team_action_sweep(self.cfg, st.step["agent"], nst.step["agent"], st.env["goal"], st.env.get("obst"),
                                         nst.step.get("hits"), a_pol, us, vs, self.Xa, self.Xo if self.n_other > 0 else None,
                                         self.efeat, self.emask, self.Fp)
+        self.edges_from_rows = False
         return self
 
     def compute_vmas(self, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time):
@@ -178,6 +186,7 @@ class GraphFeats:
         assert n_env * n_time == self.G
         K.vmas_graph_feats(self.cfg, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time,
                            self.Xa, self.efeat, self.emask, self.Fp)
+        self.edges_from_rows = False
         return self
 
 
@@ -191,13 +200,17 @@ class Net:
     """One network = flat params + flat grads + prepared GNN weights + forward/backward over a batch of graphs."""
 
     def __init__(self, kind: str, cfg: N.EnvCfg, gnn_layers: int, n_out: int, device, grads: Optional[torch.Tensor] = None,
-                 rnn: str = "gru", rnn_layers: int = 1):
+                 rnn: str = "gru", rnn_layers: int = 1, lean_attn0: bool = True):
         """grads: optional caller-owned flat gradient buffer (a slice of the engine's [g_policy | g_Vl | g_Vh | scalars]
         buffer, so that the data-parallel update all-reduces ALL gradients with one collective).
-        rnn / rnn_layers: "gru" x L stacked cells (dgppo/nn/rnn.py:14-30; the carry of a row is [L * 64]) or "none"."""
+        rnn / rnn_layers: "gru" x L stacked cells (dgppo/nn/rnn.py:14-30; the carry of a row is [L * 64]) or "none".
+        lean_attn0: the first layer's attention reads no edge features and saves no weights where the features allow it
+        (GraphFeats.edges_from_rows) and the C ABI has such kernels (dgppo_attn_rows_supported); False keeps the general entry
+        points (tests, A/B measurements)."""
         assert kind in ("policy", "Vl", "Vh", "Vhg")
         self.kind, self.cfg, self.gnn_layers, self.n_out, self.device = kind, cfg, gnn_layers, n_out, device
         self.rnn, self.rnn_layers = rnn, (rnn_layers if rnn != "none" else 0)
+        self.lean_attn0 = bool(lean_attn0) and K.attn_rows_supported(cfg, input_width(cfg), H_HEADS)
         # packed carry of one row: GRU [h_0 | h_1 | ...]; LSTM [c_0 | h_0 | c_1 | h_1 | ...] (the reference stacks (c, h) as
         # carries 0 and 1 of a layer, rnn.py:23-24); without a cell 64 zeros pass through
         self.carry_dim = HID * max(self.rnn_layers, 1) * (2 if rnn == "lstm" else 1)
@@ -296,8 +309,13 @@ class Net:
                 qt = A.get(f"{tag}.qt{l}", R, H_HEADS * fp)
                 K.dense_fwd(Xa, self.pp(f"gnn{l}.Mcat"), self.pp(f"gnn{l}.cvec"), qt)
             zcat = A.get(f"{tag}.zcat{l}", R, kp)
-            attn = A.get(f"{tag}.attn{l}", R, cfg.fan_in, H_HEADS) if train else None    # only the backward reads the weights
-            if xo_fused is not None:      # other nodes' rows recomputed in the kernel from the raw features (see below)
+            # first layer on features whose edges are differences of its rows: no efeat read, and no weights kept (its backward
+            # forms them again from qt and emask)
+            lean = l == 0 and self.lean_attn0 and feats.edges_from_rows
+            attn = A.get(f"{tag}.attn{l}", R, cfg.fan_in, H_HEADS) if train and not lean else None    # only the backward reads the weights
+            if lean:
+                K.attn_fwd_rows(cfg, fp, H_HEADS, kp, qt, Xa, Xo if Ro > 0 else None, feats.emask, zcat, None, G)
+            elif xo_fused is not None:      # other nodes' rows recomputed in the kernel from the raw features (see below)
                 K.attn_fwd_xo(cfg, fp, H_HEADS, kp, qt, Xa, xo_fused[0], xo_fused[1], xo_fused[2], feats.efeat, feats.emask, zcat, attn, G)
             else:
                 K.attn_fwd(cfg, fp, H_HEADS, kp, qt, Xa, Xo if Ro > 0 else None, feats.efeat, feats.emask, zcat, attn, G)
@@ -306,6 +324,7 @@ class Net:
             Xa_n = A.get(f"{tag}.Xa{l + 1}", R, d)
             K.dense_fwd(zcat, self.pp(f"gnn{l}.Wout"), self.p(f"gnn{l}.bu"), Xa_n, act=1)
             act[f"Xa{l}"], act[f"Xo{l}"], act[f"qt{l}"], act[f"zcat{l}"], act[f"attn{l}"] = Xa, Xo, qt, zcat, attn
+            act[f"lean{l}"] = lean
             if l < self.gnn_layers - 1 and Ro > 0:
                 # goals / hits / obstacles receive no messages: relu(W_u x + b_u)  (gnn.py:109-111 with aggr = 0)
                 if self._xo_fusable(l):
@@ -627,7 +646,10 @@ class Net:
             dXo_l = A.get(f"{tag}.dXo{l}", Ro, fp) if (need_dx and Ro > 0) else None
             more_dXo = dXo_prev is not None and dXo_l is not None       # a dense term still accumulates into dXo_l (>= 3 layers)
             xf = act.get(f"xo_fused{l}")
-            if xf is not None and dXa_l is not None and not more_dXo:
+            if act.get(f"lean{l}"):
+                K.attn_bwd_rows(cfg, fp, H_HEADS, kp, dz, None, act[f"qt{l}"], feats.emask, act[f"Xa{l}"],
+                                act[f"Xo{l}"] if Ro > 0 else None, dqt, G)
+            elif xf is not None and dXa_l is not None and not more_dXo:
                 # the gradient of the recomputed rows never leaves the kernel: it goes straight into dWout_{l-1}[:8] / dbu_{l-1}
                 ws = A.get(f"{tag}.xo_ws", K.attn_xo_workspace_floats(G), 1).view(-1)
                 K.attn_bwd_xo_dw(cfg, fp, H_HEADS, kp, dz, act[f"attn{l}"], act[f"qt{l}"], act[f"Xa{l}"], xf[0], xf[1], xf[2],

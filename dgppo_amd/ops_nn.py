@@ -598,6 +598,46 @@ def attn_bwd(cfg, F, H, Kp, dzcat, attn, qt, Xa, Xo, efeat, dqt, dXa, dXo, G, re
     N.check(rc, "dgppo_attn_bwd")
 
 
+def attn_rows_supported(cfg, F, H) -> bool:
+    """can the layer's kernels do without efeat (and, backward, without saved weights)?  (dgppo_attn_fwd_rows / _bwd_rows: the
+    slot-sparse first-layer kernels on the kinds with a 4-float state)"""
+    return bool(N.lib().dgppo_attn_rows_supported(C.byref(cfg), F, H))
+
+
+def attn_fwd_rows(cfg, F, H, Kp, qt, Xa, Xo, emask, zcat, attn, G):
+    """attn_fwd with the edge features formed in the kernel as differences of the node rows: only for features whose efeat IS
+    that difference (graph_feats, the act-step kernel)."""
+    n, S = cfg.n_agents, cfg.fan_in
+    N.expect_shape(qt, (G * n, H * F), "qt")
+    N.expect_shape(Xa, (G * n, F), "Xa")
+    N.expect_shape(emask, (G * n, S), "emask")
+    N.expect_shape(zcat, (G * n, Kp), "zcat")
+    if attn is not None:
+        N.expect_shape(attn, (G * n, S, H), "attn")
+    FLOPS[0] += 2.0 * G * n * H * S * (2 * F + 4) + 4.0 * G * n * S      # attn_fwd + the four differences of every slot
+    rc = N.lib().dgppo_attn_fwd_rows(C.byref(cfg), F, H, Kp, _p(qt), _p(Xa), _p(Xo), _p(emask), _p(zcat), _p(attn), G,
+                                     N.stream_ptr())
+    N.check(rc, "dgppo_attn_fwd_rows")
+
+
+def attn_bwd_rows(cfg, F, H, Kp, dzcat, attn, qt, emask, Xa, Xo, dqt, G):
+    """first-layer attn_bwd (dqt only) without efeat; attn None: the weights are formed again from qt and emask."""
+    n, S = cfg.n_agents, cfg.fan_in
+    N.expect_shape(dzcat, (G * n, Kp), "dzcat")
+    N.expect_shape(Xa, (G * n, F), "Xa")
+    N.expect_shape(dqt, (G * n, H * F), "dqt")
+    FLOPS[0] += 4.0 * G * n * H * S * (2 * F + 4) + 4.0 * G * n * S
+    if attn is None:
+        N.expect_shape(qt, (G * n, H * F), "qt")
+        N.expect_shape(emask, (G * n, S), "emask")
+        FLOPS[0] += 2.0 * G * n * H * S * F                               # the logits again
+    else:
+        N.expect_shape(attn, (G * n, S, H), "attn")
+    rc = N.lib().dgppo_attn_bwd_rows(C.byref(cfg), F, H, Kp, _p(dzcat), _p(attn), _p(qt), _p(emask), _p(Xa), _p(Xo), _p(dqt), G,
+                                     N.stream_ptr())
+    N.check(rc, "dgppo_attn_bwd_rows")
+
+
 def attn_xo_supported(cfg, F, H, Kp) -> bool:
     """does the topology have an attention kernel that recomputes the other nodes' rows (dgppo_attn_fwd_xo / _bwd_xo)?"""
     return bool(N.lib().dgppo_attn_xo_supported(C.byref(cfg), F, H, Kp))

@@ -494,6 +494,22 @@ int32_t dgppo_attn_fwd(const dgppo_env_cfg* cfg, int32_t F, int32_t H, int32_t K
 int32_t dgppo_attn_bwd(const dgppo_env_cfg* cfg, int32_t F, int32_t H, int32_t Kp, const float* dzcat,
                        const float* attn, const float* qt, const float* Xa, const float* Xo, const float* efeat,
                        float* dqt, float* dXa, float* dXo, int32_t relu_xo, int32_t G, void* stream);
+/* The first layer (F = 8) without the operands its kernels can form themselves.  On the kinds with a 4-float state the node
+ * rows carry the state in columns 0..3 and dgppo_graph_feats / dgppo_env_act_step_feats write efeat[i, s] as the single rounded
+ * difference of those columns of the receiver's and the sender's row (columns 2, 3 are 0 on a LiDAR hit slot), so:
+ * dgppo_attn_fwd_rows = dgppo_attn_fwd without efeat, bit for bit the same zcat / attn when efeat holds those differences;
+ * dgppo_attn_bwd_rows = dgppo_attn_bwd of the first layer (dqt only) without efeat, and with attn == NULL also without the saved
+ * weights, which it forms again from qt and emask with the forward's arithmetic (same bits; qt and emask may be NULL otherwise).
+ * Only the features of those two producers satisfy the identity: a caller with its own efeat uses dgppo_attn_fwd / _bwd.
+ * dgppo_attn_rows_supported: 1 for the slot-sparse kernels (F = 8, H = 3, n <= 32, S <= 64, whole graph within 64 KB) on a kind
+ * with a 4-float state — not the bicycle kinds, not VMASReverseTransport — else 0; the two entry points then return an error
+ * and launch nothing (so does a Kp that is no multiple of 4).                                                              */
+int32_t dgppo_attn_rows_supported(const dgppo_env_cfg* cfg, int32_t F, int32_t H);
+int32_t dgppo_attn_fwd_rows(const dgppo_env_cfg* cfg, int32_t F, int32_t H, int32_t Kp, const float* qt, const float* Xa,
+                            const float* Xo, const float* emask, float* zcat, float* attn, int32_t G, void* stream);
+int32_t dgppo_attn_bwd_rows(const dgppo_env_cfg* cfg, int32_t F, int32_t H, int32_t Kp, const float* dzcat, const float* attn,
+                            const float* qt, const float* emask, const float* Xa, const float* Xo, float* dqt, int32_t G,
+                            void* stream);
 /* The same layer (F = 32) with the sender rows of the nodes WITHOUT incoming edges (goals, LiDAR hits, obstacles) recomputed
  * inside the kernel instead of read: Xo = relu(Xo_raw Wo + bo), Xo_raw [G*(Ns-n),8] their padded raw features, Wo [8,ldwo] the
  * first 8 rows of the previous layer's update weight (Wout of dgppo_gnn_prep), bo [32] its bias — what the reference's
