@@ -184,6 +184,11 @@ def lib() -> C.CDLL:
                                        p, p, p, p, p, p]
     l.dgppo_constraint_return.restype = i32
     l.dgppo_constraint_return.argtypes = [p, i64, i32, i32, i32, i32, f32, f32, p, p, p]
+    # the lookahead shield's (same file)
+    l.dgppo_env_team_action_fork.restype = i32
+    l.dgppo_env_team_action_fork.argtypes = [C.POINTER(EnvCfg), p, p, p, p, p, p, i32, i32, p, i32, p, i32, p, p, p, p, p, p, p]
+    l.dgppo_lookahead_select.restype = i32
+    l.dgppo_lookahead_select.argtypes = [p, i64, i32, i32, i32, i32, p, p, i32, p, i32, f32, p, p, p, p, p]
     _lib = l
     return l
 

@@ -949,19 +949,69 @@ __device__ inline void wave_argmin(float& v, int& i) {
   }
 }
 
+// The choice among an agent's P candidates, shared by the barrier shield and the lookahead shield: a lane feeds its candidates'
+// values to pick_consider and the wave settles in pick_finish.  Candidate 0 is the policy's action (a0, a1), already clipped.
+struct ShieldPick {
+  float bd, bh, h0;       // nearest admissible distance, smallest value, candidate 0's value
+  int bdi, bhi;
+};
+
+__device__ inline ShieldPick pick_init() {
+  ShieldPick k;
+  k.bd = __builtin_inff(); k.bh = __builtin_inff(); k.h0 = 0.0f; k.bdi = 0x7fffffff; k.bhi = 0x7fffffff;
+  return k;
+}
+
+__device__ inline void pick_candidate(int p, float a0, float a1, const float* us, const float* vs, int nu, float& cu, float& cv) {
+  cu = a0; cv = a1;
+  if (p > 0) {
+    const int iv = (p - 1) / nu, iu = (p - 1) - iv * nu;
+    cu = clip_action(us[iu]); cv = clip_action(vs[iv]);
+  }
+}
+
+__device__ inline void pick_consider(ShieldPick& k, float h, int p, float a0, float a1, float thr, const float* us,
+                                     const float* vs, int nu) {
+  if (p == 0) k.h0 = h;
+  float cu, cv;
+  pick_candidate(p, a0, a1, us, vs, nu, cu, cv);
+  if (h <= thr) {                               // admissible (false for a NaN)
+    const float du = cu - a0, dv = cv - a1;
+    float d = du * du + dv * dv;
+    if (d != d) d = __builtin_inff();
+    if (d < k.bd || (d == k.bd && p < k.bdi)) { k.bd = d; k.bdi = p; }
+  }
+  if (h == h && (h < k.bh || (h == k.bh && p < k.bhi))) { k.bh = h; k.bhi = p; }
+}
+
+// every lane of the wave calls it; lane 0 writes the row's choice
+__device__ inline void pick_finish(ShieldPick& k, int lane, long row, float a0, float a1, float thr, const float* us,
+                                   const float* vs, int nu, float* action, int32_t* index, int32_t* flag) {
+  const float h0 = __shfl(k.h0, 0);
+  wave_argmin(k.bd, k.bdi);
+  wave_argmin(k.bh, k.bhi);
+  if (lane != 0) return;
+  int idx, fl;
+  if (h0 <= thr) { idx = 0; fl = 0; }
+  else if (k.bdi != 0x7fffffff) { idx = k.bdi; fl = 1; }
+  else { idx = (k.bhi != 0x7fffffff) ? k.bhi : 0; fl = 2; }
+  float cu, cv;
+  pick_candidate(idx, a0, a1, us, vs, nu, cu, cv);
+  action[row * 2] = cu; action[row * 2 + 1] = cv;
+  index[row] = idx; flag[row] = fl;
+}
+
 __global__ void __launch_bounds__(SHIELD_NT) shield_select_kernel(ShieldArgs a) {
   const int lane = threadIdx.x & (DGPPO_WAVE - 1);
   const long row = (long)blockIdx.x * SHIELD_WAVES + threadIdx.x / DGPPO_WAVE;   // row = e * n + i
   if (row >= a.rows) return;                      // whole waves leave: no lane of a live wave is missing from the shuffles
   const int i = (int)(row % a.n), nh = a.nh, P = a.P;
-  const float inf = __builtin_inff();
   const float* vt = a.Vh_t + row * nh;
   const float* vn = a.Vh_next + ((size_t)row * P * a.n + i) * nh;
   const size_t vn_st = (size_t)a.n * nh;
   const float a0 = clip_action(a.a_pol[row * 2]), a1 = clip_action(a.a_pol[row * 2 + 1]);
   const float thr = -a.margin;
-  float bd = inf, bh = inf, h0 = 0.0f;
-  int bdi = 0x7fffffff, bhi = 0x7fffffff;
+  ShieldPick k = pick_init();
   for (int p = lane; p < P; p += DGPPO_WAVE) {
     float h = 0.0f;
     for (int cc = 0; cc < nh; ++cc) {
@@ -970,35 +1020,9 @@ __global__ void __launch_bounds__(SHIELD_NT) shield_select_kernel(ShieldArgs a) 
       h = (cc == 0) ? hc : nanmax(h, hc);
     }
     if (a.h != nullptr) a.h[(size_t)row * P + p] = h;
-    if (p == 0) h0 = h;
-    float cu = a0, cv = a1;
-    if (p > 0) {
-      const int iv = (p - 1) / a.nu, iu = (p - 1) - iv * a.nu;
-      cu = clip_action(a.us[iu]); cv = clip_action(a.vs[iv]);
-    }
-    if (h <= thr) {                               // admissible (false for a NaN)
-      const float du = cu - a0, dv = cv - a1;
-      float d = du * du + dv * dv;
-      if (d != d) d = inf;
-      if (d < bd || (d == bd && p < bdi)) { bd = d; bdi = p; }
-    }
-    if (h == h && (h < bh || (h == bh && p < bhi))) { bh = h; bhi = p; }
+    pick_consider(k, h, p, a0, a1, thr, a.us, a.vs, a.nu);
   }
-  h0 = __shfl(h0, 0);
-  wave_argmin(bd, bdi);
-  wave_argmin(bh, bhi);
-  if (lane != 0) return;
-  int idx, fl;
-  if (h0 <= thr) { idx = 0; fl = 0; }
-  else if (bdi != 0x7fffffff) { idx = bdi; fl = 1; }
-  else { idx = (bhi != 0x7fffffff) ? bhi : 0; fl = 2; }
-  float cu = a0, cv = a1;
-  if (idx > 0) {
-    const int iv = (idx - 1) / a.nu, iu = (idx - 1) - iv * a.nu;
-    cu = clip_action(a.us[iu]); cv = clip_action(a.vs[iv]);
-  }
-  a.action[row * 2] = cu; a.action[row * 2 + 1] = cv;
-  a.index[row] = idx; a.flag[row] = fl;
+  pick_finish(k, lane, row, a0, a1, thr, a.us, a.vs, a.nu, a.action, a.index, a.flag);
 }
 
 extern "C" int32_t dgppo_shield_select(const float* Vh_next, const float* Vh_t, const float* a_pol, int32_t n_env,
@@ -1263,6 +1287,217 @@ extern "C" int32_t dgppo_constraint_return(const float* cost, int64_t cost_st, i
   if (nh == 1) hipLaunchKernelGGL(constraint_return_kernel<1>, grid, block, 0, s, cost, (long)cost_st, K, rows, gamma, one_minus_gamma, value, worst);
   else if (nh == 2) hipLaunchKernelGGL(constraint_return_kernel<2>, grid, block, 0, s, cost, (long)cost_st, K, rows, gamma, one_minus_gamma, value, worst);
   else hipLaunchKernelGGL(constraint_return_kernel<3>, grid, block, 0, s, cost, (long)cost_st, K, rows, gamma, one_minus_gamma, value, worst);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
+
+// ---- lookahead shield: the what-if environments of one step, per (env, agent, candidate action) -----------------------------------
+// The barrier shield above trusts the learned Vh one step ahead.  The lookahead shield judges a candidate by what it leads to:
+// env g = (e * n + i) * P + p, P = 1 + nv * nu, is a copy of env e in which agent i plays candidate p in the coming step and
+// everyone else the policy's action; the plain step kernels then apply that joint action and the deterministic policy rolls the
+// copy forward (Engine.lookahead_select).  The fork is pure data movement: every field of env e is repeated n * P times, and only
+// row i of the joint action differs between the copies.  The action is NOT clipped here: the step clips (clip_action).
+//
+// Organisation: a workgroup owns FORKT_TILE consecutive output envs, i.e. ONE contiguous range of every output field, and walks
+// each field with unit-stride vector stores; the source vector is found by one division per vector.  The vector width of a field
+// (16, 8 or 4 bytes) is the widest its row length and the alignment of its two pointers allow, chosen on the host.  Words are
+// moved as integers: a NaN's payload and values outside [-1, 1] arrive as they left.
+#define FORKT_NT 256
+#define FORKT_TILE 64   // output envs per workgroup
+
+struct ForkField {
+  const uint32_t* src;    // [n_env, len]
+  uint32_t* dst;          // [G, len]
+  int len;                // words per env; 0: the field is not held
+  int vec;                // words per load / store: 4, 2 or 1
+};
+
+struct TeamForkArgs {
+  ForkField f[5];         // agent, goal, obst, hits, carry
+  const uint32_t* a_pol;  // [n_env, n, 2]
+  const uint32_t* us;
+  const uint32_t* vs;
+  uint32_t* action_out;   // [G, n, 2]
+  long G;
+  int n, nu, P, nP, avec; // avec: 2 where a_pol and action_out are 8-byte aligned
+};
+
+// G < 2^31 (the host checks G * n): env numbers are divided as 32-bit words
+template <typename V>
+__device__ inline void fork_copy(const ForkField& fd, uint32_t g0, int envs, uint32_t nP, int tid) {
+  constexpr int W = sizeof(V) / 4;
+  const int lv = fd.len / W;                                    // vectors per env
+  const V* src = reinterpret_cast<const V*>(fd.src);
+  V* dst = reinterpret_cast<V*>(fd.dst) + (size_t)g0 * lv;
+  const int total = envs * lv;
+  for (int o = tid; o < total; o += FORKT_NT) {
+    const int gl = o / lv, j = o - gl * lv;
+    const uint32_t e = (g0 + (uint32_t)gl) / nP;
+    dst[o] = src[(size_t)e * lv + j];
+  }
+}
+
+__global__ void __launch_bounds__(FORKT_NT) env_team_action_fork_kernel(TeamForkArgs a) {
+  const int tid = threadIdx.x;
+  const uint32_t g0 = blockIdx.x * FORKT_TILE;
+  const int envs = (int)min((long)FORKT_TILE, a.G - (long)g0);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const ForkField& fd = a.f[k];
+    if (fd.len == 0) continue;
+    if (fd.vec == 4) fork_copy<uint4>(fd, g0, envs, (uint32_t)a.nP, tid);
+    else if (fd.vec == 2) fork_copy<uint2>(fd, g0, envs, (uint32_t)a.nP, tid);
+    else fork_copy<uint32_t>(fd, g0, envs, (uint32_t)a.nP, tid);
+  }
+  // the joint action: a_pol[e]'s words, row i replaced by candidate p (p = 0 is a_pol[e, i] itself)
+  const int n = a.n, rows = envs * n;
+  for (int o = tid; o < rows; o += FORKT_NT) {
+    const int gl = o / n, r = o - gl * n;
+    const uint32_t g = g0 + (uint32_t)gl, e = g / (uint32_t)a.nP;
+    const int rem = (int)(g - e * (uint32_t)a.nP), i = rem / a.P, p = rem - i * a.P;
+    uint2 w;
+    if (r == i && p > 0) {
+      const int iv = (p - 1) / a.nu, iu = (p - 1) - iv * a.nu;
+      w.x = a.us[iu]; w.y = a.vs[iv];
+    } else if (a.avec == 2) {
+      w = reinterpret_cast<const uint2*>(a.a_pol)[(size_t)e * n + r];
+    } else {
+      const uint32_t* s = a.a_pol + ((size_t)e * n + r) * 2;
+      w.x = s[0]; w.y = s[1];
+    }
+    const size_t q = (size_t)g0 * n + o;
+    if (a.avec == 2) reinterpret_cast<uint2*>(a.action_out)[q] = w;
+    else { a.action_out[q * 2] = w.x; a.action_out[q * 2 + 1] = w.y; }
+  }
+}
+
+extern "C" int32_t dgppo_env_team_action_fork(const dgppo_env_cfg* cfg, const float* agent, const float* goal, const float* obst,
+                                              const float* hits, const float* a_pol, const float* carry, int32_t HC, int32_t n_env,
+                                              const float* us, int32_t nu, const float* vs, int32_t nv, float* agent_out,
+                                              float* goal_out, float* obst_out, float* hits_out, float* action_out,
+                                              float* carry_out, void* stream) {
+  const char* fn = "dgppo_env_team_action_fork";
+  int32_t rc = dgppo_validate_cfg(cfg);
+  if (rc) {   // the configuration's own refusal, under this entry point's name
+    const std::string why = dgppo_last_error();
+    dgppo_set_error("%s: %s", fn, why.c_str());
+    return rc;
+  }
+  DGPPO_REFUSE_VMAS(cfg, fn, "dgppo_vmas_step on a tiled record (there is no VMAS fork)");
+  DGPPO_REQUIRE(nu >= 1 && nv >= 1, "%s: nu and nv must be >= 1 (got %d, %d)", fn, nu, nv);
+  DGPPO_REQUIRE((long)nu * nv < (1L << 24), "%s: grid too large (nu * nv < 2^24)", fn);
+  DGPPO_REQUIRE(n_env >= 0, "%s: negative counts", fn);
+  const int n = cfg->n_agents, ng = cfg->n_goals, SD = cfg->state_dim, no = cfg->n_obs, k = cfg->top_k;
+  const long P = 1 + (long)nu * nv, nP = (long)n * P;
+  DGPPO_REQUIRE((double)n_env * (double)nP * (double)n < 2147483648.0, "%s: too many envs (G * n < 2^31)", fn);
+  const bool lidar = cfg_is_lidar(*cfg), cast = lidar && no > 0;
+  if (carry != nullptr) {
+    DGPPO_REQUIRE(HC >= 1 && (long)n * HC < (1L << 24), "%s: HC %d out of range", fn, HC);
+  }
+  if (n_env == 0) return 0;
+  DGPPO_REQUIRE(agent && goal && a_pol && us && vs && agent_out && goal_out && action_out, "%s: NULL operand", fn);
+  if (no > 0) {
+    DGPPO_REQUIRE(obst, "%s: obst is NULL", fn);
+    DGPPO_REQUIRE(obst_out, "%s: obst_out is NULL", fn);
+  }
+  if (cast) {
+    DGPPO_REQUIRE(hits, "%s: hits is NULL", fn);
+    DGPPO_REQUIRE(hits_out, "%s: hits_out is NULL", fn);
+  } else {
+    DGPPO_REQUIRE(!hits && !hits_out, "%s: hits / hits_out are for the kinds that cast rays (LiDAR with obstacles)", fn);
+  }
+  if (carry != nullptr) DGPPO_REQUIRE(carry_out, "%s: carry_out is NULL", fn);
+  const int OS = lidar ? DGPPO_RECT_STRIDE : SD;
+  TeamForkArgs a;
+  auto field = [](const float* s, float* d, long len) {
+    ForkField f;
+    f.src = reinterpret_cast<const uint32_t*>(s); f.dst = reinterpret_cast<uint32_t*>(d); f.len = (int)len;
+    const uintptr_t al = (uintptr_t)s | (uintptr_t)d;
+    f.vec = (len % 4 == 0 && al % 16 == 0) ? 4 : (len % 2 == 0 && al % 8 == 0) ? 2 : 1;
+    return f;
+  };
+  a.f[0] = field(agent, agent_out, (long)n * SD);
+  a.f[1] = field(goal, goal_out, (long)ng * SD);
+  a.f[2] = field(obst, obst_out, no > 0 ? (long)no * OS : 0);
+  a.f[3] = field(hits, hits_out, cast ? (long)n * k * 2 : 0);
+  a.f[4] = field(carry, carry_out, carry != nullptr ? (long)n * HC : 0);
+  a.a_pol = reinterpret_cast<const uint32_t*>(a_pol);
+  a.us = reinterpret_cast<const uint32_t*>(us); a.vs = reinterpret_cast<const uint32_t*>(vs);
+  a.action_out = reinterpret_cast<uint32_t*>(action_out);
+  a.avec = (((uintptr_t)a_pol | (uintptr_t)action_out) % 8 == 0) ? 2 : 1;
+  a.G = (long)n_env * nP; a.n = n; a.nu = nu; a.P = (int)P; a.nP = (int)nP;
+  const dim3 grid((unsigned)((a.G + FORKT_TILE - 1) / FORKT_TILE));
+  hipLaunchKernelGGL(env_team_action_fork_kernel, grid, dim3(FORKT_NT), 0, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
+
+// ---- lookahead shield: selection on the rolled costs ----------------------------------------------------------------------------
+// Per (env e, agent i), over the P candidates of the fork above, on the agent's OWN row of its own what-if env g = (e * n + i) * P
+// + p:  s[p] = max over the K steps and the nh components of cost[k][g, i, c] — the worst cost (get_cost,
+// lidar_env/base.py:203-205) agent i meets within the horizon if it plays candidate p now; NaN-propagating max.  Admissible iff
+// s <= -margin; the choice among the candidates is shield_select_kernel's: the same pick_consider / pick_finish.  One wave per (e, i), lanes over the
+// candidates: a lane folds K * nh words of ONE row per candidate, 1 / n of what a fold over every row of the what-if envs
+// (dgppo_constraint_return) would read, and nothing but the outputs is written.
+struct LookaheadArgs {
+  const float* cost;      // step 1 of the block record: [K][G, n, nh] with step stride cost_st
+  long cost_st;
+  const float* a_pol;     // [E, n, 2]
+  const float* us;
+  const float* vs;
+  int rows, n, nh, nu, P, K;
+  float margin;
+  float* action;          // [E, n, 2]
+  int32_t* index;         // [E, n]
+  int32_t* flag;          // [E, n]
+  float* s;               // [E, n, P] or NULL
+};
+
+__global__ void __launch_bounds__(SHIELD_NT) lookahead_select_kernel(LookaheadArgs a) {
+  const int lane = threadIdx.x & (DGPPO_WAVE - 1);
+  const long row = (long)blockIdx.x * SHIELD_WAVES + threadIdx.x / DGPPO_WAVE;   // row = e * n + i
+  if (row >= a.rows) return;                      // whole waves leave: no lane of a live wave is missing from the shuffles
+  const int i = (int)(row % a.n), nh = a.nh, P = a.P;
+  const float a0 = clip_action(a.a_pol[row * 2]), a1 = clip_action(a.a_pol[row * 2 + 1]);
+  const float thr = -a.margin;
+  ShieldPick k = pick_init();
+  for (int p = lane; p < P; p += DGPPO_WAVE) {
+    const float* c = a.cost + (((size_t)row * P + p) * a.n + i) * nh;
+    float h = c[0];
+    for (int st = 0; st < a.K; ++st, c += a.cost_st)
+      for (int cc = 0; cc < nh; ++cc) h = nanmax(h, c[cc]);
+    if (a.s != nullptr) a.s[(size_t)row * P + p] = h;
+    pick_consider(k, h, p, a0, a1, thr, a.us, a.vs, a.nu);
+  }
+  pick_finish(k, lane, row, a0, a1, thr, a.us, a.vs, a.nu, a.action, a.index, a.flag);
+}
+
+extern "C" int32_t dgppo_lookahead_select(const float* cost, int64_t cost_st, int32_t K, int32_t n_env, int32_t n_agents,
+                                          int32_t n_cost, const float* a_pol, const float* us, int32_t nu, const float* vs,
+                                          int32_t nv, float margin, float* action, int32_t* index, int32_t* flag, float* s,
+                                          void* stream) {
+  const char* fn = "dgppo_lookahead_select";
+  DGPPO_REQUIRE(n_env >= 0 && n_agents >= 1, "%s: n_env >= 0 and n_agents >= 1 are required", fn);
+  DGPPO_REQUIRE(n_cost >= 1 && n_cost <= 3, "%s: n_cost %d outside [1, 3]", fn, n_cost);
+  DGPPO_REQUIRE(K >= 1, "%s: K must be >= 1 (got %d)", fn, K);
+  DGPPO_REQUIRE(nu >= 1 && nv >= 1, "%s: nu and nv must be >= 1 (got %d, %d)", fn, nu, nv);
+  DGPPO_REQUIRE((long)nu * nv < (1L << 24), "%s: grid too large (nu * nv < 2^24)", fn);
+  DGPPO_REQUIRE(margin == margin, "%s: margin must not be NaN", fn);
+  const long P = 1 + (long)nu * nv;
+  DGPPO_REQUIRE((double)n_env * (double)n_agents * (double)P * (double)n_agents < 2147483648.0,
+                "%s: too many envs (G * n < 2^31)", fn);
+  const long rows = (long)n_env * n_agents, step = rows * P * n_agents * n_cost;
+  DGPPO_REQUIRE(K == 1 || cost_st >= step, "%s: the step stride %ld is shorter than a step (%ld floats)", fn, (long)cost_st, step);
+  if (n_env == 0) return 0;
+  DGPPO_REQUIRE(cost && a_pol && us && vs && action && index && flag, "%s: NULL operand", fn);
+  LookaheadArgs a;
+  a.cost = cost; a.cost_st = (long)cost_st; a.a_pol = a_pol; a.us = us; a.vs = vs;
+  a.rows = (int)rows; a.n = n_agents; a.nh = n_cost; a.nu = nu; a.P = (int)P; a.K = K;
+  a.margin = margin; a.action = action; a.index = index; a.flag = flag; a.s = s;
+  const dim3 grid((unsigned)((rows + SHIELD_WAVES - 1) / SHIELD_WAVES));
+  hipLaunchKernelGGL(lookahead_select_kernel, grid, dim3(SHIELD_NT), 0, (hipStream_t)stream, a);
   DGPPO_LAUNCH_CHECK();
   return 0;
 }

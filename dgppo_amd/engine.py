@@ -283,21 +283,21 @@ class Engine:
         f = nets.GraphFeats(self.cfg, n_env * n_time, self.arena, tag)
         return f.compute_record(st.step, slots, st.env, env_ids, n_env, n_time)
 
-    def _rollout_steps(self, ro: RolloutData, eps, B: int, stochastic: bool):
-        """the ro.T env steps of a rollout from the state and carry in slot 0 of the record: policy forward (GNN + GRU + head)
-        and env.step, all on the current stream.  The step count is the record's (self.T in rollout(), the horizon in
-        rollout_landscape())."""
+    def _rollout_steps(self, ro: RolloutData, eps, B: int, stochastic: bool, start: int = 0):
+        """the env steps start .. ro.T - 1 of a rollout from the state and carry in slot `start` of the record: policy forward
+        (GNN + GRU + head) and env.step, all on the current stream.  The step count is the record's (self.T in rollout(), the
+        horizon in rollout_landscape(); lookahead_select() starts at slot 1, behind its forced first step)."""
         cfg, T, n = self.cfg, ro.T, self.cfg.n_agents
         tag = "ro" if stochastic else "rod"    # separate scratch per kind: the two rollouts may run on different streams
         if self.fused_step:
             # features and queries of step 0 from the stand-alone kernels; every step's launch then leaves those of the next
             # state in the same buffers, which the next forward reads
             pol, R = self.policy, B * n
-            feats = self._feats(tag, ro.states_tm[0], B)
+            feats = self._feats(tag, ro.states_tm[start], B)
             Mcat, cvec = pol.pp("gnn0.Mcat"), pol.pp("gnn0.cvec")
             qt0 = pol.arena.get(f"{tag}.qt0", R, Mcat.shape[1])
             K.dense_fwd(feats.Xa, Mcat, cvec, qt0)
-            for t in range(T):
+            for t in range(start, T):
                 act = pol.forward(feats, n_seq=R, T=1, h0=ro.rnn_tm[t].view(R, self.HC), tag=tag,
                                   hs_out=ro.rnn_tm[t + 1].view(R, self.HC), train=False, qt0=qt0)
                 nxt = dict(Xa=feats.Xa, Xo=feats.Xo, efeat=feats.efeat, emask=feats.emask, Fp=feats.Fp, Mcat=Mcat, cvec=cvec,
@@ -307,7 +307,7 @@ class Engine:
                                   **nxt)
                 feats.edges_from_rows = cfg.state_dim == 4     # the step's edges are differences of the rows it wrote, too
             return
-        for t in range(T):
+        for t in range(start, T):
             feats = self._feats(tag, ro.states_tm[t], B)
             act = self.policy.forward(feats, n_seq=B * n, T=1, h0=ro.rnn_tm[t].view(B * n, self.HC), tag=tag,
                                       hs_out=ro.rnn_tm[t + 1].view(B * n, self.HC), train=False)
@@ -812,6 +812,137 @@ class Engine:
             # 7. the step that counts
             OE.step(cfg, st, ro.action_tm[t], nst, ro.reward_tm[t], ro.cost_tm[t])
             mark(ev)
+            if ev is not None:
+                events.append(tuple(ev))
+        return ro, log
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # lookahead shield: every agent's action filtered by forked policy rollouts — the simulator and the policy, no Vh
+    # ------------------------------------------------------------------------------------------------------------------
+    def lookahead_select(self, st: OE.State, carry_next, a_pol, us, vs, horizon: int, margin: float, action, index, flag, s,
+                         records: Optional[list] = None, t: int = 0, mark: Optional[Callable[[], None]] = None):
+        """The core of one lookahead-shield step on a dense state `st` of B envs: for every (env e, agent i, candidate p) —
+        candidate 0 is a_pol[e, i], candidate 1 + iv * nu + iu is (us[iu], vs[iv]), the numbering of dgppo_shield_select — env e
+        is forked (dgppo_env_team_action_fork) with agent i playing the candidate and everyone else a_pol[e], the plain env step
+        applies that joint action, and the deterministic policy is rolled on from there (_rollout_steps from slot 1, with the
+        carry carry_next [B * n, HC] the policy left after its forward on `st`; None without an RNN) until the costs of the
+        `horizon` states after the forced step are known.  s [B, n, P] is the worst of those costs on the agent's own row;
+        dgppo_lookahead_select admits a candidate iff s <= -margin and picks per agent by dgppo_shield_select's rules ->
+        action [B, n, 2] (clipped), index / flag [B, n] int32.  us / vs: ops_nn.sweep_axis tensors.
+        Walked in blocks of whole environments: Eb envs, G = Eb * n * P what-if envs in a record of horizon + 1 steps, with
+        G * (horizon + 2) <= prepass_graphs and never fewer than one env.  The last step of the block record exists only to
+        evaluate the cost of the last state.
+        Two limits, as in rollout_shielded: agent i's candidates are judged with everyone else playing the policy, so when
+        several agents are replaced in the same step the joint outcome is not one that was rolled; and the what-if rollouts
+        run past the episode's end (there is no done flag in these environments).
+        records: a list that receives (t, e0, Eb, block record) per block (time-major, as rolled; the tests re-derive every
+        step of those); without it the block records are reused from call to call.  mark: called after the fork and forced
+        step, after the policy steps and after the selection of every block (rollout_lookahead_shielded's events)."""
+        cfg = self.cfg
+        if cfg.is_vmas:
+            raise ValueError("lookahead_select: VMASReverseTransport is not supported")
+        n, HC = cfg.n_agents, self.HC
+        H = int(horizon)
+        if H < 1:
+            raise ValueError(f"lookahead_select: horizon must be >= 1 (got {horizon})")
+        margin = float(margin)
+        if not np.isfinite(margin):
+            raise ValueError("lookahead_select: margin must be finite")
+        if self.hp.use_rnn and carry_next is None:
+            raise ValueError("lookahead_select: this engine's policy has a recurrent cell: carry_next is required")
+        if not self.hp.use_rnn:
+            carry_next = None
+        B = int(a_pol.shape[0])
+        P = 1 + int(us.numel()) * int(vs.numel())
+        block = max(1, min(B, max(1, self.prepass_graphs) // (n * P * (H + 2))))
+        cache = self._la_records = getattr(self, "_la_records", {})
+        for e0 in range(0, B, block):
+            Eb = min(block, B - e0)
+            sl = slice(e0, e0 + Eb)
+            G = Eb * n * P
+            rec = cache.get((G, H)) if records is None else None
+            if rec is None:
+                rec = RolloutData(cfg, G, H + 1, self.device, False, HC)
+                if records is None:
+                    if len(cache) >= 2:                 # a call walks two block sizes at most: the full block and the last one
+                        cache.clear()
+                    cache[(G, H)] = rec
+            cut = OE.State({k: x[sl] for k, x in st.step.items()}, {k: x[sl] for k, x in st.env.items()})
+            if carry_next is None:
+                rec.rnn_tm[1].zero_()
+            OE.team_action_fork(cfg, cut, a_pol[sl], us, vs, rec.states_tm[0], rec.action_tm[0],
+                                carry_next[e0 * n:(e0 + Eb) * n] if carry_next is not None else None,
+                                rec.rnn_tm[1].view(G * n, HC) if carry_next is not None else None)
+            OE.step(cfg, rec.states_tm[0], rec.action_tm[0], rec.states_tm[1], rec.reward_tm[0], rec.cost_tm[0])
+            if mark:
+                mark()
+            self._rollout_steps(rec, None, G, False, start=1)
+            if mark:
+                mark()
+            K.lookahead_select(rec.cost_tm[1:H + 1], a_pol[sl], us, vs, margin, action[sl], index[sl], flag[sl], s[sl])
+            if mark:
+                mark()
+            if records is not None:
+                records.append((int(t), e0, Eb, rec))
+
+    def rollout_lookahead_shielded(self, seeds: torch.Tensor, us, vs, horizon: int, margin: float = 0.0,
+                                   events: Optional[list] = None, records: Optional[list] = None):
+        """-> (RolloutData, log): a deterministic record (the conventions of rollout(seeds, False)) in which, at every step,
+        every agent's action is filtered by what it leads to within `horizon` steps of the simulator, the learned Vh left out:
+        what rollout_shielded trusts Vh to predict is rolled here.  Per step t: the policy forward on state t gives a_pol and
+        the post-step carry h_{t+1} (written to rnn_tm[t + 1]; it does not depend on the action taken); lookahead_select forks
+        state t per (env, agent, candidate), applies the forced joint action, rolls the deterministic policy and picks per
+        agent on the worst own-row cost of the `horizon` states that follow (admissible iff <= -margin); the step with the
+        chosen actions writes state t + 1.  Reward and cost belong to the pre-step state.  It needs the simulator and the policy
+        only: every algo and --no-rnn engines have it.  The limits stated at lookahead_select hold: the others are assumed to
+        play the policy, and the what-if rollouts run past the episode's end.
+        log (time-major device tensors): policy_action [T, B, n, 2], index / flag [T, B, n] (int32; flag 0 kept, 1 replaced by
+        an admissible candidate, 2 nothing admissible), s [T, B, n, P].  Eager launches; the record is a fresh one.
+        events: a list that receives one tuple of device events per step (tools/bench_lookahead_shield.py): start, policy
+        forward done, then (fork and forced step, policy steps, select) done per env block, the final step done.
+        records: as in lookahead_select."""
+        cfg, T = self.cfg, self.T
+        if cfg.is_vmas:
+            raise ValueError("rollout_lookahead_shielded: VMASReverseTransport is not supported")
+        n, HC = cfg.n_agents, self.HC
+        H = int(horizon)
+        if H < 1:
+            raise ValueError(f"rollout_lookahead_shielded: horizon must be >= 1 (got {horizon})")
+        margin = float(margin)
+        if not np.isfinite(margin):
+            raise ValueError("rollout_lookahead_shielded: margin must be finite")
+        us, vs = K.sweep_axis(us, "us", self.device), K.sweep_axis(vs, "vs", self.device)
+        P = 1 + int(us.numel()) * int(vs.numel())
+        B = int(seeds.shape[0])
+        dev = self.device
+        ro = RolloutData(cfg, B, T, dev, False, HC)
+        OE.reset(cfg, seeds, ro.states_tm[0], self.reset_failed)
+        ro.rnn_tm[0].zero_()
+        log = dict(policy_action=torch.empty(T, B, n, 2, device=dev), index=torch.empty(T, B, n, dtype=torch.int32, device=dev),
+                   flag=torch.empty(T, B, n, dtype=torch.int32, device=dev), s=torch.empty(T, B, n, P, device=dev))
+        for t in range(T):
+            st = ro.states_tm[t]
+            ev = [] if events is not None else None
+
+            def mark():
+                if ev is not None:
+                    ev.append(torch.cuda.Event(enable_timing=True))
+                    ev[-1].record()
+            mark()
+            # 1. policy forward: a_pol and h_{t+1}
+            feats = self._feats("la", st, B)
+            h_next = ro.rnn_tm[t + 1].view(B * n, HC)
+            act = self.policy.forward(feats, n_seq=B * n, T=1, h0=ro.rnn_tm[t].view(B * n, HC), tag="la", hs_out=h_next,
+                                      train=False)
+            a_pol = log["policy_action"][t]
+            K.policy_head(act["ms"], None, None, a_pol.view(B * n, 2), None, None, n, 1)
+            mark()
+            # 2. - 5. fork, forced step, policy steps, selection: blocks of environments
+            self.lookahead_select(st, h_next if self.hp.use_rnn else None, a_pol, us, vs, H, margin, ro.action_tm[t],
+                                  log["index"][t], log["flag"][t], log["s"][t], records=records, t=t, mark=mark)
+            # 6. the step that counts
+            OE.step(cfg, st, ro.action_tm[t], ro.states_tm[t + 1], ro.reward_tm[t], ro.cost_tm[t])
+            mark()
             if ev is not None:
                 events.append(tuple(ev))
         return ro, log

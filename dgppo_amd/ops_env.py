@@ -374,6 +374,55 @@ def sweep_fork(cfg: N.EnvCfg, step: Dict[str, torch.Tensor], env: Dict[str, torc
     N.check(rc_, "dgppo_env_sweep_fork")
 
 
+def team_action_fork(cfg: N.EnvCfg, st: State, a_pol, us, vs, out: State, action_out, carry=None, carry_out=None):
+    """dgppo_env_team_action_fork: the G = B * n * P what-if envs of one lookahead-shield step into `out` (State.empty(cfg, G,
+    device)), P = 1 + nv * nu — env (e * n + i) * P + p is a copy of env e of the dense state `st` (B envs), and action_out
+    [G, n, 2] its joint action: a_pol[e] [n, 2] with row i replaced by candidate p (0: a_pol[e, i]; 1 + iv * nu + iu: (us[iu],
+    vs[iv]); unclipped, the step clips).  us / vs are ops_nn.sweep_axis tensors.  carry [B * n, HC] is copied into carry_out
+    [G * n, HC] for every copy of its env; None: no carry.  Every refusal is raised before anything is launched."""
+    from . import ops_nn as K                     # the operand checks the shield bindings share
+    fn = "team_action_fork"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no fork entry point")
+    n = cfg.n_agents
+    if not (torch.is_tensor(a_pol) and a_pol.ndim == 3):
+        raise ValueError(f"{fn}: a_pol must be a [B, n, 2] tensor")
+    B = int(a_pol.shape[0])
+    for name, t_ in (("us", us), ("vs", vs)):
+        if not (torch.is_tensor(t_) and t_.ndim == 1 and t_.numel() > 0):
+            raise ValueError(f"{fn}: {name} must be a non-empty 1-D tensor (sweep_axis)")
+    P = 1 + int(us.numel()) * int(vs.numel())
+    G = B * n * P
+    operands = [("a_pol", a_pol, (B, n, 2)), ("action_out", action_out, (G, n, 2))]
+    for fields, src, dst in zip(record_fields(cfg), (st.step, st.env), (out.step, out.env)):
+        for name, shape in fields.items():
+            if src.get(name) is None:
+                raise ValueError(f"{fn}: the state has no {name}")
+            if dst.get(name) is None:
+                raise ValueError(f"{fn}: out has no {name}")
+            operands += [(name, src[name], (B,) + shape), (f"out.{name}", dst[name], (G,) + shape)]
+    HC = 0
+    if carry is not None:
+        if not (torch.is_tensor(carry) and carry.ndim == 2 and carry.shape[0] == B * n and carry.shape[1] >= 1):
+            raise ValueError(f"{fn}: carry must be [B * n, HC] = [{B * n}, HC]")
+        HC = int(carry.shape[1])
+        if carry_out is None:
+            raise ValueError(f"{fn}: carry_out is required with a carry")
+        operands += [("carry", carry, (B * n, HC)), ("carry_out", carry_out, (G * n, HC))]
+    K._shaped(fn, operands)
+    nu, nv = K._shield_axes(fn, us, vs)
+    cast = cfg.is_lidar and cfg.n_obs > 0
+    s, e, o_s, o_e = st.step, st.env, out.step, out.env
+    rc = N.lib().dgppo_env_team_action_fork(
+        C.byref(cfg), N.ptr(s["agent"], name="agent"), N.ptr(e["goal"], name="goal"), N.ptr(e.get("obst"), name="obst"),
+        N.ptr(s["hits"] if cast else None, name="hits"), N.ptr(a_pol, name="a_pol"), N.ptr(carry, name="carry"), HC, B,
+        N.ptr(us, name="us"), nu, N.ptr(vs, name="vs"), nv, N.ptr(o_s["agent"], name="out.agent"),
+        N.ptr(o_e["goal"], name="out.goal"), N.ptr(o_e.get("obst"), name="out.obst"),
+        N.ptr(o_s["hits"] if cast else None, name="out.hits"), N.ptr(action_out, name="action_out"),
+        N.ptr(carry_out if carry is not None else None, name="carry_out"), N.stream_ptr())
+    N.check(rc, "dgppo_env_team_action_fork")
+
+
 def materialize(cfg: N.EnvCfg, st: State, graph: Dict[str, torch.Tensor]):
     if cfg.is_vmas:
         return vmas_graph_materialize(cfg, st.agent, st.body, st.scene, graph)

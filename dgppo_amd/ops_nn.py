@@ -555,6 +555,56 @@ def shield_select(Vh_next, Vh_t, a_pol, us, vs, dt: float, alpha: float, margin:
     N.check(rc, "dgppo_shield_select")
 
 
+def _shaped(fn: str, operands):
+    """operands: (name, tensor, shape[, dtype]) tuples.  Every shape is looked at before anything else — a wrong shape is named
+    as such whatever else is wrong with the operands — then each has to be a dense CUDA tensor of its dtype (_dense)."""
+    for name, t_, shape, *_ in operands:
+        if not torch.is_tensor(t_) or tuple(t_.shape) != tuple(shape):
+            got = tuple(t_.shape) if torch.is_tensor(t_) else type(t_).__name__
+            raise ValueError(f"{fn}: {name}: expected shape {tuple(shape)}, got {got}")
+    for name, t_, shape, *dtype in operands:
+        _dense(fn, name, t_, shape, *dtype)
+
+
+def lookahead_select(cost_tm, a_pol, us, vs, margin: float, action, index, flag, s=None):
+    """dgppo_lookahead_select on a block of E environments: cost_tm [K, G, n, nh] are the costs of the K states after the forced
+    step of the G = E * n * P what-if envs of ops_env.team_action_fork (slots 1 .. K of the block record's cost_tm; the steps may
+    be strided, each is dense), P = 1 + nv * nu; a_pol [E, n, 2] -> action [E, n, 2], index / flag [E, n] int32 and, if given,
+    s [E, n, P]: the worst own-row cost of every candidate.  The rule is stated next to the declaration in include/dgppo_hip.h.
+    Every refusal is raised before anything is launched."""
+    fn = "lookahead_select"
+    if not (torch.is_tensor(a_pol) and a_pol.ndim == 3 and a_pol.shape[2] == 2 and a_pol.shape[1] >= 1):
+        raise ValueError(f"{fn}: a_pol must be a [E, n, 2] tensor")
+    E, n = int(a_pol.shape[0]), int(a_pol.shape[1])
+    if not (torch.is_tensor(cost_tm) and cost_tm.ndim == 4):
+        raise ValueError(f"{fn}: cost_tm must be a [K, G, n, nh] tensor")
+    K_, nh = int(cost_tm.shape[0]), int(cost_tm.shape[3])
+    if K_ < 1:
+        raise ValueError(f"{fn}: K must be >= 1")
+    if not 1 <= nh <= 3:
+        raise ValueError(f"{fn}: n_cost {nh} outside [1, 3]")
+    for name, t_ in (("us", us), ("vs", vs)):
+        if not (torch.is_tensor(t_) and t_.ndim == 1 and t_.numel() > 0):
+            raise ValueError(f"{fn}: {name} must be a non-empty 1-D tensor (sweep_axis)")
+    P = 1 + int(us.numel()) * int(vs.numel())
+    G = E * n * P
+    if tuple(cost_tm.shape[1:]) != (G, n, nh):
+        raise ValueError(f"{fn}: cost_tm: expected shape (K, {G}, {n}, {nh}), got {tuple(cost_tm.shape)}")
+    if np.isnan(float(margin)):
+        raise ValueError(f"{fn}: margin must not be NaN")
+    _shaped(fn, [("a_pol", a_pol, (E, n, 2)), ("cost_tm[0]", cost_tm[0], (G, n, nh)), ("action", action, (E, n, 2)),
+                 ("index", index, (E, n), torch.int32), ("flag", flag, (E, n), torch.int32)]
+            + ([("s", s, (E, n, P))] if s is not None else []))
+    nu, nv = _shield_axes(fn, us, vs)
+    cost_st = int(cost_tm.stride(0)) if K_ > 1 else G * n * nh
+    if cost_st < G * n * nh:
+        raise ValueError(f"{fn}: the steps of cost_tm overlap (stride {cost_st} < {G * n * nh})")
+    rc = N.lib().dgppo_lookahead_select(
+        _p(cost_tm[0], "cost"), cost_st, K_, E, n, nh, _p(a_pol, "a_pol"), _p(us, "us"), nu, _p(vs, "vs"), nv, float(margin),
+        _p(action, "action"), _p(index, "index", torch.int32), _p(flag, "flag", torch.int32), _p(s, "s"), N.stream_ptr())
+    N.check(rc, "dgppo_lookahead_select")
+
+
 def vmas_graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time,
                      Xa, efeat, emask, Fp):
     """dgppo_vmas_graph_feats: graph_feats for VMASReverseTransport (agent [.., n, 4] and body [.., 4] records addressed

@@ -95,6 +95,21 @@ class ShieldLog(NamedTuple):
     dt: float
 
 
+class LookaheadShieldLog(NamedTuple):
+    """What the lookahead shield did in the episodes of `collect_lookahead_shielded`, env-major like the Rollout next to it.
+    The candidates are numbered as in ShieldLog; s is the worst cost the agent itself meets in the `horizon` states after
+    playing the candidate, everyone else and every later step following the policy; admissible where s <= -margin."""
+    policy_action: np.ndarray   # [B, T, n, 2]: what the policy wanted
+    action: np.ndarray          # [B, T, n, 2]: what was executed (the Rollout's actions)
+    index: np.ndarray           # [B, T, n] int32: the candidate executed
+    flag: np.ndarray            # [B, T, n] int32: 0 kept, 1 replaced by an admissible candidate, 2 nothing admissible
+    s: np.ndarray               # [B, T, n, P]: the worst rolled cost of every candidate, P = 1 + nv * nu
+    us: np.ndarray              # [nu] fp32 grid lines of the first action component
+    vs: np.ndarray              # [nv] of the second
+    margin: float
+    horizon: int
+
+
 class ActionLandscape(NamedTuple):
     """The discrete control barrier condition of DGPPO (dgppo/algo/dgppo.py:246-250) with one agent's action swept over a grid
     in frames of an episode (`DGPPO.action_landscape`): cbf = (Vh_next - Vh) / dt + alpha * Vh, where Vh_next is the learned

@@ -476,6 +476,35 @@ int32_t dgppo_env_sweep_fork(const dgppo_env_cfg* cfg, const float* agent, int64
 int32_t dgppo_constraint_return(const float* cost, int64_t cost_st, int32_t K, int32_t G, int32_t n_agents, int32_t nh,
                                 float gamma, float one_minus_gamma, float* value, float* worst, void* stream);
 
+/* The what-if environments of ONE step of a lookahead shield, as a dense env state the step kernels run on: env
+ * g = (e*n + i)*P + p, P = 1 + nv*nu, G = n_env*n*P, is a copy of env e in which agent i is about to play candidate p and
+ * everyone else the policy's action; candidate 0 is a_pol[e, i], candidate 1 + iv*nu + iu is (us[iu], vs[iv]) — the numbering
+ * of dgppo_shield_select.  All operands are dense: agent [n_env, n, sd], goal [n_env, n_goals, sd], obst [n_env, n_obs, 16 | sd]
+ * (NULL without obstacles), hits [n_env, n, k, 2] (LiDAR kinds with obstacles; NULL for every other kind, as is hits_out),
+ * a_pol [n_env, n, 2], carry [n_env*n, HC] (the actor's packed carry after the step; NULL: carry_out is not written).  Outputs:
+ * the same fields for the G envs, every one a copy of env e's rows, and action_out [G, n, 2]: row i of env g is candidate p,
+ * every other row a_pol[e]'s.  Nothing is computed: words are copied as they are (a NaN keeps its payload) and the action is
+ * NOT clipped — the step that applies it clips (clip_action, env/base.py; the step itself: env/base.py step,
+ * lidar_env/base.py:146-149).  nu, nv >= 1, nu*nv < 2^24, G*n < 2^31.  The reference ships no runtime filter and no way to
+ * start an episode anywhere but at reset.                                                                                     */
+int32_t dgppo_env_team_action_fork(const dgppo_env_cfg* cfg, const float* agent, const float* goal, const float* obst,
+                                   const float* hits, const float* a_pol, const float* carry, int32_t HC, int32_t n_env,
+                                   const float* us, int32_t nu, const float* vs, int32_t nv, float* agent_out, float* goal_out,
+                                   float* obst_out, float* hits_out, float* action_out, float* carry_out, void* stream);
+
+/* The lookahead shield's choice among those candidates, per (env e, agent i) on the agent's own row of its own what-if env:
+ * s[e, i, p] = max over k in [0, K) and c in [0, n_cost) of cost[k*cost_st + ((g*n + i)*n_cost + c)], g = (e*n + i)*P + p — the
+ * worst cost (get_cost, lidar_env/base.py:203-205) the agent meets in the K states after the candidate's step, the others
+ * playing the policy (NaN-propagating max).  cost points at step 1 of the rolled record, cost_st >= G*n*n_cost is its step
+ * stride in floats.  A candidate is admissible iff s <= -margin (never a NaN).  Candidate 0 is kept if admissible (flag 0); else
+ * the admissible candidate nearest to it — du*du + dv*dv in fp32 on clipped actions (clip_action, env/base.py), lowest index on
+ * ties (flag 1); else the smallest s, lowest index on ties, NaN skipped, candidate 0 when every s is NaN (flag 2).  action
+ * [n_env, n, 2] is the chosen candidate clipped to [-1, 1], index / flag [n_env, n] int32, s [n_env, n, P] (may be NULL).
+ * K >= 1, 1 <= n_cost <= 3, margin no NaN.  The reference ships no runtime filter.                                            */
+int32_t dgppo_lookahead_select(const float* cost, int64_t cost_st, int32_t K, int32_t n_env, int32_t n_agents, int32_t n_cost,
+                               const float* a_pol, const float* us, int32_t nu, const float* vs, int32_t nv, float margin,
+                               float* action, int32_t* index, int32_t* flag, float* s, void* stream);
+
 /* GraphTransformer attention in fixed-fan-in form (dgppo/nn/gnn.py:85-117; jraph.segment_softmax/segment_sum):
  * qt [G*n,H*F] = x_i Mcat + cvec (a Dense), logits = qt . x_sender, masked softmax over the S slots of each agent,
  * zcat [G*n,Kp] = [x_i | per head: sum a x_s (F), sum a e (4) | 1 | 0...], attn [G*n,S,H] saved for backward (NULL in

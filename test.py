@@ -24,7 +24,13 @@ training target folds them.  `{stamp}_{name}_rollout.npz` holds the folded value
 line per episode says how much of the grid is doomed (unsafe within the horizon) and, with `--landscape` / `--cost-landscape`
 for the same agent, how much of the doomed set the learned Vh misses and how much of it is still safe now (which the
 instantaneous cost cannot show); the animation shows the doomed set's boundary dotted.  With `--shield` the what-if rollouts
-follow the UNSHIELDED policy: they say what the policy alone would do from each point, not what the filter would make of it."""
+follow the UNSHIELDED policy: they say what the policy alone would do from each point, not what the filter would make of it.
+`--shield --shield-horizon H` (H >= 1) replaces the learned barrier by a lookahead (`collect_lookahead_shielded`; every
+algorithm has it): for the policy's action and every action of the `--shield-grid`-squared grid the environment is forked, the
+candidate played and the policy rolled H steps on, and an action is admissible where the agent's own worst cost over those
+steps is <= -M (`--shield-margin M`).  The lines, `test_log.csv`, the landscapes and the video then describe those episodes, and
+`{stamp}_{name}_shield.npz` holds `policy_action`, `action`, `index`, `flag`, `s` (the worst rolled cost of every candidate),
+`us`, `vs`, `margin`, `horizon` and the three statistics.  `--shield-horizon 0` (the default) is the one-step barrier shield."""
 import argparse
 import datetime
 import os
@@ -63,7 +69,10 @@ def test(args):
     if len(keys) == 0:
         raise SystemExit("no episodes to run (--epi / --offset)")
     shield_log = None
-    if args.shield:
+    if args.shield and args.shield_horizon >= 1:
+        ro, shield_log = algo.collect_lookahead_shielded(keys, env=env, grid=args.shield_grid, margin=args.shield_margin,
+                                                         horizon=args.shield_horizon)
+    elif args.shield:
         ro, shield_log = algo.collect_shielded(keys, env=env, grid=args.shield_grid, margin=args.shield_margin)
     elif args.stochastic:
         ro = algo.collect_stochastic(keys, env=env)
@@ -98,9 +107,14 @@ def test(args):
             extra = {}
             if shield_log is not None:
                 out = videos_dir / f"{stamp}_{name}_shield.npz"
-                per_epi = {k: getattr(shield_log, k)[i] for k in ("policy_action", "action", "index", "flag", "h", "Vh")}
-                np.savez(out, us=shield_log.us, vs=shield_log.vs, margin=shield_log.margin, alpha=shield_log.alpha,
-                         dt=shield_log.dt, **per_epi, **{k: v[i] for k, v in sh.items()})
+                if args.shield_horizon >= 1:
+                    per_epi = {k: getattr(shield_log, k)[i] for k in ("policy_action", "action", "index", "flag", "s")}
+                    np.savez(out, us=shield_log.us, vs=shield_log.vs, margin=shield_log.margin, horizon=shield_log.horizon,
+                             **per_epi, **{k: v[i] for k, v in sh.items()})
+                else:
+                    per_epi = {k: getattr(shield_log, k)[i] for k in ("policy_action", "action", "index", "flag", "h", "Vh")}
+                    np.savez(out, us=shield_log.us, vs=shield_log.vs, margin=shield_log.margin, alpha=shield_log.alpha,
+                             dt=shield_log.dt, **per_epi, **{k: v[i] for k, v in sh.items()})
                 print(f"shield: {out}")
             if args.landscape is not None:
                 land = algo.vh_landscape(ro, i, args.landscape, nx=args.landscape_grid, ny=args.landscape_grid)
@@ -178,12 +192,15 @@ SHIELD_FLAGS = [(("--shield",), "flag", False), (("--shield-grid",), "int", 8), 
 # what Vh is trained to predict, measured (DGPPO.rollout_landscape): the policy rolled K steps forward from every point of the
 # --landscape-grid grid with one agent displaced there, per episode
 ROLLOUT_FLAGS = [(("--rollout-landscape",), "int", None), (("--rollout-horizon",), "int", 32)]
+# with --shield: filter by forked policy rollouts of H steps instead of the learned barrier (collect_lookahead_shielded; every
+# algorithm has it); 0: the one-step barrier shield
+LOOKAHEAD_FLAGS = [(("--shield-horizon",), "int", 0)]
 
 
 def build_parser() -> argparse.ArgumentParser:
     types = {"int": int, "str": str, "float": float}
     ap = argparse.ArgumentParser(description=__doc__)
-    for names, kind, default in FLAGS + COST_FLAGS + ACTION_FLAGS + SHIELD_FLAGS + ROLLOUT_FLAGS:
+    for names, kind, default in FLAGS + COST_FLAGS + ACTION_FLAGS + SHIELD_FLAGS + ROLLOUT_FLAGS + LOOKAHEAD_FLAGS:
         if kind == "flag":
             ap.add_argument(*names, action="store_true", default=False)
         elif kind.startswith("req:"):
@@ -199,6 +216,10 @@ def main(argv=None):
         raise SystemExit("--cpu: this build has no CPU product path (the HIP library is required)")
     if args.shield and args.stochastic:
         raise SystemExit("--shield --stochastic: the shield filters the deterministic policy; drop one of the two flags")
+    if args.shield_horizon < 0:
+        raise SystemExit(f"--shield-horizon must be >= 0 (got {args.shield_horizon})")
+    if args.shield_horizon >= 1 and not args.shield:
+        raise SystemExit("--shield-horizon needs --shield: it sets how far the shield looks ahead")
     return test(args)
 
 
