@@ -189,6 +189,10 @@ def lib() -> C.CDLL:
     l.dgppo_env_team_action_fork.argtypes = [C.POINTER(EnvCfg), p, p, p, p, p, p, i32, i32, p, i32, p, i32, p, p, p, p, p, p, p]
     l.dgppo_lookahead_select.restype = i32
     l.dgppo_lookahead_select.argtypes = [p, i64, i32, i32, i32, i32, p, p, i32, p, i32, f32, p, p, p, p, p]
+    # the action rollout landscape's fork (same file)
+    l.dgppo_env_action_sweep_fork.restype = i32
+    l.dgppo_env_action_sweep_fork.argtypes = [C.POINTER(EnvCfg), p, i64, p, p, p, i64, p, i64, p, i64, i32, p, i32, i32, p, i32,
+                                              p, i32, p, p, p, p, p, p, p]
     _lib = l
     return l
 

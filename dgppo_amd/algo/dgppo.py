@@ -15,8 +15,8 @@ from .. import engine as EN
 from .. import init as INIT
 from .. import nets
 from .. import ops_nn as K
-from ..trainer.data import (ActionLandscape, CostLandscape, Landscape, LookaheadShieldLog, Rollout, RolloutLandscape,
-                            ShieldLog)
+from ..trainer.data import (ActionLandscape, ActionRolloutLandscape, CostLandscape, Landscape, LookaheadShieldLog, Rollout,
+                            RolloutLandscape, ShieldLog)
 from ..utils import checkpoint as CK
 from ..utils.graph import GraphsTuple
 from .base import Algorithm
@@ -373,6 +373,27 @@ class DGPPO(Algorithm):
         actions = np.clip(ro.actions[int(index), :, int(agent)].cpu().numpy()[frames], -1.0, 1.0).astype(np.float32)
         return ActionLandscape(us, vs, cbf.cpu().numpy(), Vh_next.cpu().numpy(), Vh.cpu().numpy(), actions, int(agent),
                                frames.astype(np.int64), float(self.engine.hp.alpha), float(self.engine.cfg.dt))
+
+    def action_rollout_landscape(self, rollout: Rollout, index: int, agent: int, frames=None, nu: int = 32, nv: int = 32,
+                                 us=None, vs=None, horizon: int = 32) -> ActionRolloutLandscape:
+        """What the actions action_landscape sweeps lead to, measured (same grid arguments and defaults): in every frame t of
+        episode `index` of a rollout that one of this algo's collect methods returned, `agent` plays each grid action for ONE
+        step — everyone else their recorded action — and the deterministic policy is rolled on until the costs of the
+        `horizon` states after that step are known.  value / worst fold them as rollout_landscape does and hold every agent's
+        row: the swept agent's own row says which actions doom the agent itself within the horizon (the lookahead shield's
+        criterion), the other rows what its single action does to its neighbours.  It needs the simulator and the policy only:
+        every algorithm has it.  The what-if rollouts run past the episode's end and follow the unshielded policy whatever
+        produced the rollout.  Not in the reference."""
+        ro = getattr(self, "_last_rollouts", {}).get(id(rollout.actions))
+        if ro is None:
+            raise ValueError("action_rollout_landscape() needs a Rollout produced by this algo's collect methods")
+        us = _grid_axis("action_rollout_landscape", "us", us, nu, 1.0, lo=-1.0)
+        vs = _grid_axis("action_rollout_landscape", "vs", vs, nv, 1.0, lo=-1.0)
+        frames = np.arange(ro.T) if frames is None else np.asarray(frames, dtype=np.int64).reshape(-1)
+        value, worst = self.engine.action_rollout_landscape(ro, int(index), int(agent), frames, us, vs, int(horizon))
+        actions = np.clip(ro.actions[int(index), :, int(agent)].cpu().numpy()[frames], -1.0, 1.0).astype(np.float32)
+        return ActionRolloutLandscape(us, vs, value.cpu().numpy(), worst.cpu().numpy(), actions, int(agent),
+                                      frames.astype(np.int64), int(horizon), float(self.engine.hp.gamma))
 
     def update(self, rollout: Rollout, step: int) -> dict:
         ro = self._last_rollouts.pop(id(rollout.actions), None)

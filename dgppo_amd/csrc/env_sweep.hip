@@ -1307,11 +1307,22 @@ extern "C" int32_t dgppo_constraint_return(const float* cost, int64_t cost_st, i
 #define FORKT_TILE 64   // output envs per workgroup
 
 struct ForkField {
-  const uint32_t* src;    // [n_env, len]
+  const uint32_t* src;    // source block b starts at src + b * st
   uint32_t* dst;          // [G, len]
+  long st;                // words between source blocks: len for a dense [n_env, len] source, the frame stride of a record, 0 for
+                          // a field with ONE block (the per-env rows of the action fork below)
   int len;                // words per env; 0: the field is not held
   int vec;                // words per load / store: 4, 2 or 1
 };
+
+// the widest vector a field allows: its row length, the stride between its source blocks and both pointers have to be multiples
+inline ForkField fork_field(const float* s, float* d, long len, long st) {
+  ForkField f;
+  f.src = reinterpret_cast<const uint32_t*>(s); f.dst = reinterpret_cast<uint32_t*>(d); f.len = (int)len; f.st = st;
+  const uintptr_t al = (uintptr_t)s | (uintptr_t)d;
+  f.vec = (len % 4 == 0 && st % 4 == 0 && al % 16 == 0) ? 4 : (len % 2 == 0 && st % 2 == 0 && al % 8 == 0) ? 2 : 1;
+  return f;
+}
 
 struct TeamForkArgs {
   ForkField f[5];         // agent, goal, obst, hits, carry
@@ -1323,18 +1334,33 @@ struct TeamForkArgs {
   int n, nu, P, nP, avec; // avec: 2 where a_pol and action_out are 8-byte aligned
 };
 
-// G < 2^31 (the host checks G * n): env numbers are divided as 32-bit words
+// The one copy loop of the forks: output env g takes source block (g / per), looked up in ids where given (the frame numbers of
+// the action fork).  G < 2^31 (the host checks G * n): env numbers are divided as 32-bit words
 template <typename V>
-__device__ inline void fork_copy(const ForkField& fd, uint32_t g0, int envs, uint32_t nP, int tid) {
+__device__ inline void fork_copy(const ForkField& fd, uint32_t g0, int envs, uint32_t per, const int32_t* ids, int tid) {
   constexpr int W = sizeof(V) / 4;
   const int lv = fd.len / W;                                    // vectors per env
+  const size_t sv = (size_t)(fd.st / W);                        // vectors between source blocks
   const V* src = reinterpret_cast<const V*>(fd.src);
   V* dst = reinterpret_cast<V*>(fd.dst) + (size_t)g0 * lv;
   const int total = envs * lv;
   for (int o = tid; o < total; o += FORKT_NT) {
     const int gl = o / lv, j = o - gl * lv;
-    const uint32_t e = (g0 + (uint32_t)gl) / nP;
-    dst[o] = src[(size_t)e * lv + j];
+    uint32_t b = (g0 + (uint32_t)gl) / per;
+    if (ids != nullptr) b = (uint32_t)ids[b];
+    dst[o] = src[(size_t)b * sv + j];
+  }
+}
+
+template <int NF>
+__device__ inline void fork_fields(const ForkField (&f)[NF], uint32_t g0, int envs, uint32_t per, const int32_t* ids, int tid) {
+#pragma unroll
+  for (int k = 0; k < NF; ++k) {
+    const ForkField& fd = f[k];
+    if (fd.len == 0) continue;
+    if (fd.vec == 4) fork_copy<uint4>(fd, g0, envs, per, ids, tid);
+    else if (fd.vec == 2) fork_copy<uint2>(fd, g0, envs, per, ids, tid);
+    else fork_copy<uint32_t>(fd, g0, envs, per, ids, tid);
   }
 }
 
@@ -1342,14 +1368,7 @@ __global__ void __launch_bounds__(FORKT_NT) env_team_action_fork_kernel(TeamFork
   const int tid = threadIdx.x;
   const uint32_t g0 = blockIdx.x * FORKT_TILE;
   const int envs = (int)min((long)FORKT_TILE, a.G - (long)g0);
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const ForkField& fd = a.f[k];
-    if (fd.len == 0) continue;
-    if (fd.vec == 4) fork_copy<uint4>(fd, g0, envs, (uint32_t)a.nP, tid);
-    else if (fd.vec == 2) fork_copy<uint2>(fd, g0, envs, (uint32_t)a.nP, tid);
-    else fork_copy<uint32_t>(fd, g0, envs, (uint32_t)a.nP, tid);
-  }
+  fork_fields(a.f, g0, envs, (uint32_t)a.nP, nullptr, tid);
   // the joint action: a_pol[e]'s words, row i replaced by candidate p (p = 0 is a_pol[e, i] itself)
   const int n = a.n, rows = envs * n;
   for (int o = tid; o < rows; o += FORKT_NT) {
@@ -1410,13 +1429,7 @@ extern "C" int32_t dgppo_env_team_action_fork(const dgppo_env_cfg* cfg, const fl
   if (carry != nullptr) DGPPO_REQUIRE(carry_out, "%s: carry_out is NULL", fn);
   const int OS = lidar ? DGPPO_RECT_STRIDE : SD;
   TeamForkArgs a;
-  auto field = [](const float* s, float* d, long len) {
-    ForkField f;
-    f.src = reinterpret_cast<const uint32_t*>(s); f.dst = reinterpret_cast<uint32_t*>(d); f.len = (int)len;
-    const uintptr_t al = (uintptr_t)s | (uintptr_t)d;
-    f.vec = (len % 4 == 0 && al % 16 == 0) ? 4 : (len % 2 == 0 && al % 8 == 0) ? 2 : 1;
-    return f;
-  };
+  auto field = [](const float* s, float* d, long len) { return fork_field(s, d, len, len); };   // dense [n_env, len] sources
   a.f[0] = field(agent, agent_out, (long)n * SD);
   a.f[1] = field(goal, goal_out, (long)ng * SD);
   a.f[2] = field(obst, obst_out, no > 0 ? (long)no * OS : 0);
@@ -1429,6 +1442,122 @@ extern "C" int32_t dgppo_env_team_action_fork(const dgppo_env_cfg* cfg, const fl
   a.G = (long)n_env * nP; a.n = n; a.nu = nu; a.P = (int)P; a.nP = (int)nP;
   const dim3 grid((unsigned)((a.G + FORKT_TILE - 1) / FORKT_TILE));
   hipLaunchKernelGGL(env_team_action_fork_kernel, grid, dim3(FORKT_NT), 0, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
+
+// ---- action rollout landscape: the what-if environments of a RECORDED frame with one agent's action swept ------------------------
+// The measured twin of the CBF action landscape above: env g = (f * nv + iv) * nu + iu (dgppo_graph_feats_action_sweep's
+// numbering) is a copy of frame fid = frame_ids[f] of ONE environment of a record in which agent `agent_id` is about to play
+// (us[iu], vs[iv]) and everyone else their recorded action of that step; the plain step kernels then apply the joint action and the
+// deterministic policy rolls the copy forward (Engine.action_rollout_landscape).  No position changes before the step, so nothing
+// is cast: the hits are the recorded ones.  The carry rows are the ones the caller points at — the carries AFTER each frame's
+// policy forward, which do not depend on the action taken.
+//
+// Organisation: the team fork's, with the same device code (fork_fields): a workgroup owns FORKT_TILE consecutive output envs and
+// walks each field with unit-stride vector stores.  The source block of an output env is a frame of a strided record (agent, hits,
+// carry: block frame_ids[g / (nv * nu)] at the field's frame stride, which the vector width has to divide as well) or the single
+// block of a per-env field (goal, obst: stride 0).  Words move as integers; the action is NOT clipped: the step clips.
+struct ActionForkArgs {
+  ForkField f[5];         // agent, goal, obst, hits, carry
+  const uint32_t* action; long action_st;   // [n, 2] rows of frame t at action + t * action_st
+  const int32_t* frame_ids;
+  const uint32_t* us;
+  const uint32_t* vs;
+  uint32_t* action_out;   // [G, n, 2]
+  long G;
+  int n, nu, nuv, agent_id, avec;   // avec: 2 where action, its frame stride and action_out are 8-byte aligned
+};
+
+__global__ void __launch_bounds__(FORKT_NT) env_action_sweep_fork_kernel(ActionForkArgs a) {
+  const int tid = threadIdx.x;
+  const uint32_t g0 = blockIdx.x * FORKT_TILE;
+  const int envs = (int)min((long)FORKT_TILE, a.G - (long)g0);
+  fork_fields(a.f, g0, envs, (uint32_t)a.nuv, a.frame_ids, tid);
+  // the joint action: the recorded rows of frame fid, row agent_id replaced by the grid action
+  const int n = a.n, rows = envs * n;
+  for (int o = tid; o < rows; o += FORKT_NT) {
+    const int gl = o / n, r = o - gl * n;
+    const uint32_t g = g0 + (uint32_t)gl, f = g / (uint32_t)a.nuv;
+    uint2 w;
+    if (r == a.agent_id) {
+      const int q = (int)(g - f * (uint32_t)a.nuv), iv = q / a.nu, iu = q - iv * a.nu;
+      w.x = a.us[iu]; w.y = a.vs[iv];
+    } else {
+      const uint32_t fid = a.frame_ids ? (uint32_t)a.frame_ids[f] : f;
+      const uint32_t* s = a.action + (size_t)fid * a.action_st + (size_t)r * 2;
+      if (a.avec == 2) w = *reinterpret_cast<const uint2*>(s);
+      else { w.x = s[0]; w.y = s[1]; }
+    }
+    const size_t q = (size_t)g0 * n + o;
+    if (a.avec == 2) reinterpret_cast<uint2*>(a.action_out)[q] = w;
+    else { a.action_out[q * 2] = w.x; a.action_out[q * 2 + 1] = w.y; }
+  }
+}
+
+extern "C" int32_t dgppo_env_action_sweep_fork(const dgppo_env_cfg* cfg, const float* agent, int64_t agent_st, const float* goal,
+                                               const float* obst, const float* hits, int64_t hits_st, const float* action,
+                                               int64_t action_st, const float* carry, int64_t carry_st, int32_t HC,
+                                               const int32_t* frame_ids, int32_t n_frames, int32_t agent_id, const float* us,
+                                               int32_t nu, const float* vs, int32_t nv, float* agent_out, float* goal_out,
+                                               float* obst_out, float* hits_out, float* action_out, float* carry_out,
+                                               void* stream) {
+  const char* fn = "dgppo_env_action_sweep_fork";
+  int32_t rc = dgppo_validate_cfg(cfg);
+  if (rc) {   // the configuration's own refusal, under this entry point's name
+    const std::string why = dgppo_last_error();
+    dgppo_set_error("%s: %s", fn, why.c_str());
+    return rc;
+  }
+  DGPPO_REFUSE_VMAS(cfg, fn, "dgppo_vmas_step on a tiled record (there is no VMAS fork)");
+  DGPPO_REQUIRE(nu >= 1 && nv >= 1, "%s: nu and nv must be >= 1 (got %d, %d)", fn, nu, nv);
+  DGPPO_REQUIRE((long)nu * nv < (1L << 24), "%s: grid too large (nu * nv < 2^24)", fn);
+  DGPPO_REQUIRE(n_frames >= 1, "%s: n_frames must be >= 1 (got %d)", fn, n_frames);
+  const int n = cfg->n_agents, ng = cfg->n_goals, SD = cfg->state_dim, no = cfg->n_obs, k = cfg->top_k;
+  DGPPO_REQUIRE(agent_id >= 0 && agent_id < n, "%s: agent_id %d outside [0, %d)", fn, agent_id, n);
+  const long nuv = (long)nu * nv;
+  DGPPO_REQUIRE((double)n_frames * (double)nuv * (double)n < 2147483648.0, "%s: too many envs (G * n < 2^31)", fn);
+  const bool lidar = cfg_is_lidar(*cfg), cast = lidar && no > 0;
+  if (carry != nullptr) {
+    DGPPO_REQUIRE(HC >= 1 && (long)n * HC < (1L << 24), "%s: HC %d out of range", fn, HC);
+    DGPPO_REQUIRE(carry_st >= (long)n * HC, "%s: the frame stride of carry (%ld) is shorter than its rows (%ld floats)", fn,
+                  (long)carry_st, (long)n * HC);
+  }
+  DGPPO_REQUIRE(agent_st >= (long)n * SD, "%s: the frame stride of agent (%ld) is shorter than its rows (%ld floats)", fn,
+                (long)agent_st, (long)n * SD);
+  DGPPO_REQUIRE(action_st >= (long)n * 2, "%s: the frame stride of action (%ld) is shorter than its rows (%ld floats)", fn,
+                (long)action_st, (long)n * 2);
+  if (cast)
+    DGPPO_REQUIRE(hits_st >= (long)n * k * 2, "%s: the frame stride of hits (%ld) is shorter than its rows (%ld floats)", fn,
+                  (long)hits_st, (long)n * k * 2);
+  DGPPO_REQUIRE(agent && goal && action && us && vs && agent_out && goal_out && action_out, "%s: NULL operand", fn);
+  if (no > 0) {
+    DGPPO_REQUIRE(obst, "%s: obst is NULL", fn);
+    DGPPO_REQUIRE(obst_out, "%s: obst_out is NULL", fn);
+  }
+  if (cast) {
+    DGPPO_REQUIRE(hits, "%s: hits is NULL", fn);
+    DGPPO_REQUIRE(hits_out, "%s: hits_out is NULL", fn);
+  } else {
+    DGPPO_REQUIRE(!hits && !hits_out, "%s: hits / hits_out are for the kinds that cast rays (LiDAR with obstacles)", fn);
+  }
+  if (carry != nullptr) DGPPO_REQUIRE(carry_out, "%s: carry_out is NULL", fn);
+  const int OS = lidar ? DGPPO_RECT_STRIDE : SD;
+  ActionForkArgs a;
+  a.f[0] = fork_field(agent, agent_out, (long)n * SD, agent_st);
+  a.f[1] = fork_field(goal, goal_out, (long)ng * SD, 0);
+  a.f[2] = fork_field(obst, obst_out, no > 0 ? (long)no * OS : 0, 0);
+  a.f[3] = fork_field(hits, hits_out, cast ? (long)n * k * 2 : 0, hits_st);
+  a.f[4] = fork_field(carry, carry_out, carry != nullptr ? (long)n * HC : 0, carry_st);
+  a.action = reinterpret_cast<const uint32_t*>(action); a.action_st = action_st;
+  a.frame_ids = frame_ids;
+  a.us = reinterpret_cast<const uint32_t*>(us); a.vs = reinterpret_cast<const uint32_t*>(vs);
+  a.action_out = reinterpret_cast<uint32_t*>(action_out);
+  a.avec = (((uintptr_t)action | (uintptr_t)action_out) % 8 == 0 && action_st % 2 == 0) ? 2 : 1;
+  a.G = (long)n_frames * nuv; a.n = n; a.nu = nu; a.nuv = (int)nuv; a.agent_id = agent_id;
+  const dim3 grid((unsigned)((a.G + FORKT_TILE - 1) / FORKT_TILE));
+  hipLaunchKernelGGL(env_action_sweep_fork_kernel, grid, dim3(FORKT_NT), 0, (hipStream_t)stream, a);
   DGPPO_LAUNCH_CHECK();
   return 0;
 }

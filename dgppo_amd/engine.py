@@ -719,6 +719,96 @@ class Engine:
         cbf = (Vh_next - Vh_b) / float(cfg.dt) + float(self.hp.alpha) * Vh_b
         return cbf, Vh_next, Vh.clone()
 
+    def action_rollout_landscape(self, ro: RolloutData, env_index: int, agent_id: int, frame_ids, us, vs, horizon: int,
+                                 events: Optional[list] = None, records: Optional[list] = None):
+        """-> (value, worst), each [F, nv, nu, n, n_cost]: what the actions action_landscape judges by the learned barrier lead
+        to, measured.  For every frame t = frame_ids[f] (a subset of [0, T)) of env `env_index` and every grid action (us[iu],
+        vs[iv]) the env of frame t is forked (dgppo_env_action_sweep_fork) with agent `agent_id` playing the grid action in the
+        coming step and everyone else their RECORDED action of step t (action_landscape's convention; the step clips, the fork
+        does not), the plain env step applies that joint action, and the deterministic policy is rolled on (_rollout_steps from
+        slot 1) until the costs of the `horizon` states after the forced step are known.  It starts from the carry the policy
+        left after its forward on frame t — ro._rnn_em[e, t + 1], which does not depend on the action taken and is valid in
+        stochastic and deterministic records alike.  value / worst fold those costs as rollout_landscape does
+        (dgppo_constraint_return, hp.gamma) and hold EVERY agent's row: the swept agent's own row is what the lookahead shield
+        calls s, the others say what its single action does to its neighbours.  The rollouts run past the episode's end (no
+        done flag) and follow the unshielded policy whatever produced the record.  It needs the simulator and the policy only:
+        every algo, --no-rnn engines and stacked cells have it.  Walked as action_landscape walks its grid — whole frames, else
+        rows of one frame, else pieces of one row — in sub-grids of Gb envs with Gb * (horizon + 2) <= prepass_graphs, never
+        fewer than one env; the last step of a block record exists only to evaluate the cost of the last state.
+        events: a list that receives one (start, fork and forced step done, policy steps done, fold done) tuple of device
+        events per sub-grid (tools/bench_action_rollout.py).  records: a list that receives (f0, f1, v0, v1, u0, u1, block
+        record) per sub-grid, time-major as rolled (the tests re-derive every step of those)."""
+        cfg, T = self.cfg, self.T
+        if cfg.is_vmas:
+            raise ValueError("action_rollout_landscape: VMASReverseTransport is not supported")
+        n, nh, HC = cfg.n_agents, self.n_cost, self.HC
+        ro.finalize()
+        if not 0 <= int(env_index) < ro.B:
+            raise ValueError(f"action_rollout_landscape: env_index {env_index} outside [0, {ro.B})")
+        if not 0 <= int(agent_id) < n:
+            raise ValueError(f"action_rollout_landscape: agent_id {agent_id} outside [0, {n})")
+        frames = np.asarray(frame_ids, dtype=np.int64).reshape(-1)
+        if frames.size == 0 or frames.min() < 0 or frames.max() >= T:
+            raise ValueError(f"action_rollout_landscape: frame_ids must be a non-empty subset of [0, {T})")
+        horizon = int(horizon)
+        if horizon < 1:
+            raise ValueError(f"action_rollout_landscape: horizon must be >= 1 (got {horizon})")
+        us, vs = K.sweep_axis(us, "us", self.device), K.sweep_axis(vs, "vs", self.device)
+        nu, nv, F = int(us.numel()), int(vs.numel()), int(frames.size)
+        e = int(env_index)
+        step = {k: v[e] for k, v in ro.step.items()}
+        env = {k: v[e] for k, v in ro.env.items()}
+        actions = ro.actions[e]                                                  # [T, n, 2]
+        carry = ro._rnn_em[e, 1:] if self.hp.use_rnn else None                   # [T + 1, n, HC]: slot t = the carry after frame t
+        if carry is not None and int(frames.max()) == T - 1:
+            # values_prepass parks the final carry of a stochastic record in slot T (nothing else reads it there): the carry
+            # after frame T - 1 is put back from the time-major record, and values_prepass writes its own again before it reads
+            ro._rnn_em[e, T].copy_(ro.rnn_tm[T, e])
+        value = torch.empty(F, nv, nu, n, nh, device=self.device)
+        worst = torch.empty(F, nv, nu, n, nh, device=self.device)
+        ids_dev = torch.from_numpy(frames.astype(np.int32)).to(self.device)      # once per call; the sub-grids pass slices
+        cap = max(1, self.prepass_graphs // (horizon + 2))
+        fb = max(1, cap // (nv * nu))
+        vb = nv if cap >= nv * nu else max(1, cap // nu)
+        ub = nu if cap >= nu else cap
+        recs: Dict[int, RolloutData] = {}            # one record per sub-grid size, unless the caller keeps the records
+        for f0 in range(0, F, fb):
+            f1 = min(F, f0 + fb)
+            fr = frames[f0:f1]
+            for v0 in range(0, nv, vb):
+                v1 = min(nv, v0 + vb)
+                for u0 in range(0, nu, ub):
+                    u1 = min(nu, u0 + ub)
+                    Gb = (f1 - f0) * (v1 - v0) * (u1 - u0)
+                    rec = recs.get(Gb) if records is None else None
+                    if rec is None:
+                        rec = recs[Gb] = RolloutData(cfg, Gb, horizon + 1, self.device, False, HC)
+                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if events is not None else None
+                    if ev:
+                        ev[0].record()
+                    if carry is None:
+                        rec.rnn_tm[1].zero_()
+                    OE.action_sweep_fork(cfg, step, env, actions, ids_dev[f0:f1], f1 - f0, int(agent_id), us[u0:u1], vs[v0:v1],
+                                         rec.states_tm[0], rec.action_tm[0], carry, n * HC,
+                                         rec.rnn_tm[1].view(Gb * n, HC) if carry is not None else None, frame_max=int(fr.max()))
+                    OE.step(cfg, rec.states_tm[0], rec.action_tm[0], rec.states_tm[1], rec.reward_tm[0], rec.cost_tm[0])
+                    if ev:
+                        ev[1].record()
+                    self._rollout_steps(rec, None, Gb, False, start=1)
+                    if ev:
+                        ev[2].record()
+                    val = self.arena.get("arl.value", Gb, n, nh)
+                    wor = self.arena.get("arl.worst", Gb, n, nh)
+                    OA.constraint_return(rec.cost_tm[1:horizon + 1], self.hp.gamma, val, wor)
+                    value[f0:f1, v0:v1, u0:u1].copy_(val.view(f1 - f0, v1 - v0, u1 - u0, n, nh))
+                    worst[f0:f1, v0:v1, u0:u1].copy_(wor.view(f1 - f0, v1 - v0, u1 - u0, n, nh))
+                    if ev:
+                        ev[3].record()
+                        events.append(tuple(ev))
+                    if records is not None:
+                        records.append((f0, f1, v0, v1, u0, u1, rec))
+        return value, worst
+
     # ------------------------------------------------------------------------------------------------------------------
     # barrier shield: the deterministic rollout with every agent's action filtered through the learned barrier
     # ------------------------------------------------------------------------------------------------------------------

@@ -202,7 +202,8 @@ class MultiAgentEnv(ABC):
         return self._squeeze(self.graph_batch(st))
 
     def render_video(self, rollout, video_path, Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
-                     landscape=None, cost_landscape=None, action_landscape=None, rollout_landscape=None, **kwargs):
+                     landscape=None, cost_landscape=None, action_landscape=None, rollout_landscape=None,
+                     action_rollout_landscape=None, **kwargs):
         """One episode as an animation (dgppo/env/lidar_env/base.py:209-221, dgppo/env/mpe/base.py render_video).  `rollout`
         holds one episode ([T, ...]) or a batch ([B, T, ...], pass index=b).  Returns the path written (`.gif` when no
         ffmpeg binary is available for `.mp4`).  landscape: an optional trainer.data.Landscape of this episode
@@ -210,13 +211,16 @@ class MultiAgentEnv(ABC):
         (DGPPO.cost_landscape): the same contours of the true cost when alone, its dashed zero contour next to `landscape`.
         action_landscape: an optional trainer.data.ActionLandscape (DGPPO.action_landscape), drawn in an inset over the action
         square with the recorded action marked; it combines with the other two.  rollout_landscape: an optional
-        trainer.data.RolloutLandscape (DGPPO.rollout_landscape): the dotted zero contour of its h() over whatever else is drawn."""
+        trainer.data.RolloutLandscape (DGPPO.rollout_landscape): the dotted zero contour of its h() over whatever else is drawn.
+        action_rollout_landscape: an optional trainer.data.ActionRolloutLandscape (action_rollout_landscape): the dashed zero
+        contour of its h() inside the action landscape's inset (same agent, us and vs), or an inset of its own when alone."""
         from . import plot
         p = self._params
         common = dict(rollout=rollout, video_path=video_path, side_length=self.area_size, dim=2, n_agent=self.num_agents,
                       r=p["car_radius"], cost_components=self.cost_components, Ta_is_unsafe=Ta_is_unsafe, viz_opts=viz_opts,
                       n_goal=self.num_goals, dpi=dpi, landscape=landscape, cost_landscape=cost_landscape,
-                      action_landscape=action_landscape, rollout_landscape=rollout_landscape, **kwargs)
+                      action_landscape=action_landscape, rollout_landscape=rollout_landscape,
+                      action_rollout_landscape=action_rollout_landscape, **kwargs)
         if self.cfg.is_lidar:
             return plot.render_lidar(n_rays=self.cfg.top_k if self.cfg.n_obs > 0 else 0, **common)
         return plot.render_mpe(n_obs=self.cfg.n_obs, obs_r=p.get("obs_radius", 0.05), **common)

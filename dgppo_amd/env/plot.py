@@ -94,7 +94,17 @@ class _Scene:
 
     def __init__(self, ep: Episode, side_length: float, n_agent: int, n_goal: int, r: float, obs_r: float,
                  cost_components: Sequence[str], Ta_is_unsafe, dpi: int, landscape=None, cost_landscape=None,
-                 action_landscape=None, rollout_landscape=None):
+                 action_landscape=None, rollout_landscape=None, action_rollout_landscape=None):
+        if action_rollout_landscape is not None:
+            R = action_rollout_landscape
+            for name, other in (("landscape", landscape), ("cost_landscape", cost_landscape),
+                                ("action_landscape", action_landscape), ("rollout_landscape", rollout_landscape)):
+                if other is not None and int(other.agent) != int(R.agent):
+                    raise ValueError(f"action_rollout_landscape is swept for agent {int(R.agent)}, {name} for agent "
+                                     f"{int(other.agent)}")
+            if action_landscape is not None and not (np.array_equal(np.asarray(action_landscape.us), np.asarray(R.us))
+                                                     and np.array_equal(np.asarray(action_landscape.vs), np.asarray(R.vs))):
+                raise ValueError("action_landscape and action_rollout_landscape are swept over different grids")
         if rollout_landscape is not None:
             for name, other in (("landscape", landscape), ("cost_landscape", cost_landscape),
                                 ("action_landscape", action_landscape)):
@@ -202,17 +212,40 @@ class _Scene:
                       f"none are drawn)")
             self._act_uv = np.meshgrid(us, vs)
             self._act_norm, self._act_levels = _centred_scale(self._act_h)
-            self.act_ax = ax.inset_axes([0.76, 0.02, 0.22, 0.22], zorder=8)
-            self.act_ax.set_xlim(min(-1.0, float(us.min())), max(1.0, float(us.max())))
-            self.act_ax.set_ylim(min(-1.0, float(vs.min())), max(1.0, float(vs.max())))
-            self.act_ax.set_aspect("equal")
-            self.act_ax.set_xticks([-1, 0, 1])
-            self.act_ax.set_yticks([-1, 0, 1])
-            self.act_ax.tick_params(labelsize=8)
-            self.act_ax.set_title(f"cbf_deriv of {int(A.agent)} over its action", fontsize=9)
-            self.act_marker, = self.act_ax.plot([], [], marker="x", color="k", markersize=8, markeredgewidth=2, linestyle="none",
-                                                zorder=5)
-            self.act_ax.set_visible(False)
+            self._action_inset(us, vs, f"cbf_deriv of {int(A.agent)} over its action")
+        # action rollout landscape (trainer.data.ActionRolloutLandscape): what those actions lead to, measured.  Next to an action
+        # landscape it only adds the zero contour of its h(), dashed, to that inset: the boundary of the actions that doom the
+        # agent within the horizon.  Alone it gets the inset to itself: filled contours of h(), the zero contour in black, the
+        # recorded action marked
+        self.action_rollout_landscape = action_rollout_landscape
+        self.act_ro_zero_line = None
+        if action_rollout_landscape is not None:
+            R = action_rollout_landscape
+            self._aro_h = np.asarray(R.h(), dtype=np.float64)
+            self._aro_row = {int(t): k for k, t in enumerate(np.asarray(R.frames).reshape(-1))}
+            us, vs = np.asarray(R.us, dtype=np.float64), np.asarray(R.vs, dtype=np.float64)
+            self._aro_uv = np.meshgrid(us, vs)
+            if self._aro_h.shape[1] < 2 or self._aro_h.shape[2] < 2:
+                print(f"(action rollout grid {self._aro_h.shape[2]} x {self._aro_h.shape[1]}: contours need at least 2 lines each "
+                      f"way, none are drawn)")
+            if action_landscape is None:
+                self._aro_taken = np.asarray(R.actions, dtype=np.float64).reshape(-1, 2)
+                self._aro_norm, self._aro_levels = _centred_scale(self._aro_h)
+                self._action_inset(us, vs, f"worst cost of {int(R.agent)} within {int(R.horizon)} steps over its action")
+
+    def _action_inset(self, us, vs, title: str):
+        """the inset over the action square, with the marker of the recorded action; hidden until a frame is drawn in it"""
+        self.act_ax = self.ax.inset_axes([0.76, 0.02, 0.22, 0.22], zorder=8)
+        self.act_ax.set_xlim(min(-1.0, float(us.min())), max(1.0, float(us.max())))
+        self.act_ax.set_ylim(min(-1.0, float(vs.min())), max(1.0, float(vs.max())))
+        self.act_ax.set_aspect("equal")
+        self.act_ax.set_xticks([-1, 0, 1])
+        self.act_ax.set_yticks([-1, 0, 1])
+        self.act_ax.tick_params(labelsize=8)
+        self.act_ax.set_title(title, fontsize=9)
+        self.act_marker, = self.act_ax.plot([], [], marker="x", color="k", markersize=8, markeredgewidth=2, linestyle="none",
+                                            zorder=5)
+        self.act_ax.set_visible(False)
 
     def artists(self):
         extra = [a for a in (self.contours, self.zero_line, self.cost_zero_line, self.rollout_zero_line,
@@ -274,6 +307,32 @@ class _Scene:
                 self.act_zero_line = self.act_ax.contour(U, V, z, levels=[0.0], colors="k", linewidths=1.5)
         self.act_marker.set_data([self._act_taken[k, 0]], [self._act_taken[k, 1]])
 
+    def _draw_action_rollout_landscape(self, t: int):
+        """frame t of the action rollout landscape: the dashed zero contour in the action landscape's inset, or — alone — the
+        inset itself, rebuilt like the contours above; a frame it does not hold adds nothing (alone: shows no inset)"""
+        alone = self.action_landscape is None
+        for a in (self.act_ro_zero_line, *((self.act_contours,) if alone else ())):
+            if a is not None:
+                a.remove()
+        self.act_ro_zero_line = None
+        k = self._aro_row.get(int(t))
+        if alone:
+            self.act_contours = None
+            self.act_ax.set_visible(k is not None)
+        if k is None:
+            return
+        U, V = self._aro_uv
+        z = self._aro_h[k]
+        if _drawable(z):
+            if alone:
+                self.act_contours = self.act_ax.contourf(U, V, z, levels=self._aro_levels, cmap="RdBu_r", norm=self._aro_norm,
+                                                         extend="both")
+            if z.min() < 0.0 <= z.max():             # h >= 0: the action dooms the agent within the horizon
+                self.act_ro_zero_line = self.act_ax.contour(U, V, z, levels=[0.0], colors="k", linewidths=1.5,
+                                                            linestyles="solid" if alone else "dashed")
+        if alone:
+            self.act_marker.set_data([self._aro_taken[k, 0]], [self._aro_taken[k, 1]])
+
     def draw(self, t: int):
         ep, n = self.ep, self.n_agent
         if self.landscape is not None or self.cost_landscape is not None:
@@ -282,6 +341,8 @@ class _Scene:
             self._draw_rollout_landscape(t)
         if self.action_landscape is not None:
             self._draw_action_landscape(t)
+        if self.action_rollout_landscape is not None:
+            self._draw_action_rollout_landscape(t)
         pos = ep.states[t, :, :2]
         for i, c in enumerate(self.agent_circles):
             c.set_center(tuple(pos[i]))
@@ -324,7 +385,7 @@ def _write(scene: _Scene, n_frames: int, video_path: pathlib.Path, fps: int = 33
 
 def _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_components, Ta_is_unsafe, viz_opts, dpi, n_goal,
             index=None, max_frames=None, landscape=None, cost_landscape=None, action_landscape=None, rollout_landscape=None,
-            **kwargs) -> pathlib.Path:
+            action_rollout_landscape=None, **kwargs) -> pathlib.Path:
     if dim != 2:
         raise NotImplementedError("only the planar environments of SURVEY §8 are rendered (dim == 2)")
     if viz_opts:
@@ -332,7 +393,7 @@ def _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_compo
     ep = episode_from_rollout(rollout, index)
     n_goal = n_agent if n_goal is None else n_goal
     scene = _Scene(ep, float(side_length), n_agent, n_goal, r, obs_r, cost_components, Ta_is_unsafe, dpi, landscape,
-                   cost_landscape, action_landscape, rollout_landscape)
+                   cost_landscape, action_landscape, rollout_landscape, action_rollout_landscape)
     T = ep.states.shape[0] if max_frames is None else min(ep.states.shape[0], max_frames)
     return _write(scene, T, video_path)
 
@@ -340,7 +401,7 @@ def _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_compo
 def render_lidar(rollout, video_path, side_length: float, dim: int, n_agent: int, n_rays: int, r: float,
                  cost_components: Tuple[str, ...], Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
                  n_goal: Optional[int] = None, landscape=None, cost_landscape=None, action_landscape=None,
-                 rollout_landscape=None, **kwargs) -> pathlib.Path:
+                 rollout_landscape=None, action_rollout_landscape=None, **kwargs) -> pathlib.Path:
     """dgppo/env/plot.py:468 (LiDAR family: rectangle obstacles, `n_rays` hit nodes per agent).  landscape: a
     trainer.data.Landscape of this episode, drawn as the reference draws viz_opts["cbf"] (plot.py:348-372,437-447).
     cost_landscape: a trainer.data.CostLandscape, drawn the same way when alone ("Cost for k"), as a dashed zero contour over
@@ -348,18 +409,20 @@ def render_lidar(rollout, video_path, side_length: float, dim: int, n_agent: int
     square (filled contours of the swept agent's cbf_deriv, black zero contour, the recorded action marked); it combines with
     the other two, for the same agent.  rollout_landscape: a trainer.data.RolloutLandscape: the zero contour of its h() — the
     boundary of the set from which the policy becomes unsafe within the horizon — dotted, over whatever else is drawn, for the
-    same agent and grid."""
+    same agent and grid.  action_rollout_landscape: a trainer.data.ActionRolloutLandscape: next to an action_landscape of the same
+    agent and the same us / vs, the zero contour of its h() — the boundary of the actions that doom the agent within the horizon
+    — dashed inside that inset; alone, an inset of its own with h() as filled contours and the action taken marked."""
     return _render(rollout, video_path, side_length, dim, n_agent, r, 0.0, cost_components, Ta_is_unsafe, viz_opts, dpi,
                    n_goal, landscape=landscape, cost_landscape=cost_landscape, action_landscape=action_landscape,
-                   rollout_landscape=rollout_landscape, **kwargs)
+                   rollout_landscape=rollout_landscape, action_rollout_landscape=action_rollout_landscape, **kwargs)
 
 
 def render_mpe(rollout, video_path, side_length: float, dim: int, n_agent: int, n_obs: int, r: float, obs_r: float,
                cost_components: Tuple[str, ...], Ta_is_unsafe=None, viz_opts: Optional[dict] = None, dpi: int = 100,
                n_goal: Optional[int] = None, landscape=None, cost_landscape=None, action_landscape=None,
-               rollout_landscape=None, **kwargs) -> pathlib.Path:
+               rollout_landscape=None, action_rollout_landscape=None, **kwargs) -> pathlib.Path:
     """dgppo/env/plot.py:206 (MPE family: disc obstacles of radius obs_r).  landscape / cost_landscape / action_landscape /
-    rollout_landscape: as in render_lidar."""
+    rollout_landscape / action_rollout_landscape: as in render_lidar."""
     return _render(rollout, video_path, side_length, dim, n_agent, r, obs_r, cost_components, Ta_is_unsafe, viz_opts, dpi,
                    n_goal, landscape=landscape, cost_landscape=cost_landscape, action_landscape=action_landscape,
-                   rollout_landscape=rollout_landscape, **kwargs)
+                   rollout_landscape=rollout_landscape, action_rollout_landscape=action_rollout_landscape, **kwargs)

@@ -423,6 +423,88 @@ def team_action_fork(cfg: N.EnvCfg, st: State, a_pol, us, vs, out: State, action
     N.check(rc, "dgppo_env_team_action_fork")
 
 
+def action_sweep_fork(cfg: N.EnvCfg, step: Dict[str, torch.Tensor], env: Dict[str, torch.Tensor], actions, frame_ids,
+                      n_frames: int, agent_id: int, us, vs, out: State, action_out, carry=None, carry_st: int = 0, carry_out=None,
+                      frame_max=None):
+    """dgppo_env_action_sweep_fork: the G = n_frames * nv * nu what-if envs of an action rollout landscape into `out`
+    (State.empty(cfg, G, device)) — env (f * nv + iv) * nu + iu is a copy of frame frame_ids[f] of ONE env, and action_out
+    [G, n, 2] its joint action: the recorded rows of that frame with row `agent_id` replaced by (us[iu], vs[iv]) (unclipped, the
+    step clips).  `step` holds that env's per-step fields [T + 1, ...], `env` its per-env rows (sweep_fork's operands), `actions`
+    its recorded actions [T, n, 2]; us / vs are ops_nn.sweep_axis tensors; frame_ids as in ops_nn.graph_feats_sweep.  carry: a
+    base tensor whose [n, HC] rows of frame t start at t * carry_st floats — the carries AFTER each frame's policy forward —
+    copied into carry_out [G * n, HC] for every grid action of the frame; None: no carry.  Nothing is cast: the hits are the
+    recorded ones.  Every refusal is raised before anything is launched."""
+    from . import ops_nn as K                     # the grid and record checks the sweep bindings share
+    fn = "action_sweep_fork"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no fork entry point")
+    n, sd, k = cfg.n_agents, cfg.state_dim, cfg.top_k
+    agent, hits, obst, goal = step["agent"], step.get("hits"), env.get("obst"), env["goal"]
+    cast = cfg.is_lidar and cfg.n_obs > 0
+    o_step, o_env = out.step, out.env
+    # what is wrong with the call itself comes first, then shapes, then frame strides; only then where the operands live
+    if not 0 <= int(agent_id) < n:
+        raise ValueError(f"{fn}: agent_id {agent_id} outside [0, {n})")
+    if int(n_frames) < 1:
+        raise ValueError(f"{fn}: n_frames must be >= 1 (got {n_frames})")
+    if not cast and (hits is not None or o_step.get("hits") is not None):
+        raise ValueError(f"{fn}: hits are for the kinds that cast rays (LiDAR with obstacles)")
+    if cast and hits is None:
+        raise ValueError(f"{fn}: hits is required for a LiDAR kind with obstacles")
+    for name, t_ in (("us", us), ("vs", vs)):
+        if not (torch.is_tensor(t_) and t_.ndim == 1 and t_.numel() > 0):
+            raise ValueError(f"{fn}: {name} must be a non-empty 1-D tensor (sweep_axis)")
+    G = int(n_frames) * int(vs.numel()) * int(us.numel())
+    shapes = [("action_out", action_out, (G, n, 2)), ("goal", goal, (cfg.n_goals, sd))]
+    if cfg.n_obs > 0:
+        if obst is None:
+            raise ValueError(f"{fn}: obst is required when n_obs > 0")
+        shapes.append(("obst", obst, (cfg.n_obs, cfg.obst_stride)))
+    for fields, held in zip(record_fields(cfg), (o_step, o_env)):
+        for name, shape in fields.items():
+            if held.get(name) is None:
+                raise ValueError(f"{fn}: out has no {name}")
+            shapes.append((f"out.{name}", held[name], (G,) + shape))
+    HC = 0
+    if carry is not None:
+        if carry_out is None or not torch.is_tensor(carry_out) or carry_out.ndim != 2 or carry_out.shape[0] != G * n:
+            raise ValueError(f"{fn}: carry_out must be [G * n, HC] = [{G * n}, HC]")
+        HC = int(carry_out.shape[1])
+        shapes.append(("carry_out", carry_out, (G * n, HC)))
+    for name, t_, shape in shapes:
+        if not torch.is_tensor(t_) or tuple(t_.shape) != tuple(shape):
+            got = tuple(t_.shape) if torch.is_tensor(t_) else type(t_).__name__
+            raise ValueError(f"{fn}: {name}: expected shape {tuple(shape)}, got {got}")
+    # a record field [frames, ...] is read at its own frame stride (a view of a larger slab serves as it is)
+    fst = lambda t_, inner: int(t_.stride(0)) if torch.is_tensor(t_) and t_.ndim == len(inner) + 1 and t_.shape[0] > 1 \
+        else int(np.prod(inner))
+    strided = [("agent", agent, fst(agent, (n, sd)), (n, sd)), ("actions", actions, fst(actions, (n, 2)), (n, 2))]
+    if cast:
+        strided.append(("hits", hits, fst(hits, (n, k, 2)), (n, k, 2)))
+    if carry is not None:
+        strided.append(("carry", carry, int(carry_st), (n, HC)))
+    for name, t_, st_, inner in strided:
+        if not torch.is_tensor(t_):
+            raise ValueError(f"{fn}: {name} must be a tensor")
+        if st_ < int(np.prod(inner)):
+            raise ValueError(f"{fn}: the frame stride of {name} ({st_}) is shorter than its {inner} rows")
+    nu, nv, ids, ids_dev, last = K._sweep_grid(fn, cfg, frame_ids, n_frames, agent_id, us, vs, frame_max, ("us", "vs"))
+    K._shaped(fn, shapes)
+    for name, t_, st_, inner in strided:
+        K._check_strided(fn, name, t_, 0, st_, inner, None, 1, last + 1)
+    if ids is not None:
+        ids_dev = torch.from_numpy(ids.astype(np.int32)).to(agent.device)
+    raw = lambda t_: C.c_void_p(t_.data_ptr())       # a view into the record: only its trailing block is dense (checked above)
+    rc_ = N.lib().dgppo_env_action_sweep_fork(
+        C.byref(cfg), raw(agent), strided[0][2], N.ptr(goal, name="goal"), N.ptr(obst, name="obst"), raw(hits) if cast else None,
+        strided[2][2] if cast else 0, raw(actions), strided[1][2], raw(carry) if carry is not None else None, int(carry_st), HC,
+        N.ptr(ids_dev, torch.int32, "frame_ids"), n_frames, int(agent_id), N.ptr(us, name="us"), nu, N.ptr(vs, name="vs"), nv,
+        N.ptr(o_step["agent"], name="out.agent"), N.ptr(o_env["goal"], name="out.goal"), N.ptr(o_env.get("obst"), name="out.obst"),
+        N.ptr(o_step.get("hits") if cast else None, name="out.hits"), N.ptr(action_out, name="action_out"),
+        N.ptr(carry_out if carry is not None else None, name="carry_out"), N.stream_ptr())
+    N.check(rc_, "dgppo_env_action_sweep_fork")
+
+
 def materialize(cfg: N.EnvCfg, st: State, graph: Dict[str, torch.Tensor]):
     if cfg.is_vmas:
         return vmas_graph_materialize(cfg, st.agent, st.body, st.scene, graph)

@@ -129,3 +129,33 @@ class ActionLandscape(NamedTuple):
         """[F, nv, nu]: the swept agent's largest cbf component.  <= 0 exactly where the net admits the action (every
         component of cbf_deriv <= 0)."""
         return np.asarray(self.cbf)[:, :, :, int(self.agent), :].max(axis=-1)
+
+
+class ActionRolloutLandscape(NamedTuple):
+    """What the actions an ActionLandscape judges by the learned barrier lead to, measured (`DGPPO.action_rollout_landscape`):
+    in frames of an episode `agent` plays (us[iu], vs[iv]) for ONE step, everyone else their recorded action, and the
+    deterministic policy is rolled on until the costs of the `horizon` states after that step are known; they are folded as
+    RolloutLandscape folds them."""
+    us: np.ndarray        # [nu] fp32 grid lines of the first action component
+    vs: np.ndarray        # [nv] of the second
+    value: np.ndarray     # [F, nv, nu, n, n_cost]: the discounted-to-max constraint return of the horizon, every agent's row
+    worst: np.ndarray     # [F, nv, nu, n, n_cost]: the largest cost met within the horizon
+    actions: np.ndarray   # [F, 2]: the recorded action of `agent` in frame frames[f], clipped as the environment clips it
+    agent: int            # the agent whose action is swept
+    frames: np.ndarray    # [F] frame numbers of the episode
+    horizon: int          # states after the forced step whose costs are folded
+    gamma: float
+
+    def h(self) -> np.ndarray:
+        """[F, nv, nu]: the swept agent's largest `worst` component (a NaN propagates): what the lookahead shield calls s.
+        >= 0 exactly where the action dooms the agent itself within the horizon."""
+        return np.asarray(self.worst)[:, :, :, int(self.agent), :].max(axis=-1)
+
+    def h_others(self) -> np.ndarray:
+        """[F, nv, nu]: the same over the rows of all OTHER agents (a NaN propagates): what this agent's single action does
+        to its neighbours.  All NaN for a team of one."""
+        w = np.asarray(self.worst)
+        rest = np.delete(w, int(self.agent), axis=3)
+        if rest.shape[3] == 0:
+            return np.full(w.shape[:3], np.nan, dtype=w.dtype)
+        return rest.max(axis=(3, 4))

@@ -171,6 +171,54 @@ def action_admissibility(A) -> Dict[str, np.ndarray]:
                 taken_admitted_frac=float((taken == 1).sum() / max(int((taken >= 0).sum()), 1)))
 
 
+def action_rollout_agreement(R, A=None) -> Dict[str, np.ndarray]:
+    """What a single action decides, measured (trainer.data.ActionRolloutLandscape R), and how the learned barrier's verdict
+    on the same actions (ActionLandscape A of the same agent, us, vs and frames) compares.  A point is `doomed` where
+    R.h() >= 0 (rollout_agreement's convention).  Per frame [F], over the finite entries of R.h(): `points`, `doomed`;
+    doomed_frac = doomed.sum() / max(points.sum(), 1); `empty_frames` — the frame numbers in which every finite point is
+    doomed (frames without a finite point are not among them) — and empty_frac = len(empty_frames) / F; decisive_frac — the
+    share of frames whose grid holds doomed and not-doomed points alike, so that the one action decides.
+    For n > 1: others_doomed_frac and others_decisive_frac, the same two notions on R.h_others().
+    With A: `missed` (admitted by the barrier, A.h() <= 0, but doomed: a false admit of the filter the barrier shield relies
+    on), `conservative` (rejected but not doomed), both [F] and counted where both h() are finite; missed_frac = missed.sum()
+    / max(the doomed points counted, 1), conservative_frac likewise over the points not doomed."""
+    if A is not None:
+        same = (int(R.agent) == int(A.agent)
+                and np.array_equal(np.asarray(R.us), np.asarray(A.us)) and np.array_equal(np.asarray(R.vs), np.asarray(A.vs))
+                and np.array_equal(np.asarray(R.frames).reshape(-1), np.asarray(A.frames).reshape(-1)))
+        if not same:
+            raise ValueError("action_rollout_agreement: R and A differ in us, vs, agent or frames")
+    count = lambda m: m.sum(axis=(1, 2)).astype(np.int64)
+
+    def verdict(h):
+        fin = np.isfinite(h)
+        points, doomed = count(fin), count(fin & (h >= 0.0))
+        return fin, points, doomed
+
+    hr = np.asarray(R.h())
+    F = hr.shape[0]
+    frames = np.asarray(R.frames).reshape(-1).astype(np.int64)
+    if frames.size != F:
+        raise ValueError(f"action_rollout_agreement: {frames.size} frame numbers for {F} frames")
+    fin, points, doomed = verdict(hr)
+    empty = frames[(points > 0) & (doomed == points)]
+    decisive = (doomed > 0) & (doomed < points)
+    out = dict(points=points, doomed=doomed, doomed_frac=float(doomed.sum() / max(int(points.sum()), 1)), empty_frames=empty,
+               empty_frac=float(empty.size / max(F, 1)), decisive_frac=float(decisive.sum() / max(F, 1)))
+    if np.asarray(R.worst).shape[3] > 1:
+        _, po, do = verdict(np.asarray(R.h_others()))
+        out.update(others_doomed_frac=float(do.sum() / max(int(po.sum()), 1)),
+                   others_decisive_frac=float(((do > 0) & (do < po)).sum() / max(F, 1)))
+    if A is not None:
+        ha = np.asarray(A.h())
+        ok = fin & np.isfinite(ha)
+        missed, conservative = count(ok & (ha <= 0.0) & (hr >= 0.0)), count(ok & (ha > 0.0) & (hr < 0.0))
+        n_doomed, n_free = int(count(ok & (hr >= 0.0)).sum()), int(count(ok & (hr < 0.0)).sum())
+        out.update(missed=missed, conservative=conservative, missed_frac=float(missed.sum() / max(n_doomed, 1)),
+                   conservative_frac=float(conservative.sum() / max(n_free, 1)))
+    return out
+
+
 def shield_stats(log) -> Dict[str, np.ndarray]:
     """What the barrier shield did per episode (trainer.data.ShieldLog, arrays [B, T, n, ...]), each [B]:
     `intervention_frac` — the share of (step, agent) pairs whose action was replaced (flag != 0), `infeasible_frac` — the share

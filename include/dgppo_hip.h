@@ -505,6 +505,30 @@ int32_t dgppo_lookahead_select(const float* cost, int64_t cost_st, int32_t K, in
                                const float* a_pol, const float* us, int32_t nu, const float* vs, int32_t nv, float margin,
                                float* action, int32_t* index, int32_t* flag, float* s, void* stream);
 
+/* The what-if environments of an action rollout landscape: ONE agent's action swept in recorded frames, as a dense env state the
+ * step kernels run on.  Env g = (f*nv + iv)*nu + iu, G = n_frames*nv*nu (the numbering of dgppo_graph_feats_action_sweep), is a
+ * copy of frame fid (fid = frame_ids ? frame_ids[f] : f; operands and frame strides as in dgppo_env_sweep_fork) of ONE
+ * environment in which agent `agent_id` is about to play (us[iu], vs[iv]) and everyone else their recorded action of that step:
+ *   agent_out  [G, n, sd]            frame fid's rows, unchanged;
+ *   goal_out   [G, n_goals, sd], obst_out [G, n_obs, 16 | sd]   this env's rows (obst NULL without obstacles);
+ *   hits_out   [G, n, k, 2]          the recorded hits of frame fid, read at hits + fid*hits_st: no position changes before the
+ *                                    step, so nothing is cast (LiDAR kinds with obstacles; hits and hits_out are NULL otherwise);
+ *   action_out [G, n, 2]             row agent_id is (us[iu], vs[iv]); every other row is a copy of action + fid*action_st, laid
+ *                                    out [n, 2];
+ *   carry_out  [G*n, HC]             the rows at carry + fid*carry_st ([n, HC], the actor's packed carry): the caller passes the
+ *                                    carries AFTER each frame's policy forward, which do not depend on the action taken.  carry
+ *                                    may be NULL: nothing is written.
+ * Nothing is computed: words are copied as they are (a NaN keeps its payload) and the action is NOT clipped — the step that
+ * applies it clips (clip_action, env/base.py; the step itself: env/base.py step, lidar_env/base.py:146-149).  nu, nv >= 1, nu*nv
+ * < 2^24, n_frames >= 1, G*n < 2^31; every frame stride is at least its row block.  The reference ships no way to start an
+ * episode anywhere but at reset.                                                                                               */
+int32_t dgppo_env_action_sweep_fork(const dgppo_env_cfg* cfg, const float* agent, int64_t agent_st, const float* goal,
+                                    const float* obst, const float* hits, int64_t hits_st, const float* action, int64_t action_st,
+                                    const float* carry, int64_t carry_st, int32_t HC, const int32_t* frame_ids, int32_t n_frames,
+                                    int32_t agent_id, const float* us, int32_t nu, const float* vs, int32_t nv, float* agent_out,
+                                    float* goal_out, float* obst_out, float* hits_out, float* action_out, float* carry_out,
+                                    void* stream);
+
 /* GraphTransformer attention in fixed-fan-in form (dgppo/nn/gnn.py:85-117; jraph.segment_softmax/segment_sum):
  * qt [G*n,H*F] = x_i Mcat + cvec (a Dense), logits = qt . x_sender, masked softmax over the S slots of each agent,
  * zcat [G*n,Kp] = [x_i | per head: sum a x_s (F), sum a e (4) | 1 | 0...], attn [G*n,S,H] saved for backward (NULL in

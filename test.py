@@ -30,7 +30,16 @@ algorithm has it): for the policy's action and every action of the `--shield-gri
 candidate played and the policy rolled H steps on, and an action is admissible where the agent's own worst cost over those
 steps is <= -M (`--shield-margin M`).  The lines, `test_log.csv`, the landscapes and the video then describe those episodes, and
 `{stamp}_{name}_shield.npz` holds `policy_action`, `action`, `index`, `flag`, `s` (the worst rolled cost of every candidate),
-`us`, `vs`, `margin`, `horizon` and the three statistics.  `--shield-horizon 0` (the default) is the one-step barrier shield."""
+`us`, `vs`, `margin`, `horizon` and the three statistics.  `--shield-horizon 0` (the default) is the one-step barrier shield.
+`--action-rollout-landscape AGENT` measures what the actions `--action-landscape` judges lead to (`action_rollout_landscape`;
+every algorithm has it): in every frame that agent plays each action of the `--landscape-grid`-squared grid of [-1, 1]^2 for one
+step, everyone else their recorded action, and the deterministic policy is rolled on until the costs of the
+`--rollout-horizon K` states after that step are known.  `{stamp}_{name}_action_rollout.npz` holds `us`, `vs`, `value`, `worst`
+(every agent's row), `actions`, `agent`, `frames`, `horizon`, `gamma` and the statistics; a line per episode says how much of the
+action grid dooms the agent within the horizon, in how many frames the one action decides that, and, with `--action-landscape`
+for the same agent, how many of the doomed actions the learned barrier admits (missed_frac) and how many of the others it
+rejects (conservative_frac); the animation shows the doomed set's boundary dashed in the action inset.  It works with
+`--stochastic` and with either shield; the what-if rollouts follow the deterministic, unshielded policy."""
 import argparse
 import datetime
 import os
@@ -96,7 +105,7 @@ def test(args):
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(EV.csv_line(env, args.epi, agg))
     if (not args.no_video or args.landscape is not None or args.cost_landscape is not None or args.action_landscape is not None
-            or args.rollout_landscape is not None or shield_log is not None):
+            or args.rollout_landscape is not None or shield_log is not None or args.action_rollout_landscape is not None):
         videos_dir = pathlib.Path(args.path) / "videos" / f"{step}"
         videos_dir.mkdir(exist_ok=True, parents=True)
         stamp = datetime.datetime.now().strftime("%m%d-%H%M")
@@ -165,6 +174,25 @@ def test(args):
                          horizon=rl.horizon, gamma=rl.gamma, **agree)
                 print(f"rollout landscape: {out}")
                 extra["rollout_landscape"] = rl
+            if args.action_rollout_landscape is not None:
+                R = algo.action_rollout_landscape(ro, i, args.action_rollout_landscape, nu=args.landscape_grid,
+                                                  nv=args.landscape_grid, horizon=args.rollout_horizon)
+                A = extra.get("action_landscape") if args.action_landscape == args.action_rollout_landscape else None
+                agree = EV.action_rollout_agreement(R, A)
+                line = (f"epi: {i}, agent {R.agent}: {agree['doomed_frac'] * 100:.3f}% of the action grid dooms the agent within "
+                        f"{R.horizon} steps (doomed_frac), everything in {agree['empty_frac'] * 100:.3f}% of the frames "
+                        f"(empty_frac), the one action decides it in {agree['decisive_frac'] * 100:.3f}% of them (decisive_frac)")
+                if "others_doomed_frac" in agree:
+                    line += (f", {agree['others_doomed_frac'] * 100:.3f}% of the grid dooms another agent (others_doomed_frac, "
+                             f"decisive in {agree['others_decisive_frac'] * 100:.3f}% of the frames: others_decisive_frac)")
+                if "missed_frac" in agree:
+                    line += (f", the learned barrier admits {agree['missed_frac'] * 100:.3f}% of the doomed actions (missed_frac) "
+                             f"and rejects {agree['conservative_frac'] * 100:.3f}% of the others (conservative_frac)")
+                print(line)
+                out = videos_dir / f"{stamp}_{name}_action_rollout.npz"
+                np.savez(out, **R._asdict(), **agree)
+                print(f"action rollout landscape: {out}")
+                extra["action_rollout_landscape"] = R
             if args.no_video:
                 continue
             out = env.render_video(ro, videos_dir / f"{stamp}_{name}.mp4", unsafe[i], {}, dpi=args.dpi, index=i, **extra)
@@ -195,12 +223,16 @@ ROLLOUT_FLAGS = [(("--rollout-landscape",), "int", None), (("--rollout-horizon",
 # with --shield: filter by forked policy rollouts of H steps instead of the learned barrier (collect_lookahead_shielded; every
 # algorithm has it); 0: the one-step barrier shield
 LOOKAHEAD_FLAGS = [(("--shield-horizon",), "int", 0)]
+# what one agent's actions lead to, measured (action_rollout_landscape; every algorithm has it): each action of the
+# --landscape-grid grid played for one step, then the policy rolled until --rollout-horizon further costs are known, per episode
+ACTION_ROLLOUT_FLAGS = [(("--action-rollout-landscape",), "int", None)]
 
 
 def build_parser() -> argparse.ArgumentParser:
     types = {"int": int, "str": str, "float": float}
     ap = argparse.ArgumentParser(description=__doc__)
-    for names, kind, default in FLAGS + COST_FLAGS + ACTION_FLAGS + SHIELD_FLAGS + ROLLOUT_FLAGS + LOOKAHEAD_FLAGS:
+    for names, kind, default in (FLAGS + COST_FLAGS + ACTION_FLAGS + SHIELD_FLAGS + ROLLOUT_FLAGS + LOOKAHEAD_FLAGS
+                                 + ACTION_ROLLOUT_FLAGS):
         if kind == "flag":
             ap.add_argument(*names, action="store_true", default=False)
         elif kind.startswith("req:"):
