@@ -187,6 +187,11 @@ def lib() -> C.CDLL:
     # the lookahead shield's (same file)
     l.dgppo_env_team_action_fork.restype = i32
     l.dgppo_env_team_action_fork.argtypes = [C.POINTER(EnvCfg), p, p, p, p, p, p, i32, i32, p, i32, p, i32, p, p, p, p, p, p, p]
+    l.dgppo_env_team_action_fork_ids.restype = i32
+    l.dgppo_env_team_action_fork_ids.argtypes = [C.POINTER(EnvCfg), p, p, p, p, p, p, i32, i32, p, i32, p, i32, p, i32, p, p, p, p,
+                                                 p, p, p]
+    l.dgppo_lookahead_reselect.restype = i32
+    l.dgppo_lookahead_reselect.argtypes = [p, i64, i32, i32, i32, i32, p, p, p, i32, p, i32, f32, i32, p, p, p, p, p, p, p]
     l.dgppo_lookahead_select.restype = i32
     l.dgppo_lookahead_select.argtypes = [p, i64, i32, i32, i32, i32, p, p, i32, p, i32, f32, p, p, p, p, p]
     # the action rollout landscape's fork (same file)

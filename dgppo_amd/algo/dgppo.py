@@ -15,7 +15,8 @@ from .. import engine as EN
 from .. import init as INIT
 from .. import nets
 from .. import ops_nn as K
-from ..trainer.data import (ActionLandscape, ActionRolloutLandscape, CostLandscape, Landscape, LookaheadShieldLog, Rollout,
+from ..trainer.data import (ActionLandscape, ActionRolloutLandscape, CostLandscape, JointLookaheadShieldLog, Landscape,
+                            LookaheadShieldLog, Rollout,
                             RolloutLandscape, ShieldLog)
 from ..utils import checkpoint as CK
 from ..utils.graph import GraphsTuple
@@ -330,16 +331,21 @@ class DGPPO(Algorithm):
                                 int(horizon), float(self.engine.hp.gamma))
 
     def collect_lookahead_shielded(self, keys, env=None, grid: int = 8, us=None, vs=None, margin: float = 0.0,
-                                   horizon: int = 8):
+                                   horizon: int = 8, rounds: int = 1):
         """-> (Rollout, LookaheadShieldLog): deterministic test episodes in which every agent's action passes through a
         lookahead filter (Engine.rollout_lookahead_shielded): for the policy's action and every action of the grid us x vs
         (default: linspace(-1, 1, grid) in fp32 on both axes) the environment is forked, the candidate played, and the policy
         rolled `horizon` steps on; the policy's action is kept where the agent's own worst cost over those steps is <= -margin,
         otherwise replaced by the nearest admissible grid action, or by the least bad one where nothing is admissible.  It
         filters on what Vh is meant to predict, not on the prediction, and needs only the simulator and the policy: every
-        algorithm has it.  An agent's candidates are judged with everyone else playing the policy, and the what-if rollouts
-        run past the episode's end.  The Rollout is a deterministic one in every respect (landscapes, render_video); the log
-        says what the shield did.  Not in the reference."""
+        algorithm has it.  An agent's candidates are judged with everyone else playing the policy (with rounds >= 2 the joint
+        action the agents settle on is rolled as well: below), and the what-if rollouts run past the episode's end.  The Rollout is a deterministic one in every respect (landscapes, render_video); the log
+        says what the shield did.  Not in the reference.
+        rounds >= 2 -> (Rollout, JointLookaheadShieldLog): the agents' picks are re-judged jointly, up to `rounds` rounds per
+        step (Engine.lookahead_select_rounds): the joint action held is rolled as everyone's candidate 0, and in every round
+        after the first one agent per environment may still move.  The log's `joint` says per step whether the joint action
+        that was played had been rolled (2: rolled and admissible for every agent, 1: rolled and not admissible, 0: not
+        rolled — the rounds ran out while agents were still moving), `rounds_used` how many rounds judged the step."""
         if env is not None and env is not self._env:
             assert env.cfg.kind == self._env.cfg.kind and env.num_agents == self.n_agents
         what = "collect_lookahead_shielded"
@@ -348,11 +354,20 @@ class DGPPO(Algorithm):
             raise ValueError(f"{what}: margin must be finite")
         if int(horizon) < 1:
             raise ValueError(f"{what}: horizon must be >= 1 (got {horizon})")
-        ro, log = self.engine.rollout_lookahead_shielded(self._seeds(keys), us, vs, int(horizon), float(margin))
-        r = self._wrap(ro, env)
+        if int(rounds) < 1:
+            raise ValueError(f"{what}: rounds must be >= 1 (got {rounds})")
         em = lambda x: x.transpose(0, 1).contiguous().cpu().numpy()
-        return r, LookaheadShieldLog(em(log["policy_action"]), ro.actions.cpu().numpy(), em(log["index"]), em(log["flag"]),
-                                     em(log["s"]), us, vs, float(margin), int(horizon))
+        if int(rounds) == 1:
+            ro, log = self.engine.rollout_lookahead_shielded(self._seeds(keys), us, vs, int(horizon), float(margin))
+            r = self._wrap(ro, env)
+            return r, LookaheadShieldLog(em(log["policy_action"]), ro.actions.cpu().numpy(), em(log["index"]), em(log["flag"]),
+                                         em(log["s"]), us, vs, float(margin), int(horizon))
+        ro, log = self.engine.rollout_lookahead_shielded(self._seeds(keys), us, vs, int(horizon), float(margin),
+                                                         rounds=int(rounds))
+        r = self._wrap(ro, env)
+        return r, JointLookaheadShieldLog(em(log["policy_action"]), ro.actions.cpu().numpy(), em(log["index"]), em(log["flag"]),
+                                          em(log["s"]), us, vs, float(margin), int(horizon), em(log["joint"]),
+                                          em(log["rounds_used"]), int(rounds))
 
     def action_landscape(self, rollout: Rollout, index: int, agent: int, frames=None, nu: int = 32, nv: int = 32, us=None,
                          vs=None) -> ActionLandscape:

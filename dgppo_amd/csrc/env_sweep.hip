@@ -970,13 +970,15 @@ __device__ inline void pick_candidate(int p, float a0, float a1, const float* us
   }
 }
 
-__device__ inline void pick_consider(ShieldPick& k, float h, int p, float a0, float a1, float thr, const float* us,
-                                     const float* vs, int nu) {
+// (r0, r1): the action the distance is measured from — candidate 0 itself for the one-shot shields, the policy's action where
+// candidate 0 is an action held from an earlier round (dgppo_lookahead_reselect)
+__device__ inline void pick_consider(ShieldPick& k, float h, int p, float a0, float a1, float r0, float r1, float thr,
+                                     const float* us, const float* vs, int nu) {
   if (p == 0) k.h0 = h;
   float cu, cv;
   pick_candidate(p, a0, a1, us, vs, nu, cu, cv);
   if (h <= thr) {                               // admissible (false for a NaN)
-    const float du = cu - a0, dv = cv - a1;
+    const float du = cu - r0, dv = cv - r1;
     float d = du * du + dv * dv;
     if (d != d) d = __builtin_inff();
     if (d < k.bd || (d == k.bd && p < k.bdi)) { k.bd = d; k.bdi = p; }
@@ -984,17 +986,27 @@ __device__ inline void pick_consider(ShieldPick& k, float h, int p, float a0, fl
   if (h == h && (h < k.bh || (h == k.bh && p < k.bhi))) { k.bh = h; k.bhi = p; }
 }
 
-// every lane of the wave calls it; lane 0 writes the row's choice
-__device__ inline void pick_finish(ShieldPick& k, int lane, long row, float a0, float a1, float thr, const float* us,
-                                   const float* vs, int nu, float* action, int32_t* index, int32_t* flag) {
+__device__ inline void pick_consider(ShieldPick& k, float h, int p, float a0, float a1, float thr, const float* us,
+                                     const float* vs, int nu) {
+  pick_consider(k, h, p, a0, a1, a0, a1, thr, us, vs, nu);
+}
+
+// every lane of the wave calls it and every lane gets the row's choice: the candidate and its flag (0 kept, 1 admissible, 2 not)
+__device__ inline void pick_settle(ShieldPick& k, float thr, int& idx, int& fl) {
   const float h0 = __shfl(k.h0, 0);
   wave_argmin(k.bd, k.bdi);
   wave_argmin(k.bh, k.bhi);
-  if (lane != 0) return;
-  int idx, fl;
   if (h0 <= thr) { idx = 0; fl = 0; }
   else if (k.bdi != 0x7fffffff) { idx = k.bdi; fl = 1; }
   else { idx = (k.bhi != 0x7fffffff) ? k.bhi : 0; fl = 2; }
+}
+
+// every lane of the wave calls it; lane 0 writes the row's choice
+__device__ inline void pick_finish(ShieldPick& k, int lane, long row, float a0, float a1, float thr, const float* us,
+                                   const float* vs, int nu, float* action, int32_t* index, int32_t* flag) {
+  int idx, fl;
+  pick_settle(k, thr, idx, fl);
+  if (lane != 0) return;
   float cu, cv;
   pick_candidate(idx, a0, a1, us, vs, nu, cu, cv);
   action[row * 2] = cu; action[row * 2 + 1] = cv;
@@ -1327,6 +1339,7 @@ inline ForkField fork_field(const float* s, float* d, long len, long st) {
 struct TeamForkArgs {
   ForkField f[5];         // agent, goal, obst, hits, carry
   const uint32_t* a_pol;  // [n_env, n, 2]
+  const int32_t* ids;     // source env of output block m (dgppo_env_team_action_fork_ids); NULL: m itself
   const uint32_t* us;
   const uint32_t* vs;
   uint32_t* action_out;   // [G, n, 2]
@@ -1368,13 +1381,14 @@ __global__ void __launch_bounds__(FORKT_NT) env_team_action_fork_kernel(TeamFork
   const int tid = threadIdx.x;
   const uint32_t g0 = blockIdx.x * FORKT_TILE;
   const int envs = (int)min((long)FORKT_TILE, a.G - (long)g0);
-  fork_fields(a.f, g0, envs, (uint32_t)a.nP, nullptr, tid);
+  fork_fields(a.f, g0, envs, (uint32_t)a.nP, a.ids, tid);
   // the joint action: a_pol[e]'s words, row i replaced by candidate p (p = 0 is a_pol[e, i] itself)
   const int n = a.n, rows = envs * n;
   for (int o = tid; o < rows; o += FORKT_NT) {
     const int gl = o / n, r = o - gl * n;
-    const uint32_t g = g0 + (uint32_t)gl, e = g / (uint32_t)a.nP;
-    const int rem = (int)(g - e * (uint32_t)a.nP), i = rem / a.P, p = rem - i * a.P;
+    const uint32_t g = g0 + (uint32_t)gl, m = g / (uint32_t)a.nP;
+    const uint32_t e = a.ids ? (uint32_t)a.ids[m] : m;
+    const int rem = (int)(g - m * (uint32_t)a.nP), i = rem / a.P, p = rem - i * a.P;
     uint2 w;
     if (r == i && p > 0) {
       const int iv = (p - 1) / a.nu, iu = (p - 1) - iv * a.nu;
@@ -1391,12 +1405,12 @@ __global__ void __launch_bounds__(FORKT_NT) env_team_action_fork_kernel(TeamFork
   }
 }
 
-extern "C" int32_t dgppo_env_team_action_fork(const dgppo_env_cfg* cfg, const float* agent, const float* goal, const float* obst,
-                                              const float* hits, const float* a_pol, const float* carry, int32_t HC, int32_t n_env,
-                                              const float* us, int32_t nu, const float* vs, int32_t nv, float* agent_out,
-                                              float* goal_out, float* obst_out, float* hits_out, float* action_out,
-                                              float* carry_out, void* stream) {
-  const char* fn = "dgppo_env_team_action_fork";
+// both entry points: the G = n_ids * n * P copies of the envs env_ids[0 .. n_ids) (NULL: env m itself) of n_env dense envs
+static int32_t team_action_fork(const char* fn, const dgppo_env_cfg* cfg, const float* agent, const float* goal, const float* obst,
+                                const float* hits, const float* a_pol, const float* carry, int32_t HC, int32_t n_env,
+                                const int32_t* env_ids, int32_t n_ids, const float* us, int32_t nu, const float* vs, int32_t nv,
+                                float* agent_out, float* goal_out, float* obst_out, float* hits_out, float* action_out,
+                                float* carry_out, void* stream) {
   int32_t rc = dgppo_validate_cfg(cfg);
   if (rc) {   // the configuration's own refusal, under this entry point's name
     const std::string why = dgppo_last_error();
@@ -1406,15 +1420,18 @@ extern "C" int32_t dgppo_env_team_action_fork(const dgppo_env_cfg* cfg, const fl
   DGPPO_REFUSE_VMAS(cfg, fn, "dgppo_vmas_step on a tiled record (there is no VMAS fork)");
   DGPPO_REQUIRE(nu >= 1 && nv >= 1, "%s: nu and nv must be >= 1 (got %d, %d)", fn, nu, nv);
   DGPPO_REQUIRE((long)nu * nv < (1L << 24), "%s: grid too large (nu * nv < 2^24)", fn);
-  DGPPO_REQUIRE(n_env >= 0, "%s: negative counts", fn);
+  DGPPO_REQUIRE(n_env >= 0 && n_ids >= 0, "%s: negative counts", fn);
+  DGPPO_REQUIRE(env_ids != nullptr || n_ids == n_env, "%s: without env_ids the list is every env (n_ids %d != n_env %d)", fn, n_ids,
+                n_env);
+  DGPPO_REQUIRE(n_ids == 0 || n_env >= 1, "%s: %d envs listed of none", fn, n_ids);
   const int n = cfg->n_agents, ng = cfg->n_goals, SD = cfg->state_dim, no = cfg->n_obs, k = cfg->top_k;
   const long P = 1 + (long)nu * nv, nP = (long)n * P;
-  DGPPO_REQUIRE((double)n_env * (double)nP * (double)n < 2147483648.0, "%s: too many envs (G * n < 2^31)", fn);
+  DGPPO_REQUIRE((double)n_ids * (double)nP * (double)n < 2147483648.0, "%s: too many envs (G * n < 2^31)", fn);
   const bool lidar = cfg_is_lidar(*cfg), cast = lidar && no > 0;
   if (carry != nullptr) {
     DGPPO_REQUIRE(HC >= 1 && (long)n * HC < (1L << 24), "%s: HC %d out of range", fn, HC);
   }
-  if (n_env == 0) return 0;
+  if (n_ids == 0) return 0;
   DGPPO_REQUIRE(agent && goal && a_pol && us && vs && agent_out && goal_out && action_out, "%s: NULL operand", fn);
   if (no > 0) {
     DGPPO_REQUIRE(obst, "%s: obst is NULL", fn);
@@ -1436,14 +1453,37 @@ extern "C" int32_t dgppo_env_team_action_fork(const dgppo_env_cfg* cfg, const fl
   a.f[3] = field(hits, hits_out, cast ? (long)n * k * 2 : 0);
   a.f[4] = field(carry, carry_out, carry != nullptr ? (long)n * HC : 0);
   a.a_pol = reinterpret_cast<const uint32_t*>(a_pol);
+  a.ids = env_ids;
   a.us = reinterpret_cast<const uint32_t*>(us); a.vs = reinterpret_cast<const uint32_t*>(vs);
   a.action_out = reinterpret_cast<uint32_t*>(action_out);
   a.avec = (((uintptr_t)a_pol | (uintptr_t)action_out) % 8 == 0) ? 2 : 1;
-  a.G = (long)n_env * nP; a.n = n; a.nu = nu; a.P = (int)P; a.nP = (int)nP;
+  a.G = (long)n_ids * nP; a.n = n; a.nu = nu; a.P = (int)P; a.nP = (int)nP;
   const dim3 grid((unsigned)((a.G + FORKT_TILE - 1) / FORKT_TILE));
   hipLaunchKernelGGL(env_team_action_fork_kernel, grid, dim3(FORKT_NT), 0, (hipStream_t)stream, a);
   DGPPO_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int32_t dgppo_env_team_action_fork(const dgppo_env_cfg* cfg, const float* agent, const float* goal, const float* obst,
+                                              const float* hits, const float* a_pol, const float* carry, int32_t HC, int32_t n_env,
+                                              const float* us, int32_t nu, const float* vs, int32_t nv, float* agent_out,
+                                              float* goal_out, float* obst_out, float* hits_out, float* action_out,
+                                              float* carry_out, void* stream) {
+  return team_action_fork("dgppo_env_team_action_fork", cfg, agent, goal, obst, hits, a_pol, carry, HC, n_env, nullptr, n_env, us,
+                          nu, vs, nv, agent_out, goal_out, obst_out, hits_out, action_out, carry_out, stream);
+}
+
+// The fork of a later shield round: only the envs env_ids[0 .. n_ids) are copied, output block m from env env_ids[m], and the
+// joint action the candidates are set into is a_base[e] — the action held after the rounds so far — not the policy's.  The
+// sources stay dense over all n_env envs; the caller guarantees 0 <= env_ids[m] < n_env.
+extern "C" int32_t dgppo_env_team_action_fork_ids(const dgppo_env_cfg* cfg, const float* agent, const float* goal,
+                                                  const float* obst, const float* hits, const float* a_base, const float* carry,
+                                                  int32_t HC, int32_t n_env, const int32_t* env_ids, int32_t n_ids, const float* us,
+                                                  int32_t nu, const float* vs, int32_t nv, float* agent_out, float* goal_out,
+                                                  float* obst_out, float* hits_out, float* action_out, float* carry_out,
+                                                  void* stream) {
+  return team_action_fork("dgppo_env_team_action_fork_ids", cfg, agent, goal, obst, hits, a_base, carry, HC, n_env, env_ids,
+                          n_ids, us, nu, vs, nv, agent_out, goal_out, obst_out, hits_out, action_out, carry_out, stream);
 }
 
 
@@ -1627,6 +1667,117 @@ extern "C" int32_t dgppo_lookahead_select(const float* cost, int64_t cost_st, in
   a.margin = margin; a.action = action; a.index = index; a.flag = flag; a.s = s;
   const dim3 grid((unsigned)((rows + SHIELD_WAVES - 1) / SHIELD_WAVES));
   hipLaunchKernelGGL(lookahead_select_kernel, grid, dim3(SHIELD_NT), 0, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
+
+// ---- lookahead shield: the selection of a later round ---------------------------------------------------------------------------
+// Round r of Engine.lookahead_select_rounds re-judges the envs env_ids[0 .. n_ids) with the joint action held so far as candidate 0
+// (dgppo_env_team_action_fork_ids): the fold is lookahead_select_kernel's on what-if env (m * n + i) * P + p, the pick the same
+// pick_consider / pick_settle with the distance measured from the policy's action a_ref, and what an agent commits depends on
+// the whole team (mode 1: the lowest-numbered agent that wants to move moves alone).  One workgroup per listed env: its waves
+// take the agents in turn and leave every agent's pick in LDS, one barrier, then a thread per agent commits — no atomics, no
+// second launch, and nothing depends on the order the waves ran in.  Rows of envs that are not listed are not touched.
+struct ReselectArgs {
+  const float* cost;      // step 1 of the block record: [K][n_ids * n * P, n, nh] with step stride cost_st
+  long cost_st;
+  const int32_t* env_ids; // [n_ids] or NULL: env m itself
+  const float* a_ref;     // [n_env, n, 2]
+  const float* us;
+  const float* vs;
+  int n, nh, nu, P, K, mode;
+  float margin;
+  float* action;          // [n_env, n, 2] in and out
+  int32_t* index;         // [n_env, n] in and out
+  int32_t* flag;          // [n_env, n]
+  float* s;               // [n_env, n, P] or NULL
+  int32_t* joint;         // [n_env]
+  int32_t* changed;       // [n_env]
+};
+
+__global__ void __launch_bounds__(SHIELD_NT) lookahead_reselect_kernel(ReselectArgs a) {
+  extern __shared__ int32_t rs_pick[];            // [n] the pick, then [n] its flag
+  const int tid = threadIdx.x, lane = tid & (DGPPO_WAVE - 1), wave = tid / DGPPO_WAVE;
+  const int n = a.n, nh = a.nh, P = a.P;
+  int32_t* rs_flag = rs_pick + n;
+  const long m = blockIdx.x;
+  const long e = a.env_ids ? (long)a.env_ids[m] : m;
+  const float thr = -a.margin;
+  for (int i = wave; i < n; i += SHIELD_WAVES) {  // the whole wave takes the agent: no lane is missing from the shuffles
+    const long row = e * n + i, wrow = m * n + i;
+    const float a0 = clip_action(a.action[row * 2]), a1 = clip_action(a.action[row * 2 + 1]);
+    const float r0 = clip_action(a.a_ref[row * 2]), r1 = clip_action(a.a_ref[row * 2 + 1]);
+    ShieldPick k = pick_init();
+    for (int p = lane; p < P; p += DGPPO_WAVE) {
+      const float* c = a.cost + (((size_t)wrow * P + p) * n + i) * nh;
+      float h = c[0];
+      for (int st = 0; st < a.K; ++st, c += a.cost_st)
+        for (int cc = 0; cc < nh; ++cc) h = nanmax(h, c[cc]);
+      if (a.s != nullptr) a.s[(size_t)row * P + p] = h;
+      pick_consider(k, h, p, a0, a1, r0, r1, thr, a.us, a.vs, a.nu);
+    }
+    int idx, fl;
+    pick_settle(k, thr, idx, fl);
+    if (lane == 0) { rs_pick[i] = idx; rs_flag[i] = fl; }
+  }
+  __syncthreads();
+  // the lowest-numbered agent that wants to move, and whether candidate 0 — the joint action that was rolled — holds for everyone
+  int first = n, unsafe = 0;
+  for (int i = 0; i < n; ++i) {
+    if (rs_pick[i] != 0 && i < first) first = i;
+    unsafe |= rs_flag[i] != 0;
+  }
+  for (int i = tid; i < n; i += SHIELD_NT) {
+    const long row = e * n + i;
+    const int idx = rs_pick[i], fl = rs_flag[i];
+    const float a0 = clip_action(a.action[row * 2]), a1 = clip_action(a.action[row * 2 + 1]);
+    float cu = a0, cv = a1;
+    int out;
+    if (idx != 0 && (a.mode == 0 || i == first)) {
+      pick_candidate(idx, a0, a1, a.us, a.vs, a.nu, cu, cv);
+      a.index[row] = idx;
+      out = fl;                                   // 1: the pick is admissible; 2: the least bad of none
+    } else {
+      out = (fl != 0) ? 2 : (a.index[row] == 0 ? 0 : 1);
+    }
+    a.action[row * 2] = cu; a.action[row * 2 + 1] = cv;
+    a.flag[row] = out;
+  }
+  if (tid == 0) {
+    const int ch = first < n;
+    a.changed[e] = ch;
+    a.joint[e] = ch ? 0 : (unsafe ? 1 : 2);
+  }
+}
+
+extern "C" int32_t dgppo_lookahead_reselect(const float* cost, int64_t cost_st, int32_t K, int32_t n_ids, int32_t n_agents,
+                                            int32_t n_cost, const int32_t* env_ids, const float* a_ref, const float* us,
+                                            int32_t nu, const float* vs, int32_t nv, float margin, int32_t mode, float* action,
+                                            int32_t* index, int32_t* flag, float* s, int32_t* joint, int32_t* changed,
+                                            void* stream) {
+  const char* fn = "dgppo_lookahead_reselect";
+  DGPPO_REQUIRE(n_ids >= 0 && n_agents >= 1, "%s: n_ids >= 0 and n_agents >= 1 are required", fn);
+  DGPPO_REQUIRE(n_agents <= 4096, "%s: n_agents %d above 4096", fn, n_agents);
+  DGPPO_REQUIRE(n_cost >= 1 && n_cost <= 3, "%s: n_cost %d outside [1, 3]", fn, n_cost);
+  DGPPO_REQUIRE(K >= 1, "%s: K must be >= 1 (got %d)", fn, K);
+  DGPPO_REQUIRE(nu >= 1 && nv >= 1, "%s: nu and nv must be >= 1 (got %d, %d)", fn, nu, nv);
+  DGPPO_REQUIRE((long)nu * nv < (1L << 24), "%s: grid too large (nu * nv < 2^24)", fn);
+  DGPPO_REQUIRE(margin == margin, "%s: margin must not be NaN", fn);
+  DGPPO_REQUIRE(mode == 0 || mode == 1, "%s: mode must be 0 (every agent commits) or 1 (one mover) (got %d)", fn, mode);
+  const long P = 1 + (long)nu * nv;
+  DGPPO_REQUIRE((double)n_ids * (double)n_agents * (double)P * (double)n_agents < 2147483648.0,
+                "%s: too many envs (G * n < 2^31)", fn);
+  const long rows = (long)n_ids * n_agents, step = rows * P * n_agents * n_cost;
+  DGPPO_REQUIRE(K == 1 || cost_st >= step, "%s: the step stride %ld is shorter than a step (%ld floats)", fn, (long)cost_st, step);
+  if (n_ids == 0) return 0;
+  DGPPO_REQUIRE(cost && a_ref && us && vs && action && index && flag && joint && changed, "%s: NULL operand", fn);
+  ReselectArgs a;
+  a.cost = cost; a.cost_st = (long)cost_st; a.env_ids = env_ids; a.a_ref = a_ref; a.us = us; a.vs = vs;
+  a.n = n_agents; a.nh = n_cost; a.nu = nu; a.P = (int)P; a.K = K; a.mode = mode;
+  a.margin = margin; a.action = action; a.index = index; a.flag = flag; a.s = s; a.joint = joint; a.changed = changed;
+  const size_t smem = sizeof(int32_t) * 2 * (size_t)n_agents;
+  hipLaunchKernelGGL(lookahead_reselect_kernel, dim3((unsigned)n_ids), dim3(SHIELD_NT), smem, (hipStream_t)stream, a);
   DGPPO_LAUNCH_CHECK();
   return 0;
 }

@@ -82,6 +82,30 @@ class RolloutData:
         views = {k: v.unbind(0) for k, v in self.step_tm.items()}
         self.states_tm = [OE.State({k: v[t] for k, v in views.items()}, self.env) for t in range(T + 1)]
 
+    def prefix(self, B: int) -> "RolloutData":
+        """the time-major record of the first B envs of this one, on the same storage: every step of every field is a dense
+        [B, ...] view, the steps keep this record's stride (the shield rounds roll blocks of any size in one block record)"""
+        if not 1 <= B <= self.B:
+            raise ValueError(f"RolloutData.prefix: {B} envs of a record of {self.B}")
+        if B == self.B:
+            return self
+        v = object.__new__(RolloutData)
+        v.cfg, v.B, v.T, v.stochastic = self.cfg, B, self.T, self.stochastic
+        v.step_tm = {k: x[:, :B] for k, x in self.step_tm.items()}
+        v.env = {k: x[:B] for k, x in self.env.items()}
+        v.step = {}
+        for k in OE.STEP_FIELDS:
+            setattr(v, k + "_tm", v.step_tm.get(k))
+            setattr(v, k, None)
+        for k in OE.ENV_FIELDS:
+            setattr(v, k, v.env.get(k))
+        cut = lambda x: None if x is None else x[:, :B]
+        v.action_tm, v.log_pi_tm, v.rnn_tm = cut(self.action_tm), cut(self.log_pi_tm), cut(self.rnn_tm)
+        v.reward_tm, v.cost_tm = cut(self.reward_tm), cut(self.cost_tm)
+        v._env_major = False
+        v.states_tm = [OE.State({k: x[t] for k, x in v.step_tm.items()}, v.env) for t in range(self.T + 1)]
+        return v
+
     def finalize(self):
         """time-major -> env-major copies (pure data movement).  The env-major buffers are allocated once per record and
         rewritten in place afterwards, so that device pointers stay valid for captured HIP graphs of the update."""
@@ -923,8 +947,9 @@ class Engine:
         G * (horizon + 2) <= prepass_graphs and never fewer than one env.  The last step of the block record exists only to
         evaluate the cost of the last state.
         Two limits, as in rollout_shielded: agent i's candidates are judged with everyone else playing the policy, so when
-        several agents are replaced in the same step the joint outcome is not one that was rolled; and the what-if rollouts
-        run past the episode's end (there is no done flag in these environments).
+        several agents are replaced in the same step the joint outcome is not one that was rolled (lookahead_select_rounds rolls
+        it, and says where it could not); and the what-if rollouts run past the episode's end (there is no done flag in these
+        environments).
         records: a list that receives (t, e0, Eb, block record) per block (time-major, as rolled; the tests re-derive every
         step of those); without it the block records are reused from call to call.  mark: called after the fork and forced
         step, after the policy steps and after the selection of every block (rollout_lookahead_shielded's events)."""
@@ -975,8 +1000,93 @@ class Engine:
             if records is not None:
                 records.append((int(t), e0, Eb, rec))
 
+    def lookahead_select_rounds(self, st: OE.State, carry_next, a_pol, us, vs, horizon: int, margin: float, rounds: int, action,
+                                index, flag, s, joint, rounds_used, records: Optional[list] = None, t: int = 0,
+                                mark: Optional[Callable[[], None]] = None):
+        """lookahead_select in rounds that roll the joint action the agents settle on.  The joint action held, A = `action`
+        [B, n, 2], starts as a_pol with index = 0 and every env active.  Round r < rounds, on the active envs: every (env, agent,
+        candidate) is forked from A (dgppo_env_team_action_fork_ids: candidate 0 is what the agent holds, everyone else plays
+        A), stepped and rolled exactly as in lookahead_select, and dgppo_lookahead_reselect picks per agent — nearest to the
+        POLICY's action among the admissible — and commits: every agent in round 0 (which is lookahead_select's verdict), in
+        later rounds only the lowest-numbered agent that wants to move.  One mover per round, because agents that re-judge
+        simultaneously can dodge and return in lockstep for ever; one mover leaves a joint action whose every other row was
+        the one rolled.  An env stays active while some agent moved; the rounds end when no env is active.
+        -> action, index (the grid number of what is held, 0: the policy's action), flag (of the action held: 0 policy's and
+        admissible, 1 replaced and admissible, 2 not admissible), s [B, n, P] (the fold of the env's LAST round), joint [B]
+        int32 (2: the joint action held was rolled as candidate 0 and is admissible for every agent; 1: rolled, not admissible
+        for some agent, nobody found better; 0: some agent moved in the env's last round — the joint action held was NOT
+        rolled, the limit of lookahead_select is back for that env) and rounds_used [B] int32 (the rounds that judged the env).
+        rounds = 1 gives lookahead_select's action, index, flag and s.  One host sync per round but the last (the active list,
+        torch.nonzero).  The active list is walked in blocks of at most as many envs as lookahead_select's, in prefixes of ONE
+        block record of that capacity.  records: receives (t, r, env ids of the block, block record); the records are then
+        fresh ones.  mark: as in lookahead_select, per block of every round."""
+        cfg = self.cfg
+        fn = "lookahead_select_rounds"
+        if cfg.is_vmas:
+            raise ValueError(f"{fn}: VMASReverseTransport is not supported")
+        n, HC = cfg.n_agents, self.HC
+        H, R = int(horizon), int(rounds)
+        if H < 1:
+            raise ValueError(f"{fn}: horizon must be >= 1 (got {horizon})")
+        if R < 1:
+            raise ValueError(f"{fn}: rounds must be >= 1 (got {rounds})")
+        margin = float(margin)
+        if not np.isfinite(margin):
+            raise ValueError(f"{fn}: margin must be finite")
+        if self.hp.use_rnn and carry_next is None:
+            raise ValueError(f"{fn}: this engine's policy has a recurrent cell: carry_next is required")
+        if not self.hp.use_rnn:
+            carry_next = None
+        B = int(a_pol.shape[0])
+        P = 1 + int(us.numel()) * int(vs.numel())
+        block = max(1, min(B, max(1, self.prepass_graphs) // (n * P * (H + 2))))
+        full = None
+        if records is None:
+            key = (block * n * P, H)
+            if getattr(self, "_lar_record", (None, None))[0] != key:          # ONE record, whatever the active counts turn out to be
+                self._lar_record = (key, RolloutData(cfg, key[0], H + 1, self.device, False, HC))
+            full = self._lar_record[1]
+        action.copy_(a_pol)
+        index.zero_()
+        changed = torch.zeros(B, dtype=torch.int32, device=self.device)
+        used = np.zeros(B, np.int32)
+        ids = np.arange(B, dtype=np.int32)
+        for r in range(R):
+            ids_dev = torch.from_numpy(ids).to(self.device)
+            used[ids] += 1
+            if r > 0:
+                changed.zero_()
+            for m0 in range(0, ids.size, block):
+                blk = ids[m0:m0 + block]
+                Mb = int(blk.size)
+                G = Mb * n * P
+                rec = full.prefix(G) if full is not None else RolloutData(cfg, G, H + 1, self.device, False, HC)
+                if carry_next is None:
+                    rec.rnn_tm[1].zero_()
+                OE.team_action_fork_ids(cfg, st, action, blk, us, vs, rec.states_tm[0], rec.action_tm[0], carry_next,
+                                        rec.rnn_tm[1].view(G * n, HC) if carry_next is not None else None,
+                                        ids_dev=ids_dev[m0:m0 + Mb])
+                OE.step(cfg, rec.states_tm[0], rec.action_tm[0], rec.states_tm[1], rec.reward_tm[0], rec.cost_tm[0])
+                if mark:
+                    mark()
+                self._rollout_steps(rec, None, G, False, start=1)
+                if mark:
+                    mark()
+                K.lookahead_reselect(rec.cost_tm[1:H + 1], blk, a_pol, us, vs, margin, 0 if r == 0 else 1, action, index, flag,
+                                     joint, changed, s, ids_dev=ids_dev[m0:m0 + Mb])
+                if mark:
+                    mark()
+                if records is not None:
+                    records.append((int(t), r, blk.copy(), rec))
+            if r + 1 == R:
+                break
+            ids = torch.nonzero(changed).flatten().to(torch.int32).cpu().numpy()   # ascending; the round's one host sync
+            if ids.size == 0:
+                break
+        rounds_used.copy_(torch.from_numpy(used), non_blocking=False)
+
     def rollout_lookahead_shielded(self, seeds: torch.Tensor, us, vs, horizon: int, margin: float = 0.0,
-                                   events: Optional[list] = None, records: Optional[list] = None):
+                                   events: Optional[list] = None, records: Optional[list] = None, rounds: int = 1):
         """-> (RolloutData, log): a deterministic record (the conventions of rollout(seeds, False)) in which, at every step,
         every agent's action is filtered by what it leads to within `horizon` steps of the simulator, the learned Vh left out:
         what rollout_shielded trusts Vh to predict is rolled here.  Per step t: the policy forward on state t gives a_pol and
@@ -990,7 +1100,12 @@ class Engine:
         an admissible candidate, 2 nothing admissible), s [T, B, n, P].  Eager launches; the record is a fresh one.
         events: a list that receives one tuple of device events per step (tools/bench_lookahead_shield.py): start, policy
         forward done, then (fork and forced step, policy steps, select) done per env block, the final step done.
-        records: as in lookahead_select."""
+        records: as in lookahead_select.
+        rounds: 1 is the path above, untouched.  rounds >= 2 selects with lookahead_select_rounds — up to `rounds` rounds per
+        step, one mover per env in every round after the first — and the log gains joint [T, B] and rounds_used [T, B] (int32;
+        joint 2: the joint action played was rolled and is admissible for every agent, 1: rolled and not admissible, 0: not
+        rolled); the events then hold one (fork and forced step, policy steps, select) triple per block of every round, and
+        records receives lookahead_select_rounds' tuples."""
         cfg, T = self.cfg, self.T
         if cfg.is_vmas:
             raise ValueError("rollout_lookahead_shielded: VMASReverseTransport is not supported")
@@ -1001,6 +1116,9 @@ class Engine:
         margin = float(margin)
         if not np.isfinite(margin):
             raise ValueError("rollout_lookahead_shielded: margin must be finite")
+        R = int(rounds)
+        if R < 1:
+            raise ValueError(f"rollout_lookahead_shielded: rounds must be >= 1 (got {rounds})")
         us, vs = K.sweep_axis(us, "us", self.device), K.sweep_axis(vs, "vs", self.device)
         P = 1 + int(us.numel()) * int(vs.numel())
         B = int(seeds.shape[0])
@@ -1010,6 +1128,9 @@ class Engine:
         ro.rnn_tm[0].zero_()
         log = dict(policy_action=torch.empty(T, B, n, 2, device=dev), index=torch.empty(T, B, n, dtype=torch.int32, device=dev),
                    flag=torch.empty(T, B, n, dtype=torch.int32, device=dev), s=torch.empty(T, B, n, P, device=dev))
+        if R > 1:
+            log.update(joint=torch.empty(T, B, dtype=torch.int32, device=dev),
+                       rounds_used=torch.empty(T, B, dtype=torch.int32, device=dev))
         for t in range(T):
             st = ro.states_tm[t]
             ev = [] if events is not None else None
@@ -1028,8 +1149,13 @@ class Engine:
             K.policy_head(act["ms"], None, None, a_pol.view(B * n, 2), None, None, n, 1)
             mark()
             # 2. - 5. fork, forced step, policy steps, selection: blocks of environments
-            self.lookahead_select(st, h_next if self.hp.use_rnn else None, a_pol, us, vs, H, margin, ro.action_tm[t],
-                                  log["index"][t], log["flag"][t], log["s"][t], records=records, t=t, mark=mark)
+            if R == 1:
+                self.lookahead_select(st, h_next if self.hp.use_rnn else None, a_pol, us, vs, H, margin, ro.action_tm[t],
+                                      log["index"][t], log["flag"][t], log["s"][t], records=records, t=t, mark=mark)
+            else:
+                self.lookahead_select_rounds(st, h_next if self.hp.use_rnn else None, a_pol, us, vs, H, margin, R,
+                                             ro.action_tm[t], log["index"][t], log["flag"][t], log["s"][t], log["joint"][t],
+                                             log["rounds_used"][t], records=records, t=t, mark=mark)
             # 6. the step that counts
             OE.step(cfg, st, ro.action_tm[t], ro.states_tm[t + 1], ro.reward_tm[t], ro.cost_tm[t])
             mark()

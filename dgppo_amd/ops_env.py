@@ -423,6 +423,60 @@ def team_action_fork(cfg: N.EnvCfg, st: State, a_pol, us, vs, out: State, action
     N.check(rc, "dgppo_env_team_action_fork")
 
 
+def team_action_fork_ids(cfg: N.EnvCfg, st: State, a_base, env_ids, us, vs, out: State, action_out, carry=None, carry_out=None,
+                         ids_dev=None):
+    """dgppo_env_team_action_fork_ids: team_action_fork for the envs env_ids of the dense state `st` (B envs) only, with the
+    joint action a_base [B, n, 2] — the action held after the shield rounds so far — in the place of the policy's.  Output env
+    (m * n + i) * P + p of the G = len(env_ids) * n * P in `out` is a copy of env env_ids[m]; row i of action_out [G, n, 2] is
+    candidate p (0: a_base[e, i] itself), every other row a_base[e]'s; carry [B * n, HC] rows of env e go to carry_out
+    [G * n, HC].  env_ids: a 1-D host array of ints in [0, B) (checked here; the kernel trusts it), or None for every env in
+    order.  ids_dev: the same list as an int32 device tensor, where the caller has uploaded it already.  Every refusal is raised
+    before anything is launched."""
+    from . import ops_nn as K
+    fn = "team_action_fork_ids"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no fork entry point")
+    n = cfg.n_agents
+    if not (torch.is_tensor(a_base) and a_base.ndim == 3):
+        raise ValueError(f"{fn}: a_base must be a [B, n, 2] tensor")
+    B = int(a_base.shape[0])
+    for name, t_ in (("us", us), ("vs", vs)):
+        if not (torch.is_tensor(t_) and t_.ndim == 1 and t_.numel() > 0):
+            raise ValueError(f"{fn}: {name} must be a non-empty 1-D tensor (sweep_axis)")
+    ids, M = K.env_id_list(fn, env_ids, B, unique=False)
+    P = 1 + int(us.numel()) * int(vs.numel())
+    G = M * n * P
+    operands = [("a_base", a_base, (B, n, 2)), ("action_out", action_out, (G, n, 2))]
+    for fields, src, dst in zip(record_fields(cfg), (st.step, st.env), (out.step, out.env)):
+        for name, shape in fields.items():
+            if src.get(name) is None:
+                raise ValueError(f"{fn}: the state has no {name}")
+            if dst.get(name) is None:
+                raise ValueError(f"{fn}: out has no {name}")
+            operands += [(name, src[name], (B,) + shape), (f"out.{name}", dst[name], (G,) + shape)]
+    HC = 0
+    if carry is not None:
+        if not (torch.is_tensor(carry) and carry.ndim == 2 and carry.shape[0] == B * n and carry.shape[1] >= 1):
+            raise ValueError(f"{fn}: carry must be [B * n, HC] = [{B * n}, HC]")
+        HC = int(carry.shape[1])
+        if carry_out is None:
+            raise ValueError(f"{fn}: carry_out is required with a carry")
+        operands += [("carry", carry, (B * n, HC)), ("carry_out", carry_out, (G * n, HC))]
+    K._shaped(fn, operands)
+    nu, nv = K._shield_axes(fn, us, vs)
+    ids = K.env_ids_device(fn, ids, ids_dev, a_base.device)
+    cast = cfg.is_lidar and cfg.n_obs > 0
+    s, e, o_s, o_e = st.step, st.env, out.step, out.env
+    rc = N.lib().dgppo_env_team_action_fork_ids(
+        C.byref(cfg), N.ptr(s["agent"], name="agent"), N.ptr(e["goal"], name="goal"), N.ptr(e.get("obst"), name="obst"),
+        N.ptr(s["hits"] if cast else None, name="hits"), N.ptr(a_base, name="a_base"), N.ptr(carry, name="carry"), HC, B,
+        N.ptr(ids, torch.int32, "env_ids"), M, N.ptr(us, name="us"), nu, N.ptr(vs, name="vs"), nv,
+        N.ptr(o_s["agent"], name="out.agent"), N.ptr(o_e["goal"], name="out.goal"), N.ptr(o_e.get("obst"), name="out.obst"),
+        N.ptr(o_s["hits"] if cast else None, name="out.hits"), N.ptr(action_out, name="action_out"),
+        N.ptr(carry_out if carry is not None else None, name="carry_out"), N.stream_ptr())
+    N.check(rc, "dgppo_env_team_action_fork_ids")
+
+
 def action_sweep_fork(cfg: N.EnvCfg, step: Dict[str, torch.Tensor], env: Dict[str, torch.Tensor], actions, frame_ids,
                       n_frames: int, agent_id: int, us, vs, out: State, action_out, carry=None, carry_st: int = 0, carry_out=None,
                       frame_max=None):

@@ -605,6 +605,89 @@ def lookahead_select(cost_tm, a_pol, us, vs, margin: float, action, index, flag,
     N.check(rc, "dgppo_lookahead_select")
 
 
+def env_id_list(fn: str, env_ids, n_env: int, unique: bool = True):
+    """the env list of the shield-round entry points, checked on the host -> (int32 host array or None, its length).  env_ids:
+    None (every env, in order) or a 1-D host array of ints in [0, n_env) — the kernels trust the list, so it is checked here,
+    where it costs no device sync — without repeats where `unique` (two workgroups would write one env's rows)."""
+    if env_ids is None:
+        return None, int(n_env)
+    if torch.is_tensor(env_ids):
+        if env_ids.is_cuda:
+            raise ValueError(f"{fn}: env_ids must be a host array (pass the device copy as ids_dev)")
+        env_ids = env_ids.numpy()
+    a = np.asarray(env_ids)
+    if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{fn}: env_ids must be a 1-D array of ints")
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= n_env):
+        raise ValueError(f"{fn}: env_ids outside [0, {n_env})")
+    if unique and np.unique(a).size != a.size:
+        raise ValueError(f"{fn}: env_ids repeats an env")
+    return np.ascontiguousarray(a, dtype=np.int32), int(a.size)
+
+
+def env_ids_device(fn: str, ids, ids_dev, device):
+    """env_id_list's host list on the device: ids_dev where the caller has uploaded it already (int32, dense, the same length),
+    else a fresh copy; None for no list"""
+    if ids is None:
+        if ids_dev is not None:
+            raise ValueError(f"{fn}: ids_dev without env_ids: the host list is what is checked")
+        return None
+    if ids_dev is None:
+        if torch.device(device).type != "cuda":
+            raise ValueError(f"{fn}: the operands must be CUDA tensors")
+        ids_dev = torch.from_numpy(ids).to(device)
+    _dense(fn, "ids_dev", ids_dev, (ids.size,), torch.int32)
+    return ids_dev
+
+
+def lookahead_reselect(cost_tm, env_ids, a_ref, us, vs, margin: float, mode: int, action, index, flag, joint, changed, s=None,
+                       ids_dev=None):
+    """dgppo_lookahead_reselect: the selection of one shield round on the envs env_ids (None: all, in order) of E.  cost_tm
+    [K, G, n, nh] are the costs of the K states after the forced step of the G = len(env_ids) * n * P what-if envs of
+    ops_env.team_action_fork_ids (the steps may be strided, each is dense).  a_ref [E, n, 2] is the policy's action, action
+    [E, n, 2] (in: the joint action held, candidate 0; out: the one held now) and index [E, n] int32 (in and out), flag [E, n],
+    joint / changed [E] int32 and, if given, s [E, n, P].  mode 0: every agent commits its pick; 1: the lowest-numbered agent that
+    wants to move moves alone.  The rule is stated next to the declaration in include/dgppo_hip.h.  env_ids / ids_dev: as in
+    env_id_list / env_ids_device; rows of envs not listed are not touched.  Every refusal is raised before anything is launched."""
+    fn = "lookahead_reselect"
+    if not (torch.is_tensor(a_ref) and a_ref.ndim == 3 and a_ref.shape[2] == 2 and a_ref.shape[1] >= 1):
+        raise ValueError(f"{fn}: a_ref must be a [E, n, 2] tensor")
+    E, n = int(a_ref.shape[0]), int(a_ref.shape[1])
+    if not (torch.is_tensor(cost_tm) and cost_tm.ndim == 4):
+        raise ValueError(f"{fn}: cost_tm must be a [K, G, n, nh] tensor")
+    K_, nh = int(cost_tm.shape[0]), int(cost_tm.shape[3])
+    if K_ < 1:
+        raise ValueError(f"{fn}: K must be >= 1")
+    if not 1 <= nh <= 3:
+        raise ValueError(f"{fn}: n_cost {nh} outside [1, 3]")
+    for name, t_ in (("us", us), ("vs", vs)):
+        if not (torch.is_tensor(t_) and t_.ndim == 1 and t_.numel() > 0):
+            raise ValueError(f"{fn}: {name} must be a non-empty 1-D tensor (sweep_axis)")
+    if int(mode) not in (0, 1):
+        raise ValueError(f"{fn}: mode must be 0 or 1 (got {mode})")
+    if np.isnan(float(margin)):
+        raise ValueError(f"{fn}: margin must not be NaN")
+    ids, M = env_id_list(fn, env_ids, E)
+    P = 1 + int(us.numel()) * int(vs.numel())
+    G = M * n * P
+    if tuple(cost_tm.shape[1:]) != (G, n, nh):
+        raise ValueError(f"{fn}: cost_tm: expected shape (K, {G}, {n}, {nh}), got {tuple(cost_tm.shape)}")
+    _shaped(fn, [("a_ref", a_ref, (E, n, 2)), ("cost_tm[0]", cost_tm[0], (G, n, nh)), ("action", action, (E, n, 2)),
+                 ("index", index, (E, n), torch.int32), ("flag", flag, (E, n), torch.int32), ("joint", joint, (E,), torch.int32),
+                 ("changed", changed, (E,), torch.int32)] + ([("s", s, (E, n, P))] if s is not None else []))
+    nu, nv = _shield_axes(fn, us, vs)
+    ids = env_ids_device(fn, ids, ids_dev, a_ref.device)
+    cost_st = int(cost_tm.stride(0)) if K_ > 1 else G * n * nh
+    if cost_st < G * n * nh:
+        raise ValueError(f"{fn}: the steps of cost_tm overlap (stride {cost_st} < {G * n * nh})")
+    rc = N.lib().dgppo_lookahead_reselect(
+        _p(cost_tm[0], "cost"), cost_st, K_, M, n, nh, _p(ids, "env_ids", torch.int32), _p(a_ref, "a_ref"), _p(us, "us"), nu,
+        _p(vs, "vs"), nv, float(margin), int(mode), _p(action, "action"), _p(index, "index", torch.int32),
+        _p(flag, "flag", torch.int32), _p(s, "s"), _p(joint, "joint", torch.int32), _p(changed, "changed", torch.int32),
+        N.stream_ptr())
+    N.check(rc, "dgppo_lookahead_reselect")
+
+
 def vmas_graph_feats(cfg: N.EnvCfg, agent, agent_se, agent_st, body, body_se, body_st, scene, env_ids, n_env, n_time,
                      Xa, efeat, emask, Fp):
     """dgppo_vmas_graph_feats: graph_feats for VMASReverseTransport (agent [.., n, 4] and body [.., 4] records addressed

@@ -110,6 +110,26 @@ class LookaheadShieldLog(NamedTuple):
     horizon: int
 
 
+class JointLookaheadShieldLog(NamedTuple):
+    """LookaheadShieldLog of `collect_lookahead_shielded(rounds >= 2)`: the picks were re-judged in rounds that roll the joint
+    action held (Engine.lookahead_select_rounds).  index is the grid number of the action held (0: the policy's), flag describes
+    that action (0 the policy's and admissible, 1 replaced and admissible, 2 not admissible), s is the fold of the step's last
+    round: candidate 0 there is the action the agent held in that round, everyone else playing the joint action held."""
+    policy_action: np.ndarray   # [B, T, n, 2]
+    action: np.ndarray          # [B, T, n, 2]
+    index: np.ndarray           # [B, T, n] int32
+    flag: np.ndarray            # [B, T, n] int32
+    s: np.ndarray               # [B, T, n, P]
+    us: np.ndarray              # [nu]
+    vs: np.ndarray              # [nv]
+    margin: float
+    horizon: int
+    joint: np.ndarray           # [B, T] int32: 2 the joint action played was rolled and is admissible for every agent, 1 rolled
+                                # and not admissible for some agent, 0 NOT rolled (an agent moved in the step's last round)
+    rounds_used: np.ndarray     # [B, T] int32: the rounds that judged the step, 1 .. rounds
+    rounds: int                 # the cap
+
+
 class ActionLandscape(NamedTuple):
     """The discrete control barrier condition of DGPPO (dgppo/algo/dgppo.py:246-250) with one agent's action swept over a grid
     in frames of an episode (`DGPPO.action_landscape`): cbf = (Vh_next - Vh) / dt + alpha * Vh, where Vh_next is the learned

@@ -234,3 +234,15 @@ def shield_stats(log) -> Dict[str, np.ndarray]:
     dev = np.sqrt(((np.clip(a, -1.0, 1.0) - np.clip(p, -1.0, 1.0)) ** 2).sum(axis=-1))
     return dict(intervention_frac=(flag != 0).reshape(B, -1).mean(axis=1), infeasible_frac=(flag == 2).reshape(B, -1).mean(axis=1),
                 mean_deviation=dev.reshape(B, -1).mean(axis=1))
+
+
+def joint_shield_stats(log) -> Dict[str, np.ndarray]:
+    """What the rounds of the lookahead shield reached per episode (trainer.data.JointLookaheadShieldLog, joint / rounds_used
+    [B, T]), each [B]: `joint_verified_frac` — the share of steps whose played joint action was rolled and found admissible for
+    every agent (joint == 2), `joint_unrolled_frac` — the share whose played joint action was not rolled (joint == 0: the
+    rounds ran out), `mean_rounds` — the mean number of rounds per step."""
+    joint, used = np.asarray(log.joint), np.asarray(log.rounds_used)
+    if joint.ndim != 2 or used.shape != joint.shape:
+        raise ValueError(f"joint_shield_stats: joint {joint.shape} / rounds_used {used.shape} must both be [B, T]")
+    return dict(joint_verified_frac=(joint == 2).mean(axis=1), joint_unrolled_frac=(joint == 0).mean(axis=1),
+                mean_rounds=used.astype(np.float64).mean(axis=1))

@@ -505,6 +505,40 @@ int32_t dgppo_lookahead_select(const float* cost, int64_t cost_st, int32_t K, in
                                const float* a_pol, const float* us, int32_t nu, const float* vs, int32_t nv, float margin,
                                float* action, int32_t* index, int32_t* flag, float* s, void* stream);
 
+/* dgppo_env_team_action_fork for a later round of the lookahead shield (Engine.lookahead_select_rounds): only the envs
+ * env_ids[0 .. n_ids) are forked, and the joint action the candidates are set into is the one HELD after the rounds so far.
+ * Output env g = (m*n + i)*P + p, G = n_ids*n*P, is a copy of env e = env_ids[m]; its joint action is a_base[e] with row i
+ * replaced by candidate p for p > 0 — candidate 0 is a_base[e, i] itself — and its carry rows are env e's.  The sources stay
+ * dense over all n_env envs (operands as above, a_base [n_env, n, 2] in the place of a_pol); env_ids == NULL is the identity
+ * and needs n_ids == n_env, which makes the call dgppo_env_team_action_fork's, word for word.  The caller guarantees
+ * 0 <= env_ids[m] < n_env (the binding checks it).  Words are copied as they are, nothing is clipped: the step clips
+ * (clip_action, env/base.py).  Same device code, same refusals.  The reference ships no runtime filter.                      */
+int32_t dgppo_env_team_action_fork_ids(const dgppo_env_cfg* cfg, const float* agent, const float* goal, const float* obst,
+                                       const float* hits, const float* a_base, const float* carry, int32_t HC, int32_t n_env,
+                                       const int32_t* env_ids, int32_t n_ids, const float* us, int32_t nu, const float* vs,
+                                       int32_t nv, float* agent_out, float* goal_out, float* obst_out, float* hits_out,
+                                       float* action_out, float* carry_out, void* stream);
+
+/* The selection of one round of the lookahead shield's rounds, on the what-if envs of dgppo_env_team_action_fork_ids.  Per listed
+ * env e = env_ids[m] (NULL: e = m) and agent i, s[p] is dgppo_lookahead_select's fold (the worst own-row cost, get_cost,
+ * lidar_env/base.py:203-205, NaN-propagating) on what-if env (m*n + i)*P + p.  Candidate 0 is clip(action[e, i]), the action the
+ * agent holds (clip_action, env/base.py).  Pick: 0 if s[0] <= -margin; else the admissible candidate nearest to clip(a_ref[e, i]),
+ * the policy's action (du*du + dv*dv in fp32, a NaN distance counts as +inf, lowest index on ties); else the smallest s (lowest
+ * index on ties, NaN skipped, 0 if every s is NaN).  Commit: mode 0 — every agent commits its pick; mode 1 — only the
+ * lowest-numbered agent whose pick is not 0 commits, everyone else keeps candidate 0.  A committing agent with pick > 0 writes the
+ * clipped candidate to action [n_env, n, 2] and the pick to index [n_env, n]; an agent that keeps candidate 0 writes
+ * clip(action[e, i]) back and leaves index as it was, so index is the grid number of what is held (0: the policy's action).
+ * flag [n_env, n] describes the action now held: 2 if its s is not admissible, else 0 if index == 0, else 1.  changed[e] = 1 iff
+ * some agent committed a pick > 0, else 0.  joint[e] = 0 when changed (the held joint action was not rolled), 1 when unchanged and
+ * some s[.., 0] is not admissible (rolled, not safe, nothing better), 2 when unchanged and all are (rolled and admissible for
+ * every agent).  s [n_env, n, P] may be NULL.  Rows of envs that are not listed are not touched; env_ids must not repeat an env.
+ * One workgroup per env settles the team after one barrier: the result does not depend on scheduling.  K >= 1,
+ * 1 <= n_cost <= 3, n_agents <= 4096, margin no NaN, mode in {0, 1}.  The reference ships no runtime filter.                  */
+int32_t dgppo_lookahead_reselect(const float* cost, int64_t cost_st, int32_t K, int32_t n_ids, int32_t n_agents, int32_t n_cost,
+                                 const int32_t* env_ids, const float* a_ref, const float* us, int32_t nu, const float* vs,
+                                 int32_t nv, float margin, int32_t mode, float* action, int32_t* index, int32_t* flag, float* s,
+                                 int32_t* joint, int32_t* changed, void* stream);
+
 /* The what-if environments of an action rollout landscape: ONE agent's action swept in recorded frames, as a dense env state the
  * step kernels run on.  Env g = (f*nv + iv)*nu + iu, G = n_frames*nv*nu (the numbering of dgppo_graph_feats_action_sweep), is a
  * copy of frame fid (fid = frame_ids ? frame_ids[f] : f; operands and frame strides as in dgppo_env_sweep_fork) of ONE

@@ -31,6 +31,12 @@ candidate played and the policy rolled H steps on, and an action is admissible w
 steps is <= -M (`--shield-margin M`).  The lines, `test_log.csv`, the landscapes and the video then describe those episodes, and
 `{stamp}_{name}_shield.npz` holds `policy_action`, `action`, `index`, `flag`, `s` (the worst rolled cost of every candidate),
 `us`, `vs`, `margin`, `horizon` and the three statistics.  `--shield-horizon 0` (the default) is the one-step barrier shield.
+`--shield-rounds R` (with `--shield --shield-horizon H`, R >= 2) re-judges the picks jointly, up to R rounds per step
+(`collect_lookahead_shielded(rounds=R)`): the joint action the agents hold is rolled as everyone's candidate 0, and in every
+round after the first one agent per environment may still move.  One more line per episode says for how many steps the joint
+action played was rolled and admissible for every agent (joint_verified_frac), for how many it was not rolled because the
+rounds ran out (joint_unrolled_frac), and how many rounds a step took (mean_rounds); `{stamp}_{name}_shield.npz` also holds
+`joint`, `rounds_used`, `rounds` and the three numbers.  `--shield-rounds 1` (the default) is the shield without rounds.
 `--action-rollout-landscape AGENT` measures what the actions `--action-landscape` judges lead to (`action_rollout_landscape`;
 every algorithm has it): in every frame that agent plays each action of the `--landscape-grid`-squared grid of [-1, 1]^2 for one
 step, everyone else their recorded action, and the deterministic policy is rolled on until the costs of the
@@ -80,7 +86,8 @@ def test(args):
     shield_log = None
     if args.shield and args.shield_horizon >= 1:
         ro, shield_log = algo.collect_lookahead_shielded(keys, env=env, grid=args.shield_grid, margin=args.shield_margin,
-                                                         horizon=args.shield_horizon)
+                                                         horizon=args.shield_horizon,
+                                                         **({"rounds": args.shield_rounds} if args.shield_rounds > 1 else {}))
     elif args.shield:
         ro, shield_log = algo.collect_shielded(keys, env=env, grid=args.shield_grid, margin=args.shield_margin)
     elif args.stochastic:
@@ -101,6 +108,14 @@ def test(args):
             print(f"epi: {i}, shield: stepped in for {sh['intervention_frac'][i] * 100:.3f}% of the actions (intervention_frac), "
                   f"found nothing admissible for {sh['infeasible_frac'][i] * 100:.3f}% (infeasible_frac), moved the action by "
                   f"{sh['mean_deviation'][i]:.4f} on average (mean_deviation)")
+    joint = None
+    if shield_log is not None and args.shield_rounds > 1:
+        joint = EV.joint_shield_stats(shield_log)
+        for i in range(len(keys)):
+            print(f"epi: {i}, shield rounds: the joint action played was rolled and admissible for every agent in "
+                  f"{joint['joint_verified_frac'][i] * 100:.3f}% of the steps (joint_verified_frac), not rolled in "
+                  f"{joint['joint_unrolled_frac'][i] * 100:.3f}% (joint_unrolled_frac), {joint['mean_rounds'][i]:.3f} rounds per "
+                  f"step (mean_rounds)")
     if args.log:
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(EV.csv_line(env, args.epi, agg))
@@ -118,6 +133,9 @@ def test(args):
                 out = videos_dir / f"{stamp}_{name}_shield.npz"
                 if args.shield_horizon >= 1:
                     per_epi = {k: getattr(shield_log, k)[i] for k in ("policy_action", "action", "index", "flag", "s")}
+                    if joint is not None:
+                        per_epi.update(joint=shield_log.joint[i], rounds_used=shield_log.rounds_used[i],
+                                       rounds=shield_log.rounds, **{k: v[i] for k, v in joint.items()})
                     np.savez(out, us=shield_log.us, vs=shield_log.vs, margin=shield_log.margin, horizon=shield_log.horizon,
                              **per_epi, **{k: v[i] for k, v in sh.items()})
                 else:
@@ -226,13 +244,16 @@ LOOKAHEAD_FLAGS = [(("--shield-horizon",), "int", 0)]
 # what one agent's actions lead to, measured (action_rollout_landscape; every algorithm has it): each action of the
 # --landscape-grid grid played for one step, then the policy rolled until --rollout-horizon further costs are known, per episode
 ACTION_ROLLOUT_FLAGS = [(("--action-rollout-landscape",), "int", None)]
+# with --shield --shield-horizon H: re-judge the picks jointly, up to R rounds per step, one mover per round after the first
+# (collect_lookahead_shielded(rounds=R)); 1: the shield without rounds
+ROUNDS_FLAGS = [(("--shield-rounds",), "int", 1)]
 
 
 def build_parser() -> argparse.ArgumentParser:
     types = {"int": int, "str": str, "float": float}
     ap = argparse.ArgumentParser(description=__doc__)
     for names, kind, default in (FLAGS + COST_FLAGS + ACTION_FLAGS + SHIELD_FLAGS + ROLLOUT_FLAGS + LOOKAHEAD_FLAGS
-                                 + ACTION_ROLLOUT_FLAGS):
+                                 + ACTION_ROLLOUT_FLAGS + ROUNDS_FLAGS):
         if kind == "flag":
             ap.add_argument(*names, action="store_true", default=False)
         elif kind.startswith("req:"):
@@ -252,6 +273,10 @@ def main(argv=None):
         raise SystemExit(f"--shield-horizon must be >= 0 (got {args.shield_horizon})")
     if args.shield_horizon >= 1 and not args.shield:
         raise SystemExit("--shield-horizon needs --shield: it sets how far the shield looks ahead")
+    if args.shield_rounds < 1:
+        raise SystemExit(f"--shield-rounds must be >= 1 (got {args.shield_rounds})")
+    if args.shield_rounds > 1 and not (args.shield and args.shield_horizon >= 1):
+        raise SystemExit("--shield-rounds needs --shield and --shield-horizon >= 1: the rounds re-judge the lookahead shield's picks")
     return test(args)
 
 

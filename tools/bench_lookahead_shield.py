@@ -16,9 +16,14 @@ G = B * n * P = 16 640 what-if envs per step), horizons H = 8 and 16:
      shielded rollout is split with device events into policy forward, fork + forced step, policy steps, select and the step
      that counts, per step of the episode.
 
+  4. with --rounds R >= 2 (Engine.lookahead_select_rounds): part 3's total again with rollout_lookahead_shielded(rounds=R) at
+     --margin, alternating with the rollout without rounds at the same margin: ms per real step of both, the rounds a step
+     used and what `joint` says.  The blocks of a round vary with the active list, so there is no split by events.
+
 Device events, --repeats repeats after a warm-up; median and spread.  Writes profiles/lookahead_shield.json.
 
-  python tools/bench_lookahead_shield.py [--repeats 5] [--grid 8] [--steps 16] [--horizons 8 16] [--out ...]"""
+  python tools/bench_lookahead_shield.py [--repeats 5] [--grid 8] [--steps 16] [--horizons 8 16] [--rounds 1] [--margin 0]
+                                         [--out ...]"""
 import argparse
 import json
 import os
@@ -59,6 +64,8 @@ def main():
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--envs", type=int, default=32)
     ap.add_argument("--horizons", type=int, nargs="+", default=[8, 16])
+    ap.add_argument("--rounds", type=int, default=1)
+    ap.add_argument("--margin", type=float, default=0.0)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "lookahead_shield.json"))
     args = ap.parse_args()
     from dgppo_amd import _native as N, engine as EN, init, ops_algo as OA, ops_env as OE, ops_nn as K
@@ -131,7 +138,7 @@ def main():
     # ---- 2. and 3. per horizon ----
     names = ("policy_forward", "fork_and_forced_step", "policy_steps", "select", "final_step")
     plain = lambda: timed(lambda: eng.rollout(seeds, False))
-    res["select"], res["rollout"] = {}, {}
+    res["select"], res["rollout"], res["rounds"] = {}, {}, {}
     for H in args.horizons:
         # a block record as one real step leaves it
         recs = []
@@ -200,6 +207,29 @@ def main():
             env_steps_per_second=G * (H + 1) * T / (float(np.median(S_tot)) * 1e-3),
             note="eager launches on both sides; the split is device time between events, the totals include the host's launch "
                  "gaps")
+        if args.rounds >= 2:
+            def rolled(R):
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                _, log = eng.rollout_lookahead_shielded(seeds, dus, dvs, H, margin=args.margin, rounds=R)
+                t1.record()
+                torch.cuda.synchronize()
+                return t0.elapsed_time(t1), log
+            rolled(1); rolled(args.rounds)                                    # warm-up: the block record of the rounds
+            one, many = [], []
+            for _ in range(args.repeats):
+                one.append(rolled(1)[0])
+                ms, log = rolled(args.rounds)
+                many.append(ms)
+            used, joint = log["rounds_used"].cpu().numpy(), log["joint"].cpu().numpy()
+            res["rounds"][f"H{H}"] = dict(
+                rounds=args.rounds, margin=args.margin, without_rounds_ms=spread(one), with_rounds_ms=spread(many),
+                without_rounds_ms_per_step=float(np.median(one)) / T, with_rounds_ms_per_step=float(np.median(many)) / T,
+                with_over_without=float(np.median(many)) / float(np.median(one)), mean_rounds_per_env_step=float(used.mean()),
+                env_rounds_per_step=float(used.sum()) / T, rounds_used_histogram=np.bincount(used.ravel(), minlength=args.rounds + 1).tolist(),
+                joint_unrolled_rolled_unsafe_verified=np.bincount(joint.ravel(), minlength=3).tolist(),
+                replaced_frac=float((log["index"] != 0).float().mean()),
+                note="eager launches, one host sync per round but the last; totals include the host's launch gaps")
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
@@ -209,7 +239,8 @@ def main():
         select={h: short(v, ("kernel_ms", "composition_device_ms", "composition_host_ms", "composition_over_kernel"))
                 for h, v in res["select"].items()},
         rollout={h: dict(short(v, ("shielded_ms", "plain_deterministic_ms", "shielded_ms_per_step")),
-                         split={k_: x["median"] for k_, x in v["split_ms_per_step"].items()}) for h, v in res["rollout"].items()})))
+                         split={k_: x["median"] for k_, x in v["split_ms_per_step"].items()}) for h, v in res["rollout"].items()},
+        rounds={h: {k_: x for k_, x in v.items() if not isinstance(x, (dict, str))} for h, v in res["rounds"].items()})))
 
 
 if __name__ == "__main__":
