@@ -86,8 +86,11 @@ __device__ inline void step_state(const float* x, float u0, float u1, const dgpp
 }
 
 // get_cost (lidar_env/base.py:180-207, mpe/base.py:164-191): a margin m becomes m -/+ 0.5 before the clip, which each
-// caller applies (MPE clips only from below)
+// caller applies (MPE clips only from below, through clip_lo_nan: like jnp.clip(cost, a_min=-1.0), mpe/base.py:189, that
+// clip keeps a NaN, where fmaxf alone would report the safest cost there is)
 __device__ inline float cost_value(float m) { return (m <= 0.0f) ? m - 0.5f : m + 0.5f; }
+// one-sided clampf_nan: a NaN stays a NaN, every other input gets the bits of fmaxf(v, lo)
+__device__ inline float clip_lo_nan(float v, float lo) { return (v != v) ? v : fmaxf(v, lo); }
 
 // get_reward (lidar_spread.py:35-52 and its siblings) from the three sums in index order: distances to the ng reward
 // goals, goals not reached, squared action norms of the n agents

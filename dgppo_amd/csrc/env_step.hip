@@ -148,7 +148,7 @@ __global__ void env_step_kernel(StepArgs a) {
         }
         float c0 = cost_value(agent_cost), c1 = cost_value(obs_cost);
         if (lidar || c.kind == DGPPO_ENV_MPE_CONNECT_SPREAD) { c0 = clampf_nan(c0, -1.0f, 1.0f); c1 = clampf_nan(c1, -1.0f, 1.0f); }
-        else { c0 = fmaxf(c0, -1.0f); c1 = fmaxf(c1, -1.0f); }   // mpe/base.py:189 clips only from below
+        else { c0 = clip_lo_nan(c0, -1.0f); c1 = clip_lo_nan(c1, -1.0f); }   // mpe/base.py:189 clips only from below
         a.cost[((size_t)b * n + i) * c.n_cost] = c0;
         a.cost[((size_t)b * n + i) * c.n_cost + 1] = c1;
         s_md[i] = md;

@@ -449,7 +449,7 @@ __global__ void __launch_bounds__(COST_NT) cost_sweep_kernel(CostSweepArgs a) {
       m = s_pw[p];
     }
     const float v = cost_value(m);
-    out[idx] = clip_hi ? clampf_nan(v, -1.0f, 1.0f) : ((v != v) ? v : fmaxf(v, -1.0f));
+    out[idx] = clip_hi ? clampf_nan(v, -1.0f, 1.0f) : clip_lo_nan(v, -1.0f);
   }
 }
 
