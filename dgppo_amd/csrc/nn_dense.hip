@@ -424,16 +424,38 @@ struct DenseBwdWArgs {
 // add their accumulators through the tile LDS once the chunks are done, and group 0 writes the workgroup's ONE slab: a
 // CU that kept NG resident workgroups busy wrote NG slabs for the second stage to read back.
 // DX: the same pass also forms dX[32,K] = dY W^T of every tile (dgppo_dense_bwd_xw; K = KT*16 and N = NT*16 exactly, 16-byte
-// aligned operands: the launcher's condition).  The product runs per wave on its output column tiles x both
-// 16-row tiles, reduction over n - kt counted from the LAST wave (kt = 3 - w, 7 - w, ...), so that with KT = 9 the wave that
-// has three row tiles of dW has two column tiles of dX and the other way round: five products on the longest wave, not six.
-// W^T stays in registers for the whole launch (KTW * NT float4 per lane); the dY operand is
-// read from memory again in the MFMA A layout (lane (li, lq) = row li, the four columns 16s + 4lq ..: one float4 per 16
-// columns, the k-steps taking n in that order on both operands) - the rows were just fetched for the LDS tile, so these are
-// cache hits, and a column walk of the row-major LDS tile would be an 8-way bank conflict.  The ReLU mask of the `+=` form is
-// X itself: the LDS tile.
+// aligned operands: the launcher's condition).  The tile's 2 KT products (16 rows x 16 columns, reduction over n) are dealt
+// over the group's four waves so that every wave issues the same number of MFMAs per tile (XwDeal below; a wave without a
+// KTW-th row tile of dW skips it instead of redoing the last one).  A wave keeps W^T in registers only for the column tiles of
+// its own units (at most kw() * NT float4 per lane); the dY operand is read from memory again in the fragment layout (lane
+// (li, lq) = row li, the four columns 16s + 4lq ..: one float4 per 16 columns, the k-steps taking n in that order on both
+// operands) - the rows were just fetched for the LDS tile, so these are cache hits, and a column walk of the row-major LDS
+// tile would be an 8-way bank conflict.  The product is formed transposed (W dY^T), which leaves a lane with 16 contiguous bytes
+// of one dX row; the `+=` form adds the old dX (requested in that shape with the dY operand, at the top of the round) and applies
+// the ReLU mask, X itself: the LDS tile.  The units go to a dX tile in LDS, and the tile leaves one round later as 16-byte
+// stores of whole rows by all threads of the group; a second LDS barrier per round separates that read-out from the next units.
 #define BW_ROWS 32
-template <int NT, int KT, int NG, bool DX = false>
+// DX: how a group's four waves share the 2 KT products (16-row tile mt, 16-column tile kt) of a dX tile, unit u = 2 kt + mt.
+// Wave w owns nkt(w) row tiles of dW, 8 NT MFMAs per tile each against 4 NT per unit: with units(w) = KT - 2 nkt(w) every
+// wave issues KT * 4 NT MFMAs per tile (KT = 9: 3, 5, 5, 5 units; KT = 3: 1, 1, 1, 3; KT = 2: 0, 0, 2, 2), and the units of a
+// wave are consecutive, so that it keeps W^T for at most kw() column tiles.
+template <int KT>
+struct XwDeal {
+  static constexpr int nkt(int w) { return w < KT ? (KT - w + 3) / 4 : 0; }
+  static constexpr int units(int w) { return KT - 2 * nkt(w); }
+  static constexpr int start(int w) { int s = 0; for (int v = 0; v < w; ++v) s += units(v); return s; }
+  static constexpr int kw() {
+    int m = 1;
+    for (int w = 0; w < 4; ++w) {
+      const int k = units(w) > 0 ? ((start(w) + units(w) - 1) >> 1) - (start(w) >> 1) + 1 : 0;
+      m = k > m ? k : m;
+    }
+    return m;
+  }
+};
+#define XW_DL(KT) ((KT) * 16 + 4)   // row stride of the dX tile in LDS: = 4 (mod 8) floats, 16-byte fragment stores hit 8 x 4 banks
+
+template <int NT, int KT, int NG, bool DX = false, bool ACCM = false>
 __global__ void __launch_bounds__(256 * NG) dense_bwd_w_kernel(DenseBwdWArgs a) {
   extern __shared__ float sm_wg[];
   constexpr int KTW = (KT + 3) / 4;
@@ -465,77 +487,114 @@ __global__ void __launch_bounds__(256 * NG) dense_bwd_w_kernel(DenseBwdWArgs a) 
   float4 pfx[PFX], pfy[PFY], csum[PFY];
 #pragma unroll
   for (int u = 0; u < PFY; ++u) csum[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-  // DX: B[kk = lq][j = li] of k-step (s, e) = W[kt*16 + li][16 s + 4 lq + e]; A of the same step = dY[row li][16 s + 4 lq + e]
-  float4 wreg[DX ? KTW : 1][DX ? NT : 1], ya[DX ? 2 : 1][DX ? NT : 1];
+  // DX: the product is formed TRANSPOSED, dX^T[16 k, 16 m] = W dY^T: A[i = li][kk = lq] of k-step (s, e) = W[kt*16 + li][16 s + 4 lq + e],
+  // B[kk = lq][j = li] of the same step = dY[row li][16 s + 4 lq + e]; the C/D layout (row i = 4 lq + reg, col j = li) then leaves
+  // a lane with dX[row li][kt*16 + 4 lq .. + 3]: 16 contiguous bytes of one row
+  using D = XwDeal<KT>;
+  constexpr int KW = DX ? D::kw() : 1;
+  constexpr int Dl = XW_DL(KT);
+  const int wv = __builtin_amdgcn_readfirstlane(wave);
+  const int u0 = wv == 0 ? D::start(0) : wv == 1 ? D::start(1) : wv == 2 ? D::start(2) : D::start(3);
+  const int u1 = u0 + (wv == 0 ? D::units(0) : wv == 1 ? D::units(1) : wv == 2 ? D::units(2) : D::units(3));
+  const int kb = u0 >> 1;               // the wave's first column tile of dX
+  float* dxs = sm_wg + NG * 2 * BUF + grp * BW_ROWS * Dl;     // the group's dX tile [32][Dl], behind every group's X / dY buffers
+  float4 wreg[KW][DX ? NT : 1], old[ACCM ? KW : 1][ACCM ? 2 : 1];
   if constexpr (DX) {
+    static_assert(KT >= 2 && D::start(3) + D::units(3) == 2 * KT, "dense_bwd_xw: the waves' units cover the dX tile");
 #pragma unroll
-    for (int i = 0; i < KTW; ++i) {
-      int kt = (3 - wave) + 4 * i;
-      kt = kt < KT ? kt : KT - 1;
+    for (int c = 0; c < KW; ++c) {
+      const int kt = kb + c < KT ? kb + c : KT - 1;
 #pragma unroll
       for (int s = 0; s < NT; ++s)
-        wreg[i][s] = *reinterpret_cast<const float4*>(a.W + (size_t)(kt * 16 + li) * a.ldwp + 16 * s + 4 * lq);
+        wreg[c][s] = *reinterpret_cast<const float4*>(a.W + (size_t)(kt * 16 + li) * a.ldwp + 16 * s + 4 * lq);
     }
   }
-  auto fetch_a = [&](int m0) {          // DX: the dY rows of tile m0 in the A layout (rows clamped; stores are masked)
-    if constexpr (DX) {
+  auto fetch_old = [&](int m0) {        // ACCM: the old dX of the wave's units in the fragment shape (rows clamped; stores are masked)
+    if constexpr (ACCM) {
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
         int row = m0 + mt * 16 + li;
         row = row < a.M ? row : a.M - 1;
 #pragma unroll
-        for (int s = 0; s < NT; ++s) ya[mt][s] = *reinterpret_cast<const float4*>(a.dY + (size_t)row * a.ldy + 16 * s + 4 * lq);
+        for (int c = 0; c < KW; ++c) {
+          const int u = 2 * (kb + c) + mt;
+          if (u >= u0 && u < u1) old[c][mt] = *reinterpret_cast<const float4*>(a.dX + (size_t)row * a.lddx + (kb + c) * 16 + 4 * lq);
+        }
       }
     }
   };
-  auto dx_tile = [&](int m0, int b) {   // DX: dX rows m0 .. m0+31 (C/D layout: col = li, row = lq * 4 + reg); b = the X tile's buffer
+  auto dx_tile = [&](int b) {           // DX: the wave's units of the dX tile -> dxs; b = the X tile's buffer (the mask of ACCM)
     if constexpr (DX) {
-      const float* xs = sm + b * BUF;
+      [[maybe_unused]] const float* xs = sm + b * BUF;
+      if (u1 == u0) return;
+      // the dY operand from the row-major LDS tile: 16 bytes per lane, a 2-way bank conflict (rows li and li + 4 of a 16-lane
+      // group share banks at a stride of 16 mod 32 floats) on NT reads per 16 rows
+      const float* ys = sm + b * BUF + BW_ROWS * Kl + li * Nl + 4 * lq;
+      f32x4 ya[2][NT];
 #pragma unroll
-      for (int i = 0; i < KTW; ++i) {
-        const int kt = (3 - wave) + 4 * i;
-        if (kt >= KT) continue;
-        const int col = kt * 16 + li;
-        float old[2][4];
-        if (a.acc_mask) {
+      for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-          for (int mt = 0; mt < 2; ++mt)
+        for (int s = 0; s < NT; ++s) ya[mt][s] = *reinterpret_cast<const f32x4*>(ys + mt * 16 * Nl + 16 * s);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              int row = m0 + mt * 16 + lq * 4 + r;
-              row = row < m_end ? row : m_end - 1;
-              old[mt][r] = a.dX[(size_t)row * a.lddx + col];
-            }
-        }
+      for (int c = 0; c < KW; ++c)
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
+          const int u = 2 * (kb + c) + mt;
+          if (u < u0 || u >= u1) continue;
           f32x4 dx = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int s = 0; s < NT; ++s) {
-            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[mt][s].x, wreg[i][s].x, dx, 0, 0, 0);
-            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[mt][s].y, wreg[i][s].y, dx, 0, 0, 0);
-            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[mt][s].z, wreg[i][s].z, dx, 0, 0, 0);
-            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(ya[mt][s].w, wreg[i][s].w, dx, 0, 0, 0);
+            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[c][s].x, ya[mt][s][0], dx, 0, 0, 0);
+            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[c][s].y, ya[mt][s][1], dx, 0, 0, 0);
+            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[c][s].z, ya[mt][s][2], dx, 0, 0, 0);
+            dx = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[c][s].w, ya[mt][s][3], dx, 0, 0, 0);
           }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int rl = mt * 16 + lq * 4 + r;
-            float v = dx[r];
-            if (a.acc_mask) {
-              v += old[mt][r];
-              v = (xs[rl * Kl + col] > 0.0f) ? v : 0.0f;
-            }
-            if (m0 + rl < m_end) a.dX[(size_t)(m0 + rl) * a.lddx + col] = v;
+          const int rl = mt * 16 + li, col = (kb + c) * 16 + 4 * lq;
+          if constexpr (ACCM) {
+            const float4 x = *reinterpret_cast<const float4*>(xs + rl * Kl + col);
+            const float4 o = old[c][mt];
+            dx[0] = (x.x > 0.0f) ? o.x + dx[0] : 0.0f; dx[1] = (x.y > 0.0f) ? o.y + dx[1] : 0.0f;
+            dx[2] = (x.z > 0.0f) ? o.z + dx[2] : 0.0f; dx[3] = (x.w > 0.0f) ? o.w + dx[3] : 0.0f;
           }
+          *reinterpret_cast<f32x4*>(dxs + rl * Dl + col) = dx;
         }
+    }
+  };
+#define DGPPO_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+  // DX: the finished dX tile leaves as whole rows, 16 bytes per thread, by all threads of the group: dxs -> registers before a
+  // barrier (the waves' next units overwrite dxs behind it), registers -> memory after it.  m0 = m_begin - 32 in round 0: no row
+  // passes the mask
+  auto rows_out = [&](int m0, bool in_loop) {
+    if constexpr (DX) {
+      // RPP whole rows per pass, thread (r0, q) = (tid / XQ, tid % XQ) of each: one LDS address and one row pointer per thread,
+      // the passes differ by compile-time offsets (rows past the tile's 32 are clamped for the read and masked for the store)
+      constexpr int RPP = 256 / XQ, NP = (BW_ROWS + RPP - 1) / RPP;
+      const int r0 = tid / XQ, q = tid - r0 * XQ;
+      const bool lane_ok = r0 < RPP;
+      const float* src = dxs + (lane_ok ? r0 : 0) * Dl + 4 * q;
+      f32x4 q4[NP];                     // (a vector type: float4 copies out of LDS would keep the array in scratch)
+#pragma unroll
+      for (int u = 0; u < NP; ++u)
+        q4[u] = *reinterpret_cast<const f32x4*>(src + (u * RPP + RPP <= BW_ROWS ? u * RPP : BW_ROWS - RPP) * Dl);
+      if (in_loop) DGPPO_LDS_BARRIER();
+      float* dst = a.dX + (size_t)(m0 + r0) * a.lddx + 4 * q;
+#pragma unroll
+      for (int u = 0; u < NP; ++u) {
+        // the last pass re-reads rows of the pass before (its window is shifted up to end at row 31): it stores only the new ones
+        constexpr int kShift = NP * RPP - BW_ROWS;
+        const int r = (u == NP - 1 ? u * RPP - kShift : u * RPP) + r0;
+        const bool fresh = u < NP - 1 || r0 >= kShift;
+        if (lane_ok && fresh && m0 + r >= m_begin && m0 + r < m_end)
+          *reinterpret_cast<f32x4*>(dst + (ptrdiff_t)(u == NP - 1 ? u * RPP - kShift : u * RPP) * a.lddx) = q4[u];
       }
     }
   };
 
+  int tl = tid;                         // tid as fetch / commit see it (DX: made opaque once per round, see the loop)
   auto fetch = [&](int m0) {            // global -> registers (rows clamped; masking happens in commit)
 #pragma unroll
     for (int u = 0; u < PFX; ++u) {
-      int idx = u * 256 + tid;
+      int idx = u * 256 + tl;
       idx = idx < BW_ROWS * XQ ? idx : BW_ROWS * XQ - 1;
       const int r = idx / XQ, q = idx - r * XQ;
       int row = m0 + r;
@@ -544,7 +603,7 @@ __global__ void __launch_bounds__(256 * NG) dense_bwd_w_kernel(DenseBwdWArgs a) 
     }
 #pragma unroll
     for (int u = 0; u < PFY; ++u) {
-      int idx = u * 256 + tid;
+      int idx = u * 256 + tl;
       idx = idx < BW_ROWS * YQ ? idx : BW_ROWS * YQ - 1;
       const int r = idx / YQ, q = idx - r * YQ;
       int row = m0 + r;
@@ -557,7 +616,7 @@ __global__ void __launch_bounds__(256 * NG) dense_bwd_w_kernel(DenseBwdWArgs a) 
     float* ys = xs + BW_ROWS * Kl;
 #pragma unroll
     for (int u = 0; u < PFX; ++u) {
-      const int idx = u * 256 + tid;
+      const int idx = u * 256 + tl;
       const int r = idx / XQ, q = idx - r * XQ;
       const bool ok = (m0 + r < m_end) && (q < K4);
       const float4 v = ok ? pfx[u] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -565,7 +624,7 @@ __global__ void __launch_bounds__(256 * NG) dense_bwd_w_kernel(DenseBwdWArgs a) 
     }
 #pragma unroll
     for (int u = 0; u < PFY; ++u) {
-      const int idx = u * 256 + tid;
+      const int idx = u * 256 + tl;
       const int r = idx / YQ, q = idx - r * YQ;
       const bool ok = (m0 + r < m_end) && (q < N4) && (idx < BW_ROWS * YQ);
       const float4 v = ok ? pfy[u] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -585,28 +644,30 @@ __global__ void __launch_bounds__(256 * NG) dense_bwd_w_kernel(DenseBwdWArgs a) 
       ys[r * Nl + c] = (m0 + r < m_end && c < N) ? a.dY[(size_t)(m0 + r) * a.ldy + c] : 0.0f;
     }
   };
+  // the first NA of the wave's KTW row tiles x all NT column tiles over the tile's 8 four-row slabs
+#define DGPPO_BW_COMPUTE(NA)                                                                                                  \
+  _Pragma("unroll") for (int s4 = 0; s4 < BW_ROWS / 4; ++s4) {                                                                \
+    float bv[NT], av[(NA) > 0 ? (NA) : 1];                                                                                    \
+    _Pragma("unroll") for (int t = 0; t < NT; ++t) bv[t] = ys[s4 * 4 * Nl + t * 16];                                         \
+    _Pragma("unroll") for (int i = 0; i < (NA); ++i) {                                                                        \
+      int kt = wave + 4 * i;                                                                                                  \
+      kt = kt < KT ? kt : KT - 1;                              /* surplus waves redo the last tile (never written back) */    \
+      av[i] = xs[s4 * 4 * Kl + kt * 16];                                                                                      \
+    }                                                                                                                         \
+    _Pragma("unroll") for (int i = 0; i < (NA); ++i)                                                                          \
+      _Pragma("unroll") for (int t = 0; t < NT; ++t)                                                                          \
+        acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[t], acc[i][t], 0, 0, 0);                                   \
+  }
+  // DX: a wave without a KTW-th row tile skips it (its MFMAs are dealt to dX units instead: XwDeal)
+  const bool surplus = DX && wv + 4 * (KTW - 1) >= KT;
   auto compute = [&](int b) {
     const float* xs = sm + b * BUF + lq * Kl + li;
     const float* ys = sm + b * BUF + BW_ROWS * Kl + lq * Nl + li;
-#pragma unroll
-    for (int s4 = 0; s4 < BW_ROWS / 4; ++s4) {
-      float bv[NT], av[KTW];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) bv[t] = ys[s4 * 4 * Nl + t * 16];
-#pragma unroll
-      for (int i = 0; i < KTW; ++i) {
-        int kt = wave + 4 * i;
-        kt = kt < KT ? kt : KT - 1;                            // surplus waves redo the last tile (never written back)
-        av[i] = xs[s4 * 4 * Kl + kt * 16];
-      }
-#pragma unroll
-      for (int i = 0; i < KTW; ++i)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) acc[i][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[t], acc[i][t], 0, 0, 0);
-    }
+    if (DX && surplus) { DGPPO_BW_COMPUTE(KTW - 1) }
+    else { DGPPO_BW_COMPUTE(KTW) }
   };
-#define DGPPO_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-  float colsum = 0.0f;                  // scalar path only
+#undef DGPPO_BW_COMPUTE
+  float colsum = 0.0f;                 // scalar path only
   // DX has no scalar path (it would form no dX): the host launches it only where bwd_w_vec() holds, which is `vec`
   if (DX || vec) {
     fetch(m_begin);
@@ -614,15 +675,20 @@ __global__ void __launch_bounds__(256 * NG) dense_bwd_w_kernel(DenseBwdWArgs a) 
     __syncthreads();
     int cur = 0;
     for (int it = 0, m0 = m_begin; it < n_tiles; ++it, m0 += BW_ROWS) {
-      fetch_a(m0);
+      // DX: what fetch / commit derive from the thread index is formed again every round instead of living in ~40 registers
+      if constexpr (DX) asm volatile("" : "+v"(tl));
+      rows_out(m0 - BW_ROWS, true);                            // DX: the tile of the round before, one round behind its products
+      if constexpr (DX) __builtin_amdgcn_sched_barrier(0);     // (its registers are free again before the fetches take theirs)
+      fetch_old(m0);
       fetch(m0 + BW_ROWS);                                     // past m_end on the last round: masked to zeros in commit
       __builtin_amdgcn_sched_barrier(0);
       compute(cur);
       commit(m0 + BW_ROWS, cur ^ 1);
-      dx_tile(m0, cur);                                        // reads X's tile (the mask) before the barrier frees it
+      dx_tile(cur);                                            // reads X's tile (the mask) before the barrier frees it
       DGPPO_LDS_BARRIER();
       cur ^= 1;
     }
+    rows_out(m_begin + (n_tiles - 1) * BW_ROWS, false);        // DX: the last tile
   } else {
     for (int it = 0, m0 = m_begin; it < n_tiles; ++it, m0 += BW_ROWS) {
       stage_scalar(m0);
@@ -836,21 +902,22 @@ constexpr int bwd_w_groups() {
 }
 
 // NGX: group count given by the caller (the DX sites, kXwSites below); 0 = what the tile buffers allow
-template <int NT, int KT, bool DX = false, int NGX = 0>
+template <int NT, int KT, bool DX = false, int NGX = 0, bool ACCM = false>
 static void launch_bwd_w_kt(DenseBwdWArgs a, hipStream_t s) {
   constexpr int Kl = (KT & 1) ? KT * 16 : KT * 16 + 16;
   constexpr int Nl = (NT & 1) ? NT * 16 : NT * 16 + 16;
-  constexpr size_t smem = 2 * sizeof(float) * BW_ROWS * (Kl + Nl);
+  // per group: the two X / dY buffers, and with DX the dX tile
+  constexpr size_t smem = sizeof(float) * BW_ROWS * (2 * (Kl + Nl) + (DX ? XW_DL(KT) : 0));
   constexpr int NG = NGX > 0 ? NGX : bwd_w_groups<NT, KT>();
   static_assert(NG <= bwd_w_groups<NT, KT>(), "dense_bwd_w: more groups than the tile buffers and their exchange allow");
   static_assert(smem * NG <= 160 * 1024, "dense_bwd_w tiles exceed the 160 KB LDS of a gfx950 CU");
   static thread_local bool opted = false;
   if (!opted) {
     if (smem > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_w_kernel<NT, KT, 1, DX>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_w_kernel<NT, KT, 1, DX, ACCM>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (NG > 1 && smem * NG > 64 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_w_kernel<NT, KT, NG, DX>),
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_bwd_w_kernel<NT, KT, NG, DX, ACCM>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(smem * NG));
     opted = true;
   }
@@ -874,8 +941,8 @@ static void launch_bwd_w_kt(DenseBwdWArgs a, hipStream_t s) {
   a.part = ws;
   a.part_stride = stride;
   const int grid = cdiv(a.M, rpb * ng);
-  if (NG > 1 && ng > 1) hipLaunchKernelGGL((dense_bwd_w_kernel<NT, KT, NG, DX>), dim3(grid), dim3(256 * NG), smem * NG, s, a);
-  else hipLaunchKernelGGL((dense_bwd_w_kernel<NT, KT, 1, DX>), dim3(grid), dim3(256), smem, s, a);
+  if (NG > 1 && ng > 1) hipLaunchKernelGGL((dense_bwd_w_kernel<NT, KT, NG, DX, ACCM>), dim3(grid), dim3(256 * NG), smem * NG, s, a);
+  else hipLaunchKernelGGL((dense_bwd_w_kernel<NT, KT, 1, DX, ACCM>), dim3(grid), dim3(256), smem, s, a);
   if (ws) reduce_or_defer(s, ws, stride, grid, a.dW, a.ldw, a.db, a.K, a.N);
 }
 
@@ -1025,12 +1092,14 @@ int32_t dense_bwd_w_launch(DenseBwdWArgs a, hipStream_t s) {
 // ---- input and weight gradient of a Dense from one pass (dgppo_dense_bwd_xw) ---------------------------------------------
 // THE place that chooses between the fused kernel and the pair (dense_bwd_w, then dense_fwd with W^T): shape and alignment
 // only.  The shapes are GNN glue Denses of the networks, each moved here after a measured per-call gain at 131 072 rows
-// (profiles/README.md, round 7); everything else runs the pair, the `+=` site K = 32, N = 96 included (its KT = 2 gives two of
-// a group's four waves nothing to multiply: 56.8 us fused against 54.7 us for the pair).
-// The sites, in ONE table: shape, its tiles, and the groups per CU - at most 2, so that a lane keeps 256 registers for W^T and
-// the dY operand next to the accumulators; 48 x 32 needs 114 and keeps the 4 of dense_bwd_w (27.6 -> 25.4 us at 131 072 rows).
-struct XwSite { int K, N, NT, KT, NG; };
-constexpr XwSite kXwSites[] = {{144, 64, 4, 9, 2}, {48, 32, 2, 3, 4}, {48, 64, 4, 3, 2}};
+// (profiles/README.md, rounds 7 and 10); everything else runs the pair.  Round 10, fused against the round-9 path, us per call:
+// 144 x 64 81.5 -> 66.1, 48 x 32 25.2 -> 23.6, 48 x 64 41.7 -> 32.6, and the `+=` site 32 x 96 54.6 (the pair) -> 33.9 now that
+// its four waves all multiply: 1.5 - 1.75 times the time of their bytes at 4.5 TB/s.
+// The sites, in ONE table: shape, its tiles, the groups per CU (what 160 KB of LDS hold of two X / dY buffers and a dX tile per
+// group, with rows that divide over groups x CUs: 3 groups would leave 28 CUs idle at 131 072 rows), and whether the `+=` form
+// is fused too: at 144 x 64 it is not (no caller has it; with the old dX fragments the kernel would not fit 256 registers).
+struct XwSite { int K, N, NT, KT, NG; bool ACC; };
+constexpr XwSite kXwSites[] = {{144, 64, 4, 9, 2, false}, {48, 32, 2, 3, 4, true}, {48, 64, 4, 3, 2, true}, {32, 96, 6, 2, 2, true}};
 constexpr int kXwSiteCount = sizeof(kXwSites) / sizeof(kXwSites[0]);
 
 // what dense_bwd_w_kernel calls `vec`: the fused form exists only on the 16-byte staging path (its scalar path forms no dX)
@@ -1041,7 +1110,7 @@ static bool bwd_w_vec(const DenseBwdWArgs& a) {
 
 static bool bwd_xw_fused(const DenseBwdWArgs& a) {
   bool site = false;
-  for (int i = 0; i < kXwSiteCount; ++i) site = site || (a.K == kXwSites[i].K && a.N == kXwSites[i].N);
+  for (int i = 0; i < kXwSiteCount; ++i) site = site || (a.K == kXwSites[i].K && a.N == kXwSites[i].N && (kXwSites[i].ACC || !a.acc_mask));
   const uintptr_t p = reinterpret_cast<uintptr_t>(a.W) | reinterpret_cast<uintptr_t>(a.dX);
   return site && a.N <= 192 && bwd_w_vec(a) && ((a.ldwp | a.lddx) & 3) == 0 && (p & 15) == 0;
 }
@@ -1051,8 +1120,9 @@ static void launch_xw_site(const DenseBwdWArgs& a, hipStream_t s) {
   if constexpr (I < kXwSiteCount) {
     constexpr XwSite S = kXwSites[I];
     static_assert(S.K == S.KT * 16 && S.N == S.NT * 16, "dense_bwd_xw: a site is whole 16-wide tiles (W^T and dY fragments are unguarded)");
-    if (a.K == S.K && a.N == S.N) launch_bwd_w_kt<S.NT, S.KT, true, S.NG>(a, s);
-    else launch_xw_site<I + 1>(a, s);
+    if (a.K != S.K || a.N != S.N) launch_xw_site<I + 1>(a, s);
+    else if (!a.acc_mask) launch_bwd_w_kt<S.NT, S.KT, true, S.NG, false>(a, s);
+    else if constexpr (S.ACC) launch_bwd_w_kt<S.NT, S.KT, true, S.NG, true>(a, s);
   }
 }
 

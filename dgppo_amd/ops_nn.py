@@ -221,8 +221,9 @@ def dense_bwd_w(X, dY, dW, db=None):
 
 def dense_bwd_xw(X, dY, W, dX, dW, db=None, accumulate_mask: bool = False):
     """dense_bwd_w(X, dY, dW, db) and dense_fwd(dY, W, None, dX, trans_w=True) - with accumulate_mask: accumulate=True,
-    relu_mask=X - as ONE call: the library runs them as one pass over X and dY for the GNN glue shapes (dgppo_dense_bwd_xw in
-    the header) and as the pair otherwise."""
+    relu_mask=X - as ONE call: the library runs them as one pass over X and dY for the GNN glue shapes (K, N) = (144, 64),
+    (48, 32), (48, 64) and (32, 96) with 16-byte aligned operands - at (144, 64) only the `=` form - and as the pair otherwise
+    (dgppo_dense_bwd_xw in the header; the table kXwSites in nn_dense.hip)."""
     xp, ldx, M, K = _mat(X, "X")
     yp, ldy, My, Ncol = _mat(dY, "dY")
     pp, ldp, Kp, Np = _mat(W, "W")

@@ -9,7 +9,10 @@ R = 131072          # agent rows of a minibatch (16384 graphs x 8)
 Ro = 16384 * 72
 
 
-def timeit(name, fn, iters=20, flops=None, bytes_=None):
+HBM_TBS = 4.5      # the streaming rate DESIGN 4.2 holds the one-pass Dense backward to: `x HBM` = time over bytes at that rate
+
+
+def timeit(name, fn, iters=20, flops=None, bytes_=None, hbm=False):
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
@@ -25,6 +28,8 @@ def timeit(name, fn, iters=20, flops=None, bytes_=None):
         extra += f"  {flops / us / 1e6:7.1f} TFLOP/s"
     if bytes_:
         extra += f"  {bytes_ / us / 1e3:7.0f} GB/s"
+        if hbm:
+            extra += f"  {us / (bytes_ / (HBM_TBS * 1e6)):5.2f} x HBM"
     print(f"{name:44s} {us:9.1f} us{extra}", flush=True)
 
 
@@ -129,9 +134,9 @@ if which in ("all", "xw"):
                 K.dense_bwd_xw(X, dY, W, dX, dW, db, accumulate_mask=accm)
         nbytes = 4.0 * M * (Kd + Nd + Kd * (2 if accm else 1))
         for rep in range(3):
-            timeit(f"dense bwd K={Kd} N={Nd}: dense_bwd_w + dense_fwd^T", pair, iters=50, bytes_=nbytes)
+            timeit(f"dense bwd K={Kd} N={Nd}: dense_bwd_w + dense_fwd^T", pair, iters=50, bytes_=nbytes, hbm=True)
             if hasattr(K, "dense_bwd_xw"):
-                timeit(f"dense bwd K={Kd} N={Nd}: dense_bwd_xw", one, iters=50, bytes_=nbytes)
+                timeit(f"dense bwd K={Kd} N={Nd}: dense_bwd_xw", one, iters=50, bytes_=nbytes, hbm=True)
 if which in ("all", "attn"):
     cfg = N.make_env_cfg(0, 8, 3)
     for G in (16384, 4096):
