@@ -25,6 +25,8 @@ ENV_KINDS = {"LidarSpread": 0, "LidarTarget": 1, "LidarBicycleTarget": 2, "MPESp
 VMAS_REVERSE_TRANSPORT = 10
 GOALS_NODES, GOALS_LINE, GOALS_LINE_INTERIOR, GOALS_CIRCLE = range(4)
 RECT_STRIDE = 16
+# DGPPO_SCENE_* (dgppo_env_scene_load's validity bits), lowest bit first
+SCENE_BITS = ("NONFINITE", "OUT_OF_AREA", "AGENTS_OVERLAP", "AGENT_IN_OBSTACLE")
 
 
 class EnvCfg(C.Structure):
@@ -198,6 +200,9 @@ def lib() -> C.CDLL:
     l.dgppo_env_action_sweep_fork.restype = i32
     l.dgppo_env_action_sweep_fork.argtypes = [C.POINTER(EnvCfg), p, i64, p, p, p, i64, p, i64, p, i64, i32, p, i32, i32, p, i32,
                                               p, i32, p, p, p, p, p, p, p]
+    # the scene loader (csrc/env_scene.hip): the jitter travels by value
+    l.dgppo_env_scene_load.restype = i32
+    l.dgppo_env_scene_load.argtypes = [C.POINTER(EnvCfg), p, p, p, i32, p, p, f32, p, p, p, p, p, i32, p]
     _lib = l
     return l
 

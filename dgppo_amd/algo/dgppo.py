@@ -219,6 +219,22 @@ class DGPPO(Algorithm):
             return keys.to(self.device, torch.int64)
         return torch.from_numpy(np.ascontiguousarray(np.asarray(keys).astype(np.uint64).view(np.int64))).to(self.device)
 
+    def _scene_start(self, scenes, scene_ids, jitter, B_local: int):
+        """the engine's `start` of a collect call: None without scenes (the sampled reset), else (scenes, ids, jitter).  Episode b
+        starts in scene scene_ids[b]; without a list, in scene g % S of its GLOBAL env index g = rank * B_local + b, so that the
+        union over the ranks is what one device would run for the global batch."""
+        if scenes is None:
+            if scene_ids is not None or float(jitter) != 0.0:
+                raise ValueError("scene_ids / jitter need scenes: without them the episodes start at the sampled reset")
+            return None
+        cfg, mine = scenes.cfg, self._env.cfg
+        if (cfg.kind, cfg.n_agents, cfg.n_obs) != (mine.kind, mine.n_agents, mine.n_obs):
+            raise ValueError(f"scenes of env kind {cfg.kind} with {cfg.n_agents} agents and {cfg.n_obs} obstacles do not fit this "
+                             f"algo's env (kind {mine.kind}, {mine.n_agents} agents, {mine.n_obs} obstacles)")
+        if scene_ids is None and self.world > 1:
+            scene_ids = (self.rank * B_local + np.arange(B_local)) % scenes.S
+        return scenes.start(scene_ids, jitter)
+
     def _wrap(self, ro: EN.RolloutData, env=None) -> Rollout:
         ro.finalize()
         env = self._env if env is None else env
@@ -228,18 +244,22 @@ class DGPPO(Algorithm):
         self._last_rollouts[id(r.actions)] = ro
         return r
 
-    def collect(self, params, keys) -> Rollout:
-        """algo.collect(params, keys): one stochastic rollout per key (informarl.py:254-256)."""
+    def collect(self, params, keys, scenes=None, scene_ids=None, jitter: float = 0.0) -> Rollout:
+        """algo.collect(params, keys): one stochastic rollout per key (informarl.py:254-256).  scenes (env.Scenes): the
+        episodes — and those of the deterministic companion rollout — start in the given scenes instead of at the sampled
+        reset (_scene_start); not in the reference."""
         self._maybe_load(params)
         seeds = self._seeds(keys)
+        start = self._scene_start(scenes, scene_ids, jitter, int(seeds.shape[0]))
         # the deterministic rollout that update() needs for the constraint-value targets (dgppo.py:139-141) uses the same
         # parameters as this collect: it is launched alongside on a second stream and handed to update()
         det_seeds = self._seeds(self._draw_keys(int(seeds.shape[0])))
-        ro, det = self.engine.rollout_pair(seeds, det_seeds, noise_seed=int(self._rng.integers(1, 2 ** 62)))
+        ro, det = self.engine.rollout_pair(seeds, det_seeds, noise_seed=int(self._rng.integers(1, 2 ** 62)),
+                                           **({} if start is None else {"start": start}))
         self._pending_det = (ro, det)
         return self._wrap(ro)
 
-    def collect_deterministic(self, keys, env=None) -> Rollout:
+    def collect_deterministic(self, keys, env=None, scenes=None, scene_ids=None, jitter: float = 0.0) -> Rollout:
         eng = self.engine
         if env is not None and env is not self._env:
             assert env.cfg.kind == self._env.cfg.kind and env.num_agents == self.n_agents
@@ -249,17 +269,20 @@ class DGPPO(Algorithm):
             # this rollout reuses the record buffers of the deterministic rollout that collect() prepared for update():
             # drop the hand-over, update() will produce its own
             self._pending_det = None
-        ro = eng.rollout(seeds, False)
+        ro = eng.rollout(seeds, False, start=self._scene_start(scenes, scene_ids, jitter, int(seeds.shape[0])))
         return self._wrap(ro, env)
 
-    def collect_stochastic(self, keys, env=None) -> Rollout:
+    def collect_stochastic(self, keys, env=None, scenes=None, scene_ids=None, jitter: float = 0.0) -> Rollout:
         """stochastic test rollouts (test.py:78-83 with --stochastic: algo.step inside test_rollout), batched"""
         if env is not None and env is not self._env:
             assert env.cfg.kind == self._env.cfg.kind and env.num_agents == self.n_agents
-        ro = self.engine.rollout(self._seeds(keys), True, noise_seed=int(self._rng.integers(1, 2 ** 62)))
+        seeds = self._seeds(keys)
+        ro = self.engine.rollout(seeds, True, noise_seed=int(self._rng.integers(1, 2 ** 62)),
+                                 start=self._scene_start(scenes, scene_ids, jitter, int(seeds.shape[0])))
         return self._wrap(ro, env)
 
-    def collect_shielded(self, keys, env=None, grid: int = 8, us=None, vs=None, margin: float = 0.0):
+    def collect_shielded(self, keys, env=None, grid: int = 8, us=None, vs=None, margin: float = 0.0, scenes=None, scene_ids=None,
+                         jitter: float = 0.0):
         """-> (Rollout, ShieldLog): deterministic test episodes in which every agent's action passes through the learned barrier
         as a runtime filter (Engine.rollout_shielded): the policy's action is kept where cbf_deriv of the agent's own Vh
         (dgppo.py:246-250) is <= -margin for it, otherwise replaced by the nearest admissible action of the grid us x vs
@@ -273,7 +296,9 @@ class DGPPO(Algorithm):
         vs = _grid_axis("collect_shielded", "vs", vs, grid, 1.0, lo=-1.0)
         if not np.isfinite(float(margin)):
             raise ValueError("collect_shielded: margin must be finite")
-        ro, log = self.engine.rollout_shielded(self._seeds(keys), us, vs, float(margin))
+        seeds = self._seeds(keys)
+        ro, log = self.engine.rollout_shielded(seeds, us, vs, float(margin),
+                                               start=self._scene_start(scenes, scene_ids, jitter, int(seeds.shape[0])))
         r = self._wrap(ro, env)
         em = lambda x: x.transpose(0, 1).contiguous().cpu().numpy()
         return r, ShieldLog(em(log["policy_action"]), ro.actions.cpu().numpy(), em(log["index"]), em(log["flag"]), em(log["h"]),
@@ -331,7 +356,7 @@ class DGPPO(Algorithm):
                                 int(horizon), float(self.engine.hp.gamma))
 
     def collect_lookahead_shielded(self, keys, env=None, grid: int = 8, us=None, vs=None, margin: float = 0.0,
-                                   horizon: int = 8, rounds: int = 1):
+                                   horizon: int = 8, rounds: int = 1, scenes=None, scene_ids=None, jitter: float = 0.0):
         """-> (Rollout, LookaheadShieldLog): deterministic test episodes in which every agent's action passes through a
         lookahead filter (Engine.rollout_lookahead_shielded): for the policy's action and every action of the grid us x vs
         (default: linspace(-1, 1, grid) in fp32 on both axes) the environment is forked, the candidate played, and the policy
@@ -357,13 +382,14 @@ class DGPPO(Algorithm):
         if int(rounds) < 1:
             raise ValueError(f"{what}: rounds must be >= 1 (got {rounds})")
         em = lambda x: x.transpose(0, 1).contiguous().cpu().numpy()
+        seeds = self._seeds(keys)
+        start = self._scene_start(scenes, scene_ids, jitter, int(seeds.shape[0]))
         if int(rounds) == 1:
-            ro, log = self.engine.rollout_lookahead_shielded(self._seeds(keys), us, vs, int(horizon), float(margin))
+            ro, log = self.engine.rollout_lookahead_shielded(seeds, us, vs, int(horizon), float(margin), start=start)
             r = self._wrap(ro, env)
             return r, LookaheadShieldLog(em(log["policy_action"]), ro.actions.cpu().numpy(), em(log["index"]), em(log["flag"]),
                                          em(log["s"]), us, vs, float(margin), int(horizon))
-        ro, log = self.engine.rollout_lookahead_shielded(self._seeds(keys), us, vs, int(horizon), float(margin),
-                                                         rounds=int(rounds))
+        ro, log = self.engine.rollout_lookahead_shielded(seeds, us, vs, int(horizon), float(margin), rounds=int(rounds), start=start)
         r = self._wrap(ro, env)
         return r, JointLookaheadShieldLog(em(log["policy_action"]), ro.actions.cpu().numpy(), em(log["index"]), em(log["flag"]),
                                           em(log["s"]), us, vs, float(margin), int(horizon), em(log["joint"]),

@@ -342,7 +342,17 @@ class Engine:
                 K.policy_head(act["ms"], None, None, a_t, None, None, n, 1)
             OE.step(cfg, ro.states_tm[t], ro.action_tm[t], ro.states_tm[t + 1], ro.reward_tm[t], ro.cost_tm[t])
 
-    def rollout(self, seeds: torch.Tensor, stochastic: bool, noise_seed: int = 0) -> RolloutData:
+    def _start(self, seeds: torch.Tensor, st: OE.State, start=None):
+        """slot 0 of a rollout's record: the sampled reset of seeds, or — start = (scenes, scene_ids | None, jitter), an
+        env.scenes.SceneStart — the user-given scenes (ops_env.scene_start: env b in scene scene_ids[b], or b % S; agents moved by
+        up to `jitter`, drawn from seeds).  Either way sensed, and envs without a valid scene counted in reset_failed."""
+        if start is None:
+            return OE.reset(self.cfg, seeds, st, self.reset_failed)
+        scenes, scene_ids, jitter = start
+        OE.scene_start(self.cfg, scenes.dev, scene_ids, seeds, float(jitter), st, None, self.reset_failed)
+
+    def rollout(self, seeds: torch.Tensor, stochastic: bool, noise_seed: int = 0, start=None) -> RolloutData:
+        """start: None, or where the episodes begin instead of at the reset (_start); everything after slot 0 is the same"""
         cfg, T = self.cfg, self.T
         B = int(seeds.shape[0])
         n = cfg.n_agents
@@ -356,7 +366,7 @@ class Engine:
             ro._env_major = False
         else:
             ro = RolloutData(cfg, B, T, self.device, stochastic, self.HC)
-        OE.reset(cfg, seeds, ro.states_tm[0], self.reset_failed)         # with the sense pass that fills hits_tm[0]
+        self._start(seeds, ro.states_tm[0], start)                 # with the sense pass that fills hits_tm[0]
         ro.rnn_tm[0].zero_()                                   # init_rnn_state = zeros (informarl.py:115-124)
         eps = None
         if stochastic:
@@ -408,18 +418,18 @@ class Engine:
         """scratch buffers the rollout loop touches live in the engine's arena (features) and the policy's (activations)"""
         return self.arena.generation + self.policy.arena.generation
 
-    def rollout_pair(self, seeds: torch.Tensor, det_seeds: torch.Tensor, noise_seed: int = 0):
+    def rollout_pair(self, seeds: torch.Tensor, det_seeds: torch.Tensor, noise_seed: int = 0, start=None):
         """the stochastic training rollout and the deterministic rollout of the same parameters (informarl.py:254-256 and
         dgppo.py:139-141).  They are independent, so with multi_stream they run on two HIP streams side by side."""
         if not (self.multi_stream and self.device.type == "cuda"):
-            return self.rollout(seeds, True, noise_seed), self.rollout(det_seeds, False)
+            return self.rollout(seeds, True, noise_seed, start), self.rollout(det_seeds, False, start=start)
         main = torch.cuda.current_stream(self.device)
         s0, s1 = self._net_streams()[:2]
         out = [None, None]
         for k, (st, sd, stoch) in enumerate(((s0, seeds, True), (s1, det_seeds, False))):
             st.wait_stream(main)
             with torch.cuda.stream(st):
-                out[k] = self.rollout(sd, stoch, noise_seed if stoch else 0)
+                out[k] = self.rollout(sd, stoch, noise_seed if stoch else 0, start)
         main.wait_stream(s0)
         main.wait_stream(s1)
         return out[0], out[1]
@@ -836,7 +846,7 @@ class Engine:
     # ------------------------------------------------------------------------------------------------------------------
     # barrier shield: the deterministic rollout with every agent's action filtered through the learned barrier
     # ------------------------------------------------------------------------------------------------------------------
-    def rollout_shielded(self, seeds: torch.Tensor, us, vs, margin: float = 0.0, events: Optional[list] = None):
+    def rollout_shielded(self, seeds: torch.Tensor, us, vs, margin: float = 0.0, events: Optional[list] = None, start=None):
         """-> (RolloutData, log): a deterministic record (the conventions of rollout(seeds, False)) in which, at every step,
         every agent's action is filtered through the barrier condition the policy is trained under (dgppo.py:246-250).  The
         candidates of an agent are its own policy action (index 0) and the grid (us[iu], vs[iv]) (index 1 + iv * nu + iu).  Per
@@ -863,7 +873,7 @@ class Engine:
         B = int(seeds.shape[0])
         dev = self.device
         ro = RolloutData(cfg, B, T, dev, False, HC)
-        OE.reset(cfg, seeds, ro.states_tm[0], self.reset_failed)
+        self._start(seeds, ro.states_tm[0], start)
         ro.rnn_tm[0].zero_()
         log = dict(policy_action=torch.empty(T, B, n, 2, device=dev), index=torch.empty(T, B, n, dtype=torch.int32, device=dev),
                    flag=torch.empty(T, B, n, dtype=torch.int32, device=dev), h=torch.empty(T, B, n, P, device=dev),
@@ -1086,7 +1096,8 @@ class Engine:
         rounds_used.copy_(torch.from_numpy(used), non_blocking=False)
 
     def rollout_lookahead_shielded(self, seeds: torch.Tensor, us, vs, horizon: int, margin: float = 0.0,
-                                   events: Optional[list] = None, records: Optional[list] = None, rounds: int = 1):
+                                   events: Optional[list] = None, records: Optional[list] = None, rounds: int = 1,
+                                   start=None):
         """-> (RolloutData, log): a deterministic record (the conventions of rollout(seeds, False)) in which, at every step,
         every agent's action is filtered by what it leads to within `horizon` steps of the simulator, the learned Vh left out:
         what rollout_shielded trusts Vh to predict is rolled here.  Per step t: the policy forward on state t gives a_pol and
@@ -1124,7 +1135,7 @@ class Engine:
         B = int(seeds.shape[0])
         dev = self.device
         ro = RolloutData(cfg, B, T, dev, False, HC)
-        OE.reset(cfg, seeds, ro.states_tm[0], self.reset_failed)
+        self._start(seeds, ro.states_tm[0], start)
         ro.rnn_tm[0].zero_()
         log = dict(policy_action=torch.empty(T, B, n, 2, device=dev), index=torch.empty(T, B, n, dtype=torch.int32, device=dev),
                    flag=torch.empty(T, B, n, dtype=torch.int32, device=dev), s=torch.empty(T, B, n, P, device=dev))

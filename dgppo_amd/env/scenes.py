@@ -1,0 +1,144 @@
+"""User-given start scenes: where an episode begins when it does not begin at the sampled reset.
+
+The reference ships no way to start an episode anywhere but at reset; its env_states is a Python pytree a user can fill by hand.
+Here the state is a device record, so a scene is given as template rows — agents and goals in the record's own layout,
+obstacles as (cx, cy, w, h, theta) or (ox, oy) — and dgppo_env_scene_load (csrc/env_scene.hip) forms the record from them.
+
+    scenes = Scenes(env, agent, goal, rect=rect)          # or Scenes.load("headon.npz", env)
+    ro = algo.collect_deterministic(keys, env=env, scenes=scenes)     # episode b starts in scene b % S
+"""
+from __future__ import annotations
+
+from typing import Dict, NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from .. import _native as N
+from .. import ops_env as OE
+
+f32 = np.float32
+
+
+class SceneStart(NamedTuple):
+    """what the engine's rollouts take as `start`: the scenes, which scene every env starts in (host ints [B]; None: env b
+    takes scene b % S) and how far the agents are moved off their template positions (0: not at all)"""
+    scenes: "Scenes"
+    scene_ids: Optional[np.ndarray] = None
+    jitter: float = 0.0
+
+
+def decode_flags(bits: int) -> str:
+    """the names of the validity bits of dgppo_env_scene_load that are set"""
+    return " | ".join(name for k, name in enumerate(N.SCENE_BITS) if int(bits) >> k & 1) or "valid"
+
+
+def check_templates(cfg: N.EnvCfg, agent, goal, rect=None, disc=None, names=None) -> Dict[str, np.ndarray]:
+    """the host half of Scenes(): kind, shapes and names against cfg -> dict(agent, goal[, obst], names) of float32 arrays with
+    a leading S.  Raises ValueError; touches no device."""
+    if cfg.is_vmas:
+        raise ValueError("Scenes: VMASReverseTransport has no scene entry point (its record has a body and a scene row, "
+                         "no goal / obstacle rows)")
+    agent, goal = np.ascontiguousarray(agent, f32), np.ascontiguousarray(goal, f32)
+    if agent.ndim != 3 or agent.shape[0] < 1:
+        raise ValueError(f"Scenes: agent must be [S, n, sd] with S >= 1 (got shape {agent.shape})")
+    S = agent.shape[0]
+    shapes = OE.scene_template_shapes(cfg)
+    given = {"agent": agent, "goal": goal}
+    which = "rect" if cfg.is_lidar else "disc"
+    other, other_name = (disc, "disc") if cfg.is_lidar else (rect, "rect")
+    if other is not None:
+        raise ValueError(f"Scenes: {other_name} rows are for the {'MPE' if cfg.is_lidar else 'LiDAR'} kinds; env kind {cfg.kind} "
+                         f"takes {which}")
+    obst = rect if cfg.is_lidar else disc
+    if cfg.n_obs > 0:
+        if obst is None:
+            raise ValueError(f"Scenes: {which} [S, {cfg.n_obs}, {shapes['obst'][1]}] is required (the env has {cfg.n_obs} obstacles)")
+        given["obst"] = np.ascontiguousarray(obst, f32)
+    elif obst is not None:
+        raise ValueError(f"Scenes: the env has no obstacles, {which} must be None")
+    for name, x in given.items():
+        if tuple(x.shape) != (S,) + shapes[name]:
+            shown = which if name == "obst" else name
+            raise ValueError(f"Scenes: {shown}: expected shape {(S,) + shapes[name]}, got {tuple(x.shape)}")
+    names = [f"scene{s}" for s in range(S)] if names is None else [str(x) for x in names]
+    if len(names) != S:
+        raise ValueError(f"Scenes: {len(names)} names for {S} scenes")
+    given["names"] = names
+    return given
+
+
+def write_npz(path, env_id: str, num_agents: int, agent, goal, obst, obst_key: Optional[str], names: Sequence[str]) -> None:
+    """the file format of Scenes.save: env_id, num_agents, agent, goal, rect or disc (absent without obstacles), names"""
+    out = dict(env_id=np.array(env_id), num_agents=np.array(int(num_agents), np.int64), agent=np.asarray(agent, f32),
+               goal=np.asarray(goal, f32), names=np.array(list(names), dtype=np.str_))
+    if obst is not None:
+        out[obst_key] = np.asarray(obst, f32)
+    with open(path, "wb") as f:          # a file object: numpy appends no suffix
+        np.savez(f, **out)
+
+
+def read_npz(path) -> dict:
+    """-> dict(env_id, num_agents, agent, goal, rect, disc, names); rect / disc None where the file has none"""
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in ("env_id", "num_agents", "agent", "goal", "names") if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: not a scenes file: no {missing}")
+        return dict(env_id=str(z["env_id"]), num_agents=int(z["num_agents"]), agent=z["agent"], goal=z["goal"],
+                    rect=z["rect"] if "rect" in z.files else None, disc=z["disc"] if "disc" in z.files else None,
+                    names=[str(x) for x in z["names"]])
+
+
+class Scenes:
+    """S start scenes of one environment: template rows checked against env.cfg, uploaded once, and validated by one
+    dgppo_env_scene_load call (B = S, no jitter): a scene with a non-finite word, an agent outside the area, two overlapping
+    agents or an agent inside an obstacle raises ValueError naming the scene and what is wrong with it.  Goals are checked for
+    finiteness only: a goal behind a wall is a legitimate hard scene.
+      agent [S, n, sd], goal [S, n_goals, sd]   rows in the record's layout (x, y, vx, vy; bicycle_rows for LidarBicycleTarget)
+      rect  [S, n_obs, 5]                        LiDAR kinds: cx, cy, w, h, theta
+      disc  [S, n_obs, 2]                        MPE kinds: ox, oy
+      names                                      S strings (default scene0, scene1, ...)"""
+
+    def __init__(self, env, agent, goal, rect=None, disc=None, names=None):
+        cfg = env.cfg
+        rows = check_templates(cfg, agent, goal, rect, disc, names)
+        self.env_id, self.num_agents, self.cfg = env.KIND, int(cfg.n_agents), cfg
+        self.names = rows.pop("names")
+        self.rows: Dict[str, np.ndarray] = rows                      # host copies: agent, goal[, obst]
+        self.S = int(rows["agent"].shape[0])
+        dev = env.device
+        self.dev: Dict[str, torch.Tensor] = {k: torch.from_numpy(v).to(dev) for k, v in rows.items()}
+        st = OE.State.empty(cfg, self.S, dev)
+        flags = torch.zeros(self.S, dtype=torch.int32, device=dev)
+        OE.scene_load(cfg, self.dev, None, None, 0.0, st, flags)
+        bad = [(s, int(b)) for s, b in enumerate(flags.cpu().tolist()) if b]
+        if bad:
+            raise ValueError("Scenes: invalid scene(s): " + "; ".join(f"{self.names[s]} (#{s}): {decode_flags(b)}" for s, b in bad))
+
+    @property
+    def obst_key(self) -> Optional[str]:
+        return None if "obst" not in self.rows else ("rect" if self.cfg.is_lidar else "disc")
+
+    def start(self, scene_ids=None, jitter: float = 0.0) -> SceneStart:
+        """the `start` argument of the engine's rollouts"""
+        return SceneStart(self, None if scene_ids is None else np.asarray(scene_ids), float(jitter))
+
+    def save(self, path) -> None:
+        write_npz(path, self.env_id, self.num_agents, self.rows["agent"], self.rows["goal"], self.rows.get("obst"), self.obst_key,
+                  self.names)
+
+    @classmethod
+    def load(cls, path, env) -> "Scenes":
+        z = read_npz(path)
+        if z["env_id"] != env.KIND or z["num_agents"] != env.num_agents:
+            raise ValueError(f"{path}: scenes of {z['env_id']} with {z['num_agents']} agents, the env is {env.KIND} with "
+                             f"{env.num_agents}")
+        return cls(env, z["agent"], z["goal"], rect=z["rect"], disc=z["disc"], names=z["names"])
+
+    @staticmethod
+    def bicycle_rows(x, y, heading, speed) -> np.ndarray:
+        """[..., 5] agent or goal rows of LidarBicycleTarget in the record's layout: x, y, cos(heading), sin(heading), speed
+        (lidar_bicycle_target.py:48-50)"""
+        x, y, heading, speed = np.broadcast_arrays(np.asarray(x, f32), np.asarray(y, f32), np.asarray(heading, f32),
+                                                   np.asarray(speed, f32))
+        return np.stack([x, y, np.cos(heading).astype(f32), np.sin(heading).astype(f32), speed], axis=-1).astype(f32)

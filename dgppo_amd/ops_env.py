@@ -272,6 +272,76 @@ def reset(cfg: N.EnvCfg, seeds: torch.Tensor, st: State, n_failed: torch.Tensor 
         materialize(cfg, st, graph)
 
 
+def scene_template_shapes(cfg: N.EnvCfg) -> Dict[str, tuple]:
+    """name -> trailing shape of the template rows dgppo_env_scene_load reads per scene: agent and goal rows in the record's own
+    layout, obstacles as (cx, cy, w, h, theta) for the LiDAR kinds and (ox, oy) for the MPE kinds (no entry without obstacles)"""
+    shapes = {"agent": (cfg.n_agents, cfg.state_dim), "goal": (cfg.n_goals, cfg.state_dim)}
+    if cfg.n_obs > 0:
+        shapes["obst"] = (cfg.n_obs, 5 if cfg.is_lidar else 2)
+    return shapes
+
+
+def scene_load(cfg: N.EnvCfg, scenes_dev: Dict[str, torch.Tensor], scene_ids, seeds, jitter: float, st: State, flags=None,
+               n_failed=None):
+    """dgppo_env_scene_load: the dense state st (State.empty, B envs) from the S template scenes scenes_dev (device tensors by
+    scene_template_shapes, each with a leading S).  Env b takes scene scene_ids[b] — a host array or list of B ints, checked here
+    against [0, S) (a tensor is read back for that) — or b % S without a list.  jitter > 0 moves every agent's x, y by up to that
+    much, drawn from seeds [B] (int64 tensor) and retried up to 16 times until the scene is valid; seeds may be None at jitter
+    0.  flags [B] int32 (optional) receives the validity bits (N.SCENE_BITS, 0 = valid), n_failed as in env_reset: touched only
+    at jitter > 0.  hits are not sensed here: scene_start does that.  Every refusal is raised before anything is launched."""
+    fn = "scene_load"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no scene entry point")
+    B = int(st.agent.shape[0])
+    _check_state(cfg, B, agent=st.agent, goal=st.goal, obst=st.obst)
+    shapes = scene_template_shapes(cfg)
+    agent_t = scenes_dev.get("agent")
+    if not torch.is_tensor(agent_t) or agent_t.ndim != 3 or agent_t.shape[0] < 1:
+        raise ValueError(f"{fn}: scenes_dev['agent'] must be a [S, n, sd] tensor with S >= 1")
+    S = int(agent_t.shape[0])
+    for name, shape in shapes.items():
+        if not torch.is_tensor(scenes_dev.get(name)):
+            raise ValueError(f"{fn}: scenes_dev has no {name}")
+        N.expect_shape(scenes_dev[name], (S,) + shape, f"scenes_dev.{name}")
+    jitter = float(jitter)
+    if not jitter >= 0.0:
+        raise ValueError(f"{fn}: jitter must be >= 0 (got {jitter})")
+    if seeds is None and jitter > 0.0:
+        raise ValueError(f"{fn}: seeds are required with jitter > 0")
+    if seeds is not None:
+        N.expect_shape(seeds, (B,), "seeds")
+    ids_dev = None
+    if scene_ids is not None:
+        ids = np.asarray(scene_ids.cpu() if torch.is_tensor(scene_ids) else scene_ids)
+        if ids.shape != (B,) or ids.dtype.kind not in "iu":
+            raise ValueError(f"{fn}: scene_ids must be {B} ints (got shape {ids.shape}, dtype {ids.dtype})")
+        if B and (int(ids.min()) < 0 or int(ids.max()) >= S):
+            raise ValueError(f"{fn}: scene_ids outside [0, {S})")
+        ids_dev = torch.from_numpy(np.ascontiguousarray(ids, np.int32)).to(st.agent.device)
+    if flags is not None:
+        N.expect_shape(flags, (B,), "flags")
+    if n_failed is not None:
+        N.expect_shape(n_failed, (1,), "n_failed")
+    rc = N.lib().dgppo_env_scene_load(
+        C.byref(cfg), N.ptr(agent_t, name="scenes_dev.agent"), N.ptr(scenes_dev["goal"], name="scenes_dev.goal"),
+        N.ptr(scenes_dev.get("obst") if cfg.n_obs > 0 else None, name="scenes_dev.obst"), S, N.ptr(ids_dev, torch.int32, "scene_ids"),
+        N.ptr(seeds, torch.int64, "seeds"), jitter, N.ptr(st.agent, name="agent"), N.ptr(st.goal, name="goal"),
+        N.ptr(st.obst, name="obst"), N.ptr(flags, torch.int32, "flags"), N.ptr(n_failed, torch.int32, "n_failed"), B,
+        N.stream_ptr())
+    N.check(rc, "dgppo_env_scene_load")
+
+
+def scene_start(cfg: N.EnvCfg, scenes_dev: Dict[str, torch.Tensor], scene_ids, seeds, jitter: float, st: State, flags=None,
+                n_failed=None, graph: Optional[Dict[str, torch.Tensor]] = None):
+    """the episode start of user-given scenes into st: scene_load, then what reset does after its kernel — sensed where the
+    record has hits, the graph written where one is asked for"""
+    scene_load(cfg, scenes_dev, scene_ids, seeds, jitter, st, flags, n_failed)
+    if "hits" in st.step:
+        sense(cfg, st, graph)
+    elif graph is not None:
+        materialize(cfg, st, graph)
+
+
 def step(cfg: N.EnvCfg, st: State, action, nst: State, reward, cost, graph: Optional[Dict[str, torch.Tensor]] = None):
     """one env step from st into the per-step fields of nst (st.like()): reward [B] and cost [B, n, n_cost] of the pre-step
     state, the optional graph of the post-step state"""

@@ -194,6 +194,36 @@ int32_t dgppo_env_reset(const dgppo_env_cfg* cfg, const uint64_t* seeds,
 int32_t dgppo_env_reset_checked(const dgppo_env_cfg* cfg, const uint64_t* seeds, float* agent, float* goal, float* obst,
                                 int32_t* n_failed, int32_t B, void* stream);
 
+/* Episode start from user-given scenes: the dense env state that dgppo_env_reset writes, from S template scenes instead of
+ * the sampled one.  Not in the reference, whose env_states is a Python pytree a user can fill (lidar_env/base.py:21-27); it
+ * ships no way to start an episode anywhere but at reset.  Env b takes scene s = scene_ids ? scene_ids[b] : b % S.
+ *   agent_t   [S, n, sd]   template rows, the record's own layout
+ *   goal_t    [S, ng, sd]
+ *   obst_t    LiDAR: [S, n_obs, 5] = cx, cy, w, h, theta; MPE: [S, n_obs, 2] = ox, oy; NULL iff n_obs == 0
+ *   scene_ids [B] DEVICE int32 in [0, S) (the caller checks the range; the kernel trusts it), or NULL
+ *   seeds     [B] uint64; NULL allowed iff jitter == 0
+ *   agent, goal, obst      out, as dgppo_env_reset writes them (obst NULL iff n_obs == 0)
+ *   flags     [B] out, or NULL: 0 = the scene is valid, else DGPPO_SCENE_* bits
+ *   n_failed  as dgppo_env_reset_checked (caller-zeroed device int32, may be NULL)
+ * Goal rows are copied word for word (a NaN keeps its payload).  A rectangle becomes the 16-float record above with
+ * [5] = cosf(theta), [6] = sinf(theta) and the corner points of Rectangle.create (obstacle.py:39-56), formed exactly as the
+ * reset forms them; a disc becomes [ox, oy, 0, 0].  Goals and obstacles are never jittered.
+ * jitter == 0: the agent rows are copied and nothing is drawn; an invalid scene is still written, only its flags say so, and
+ * *n_failed is not touched (the caller decides).
+ * jitter = J > 0: the Philox stream keyed by seeds[b] as in dgppo_env_reset; attempt a = 0 .. 15 draws d = a * n + i for
+ * agent i (two uniforms u0, u1: words 0, 1 of counter (d, 0, 0, 0)) and sets x = x_t + (2 u0 - 1) J, y = y_t + (2 u1 - 1) J,
+ * always measured from the template; the other state columns are untouched.  The first attempt whose scene is valid is
+ * kept; if none is, the last one stays, flags[b] holds its bits and *n_failed gains 1.
+ * Refused on the host, before any launch: an invalid cfg, VMASReverseTransport, S < 1, B < 0, a negative or NaN jitter, NULL
+ * operands (obst_t / obst must be NULL exactly when n_obs == 0; seeds may be NULL only with jitter == 0), n_agents > 64.   */
+#define DGPPO_SCENE_NONFINITE 1         /* a non-finite word anywhere in the scene's template rows (goals: this test only) */
+#define DGPPO_SCENE_OUT_OF_AREA 2       /* an agent with x outside [0, area_size] or y outside [0, y_limit]               */
+#define DGPPO_SCENE_AGENTS_OVERLAP 4    /* a pair with sqrtf(dx*dx + dy*dy) < two_car_radius                              */
+#define DGPPO_SCENE_AGENT_IN_OBSTACLE 8 /* LiDAR: Rectangle.inside at car_radius (obstacle.py:62-72); MPE: < car_plus_obs */
+int32_t dgppo_env_scene_load(const dgppo_env_cfg* cfg, const float* agent_t, const float* goal_t, const float* obst_t,
+                             int32_t S, const int32_t* scene_ids, const uint64_t* seeds, float jitter, float* agent,
+                             float* goal, float* obst, int32_t* flags, int32_t* n_failed, int32_t B, void* stream);
+
 /* ---- VMASReverseTransport (dgppo/env/vmas/vmas_reverse_transport.py) ------------------------------------------
  * n agents (discs of radius 0.03) push a hollow 0.6 x 0.6 box of mass 10 towards a goal past 3 disc obstacles.  The record
  * differs from the other kinds, so the kind has its own entry points; dgppo_env_step / dgppo_env_reset* /

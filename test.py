@@ -45,7 +45,12 @@ step, everyone else their recorded action, and the deterministic policy is rolle
 action grid dooms the agent within the horizon, in how many frames the one action decides that, and, with `--action-landscape`
 for the same agent, how many of the doomed actions the learned barrier admits (missed_frac) and how many of the others it
 rejects (conservative_frac); the animation shows the doomed set's boundary dashed in the action inset.  It works with
-`--stochastic` and with either shield; the what-if rollouts follow the deterministic, unshielded policy."""
+`--stochastic` and with either shield; the what-if rollouts follow the deterministic, unshielded policy.
+`--scenes FILE` starts the episodes in designed situations instead of at the sampled reset: FILE is a `.npz` of `dgppo.env.Scenes`
+(`Scenes.save`; S scenes of this env and team size), episode i runs scene (offset + i) % S and its line names the scene.
+`--scene-jitter J` (with `--scenes`, J > 0) moves every agent by up to J off its place in the scene, drawn from the episode's
+seed, so that several episodes of one scene differ.  Everything else — both shields, the rounds, every landscape, the video,
+`test_log.csv` — describes those episodes as it would the sampled ones."""
 import argparse
 import datetime
 import os
@@ -54,7 +59,7 @@ import pathlib
 import numpy as np
 
 from dgppo.algo import make_algo
-from dgppo.env import make_env
+from dgppo.env import Scenes, make_env
 from dgppo_amd.trainer import evaluate as EV
 
 
@@ -84,19 +89,27 @@ def test(args):
     if len(keys) == 0:
         raise SystemExit("no episodes to run (--epi / --offset)")
     shield_log = None
+    where, scene_of = {}, None                  # --scenes: the start of every collect call below, and the scene name per episode
+    if args.scenes is not None:
+        scenes = Scenes.load(args.scenes, env)
+        ids = (args.offset + np.arange(len(keys))) % scenes.S
+        where = dict(scenes=scenes, scene_ids=ids, jitter=args.scene_jitter)
+        scene_of = [scenes.names[s] for s in ids]
     if args.shield and args.shield_horizon >= 1:
         ro, shield_log = algo.collect_lookahead_shielded(keys, env=env, grid=args.shield_grid, margin=args.shield_margin,
                                                          horizon=args.shield_horizon,
-                                                         **({"rounds": args.shield_rounds} if args.shield_rounds > 1 else {}))
+                                                         **({"rounds": args.shield_rounds} if args.shield_rounds > 1 else {}),
+                                                         **where)
     elif args.shield:
-        ro, shield_log = algo.collect_shielded(keys, env=env, grid=args.shield_grid, margin=args.shield_margin)
+        ro, shield_log = algo.collect_shielded(keys, env=env, grid=args.shield_grid, margin=args.shield_margin, **where)
     elif args.stochastic:
-        ro = algo.collect_stochastic(keys, env=env)
+        ro = algo.collect_stochastic(keys, env=env, **where)
     else:
-        ro = algo.collect_deterministic(keys, env=env)
+        ro = algo.collect_deterministic(keys, env=env, **where)
     stats = EV.episode_stats(ro.rewards.cpu().numpy(), ro.costs.cpu().numpy())
     for i in range(len(keys)):
-        print(f"epi: {i}, reward: {stats['reward'][i]:.3f}, cost: {stats['cost'][i]:.3f}, "
+        scene = "" if scene_of is None else f"scene: {scene_of[i]}, "
+        print(f"epi: {i}, {scene}reward: {stats['reward'][i]:.3f}, cost: {stats['cost'][i]:.3f}, "
               f"safe rate: {stats['safe_rate'][i] * 100:.3f}%")
     agg = EV.aggregate(stats)
     print(f"reward: {agg['reward']:.3f}, min/max reward: {agg['reward_min']:.3f}/{agg['reward_max']:.3f}, "
@@ -247,13 +260,16 @@ ACTION_ROLLOUT_FLAGS = [(("--action-rollout-landscape",), "int", None)]
 # with --shield --shield-horizon H: re-judge the picks jointly, up to R rounds per step, one mover per round after the first
 # (collect_lookahead_shielded(rounds=R)); 1: the shield without rounds
 ROUNDS_FLAGS = [(("--shield-rounds",), "int", 1)]
+# start the episodes in the scenes of a dgppo.env.Scenes file instead of at the sampled reset (episode i: scene (offset + i) % S);
+# --scene-jitter J moves every agent by up to J off its place, drawn from the episode's seed
+SCENE_FLAGS = [(("--scenes",), "str", None), (("--scene-jitter",), "float", 0.0)]
 
 
 def build_parser() -> argparse.ArgumentParser:
     types = {"int": int, "str": str, "float": float}
     ap = argparse.ArgumentParser(description=__doc__)
     for names, kind, default in (FLAGS + COST_FLAGS + ACTION_FLAGS + SHIELD_FLAGS + ROLLOUT_FLAGS + LOOKAHEAD_FLAGS
-                                 + ACTION_ROLLOUT_FLAGS + ROUNDS_FLAGS):
+                                 + ACTION_ROLLOUT_FLAGS + ROUNDS_FLAGS + SCENE_FLAGS):
         if kind == "flag":
             ap.add_argument(*names, action="store_true", default=False)
         elif kind.startswith("req:"):
@@ -277,6 +293,10 @@ def main(argv=None):
         raise SystemExit(f"--shield-rounds must be >= 1 (got {args.shield_rounds})")
     if args.shield_rounds > 1 and not (args.shield and args.shield_horizon >= 1):
         raise SystemExit("--shield-rounds needs --shield and --shield-horizon >= 1: the rounds re-judge the lookahead shield's picks")
+    if not args.scene_jitter >= 0.0:
+        raise SystemExit(f"--scene-jitter must be >= 0 (got {args.scene_jitter})")
+    if args.scene_jitter > 0.0 and args.scenes is None:
+        raise SystemExit("--scene-jitter needs --scenes: it moves the agents off their places in the given scenes")
     return test(args)
 
 
