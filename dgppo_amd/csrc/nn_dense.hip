@@ -1175,6 +1175,7 @@ struct GruBwdWArgs {
   const float* dhs;       // [M,64] dense
   const float* gates;     // [M,256] dense (r | z | n | hn)
   float* dgi_out;         // [M,192] dense
+  GruH0Map hmap;          // n_inner.d > 0: row m of h0 is read through the carry map (nn_gru.h) instead of hprev + m * ldh
 };
 
 // T1: the one-step GRU backward inside the pass.  With T = 1 the scan (gru_bwd_kernel) is elementwise in (dhs, gates, h0), so
@@ -1201,19 +1202,24 @@ __global__ void __launch_bounds__(512) gru_bwd_w_kernel(GruBwdWArgs a) {
   for (int u = 0; u < (T1 ? 4 : 1); ++u) csum[u] = make_float4(0.f, 0.f, 0.f, 0.f);
   const int qa = tid & 31, ra = tid >> 5, qy = tid & 63, ry = tid >> 6;
   const int q1 = tid & 15, r1 = tid >> 4;
+  // T1: h0 may be a record read in place (one address per tile row and thread, two integer divisions; the loads stay 16 bytes)
+  auto hrow = [&](int row) -> const float* {
+    if constexpr (T1) { if (a.hmap.n_inner.d > 0) return gru_h0_map_row(a.hprev, a.hmap, row); }
+    return a.hprev + (size_t)row * a.ldh;
+  };
   auto fetch = [&](int m0) {            // rows clamped; masking happens in commit
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       int row = m0 + u * 16 + ra;
       row = row < a.M ? row : a.M - 1;
-      const float* src = qa < 16 ? a.x + (size_t)row * a.ldx + 4 * qa : a.hprev + (size_t)row * a.ldh + 4 * (qa - 16);
+      const float* src = qa < 16 ? a.x + (size_t)row * a.ldx + 4 * qa : hrow(row) + 4 * (qa - 16);
       pfa[u] = *reinterpret_cast<const float4*>(src);
     }
     if constexpr (T1) {
       int row = m0 + r1;
       row = row < a.M ? row : a.M - 1;
       pfy[0] = *reinterpret_cast<const float4*>(a.dhs + (size_t)row * 64 + 4 * q1);
-      pfy[1] = *reinterpret_cast<const float4*>(a.hprev + (size_t)row * a.ldh + 4 * q1);
+      pfy[1] = *reinterpret_cast<const float4*>(hrow(row) + 4 * q1);
       const float* gs = a.gates + (size_t)row * 256 + 4 * q1;
 #pragma unroll
       for (int g = 0; g < 4; ++g) pfy[2 + g] = *reinterpret_cast<const float4*>(gs + 64 * g);
@@ -1406,6 +1412,23 @@ extern "C" int32_t dgppo_gru_bwd_w_t1(const float* x, int32_t ldx, const float* 
   GruBwdWArgs a{};
   a.x = x; a.ldx = ldx; a.hprev = h0; a.ldh = ldh; a.dhs = dhs; a.gates = gates; a.dgi_out = dgi;
   a.dWi = dWi; a.ldwi = ldwi; a.dbi = dbi; a.dWh = dWh; a.ldwh = ldwh; a.dbhn = dbhn; a.M = M;
+  return gru_bwd_w_launch<true>(a, workspace, workspace_bytes, pending, (hipStream_t)stream);
+}
+
+extern "C" int32_t dgppo_gru_bwd_w_t1_map(const float* x, int32_t ldx, const float* h0, const int32_t* ids, int32_t n_env,
+                                          int32_t n_time, int32_t n_inner, int64_t env_stride, int64_t time_stride,
+                                          const float* dhs, const float* gates, float* dgi, float* dWi, int32_t ldwi,
+                                          float* dbi, float* dWh, int32_t ldwh, float* dbhn, int32_t M, float* workspace,
+                                          int64_t workspace_bytes, dgppo_reduce_desc* pending, void* stream) {
+  GruBwdWArgs a{};
+  a.x = x; a.ldx = ldx; a.hprev = h0; a.ldh = 64; a.dhs = dhs; a.gates = gates; a.dgi_out = dgi;
+  a.dWi = dWi; a.ldwi = ldwi; a.dbi = dbi; a.dWh = dWh; a.ldwh = ldwh; a.dbhn = dbhn; a.M = M;
+  DGPPO_REQUIRE(n_env >= 1 && n_time >= 1 && n_inner >= 1, "gru_bwd_w_t1_map: bad sizes n_env=%d n_time=%d n_inner=%d", n_env,
+                n_time, n_inner);
+  DGPPO_REQUIRE(env_stride % 4 == 0 && time_stride % 4 == 0 && env_stride >= 0 && time_stride >= 0,
+                "gru_bwd_w_t1_map: env_stride and time_stride must be non-negative multiples of 4 floats");
+  DGPPO_REQUIRE((int64_t)M <= (int64_t)n_env * n_time * n_inner, "gru_bwd_w_t1_map: the map holds fewer than M = %d carries", M);
+  a.hmap = gru_h0_map(ids, (long)env_stride, (long)time_stride, n_inner, n_time);
   return gru_bwd_w_launch<true>(a, workspace, workspace_bytes, pending, (hipStream_t)stream);
 }
 

@@ -181,6 +181,7 @@ struct GruArgs {
   int n_seq, T, n_inner;
   int h0_rpb;           // > 0: h0 is blocked — sequence s at h0 + (s / h0_rpb) * h0_bstride + (s % h0_rpb) * 64 (dgppo_gru_fwd_h0_blocks)
   long h0_bstride;
+  GruH0Map h0_map;      // n_inner.d > 0: h0 is a record read through the two-level map of nn_gru.h (dgppo_gru_fwd_h0_map)
 };
 
 __device__ inline size_t gru_row(const GruArgs& a, int s, int tau) {
@@ -229,6 +230,7 @@ __global__ void __launch_bounds__(256) gru_fwd_kernel(GruArgs a) {
       if (a.h0 != nullptr) {
         const float* hp = a.h0 + (size_t)s * GRU_H;
         if (a.h0_rpb > 0) { const int b = s / a.h0_rpb; hp = a.h0 + (size_t)b * a.h0_bstride + (size_t)(s - b * a.h0_rpb) * GRU_H; }
+        else if (a.h0_map.n_inner.d > 0) hp = gru_h0_map_row(a.h0, a.h0_map, s);
         v = reinterpret_cast<const float4*>(hp)[q];
       }
       hpf[u][0] = v.x; hpf[u][1] = v.y; hpf[u][2] = v.z; hpf[u][3] = v.w;
@@ -511,6 +513,24 @@ extern "C" int32_t dgppo_gru_fwd_h0_blocks(const float* gi, const float* Wh, con
   DGPPO_REQUIRE(block_stride >= (int64_t)rows_per_block * GRU_H && block_stride % 4 == 0,
                 "gru_fwd_h0_blocks: block_stride must be a multiple of 4 and >= rows_per_block * 64");
   a.h0_rpb = rows_per_block; a.h0_bstride = (long)block_stride;
+  return gru_fwd_launch(a, (hipStream_t)stream);
+}
+
+extern "C" int32_t dgppo_gru_fwd_h0_map(const float* gi, const float* Wh, const float* bhn, const float* h0,
+                                        const int32_t* ids, int32_t n_env, int32_t n_time, int64_t env_stride,
+                                        int64_t time_stride, float* hs, float* hprev, float* gates, int32_t n_seq,
+                                        int32_t n_inner, void* stream) {
+  GruArgs a{};
+  a.gi = gi; a.Wh = Wh; a.bhn = bhn; a.h0 = h0; a.hs = hs; a.hprev = hprev; a.gates = gates;
+  a.n_seq = n_seq; a.T = 1; a.n_inner = n_inner;
+  DGPPO_REQUIRE(h0 != nullptr && ((uintptr_t)h0 & 15) == 0, "gru_fwd_h0_map: h0 must be a 16-byte aligned pointer");
+  DGPPO_REQUIRE(n_env >= 1 && n_time >= 1 && n_inner >= 1, "gru_fwd_h0_map: bad sizes n_env=%d n_time=%d n_inner=%d", n_env,
+                n_time, n_inner);
+  DGPPO_REQUIRE(env_stride % 4 == 0 && time_stride % 4 == 0 && env_stride >= 0 && time_stride >= 0,
+                "gru_fwd_h0_map: env_stride and time_stride must be non-negative multiples of 4 floats");
+  DGPPO_REQUIRE((int64_t)n_seq <= (int64_t)n_env * n_time * n_inner, "gru_fwd_h0_map: the map holds fewer than n_seq = %d carries",
+                n_seq);
+  a.h0_map = gru_h0_map(ids, (long)env_stride, (long)time_stride, n_inner, n_time);
   return gru_fwd_launch(a, (hipStream_t)stream);
 }
 

@@ -54,7 +54,11 @@ class Hyper:
 
 
 class RolloutData:
-    """Compact rollout record (SURVEY §7 'compact rollout storage'): time-major while collecting, env-major afterwards."""
+    """Compact rollout record (SURVEY §7 'compact rollout storage'): time-major while collecting, env-major afterwards.  The
+    actor carry stays time-major (rnn_tm): the update reads it where the rollout wrote it (ops_nn.H0Map), and the env-major
+    views of it (_rnn_em, rnn_states) are made on first access after a rollout, in a buffer that is allocated once."""
+    _rnn_em_buf = None          # [B, T+2, n, HC], persistent
+    _rnn_em_fresh = False       # _rnn_em_buf holds this rollout's carries
 
     def __init__(self, cfg: N.EnvCfg, B: int, T: int, device, stochastic: bool, carry_dim: int = nets.HID):
         n = cfg.n_agents
@@ -74,7 +78,11 @@ class RolloutData:
             setattr(self, k, self.env.get(k))
         self.action_tm = z(T, B, n, 2)
         self.log_pi_tm = z(T, B, n) if stochastic else None
-        self.rnn_tm = z(T + 1, B, n, carry_dim)          # packed actor carry [h_0 | h_1 | ...] of the stacked cells
+        # packed actor carry [h_0 | h_1 | ...] of the stacked cells: rnn_tm, slots 0..T, is the rollout's.  It is the head of a
+        # [T+2, ...] allocation whose last slot is spare: the value pre-pass puts the final carry behind the T stored ones of
+        # either kind of record and reads all T+1 in place (Engine.values_prepass).
+        self._rnn_all = torch.zeros(T + 2, B, n, carry_dim, device=device)
+        self.rnn_tm = self._rnn_all[:T + 1]
         self.reward_tm = z(T, B)
         self.cost_tm = z(T, B, n, cfg.n_cost)
         self._env_major = False
@@ -100,7 +108,8 @@ class RolloutData:
         for k in OE.ENV_FIELDS:
             setattr(v, k, v.env.get(k))
         cut = lambda x: None if x is None else x[:, :B]
-        v.action_tm, v.log_pi_tm, v.rnn_tm = cut(self.action_tm), cut(self.log_pi_tm), cut(self.rnn_tm)
+        v.action_tm, v.log_pi_tm, v._rnn_all = cut(self.action_tm), cut(self.log_pi_tm), cut(self._rnn_all)
+        v.rnn_tm = v._rnn_all[:self.T + 1]
         v.reward_tm, v.cost_tm = cut(self.reward_tm), cut(self.cost_tm)
         v._env_major = False
         v.states_tm = [OE.State({k: x[t] for k, x in v.step_tm.items()}, v.env) for t in range(self.T + 1)]
@@ -126,21 +135,31 @@ class RolloutData:
             setattr(self, k, self.step[k])
         self.actions = tr("actions", self.action_tm)                  # [B, T, n, 2]
         self.log_pis = tr("log_pis", self.log_pi_tm) if self.stochastic else None
-        # [B, T+2, n, HC]: slots 0..T are the carries of rnn_tm; the spare slot lets the value pre-pass put the final carry
-        # next to the stored ones and read all T+1 of an env in place (Engine.values_prepass)
-        T, x = self.T, self.rnn_tm
-        want = (x.shape[1], T + 2) + tuple(x.shape[2:])
-        cur = getattr(self, "_rnn_em", None)
-        if cur is None or tuple(cur.shape) != want:
-            cur = torch.empty(want, device=x.device, dtype=x.dtype)
-        cur[:, :T + 1].copy_(x.transpose(0, 1))
-        self._rnn_em = cur
-        # stored carry of step t: pre-step (rollout, trainer/utils.py:46-51) or post-step (test_rollout, :71-77)
-        self.rnn_states = self._rnn_em[:, :T] if self.stochastic else self._rnn_em[:, 1:T + 1]
+        self._rnn_em_fresh = False                                    # the carry: _rnn_em / rnn_states, on first access
         self.rewards = tr("rewards", self.reward_tm)                  # [B, T]
         self.costs = tr("costs", self.cost_tm)                        # [B, T, n, n_cost]
         self._env_major = True
         return self
+
+    @property
+    def _rnn_em(self) -> torch.Tensor:
+        """[B, T+2, n, HC]: the env-major copy of the carry record (slot for slot, the spare one included), made on first
+        access after finalize()"""
+        if not self._rnn_em_fresh:
+            x = self._rnn_all
+            want = (x.shape[1], x.shape[0]) + tuple(x.shape[2:])
+            cur = self._rnn_em_buf
+            if cur is None or tuple(cur.shape) != want:
+                cur = torch.empty(want, device=x.device, dtype=x.dtype)
+            cur.copy_(x.transpose(0, 1))
+            self._rnn_em_buf, self._rnn_em_fresh = cur, True
+        return self._rnn_em_buf
+
+    @property
+    def rnn_states(self) -> torch.Tensor:
+        """[B, T, n, HC] stored carry of step t: pre-step (rollout, trainer/utils.py:46-51) or post-step (test_rollout, :71-77)"""
+        T = self.T
+        return self._rnn_em[:, :T] if self.stochastic else self._rnn_em[:, 1:T + 1]
 
 
 class OptState:
@@ -154,7 +173,7 @@ class Engine:
     def __init__(self, cfg: N.EnvCfg, hyper: Hyper, device, T: int = 128,
                  allreduce: Optional[Callable[[torch.Tensor], None]] = None, world: int = 1, prepass_graphs: int = 1 << 20,
                  use_graphs: bool = False, multi_stream: bool = False, algo: str = "dgppo", rank: int = 0,
-                 fused_step: bool = True, lean_attn0: bool = True):
+                 fused_step: bool = True, lean_attn0: bool = True, carry_in_place: bool = True):
         self.cfg, self.hp, self.device, self.T = cfg, hyper, device, T
         assert algo in ("dgppo", "informarl", "hcbfcrpo", "informarl_lagr"), algo
         # "informarl" / "hcbfcrpo": no constraint-value network and no deterministic rollout (informarl.py, hcbfcrpo.py);
@@ -172,6 +191,9 @@ class Engine:
         self.fused_step = bool(fused_step) and OE.act_step_feats_supported(cfg, nets.input_width(cfg), nets.H_HEADS)
         # the first layer's attention without edge features and saved weights (nets.Net); False: the general entry points
         self.lean_attn0 = bool(lean_attn0)
+        # the Vh minibatch pass reads the deterministic record's carry rows in place, through the minibatch's env ids
+        # (ops_nn.H0Map); False: the gathered copy h0_det of every minibatch, as before (tests compare the two)
+        self.carry_in_place = bool(carry_in_place)
         self._ro_cache: Dict[tuple, dict] = {}
         self._upd_graph: dict = {}
         self.n_cost = cfg.n_cost              # 2, or 3 with MPEConnectSpread's connectivity cost
@@ -443,6 +465,19 @@ class Engine:
         st = OE.State({k: v[envs, t0] for k, v in ro.step.items()}, {k: v[envs] for k, v in ro.env.items()})
         return self._feats(tag, st, Eb, n_time, self.T + 1, env_ids)
 
+    def _carry_mapped(self) -> bool:
+        """the Vh minibatch pass reads the deterministic record's carry through ops_nn.H0Map: DGPPO with one actor GRU cell (the stored carry rows are
+        Vh's own 64 floats) on the GPU, unless the engine was built with carry_in_place=False"""
+        return (self.algo == "dgppo" and self.carry_in_place and self.hp.use_rnn and self.HC == nets.HID
+                and self.device.type == "cuda")
+
+    def _mb_carry(self, det: RolloutData, ids: torch.Tensor) -> K.H0Map:
+        """the carry rows the Vh minibatch pass reads for the envs `ids` (int32, on the device): the stored carries of the
+        deterministic record where the rollout wrote them — the post-step carry of step t is slot t + 1 of the time-major
+        record"""
+        tm = det.rnn_tm
+        return K.H0Map(tm[1], tm.stride(1), tm.stride(0), self.T, self.cfg.n_agents, int(ids.numel()), ids=ids, n_env_src=det.B)
+
     def _vh_carry(self, ro: RolloutData, e0: int, Eb: int) -> torch.Tensor:
         """[Eb, T, n, H]: the carry the constraint-value net reads for (env, t), t < T — layer 0 of the actor's stored carry
         of that step (rnn.py:20: rnn_state[0]; pre-step in a stochastic record, post-step in a deterministic one)"""
@@ -453,8 +488,11 @@ class Engine:
         (dgppo.py:222-226)"""
         T, n, HC = self.T, self.cfg.n_agents, self.HC
         fin = self._block_feats("fin", ro, e0, Eb, T, 1)
-        h_last = self.arena.get("pre.hlast", Eb * n, HC)
-        h_last.view(Eb, n, HC).copy_(ro.rnn_states[e0:e0 + Eb, T - 1])
+        if self.carry_in_place:                  # the stored carry of step T - 1, a dense block of the time-major record
+            h_last = ro.rnn_tm[T - 1 if ro.stochastic else T, e0:e0 + Eb].view(Eb * n, HC)
+        else:
+            h_last = self.arena.get("pre.hlast", Eb * n, HC)
+            h_last.view(Eb, n, HC).copy_(ro.rnn_states[e0:e0 + Eb, T - 1])
         hstar = self.arena.get("pre.hstar", Eb * n, HC)
         self.policy.forward(fin, n_seq=Eb * n, T=1, h0=h_last, tag="fin", hs_out=hstar, train=False)
         return hstar
@@ -477,9 +515,23 @@ class Engine:
                 continue
             HC = self.HC
             hstar = self._final_carry(ro, e0, Eb)
+            restore = False
             # the constraint-value net has ONE cell and reads layer 0 of the actor's packed carry (rnn.py:20: rnn_state[0])
             if not self.hp.use_rnn:
                 h0 = None
+            elif HC == H and self.carry_in_place:
+                # the T stored carries of an env lie one time stride apart in the time-major record: the final carry goes into
+                # the slot behind them and the kernel reads all T+1 through the map.  That slot is the spare one (T+1) of a
+                # deterministic record.  In a stochastic record it is slot T, which holds the rollout's carry after the last
+                # step: that waits in the spare slot while Vh reads and is put back below, so outside this function rnn_tm is
+                # always the rollout's.  h_last read the slot before.
+                s0 = 0 if ro.stochastic else 1
+                tm = ro._rnn_all
+                if ro.stochastic:
+                    tm[T + 1, e0:e0 + Eb].copy_(tm[T, e0:e0 + Eb])
+                tm[s0 + T, e0:e0 + Eb].copy_(hstar.view(Eb, n, H))
+                h0 = K.H0Map(tm[s0, e0:], tm.stride(1), tm.stride(0), T + 1, n, Eb, n_env_src=B - e0)
+                restore = ro.stochastic
             elif HC == H:
                 # the T stored carries of an env already lie side by side in the env-major record: the final carry goes into
                 # the slot behind them (slot T of a stochastic record, the spare slot T+1 of a deterministic one — nothing
@@ -494,6 +546,8 @@ class Engine:
                 h0 = h0_all.view(-1, H)
             act = self.Vh.forward(feats, n_seq=Eb * (T + 1) * n, T=1, h0=h0, tag="pre", train=False)
             Vh_buf[e0:e0 + Eb].copy_(act["v"].view(Eb, T + 1, n, nh))
+            if restore:
+                ro._rnn_all[T, e0:e0 + Eb].copy_(ro._rnn_all[T + 1, e0:e0 + Eb])
         return Vl_buf, Vh_buf
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -1305,6 +1359,8 @@ class Engine:
         ro.finalize()
         if self.algo == "dgppo":
             det.finalize()
+            if hp.use_rnn and not self._carry_mapped():
+                det.rnn_states                       # the gathered form reads the env-major copy: made here, not under capture
         assert B * T >= hp.batch_size, "n_env_train * T must be >= batch_size (dgppo.py:153)"
         Eb = hp.batch_size // T
         assert B % Eb == 0 and T % hp.rnn_step == 0, "B % (batch_size // T) == 0 and T % rnn_step == 0 required (SURVEY A.11)"
@@ -1328,8 +1384,11 @@ class Engine:
         act_mb = A.get("mb.act", Eb, T, n, 2)
         lp_old_mb = A.get("mb.lp_old", Eb, T, n)
         adv_mb = A.get("mb.adv", Eb, T, n)
+        # one actor cell of width H: Vh's GRU reads the carry rows of the envs mb_idx32 in the record (_mb_carry); stacked cells
+        # keep the gathered copy of layer 0 (their rows are HC wide, of which Vh reads the first H)
+        h0_mapped = self._carry_mapped()
         if self.algo == "dgppo":
-            h0_det = A.get("mb.h0_det", Eb, T, n, H)
+            h0_det = None if h0_mapped else A.get("mb.h0_det", Eb, T, n, H)
             Qh_det_mb = A.get("mb.Qh_det", Eb, T, n, nh)
         if lagr:
             Qh_mb = A.get("mb.Qh", Eb, T, n, nh)
@@ -1363,7 +1422,9 @@ class Engine:
             if self.algo == "dgppo":
                 feats_det = self._block_feats("mbd", det, 0, Eb, 0, T, env_ids=mb_idx32)
                 full = None
-                if self.HC == H:
+                if h0_mapped:
+                    pass
+                elif self.HC == H:
                     pairs.append((det.rnn_states, h0_det))
                 else:                                          # stacked cells: gather the packed carry, keep layer 0
                     full = A.get("mb.h0_det_full", Eb, T, n, self.HC)
@@ -1390,7 +1451,11 @@ class Engine:
                     act = self.Vh.forward(feats, n_seq=Eb * C * n, T=hp.rnn_step, h0=None, tag="tr")
                     target = Qh_mb
                 else:             # dgppo.py:296-321: the deterministic rollout with its stored carry
-                    act = self.Vh.forward(feats_det, n_seq=R, T=1, h0=h0_det.view(R, H) if hp.use_rnn else None, tag="tr")
+                    if h0_mapped:
+                        h0 = self._mb_carry(det, mb_idx32)
+                    else:
+                        h0 = h0_det.view(R, H) if hp.use_rnn else None
+                    act = self.Vh.forward(feats_det, n_seq=R, T=1, h0=h0, tag="tr")
                     target = Qh_det_mb
                 dvh = A.get("mb.dvh", R, nh)
                 K.value_loss(act["v"], target.view(R, nh), dvh, self.stats[1])
@@ -1466,6 +1531,7 @@ class Engine:
         slot = None
         if self.use_graphs and is_cuda and self.grad_hook is None:
             key = (self.algo, B, Eb, ro.agent.data_ptr(), det.agent.data_ptr() if det is not None else 0,
+                   det.rnn_tm.data_ptr() if det is not None else 0,
                    tg["adv"].data_ptr(), tg["Ql"].data_ptr(), mb_idx32.data_ptr(), self._update_generation())
             slot = self._upd_graph
             if slot.get("key") != key:

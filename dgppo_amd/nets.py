@@ -378,7 +378,11 @@ class Net:
         if h0_blocks:
             assert self.rnn == "gru" and L == 1 and T == 1 and not train and self.kind != "policy", \
                 "a blocked h0 serves the one-cell GRU value nets' T = 1 inference pass"
-        elif h0 is not None:
+        h0_map = isinstance(h0, K.H0Map)            # the carry read in place through a map, ids included (Vh's minibatch pass)
+        if h0_map:
+            assert self.rnn == "gru" and L == 1 and T == 1 and self.kind != "policy" and h0.n_inner == n_inner, \
+                "a mapped h0 serves the one-cell GRU value nets' T = 1 passes"
+        elif h0 is not None and not h0_blocks:
             assert tuple(h0.shape) == (n_seq, CD), (tuple(h0.shape), n_seq, CD)
         if hs_out is not None:
             assert tuple(hs_out.shape) == (Rh, CD), (tuple(hs_out.shape), Rh, CD)
@@ -399,6 +403,8 @@ class Net:
         if simple and not fused_tail:
             if h0_blocks:
                 K.gru_fwd_h0_blocks(gi, self.p("gru.Wh"), self.p("gru.bhn"), h0, hs, hprev, gates, n_seq, T, n_inner)
+            elif h0_map:
+                K.gru_fwd_h0_map(gi, self.p("gru.Wh"), self.p("gru.bhn"), h0, hs, hprev, gates, n_seq, T, n_inner)
             else:
                 K.gru_fwd(gi, self.p("gru.Wh"), self.p("gru.bhn"), h0, hs, hprev, gates, n_seq, T, n_inner)
             if hprev_is_h0:
@@ -509,9 +515,10 @@ class Net:
 
     @staticmethod
     def _gru_t1_in_pass(act, T, row_operands) -> bool:
-        """gru_bwd_w_t1 applies: one step whose saved hprev IS the given h0, all row operands on the GPU and 16-byte aligned"""
+        """gru_bwd_w_t1 applies: one step whose saved hprev IS the given h0, all row operands on the GPU and 16-byte aligned (a
+        mapped h0 is no tensor: the library checks its base and strides)"""
         return (T == 1 and act.get("h0") is not None and act["hprev"] is act["h0"]
-                and all(t.is_cuda and t.data_ptr() % 16 == 0 for t in row_operands))
+                and all(isinstance(t, K.H0Map) or (t.is_cuda and t.data_ptr() % 16 == 0) for t in row_operands))
 
     def _backward_body(self, act, dout: torch.Tensor, tag: str):
         cfg, A = self.cfg, self.arena
@@ -568,6 +575,8 @@ class Net:
                     # one step from h0: the scan is elementwise, so the weight-gradient pass forms the gate gradients itself
                     K.gru_bwd_w_t1(act["y2"], st["hprev"], dhs, st["gates"], dgi, *gW)
                 else:
+                    if isinstance(st["hprev"], K.H0Map):
+                        raise RuntimeError("a mapped h0 is read by gru_bwd_w_t1 alone: its row operands must be 16-byte aligned")
                     dhn = A.get(f"{tag}.dhn0", Rh, HID)
                     K.gru_bwd_dhn(dhs, self.p("gru.Wh"), st["hprev"], st["gates"], dgi, dhn, n_seq, T, n_inner)
                     K.gru_bwd_w(act["y2"], st["hprev"], dgi, dhn, *gW)

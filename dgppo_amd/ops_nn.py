@@ -910,6 +910,65 @@ def gru_fwd_h0_blocks(gi, Wh, bhn, h0: H0Blocks, hs, hprev, gates, n_seq, T, n_i
     N.check(rc, "dgppo_gru_fwd_h0_blocks")
 
 
+class H0Map:
+    """initial GRU carry of a T = 1 pass read in place from a record (dgppo_gru_fwd_h0_map, dgppo_gru_bwd_w_t1_map): sequence s
+    is cell c = s // n_inner, agent a = s % n_inner, the cell is (e, t) = (c // n_time, c % n_time), and its carry lies at
+    base + env * env_stride + t * time_stride + a * 64 floats, env = ids[e] if ids is given else e.  `base` is any float32
+    CUDA view whose first element is that of (env 0, t 0, agent 0) (it keeps the storage alive); n_env_src = the envs of the
+    record (every id must be below it: the caller vouches for that, the ids live on the device); n_env = the envs of the pass
+    (len(ids) with ids)."""
+
+    def __init__(self, base: torch.Tensor, env_stride: int, time_stride: int, n_time: int, n_inner: int, n_env: int,
+                 ids: Optional[torch.Tensor] = None, n_env_src: Optional[int] = None):
+        assert base.dtype == torch.float32 and base.is_cuda
+        if ids is not None:
+            if ids.dtype != torch.int32 or not ids.is_cuda or not ids.is_contiguous() or ids.dim() != 1:
+                raise TypeError("H0Map: ids must be a contiguous 1-d int32 CUDA tensor")
+            if int(ids.numel()) != n_env:
+                raise ValueError(f"H0Map: {int(ids.numel())} ids for {n_env} envs")
+        n_env_src = int(n_env if n_env_src is None else n_env_src)
+        assert n_env >= 1 and n_time >= 1 and n_inner >= 1 and n_env_src >= 1 and env_stride >= 0 and time_stride >= 0
+        st = base.untyped_storage()
+        last = base.storage_offset() + (n_env_src - 1) * env_stride + (n_time - 1) * time_stride + n_inner * 64
+        assert last * 4 <= st.nbytes(), "H0Map: the mapped rows leave the storage of base"
+        self.base, self.ids = base, ids
+        self.env_stride, self.time_stride = int(env_stride), int(time_stride)
+        self.n_time, self.n_inner, self.n_env = int(n_time), int(n_inner), int(n_env)
+
+    @property
+    def n_seq(self) -> int:
+        return self.n_env * self.n_time * self.n_inner
+
+    def dense(self) -> torch.Tensor:
+        """[n_seq, 64]: the gathered copy of the mapped rows (tests, tools)"""
+        dev = self.base.device
+        e = self.ids.long() if self.ids is not None else torch.arange(self.n_env, device=dev)
+        t = torch.arange(self.n_time, device=dev)
+        a = torch.arange(self.n_inner, device=dev)
+        off = (e[:, None, None] * self.env_stride + t[None, :, None] * self.time_stride + a[None, None, :] * 64).reshape(-1)
+        flat = torch.as_strided(self.base, (self.base.untyped_storage().nbytes() // 4 - self.base.storage_offset(),), (1,))
+        return flat[(off[:, None] + torch.arange(64, device=dev)[None, :])].contiguous()
+
+    def _args(self):
+        return (C.c_void_p(self.base.data_ptr()), C.c_void_p(self.ids.data_ptr()) if self.ids is not None else None,
+                self.n_env, self.n_time)
+
+
+def gru_fwd_h0_map(gi, Wh, bhn, h0: H0Map, hs, hprev, gates, n_seq, T, n_inner):
+    if T != 1 or n_inner != h0.n_inner:
+        raise ValueError(f"a mapped h0 serves one-step passes of its own n_inner = {h0.n_inner} (got T = {T}, n_inner = {n_inner})")
+    N.expect_shape(gi, (n_seq, 192), "gi")
+    N.expect_shape(hs, (n_seq, 64), "hs")
+    N.expect_shape(Wh, (64, 192), "Wh")
+    if n_seq > h0.n_seq:
+        raise ValueError(f"h0: the map holds {h0.n_seq} carries, fewer than n_seq = {n_seq}")
+    FLOPS[0] += 2.0 * n_seq * 64 * 192
+    base, ids, n_env, n_time = h0._args()
+    rc = N.lib().dgppo_gru_fwd_h0_map(_p(gi), _p(Wh), _p(bhn), base, ids, n_env, n_time, C.c_int64(h0.env_stride),
+                                      C.c_int64(h0.time_stride), _p(hs), _p(hprev), _p(gates), n_seq, n_inner, N.stream_ptr())
+    N.check(rc, "dgppo_gru_fwd_h0_map")
+
+
 class GatherDesc(C.Structure):
     """struct dgppo_gather_desc"""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64), ("src_stride", C.c_int64)]
@@ -965,11 +1024,17 @@ def gru_bwd_dhn(dhs, Wh, hprev, gates, dgi, dhn, n_seq, T, n_inner):
 def _gru_bwd_w_call(name, x, hprev, rows_in, dgi, dWi, dbi, dWh, dbhn):
     """the common part of gru_bwd_w / gru_bwd_w_t1: rows_in = the dense row operands between hprev and the outputs"""
     xp, ldx, M, Kx = _mat(x, "x")
-    hp, ldh, Mh, Kh = _mat(hprev, "hprev")
+    hmap = hprev if isinstance(hprev, H0Map) else None      # gru_bwd_w_t1 alone: h0 read through the carry map
+    if hmap is not None:
+        if x.shape[0] > hmap.n_seq:
+            raise ValueError(f"{name}: the map holds {hmap.n_seq} carries, fewer than M = {x.shape[0]}")
+        Mh, Kh = x.shape[0], 64
+    else:
+        hp, ldh, Mh, Kh = _mat(hprev, "hprev")
     wip, ldwi, _, _ = _mat(dWi, "dWi")
     whp, ldwh, _, _ = _mat(dWh, "dWh")
     if Kx != 64 or (Mh, Kh) != (M, 64) or tuple(dWi.shape) != (64, 192) or tuple(dWh.shape) != (64, 192):
-        raise ValueError(f"{name}: shape mismatch x{tuple(x.shape)} hprev{tuple(hprev.shape)} dWi{tuple(dWi.shape)} "
+        raise ValueError(f"{name}: shape mismatch x{tuple(x.shape)} hprev{(Mh, Kh)} dWi{tuple(dWi.shape)} "
                          f"dWh{tuple(dWh.shape)}")
     for nm, (t, w) in rows_in.items():
         N.expect_shape(t, (M, w), nm)
@@ -994,7 +1059,13 @@ def _gru_bwd_w_call(name, x, hprev, rows_in, dgi, dWi, dbi, dWh, dbhn):
         mid = [_p(dgi, "dgi")] + mid               # (x, hprev, dgi, dhn, outputs)
     else:
         mid = mid + [_p(dgi, "dgi")]               # (x, h0, dhs, gates, dgi, outputs)
-    rc = getattr(lib, name)(xp, ldx, hp, ldh, *mid, wip, ldwi, _p(dbi, "dbi"), whp, ldwh, _p(dbhn, "dbhn"), M,
+    if hmap is not None:
+        base, ids, n_env, n_time = hmap._args()
+        name = "dgppo_gru_bwd_w_t1_map"
+        h_args = (base, ids, n_env, n_time, hmap.n_inner, C.c_int64(hmap.env_stride), C.c_int64(hmap.time_stride))
+    else:
+        h_args = (hp, ldh)
+    rc = getattr(lib, name)(xp, ldx, *h_args, *mid, wip, ldwi, _p(dbi, "dbi"), whp, ldwh, _p(dbhn, "dbhn"), M,
                             _p(ws, "workspace"), C.c_int64(ws.numel() * 4), pend, N.stream_ptr())
     N.check(rc, name)
     if batch is not None:
@@ -1011,7 +1082,8 @@ def gru_bwd_w(x, hprev, dgi, dhn, dWi, dbi, dWh, dbhn):
 
 def gru_bwd_w_t1(x, h0, dhs, gates, dgi, dWi, dbi, dWh, dbhn):
     """gru_bwd_dhn(T = 1, hprev = h0) and gru_bwd_w in one pass: writes dgi [M,192] (the bits gru_bwd_dhn writes) and
-    accumulates the four GRU gradients; dhn stays on chip.  The gate gradients are elementwise: no product is counted."""
+    accumulates the four GRU gradients; dhn stays on chip.  The gate gradients are elementwise: no product is counted.
+    h0: [M, 64] rows, or an H0Map (both reads of the rows go through the map: dgppo_gru_bwd_w_t1_map)."""
     _gru_bwd_w_call("dgppo_gru_bwd_w_t1", x, h0, {"dhs": (dhs, 64), "gates": (gates, 256)}, dgi, dWi, dbi, dWh, dbhn)
 
 

@@ -682,6 +682,16 @@ int32_t dgppo_gru_fwd(const float* gi, const float* Wh, const float* bhn, const 
 int32_t dgppo_gru_fwd_h0_blocks(const float* gi, const float* Wh, const float* bhn, const float* h0,
                                 int32_t rows_per_block, int64_t block_stride, float* hs, float* hprev, float* gates,
                                 int32_t n_seq, int32_t T, int32_t n_inner, void* stream);
+/* The one-step pass (T = 1) with h0 read in place through a two-level map with an optional id list: sequence s is cell
+ * c = s / n_inner, agent a = s % n_inner, the cell is (e, t) = (c / n_time, c % n_time), and its carry lies at
+ * h0 + env * env_stride + t * time_stride + a * 64, env = ids ? ids[e] : e (floats).  ids: n_env int32 env numbers on the
+ * device (the caller vouches that each addresses the record) or NULL; n_seq <= n_env * n_time * n_inner.  h0 16-byte
+ * aligned and both strides multiples of 4, anything else is refused.  time_stride = n_inner * 64 without ids is
+ * dgppo_gru_fwd_h0_blocks with rows_per_block = n_time * n_inner.  The Vh minibatch pass reads the carry record of the
+ * deterministic rollout this way, through the minibatch's env ids, instead of a gathered copy.                          */
+int32_t dgppo_gru_fwd_h0_map(const float* gi, const float* Wh, const float* bhn, const float* h0, const int32_t* ids,
+                             int32_t n_env, int32_t n_time, int64_t env_stride, int64_t time_stride, float* hs,
+                             float* hprev, float* gates, int32_t n_seq, int32_t n_inner, void* stream);
 /* BPTT over the T steps of every sequence: dgi [rows,192], dgh [rows,192] (then dWh = hprev^T dgh).               */
 int32_t dgppo_gru_bwd(const float* dhs, const float* Wh, const float* hprev, const float* gates, float* dgi,
                       float* dgh, int32_t n_seq, int32_t T, int32_t n_inner, void* stream);
@@ -709,6 +719,13 @@ int32_t dgppo_gru_bwd_w(const float* x, int32_t ldx, const float* hprev, int32_t
 int32_t dgppo_gru_bwd_w_t1(const float* x, int32_t ldx, const float* h0, int32_t ldh, const float* dhs, const float* gates,
                            float* dgi, float* dWi, int32_t ldwi, float* dbi, float* dWh, int32_t ldwh, float* dbhn, int32_t M,
                            float* workspace, int64_t workspace_bytes, dgppo_reduce_desc* pending, void* stream);
+/* dgppo_gru_bwd_w_t1 with row m of h0 read through the map of dgppo_gru_fwd_h0_map (both of its reads: the operand of dWh and
+ * the gate gradients); M <= n_env * n_time * n_inner.  Every value and every sum is that of dgppo_gru_bwd_w_t1 on the gathered
+ * dense copy of the same rows.                                                                                                  */
+int32_t dgppo_gru_bwd_w_t1_map(const float* x, int32_t ldx, const float* h0, const int32_t* ids, int32_t n_env, int32_t n_time,
+                               int32_t n_inner, int64_t env_stride, int64_t time_stride, const float* dhs, const float* gates,
+                               float* dgi, float* dWi, int32_t ldwi, float* dbi, float* dWh, int32_t ldwh, float* dbhn,
+                               int32_t M, float* workspace, int64_t workspace_bytes, dgppo_reduce_desc* pending, void* stream);
 
 /* LSTM scan (train.py --use-lstm; dgppo/nn/rnn.py:22-24 with flax nn.LSTMCell(64): i,f,o sigmoid, g tanh, c' = f c + i g,
  * h' = o tanh(c'), carry (c, h)).  zi [rows,256] = x [W_ii|W_if|W_ig|W_io] precomputed (flax's input Denses have no bias);

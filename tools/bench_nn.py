@@ -115,6 +115,74 @@ if which in ("all", "gruw1"):
         timeit(f"GRU T=1 bwd: gru_bwd_dhn + gru_bwd_w M={M}", pair, iters=50, bytes_=4.0 * M * (384 + 256 + 256 + 384))
         if hasattr(K, "gru_bwd_w_t1"):
             timeit(f"GRU T=1 bwd: gru_bwd_w_t1 M={M}", one, iters=50, bytes_=4.0 * M * (64 + 64 + 64 + 256 + 192))
+if which in ("all", "h0map"):
+    # Vh's minibatch pair (T = 1 forward + weight-gradient pass) at 131 072 rows from the carry record of 4096 envs x 128 steps x
+    # 8 agents: the gathered copy (gather_rows of 128 env rows included) against the map over the env-major and over the
+    # time-major record through the same ids.  Also the value pre-pass read (528 384 graphs, 129 slots per env): the env-major blocks against the time-major map.
+    # Three repeats, alternating
+    Bm, Tm, nm, Em = 4096, 128, 8, 128
+    M = Em * Tm * nm
+    tm = torch.randn(Tm + 2, Bm, nm, 64, device=dev)
+    em = tm.transpose(0, 1).contiguous()                       # [B, T+2, n, 64], what finalize() used to make
+    ids = torch.randperm(Bm, device=dev)[:Em].to(torch.int32)
+    Wh = torch.randn(64, 192, device=dev) * 0.1; bh = torch.zeros(64, device=dev)
+    gi = torch.randn(M, 192, device=dev); hs = torch.empty(M, 64, device=dev); gt = torch.empty(M, 256, device=dev)
+    x = torch.randn(M, 64, device=dev); dhs = torch.randn(M, 64, device=dev); dgi = torch.empty(M, 192, device=dev)
+    dW = [torch.zeros(64, 192, device=dev), torch.zeros(192, device=dev), torch.zeros(64, 192, device=dev), torch.zeros(64, device=dev)]
+    wsbuf = torch.empty(16 << 20, device=dev)
+    h0g = torch.empty(Em, Tm, nm, 64, device=dev)
+    hmap = K.H0Map(tm[1], tm.stride(1), tm.stride(0), Tm, nm, Em, ids=ids, n_env_src=Bm)
+
+    def gathered():
+        K.gather_rows([(em[:, 1:Tm + 1], h0g)], ids)
+        K.gru_fwd(gi, Wh, bh, h0g.view(M, 64), hs, None, gt, M, 1, nm)
+        with K.BwdWBatch(dev, lambda n: wsbuf):
+            K.gru_bwd_w_t1(x, h0g.view(M, 64), dhs, gt, dgi, *dW)
+
+    rs = em[:, 1:Tm + 1]
+    hmap_em = K.H0Map(rs, rs.stride(0), rs.stride(1), Tm, nm, Em, ids=ids, n_env_src=Bm)
+
+    def mapped(m):
+        K.gru_fwd_h0_map(gi, Wh, bh, m, hs, None, gt, M, 1, nm)
+        with K.BwdWBatch(dev, lambda n: wsbuf):
+            K.gru_bwd_w_t1(x, m, dhs, gt, dgi, *dW)
+    for rep in range(3):
+        timeit(f"Vh T=1 pair M={M}: gather + dense h0", gathered, iters=50)
+        timeit(f"Vh T=1 pair M={M}: mapped h0 (env-major, ids)", lambda: mapped(hmap_em), iters=50)
+        timeit(f"Vh T=1 pair M={M}: mapped h0 (time-major, ids)", lambda: mapped(hmap), iters=50)
+    Ep = Bm
+    Mp = Ep * (Tm + 1) * nm
+    gip = torch.randn(Mp, 192, device=dev); hsp = torch.empty(Mp, 64, device=dev)
+    blocks = K.H0Blocks(em[0, 0], (Tm + 1) * nm, (Tm + 2) * nm * 64, Ep)
+    pmap = K.H0Map(tm[0], tm.stride(1), tm.stride(0), Tm + 1, nm, Ep, n_env_src=Bm)
+    for rep in range(3):
+        timeit(f"pre-pass gru_fwd M={Mp}: env-major blocks", lambda: K.gru_fwd_h0_blocks(gip, Wh, bh, blocks, hsp, None, None, Mp, 1, nm),
+               iters=50, bytes_=4.0 * Mp * 320)
+        timeit(f"pre-pass gru_fwd M={Mp}: time-major map", lambda: K.gru_fwd_h0_map(gip, Wh, bh, pmap, hsp, None, None, Mp, 1, nm),
+               iters=50, bytes_=4.0 * Mp * 320)
+if which in ("all", "featlayout"):
+    # dgppo_graph_feats reading the env-major record [B, T+1, ...] against the time-major one [T+1, B, ...] (env and time stride
+    # swapped): the minibatch form (128 envs by ids x 128 steps = 16 384 graphs) and the pre-pass form (4096 envs x 129 steps =
+    # 528 384 graphs), LidarSpread n = 8 / 3 obstacles.  Three repeats each, alternating
+    from dgppo_amd import nets
+    cfg = N.make_env_cfg(0, 8, 3)
+    Bm, Tm, nm = 4096, 128, 8
+    ag_tm = torch.rand(Tm + 1, Bm, nm, cfg.state_dim, device=dev) * 2.0
+    hi_tm = ag_tm[..., None, :2] + 0.3 * torch.rand(Tm + 1, Bm, nm, cfg.top_k, 2, device=dev)
+    ag_em, hi_em = ag_tm.transpose(0, 1).contiguous(), hi_tm.transpose(0, 1).contiguous()
+    goal = torch.rand(Bm, nm, cfg.state_dim, device=dev) * 2.0
+    obst = torch.rand(Bm, 3, 16, device=dev)
+    ids = torch.randperm(Bm, device=dev)[:128].to(torch.int32)
+    ia, ih = nm * cfg.state_dim, nm * cfg.top_k * 2
+    arena = nets.Arena(dev)
+    for n_env, n_time, use_ids in ((128, Tm, True), (Bm, Tm + 1, False)):
+        f = nets.GraphFeats(cfg, n_env * n_time, arena, "bench")
+        e_ids = ids if use_ids else None
+        em = lambda: f.compute(ag_em, (Tm + 1) * ia, ia, goal, obst, hi_em, (Tm + 1) * ih, ih, e_ids, n_env, n_time)
+        tmj = lambda: f.compute(ag_tm, ia, Bm * ia, goal, obst, hi_tm, ih, Bm * ih, e_ids, n_env, n_time)
+        for rep in range(3):
+            timeit(f"graph_feats G={n_env * n_time}: env-major record", em, iters=20)
+            timeit(f"graph_feats G={n_env * n_time}: time-major record", tmj, iters=20)
 if which in ("all", "xw"):
     # both gradients of a GNN glue Dense: dense_bwd_w + dense_fwd(W^T) against the one dense_bwd_xw call, per site of
     # Net._backward_body; inside a BwdWBatch (kernel plus its share of the batched reduce).  Three repeats, alternating
