@@ -203,6 +203,9 @@ def lib() -> C.CDLL:
     # the scene loader (csrc/env_scene.hip): the jitter travels by value
     l.dgppo_env_scene_load.restype = i32
     l.dgppo_env_scene_load.argtypes = [C.POINTER(EnvCfg), p, p, p, i32, p, p, f32, p, p, p, p, p, i32, p]
+    # the scene mix of a training batch (same file, same operand order: scene_of in place of scene_ids)
+    l.dgppo_env_scene_mix.restype = i32
+    l.dgppo_env_scene_mix.argtypes = [C.POINTER(EnvCfg), p, p, p, i32, p, p, f32, p, p, p, p, p, i32, p]
     _lib = l
     return l
 

@@ -219,18 +219,27 @@ class DGPPO(Algorithm):
             return keys.to(self.device, torch.int64)
         return torch.from_numpy(np.ascontiguousarray(np.asarray(keys).astype(np.uint64).view(np.int64))).to(self.device)
 
-    def _scene_start(self, scenes, scene_ids, jitter, B_local: int):
+    def _scene_start(self, scenes, scene_ids, jitter, B_local: int, scene_of=None):
         """the engine's `start` of a collect call: None without scenes (the sampled reset), else (scenes, ids, jitter).  Episode b
         starts in scene scene_ids[b]; without a list, in scene g % S of its GLOBAL env index g = rank * B_local + b, so that the
-        union over the ranks is what one device would run for the global batch."""
+        union over the ranks is what one device would run for the global batch.  scene_of (one int per key, this rank's window
+        of env.scenes.mix_assignment) asks for a mix instead: episode b starts at its sampled reset where scene_of[b] < 0 and in
+        scene scene_of[b] otherwise (env.scenes.SceneMix)."""
         if scenes is None:
-            if scene_ids is not None or float(jitter) != 0.0:
-                raise ValueError("scene_ids / jitter need scenes: without them the episodes start at the sampled reset")
+            if scene_ids is not None or scene_of is not None or float(jitter) != 0.0:
+                raise ValueError("scene_ids / scene_of / jitter need scenes: without them the episodes start at the sampled reset")
             return None
+        if scene_of is not None:
+            if scene_ids is not None:
+                raise ValueError("scene_of and scene_ids exclude each other: a mix names every env's scene itself")
+            if np.shape(scene_of) != (B_local,):
+                raise ValueError(f"scene_of must have one entry per key ({B_local}), got shape {np.shape(scene_of)}")
         cfg, mine = scenes.cfg, self._env.cfg
         if (cfg.kind, cfg.n_agents, cfg.n_obs) != (mine.kind, mine.n_agents, mine.n_obs):
             raise ValueError(f"scenes of env kind {cfg.kind} with {cfg.n_agents} agents and {cfg.n_obs} obstacles do not fit this "
                              f"algo's env (kind {mine.kind}, {mine.n_agents} agents, {mine.n_obs} obstacles)")
+        if scene_of is not None:
+            return scenes.mix(scene_of, jitter)
         if scene_ids is None and self.world > 1:
             scene_ids = (self.rank * B_local + np.arange(B_local)) % scenes.S
         return scenes.start(scene_ids, jitter)
@@ -244,13 +253,14 @@ class DGPPO(Algorithm):
         self._last_rollouts[id(r.actions)] = ro
         return r
 
-    def collect(self, params, keys, scenes=None, scene_ids=None, jitter: float = 0.0) -> Rollout:
+    def collect(self, params, keys, scenes=None, scene_ids=None, jitter: float = 0.0, scene_of=None) -> Rollout:
         """algo.collect(params, keys): one stochastic rollout per key (informarl.py:254-256).  scenes (env.Scenes): the
         episodes — and those of the deterministic companion rollout — start in the given scenes instead of at the sampled
-        reset (_scene_start); not in the reference."""
+        reset (_scene_start); with scene_of only the envs it names do, and the companion rollout gets the same mix with its own
+        seeds.  Not in the reference."""
         self._maybe_load(params)
         seeds = self._seeds(keys)
-        start = self._scene_start(scenes, scene_ids, jitter, int(seeds.shape[0]))
+        start = self._scene_start(scenes, scene_ids, jitter, int(seeds.shape[0]), scene_of)
         # the deterministic rollout that update() needs for the constraint-value targets (dgppo.py:139-141) uses the same
         # parameters as this collect: it is launched alongside on a second stream and handed to update()
         det_seeds = self._seeds(self._draw_keys(int(seeds.shape[0])))

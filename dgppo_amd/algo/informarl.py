@@ -61,13 +61,13 @@ class InforMARL(DGPPO):
         e = self.engine
         return {"policy": e.policy.to_tree(), "Vl": e.Vl.to_tree()}
 
-    def collect(self, params, keys, scenes=None, scene_ids=None, jitter: float = 0.0):
-        """one stochastic rollout per key (informarl.py:254-256); no deterministic companion rollout.  scenes as in
-        DGPPO.collect"""
+    def collect(self, params, keys, scenes=None, scene_ids=None, jitter: float = 0.0, scene_of=None):
+        """one stochastic rollout per key (informarl.py:254-256); no deterministic companion rollout.  scenes and scene_of as
+        in DGPPO.collect"""
         self._maybe_load(params)
         seeds = self._seeds(keys)
         ro = self.engine.rollout(seeds, True, noise_seed=int(self._rng.integers(1, 2 ** 62)),
-                                 start=self._scene_start(scenes, scene_ids, jitter, int(seeds.shape[0])))
+                                 start=self._scene_start(scenes, scene_ids, jitter, int(seeds.shape[0]), scene_of))
         return self._wrap(ro)
 
     def update(self, rollout, step: int) -> dict:

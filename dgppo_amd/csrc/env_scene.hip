@@ -9,7 +9,10 @@
 //              from the stream of env_reset.hip (Philox(counter=(d,0,0,0), key=(lo32 seed, hi32 seed)), words 0, 1), always
 //              measured from the template; the first attempt whose scene is valid is kept
 //   flags      0 = valid; DGPPO_SCENE_* bits otherwise
+// The second half of the file, dgppo_env_scene_mix, puts SOME envs of a batch that holds a reset into such scenes (training on a
+// mix of sampled and given starts): one wave per environment, and nothing of an env is written unless its scene is valid.
 // Built with -ffp-contract=off like env_reset.hip.
+#include <stdio.h>
 #include "env_step.h"
 
 #define SCENE_MAX_AGENTS 64
@@ -61,6 +64,21 @@ __device__ inline int scene_geometry(const dgppo_env_cfg& c, const float* agent,
   return bits;
 }
 
+// one rectangle template row (cx, cy, w, h, theta) -> its 16-float record: the record of env_reset_kernel, statement for
+// statement.  Shared by the two kernels below, so that their records cannot differ
+__device__ inline void scene_rect_record(const float* t, float* rec) {
+  const float cx = t[0], cy = t[1], w = t[2], h = t[3], th = t[4];
+  float cs = cosf(th), sn = sinf(th);
+  rec[0] = cx; rec[1] = cy; rec[2] = w; rec[3] = h; rec[4] = th; rec[5] = cs; rec[6] = sn; rec[7] = 0.0f;
+  float hw = w / 2.0f, hh = h / 2.0f;
+  float bx[4] = {hw, -hw, -hw, hw};
+  float by[4] = {hh, hh, -hh, -hh};
+  for (int m = 0; m < 4; ++m) {  // obstacle.py:40-54
+    rec[8 + 2 * m] = (cs * bx[m] + (-sn) * by[m]) + cx;
+    rec[9 + 2 * m] = (sn * bx[m] + cs * by[m]) + cy;
+  }
+}
+
 __global__ void env_scene_load_kernel(SceneArgs a) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= a.B) return;
@@ -84,19 +102,8 @@ __global__ void env_scene_load_kernel(SceneArgs a) {
   for (int i = 0; i < n * SD; ++i) ((uint32_t*)agent)[i] = ((const uint32_t*)agent_t)[i];
 
   for (int o = 0; o < no; ++o) {
-    if (lidar) {                                         // the record of env_reset_kernel, statement for statement
-      const float* t = obst_t + o * 5;
-      const float cx = t[0], cy = t[1], w = t[2], h = t[3], th = t[4];
-      float cs = cosf(th), sn = sinf(th);
-      float* rec = obst + o * DGPPO_RECT_STRIDE;
-      rec[0] = cx; rec[1] = cy; rec[2] = w; rec[3] = h; rec[4] = th; rec[5] = cs; rec[6] = sn; rec[7] = 0.0f;
-      float hw = w / 2.0f, hh = h / 2.0f;
-      float bx[4] = {hw, -hw, -hw, hw};
-      float by[4] = {hh, hh, -hh, -hh};
-      for (int m = 0; m < 4; ++m) {  // obstacle.py:40-54
-        rec[8 + 2 * m] = (cs * bx[m] + (-sn) * by[m]) + cx;
-        rec[9 + 2 * m] = (sn * bx[m] + cs * by[m]) + cy;
-      }
+    if (lidar) {
+      scene_rect_record(obst_t + o * 5, obst + o * DGPPO_RECT_STRIDE);
     } else {                                             // mpe/base.py:121
       for (int d = 0; d < SD; ++d) obst[o * SD + d] = 0.0f;
       obst[o * SD] = obst_t[o * 2];
@@ -143,6 +150,170 @@ extern "C" int32_t dgppo_env_scene_load(const dgppo_env_cfg* cfg, const float* a
   a.cfg = *cfg; a.agent_t = agent_t; a.goal_t = goal_t; a.obst_t = obst_t; a.S = S; a.scene_ids = scene_ids; a.seeds = seeds;
   a.jitter = jitter; a.agent = agent; a.goal = goal; a.obst = obst; a.flags = flags; a.n_failed = n_failed; a.B = B;
   hipLaunchKernelGGL(env_scene_load_kernel, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- dgppo_env_scene_mix: the scene start of SOME envs of a batch that already holds a valid reset ---------------------------
+// One wave64 per env, lane i = agent i (SCENE_MAX_AGENTS is the wave width) and, for the obstacle records, lane o = obstacle o
+// (n_obs <= 64, dgppo_validate_cfg).  The candidate position and the obstacle record live in registers; a lane reads the other
+// agents' positions and the obstacles' words through __shfl, and the validity bits are folded with __any, so the attempt loop
+// and the commit are wave-uniform: no LDS, no barrier.  Draws, expressions, attempts and bits are env_scene_load_kernel's.
+// Nothing of the record is written before the verdict: an env whose scene stays invalid keeps its reset.
+#define SCENE_MIX_WAVES 4                                 // waves (envs) per 256-thread block
+
+struct SceneMixArgs {
+  dgppo_env_cfg cfg;
+  const float* agent_t;
+  const float* goal_t;
+  const float* obst_t;
+  int S;
+  const int32_t* scene_of;
+  const uint64_t* seeds;
+  float jitter;
+  float* agent;
+  float* goal;
+  float* obst;
+  int32_t* flags;
+  int* n_fallback;
+  int B;
+};
+
+// any lane's word of p[0 .. n_words) not finite?  (lanes stride over the words)
+__device__ inline bool scene_wave_nonfinite(const float* p, int n_words, int lane) {
+  bool bad = false;
+  for (int i = lane; i < n_words; i += 64) bad = bad || !isfinite(p[i]);
+  return __any(bad);
+}
+
+// the geometric bits of scene_geometry for the wave's candidate: lane i < n holds agent i at (x, y); lane o < n_obs holds
+// obstacle o's record in rec (LiDAR) or its centre in rec[0], rec[1] (MPE).  The pair (i, j > i) is tested by lane i
+__device__ inline int scene_wave_geometry(const dgppo_env_cfg& c, int lane, float x, float y, const float* rec, bool lidar) {
+  const int n = c.n_agents, no = c.n_obs;
+  const bool mine = lane < n;
+  const bool out = mine && (x < 0.0f || x > c.area_size || y < 0.0f || y > c.y_limit);
+  bool overlap = false, inside = false;
+  for (int j = 1; j < n; ++j) {
+    const float dx = x - __shfl(x, j), dy = y - __shfl(y, j);
+    if (mine && j > lane && sqrtf(dx * dx + dy * dy) < c.two_car_radius) overlap = true;
+  }
+  for (int o = 0; o < no; ++o) {
+    if (lidar) {
+      float r[7];                                        // the words rect_inside reads, from lane o's registers
+      r[0] = __shfl(rec[0], o); r[1] = __shfl(rec[1], o); r[2] = __shfl(rec[2], o); r[3] = __shfl(rec[3], o);
+      r[4] = 0.0f; r[5] = __shfl(rec[5], o); r[6] = __shfl(rec[6], o);
+      if (mine && rect_inside(r, x, y, c.car_radius)) inside = true;
+    } else {
+      const float dx = x - __shfl(rec[0], o), dy = y - __shfl(rec[1], o);
+      if (mine && sqrtf(dx * dx + dy * dy) < c.car_plus_obs) inside = true;
+    }
+  }
+  return (__any(out) ? DGPPO_SCENE_OUT_OF_AREA : 0) | (__any(overlap) ? DGPPO_SCENE_AGENTS_OVERLAP : 0) |
+         (__any(inside) ? DGPPO_SCENE_AGENT_IN_OBSTACLE : 0);
+}
+
+__global__ __launch_bounds__(64 * SCENE_MIX_WAVES) void env_scene_mix_kernel(SceneMixArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * SCENE_MIX_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (b >= a.B) return;
+  const int s = a.scene_of[b];
+  if (s < 0) return;                                     // a kept env: its reset stands, its flag is not ours
+  const dgppo_env_cfg& c = a.cfg;
+  const int n = c.n_agents, ng = c.n_goals, no = c.n_obs, SD = c.state_dim;
+  const bool lidar = cfg_is_lidar(c);
+  const int OT = lidar ? 5 : 2;
+  const float* agent_t = a.agent_t + (size_t)s * n * SD;
+  const float* goal_t = a.goal_t + (size_t)s * ng * SD;
+  const float* obst_t = a.obst_t ? a.obst_t + (size_t)s * no * OT : nullptr;
+
+  bool bad = scene_wave_nonfinite(agent_t, n * SD, lane);
+  bad = scene_wave_nonfinite(goal_t, ng * SD, lane) || bad;
+  if (no > 0) bad = scene_wave_nonfinite(obst_t, no * OT, lane) || bad;
+  const int nonfinite = bad ? DGPPO_SCENE_NONFINITE : 0;
+
+  float rec[DGPPO_RECT_STRIDE];
+  for (int k = 0; k < DGPPO_RECT_STRIDE; ++k) rec[k] = 0.0f;
+  if (lane < no) {
+    if (lidar) {
+      scene_rect_record(obst_t + lane * 5, rec);
+    } else {
+      rec[0] = obst_t[lane * 2];
+      rec[1] = obst_t[lane * 2 + 1];
+    }
+  }
+  const bool mine = lane < n;
+  const float xt = mine ? agent_t[lane * SD] : 0.0f, yt = mine ? agent_t[lane * SD + 1] : 0.0f;
+  float x = xt, y = yt;
+  int bits;
+  if (a.jitter > 0.0f) {
+    const uint64_t seed = a.seeds[b];
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const float J = a.jitter;
+    for (int attempt = 0; attempt < SCENE_ATTEMPTS; ++attempt) {
+      Philox4 p = philox4x32_10((uint32_t)(attempt * n + lane), 0u, 0u, 0u, k0, k1);
+      const float u0 = u01_from_u32(p.v[0]), u1 = u01_from_u32(p.v[1]);
+      x = xt + (2.0f * u0 - 1.0f) * J;
+      y = yt + (2.0f * u1 - 1.0f) * J;
+      bits = nonfinite | scene_wave_geometry(c, lane, x, y, rec, lidar);
+      if (bits == 0) break;
+    }
+  } else {
+    bits = nonfinite | scene_wave_geometry(c, lane, x, y, rec, lidar);
+  }
+
+  if (bits == 0) {                                       // the commit: words, as env_scene_load_kernel copies them
+    uint32_t* goal = (uint32_t*)(a.goal + (size_t)b * ng * SD);
+    for (int i = lane; i < ng * SD; i += 64) goal[i] = ((const uint32_t*)goal_t)[i];
+    if (mine) {
+      float* agent = a.agent + (size_t)b * n * SD + lane * SD;
+      for (int d = 0; d < SD; ++d) ((uint32_t*)agent)[d] = ((const uint32_t*)agent_t)[lane * SD + d];
+      if (a.jitter > 0.0f) {
+        agent[0] = x;
+        agent[1] = y;
+      }
+    }
+    for (int o = lane; o < no; o += 64) {                // n_obs <= 64: one trip, lane o's own record
+      if (lidar) {
+        float* out = a.obst + ((size_t)b * no + o) * DGPPO_RECT_STRIDE;
+        for (int k = 0; k < DGPPO_RECT_STRIDE; ++k) out[k] = rec[k];
+      } else {                                           // mpe/base.py:121
+        float* out = a.obst + ((size_t)b * no + o) * SD;
+        for (int d = 0; d < SD; ++d) out[d] = 0.0f;
+        out[0] = rec[0];
+        out[1] = rec[1];
+      }
+    }
+  }
+  if (lane == 0) {
+    if (a.flags) a.flags[b] = bits;
+    if (bits != 0 && a.n_fallback) atomicAdd(a.n_fallback, 1);
+  }
+}
+
+extern "C" int32_t dgppo_env_scene_mix(const dgppo_env_cfg* cfg, const float* agent_t, const float* goal_t, const float* obst_t,
+                                       int32_t S, const int32_t* scene_of, const uint64_t* seeds, float jitter, float* agent,
+                                       float* goal, float* obst, int32_t* flags, int32_t* n_fallback, int32_t B, void* stream) {
+  int32_t rc = dgppo_validate_cfg(cfg);
+  if (rc) {                                              // every refusal names the entry point: dgppo_validate_cfg's does not
+    char why[256];
+    snprintf(why, sizeof(why), "%s", dgppo_last_error());
+    dgppo_set_error("dgppo_env_scene_mix: %s", why);
+    return rc;
+  }
+  DGPPO_REFUSE_VMAS(cfg, "dgppo_env_scene_mix", "dgppo_vmas_reset_checked (VMASReverseTransport has no scene entry point)");
+  DGPPO_REQUIRE(S >= 1, "dgppo_env_scene_mix: S must be >= 1 (got %d)", S);
+  DGPPO_REQUIRE(B >= 0, "dgppo_env_scene_mix: B must be >= 0 (got %d)", B);
+  DGPPO_REQUIRE(jitter >= 0.0f, "dgppo_env_scene_mix: jitter must be >= 0 and not NaN (got %g)", (double)jitter);
+  DGPPO_REQUIRE(agent_t && goal_t && agent && goal, "dgppo_env_scene_mix: agent_t/goal_t/agent/goal must not be NULL");
+  DGPPO_REQUIRE(scene_of && seeds, "dgppo_env_scene_mix: scene_of/seeds must not be NULL");
+  DGPPO_REQUIRE((cfg->n_obs == 0) == (obst_t == nullptr), "dgppo_env_scene_mix: obst_t must be NULL exactly when n_obs == 0");
+  DGPPO_REQUIRE((cfg->n_obs == 0) == (obst == nullptr), "dgppo_env_scene_mix: obst must be NULL exactly when n_obs == 0");
+  DGPPO_REQUIRE(cfg->n_agents <= SCENE_MAX_AGENTS, "dgppo_env_scene_mix supports at most %d agents", SCENE_MAX_AGENTS);
+  if (B == 0) return 0;
+  SceneMixArgs a;
+  a.cfg = *cfg; a.agent_t = agent_t; a.goal_t = goal_t; a.obst_t = obst_t; a.S = S; a.scene_of = scene_of; a.seeds = seeds;
+  a.jitter = jitter; a.agent = agent; a.goal = goal; a.obst = obst; a.flags = flags; a.n_fallback = n_fallback; a.B = B;
+  hipLaunchKernelGGL(env_scene_mix_kernel, dim3(cdiv(B, SCENE_MIX_WAVES)), dim3(64 * SCENE_MIX_WAVES), 0, (hipStream_t)stream, a);
   DGPPO_LAUNCH_CHECK();
   return 0;
 }

@@ -245,6 +245,10 @@ class Engine:
         # envs whose reset could not place a valid scene within the kernels' loop bounds (dgppo_env_reset_checked): counted on
         # the device by every rollout, read at the iteration's one host sync (info) — training on such a batch is an error
         self.reset_failed = torch.zeros(1, dtype=torch.int32, device=device)
+        # envs of a mixed start (env.scenes.SceneMix) whose scene stayed invalid and that kept their sampled reset instead
+        # (dgppo_env_scene_mix): counted next to reset_failed, reported by info() as rollout/scene_fallback, never an error
+        self.scene_fallback = torch.zeros(1, dtype=torch.int32, device=device)
+        self._mix_used = False
         self.grad_hook: Optional[Callable[[str, nets.Net, int], None]] = None   # (net name, net, minibatch) before the optimiser
         self._mb = 0
 
@@ -367,9 +371,16 @@ class Engine:
     def _start(self, seeds: torch.Tensor, st: OE.State, start=None):
         """slot 0 of a rollout's record: the sampled reset of seeds, or — start = (scenes, scene_ids | None, jitter), an
         env.scenes.SceneStart — the user-given scenes (ops_env.scene_start: env b in scene scene_ids[b], or b % S; agents moved by
-        up to `jitter`, drawn from seeds).  Either way sensed, and envs without a valid scene counted in reset_failed."""
+        up to `jitter`, drawn from seeds).  Either way sensed, and envs without a valid scene counted in reset_failed.
+        start = an env.scenes.SceneMix: the reset of every env, then the scenes of those scene_of names (ops_env.mixed_start);
+        an env whose scene stays invalid keeps its reset and is counted in scene_fallback, not in reset_failed."""
         if start is None:
             return OE.reset(self.cfg, seeds, st, self.reset_failed)
+        from .env.scenes import SceneMix
+        if isinstance(start, SceneMix):
+            self._mix_used = True
+            return OE.mixed_start(self.cfg, seeds, st, start.scenes.dev, start.scene_of, float(start.jitter), self.reset_failed,
+                                  self.scene_fallback)
         scenes, scene_ids, jitter = start
         OE.scene_start(self.cfg, scenes.dev, scene_ids, seeds, float(jitter), st, None, self.reset_failed)
 
@@ -1603,7 +1614,13 @@ class Engine:
         if lagr:
             ext += [float(L["Qh_mb"].max()), -float(L["Qh_mb"].min())]
         ext = D.host_allreduce(np.asarray(ext, np.float64), "max", self.world)
-        safe = float(D.host_allreduce(np.asarray([s[3, 0]], np.float64), "sum", self.world)[0])
+        sums = [s[3, 0]]
+        mixed, self._mix_used = self._mix_used, False         # the same on every rank: the mix is a function of the flags
+        if mixed:
+            sums.append(float(self.scene_fallback.item()))
+            self.scene_fallback.zero_()
+        sums = D.host_allreduce(np.asarray(sums, np.float64), "sum", self.world)
+        safe = float(sums[0])
         out = {
             "Vl/loss": float(s[0, 0] / G), "Vl/grad_norm": float(o["Vl"][4]), "Vl/has_nan": float(o["Vl"][5]),
             "Vl/max_target": float(ext[0]), "Vl/min_target": float(-ext[1]),
@@ -1620,4 +1637,6 @@ class Engine:
                         "Vh/grad_Vh_has_nan": float(o["Vh"][5])})
         if self.algo in ("dgppo", "hcbfcrpo"):   # hcbfcrpo.py:204
             out["eval/safe_data"] = safe / (self.world * B * self.T * self.cfg.n_agents)
+        if mixed:                      # envs of this iteration's rollouts, over all ranks, that kept their reset
+            out["rollout/scene_fallback"] = float(sums[1])
         return out

@@ -28,6 +28,29 @@ class SceneStart(NamedTuple):
     jitter: float = 0.0
 
 
+class SceneMix(NamedTuple):
+    """the `start` of a rollout whose batch mixes sampled and given starts (dgppo_env_scene_mix): every env is reset from its
+    seed, then env b with scene_of[b] >= 0 (host ints [B]) restarts in that scene, moved by up to `jitter`; an env whose scene
+    stays invalid keeps its reset and is counted in the engine's scene_fallback"""
+    scenes: "Scenes"
+    scene_of: np.ndarray
+    jitter: float = 0.0
+
+
+def mix_assignment(n_total: int, n_scene: int, S: int, step: int, lo: int, hi: int) -> np.ndarray:
+    """int32 [hi - lo]: the scene_of window of the global envs lo .. hi - 1 of a batch of n_total envs of which n_scene start in
+    one of S scenes.  Global env g is a scene env iff (g + 1) n_scene // n_total > g n_scene // n_total, which spreads them
+    evenly; its ordinal is k = g n_scene // n_total and its scene (k + step) % S, so the scenes rotate over the iterations;
+    every other env gets -1.  A function of the global index alone: the ranks' windows together are what one device runs."""
+    n_total, n_scene, S, step, lo, hi = (int(v) for v in (n_total, n_scene, S, step, lo, hi))
+    if not (0 <= n_scene <= n_total and S >= 1 and 0 <= lo <= hi <= n_total):
+        raise ValueError(f"mix_assignment: need 0 <= n_scene <= n_total, S >= 1 and 0 <= lo <= hi <= n_total (got n_total "
+                         f"{n_total}, n_scene {n_scene}, S {S}, window [{lo}, {hi}))")
+    g = np.arange(lo, hi, dtype=np.int64)
+    k = g * n_scene // n_total
+    return np.where((g + 1) * n_scene // n_total > k, (k + step) % S, -1).astype(np.int32)
+
+
 def decode_flags(bits: int) -> str:
     """the names of the validity bits of dgppo_env_scene_load that are set"""
     return " | ".join(name for k, name in enumerate(N.SCENE_BITS) if int(bits) >> k & 1) or "valid"
@@ -89,6 +112,15 @@ def read_npz(path) -> dict:
                     names=[str(x) for x in z["names"]])
 
 
+def check_file(path, env_id: str, num_agents: int) -> dict:
+    """read_npz of a file that must hold scenes of env kind env_id with num_agents agents; ValueError otherwise.  Touches no
+    device: train.py asks before it starts a rank"""
+    z = read_npz(path)
+    if z["env_id"] != env_id or z["num_agents"] != num_agents:
+        raise ValueError(f"{path}: scenes of {z['env_id']} with {z['num_agents']} agents, the env is {env_id} with {num_agents}")
+    return z
+
+
 class Scenes:
     """S start scenes of one environment: template rows checked against env.cfg, uploaded once, and validated by one
     dgppo_env_scene_load call (B = S, no jitter): a scene with a non-finite word, an agent outside the area, two overlapping
@@ -123,16 +155,17 @@ class Scenes:
         """the `start` argument of the engine's rollouts"""
         return SceneStart(self, None if scene_ids is None else np.asarray(scene_ids), float(jitter))
 
+    def mix(self, scene_of, jitter: float = 0.0) -> SceneMix:
+        """the `start` argument of a rollout that mixes the sampled reset (scene_of[b] < 0) with these scenes"""
+        return SceneMix(self, np.asarray(scene_of), float(jitter))
+
     def save(self, path) -> None:
         write_npz(path, self.env_id, self.num_agents, self.rows["agent"], self.rows["goal"], self.rows.get("obst"), self.obst_key,
                   self.names)
 
     @classmethod
     def load(cls, path, env) -> "Scenes":
-        z = read_npz(path)
-        if z["env_id"] != env.KIND or z["num_agents"] != env.num_agents:
-            raise ValueError(f"{path}: scenes of {z['env_id']} with {z['num_agents']} agents, the env is {env.KIND} with "
-                             f"{env.num_agents}")
+        z = check_file(path, env.KIND, env.num_agents)
         return cls(env, z["agent"], z["goal"], rect=z["rect"], disc=z["disc"], names=z["names"])
 
     @staticmethod

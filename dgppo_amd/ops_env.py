@@ -342,6 +342,79 @@ def scene_start(cfg: N.EnvCfg, scenes_dev: Dict[str, torch.Tensor], scene_ids, s
         materialize(cfg, st, graph)
 
 
+def _scene_mix_checked(cfg: N.EnvCfg, scenes_dev, scene_of, seeds, jitter, st: State, flags, n_fallback):
+    """every refusal of scene_mix -> (S, jitter, scene_of as int32 on the host); launches nothing"""
+    fn = "scene_mix"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no scene entry point")
+    B = int(st.agent.shape[0])
+    _check_state(cfg, B, agent=st.agent, goal=st.goal, obst=st.obst)
+    shapes = scene_template_shapes(cfg)
+    agent_t = scenes_dev.get("agent")
+    if not torch.is_tensor(agent_t) or agent_t.ndim != 3 or agent_t.shape[0] < 1:
+        raise ValueError(f"{fn}: scenes_dev['agent'] must be a [S, n, sd] tensor with S >= 1")
+    S = int(agent_t.shape[0])
+    for name, shape in shapes.items():
+        if not torch.is_tensor(scenes_dev.get(name)):
+            raise ValueError(f"{fn}: scenes_dev has no {name}")
+        N.expect_shape(scenes_dev[name], (S,) + shape, f"scenes_dev.{name}")
+    jitter = float(jitter)
+    if not jitter >= 0.0:
+        raise ValueError(f"{fn}: jitter must be >= 0 (got {jitter})")
+    if seeds is None:
+        raise ValueError(f"{fn}: seeds are required")
+    N.expect_shape(seeds, (B,), "seeds")
+    if scene_of is None:
+        raise ValueError(f"{fn}: scene_of is required")
+    of = np.asarray(scene_of.cpu() if torch.is_tensor(scene_of) else scene_of)
+    if of.shape != (B,) or of.dtype.kind not in "iu":
+        raise ValueError(f"{fn}: scene_of must be {B} ints (got shape {of.shape}, dtype {of.dtype})")
+    if B and int(of.max()) >= S:
+        raise ValueError(f"{fn}: scene_of outside [-inf, {S})")
+    if flags is not None:
+        N.expect_shape(flags, (B,), "flags")
+    if n_fallback is not None:
+        N.expect_shape(n_fallback, (1,), "n_fallback")
+    return S, jitter, np.ascontiguousarray(np.maximum(of.astype(np.int64), -1), np.int32)
+
+
+def _scene_mix_launch(cfg: N.EnvCfg, scenes_dev, S: int, of: np.ndarray, seeds, jitter: float, st: State, flags, n_fallback):
+    of_dev = torch.from_numpy(of).to(st.agent.device)
+    rc = N.lib().dgppo_env_scene_mix(
+        C.byref(cfg), N.ptr(scenes_dev["agent"], name="scenes_dev.agent"), N.ptr(scenes_dev["goal"], name="scenes_dev.goal"),
+        N.ptr(scenes_dev.get("obst") if cfg.n_obs > 0 else None, name="scenes_dev.obst"), S, N.ptr(of_dev, torch.int32, "scene_of"),
+        N.ptr(seeds, torch.int64, "seeds"), jitter, N.ptr(st.agent, name="agent"), N.ptr(st.goal, name="goal"),
+        N.ptr(st.obst, name="obst"), N.ptr(flags, torch.int32, "flags"), N.ptr(n_fallback, torch.int32, "n_fallback"),
+        int(st.agent.shape[0]), N.stream_ptr())
+    N.check(rc, "dgppo_env_scene_mix")
+
+
+def scene_mix(cfg: N.EnvCfg, scenes_dev: Dict[str, torch.Tensor], scene_of, seeds, jitter: float, st: State, flags=None,
+              n_fallback=None):
+    """dgppo_env_scene_mix: some envs of the dense state st, which already holds a valid reset, restart in the template scenes
+    scenes_dev (as scene_load takes them).  scene_of — a host array or list of B ints, checked here against [-inf, S) (a tensor
+    is read back for that) — keeps env b where it is negative and names its scene otherwise; seeds [B] (int64 tensor) and
+    jitter as in scene_load.  An env whose scene is or stays invalid keeps its reset: flags [B] int32 (optional; kept envs'
+    entries are not written) receives its bits and n_fallback (optional int32 [1], caller-zeroed) gains 1.  hits are not
+    sensed here: mixed_start does that.  Every refusal is raised before anything is launched."""
+    S, jitter, of = _scene_mix_checked(cfg, scenes_dev, scene_of, seeds, jitter, st, flags, n_fallback)
+    _scene_mix_launch(cfg, scenes_dev, S, of, seeds, jitter, st, flags, n_fallback)
+
+
+def mixed_start(cfg: N.EnvCfg, seeds: torch.Tensor, st: State, scenes_dev: Dict[str, torch.Tensor], scene_of, jitter: float,
+                n_failed=None, n_fallback=None, graph: Optional[Dict[str, torch.Tensor]] = None):
+    """the episode start of a training batch that mixes sampled and given starts: the reset of every env (n_failed as in
+    env_reset), scene_mix over it (n_fallback as there), then what reset does after its kernel — sensed where the record has
+    hits, the graph written where one is asked for.  The mix's refusals come before the reset is launched."""
+    S, jitter, of = _scene_mix_checked(cfg, scenes_dev, scene_of, seeds, jitter, st, None, n_fallback)
+    env_reset(cfg, seeds, st.agent, st.goal, st.obst, n_failed)
+    _scene_mix_launch(cfg, scenes_dev, S, of, seeds, jitter, st, None, n_fallback)
+    if "hits" in st.step:
+        sense(cfg, st, graph)
+    elif graph is not None:
+        materialize(cfg, st, graph)
+
+
 def step(cfg: N.EnvCfg, st: State, action, nst: State, reward, cost, graph: Optional[Dict[str, torch.Tensor]] = None):
     """one env step from st into the per-step fields of nst (st.like()): reward [B] and cost [B, n, n_cost] of the pre-step
     state, the optional graph of the post-step state"""

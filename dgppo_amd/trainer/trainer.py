@@ -9,7 +9,12 @@ bit-identical on every rank, so nothing is lost.
 
 Stopped runs (not in the reference): with every weights save rank 0 also writes the whole training state to
 `{log_dir}/resume/{step}.pkl`; `Trainer(..., resume=True)` loads the newest one on every rank and the loop goes on from that
-step ("Resuming a stopped run")."""
+step ("Resuming a stopped run").
+
+Designed scenes (not in the reference): `Trainer(..., scenes=Scenes, scene_frac=P, scene_jitter=J)` starts
+floor(P n_env_train + 0.5) envs of every training batch in the given scenes, jittered by up to J, and the rest at the sampled
+reset (env.scenes.mix_assignment, a function of the global env index and the step: no new state to resume); every evaluation
+also rolls each scene once."""
 from __future__ import annotations
 
 import json
@@ -19,6 +24,7 @@ from time import time
 import numpy as np
 import torch
 
+from ..env.scenes import mix_assignment
 from ..utils import checkpoint as CK
 
 KEEP_STATES = 2          # state files kept under {log_dir}/resume: the newest and the one before it
@@ -28,6 +34,11 @@ def no_state_error(run_dir: str) -> FileNotFoundError:
     return FileNotFoundError(f"{run_dir}: no training state to resume from (resume/flags.yaml and resume/{{step}}.pkl). Runs "
                              f"written before full-state checkpoints existed hold weights only (models/{{step}}/*.pkl): "
                              f"they can be tested, not continued.")
+
+
+def scene_count(scene_frac: float, n_env_train: int) -> int:
+    """envs of a training batch that start in scenes: floor(P n + 0.5)"""
+    return int(np.floor(float(scene_frac) * int(n_env_train) + 0.5))
 
 
 class _Logger:
@@ -52,7 +63,8 @@ class _Logger:
 
 class Trainer:
     def __init__(self, env, env_test, algo, gamma: float, n_env_train: int, n_env_test: int, log_dir: str, seed: int,
-                 params: dict, save_log: bool = True, rank: int = 0, world: int = 1, resume: bool = False):
+                 params: dict, save_log: bool = True, rank: int = 0, world: int = 1, resume: bool = False, scenes=None,
+                 scene_frac: float = 0.0, scene_jitter: float = 0.0):
         self.env, self.env_test, self.algo, self.gamma = env, env_test, algo, gamma
         self.n_env_train, self.n_env_test, self.log_dir, self.seed = n_env_train, n_env_test, log_dir, seed
         self.rank, self.world = int(rank), int(world)
@@ -81,6 +93,14 @@ class Trainer:
         self.update_steps = 0
         self.key = np.random.default_rng([seed, 7])
         self.start_step = 0
+        # the share of every training batch that starts in the given scenes: n_scene of the n_env_train global envs
+        self.scenes, self.scene_jitter = scenes, float(scene_jitter)
+        self.n_scene = scene_count(scene_frac, n_env_train) if scenes is not None else 0
+        if scenes is None and (float(scene_frac) != 0.0 or self.scene_jitter != 0.0):
+            raise ValueError("Trainer: scene_frac / scene_jitter need scenes")
+        if scenes is not None and not (0.0 < float(scene_frac) <= 1.0 and self.scene_jitter >= 0.0 and self.n_scene >= 1):
+            raise ValueError(f"Trainer: with scenes, scene_frac must be in (0, 1] and give at least one of the {n_env_train} "
+                             f"training envs, and scene_jitter must be >= 0 (got {scene_frac}, {scene_jitter})")
         if resume:
             self._resume()
 
@@ -145,6 +165,14 @@ class Trainer:
             "_reward_min": float(total.min()), "_reward_max": float(total.max()),
         }
 
+    def evaluate_scenes(self) -> dict:
+        """every given scene rolled once on env_test: deterministic, not jittered; the reductions of evaluate"""
+        r = self.algo.collect_deterministic(np.arange(1, self.scenes.S + 1), env=self.env_test, scenes=self.scenes)
+        rewards, costs = r.rewards.cpu().numpy(), r.costs.cpu().numpy()
+        return {"eval/scene_reward": float(rewards.sum(-1).mean()),
+                "eval/scene_cost": float(np.maximum(costs, 0.0).max(-1).max(-1).sum(-1).mean()),
+                "eval/scene_unsafe_frac": float((costs.max(-1).max(-2) >= 1e-6).mean())}
+
     def train(self):
         start_time = time()
         assert self.n_env_test <= 1000, "n_env_test must be less than or equal to 1_000"
@@ -156,13 +184,22 @@ class Trainer:
                 print(f"step: {step:3}, time: {time() - start_time:5.0f}s, reward: {ev['eval/reward']:9.4f}, "
                       f"min/max reward: {rmin:7.2f}/{rmax:7.2f}, cost: {ev['eval/cost']:8.4f}, "
                       f"unsafe_frac: {ev['eval/unsafe_frac']:6.2f}", flush=True)
+                if self.scenes is not None:
+                    ev.update(self.evaluate_scenes())
+                    print(f"           scenes: reward: {ev['eval/scene_reward']:9.4f}, cost: {ev['eval/scene_cost']:8.4f}, "
+                          f"unsafe_frac: {ev['eval/scene_unsafe_frac']:6.2f}", flush=True)
                 self.logger.log(ev, step=self.update_steps)
             if self.save_log and step % self.save_interval == 0:
                 self.algo.save(os.path.join(self.model_dir), step)
                 self._save_state(step)
             keys = self.key.integers(1, 2 ** 62, size=self.n_env_train)        # the global batch, identical on every rank
             share = self.n_env_train // self.world
-            rollouts = self.algo.collect(None, keys[self.rank * share:(self.rank + 1) * share])
+            lo, hi = self.rank * share, (self.rank + 1) * share
+            if self.scenes is None:
+                rollouts = self.algo.collect(None, keys[lo:hi])
+            else:
+                scene_of = mix_assignment(self.n_env_train, self.n_scene, self.scenes.S, step, lo, hi)
+                rollouts = self.algo.collect(None, keys[lo:hi], scenes=self.scenes, jitter=self.scene_jitter, scene_of=scene_of)
             update_info = self.algo.update(rollouts, step)                      # global values on every rank (Engine.info)
             if self.logger is not None:
                 self.logger.log(update_info, step=self.update_steps)

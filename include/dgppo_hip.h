@@ -223,6 +223,25 @@ int32_t dgppo_env_reset_checked(const dgppo_env_cfg* cfg, const uint64_t* seeds,
 int32_t dgppo_env_scene_load(const dgppo_env_cfg* cfg, const float* agent_t, const float* goal_t, const float* obst_t,
                              int32_t S, const int32_t* scene_ids, const uint64_t* seeds, float jitter, float* agent,
                              float* goal, float* obst, int32_t* flags, int32_t* n_failed, int32_t B, void* stream);
+/* The scene start of SOME envs of a batch whose record already holds a valid reset (training on a mix of sampled and given
+ * starts).  Operands as dgppo_env_scene_load, but for
+ *   scene_of   [B] DEVICE int32: < 0 = keep env b as it is, else its scene id in [0, S) (the caller checks the range)
+ *   seeds      [B] uint64, never NULL
+ *   agent, goal, obst      in / out: the dense record of dgppo_env_reset
+ *   n_fallback DEVICE int32 [1], may be NULL
+ * scene_of[b] < 0: nothing of env b is read or written, flags[b] included.
+ * scene_of[b] = s: what dgppo_env_scene_load computes for (scene s, seeds[b], jitter): the same draws, expressions, 16 attempts
+ * and validity bits.  Bits 0: env b's agent, goal and obstacle rows are written, word for word what dgppo_env_scene_load writes,
+ * and flags[b] = 0.  Bits not 0 (a non-finite template, an invalid scene at jitter 0, no valid attempt at jitter > 0): none of
+ * env b's rows is written, so the reset stands; flags[b] = the bits and *n_fallback gains 1, at jitter 0 too.
+ * One wave64 per env: lane i holds agent i's candidate position in registers, the pair and obstacle tests read the other lanes
+ * through __shfl, the bits are folded with __any; no LDS, no barrier.
+ * Refused on the host, before any launch, with an error that names dgppo_env_scene_mix: an invalid cfg, VMASReverseTransport,
+ * S < 1, B < 0, a negative or NaN jitter, NULL agent_t / goal_t / agent / goal / scene_of / seeds, obst_t / obst not NULL
+ * exactly when n_obs == 0, n_agents > 64.  B == 0 returns 0.                                                               */
+int32_t dgppo_env_scene_mix(const dgppo_env_cfg* cfg, const float* agent_t, const float* goal_t, const float* obst_t,
+                            int32_t S, const int32_t* scene_of, const uint64_t* seeds, float jitter, float* agent,
+                            float* goal, float* obst, int32_t* flags, int32_t* n_fallback, int32_t B, void* stream);
 
 /* ---- VMASReverseTransport (dgppo/env/vmas/vmas_reverse_transport.py) ------------------------------------------
  * n agents (discs of radius 0.03) push a hollow 0.6 x 0.6 box of mass 10 towards a goal past 3 disc obstacles.  The record

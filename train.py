@@ -10,8 +10,8 @@ import numpy as np
 import yaml
 
 from dgppo.algo import make_algo
-from dgppo.env import make_env
-from dgppo.trainer.trainer import Trainer, no_state_error
+from dgppo.env import Scenes, make_env
+from dgppo.trainer.trainer import Trainer, no_state_error, scene_count
 from dgppo.trainer.utils import is_connected
 
 # (flags, kind, default)   kind: a type -> typed option, "flag" -> store_true, "req:<type>" -> required option
@@ -30,6 +30,9 @@ FLAGS = [
     (("--rnn-step",), "int", 16), (("--n-env-train",), "int", 128), (("--batch-size",), "int", 16384),
     (("--n-env-test",), "int", 32), (("--log-dir",), "str", "./logs"), (("--eval-interval",), "int", 50),
     (("--eval-epi",), "int", 1), (("--save-interval",), "int", 50),
+    # not in the reference: a share P of every training batch starts in the designed scenes of FILE (env.Scenes.save), moved by
+    # up to J, the rest at the sampled reset; every evaluation also rolls each scene once (README "Training on scenes")
+    (("--scenes",), "str", None), (("--scene-frac",), "float", 0.0), (("--scene-jitter",), "float", 0.0),
     # not in the reference (it is single-device): data-parallel training, one process per GPU
     (("--gpus",), "int", 1),
     # continue the stopped run in RUN_DIR from its newest full-state checkpoint; every other flag as in the stopped run
@@ -37,6 +40,8 @@ FLAGS = [
 ]
 # flags a resumed run may give differently: where it logs and what it is called play no part in the computation
 _RESUME_FREE = ("resume", "log_dir", "name", "debug")
+# flags newer than full-state checkpoints: a stopped run that does not record them ran without them, at their defaults
+_RESUME_LATER = ("scenes", "scene_frac", "scene_jitter")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -64,10 +69,12 @@ def check_resume_flags(a, stored: dict) -> None:
     """the shares, the minibatch order and the schedules depend on the flags (--gpus and --steps included), so a resumed run
     must repeat those of the stopped one (`stored`: its resume/flags.yaml).  SystemExit naming every flag that differs."""
     diff = []
-    for names, _, _ in FLAGS:
+    for names, _, default in FLAGS:
         k = _dest(names)
         if k in _RESUME_FREE:
             continue
+        if k in _RESUME_LATER:
+            stored = {k: default, **stored}
         if k not in stored:
             diff.append(f"{names[-1]} (not recorded by the stopped run)")
         elif stored[k] != getattr(a, k):
@@ -87,6 +94,30 @@ def check_resume(a) -> None:
         raise no_state_error(a.resume)
     with open(path) as f:
         check_resume_flags(a, yaml.safe_load(f) or {})
+
+
+def check_scenes(a) -> None:
+    """needs no GPU: called before any rank is started.  SystemExit naming the flag at fault"""
+    if a.scenes is None:
+        for flag, v in (("--scene-frac", a.scene_frac), ("--scene-jitter", a.scene_jitter)):
+            if v != 0.0:
+                raise SystemExit(f"train.py: {flag} needs --scenes")
+        return
+    if not 0.0 < a.scene_frac <= 1.0:
+        raise SystemExit(f"train.py: --scene-frac must be in (0, 1] with --scenes (got {a.scene_frac})")
+    if not a.scene_jitter >= 0.0:
+        raise SystemExit(f"train.py: --scene-jitter must be >= 0 (got {a.scene_jitter})")
+    if a.env == "VMASReverseTransport":
+        raise SystemExit("train.py: --scenes: VMASReverseTransport has no scene entry point")
+    if not os.path.isfile(a.scenes):
+        raise SystemExit(f"train.py: --scenes {a.scenes}: no such file")
+    from dgppo_amd.env.scenes import check_file
+    try:
+        check_file(a.scenes, a.env, a.num_agents)
+    except ValueError as ex:
+        raise SystemExit(f"train.py: --scenes: {ex}")
+    if scene_count(a.scene_frac, a.n_env_train) < 1:
+        raise SystemExit(f"train.py: --scene-frac {a.scene_frac} of --n-env-train {a.n_env_train} is less than one environment")
 
 
 def _unique_run_dir(root: str, seed: int):
@@ -160,6 +191,7 @@ def train(a):
 
     env, env_test = new_env(), new_env()
     algo = make_algo(**_algo_kwargs(a, env, world), allreduce=allreduce, world=world, rank=rank)
+    scenes = None if a.scenes is None else Scenes.load(a.scenes, env)
 
     root = f"{a.log_dir}/{a.env}/{a.algo}"
     write = not a.debug and rank == 0                # one writer (rank 0); the other ranks never touch the log directory
@@ -177,7 +209,7 @@ def train(a):
                 "save_interval": a.save_interval}
     trainer = Trainer(env=env, env_test=env_test, algo=algo, gamma=0.99, log_dir=log_dir, n_env_train=a.n_env_train,
                       n_env_test=a.n_env_test, seed=a.seed, params=schedule, save_log=write, rank=rank, world=world,
-                      resume=a.resume is not None)
+                      resume=a.resume is not None, scenes=scenes, scene_frac=a.scene_frac, scene_jitter=a.scene_jitter)
     if write and a.resume is None:   # plain mappings (the reference dumps the argparse.Namespace object itself; test.py reads both)
         with open(f"{log_dir}/config.yaml", "w") as f:
             yaml.safe_dump(_flags_to_store(a), f)
@@ -189,16 +221,18 @@ def train(a):
     close()
 
 
-def main():
-    a = build_parser().parse_args()
+def main(argv=None):
+    import sys
+    argv = sys.argv[1:] if argv is None else list(argv)
+    a = build_parser().parse_args(argv)
     check_resume(a)
+    check_scenes(a)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher environment: start the ranks ourselves, before this process touches the GPU, and supervise them
         # (per-rank logs, everything stops on the first failure — dgppo_amd/launch.py)
-        import sys
         from dgppo_amd import launch
         here = os.path.dirname(os.path.abspath(__file__))
-        sys.exit(launch.spawn_ranks(os.path.abspath(__file__), sys.argv[1:], a.gpus, launch.default_log_dir(here),
+        sys.exit(launch.spawn_ranks(os.path.abspath(__file__), argv, a.gpus, launch.default_log_dir(here),
                                     stall_seconds=float(os.environ.get("DGPPO_STALL_SECONDS", "900"))))
     train(a)
 
