@@ -5,6 +5,7 @@
 //   MLP block (Dense -> LayerNorm -> ReLU) x 2     dgppo/nn/mlp.py:17-29   (hid_sizes (64, 64), act_final=True)
 //   GRUCell input projection  x W_i + b_i          dgppo/nn/rnn.py:14-30   (flax GRUCell: dense_i of the r|z|n gates)
 //   as composed by                                  dgppo/algo/module/policy.py:191-212, value.py:58-80
+#include <type_traits>
 #include "common.h"
 #include "nn_ln.h"
 
@@ -451,13 +452,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FZ_BWD
   const int n_tiles = (a.M + BRB - 1) / BRB;
   constexpr int GSL = BRB * 48 / 256;       // float4 slots of a dgi tile per lane
   float4 gpf[GSL];
+  const bool gvec = (reinterpret_cast<uintptr_t>(a.dgi) & 15) == 0;   // (an aligned dgi takes mlp_gi_bwd_rw_kernel: see the selection)
   auto fetch = [&](int tile) {            // BRB rows x 48 float4; rows clamped
 #pragma unroll
     for (int u = 0; u < GSL; ++u) {
       const int idx = u * 256 + tid, r = idx / 48, q = idx - r * 48;
       int row = tile * BRB + r;
       row = row < a.M ? row : a.M - 1;
-      gpf[u] = *reinterpret_cast<const float4*>(a.dgi + (size_t)row * 192 + 4 * q);
+      const float* p = a.dgi + (size_t)row * 192 + 4 * q;
+      if (gvec) gpf[u] = *reinterpret_cast<const float4*>(p);
+      else gpf[u] = make_float4(p[0], p[1], p[2], p[3]);
     }
   };
   auto commit = [&]() {
@@ -720,6 +724,394 @@ constexpr size_t mlp_gi_bwd_smem() {
   return smem_t > smem_r ? smem_t : smem_r;
 }
 
+// ---- the same backward chain, rows per WAVE (round 12) -----------------------------------------------------------------------
+// mlp_gi_bwd_kernel above has the shape mlp_gi_fwd_kernel had: the 64 columns of a tile split over four waves, so each LayerNorm
+// backward is a cross-wave exchange with two barriers, each product one dependent chain of MFMAs, and 80 registers of W^T next to
+// everything else.  Here, as in mlp_gi_fwd_rw_kernel, a WAVE owns 16 rows through the whole chain and all 64 columns of each result:
+//   * the three weight matrices sit in LDS once per workgroup in the forward's [k][c] layout; the B fragment of X W^T is the
+//     transposed read — lane (li, lq) reads W[ct * 16 + li][lq * 16 + kk]: bank (li + 16 lq + kk) mod 64, all different;
+//   * four independent accumulators per product, B fragments double-buffered two k-steps at a time;
+//   * dgi rows come from global memory in the A layout, 32 bytes per lane and chunk of 8 k-steps, two chunks in flight;
+//   * both row sums of a LayerNorm backward are sums over the lane's four column tiles + row16_sum: no exchange, no barrier;
+//   * dpre2 / dpre1 become the next A operand through the wave's own 16 x 68 LDS tile (DS operations of a wave execute in order);
+//     rows >= M are written there as zeros, so the tile is also the B operand of the weight gradients;
+//   * WG: dW2 += y1^T dpre2 and dW1 += x^T dpre1 with BOTH operands in the C/D layout (y1 and x are loaded in it anyway, as the
+//     ReLU mask of layer 1 and of dx): k-step r contracts rows {4 lq + r}; 64 MFMAs and 64 accumulator registers per matrix,
+//     live across the tile loop.  dpre comes back from the LDS tile (16 reads) rather than staying live through the next product.
+// Register plan at two waves per SIMD (256): 128 dW accumulators, 8 running bias sums (those of dgamma / dbeta sit in LDS), and a
+// chain that requests each tile's p / y / st / x one stage ahead of their use and no earlier.  <true> compiles to exactly 256
+// VGPRs without scratch (profiles/r12_resource_usage.txt; profiles/README.md, round 12, lists what that took): tile bases are
+// scalar, lane offsets 32-bit and formed where they are used.  Check -Rpass-analysis=kernel-resource-usage after every edit.
+// End: LayerNorm / bias sums of the 8 waves x 4 row groups are added in LDS in a fixed order; the dW accumulators meet in wave 0
+// through lane-major LDS images in three halving rounds (head_bwd_kernel), one slab per workgroup.
+#define BRW_WAVES 8
+#define BRW_SUMS 16                                         // dgamma / dbeta running sums of a lane: [layer][kind][ct]
+#define BRW_CHAIN_FLOATS (2 * 64 * RW_WL + 64 * RW_WIL + 128 + BRW_WAVES * 16 * RW_YL + BRW_WAVES * BRW_SUMS * 64)
+#define BRW_IMAGE_FLOATS ((BRW_WAVES / 2) * 128 * 64)      // first halving round: 4 waves x 128 values x 64 lanes
+template <bool WG>
+__global__ void __launch_bounds__(64 * BRW_WAVES) mlp_gi_bwd_rw_kernel(MlpGiBwdArgs a) {
+  extern __shared__ float sm[];
+  float* sW1 = sm;                               // [64][65]   W1[k][c]
+  float* sW2 = sW1 + 64 * RW_WL;                 // [64][65]
+  float* sWi = sW2 + 64 * RW_WL;                 // [64][193]
+  float* sP = sWi + 64 * RW_WIL;                 // g2, g1
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, lq = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform: tile bases below are scalar, lane offsets 32-bit
+  float* sY = sP + 128 + w * (16 * RW_YL);       // wave-private transposition tile
+  // the lane's running sums of dgamma / dbeta live in LDS (slot j at [j][lane]: conflict-free, touched by this lane alone):
+  // next to the 128 dW accumulators there are no 16 registers for them while a tile's saved rows are in flight
+  float* sS = sP + 128 + BRW_WAVES * (16 * RW_YL) + w * (BRW_SUMS * 64) + lane;
+#pragma unroll
+  for (int j = 0; j < BRW_SUMS; ++j) sS[j * 64] = 0.0f;
+  {   // weights as single words (parameter slices: any alignment), ALL requested before the first LDS write
+    static_assert(BRW_WAVES == 8, "the staging below assumes 512 threads");
+    float v1[8], v2[8], vi[24];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { v1[j] = a.W1[j * 512 + tid]; v2[j] = a.W2[j * 512 + tid]; }
+#pragma unroll
+    for (int j = 0; j < 24; ++j) vi[j] = a.Wi[j * 512 + tid];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int idx = j * 512 + tid, k = idx >> 6, c = idx & 63;
+      sW1[k * RW_WL + c] = v1[j]; sW2[k * RW_WL + c] = v2[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 24; ++j) {
+      const int idx = j * 512 + tid, k = idx / 192, c = idx - k * 192;
+      sWi[k * RW_WIL + c] = vi[j];
+    }
+  }
+  if (tid < 64) { sP[tid] = a.g2[tid]; sP[64 + tid] = a.g1[tid]; }
+  __syncthreads();
+  f32x4 aw2[4][4], aw1[4][4];                    // dW2 / dW1 rows 16 kt + 4 lq + r, columns 16 ct + li (WG)
+  float dcs[2][4];                               // running sums of the Dense bias gradients: [layer 2, layer 1][ct]
+#pragma unroll
+  for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) aw2[kt][ct] = aw1[kt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int l = 0; l < 2; ++l)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) dcs[l][ct] = 0.0f;
+  const int n_tiles = (a.M + 15) >> 4, stride = gridDim.x * BRW_WAVES;
+  // element i (a 32-bit lane offset) of a scalar tile base: scalar base + 32-bit byte offset is one address register, not two
+  auto at = [](auto* base, unsigned i) -> decltype(*base)& {
+    using T = std::remove_reference_t<decltype(*base)>;
+    using B = std::conditional_t<std::is_const_v<T>, const char, char>;
+    return *reinterpret_cast<T*>(reinterpret_cast<B*>(base) + i * (unsigned)sizeof(T));
+  };
+  const bool x_masks = WG && a.mask == a.x && a.ldm == a.ldx;      // the per-agent networks mask by their own input: one load
+  // dgi in the A layout: row li, k-step s of the product reads column (s >> 4) * 64 + lq * 16 + (s & 15); chunk q = 8 k-steps
+  float G[2][8];
+  auto grow = [&](int t) {                       // t < n_tiles: the clamped row is never below the tile's first
+    const int last = a.M - 1 - t * 16;           // scalar
+    int l = lane;
+    asm volatile("" : "+v"(l));                  // (li and 16 lq are formed here, twice a tile, rather than kept in registers)
+    const int rl = (l & 15) < last ? (l & 15) : last;
+    return &at(a.dgi + (size_t)t * (16 * 192), (unsigned)(rl * 192 + (l & 48)));
+  };
+  auto fetchG = [&](int buf, const float* gp, int q) {
+    const float4* p = reinterpret_cast<const float4*>(gp + (q >> 1) * 64 + (q & 1) * 8);
+    const float4 u0 = p[0], u1 = p[1];
+    G[buf][0] = u0.x; G[buf][1] = u0.y; G[buf][2] = u0.z; G[buf][3] = u0.w;
+    G[buf][4] = u1.x; G[buf][5] = u1.y; G[buf][6] = u1.z; G[buf][7] = u1.w;
+  };
+  // one 64-wide product from the wave's LDS tile: acc = A W^T, A = row li, columns lq * 16 .. + 15 of the tile
+  auto gemm64 = [&](f32x4 (&acc)[4], const float* sW) {
+    float A[16];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float4 v = *reinterpret_cast<const float4*>(sY + li * RW_YL + lq * 16 + 4 * j);
+      A[4 * j] = v.x; A[4 * j + 1] = v.y; A[4 * j + 2] = v.z; A[4 * j + 3] = v.w;
+    }
+    float bw[2][2][4];
+    auto ldb = [&](int buf, int g) {
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const float* wr = sW + li * RW_WL + lq * 16 + g * 2 + kk;
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) bw[buf][kk][ct] = wr[ct * 16 * RW_WL];
+      }
+    };
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    ldb(0, 0);
+#pragma unroll
+    for (int g = 0; g < 8; ++g) {
+      if (g + 1 < 8) ldb((g + 1) & 1, g + 1);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[g * 2 + kk], bw[g & 1][kk][ct], acc[ct], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  int tile = w * gridDim.x + blockIdx.x;         // consecutive tiles on different CUs
+  if (tile < n_tiles) { const float* gp = grow(tile); fetchG(0, gp, 0); fetchG(1, gp, 1); }
+  for (; tile < n_tiles; tile += stride) {          // (the tile's first two dgi chunks are on their way)
+    const int row0 = tile * 16;
+    const float* gp = grow(tile);
+    int rl[4]; bool ok[4];                       // this lane's rows in the C/D layout, relative to row0, clamped
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int last = a.M - 1 - row0;           // scalar
+      ok[r] = lq * 4 + r <= last;
+      rl[r] = ok[r] ? lq * 4 + r : last;
+      asm volatile("" : "+v"(rl[r]));            // offsets are formed from these four where they are used: as selects between a
+    }                                            // hoisted (lq * 4 + r) * ld + li and the clamped row they cost 4 registers per ld
+    auto load16 = [&](const float* src, int ld, float (&o)[4][4]) {
+      const float* base = src + (size_t)row0 * ld;               // scalar
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[ct][r] = at(base + ct * 16, (unsigned)(rl[r] * ld + li));
+    };
+    auto load_st = [&](const float* src, float2 (&o)[4]) {
+      const float2* base = reinterpret_cast<const float2*>(src) + row0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = at(base, (unsigned)rl[r]);
+    };
+    // LayerNorm + ReLU backward on the C/D layout: v = dy in, dpre out (zeros in rows >= M), also to the wave's LDS tile
+    auto ln_relu_bwd = [&](f32x4 (&v)[4], float (&pv)[4][4], const float (&yv)[4][4], const float2 (&st)[4], const float* gam,
+                           float* s_acc, float (&dc_acc)[4], float* d_out) {
+      float* d_base = d_out + (size_t)row0 * FZ_H;               // (only dereferenced where d_out is given)
+      float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const float g = gam[ct * 16 + li];
+        float dg_t = 0.0f, db_t = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float2 ms = st[r];
+          const float xh = (pv[ct][r] - ms.x) * ms.y;
+          const float dl = (ok[r] && yv[ct][r] > 0.0f) ? v[ct][r] : 0.0f;
+          dg_t += dl * xh;
+          db_t += dl;
+          const float dxh = dl * g;
+          s1[r] += dxh;
+          s2[r] += dxh * xh;
+          pv[ct][r] = xh;
+          v[ct][r] = dxh;
+        }
+        s_acc[ct * 64] += dg_t;
+        s_acc[(4 + ct) * 64] += db_t;
+      }
+      float m1[4], m2[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        m1[r] = row16_sum(s1[r]) * (1.0f / 64.0f);
+        m2[r] = row16_sum(s2[r]) * (1.0f / 64.0f);
+      }
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float dp = st[r].y * (v[ct][r] - m1[r] - pv[ct][r] * m2[r]);
+          if (ok[r]) {                                          // rows >= M contribute exactly zero, whatever the clamped row holds
+            dc_acc[ct] += dp;
+            if (d_out != nullptr) at(d_base + ct * 16, (unsigned)(rl[r] * FZ_H + li)) = dp;
+          }
+          v[ct][r] = ok[r] ? dp : 0.0f;
+          sY[(lq * 4 + r) * RW_YL + ct * 16 + li] = v[ct][r];
+        }
+      // the bias sums are complete HERE: left alone, the compiler sinks such additions to the end of the tile and keeps their
+      // terms live until then
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) asm volatile("" : "+v"(dc_acc[ct]));
+    };
+    // acc[kt][ct] += A^T dpre over the tile's rows: A = av (y1 or x in the C/D layout, zeros past M), dpre from the wave's tile
+    auto wgrad = [&](f32x4 (&acc)[4][4], const float (&av)[4][4]) {
+      float bv[4][4];
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bv[ct][r] = sY[(lq * 4 + r) * RW_YL + ct * 16 + li];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+          const float x = ok[r] ? av[kt][r] : 0.0f;
+#pragma unroll
+          for (int ct = 0; ct < 4; ++ct) acc[kt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(x, bv[ct][r], acc[kt][ct], 0, 0, 0);
+        }
+    };
+    float pv[4][4], yv[4][4];
+    float2 sv[4];
+    load16(a.p2, FZ_H, pv); load16(a.y2, FZ_H, yv); load_st(a.st2, sv);
+    __builtin_amdgcn_sched_barrier(0);
+    f32x4 acc[4];
+    // ---- dy2 = dgi Wi^T (K = 192): 48 k-steps, the B fragment one step ahead (this is the stage where the tile's saved rows
+    // are in flight next to the dgi chunks: two steps ahead, as in gemm64, is 8 registers too many); the dgi chunk two ahead is
+    // requested when its buffer falls free ----
+    {
+      float bw[2][4];
+      auto ldb = [&](int buf, int s) {
+        const float* wr = sWi + li * RW_WIL + (s >> 4) * 64 + lq * 16 + (s & 15);
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) bw[buf][ct] = wr[ct * 16 * RW_WIL];
+      };
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+      ldb(0, 0);
+#pragma unroll
+      for (int s = 0; s < 48; ++s) {
+        if (s + 1 < 48) ldb((s + 1) & 1, s + 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+          acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(G[(s >> 3) & 1][s & 7], bw[s & 1][ct], acc[ct], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if ((s & 7) == 7 && (s >> 3) + 2 < 6) fetchG((s >> 3) & 1, gp, (s >> 3) + 2);
+      }
+    }
+    ln_relu_bwd(acc, pv, yv, sv, sP, sS, dcs[0], a.dpre2);
+    // layer 1's saved rows are requested here and land behind the next product
+    float xv[4][4];
+    load16(a.p1, FZ_H, pv); load16(a.y1, FZ_H, yv); load_st(a.st1, sv);
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- dy1 = dpre2 W2^T, then dW2 += y1^T dpre2 ----
+    gemm64(acc, sW2);
+    if constexpr (WG) {
+      wgrad(aw2, yv);
+      load16(a.x, a.ldx, xv);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    ln_relu_bwd(acc, pv, yv, sv, sP + 64, sS + 8 * 64, dcs[1], a.dpre1);
+    // ---- dx = dpre1 W1^T, then dW1 += x^T dpre1 ----
+    gemm64(acc, sW1);
+    if (a.mask != nullptr) {
+      if (x_masks) {
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[ct][r] = xv[ct][r] > 0.0f ? acc[ct][r] : 0.0f;
+      } else {                                   // a separate mask is the rare form: requested where it is used, a row at a time
+        const float* mb = a.mask + (size_t)row0 * a.ldm;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float mk[4];
+#pragma unroll
+          for (int ct = 0; ct < 4; ++ct) mk[ct] = at(mb + ct * 16, (unsigned)(rl[r] * a.ldm + li));
+#pragma unroll
+          for (int ct = 0; ct < 4; ++ct) acc[ct][r] = mk[ct] > 0.0f ? acc[ct][r] : 0.0f;
+        }
+      }
+    }
+    float* dxb = a.dx + (size_t)row0 * a.lddx;
+    unsigned ob = (unsigned)(lq * 4 * a.lddx + li);              // (a stored row is never a clamped one)
+    asm volatile("" : "+v"(ob));                 // formed here: hoisted out of the tile loop, the four row offsets cost 8 registers
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (ok[r]) {
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) at(dxb + ct * 16, ob + (unsigned)(r * a.lddx)) = acc[ct][r];
+      }
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (WG) wgrad(aw1, xv);
+    if (tile + stride < n_tiles) { const float* gn = grow(tile + stride); fetchG(0, gn, 0); fetchG(1, gn, 1); }
+  }
+  // ---- LayerNorm parameter (and Dense bias) gradients: 8 waves x 4 row groups per column, added in LDS in a fixed order ----
+  float dgs[2][4], dbs[2][4];
+#pragma unroll
+  for (int l = 0; l < 2; ++l)
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) { dgs[l][ct] = sS[(l * 8 + ct) * 64]; dbs[l][ct] = sS[(l * 8 + 4 + ct) * 64]; }
+  __syncthreads();                               // the weights, every wave's tile and its sums are dead
+  constexpr int NK = WG ? 3 : 2;                 // kinds per layer: dgamma, dbeta(, dbias)
+  {
+    const int slot = w * 4 + lq;
+#pragma unroll
+    for (int l = 0; l < 2; ++l)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) {
+        const int col = ct * 16 + li;
+        sm[((l * NK + 0) * 32 + slot) * 64 + col] = dgs[l][ct];
+        sm[((l * NK + 1) * 32 + slot) * 64 + col] = dbs[l][ct];
+        if constexpr (WG) sm[((l * NK + 2) * 32 + slot) * 64 + col] = dcs[l][ct];
+      }
+  }
+  __syncthreads();
+  float* slab = (WG && a.part) ? a.part + (size_t)blockIdx.x * TW_SLAB : nullptr;
+  if (tid < 2 * NK * 64) {
+    const int which = tid >> 6, col = tid & 63, l = which / NK, kind = which - l * NK;
+    float tot = 0.0f;
+    for (int j = 0; j < 32; ++j) tot += sm[(which * 32 + j) * 64 + col];
+    if (kind == 0) atomicAdd((l == 0 ? a.dg2 : a.dg1) + col, tot);
+    else if (kind == 1) atomicAdd((l == 0 ? a.db2 : a.db1) + col, tot);
+    else if (slab) slab[l * TW_HALF + FZ_H * FZ_H + col] = tot;
+    else atomicAdd((l == 0 ? a.dbias2 : a.dbias1) + col, tot);
+  }
+  if constexpr (WG) {
+    // the eight waves' dW accumulators meet in wave 0: three halving rounds through lane-major LDS images (slot j of lane l at
+    // [j][l]: conflict-free, the same lane of every wave holds the same element), then wave 0 writes the slab from registers
+    auto each = [&](auto&& f) {
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            aw2[kt][ct][r] = f((kt * 4 + ct) * 4 + r, aw2[kt][ct][r]);
+            aw1[kt][ct][r] = f(64 + (kt * 4 + ct) * 4 + r, aw1[kt][ct][r]);
+          }
+    };
+    __syncthreads();                             // the column sums above are read
+#pragma unroll
+    for (int half = BRW_WAVES / 2; half >= 1; half >>= 1) {
+      if (w >= half && w < 2 * half) each([&](int j, float v) { sm[((w - half) * 128 + j) * 64 + lane] = v; return v; });
+      __syncthreads();
+      if (w < half) each([&](int j, float v) { return v + sm[(w * 128 + j) * 64 + lane]; });
+      __syncthreads();
+    }
+    if (w != 0) return;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int krow = kt * 16 + lq * 4 + r, col = ct * 16 + li;
+          if (slab) {
+            slab[krow * FZ_H + col] = aw2[kt][ct][r];
+            slab[TW_HALF + krow * FZ_H + col] = aw1[kt][ct][r];
+          } else {
+            atomicAdd(a.dW2 + (size_t)krow * a.ldw2 + col, aw2[kt][ct][r]);
+            atomicAdd(a.dW1 + (size_t)krow * a.ldw1 + col, aw1[kt][ct][r]);
+          }
+        }
+  }
+}
+
+static int head_bwd_cus();                      // (the device's CU count, defined with dgppo_head_bwd below)
+// Which kernel a call runs, for BOTH entry points (by shape and alignment only): the rows-per-wave form needs 16-byte dgi rows
+// (192 floats: the first one decides); every other operand moves as single words.  Its grid: one 8-wave workgroup per CU, fewer
+// when the 16-row tiles do not give every wave one.
+static bool mlp_gi_bwd_rw_selected(const float* dgi, int M) { return M > 0 && (reinterpret_cast<uintptr_t>(dgi) & 15) == 0; }
+static int mlp_gi_bwd_rw_grid(int M) {
+  const int tiles = (M + 15) / 16, want = (tiles + BRW_WAVES - 1) / BRW_WAVES, cus = head_bwd_cus();
+  return want < cus ? want : cus;
+}
+template <bool WG>
+constexpr size_t mlp_gi_bwd_rw_smem() {
+  return sizeof(float) * ((WG && BRW_IMAGE_FLOATS > BRW_CHAIN_FLOATS) ? BRW_IMAGE_FLOATS : BRW_CHAIN_FLOATS);
+}
+template <bool WG>
+static int32_t mlp_gi_bwd_rw_launch(const MlpGiBwdArgs& a, int grid, hipStream_t stream) {
+  constexpr size_t smem = mlp_gi_bwd_rw_smem<WG>();
+  static_assert(smem <= 160 * 1024 && sizeof(float) * 2 * 3 * 32 * 64 <= smem, "mlp_gi_bwd_rw: LDS image");
+  static thread_local bool opted = false;
+  if (!opted) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_gi_bwd_rw_kernel<WG>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    DGPPO_REQUIRE(e == hipSuccess, "mlp_gi_bwd: cannot reserve %zu bytes of LDS per workgroup: %s", smem, hipGetErrorString(e));
+    opted = true;
+  }
+  hipLaunchKernelGGL(mlp_gi_bwd_rw_kernel<WG>, dim3(grid), dim3(64 * BRW_WAVES), smem, stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int32_t dgppo_mlp_gi_bwd(const float* dgi, const float* Wi, const float* W2, const float* W1, const float* g2,
                                     const float* g1, const float* p2, const float* y2, const float* st2, const float* p1,
                                     const float* y1, const float* st1, const float* relu_mask, int32_t ldm, float* dpre2,
@@ -728,10 +1120,10 @@ extern "C" int32_t dgppo_mlp_gi_bwd(const float* dgi, const float* Wi, const flo
   DGPPO_REQUIRE(M >= 0 && lddx >= FZ_H && (relu_mask == nullptr || ldm >= FZ_H), "mlp_gi_bwd: bad shape M=%d lddx=%d ldm=%d", M, lddx, ldm);
   DGPPO_REQUIRE(dgi && Wi && W2 && W1 && g2 && g1 && p2 && y2 && st2 && p1 && y1 && st1 && dpre2 && dpre1 && dx && dg2 && db2 &&
                 dg1 && db1, "mlp_gi_bwd: NULL operand");
-  DGPPO_REQUIRE((reinterpret_cast<uintptr_t>(dgi) & 15) == 0, "mlp_gi_bwd: dgi must be 16-byte aligned");
   if (M == 0) return 0;
   MlpGiBwdArgs a{dgi, M, Wi, W2, W1, g2, g1, p2, y2, st2, p1, y1, st1, relu_mask, ldm, dpre2, dpre1, dx, lddx, dg2, db2, dg1, db1,
                  nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr};
+  if (mlp_gi_bwd_rw_selected(dgi, M)) return mlp_gi_bwd_rw_launch<false>(a, mlp_gi_bwd_rw_grid(M), (hipStream_t)stream);
   constexpr size_t smem = mlp_gi_bwd_smem<false>();
   const int cap = mlp_gi_bwd_cap<false>(smem);
   const int tiles = (M + 16 * FZ_BWD_RT - 1) / (16 * FZ_BWD_RT);
@@ -745,9 +1137,11 @@ extern "C" int32_t dgppo_mlp_gi_bwd(const float* dgi, const float* Wi, const flo
 // TW_MIN_TILES tiles: below that the slab a workgroup writes (33 KB) outweighs the rows it reads (7.4 KB per tile), so fewer
 // workgroups walk more tiles (16 384 rows with the batched reduce: 44 us at 1 or 2 tiles, 39 at 4, 51 at 8); at <= 4 workgroups
 // the sums go straight into the outputs with atomicAdd, as in dense_bwd_w.
-extern "C" int64_t dgppo_mlp_gi_bwd_w_workspace_bytes(void) {
-  return (int64_t)TW_SLAB * sizeof(float) * mlp_gi_bwd_cap<true>(mlp_gi_bwd_smem<true>());
-}
+// The rows-per-wave form (mlp_gi_bwd_rw_kernel<true>, an aligned dgi) writes one slab per workgroup of its own grid, which is the
+// grid of dgppo_mlp_gi_bwd at the same M: at most one per CU, and the workspace is sized for that.  Up to 4 workgroups, or
+// with no room for a slab each, it adds atomically from the SAME grid.  mlp_gi_bwd_kernel<true> with that workspace walks
+// at most one workgroup per slab.
+extern "C" int64_t dgppo_mlp_gi_bwd_w_workspace_bytes(void) { return (int64_t)TW_SLAB * sizeof(float) * head_bwd_cus(); }
 
 extern "C" int32_t dgppo_mlp_gi_bwd_w(const float* dgi, const float* Wi, const float* W2, const float* W1, const float* g2,
                                       const float* g1, const float* p2, const float* y2, const float* st2, const float* p1,
@@ -764,19 +1158,29 @@ extern "C" int32_t dgppo_mlp_gi_bwd_w(const float* dgi, const float* Wi, const f
   if (M == 0) return 0;                            // (the row operands of an empty call may be NULL)
   DGPPO_REQUIRE(dgi && Wi && W2 && W1 && g2 && g1 && p2 && y2 && st2 && p1 && y1 && st1 && x && dx && dg2 && db2 && dg1 && db1 &&
                 dW2 && dbias2 && dW1 && dbias1, "mlp_gi_bwd_w: NULL operand");
-  DGPPO_REQUIRE((reinterpret_cast<uintptr_t>(dgi) & 15) == 0, "mlp_gi_bwd_w: dgi must be 16-byte aligned");
-  constexpr size_t smem = mlp_gi_bwd_smem<true>();
-  const int tiles = (M + 16 * FZ_BWD_RT - 1) / (16 * FZ_BWD_RT);
-  int grid = mlp_gi_bwd_cap<true>(smem);
-  if (grid > tiles / TW_MIN_TILES) grid = tiles / TW_MIN_TILES;
   const long max_slabs = (long)(workspace_bytes / (sizeof(float) * TW_SLAB));
-  float* ws = (grid > 4 && max_slabs >= 8) ? workspace : nullptr;
-  if (ws && grid > max_slabs) grid = (int)max_slabs;
-  if (!ws) grid = tiles < 4 ? tiles : 4;
-  MlpGiBwdArgs a{dgi, M, Wi, W2, W1, g2, g1, p2, y2, st2, p1, y1, st1, relu_mask, ldm, dpre2, dpre1, dx, lddx, dg2, db2, dg1, db1,
-                 x, ldx, ws, dW2, ldw2, dbias2, dW1, ldw1, dbias1};
-  hipLaunchKernelGGL(mlp_gi_bwd_kernel<true>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
-  DGPPO_LAUNCH_CHECK();
+  int grid;
+  float* ws;
+  if (mlp_gi_bwd_rw_selected(dgi, M)) {
+    grid = mlp_gi_bwd_rw_grid(M);
+    ws = (grid > 4 && max_slabs >= grid) ? workspace : nullptr;
+    MlpGiBwdArgs a{dgi, M, Wi, W2, W1, g2, g1, p2, y2, st2, p1, y1, st1, relu_mask, ldm, dpre2, dpre1, dx, lddx, dg2, db2, dg1, db1,
+                   x, ldx, ws, dW2, ldw2, dbias2, dW1, ldw1, dbias1};
+    const int32_t rc = mlp_gi_bwd_rw_launch<true>(a, grid, (hipStream_t)stream);
+    if (rc != 0) return rc;
+  } else {
+    constexpr size_t smem = mlp_gi_bwd_smem<true>();
+    const int tiles = (M + 16 * FZ_BWD_RT - 1) / (16 * FZ_BWD_RT);
+    grid = mlp_gi_bwd_cap<true>(smem);
+    if (grid > tiles / TW_MIN_TILES) grid = tiles / TW_MIN_TILES;
+    ws = (grid > 4 && max_slabs >= 8) ? workspace : nullptr;
+    if (ws && grid > max_slabs) grid = (int)max_slabs;
+    if (!ws) grid = tiles < 4 ? tiles : 4;
+    MlpGiBwdArgs a{dgi, M, Wi, W2, W1, g2, g1, p2, y2, st2, p1, y1, st1, relu_mask, ldm, dpre2, dpre1, dx, lddx, dg2, db2, dg1, db1,
+                   x, ldx, ws, dW2, ldw2, dbias2, dW1, ldw1, dbias1};
+    hipLaunchKernelGGL(mlp_gi_bwd_kernel<true>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
+    DGPPO_LAUNCH_CHECK();
+  }
   if (!ws) return 0;
   dgppo_reduce_desc d[2];
   d[0] = dgppo_reduce_desc{ws, dW2, dbias2, TW_SLAB, grid, ldw2, FZ_H, FZ_H, 1};

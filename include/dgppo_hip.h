@@ -327,7 +327,9 @@ int32_t dgppo_mlp_gi_fwd(const float* X, int32_t ldx, const float* W1, const flo
  * dpre2 = LNReLU'(p2, y2, st2, g2; dgi Wi^T), dpre1 = LNReLU'(p1, y1, st1, g1; dpre2 W2^T), dx = dpre1 W1^T, where
  * LNReLU'(p, y, st, g; dy) = rstd (dxh - mean(dxh) - xhat mean(dxh xhat)), dxh = dy (y > 0) g.  relu_mask [M, ldm] (may be
  * NULL): dx = (mask > 0) ? dx : 0.  dpre2 / dpre1 [M,64] are outputs (the weight gradients dW2 = y1^T dpre2, dW1 = X^T dpre1
- * read them); dg2/db2/dg1/db1 [64] += the LayerNorm scale / bias gradients.  dgi [M,192] 16-byte aligned.          */
+ * read them); dg2/db2/dg1/db1 [64] += the LayerNorm scale / bias gradients.  M > 0 and a 16-byte aligned dgi [M,192] run
+ * the rows-per-wave kernel (one 8-wave workgroup per CU); any other dgi the 16-row-tile kernel.  The choice depends on
+ * nothing else and is the one dgppo_mlp_gi_bwd_w makes, on the same grid.                                           */
 int32_t dgppo_mlp_gi_bwd(const float* dgi, const float* Wi, const float* W2, const float* W1, const float* g2,
                          const float* g1, const float* p2, const float* y2, const float* st2, const float* p1,
                          const float* y1, const float* st1, const float* relu_mask, int32_t ldm, float* dpre2, float* dpre1,
@@ -366,11 +368,12 @@ int32_t dgppo_dense_bwd_xw(const float* X, int32_t ldx, const float* dY, int32_t
  * dW2 [64, ldw2] += y1^T dpre2, dbias2 [64] += colsum(dpre2), dW1 [64, ldw1] += x^T dpre1, dbias1 [64] += colsum(dpre1), where
  * x [M, ldx] is the chain's input (it may be the relu_mask tensor itself).  dpre2 / dpre1 may be NULL: then they never leave
  * the CU.  dx (and dpre* where given) are bit for bit those of dgppo_mlp_gi_bwd; dg* / db* are the same sums, but both
- * entry points add per-workgroup partial sums with atomicAdd in arrival order, and this one may split the rows over fewer
- * workgroups, so they agree only to the rounding of a reordered fp32 sum.  Rows >= M of a ragged tile contribute exactly
- * zero.  workspace: dgppo_mlp_gi_bwd_w_workspace_bytes() bytes for one partial slab [dW2 | dbias2 | dW1 | dbias1] per
- * workgroup; a smaller one shrinks the grid, and one with room for fewer than 8 slabs (or NULL) makes the call add atomically
- * from at most 4 workgroups whatever M is: correct, but slow at many rows.  Few rows always add atomically.
+ * entry points add per-workgroup partial sums with atomicAdd in arrival order (and, with a dgi that is not 16-byte aligned,
+ * this one may split the rows over fewer workgroups), so from three workgroups on they agree only to the rounding of a
+ * reordered fp32 sum.  Rows >= M of a ragged tile contribute exactly zero.  workspace:
+ * dgppo_mlp_gi_bwd_w_workspace_bytes() bytes for one partial slab [dW2 | dbias2 | dW1 | dbias1] per workgroup (one per
+ * CU); without room for a slab per workgroup (or NULL) the call adds atomically: correct, but slow at many rows.  Up to 4
+ * workgroups (M <= 512) always add atomically.
  * pending == NULL: the slabs are reduced at once.  Otherwise pending[0..1] receive the two owed reductions (pending = 0 where
  * none is owed) for dgppo_dense_bwd_w_reduce_batch, under the rules of dgppo_dense_bwd_w_deferred.  M == 0 touches nothing. */
 int64_t dgppo_mlp_gi_bwd_w_workspace_bytes(void);
