@@ -206,6 +206,11 @@ def lib() -> C.CDLL:
     # the scene mix of a training batch (same file, same operand order: scene_of in place of scene_ids)
     l.dgppo_env_scene_mix.restype = i32
     l.dgppo_env_scene_mix.argtypes = [C.POINTER(EnvCfg), p, p, p, i32, p, p, f32, p, p, p, p, p, i32, p]
+    # failure scenes from a rollout record, and their ring of pool slots (same file)
+    l.dgppo_env_scene_mine.restype = i32
+    l.dgppo_env_scene_mine.argtypes = [C.POINTER(EnvCfg), p, p, i32, p, p, i32, i32, f32, p, p, p, p, p, p, p, i32, p]
+    l.dgppo_env_scene_pool_push.restype = i32
+    l.dgppo_env_scene_pool_push.argtypes = [C.POINTER(EnvCfg), p, p, p, p, p, p, p, p, i32, i32, p, p, i32, p]
     _lib = l
     return l
 

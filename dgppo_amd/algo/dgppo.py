@@ -291,6 +291,23 @@ class DGPPO(Algorithm):
                                  start=self._scene_start(scenes, scene_ids, jitter, int(seeds.shape[0])))
         return self._wrap(ro, env)
 
+    def rollout_record(self, rollout: Rollout, what: str = "rollout_record") -> EN.RolloutData:
+        """the device record behind a Rollout that one of this algo's collect methods returned (until update() consumes it)"""
+        ro = getattr(self, "_last_rollouts", {}).get(id(rollout.actions))
+        if ro is None:
+            raise ValueError(f"{what}() needs a Rollout produced by this algo's collect methods")
+        return ro
+
+    def mine_scenes(self, rollout: Rollout, back: int = 8, thresh: float = 1e-6, max_scenes=None, names=None):
+        """the failure scenes of a rollout that one of this algo's collect methods returned (env.Scenes.mine on its record): for
+        every episode that becomes unsafe at some step >= 1, the state `back` steps before as a scene; None when there is none.
+        Not in the reference."""
+        if self._env.cfg.is_vmas:
+            raise ValueError("mine_scenes: VMASReverseTransport has no scene entry point")
+        from ..env.scenes import Scenes
+        return Scenes.mine(self._env, self.rollout_record(rollout, "mine_scenes"), back=back, thresh=thresh, max_scenes=max_scenes,
+                           names=names)
+
     def collect_shielded(self, keys, env=None, grid: int = 8, us=None, vs=None, margin: float = 0.0, scenes=None, scene_ids=None,
                          jitter: float = 0.0):
         """-> (Rollout, ShieldLog): deterministic test episodes in which every agent's action passes through the learned barrier

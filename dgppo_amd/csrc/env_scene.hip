@@ -11,6 +11,9 @@
 //   flags      0 = valid; DGPPO_SCENE_* bits otherwise
 // The second half of the file, dgppo_env_scene_mix, puts SOME envs of a batch that holds a reset into such scenes (training on a
 // mix of sampled and given starts): one wave per environment, and nothing of an env is written unless its scene is valid.
+// The last part goes the other way: dgppo_env_scene_mine reads, from a rollout record, the state a few steps before every env's first
+// unsafe step as template rows, with the validity bits the two kernels above would give them, and dgppo_env_scene_pool_push keeps
+// the valid ones in a ring of pool slots that a later dgppo_env_scene_mix starts envs in.
 // Built with -ffp-contract=off like env_reset.hip.
 #include <stdio.h>
 #include "env_step.h"
@@ -314,6 +317,246 @@ extern "C" int32_t dgppo_env_scene_mix(const dgppo_env_cfg* cfg, const float* ag
   a.cfg = *cfg; a.agent_t = agent_t; a.goal_t = goal_t; a.obst_t = obst_t; a.S = S; a.scene_of = scene_of; a.seeds = seeds;
   a.jitter = jitter; a.agent = agent; a.goal = goal; a.obst = obst; a.flags = flags; a.n_fallback = n_fallback; a.B = B;
   hipLaunchKernelGGL(env_scene_mix_kernel, dim3(cdiv(B, SCENE_MIX_WAVES)), dim3(64 * SCENE_MIX_WAVES), 0, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- dgppo_env_scene_mine: the state `back` steps before every env's first unsafe step, as scene template rows ---------------
+// One wave64 per env, SCENE_MIX_WAVES envs per block.  The scan reads the env's cost row of a step, W = n * n_cost words, with
+// consecutive lanes on consecutive words, max(1, 64 / W) steps per pass; the passes run in time order and the wave leaves at
+// the first one in which any lane saw a word >= thresh (a NaN compares false), so a failing env reads only up to its failure.
+// The smallest key t * W + w over the lanes is the first unsafe step and its lowest unsafe word.  The rows of step
+// t0 = max(first - back, 0) are then copied word for word and judged with the functions of env_scene_mix_kernel: lane i = agent
+// i, lane o = obstacle o with its record rebuilt from the five words the template keeps.  No LDS, no barrier.
+struct SceneMineArgs {
+  dgppo_env_cfg cfg;
+  const float* agent_tm;
+  const float* cost_tm;
+  int Bs;
+  const float* goal;
+  const float* obst;
+  int T;
+  int back;
+  float thresh;
+  int32_t* first;
+  int32_t* who;
+  int32_t* t0;
+  int32_t* flags;
+  float* agent_t;
+  float* goal_t;
+  float* obst_t;
+  int B;
+};
+
+#define SCENE_NO_KEY 0x7fffffff
+
+__global__ __launch_bounds__(64 * SCENE_MIX_WAVES) void env_scene_mine_kernel(SceneMineArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * SCENE_MIX_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (b >= a.B) return;
+  const dgppo_env_cfg& c = a.cfg;
+  const int n = c.n_agents, ng = c.n_goals, no = c.n_obs, SD = c.state_dim;
+  const bool lidar = cfg_is_lidar(c);
+  const int OT = lidar ? 5 : 2, OS = cfg_obst_stride(c);
+  const int W = n * c.n_cost;
+  const int P = W < 64 ? 64 / W : 1;                     // steps per pass
+  const size_t step_words = (size_t)a.Bs * W;
+  const float* cost = a.cost_tm + (size_t)b * W;
+
+  int key = SCENE_NO_KEY;
+  for (int tb = 0; tb < a.T; tb += P) {
+    for (int idx = lane; idx < P * W; idx += 64) {
+      const int dt = idx / W, w = idx - dt * W, t = tb + dt;
+      if (t < a.T && cost[(size_t)t * step_words + w] >= a.thresh) key = min(key, t * W + w);
+    }
+    if (__any(key != SCENE_NO_KEY)) break;
+  }
+  for (int m = 32; m >= 1; m >>= 1) key = min(key, __shfl_xor(key, m));
+
+  if (key == SCENE_NO_KEY) {                             // never unsafe: the rows are not ours to touch
+    if (lane == 0) {
+      a.first[b] = -1; a.who[b] = -1; a.t0[b] = -1; a.flags[b] = 0;
+    }
+    return;
+  }
+  const int first = key / W, who = key - first * W;
+  const int t0 = max(first - a.back, 0);
+  const float* agent = a.agent_tm + ((size_t)t0 * a.Bs + b) * n * SD;
+  const float* goal = a.goal + (size_t)b * ng * SD;
+  const float* obst = a.obst ? a.obst + (size_t)b * no * OS : nullptr;
+
+  bool bad = scene_wave_nonfinite(agent, n * SD, lane);
+  bad = scene_wave_nonfinite(goal, ng * SD, lane) || bad;
+  bool obad = false;
+  for (int i = lane; i < no * OT; i += 64) {             // the template's words of the obstacle records
+    const int o = i / OT;
+    obad = obad || !isfinite(obst[o * OS + (i - o * OT)]);
+  }
+  bad = __any(obad) || bad;
+  const int nonfinite = bad ? DGPPO_SCENE_NONFINITE : 0;
+
+  float rec[DGPPO_RECT_STRIDE];
+  for (int k = 0; k < DGPPO_RECT_STRIDE; ++k) rec[k] = 0.0f;
+  if (lane < no) {
+    if (lidar) {
+      float t[5];
+      for (int k = 0; k < 5; ++k) t[k] = obst[lane * OS + k];
+      scene_rect_record(t, rec);
+    } else {
+      rec[0] = obst[lane * OS];
+      rec[1] = obst[lane * OS + 1];
+    }
+  }
+  const bool mine = lane < n;
+  const float x = mine ? agent[lane * SD] : 0.0f, y = mine ? agent[lane * SD + 1] : 0.0f;
+  const int bits = nonfinite | scene_wave_geometry(c, lane, x, y, rec, lidar);
+
+  uint32_t* agent_t = (uint32_t*)(a.agent_t + (size_t)b * n * SD);
+  for (int i = lane; i < n * SD; i += 64) agent_t[i] = ((const uint32_t*)agent)[i];
+  uint32_t* goal_t = (uint32_t*)(a.goal_t + (size_t)b * ng * SD);
+  for (int i = lane; i < ng * SD; i += 64) goal_t[i] = ((const uint32_t*)goal)[i];
+  if (no > 0) {
+    uint32_t* obst_t = (uint32_t*)(a.obst_t + (size_t)b * no * OT);
+    for (int i = lane; i < no * OT; i += 64) {
+      const int o = i / OT;
+      obst_t[i] = ((const uint32_t*)obst)[o * OS + (i - o * OT)];
+    }
+  }
+  if (lane == 0) {
+    a.first[b] = first; a.who[b] = who; a.t0[b] = t0; a.flags[b] = bits;
+  }
+}
+
+// every refusal of the two entry points below names them: dgppo_validate_cfg's own message does not
+static int32_t scene_validate_cfg(const dgppo_env_cfg* cfg, const char* fn) {
+  int32_t rc = dgppo_validate_cfg(cfg);
+  if (rc) {
+    char why[256];
+    snprintf(why, sizeof(why), "%s", dgppo_last_error());
+    dgppo_set_error("%s: %s", fn, why);
+  }
+  return rc;
+}
+
+extern "C" int32_t dgppo_env_scene_mine(const dgppo_env_cfg* cfg, const float* agent_tm, const float* cost_tm, int32_t Bs,
+                                        const float* goal, const float* obst, int32_t T, int32_t back, float thresh,
+                                        int32_t* first, int32_t* who, int32_t* t0, int32_t* flags, float* agent_t, float* goal_t,
+                                        float* obst_t, int32_t B, void* stream) {
+  int32_t rc = scene_validate_cfg(cfg, "dgppo_env_scene_mine");
+  if (rc) return rc;
+  DGPPO_REFUSE_VMAS(cfg, "dgppo_env_scene_mine", "nothing (VMASReverseTransport has no scene entry point)");
+  DGPPO_REQUIRE(B >= 0, "dgppo_env_scene_mine: B must be >= 0 (got %d)", B);
+  DGPPO_REQUIRE(Bs >= B, "dgppo_env_scene_mine: Bs, the envs per time slot of the record, must be >= B (got %d, B %d)", Bs, B);
+  DGPPO_REQUIRE(T >= 1, "dgppo_env_scene_mine: T must be >= 1 (got %d)", T);
+  DGPPO_REQUIRE(back >= 0, "dgppo_env_scene_mine: back must be >= 0 (got %d)", back);
+  DGPPO_REQUIRE(isfinite(thresh), "dgppo_env_scene_mine: thresh must be finite (got %g)", (double)thresh);
+  DGPPO_REQUIRE(agent_tm && cost_tm && goal, "dgppo_env_scene_mine: agent_tm/cost_tm/goal must not be NULL");
+  DGPPO_REQUIRE(first && who && t0 && flags && agent_t && goal_t,
+                "dgppo_env_scene_mine: first/who/t0/flags/agent_t/goal_t must not be NULL");
+  DGPPO_REQUIRE((cfg->n_obs == 0) == (obst == nullptr), "dgppo_env_scene_mine: obst must be NULL exactly when n_obs == 0");
+  DGPPO_REQUIRE((cfg->n_obs == 0) == (obst_t == nullptr), "dgppo_env_scene_mine: obst_t must be NULL exactly when n_obs == 0");
+  DGPPO_REQUIRE(cfg->n_agents <= SCENE_MAX_AGENTS, "dgppo_env_scene_mine supports at most %d agents", SCENE_MAX_AGENTS);
+  DGPPO_REQUIRE((int64_t)T * cfg->n_agents * cfg->n_cost < (int64_t)SCENE_NO_KEY,
+                "dgppo_env_scene_mine: T * n_agents * n_cost must be below 2^31 - 1 (T %d)", T);
+  if (B == 0) return 0;
+  SceneMineArgs a;
+  a.cfg = *cfg; a.agent_tm = agent_tm; a.cost_tm = cost_tm; a.Bs = Bs; a.goal = goal; a.obst = obst; a.T = T; a.back = back;
+  a.thresh = thresh; a.first = first; a.who = who; a.t0 = t0; a.flags = flags; a.agent_t = agent_t; a.goal_t = goal_t;
+  a.obst_t = obst_t; a.B = B;
+  hipLaunchKernelGGL(env_scene_mine_kernel, dim3(cdiv(B, SCENE_MIX_WAVES)), dim3(64 * SCENE_MIX_WAVES), 0, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- dgppo_env_scene_pool_push: the mined rows of the taken envs into a ring of pool slots ---------------------------------------
+// One workgroup: a deterministic stream compaction.  Env b is taken iff first[b] >= 1 && flags[b] == 0; the taken envs are ranked
+// in ascending b (a ballot per wave, a prefix over the waves in LDS, chunks of the block size over B) and rank r < R goes to slot
+// fixed + (head + r) % R: the ranks are distinct, so are the slots, and no atomic decides anything.  A wave copies the rows of
+// its own taken envs, its lanes striding over a row's words.
+#define SCENE_PUSH_WAVES 4
+
+struct ScenePushArgs {
+  const int32_t* first;
+  const int32_t* flags;
+  const uint32_t* agent_t;
+  const uint32_t* goal_t;
+  const uint32_t* obst_t;
+  uint32_t* pool_agent;
+  uint32_t* pool_goal;
+  uint32_t* pool_obst;
+  int words_agent, words_goal, words_obst;               // per row
+  int M, fixed;
+  int32_t* state;
+  int32_t* slot_of;
+  int B;
+};
+
+__global__ __launch_bounds__(64 * SCENE_PUSH_WAVES) void env_scene_pool_push_kernel(ScenePushArgs a) {
+  __shared__ int wave_count[SCENE_PUSH_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int R = a.M - a.fixed;
+  const int head = a.state[0], filled = a.state[1], pushed = a.state[2];    // read before the first barrier, written after the last
+  int base = 0;                                          // taken envs of the chunks before this one
+  for (int chunk = 0; chunk < a.B; chunk += 64 * SCENE_PUSH_WAVES) {
+    const int b = chunk + tid;
+    const bool taken = b < a.B && a.first[b] >= 1 && a.flags[b] == 0;
+    const unsigned long long ballot = __ballot(taken);
+    if (lane == 0) wave_count[wave] = __popcll(ballot);
+    __syncthreads();
+    int before = 0, total = 0;
+    for (int w = 0; w < SCENE_PUSH_WAVES; ++w) {
+      const int cnt = wave_count[w];
+      if (w < wave) before += cnt;
+      total += cnt;
+    }
+    const int r = base + before + __popcll(ballot & ((1ull << lane) - 1ull));
+    const int slot = (taken && r < R) ? a.fixed + (head + r) % R : -1;
+    if (b < a.B && a.slot_of) a.slot_of[b] = slot;
+    unsigned long long todo = __ballot(slot >= 0);
+    while (todo) {                                       // wave-uniform: one taken env of this wave per trip
+      const int k = __ffsll((long long)todo) - 1;
+      todo &= todo - 1ull;
+      const size_t src = (size_t)(chunk + wave * 64 + k), dst = (size_t)__shfl(slot, k);
+      for (int i = lane; i < a.words_agent; i += 64) a.pool_agent[dst * a.words_agent + i] = a.agent_t[src * a.words_agent + i];
+      for (int i = lane; i < a.words_goal; i += 64) a.pool_goal[dst * a.words_goal + i] = a.goal_t[src * a.words_goal + i];
+      for (int i = lane; i < a.words_obst; i += 64) a.pool_obst[dst * a.words_obst + i] = a.obst_t[src * a.words_obst + i];
+    }
+    base += total;
+    __syncthreads();                                     // wave_count is rewritten by the next chunk
+  }
+  if (tid == 0) {
+    const int m = min(base, R);
+    a.state[0] = (head + m) % R;
+    a.state[1] = min(R, filled + m);
+    a.state[2] = (int32_t)((uint32_t)pushed + (uint32_t)m);
+    a.state[3] = base;
+  }
+}
+
+extern "C" int32_t dgppo_env_scene_pool_push(const dgppo_env_cfg* cfg, const int32_t* first, const int32_t* flags,
+                                             const float* agent_t, const float* goal_t, const float* obst_t, float* pool_agent,
+                                             float* pool_goal, float* pool_obst, int32_t M, int32_t fixed, int32_t* state,
+                                             int32_t* slot_of, int32_t B, void* stream) {
+  int32_t rc = scene_validate_cfg(cfg, "dgppo_env_scene_pool_push");
+  if (rc) return rc;
+  DGPPO_REFUSE_VMAS(cfg, "dgppo_env_scene_pool_push", "nothing (VMASReverseTransport has no scene entry point)");
+  DGPPO_REQUIRE(B >= 0, "dgppo_env_scene_pool_push: B must be >= 0 (got %d)", B);
+  DGPPO_REQUIRE(M >= 1 && M <= (1 << 30), "dgppo_env_scene_pool_push: M must be in [1, 2^30] (got %d)", M);
+  DGPPO_REQUIRE(fixed >= 0 && fixed < M, "dgppo_env_scene_pool_push: fixed must be in [0, M) (got %d, M %d)", fixed, M);
+  DGPPO_REQUIRE(first && flags && agent_t && goal_t && pool_agent && pool_goal && state,
+                "dgppo_env_scene_pool_push: first/flags/agent_t/goal_t/pool_agent/pool_goal/state must not be NULL");
+  DGPPO_REQUIRE((cfg->n_obs == 0) == (obst_t == nullptr), "dgppo_env_scene_pool_push: obst_t must be NULL exactly when n_obs == 0");
+  DGPPO_REQUIRE((cfg->n_obs == 0) == (pool_obst == nullptr),
+                "dgppo_env_scene_pool_push: pool_obst must be NULL exactly when n_obs == 0");
+  DGPPO_REQUIRE(cfg->n_agents <= SCENE_MAX_AGENTS, "dgppo_env_scene_pool_push supports at most %d agents", SCENE_MAX_AGENTS);
+  ScenePushArgs a;
+  a.first = first; a.flags = flags; a.agent_t = (const uint32_t*)agent_t; a.goal_t = (const uint32_t*)goal_t;
+  a.obst_t = (const uint32_t*)obst_t; a.pool_agent = (uint32_t*)pool_agent; a.pool_goal = (uint32_t*)pool_goal;
+  a.pool_obst = (uint32_t*)pool_obst;
+  a.words_agent = cfg->n_agents * cfg->state_dim; a.words_goal = cfg->n_goals * cfg->state_dim;
+  a.words_obst = cfg->n_obs * (cfg_is_lidar(*cfg) ? 5 : 2);
+  a.M = M; a.fixed = fixed; a.state = state; a.slot_of = slot_of; a.B = B;
+  hipLaunchKernelGGL(env_scene_pool_push_kernel, dim3(1), dim3(64 * SCENE_PUSH_WAVES), 0, (hipStream_t)stream, a);
   DGPPO_LAUNCH_CHECK();
   return 0;
 }

@@ -246,9 +246,12 @@ class Engine:
         # the device by every rollout, read at the iteration's one host sync (info) — training on such a batch is an error
         self.reset_failed = torch.zeros(1, dtype=torch.int32, device=device)
         # envs of a mixed start (env.scenes.SceneMix) whose scene stayed invalid and that kept their sampled reset instead
-        # (dgppo_env_scene_mix): counted next to reset_failed, reported by info() as rollout/scene_fallback, never an error
+        # (dgppo_env_scene_mix): counted next to reset_failed, reported by info() as rollout/scene_fallback, never an error.
+        # Under a pool of mined scenes (env.scenes.ScenePool) an empty ring slot holds NaN words and means "sampled reset", so
+        # while the ring is not full the counter also holds the envs that drew an empty slot
         self.scene_fallback = torch.zeros(1, dtype=torch.int32, device=device)
         self._mix_used = False
+        self._mix_pool = None
         self.grad_hook: Optional[Callable[[str, nets.Net, int], None]] = None   # (net name, net, minibatch) before the optimiser
         self._mb = 0
 
@@ -379,6 +382,8 @@ class Engine:
         from .env.scenes import SceneMix
         if isinstance(start, SceneMix):
             self._mix_used = True
+            # a pool of mined scenes (env.scenes.ScenePool): info() reports its fill next to scene_fallback
+            self._mix_pool = start.scenes if hasattr(start.scenes, "fill") else None
             return OE.mixed_start(self.cfg, seeds, st, start.scenes.dev, start.scene_of, float(start.jitter), self.reset_failed,
                                   self.scene_fallback)
         scenes, scene_ids, jitter = start
@@ -1637,6 +1642,11 @@ class Engine:
                         "Vh/grad_Vh_has_nan": float(o["Vh"][5])})
         if self.algo in ("dgppo", "hcbfcrpo"):   # hcbfcrpo.py:204
             out["eval/safe_data"] = safe / (self.world * B * self.T * self.cfg.n_agents)
-        if mixed:                      # envs of this iteration's rollouts, over all ranks, that kept their reset
-            out["rollout/scene_fallback"] = float(sums[1])
+        if mixed:                      # envs of this iteration's rollouts, over all ranks, that kept their reset; with a pool
+            out["rollout/scene_fallback"] = float(sums[1])   # of mined scenes also those that drew a slot still empty
+            pool, self._mix_pool = self._mix_pool, None
+            if pool is not None:       # one rank only (train.py refuses more): the ring after this iteration's push
+                filled, pushed, taken = pool.fill()
+                out.update({"rollout/scene_pool_fill": float(filled), "rollout/scene_pool_pushed": float(pushed),
+                            "rollout/scene_pool_taken": float(taken)})
         return out

@@ -6,6 +6,10 @@ obstacles as (cx, cy, w, h, theta) or (ox, oy) — and dgppo_env_scene_load (csr
 
     scenes = Scenes(env, agent, goal, rect=rect)          # or Scenes.load("headon.npz", env)
     ro = algo.collect_deterministic(keys, env=env, scenes=scenes)     # episode b starts in scene b % S
+
+Scenes also come out of rollouts: the state a few steps before an episode's first unsafe step is a scene from which this policy
+fails (dgppo_env_scene_mine).  Scenes.mine(env, record) reads them back as a Scenes; ScenePool keeps them on the device, in a ring
+that a training run refills from every rollout (dgppo_env_scene_pool_push) and starts a share of its next batch in.
 """
 from __future__ import annotations
 
@@ -168,6 +172,39 @@ class Scenes:
         z = check_file(path, env.KIND, env.num_agents)
         return cls(env, z["agent"], z["goal"], rect=z["rect"], disc=z["disc"], names=z["names"])
 
+    @classmethod
+    def mine(cls, env, record, back: int = 8, thresh: float = 1e-6, max_scenes: Optional[int] = None,
+             names=None) -> Optional["Scenes"]:
+        """failure scenes of a rollout record (engine.RolloutData; its time-major fields are enough, before or after
+        finalize()): for every env whose cost reaches `thresh` at some step first >= 1, the state `back` steps earlier
+        (t0 = max(first - back, 0)) as a scene, where that state is a valid one (dgppo_env_scene_mine's flags).  The taken
+        envs are kept in env order, the first max_scenes of them; None when there is none.  names: one string per kept
+        scene, or a function (env index, first, t0, who) -> string; default env{b}_t{t0}_first{first}_a{agent}.  The result
+        carries .mined = dict(env, first, t0, who): host int arrays, one entry per scene (who = agent * n_cost + cost column).
+        The state is the situation, not the rest of the episode: it restarts with a zero actor carry and a fresh step count."""
+        cfg = env.cfg
+        if cfg.is_vmas:
+            raise ValueError("Scenes.mine: VMASReverseTransport has no scene entry point")
+        B = int(record.agent_tm.shape[1])
+        out = OE.alloc_mined(cfg, B, record.agent_tm.device)
+        OE.scene_mine(cfg, record.agent_tm, record.cost_tm, record.goal, record.obst, back, thresh, out)
+        host = {k: v.cpu().numpy() for k, v in out.items()}
+        took = np.flatnonzero((host["first"] >= 1) & (host["flags"] == 0))
+        if max_scenes is not None:
+            took = took[:max(int(max_scenes), 0)]
+        if len(took) == 0:
+            return None
+        first, t0, who = host["first"][took], host["t0"][took], host["who"][took]
+        if names is None:
+            names = lambda b, f, t, w: f"env{b}_t{t}_first{f}_a{w // cfg.n_cost}"
+        if callable(names):
+            names = [names(int(b), int(f), int(t), int(w)) for b, f, t, w in zip(took, first, t0, who)]
+        obst = host["obst"][took] if "obst" in host else None
+        sc = cls(env, host["agent"][took], host["goal"][took], rect=obst if cfg.is_lidar else None,
+                 disc=None if cfg.is_lidar else obst, names=names)
+        sc.mined = dict(env=took.astype(np.int64), first=first.astype(np.int64), t0=t0.astype(np.int64), who=who.astype(np.int64))
+        return sc
+
     @staticmethod
     def bicycle_rows(x, y, heading, speed) -> np.ndarray:
         """[..., 5] agent or goal rows of LidarBicycleTarget in the record's layout: x, y, cos(heading), sin(heading), speed
@@ -175,3 +212,85 @@ class Scenes:
         x, y, heading, speed = np.broadcast_arrays(np.asarray(x, f32), np.asarray(y, f32), np.asarray(heading, f32),
                                                    np.asarray(speed, f32))
         return np.stack([x, y, np.cos(heading).astype(f32), np.sin(heading).astype(f32), speed], axis=-1).astype(f32)
+
+
+def check_pool(capacity: int, n_pinned: int) -> None:
+    """the host half of ScenePool(): ValueError; touches no device"""
+    if int(capacity) < 1 or int(capacity) <= int(n_pinned):
+        raise ValueError(f"ScenePool: capacity must be >= 1 and larger than the number of pinned scenes, so that the ring of mined "
+                         f"scenes has a slot (got capacity {capacity}, {n_pinned} pinned)")
+
+
+class ScenePool:
+    """A device-resident pool of M = capacity scenes for a training run that mines its own failures: the scenes of `pinned` in
+    slots 0 .. P-1, never overwritten, and behind them a ring of R = M - P slots that push_from() fills with the failure scenes of
+    a rollout record (dgppo_env_scene_mine, dgppo_env_scene_pool_push), oldest overwritten first.  It has what the engine and
+    SceneMix read of a Scenes (.dev, .S = M, .cfg, .names, .mix), so collect(..., scenes=pool, scene_of=...) works unchanged.
+    An empty ring slot holds NaN words: dgppo_env_scene_mix gives an env that draws it the NONFINITE bit and leaves its sampled
+    reset standing, so an empty slot means "sampled reset" (counted in rollout/scene_fallback), mix_assignment keeps S = M from
+    the first iteration, and no count has to come back to the host before a rollout.
+      state (device int32 [4])   head, filled, pushed_total, taken_last (dgppo_env_scene_pool_push)"""
+
+    def __init__(self, env, capacity: int, pinned: Optional[Scenes] = None):
+        cfg = env.cfg
+        if cfg.is_vmas:
+            raise ValueError("ScenePool: VMASReverseTransport has no scene entry point")
+        self.P = 0 if pinned is None else int(pinned.S)
+        check_pool(capacity, self.P)
+        if pinned is not None and (pinned.cfg.kind, pinned.cfg.n_agents, pinned.cfg.n_obs) != (cfg.kind, cfg.n_agents, cfg.n_obs):
+            raise ValueError("ScenePool: the pinned scenes are of another env")
+        self.env, self.cfg, self.S = env, cfg, int(capacity)
+        self.env_id, self.num_agents = env.KIND, int(cfg.n_agents)
+        dev = env.device
+        self.dev: Dict[str, torch.Tensor] = {k: torch.full((self.S,) + s, float("nan"), device=dev)
+                                             for k, s in OE.scene_template_shapes(cfg).items()}
+        if pinned is not None:
+            for k, v in self.dev.items():
+                v[:self.P].copy_(pinned.dev[k])
+        self.pinned_names = [] if pinned is None else list(pinned.names)
+        self.state = torch.zeros(4, dtype=torch.int32, device=dev)
+        self._mined: Dict[int, Dict[str, torch.Tensor]] = {}      # scene_mine's outputs per batch size, allocated once
+
+    @property
+    def names(self):
+        return self.pinned_names + [f"pool{m}" for m in range(self.P, self.S)]
+
+    def mix(self, scene_of, jitter: float = 0.0) -> SceneMix:
+        return SceneMix(self, np.asarray(scene_of), float(jitter))
+
+    def push_from(self, record, back: int = 8, thresh: float = 1e-6) -> None:
+        """mine the record (engine.RolloutData) and push its taken envs into the ring: two launches, no sync"""
+        B = int(record.agent_tm.shape[1])
+        if B not in self._mined:
+            self._mined[B] = OE.alloc_mined(self.cfg, B, self.state.device)
+        out = self._mined[B]
+        OE.scene_mine(self.cfg, record.agent_tm, record.cost_tm, record.goal, record.obst, back, thresh, out)
+        OE.scene_pool_push(self.cfg, out, self.dev, self.P, self.state)
+
+    def fill(self):
+        """-> (filled, pushed_total, taken_last); one host sync"""
+        _, filled, pushed, taken = self.state.cpu().tolist()
+        return int(filled), int(pushed), int(taken)
+
+    def to_scenes(self) -> Optional[Scenes]:
+        """the pinned and the filled slots as a host Scenes (the ring fills from its first slot on); None while there is none"""
+        k = self.P + self.fill()[0]
+        if k == 0:
+            return None
+        rows = {name: v[:k].cpu().numpy() for name, v in self.dev.items()}
+        obst = rows.get("obst")
+        return Scenes(self.env, rows["agent"], rows["goal"], rect=obst if self.cfg.is_lidar else None,
+                      disc=None if self.cfg.is_lidar else obst, names=self.names[:k])
+
+    def state_dict(self) -> dict:
+        d = {k: v.cpu().numpy() for k, v in self.dev.items()}
+        d["state"] = self.state.cpu().numpy()
+        d["pinned"] = int(self.P)
+        return d
+
+    def load_state_dict(self, d: dict) -> None:
+        if int(d.get("pinned", -1)) != self.P or any(k not in d or tuple(d[k].shape) != tuple(v.shape) for k, v in self.dev.items()):
+            raise ValueError("ScenePool: the stored pool does not fit this one (capacity, pinned scenes or env differ)")
+        for k, v in self.dev.items():
+            v.copy_(torch.from_numpy(np.ascontiguousarray(d[k], f32)))
+        self.state.copy_(torch.from_numpy(np.ascontiguousarray(d["state"], np.int32)))

@@ -415,6 +415,99 @@ def mixed_start(cfg: N.EnvCfg, seeds: torch.Tensor, st: State, scenes_dev: Dict[
         materialize(cfg, st, graph)
 
 
+MINED_FIELDS = ("first", "who", "t0", "flags")          # the int32 [B] outputs of scene_mine, next to the template rows
+
+
+def alloc_mined(cfg: N.EnvCfg, B: int, device) -> Dict[str, torch.Tensor]:
+    """the outputs of scene_mine for B envs: first, who, t0, flags (int32 [B]) and the template rows agent, goal[, obst]
+    (scene_template_shapes with a leading B), uninitialised"""
+    out = {k: torch.empty(B, dtype=torch.int32, device=device) for k in MINED_FIELDS}
+    out.update({k: torch.empty(B, *s, device=device) for k, s in scene_template_shapes(cfg).items()})
+    return out
+
+
+def _time_major(x: torch.Tensor, lead: int, B: int, tail: tuple, name: str) -> int:
+    """x [lead, B, *tail], dense but for its step stride -> Bs, the envs per time slot of its allocation (x may be the first B
+    envs of a wider record: RolloutData.prefix)"""
+    N.expect_shape(x, (lead, B) + tuple(tail), name)
+    row = int(np.prod(tail))
+    inner = tuple(int(np.prod(tail[k + 1:])) for k in range(len(tail)))
+    st = x.stride()
+    if tuple(st[2:]) != inner or st[1] != row or st[0] % row or st[0] < B * row:
+        raise ValueError(f"{name}: a time-major record [T, B, ...] with dense rows is required (strides {tuple(st)})")
+    return int(st[0]) // row
+
+
+def scene_mine(cfg: N.EnvCfg, agent_tm, cost_tm, goal, obst, back: int, thresh: float, out: Dict[str, torch.Tensor]):
+    """dgppo_env_scene_mine: for every env of the time-major record agent_tm [T+1, B, n, sd], cost_tm [T, B, n, n_cost] (dense,
+    or the first B envs of a wider record: the step stride is read off the tensors) with the per-env rows goal [B, ng, sd] and
+    obst [B, n_obs, stride] (None without obstacles), the first step with a cost word >= thresh, and the state `back` steps
+    before it as template rows, into out (alloc_mined).  Every refusal is raised before anything is launched."""
+    fn = "scene_mine"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no scene entry point")
+    if not (torch.is_tensor(agent_tm) and agent_tm.ndim == 4 and agent_tm.shape[0] >= 2):
+        raise ValueError(f"{fn}: agent_tm must be a [T+1, B, n, sd] tensor with T >= 1")
+    T, B = int(agent_tm.shape[0]) - 1, int(agent_tm.shape[1])
+    n, sd = cfg.n_agents, cfg.state_dim
+    Bs = _time_major(agent_tm, T + 1, B, (n, sd), "agent_tm")
+    if _time_major(cost_tm, T, B, (n, cfg.n_cost), "cost_tm") != Bs:
+        raise ValueError(f"{fn}: agent_tm and cost_tm must be views of records with the same number of envs")
+    _check_state(cfg, B, agent=agent_tm[0], goal=goal, obst=obst)
+    back, thresh = int(back), float(thresh)
+    if back < 0:
+        raise ValueError(f"{fn}: back must be >= 0 (got {back})")
+    if not np.isfinite(thresh):
+        raise ValueError(f"{fn}: thresh must be finite (got {thresh})")
+    for k in MINED_FIELDS:
+        N.expect_shape(out[k], (B,), f"out.{k}")
+    for k, s in scene_template_shapes(cfg).items():
+        N.expect_shape(out[k], (B,) + s, f"out.{k}")
+    if B == 0:
+        return
+    for x, name in ((agent_tm, "agent_tm"), (cost_tm, "cost_tm")):
+        if not x.is_cuda or x.dtype != torch.float32:
+            raise TypeError(f"{fn}: {name} must be a float32 tensor on the GPU")
+    i32 = torch.int32
+    rc = N.lib().dgppo_env_scene_mine(
+        C.byref(cfg), C.c_void_p(agent_tm.data_ptr()), C.c_void_p(cost_tm.data_ptr()), Bs, N.ptr(goal, name="goal"),
+        N.ptr(obst if cfg.n_obs > 0 else None, name="obst"), T, back, thresh, N.ptr(out["first"], i32, "out.first"),
+        N.ptr(out["who"], i32, "out.who"), N.ptr(out["t0"], i32, "out.t0"), N.ptr(out["flags"], i32, "out.flags"),
+        N.ptr(out["agent"], name="out.agent"), N.ptr(out["goal"], name="out.goal"),
+        N.ptr(out.get("obst") if cfg.n_obs > 0 else None, name="out.obst"), B, N.stream_ptr())
+    N.check(rc, "dgppo_env_scene_mine")
+
+
+def scene_pool_push(cfg: N.EnvCfg, mined: Dict[str, torch.Tensor], pool: Dict[str, torch.Tensor], fixed: int, state, slot_of=None):
+    """dgppo_env_scene_pool_push: the rows of the taken envs of `mined` (scene_mine's outputs: first >= 1 and flags == 0) into
+    the ring of pool slots fixed .. M-1 of `pool` (agent, goal[, obst], each [M, ...] in the template shapes), in env order from
+    state[0] = head on; state (int32 [4] on the device: head, filled, pushed_total, taken_last) is advanced, slot_of (int32 [B],
+    optional) receives every env's slot or -1.  Every refusal is raised before anything is launched."""
+    fn = "scene_pool_push"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no scene entry point")
+    shapes = scene_template_shapes(cfg)
+    B, M = int(mined["first"].shape[0]), int(pool["agent"].shape[0])
+    fixed = int(fixed)
+    if not (M >= 1 and 0 <= fixed < M):
+        raise ValueError(f"{fn}: need M >= 1 and 0 <= fixed < M (got M {M}, fixed {fixed})")
+    N.expect_shape(mined["flags"], (B,), "mined.flags")
+    for k, s in shapes.items():
+        N.expect_shape(mined[k], (B,) + s, f"mined.{k}")
+        N.expect_shape(pool[k], (M,) + s, f"pool.{k}")
+    N.expect_shape(state, (4,), "state")
+    if slot_of is not None:
+        N.expect_shape(slot_of, (B,), "slot_of")
+    i32, obst = torch.int32, cfg.n_obs > 0
+    rc = N.lib().dgppo_env_scene_pool_push(
+        C.byref(cfg), N.ptr(mined["first"], i32, "mined.first"), N.ptr(mined["flags"], i32, "mined.flags"),
+        N.ptr(mined["agent"], name="mined.agent"), N.ptr(mined["goal"], name="mined.goal"),
+        N.ptr(mined["obst"] if obst else None, name="mined.obst"), N.ptr(pool["agent"], name="pool.agent"),
+        N.ptr(pool["goal"], name="pool.goal"), N.ptr(pool["obst"] if obst else None, name="pool.obst"), M, fixed,
+        N.ptr(state, i32, "state"), N.ptr(slot_of, i32, "slot_of"), B, N.stream_ptr())
+    N.check(rc, "dgppo_env_scene_pool_push")
+
+
 def step(cfg: N.EnvCfg, st: State, action, nst: State, reward, cost, graph: Optional[Dict[str, torch.Tensor]] = None):
     """one env step from st into the per-step fields of nst (st.like()): reward [B] and cost [B, n, n_cost] of the pre-step
     state, the optional graph of the post-step state"""

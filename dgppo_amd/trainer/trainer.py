@@ -14,7 +14,12 @@ step ("Resuming a stopped run").
 Designed scenes (not in the reference): `Trainer(..., scenes=Scenes, scene_frac=P, scene_jitter=J)` starts
 floor(P n_env_train + 0.5) envs of every training batch in the given scenes, jittered by up to J, and the rest at the sampled
 reset (env.scenes.mix_assignment, a function of the global env index and the step: no new state to resume); every evaluation
-also rolls each scene once."""
+also rolls each scene once.
+
+Mined scenes (not in the reference): `Trainer(..., mine_scenes=M, mine_back=K, scene_frac=P)` keeps a device-resident pool of M
+scenes (env.scenes.ScenePool; `scenes`, if given, pinned in its first slots), starts the share P of every batch in it, and after
+every collect pushes the states K steps before the rollout's failures into its ring.  One rank only; the pool is part of the
+state a stopped run resumes from, and every save also writes it as `{log_dir}/scenes/{step}.npz`."""
 from __future__ import annotations
 
 import json
@@ -24,7 +29,7 @@ from time import time
 import numpy as np
 import torch
 
-from ..env.scenes import mix_assignment
+from ..env.scenes import ScenePool, mix_assignment
 from ..utils import checkpoint as CK
 
 KEEP_STATES = 2          # state files kept under {log_dir}/resume: the newest and the one before it
@@ -64,7 +69,7 @@ class _Logger:
 class Trainer:
     def __init__(self, env, env_test, algo, gamma: float, n_env_train: int, n_env_test: int, log_dir: str, seed: int,
                  params: dict, save_log: bool = True, rank: int = 0, world: int = 1, resume: bool = False, scenes=None,
-                 scene_frac: float = 0.0, scene_jitter: float = 0.0):
+                 scene_frac: float = 0.0, scene_jitter: float = 0.0, mine_scenes: int = 0, mine_back: int = 8):
         self.env, self.env_test, self.algo, self.gamma = env, env_test, algo, gamma
         self.n_env_train, self.n_env_test, self.log_dir, self.seed = n_env_train, n_env_test, log_dir, seed
         self.rank, self.world = int(rank), int(world)
@@ -95,10 +100,20 @@ class Trainer:
         self.start_step = 0
         # the share of every training batch that starts in the given scenes: n_scene of the n_env_train global envs
         self.scenes, self.scene_jitter = scenes, float(scene_jitter)
-        self.n_scene = scene_count(scene_frac, n_env_train) if scenes is not None else 0
-        if scenes is None and (float(scene_frac) != 0.0 or self.scene_jitter != 0.0):
-            raise ValueError("Trainer: scene_frac / scene_jitter need scenes")
-        if scenes is not None and not (0.0 < float(scene_frac) <= 1.0 and self.scene_jitter >= 0.0 and self.n_scene >= 1):
+        # mining: the pool takes the place of the scenes in every collect; the given scenes are its pinned slots
+        self.pool, self.mine_back = None, int(mine_back)
+        if int(mine_scenes) != 0:
+            if self.world > 1:
+                raise ValueError("Trainer: mine_scenes runs on one rank: every rank would keep a pool of its own failures and the "
+                                 "ranks' windows would no longer be what one device runs")
+            if self.mine_back < 0:
+                raise ValueError(f"Trainer: mine_back must be >= 0 (got {mine_back})")
+            self.pool = ScenePool(env, int(mine_scenes), pinned=scenes)
+        source = self.pool if self.pool is not None else scenes
+        self.n_scene = scene_count(scene_frac, n_env_train) if source is not None else 0
+        if source is None and (float(scene_frac) != 0.0 or self.scene_jitter != 0.0):
+            raise ValueError("Trainer: scene_frac / scene_jitter need scenes (given ones, or mine_scenes for a pool of mined ones)")
+        if source is not None and not (0.0 < float(scene_frac) <= 1.0 and self.scene_jitter >= 0.0 and self.n_scene >= 1):
             raise ValueError(f"Trainer: with scenes, scene_frac must be in (0, 1] and give at least one of the {n_env_train} "
                              f"training envs, and scene_jitter must be >= 0 (got {scene_frac}, {scene_jitter})")
         if resume:
@@ -107,8 +122,19 @@ class Trainer:
     # ---- the state at step s is the state BEFORE iteration s: the loop saves it after eval and the weights save, before it
     # draws the keys of iteration s, so a resumed run repeats the evaluation and the save of step s and goes on from there ----
     def state_dict(self, step: int) -> dict:
-        return {"algo": self.algo.state_dict(),
-                "trainer": {"key": CK.generator_state(self.key), "step": int(step), "update_steps": int(self.update_steps)}}
+        d = {"algo": self.algo.state_dict(),
+             "trainer": {"key": CK.generator_state(self.key), "step": int(step), "update_steps": int(self.update_steps)}}
+        if self.pool is not None:
+            d["scene_pool"] = self.pool.state_dict()
+        return d
+
+    def _save_scenes(self, step: int):
+        """the pinned and mined scenes of the pool as a scenes file, {log_dir}/scenes/{step}.npz (test.py --scenes reads it);
+        nothing while the pool holds none"""
+        sc = self.pool.to_scenes()
+        if sc is not None:
+            os.makedirs(os.path.join(self.log_dir, "scenes"), exist_ok=True)
+            sc.save(os.path.join(self.log_dir, "scenes", f"{step}.npz"))
 
     def _save_state(self, step: int):
         CK.save_state(self.state_dict(step), os.path.join(self.resume_dir, f"{step}.pkl"))
@@ -125,6 +151,10 @@ class Trainer:
         tr = tree["trainer"]
         if int(tr["step"]) != s:
             raise ValueError(f"{self.resume_dir}/{s}.pkl holds the state of step {int(tr['step'])}")
+        if self.pool is not None:
+            if "scene_pool" not in tree:
+                raise ValueError(f"{self.resume_dir}/{s}.pkl holds no scene pool: the stopped run did not mine scenes")
+            self.pool.load_state_dict(tree["scene_pool"])
         self.algo.load_state_dict(tree["algo"])
         CK.set_generator_state(self.key, tr["key"])
         self.start_step, self.update_steps = s, int(tr["update_steps"])
@@ -165,9 +195,11 @@ class Trainer:
             "_reward_min": float(total.min()), "_reward_max": float(total.max()),
         }
 
-    def evaluate_scenes(self) -> dict:
-        """every given scene rolled once on env_test: deterministic, not jittered; the reductions of evaluate"""
-        r = self.algo.collect_deterministic(np.arange(1, self.scenes.S + 1), env=self.env_test, scenes=self.scenes)
+    def evaluate_scenes(self, scenes=None) -> dict:
+        """every given scene (default: self.scenes) rolled once on env_test: deterministic, not jittered; the reductions of
+        evaluate"""
+        scenes = self.scenes if scenes is None else scenes
+        r = self.algo.collect_deterministic(np.arange(1, scenes.S + 1), env=self.env_test, scenes=scenes)
         rewards, costs = r.rewards.cpu().numpy(), r.costs.cpu().numpy()
         return {"eval/scene_reward": float(rewards.sum(-1).mean()),
                 "eval/scene_cost": float(np.maximum(costs, 0.0).max(-1).max(-1).sum(-1).mean()),
@@ -184,22 +216,28 @@ class Trainer:
                 print(f"step: {step:3}, time: {time() - start_time:5.0f}s, reward: {ev['eval/reward']:9.4f}, "
                       f"min/max reward: {rmin:7.2f}/{rmax:7.2f}, cost: {ev['eval/cost']:8.4f}, "
                       f"unsafe_frac: {ev['eval/unsafe_frac']:6.2f}", flush=True)
-                if self.scenes is not None:
-                    ev.update(self.evaluate_scenes())
+                held = self.pool.to_scenes() if self.pool is not None else self.scenes     # a pool: its pinned + filled slots
+                if held is not None:
+                    ev.update(self.evaluate_scenes(held))
                     print(f"           scenes: reward: {ev['eval/scene_reward']:9.4f}, cost: {ev['eval/scene_cost']:8.4f}, "
                           f"unsafe_frac: {ev['eval/scene_unsafe_frac']:6.2f}", flush=True)
                 self.logger.log(ev, step=self.update_steps)
             if self.save_log and step % self.save_interval == 0:
                 self.algo.save(os.path.join(self.model_dir), step)
                 self._save_state(step)
+                if self.pool is not None:
+                    self._save_scenes(step)
             keys = self.key.integers(1, 2 ** 62, size=self.n_env_train)        # the global batch, identical on every rank
             share = self.n_env_train // self.world
             lo, hi = self.rank * share, (self.rank + 1) * share
-            if self.scenes is None:
+            source = self.pool if self.pool is not None else self.scenes
+            if source is None:
                 rollouts = self.algo.collect(None, keys[lo:hi])
             else:
-                scene_of = mix_assignment(self.n_env_train, self.n_scene, self.scenes.S, step, lo, hi)
-                rollouts = self.algo.collect(None, keys[lo:hi], scenes=self.scenes, jitter=self.scene_jitter, scene_of=scene_of)
+                scene_of = mix_assignment(self.n_env_train, self.n_scene, source.S, step, lo, hi)
+                rollouts = self.algo.collect(None, keys[lo:hi], scenes=source, jitter=self.scene_jitter, scene_of=scene_of)
+            if self.pool is not None:      # the envs that started in scenes included: a jittered scene that still fails is a failure
+                self.pool.push_from(self.algo.rollout_record(rollouts), self.mine_back, 1e-6)
             update_info = self.algo.update(rollouts, step)                      # global values on every rank (Engine.info)
             if self.logger is not None:
                 self.logger.log(update_info, step=self.update_steps)

@@ -242,6 +242,46 @@ int32_t dgppo_env_scene_load(const dgppo_env_cfg* cfg, const float* agent_t, con
 int32_t dgppo_env_scene_mix(const dgppo_env_cfg* cfg, const float* agent_t, const float* goal_t, const float* obst_t,
                             int32_t S, const int32_t* scene_of, const uint64_t* seeds, float jitter, float* agent,
                             float* goal, float* obst, int32_t* flags, int32_t* n_fallback, int32_t B, void* stream);
+/* Failure scenes from a rollout record: for every env the first step at which its cost is unsafe, and the state `back` steps
+ * before it as the template rows dgppo_env_scene_load reads.  Not in the reference.
+ *   agent_tm [T+1, Bs, n, sd], cost_tm [T, Bs, n, n_cost]   the time-major record; Bs >= B is the number of envs per time
+ *                                   slot of the allocation, the first B of them are mined
+ *   goal [B, ng, sd], obst [B, n_obs, stride] (NULL iff n_obs == 0)   the per-env fields, dense
+ *   T >= 1, back >= 0, thresh finite
+ *   first [B]   the smallest t with any word of cost_tm[t, b] >= thresh (a NaN compares false), -1 if there is none
+ *   who   [B]   the lowest word index i * n_cost + c that is unsafe at step first[b], or -1
+ *   t0    [B]   max(first[b] - back, 0), or -1
+ *   agent_t [B, n, sd] = agent_tm[t0, b], goal_t [B, ng, sd] = goal[b], word for word; obst_t [B, n_obs, 5] = words 0..4 of
+ *               each rectangle record (LiDAR) or [B, n_obs, 2] = words 0, 1 of each obstacle row (MPE), NULL iff n_obs == 0
+ *   flags [B]   the DGPPO_SCENE_* bits of those rows, formed with the functions of dgppo_env_scene_mix (the rectangle record
+ *               rebuilt from the five words), so they are what dgppo_env_scene_load gives the mined row at jitter 0
+ * Where first[b] < 0: flags[b] = 0 and none of env b's rows is written.
+ * One wave64 per env; the cost scan runs in time order, several steps per pass where n * n_cost < 64, and stops at the first
+ * pass with an unsafe word, so a failing env reads only up to its failure.
+ * Refused on the host, before any launch, with an error that names dgppo_env_scene_mine: an invalid cfg, VMASReverseTransport,
+ * B < 0, Bs < B, T < 1, back < 0, a non-finite thresh, NULL operands (obst / obst_t NULL exactly when n_obs == 0),
+ * n_agents > 64, T * n * n_cost >= 2^31 - 1.  B == 0 returns 0.                                                          */
+int32_t dgppo_env_scene_mine(const dgppo_env_cfg* cfg, const float* agent_tm, const float* cost_tm, int32_t Bs,
+                             const float* goal, const float* obst, int32_t T, int32_t back, float thresh, int32_t* first,
+                             int32_t* who, int32_t* t0, int32_t* flags, float* agent_t, float* goal_t, float* obst_t, int32_t B,
+                             void* stream);
+/* The mined rows of the taken envs into a ring of pool slots: a deterministic stream compaction in one workgroup.
+ *   first, flags [B], agent_t, goal_t, obst_t [B, ...]   as dgppo_env_scene_mine wrote them
+ *   pool_agent, pool_goal, pool_obst [M, ...]            the pool rows in the template shapes (pool_obst NULL iff n_obs == 0)
+ *   M >= 1, 0 <= fixed < M     slots 0 .. fixed-1 are never written; the ring is the R = M - fixed slots after them
+ *   state [4] DEVICE int32     head, filled, pushed_total, taken_last; head in [0, R) is the caller's to keep
+ *   slot_of [B] out, or NULL   the slot env b went to, or -1
+ * Env b is taken iff first[b] >= 1 && flags[b] == 0 (a failure at step 0 is a bad start, not a mined scene).  The taken envs
+ * get ranks r = 0, 1, ... in ascending b; rank r < R is written to slot fixed + (head + r) % R word for word, later ranks are
+ * dropped.  Then, with count the number of taken envs and m = min(count, R): head = (head + m) % R, filled = min(R, filled +
+ * m), pushed_total += m, taken_last = count.  No atomic decides a slot: two runs give the same pool word for word.
+ * Refused on the host with an error that names dgppo_env_scene_pool_push: an invalid cfg, VMASReverseTransport, B < 0, M
+ * outside [1, 2^30], fixed outside [0, M), NULL operands (obst_t / pool_obst NULL exactly when n_obs == 0), n_agents > 64.
+ * B == 0 is a push of nothing: taken_last = 0.                                                                            */
+int32_t dgppo_env_scene_pool_push(const dgppo_env_cfg* cfg, const int32_t* first, const int32_t* flags, const float* agent_t,
+                                  const float* goal_t, const float* obst_t, float* pool_agent, float* pool_goal,
+                                  float* pool_obst, int32_t M, int32_t fixed, int32_t* state, int32_t* slot_of, int32_t B,
+                                  void* stream);
 
 /* ---- VMASReverseTransport (dgppo/env/vmas/vmas_reverse_transport.py) ------------------------------------------
  * n agents (discs of radius 0.03) push a hollow 0.6 x 0.6 box of mass 10 towards a goal past 3 disc obstacles.  The record

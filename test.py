@@ -50,7 +50,13 @@ rejects (conservative_frac); the animation shows the doomed set's boundary dashe
 (`Scenes.save`; S scenes of this env and team size), episode i runs scene (offset + i) % S and its line names the scene.
 `--scene-jitter J` (with `--scenes`, J > 0) moves every agent by up to J off its place in the scene, drawn from the episode's
 seed, so that several episodes of one scene differ.  Everything else — both shields, the rounds, every landscape, the video,
-`test_log.csv` — describes those episodes as it would the sampled ones."""
+`test_log.csv` — describes those episodes as it would the sampled ones.
+`--mine-scenes OUT.npz` turns the failures of the episodes into such a file (`algo.mine_scenes`, `Scenes.mine`): for every episode
+whose cost reaches 0 at some step >= 1 — the rule of the unsafe marks in the video — the state `--mine-back K` (default 8) steps
+earlier becomes the scene `epi{i}_t{t0}_a{agent}`, where it is a valid one; a line per mined episode names the first unsafe step,
+the start step, the agent and the cost component.  It works with every other flag (the shields, `--stochastic`, `--scenes`); with
+nothing mined a line says so and no file is written.  A mined state restarts with a zero actor carry and a fresh step counter:
+the situation is reproduced, not the rest of the episode."""
 import argparse
 import datetime
 import os
@@ -63,10 +69,35 @@ from dgppo.env import Scenes, make_env
 from dgppo_amd.trainer import evaluate as EV
 
 
+VMAS_MINE = "--mine-scenes: VMASReverseTransport has no scene entry point"
+
+
+def mine(args, algo, env, ro):
+    """--mine-scenes OUT.npz: the failures of the episodes as a scenes file, by this file's own unsafe rule (a cost >= 0, the rule
+    of the `unsafe` array the video marks): for every episode that becomes unsafe at some step >= 1 and whose state --mine-back
+    steps earlier is a valid scene, that state.  One line per mined episode, then the count; with nothing mined, no file"""
+    back = MINE_BACK_DEFAULT if args.mine_back is None else args.mine_back
+    n_cost = int(env.cfg.n_cost)
+    scenes = algo.mine_scenes(ro, back=back, thresh=0.0,
+                              names=lambda b, first, t0, who: f"epi{args.offset + b}_t{t0}_a{who // n_cost}")
+    if scenes is None:
+        print(f"mined scenes: none (no episode became unsafe after its first step from a valid state); {args.mine_scenes} not written")
+        return None
+    m = scenes.mined
+    for b, first, t0, who in zip(m["env"], m["first"], m["t0"], m["who"]):
+        print(f"epi: {b}, mined: first unsafe at step {first}, scene starts at step {t0}, agent {who // n_cost}, "
+              f"cost {env.cost_components[who % n_cost]}")
+    scenes.save(args.mine_scenes)
+    print(f"mined scenes: {scenes.S} of {ro.actions.shape[0]} episodes -> {args.mine_scenes}")
+    return scenes
+
+
 def test(args):
     print(f"> Running test.py {args}")
     np.random.seed(args.seed)
     config = EV.load_config(os.path.join(args.path, "config.yaml"))
+    if args.mine_scenes is not None and (config.env if args.env is None else args.env) == "VMASReverseTransport":
+        raise SystemExit(VMAS_MINE)
     num_agents = config.num_agents if args.num_agents is None else args.num_agents
     env = make_env(env_id=config.env if args.env is None else args.env, num_agents=num_agents,
                    num_obs=config.obs if args.obs is None else args.obs, max_step=args.max_step,
@@ -129,6 +160,8 @@ def test(args):
                   f"{joint['joint_verified_frac'][i] * 100:.3f}% of the steps (joint_verified_frac), not rolled in "
                   f"{joint['joint_unrolled_frac'][i] * 100:.3f}% (joint_unrolled_frac), {joint['mean_rounds'][i]:.3f} rounds per "
                   f"step (mean_rounds)")
+    if args.mine_scenes is not None:
+        mine(args, algo, env, ro)
     if args.log:
         with open(os.path.join(args.path, "test_log.csv"), "a") as f:
             f.write(EV.csv_line(env, args.epi, agg))
@@ -263,13 +296,17 @@ ROUNDS_FLAGS = [(("--shield-rounds",), "int", 1)]
 # start the episodes in the scenes of a dgppo.env.Scenes file instead of at the sampled reset (episode i: scene (offset + i) % S);
 # --scene-jitter J moves every agent by up to J off its place, drawn from the episode's seed
 SCENE_FLAGS = [(("--scenes",), "str", None), (("--scene-jitter",), "float", 0.0)]
+# write the failures of these episodes as a dgppo.env.Scenes file: for every episode that becomes unsafe at some step >= 1, the state
+# --mine-back steps earlier (Scenes.mine); every flag that takes --scenes then works on OUT.npz
+MINE_FLAGS = [(("--mine-scenes",), "str", None), (("--mine-back",), "int", None)]
+MINE_BACK_DEFAULT = 8
 
 
 def build_parser() -> argparse.ArgumentParser:
     types = {"int": int, "str": str, "float": float}
     ap = argparse.ArgumentParser(description=__doc__)
     for names, kind, default in (FLAGS + COST_FLAGS + ACTION_FLAGS + SHIELD_FLAGS + ROLLOUT_FLAGS + LOOKAHEAD_FLAGS
-                                 + ACTION_ROLLOUT_FLAGS + ROUNDS_FLAGS + SCENE_FLAGS):
+                                 + ACTION_ROLLOUT_FLAGS + ROUNDS_FLAGS + SCENE_FLAGS + MINE_FLAGS):
         if kind == "flag":
             ap.add_argument(*names, action="store_true", default=False)
         elif kind.startswith("req:"):
@@ -297,6 +334,12 @@ def main(argv=None):
         raise SystemExit(f"--scene-jitter must be >= 0 (got {args.scene_jitter})")
     if args.scene_jitter > 0.0 and args.scenes is None:
         raise SystemExit("--scene-jitter needs --scenes: it moves the agents off their places in the given scenes")
+    if args.mine_back is not None and args.mine_scenes is None:
+        raise SystemExit("--mine-back needs --mine-scenes: it says how many steps before a failure the mined scene starts")
+    if args.mine_back is not None and args.mine_back < 0:
+        raise SystemExit(f"--mine-back must be >= 0 (got {args.mine_back})")
+    if args.mine_scenes is not None and args.env == "VMASReverseTransport":
+        raise SystemExit(VMAS_MINE)
     return test(args)
 
 

@@ -30,6 +30,10 @@ FLAGS = [
     (("--rnn-step",), "int", 16), (("--n-env-train",), "int", 128), (("--batch-size",), "int", 16384),
     (("--n-env-test",), "int", 32), (("--log-dir",), "str", "./logs"), (("--eval-interval",), "int", 50),
     (("--eval-epi",), "int", 1), (("--save-interval",), "int", 50),
+    # not in the reference: a device-resident pool of M scenes mined from the policy's own recent failures (the state --mine-back
+    # steps before a rollout's first unsafe step); the share --scene-frac of every batch starts there, the scenes of --scenes FILE
+    # are pinned in its first slots (README "Mining failure scenes")
+    (("--mine-scenes",), "int", 0), (("--mine-back",), "int", 8),
     # not in the reference: a share P of every training batch starts in the designed scenes of FILE (env.Scenes.save), moved by
     # up to J, the rest at the sampled reset; every evaluation also rolls each scene once (README "Training on scenes")
     (("--scenes",), "str", None), (("--scene-frac",), "float", 0.0), (("--scene-jitter",), "float", 0.0),
@@ -41,7 +45,7 @@ FLAGS = [
 # flags a resumed run may give differently: where it logs and what it is called play no part in the computation
 _RESUME_FREE = ("resume", "log_dir", "name", "debug")
 # flags newer than full-state checkpoints: a stopped run that does not record them ran without them, at their defaults
-_RESUME_LATER = ("scenes", "scene_frac", "scene_jitter")
+_RESUME_LATER = ("scenes", "scene_frac", "scene_jitter", "mine_scenes", "mine_back")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -96,19 +100,49 @@ def check_resume(a) -> None:
         check_resume_flags(a, yaml.safe_load(f) or {})
 
 
+def check_mining(a) -> None:
+    """--mine-scenes / --mine-back; needs no GPU.  SystemExit naming the flag at fault"""
+    if a.mine_scenes == 0:
+        if a.mine_back != 8:
+            raise SystemExit("train.py: --mine-back needs --mine-scenes: it says how many steps before a failure the mined scene starts")
+        return
+    if a.mine_scenes < 1:
+        raise SystemExit(f"train.py: --mine-scenes must be >= 1, the capacity of the pool (got {a.mine_scenes})")
+    if a.mine_back < 0:
+        raise SystemExit(f"train.py: --mine-back must be >= 0 (got {a.mine_back})")
+    if a.scene_frac == 0.0:
+        raise SystemExit("train.py: --mine-scenes needs --scene-frac: the share of every batch that starts in the pool")
+    if a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("train.py: --mine-scenes runs on one rank (--gpus 1, no launcher): every rank would keep a pool of its own "
+                         "failures, and the ranks' windows together would no longer be what one device runs (DESIGN.md §9)")
+    if a.scenes is not None and os.path.isfile(a.scenes):
+        from dgppo_amd.env.scenes import check_pool, read_npz
+        try:
+            check_pool(a.mine_scenes, read_npz(a.scenes)["agent"].shape[0])
+        except ValueError as ex:
+            raise SystemExit(f"train.py: --mine-scenes: {ex}")
+
+
 def check_scenes(a) -> None:
     """needs no GPU: called before any rank is started.  SystemExit naming the flag at fault"""
-    if a.scenes is None:
+    check_mining(a)
+    if a.scenes is None and a.mine_scenes == 0:
         for flag, v in (("--scene-frac", a.scene_frac), ("--scene-jitter", a.scene_jitter)):
             if v != 0.0:
-                raise SystemExit(f"train.py: {flag} needs --scenes")
+                raise SystemExit(f"train.py: {flag} needs --scenes FILE, or --mine-scenes M for a pool of mined scenes")
         return
     if not 0.0 < a.scene_frac <= 1.0:
-        raise SystemExit(f"train.py: --scene-frac must be in (0, 1] with --scenes (got {a.scene_frac})")
+        raise SystemExit(f"train.py: --scene-frac must be in (0, 1] with --scenes / --mine-scenes (got {a.scene_frac})")
     if not a.scene_jitter >= 0.0:
         raise SystemExit(f"train.py: --scene-jitter must be >= 0 (got {a.scene_jitter})")
     if a.env == "VMASReverseTransport":
-        raise SystemExit("train.py: --scenes: VMASReverseTransport has no scene entry point")
+        raise SystemExit(f"train.py: {'--scenes' if a.scenes is not None else '--mine-scenes'}: VMASReverseTransport has no scene "
+                         f"entry point")
+    few = f"train.py: --scene-frac {a.scene_frac} of --n-env-train {a.n_env_train} is less than one environment"
+    if a.scenes is None:                             # a pool of mined scenes alone: no file to look at
+        if scene_count(a.scene_frac, a.n_env_train) < 1:
+            raise SystemExit(few)
+        return
     if not os.path.isfile(a.scenes):
         raise SystemExit(f"train.py: --scenes {a.scenes}: no such file")
     from dgppo_amd.env.scenes import check_file
@@ -117,7 +151,7 @@ def check_scenes(a) -> None:
     except ValueError as ex:
         raise SystemExit(f"train.py: --scenes: {ex}")
     if scene_count(a.scene_frac, a.n_env_train) < 1:
-        raise SystemExit(f"train.py: --scene-frac {a.scene_frac} of --n-env-train {a.n_env_train} is less than one environment")
+        raise SystemExit(few)
 
 
 def _unique_run_dir(root: str, seed: int):
@@ -209,7 +243,8 @@ def train(a):
                 "save_interval": a.save_interval}
     trainer = Trainer(env=env, env_test=env_test, algo=algo, gamma=0.99, log_dir=log_dir, n_env_train=a.n_env_train,
                       n_env_test=a.n_env_test, seed=a.seed, params=schedule, save_log=write, rank=rank, world=world,
-                      resume=a.resume is not None, scenes=scenes, scene_frac=a.scene_frac, scene_jitter=a.scene_jitter)
+                      resume=a.resume is not None, scenes=scenes, scene_frac=a.scene_frac, scene_jitter=a.scene_jitter,
+                      **({} if a.mine_scenes == 0 else {"mine_scenes": a.mine_scenes, "mine_back": a.mine_back}))
     if write and a.resume is None:   # plain mappings (the reference dumps the argparse.Namespace object itself; test.py reads both)
         with open(f"{log_dir}/config.yaml", "w") as f:
             yaml.safe_dump(_flags_to_store(a), f)
