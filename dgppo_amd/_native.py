@@ -211,6 +211,14 @@ def lib() -> C.CDLL:
     l.dgppo_env_scene_mine.argtypes = [C.POINTER(EnvCfg), p, p, i32, p, p, i32, i32, f32, p, p, p, p, p, p, p, i32, p]
     l.dgppo_env_scene_pool_push.restype = i32
     l.dgppo_env_scene_pool_push.argtypes = [C.POINTER(EnvCfg), p, p, p, p, p, p, p, p, i32, i32, p, p, i32, p]
+    # the pool by priority (csrc/env_scene_pool.hip): score the replays, draw the slots, push with eviction
+    l.dgppo_env_scene_pool_score.restype = i32
+    l.dgppo_env_scene_pool_score.argtypes = [C.POINTER(EnvCfg), p, p, p, p, p, p, p, i32, f32, i32, p, i32, p]
+    l.dgppo_env_scene_pool_draw.restype = i32
+    l.dgppo_env_scene_pool_draw.argtypes = [C.POINTER(EnvCfg), p, p, p, i32, i32, i32, i32, C.c_uint64, i64, i64, i64, p, p, i32, p]
+    l.dgppo_env_scene_pool_push_evict.restype = i32
+    l.dgppo_env_scene_pool_push_evict.argtypes = [C.POINTER(EnvCfg), p, p, p, p, p, p, p, p, p, p, p, p, i32, i32, i32, f32, i32, p, p,
+                                                  i32, p]
     _lib = l
     return l
 

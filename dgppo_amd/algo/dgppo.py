@@ -224,11 +224,22 @@ class DGPPO(Algorithm):
         starts in scene scene_ids[b]; without a list, in scene g % S of its GLOBAL env index g = rank * B_local + b, so that the
         union over the ranks is what one device would run for the global batch.  scene_of (one int per key, this rank's window
         of env.scenes.mix_assignment) asks for a mix instead: episode b starts at its sampled reset where scene_of[b] < 0 and in
-        scene scene_of[b] otherwise (env.scenes.SceneMix)."""
+        scene scene_of[b] otherwise (env.scenes.SceneMix).  scene_of = an env.scenes.SceneDraw (ScenePool.drawn of the device
+        tensor ScenePool.draw returned for this rank's window, `scenes` being that priority pool) asks for the same mix without a
+        host copy (env.scenes.SceneMixDrawn); the validity bits of the scored rollout go to its flags."""
+        from ..env.scenes import SceneDraw
         if scenes is None:
             if scene_ids is not None or scene_of is not None or float(jitter) != 0.0:
                 raise ValueError("scene_ids / scene_of / jitter need scenes: without them the episodes start at the sampled reset")
             return None
+        drawn, scene_of = (scene_of, None) if isinstance(scene_of, SceneDraw) else (None, scene_of)
+        if drawn is not None:
+            if scene_ids is not None:
+                raise ValueError("scene_of and scene_ids exclude each other: a mix names every env's scene itself")
+            if not getattr(scenes, "priority", False):
+                raise ValueError("a drawn scene_of needs scenes=ScenePool(..., priority=True), the pool whose draw() it is")
+            if tuple(drawn.scene_of.shape) != (B_local,):
+                raise ValueError(f"scene_of must have one entry per key ({B_local}), got shape {tuple(drawn.scene_of.shape)}")
         if scene_of is not None:
             if scene_ids is not None:
                 raise ValueError("scene_of and scene_ids exclude each other: a mix names every env's scene itself")
@@ -238,6 +249,8 @@ class DGPPO(Algorithm):
         if (cfg.kind, cfg.n_agents, cfg.n_obs) != (mine.kind, mine.n_agents, mine.n_obs):
             raise ValueError(f"scenes of env kind {cfg.kind} with {cfg.n_agents} agents and {cfg.n_obs} obstacles do not fit this "
                              f"algo's env (kind {mine.kind}, {mine.n_agents} agents, {mine.n_obs} obstacles)")
+        if drawn is not None:
+            return scenes.mix_drawn(drawn.scene_of, drawn.flags, jitter)
         if scene_of is not None:
             return scenes.mix(scene_of, jitter)
         if scene_ids is None and self.world > 1:
@@ -257,7 +270,7 @@ class DGPPO(Algorithm):
         """algo.collect(params, keys): one stochastic rollout per key (informarl.py:254-256).  scenes (env.Scenes): the
         episodes — and those of the deterministic companion rollout — start in the given scenes instead of at the sampled
         reset (_scene_start); with scene_of only the envs it names do, and the companion rollout gets the same mix with its own
-        seeds.  Not in the reference."""
+        seeds; scene_of may be what a priority pool drew, on the device (ScenePool.drawn).  Not in the reference."""
         self._maybe_load(params)
         seeds = self._seeds(keys)
         start = self._scene_start(scenes, scene_ids, jitter, int(seeds.shape[0]), scene_of)

@@ -376,10 +376,16 @@ class Engine:
         env.scenes.SceneStart — the user-given scenes (ops_env.scene_start: env b in scene scene_ids[b], or b % S; agents moved by
         up to `jitter`, drawn from seeds).  Either way sensed, and envs without a valid scene counted in reset_failed.
         start = an env.scenes.SceneMix: the reset of every env, then the scenes of those scene_of names (ops_env.mixed_start);
-        an env whose scene stays invalid keeps its reset and is counted in scene_fallback, not in reset_failed."""
+        an env whose scene stays invalid keeps its reset and is counted in scene_fallback, not in reset_failed.
+        start = an env.scenes.SceneMixDrawn: the same mix with the device scene_of a priority pool drew; the bits of the envs it
+        names go to start.flags where that is given."""
         if start is None:
             return OE.reset(self.cfg, seeds, st, self.reset_failed)
-        from .env.scenes import SceneMix
+        from .env.scenes import SceneMix, SceneMixDrawn
+        if isinstance(start, SceneMixDrawn):                   # scene_of stays on the device: no copy, no sync
+            self._mix_used, self._mix_pool = True, start.scenes
+            return OE.mixed_start_drawn(self.cfg, seeds, st, start.scenes.dev, start.scene_of, float(start.jitter), start.flags,
+                                        self.reset_failed, self.scene_fallback)
         if isinstance(start, SceneMix):
             self._mix_used = True
             # a pool of mined scenes (env.scenes.ScenePool): info() reports its fill next to scene_fallback
@@ -458,16 +464,19 @@ class Engine:
 
     def rollout_pair(self, seeds: torch.Tensor, det_seeds: torch.Tensor, noise_seed: int = 0, start=None):
         """the stochastic training rollout and the deterministic rollout of the same parameters (informarl.py:254-256 and
-        dgppo.py:139-141).  They are independent, so with multi_stream they run on two HIP streams side by side."""
+        dgppo.py:139-141).  They are independent, so with multi_stream they run on two HIP streams side by side.  Under a drawn mix
+        (env.scenes.SceneMixDrawn) both read the same scene_of; only the stochastic one, whose record is scored, writes flags."""
+        from .env.scenes import SceneMixDrawn
+        det_start = start._replace(flags=None) if isinstance(start, SceneMixDrawn) else start
         if not (self.multi_stream and self.device.type == "cuda"):
-            return self.rollout(seeds, True, noise_seed, start), self.rollout(det_seeds, False, start=start)
+            return self.rollout(seeds, True, noise_seed, start), self.rollout(det_seeds, False, start=det_start)
         main = torch.cuda.current_stream(self.device)
         s0, s1 = self._net_streams()[:2]
         out = [None, None]
         for k, (st, sd, stoch) in enumerate(((s0, seeds, True), (s1, det_seeds, False))):
             st.wait_stream(main)
             with torch.cuda.stream(st):
-                out[k] = self.rollout(sd, stoch, noise_seed if stoch else 0, start)
+                out[k] = self.rollout(sd, stoch, noise_seed if stoch else 0, start if stoch else det_start)
         main.wait_stream(s0)
         main.wait_stream(s1)
         return out[0], out[1]
@@ -1646,7 +1655,14 @@ class Engine:
             out["rollout/scene_fallback"] = float(sums[1])   # of mined scenes also those that drew a slot still empty
             pool, self._mix_pool = self._mix_pool, None
             if pool is not None:       # one rank only (train.py refuses more): the ring after this iteration's push
-                filled, pushed, taken = pool.fill()
+                st = pool.stats() if getattr(pool, "priority", False) else None      # one copy carries the fill too
+                filled, pushed, taken = pool.fill() if st is None else (int(v) for v in st["state"][1:4])
                 out.update({"rollout/scene_pool_fill": float(filled), "rollout/scene_pool_pushed": float(pushed),
                             "rollout/scene_pool_taken": float(taken)})
+                if st is not None:             # what the iteration's score call and evicting push counted
+                    live = pool.P + int(st["state"][1])
+                    out.update({"rollout/scene_replay_fail_frac": float(st["state"][7]) / max(float(st["state"][6]), 1.0),
+                                "rollout/scene_pool_evicted": float(st["state"][4]),
+                                "rollout/scene_pool_dropped": float(st["state"][5]),
+                                "rollout/scene_pool_score_mean": float(st["score"][:live].mean()) if live else 0.0})
         return out

@@ -4,7 +4,7 @@ from typing import Optional
 from . import envs as _envs
 from .base import MultiAgentEnv
 from .envs import LidarEnvState, MPEEnvState, Rectangle          # re-exported: users import them from dgppo.env
-from .scenes import ScenePool, Scenes, SceneMix, SceneStart                # user-given start scenes (not in the reference)
+from .scenes import ScenePool, Scenes, SceneDraw, SceneMix, SceneMixDrawn, SceneStart               # user-given start scenes (not in the reference)
 from .vmas import VMASReverseTransport, VMASReverseTransportState
 
 DEFAULT_MAX_STEP = 128

@@ -41,6 +41,23 @@ class SceneMix(NamedTuple):
     jitter: float = 0.0
 
 
+class SceneMixDrawn(NamedTuple):
+    """SceneMix whose scene_of is the device int32 [B] tensor that ScenePool.draw wrote (dgppo_env_scene_pool_draw): trusted to be
+    in range, so the start copies nothing to the host and waits for nothing.  flags (device int32 [B], or None) receives the
+    validity bits of the envs scene_of names; the rollout whose record is scored passes it, its deterministic twin passes None"""
+    scenes: "ScenePool"
+    scene_of: torch.Tensor
+    flags: Optional[torch.Tensor] = None
+    jitter: float = 0.0
+
+
+class SceneDraw(NamedTuple):
+    """what collect(..., scene_of=) takes in place of host ints under a priority pool (ScenePool.drawn): the device int32 [B] tensor
+    the pool drew, and the device int32 [B] buffer the scored rollout's validity bits go to"""
+    scene_of: torch.Tensor
+    flags: Optional[torch.Tensor] = None
+
+
 def mix_assignment(n_total: int, n_scene: int, S: int, step: int, lo: int, hi: int) -> np.ndarray:
     """int32 [hi - lo]: the scene_of window of the global envs lo .. hi - 1 of a batch of n_total envs of which n_scene start in
     one of S scenes.  Global env g is a scene env iff (g + 1) n_scene // n_total > g n_scene // n_total, which spreads them
@@ -95,10 +112,13 @@ def check_templates(cfg: N.EnvCfg, agent, goal, rect=None, disc=None, names=None
     return given
 
 
-def write_npz(path, env_id: str, num_agents: int, agent, goal, obst, obst_key: Optional[str], names: Sequence[str]) -> None:
-    """the file format of Scenes.save: env_id, num_agents, agent, goal, rect or disc (absent without obstacles), names"""
+def write_npz(path, env_id: str, num_agents: int, agent, goal, obst, obst_key: Optional[str], names: Sequence[str],
+              extra: Optional[Dict[str, np.ndarray]] = None) -> None:
+    """the file format of Scenes.save: env_id, num_agents, agent, goal, rect or disc (absent without obstacles), names; extra:
+    further arrays under their own names (a priority pool's statistics), which read_npz does not look at"""
     out = dict(env_id=np.array(env_id), num_agents=np.array(int(num_agents), np.int64), agent=np.asarray(agent, f32),
                goal=np.asarray(goal, f32), names=np.array(list(names), dtype=np.str_))
+    out.update(extra or {})
     if obst is not None:
         out[obst_key] = np.asarray(obst, f32)
     with open(path, "wb") as f:          # a file object: numpy appends no suffix
@@ -221,6 +241,22 @@ def check_pool(capacity: int, n_pinned: int) -> None:
                          f"scenes has a slot (got capacity {capacity}, {n_pinned} pinned)")
 
 
+def check_pool_priority(capacity: int, beta: float, age_cap: int, min_visits: int, evict_w: float, draw_seed: int) -> None:
+    """the host half of ScenePool(priority=True): ValueError; touches no device"""
+    if int(capacity) > OE.POOL_MAX_M:
+        raise ValueError(f"ScenePool: with priority, capacity must be <= {OE.POOL_MAX_M} (got {capacity})")
+    if not 0.0 < float(beta) <= 1.0:
+        raise ValueError(f"ScenePool: beta must be in (0, 1] (got {beta})")
+    if int(age_cap) != age_cap or not 1 <= int(age_cap) <= OE.POOL_MAX_AGE:
+        raise ValueError(f"ScenePool: age_cap must be an int in [1, {OE.POOL_MAX_AGE}] (got {age_cap})")
+    if int(min_visits) != min_visits or int(min_visits) < 0:
+        raise ValueError(f"ScenePool: min_visits must be an int >= 0 (got {min_visits})")
+    if not 0.0 <= float(evict_w) <= 1.0:
+        raise ValueError(f"ScenePool: evict_w must be in [0, 1] (got {evict_w})")
+    if int(draw_seed) != draw_seed or not 0 <= int(draw_seed) < 2 ** 64:
+        raise ValueError(f"ScenePool: draw_seed must be an int in [0, 2^64) (got {draw_seed})")
+
+
 class ScenePool:
     """A device-resident pool of M = capacity scenes for a training run that mines its own failures: the scenes of `pinned` in
     slots 0 .. P-1, never overwritten, and behind them a ring of R = M - P slots that push_from() fills with the failure scenes of
@@ -229,14 +265,26 @@ class ScenePool:
     An empty ring slot holds NaN words: dgppo_env_scene_mix gives an env that draws it the NONFINITE bit and leaves its sampled
     reset standing, so an empty slot means "sampled reset" (counted in rollout/scene_fallback), mix_assignment keeps S = M from
     the first iteration, and no count has to come back to the host before a rollout.
-      state (device int32 [4])   head, filled, pushed_total, taken_last (dgppo_env_scene_pool_push)"""
+      state (device int32 [4])   head, filled, pushed_total, taken_last (dgppo_env_scene_pool_push)
+    priority=True (csrc/env_scene_pool.hip) keeps, per slot, score (the EMA, with weight beta, of the failed fraction of the slot's
+    replays), visits and last (the step of its last replay or write), and an int32 [8] state (the four words above, evicted_last,
+    dropped_last, replays_last, replay_fails_last).  draw() gives every scene env a live slot in proportion to q(score) *
+    min(1 + step - last, age_cap) with q = 4 s (1 - s) in integers (Philox keyed by draw_seed), so an empty slot is never drawn;
+    score_from() folds what the replays of a rollout did into the statistics; push_from() writes empty slots first and then
+    evicts the filled ones with visits >= min_visits and 4 s (1 - s) <= evict_w — solved and hopeless ones — instead of the oldest."""
 
-    def __init__(self, env, capacity: int, pinned: Optional[Scenes] = None):
+    def __init__(self, env, capacity: int, pinned: Optional[Scenes] = None, priority: bool = False, beta: float = 0.3,
+                 age_cap: int = 16, min_visits: int = 2, evict_w: float = 0.36, draw_seed: int = 0):
         cfg = env.cfg
         if cfg.is_vmas:
             raise ValueError("ScenePool: VMASReverseTransport has no scene entry point")
         self.P = 0 if pinned is None else int(pinned.S)
         check_pool(capacity, self.P)
+        self.priority = bool(priority)
+        if self.priority:
+            check_pool_priority(capacity, beta, age_cap, min_visits, evict_w, draw_seed)
+        self.beta, self.age_cap, self.min_visits = float(beta), int(age_cap), int(min_visits)
+        self.evict_w, self.draw_seed = float(evict_w), int(draw_seed)
         if pinned is not None and (pinned.cfg.kind, pinned.cfg.n_agents, pinned.cfg.n_obs) != (cfg.kind, cfg.n_agents, cfg.n_obs):
             raise ValueError("ScenePool: the pinned scenes are of another env")
         self.env, self.cfg, self.S = env, cfg, int(capacity)
@@ -248,8 +296,11 @@ class ScenePool:
             for k, v in self.dev.items():
                 v[:self.P].copy_(pinned.dev[k])
         self.pinned_names = [] if pinned is None else list(pinned.names)
-        self.state = torch.zeros(4, dtype=torch.int32, device=dev)
+        self._stats: Optional[Dict[str, torch.Tensor]] = OE.alloc_pool_stats(self.S, dev) if self.priority else None
+        self.state = self._stats["state"] if self.priority else torch.zeros(4, dtype=torch.int32, device=dev)
         self._mined: Dict[int, Dict[str, torch.Tensor]] = {}      # scene_mine's outputs per batch size, allocated once
+        self._drawn: Dict[int, torch.Tensor] = {}                 # draw's scene_of per batch size, allocated once
+        self._flags: Dict[int, torch.Tensor] = {}                 # the mix flags of a drawn start per batch size
 
     @property
     def names(self):
@@ -258,19 +309,79 @@ class ScenePool:
     def mix(self, scene_of, jitter: float = 0.0) -> SceneMix:
         return SceneMix(self, np.asarray(scene_of), float(jitter))
 
-    def push_from(self, record, back: int = 8, thresh: float = 1e-6) -> None:
-        """mine the record (engine.RolloutData) and push its taken envs into the ring: two launches, no sync"""
+    def _need_priority(self, what: str):
+        if not self.priority:
+            raise ValueError(f"ScenePool.{what} needs ScenePool(..., priority=True)")
+
+    def _mine(self, record, back: int, thresh: float) -> Dict[str, torch.Tensor]:
         B = int(record.agent_tm.shape[1])
         if B not in self._mined:
             self._mined[B] = OE.alloc_mined(self.cfg, B, self.state.device)
         out = self._mined[B]
         OE.scene_mine(self.cfg, record.agent_tm, record.cost_tm, record.goal, record.obst, back, thresh, out)
-        OE.scene_pool_push(self.cfg, out, self.dev, self.P, self.state)
+        return out
+
+    def draw(self, n_total: int, n_scene: int, step: int, lo: int, hi: int) -> torch.Tensor:
+        """priority mode: the device int32 scene_of of the global envs lo .. hi - 1 of a batch of n_total envs of which n_scene are
+        scene envs (those of mix_assignment), every one with a live slot drawn by priority, or -1 while none is live; one launch,
+        no sync.  The tensor is the pool's own, one per window size: the next draw of that size overwrites it"""
+        self._need_priority("draw")
+        B = int(hi) - int(lo)
+        if B < 0:
+            raise ValueError(f"ScenePool.draw: need lo <= hi (got [{lo}, {hi}))")
+        if B not in self._drawn:
+            self._drawn[B] = torch.empty(B, dtype=torch.int32, device=self.state.device)
+        OE.scene_pool_draw(self.cfg, self._stats, self.P, self.age_cap, step, self.draw_seed, n_total, n_scene, lo, self._drawn[B])
+        return self._drawn[B]
+
+    def mix_flags(self, B: int) -> torch.Tensor:
+        """priority mode: the pool's device int32 [B] buffer for the validity bits of a drawn mix of B envs (score_from reads it)"""
+        self._need_priority("mix_flags")
+        if B not in self._flags:
+            self._flags[B] = torch.zeros(int(B), dtype=torch.int32, device=self.state.device)
+        return self._flags[B]
+
+    def drawn(self, scene_of: torch.Tensor) -> SceneDraw:
+        """what draw() returned, as collect(..., scenes=pool, scene_of=) takes it, with mix_flags of its size for the bits"""
+        return SceneDraw(scene_of, self.mix_flags(int(scene_of.shape[0])))
+
+    def mix_drawn(self, scene_of: torch.Tensor, flags: Optional[torch.Tensor] = None, jitter: float = 0.0) -> SceneMixDrawn:
+        """the `start` argument of a rollout that starts the envs draw() named in their slots"""
+        self._need_priority("mix_drawn")
+        return SceneMixDrawn(self, scene_of, flags, float(jitter))
+
+    def score_from(self, record, scene_of: torch.Tensor, mix_flags: torch.Tensor, step: int, back: int = 8,
+                   thresh: float = 1e-6) -> Dict[str, torch.Tensor]:
+        """priority mode: mine the record (engine.RolloutData) of the rollout that draw()'s scene_of started and whose scene mix
+        wrote mix_flags, and fold what its replays did into score, visits and last.  -> what was mined, which a push_from of the
+        same record, back and thresh takes as `mined` so as not to mine again.  No sync"""
+        self._need_priority("score_from")
+        out = self._mine(record, back, thresh)
+        OE.scene_pool_score(self.cfg, scene_of, mix_flags, out["first"], self._stats, self.beta, step)
+        return out
+
+    def push_from(self, record, back: int = 8, thresh: float = 1e-6, step: int = 0, mined=None) -> None:
+        """mine the record (engine.RolloutData), unless score_from's `mined` of it is given, and push its taken envs into the ring:
+        two launches, no sync.  Priority mode: the evicting push (dgppo_env_scene_pool_push_evict), the written slots' `last` set
+        to `step`"""
+        out = self._mine(record, back, thresh) if mined is None else mined
+        if self.priority:
+            OE.scene_pool_push_evict(self.cfg, out, self.dev, self.P, self._stats, self.min_visits, self.evict_w, step)
+        else:
+            OE.scene_pool_push(self.cfg, out, self.dev, self.P, self.state)
 
     def fill(self):
         """-> (filled, pushed_total, taken_last); one host sync"""
-        _, filled, pushed, taken = self.state.cpu().tolist()
+        _, filled, pushed, taken = self.state.cpu().tolist()[:4]
         return int(filled), int(pushed), int(taken)
+
+    def stats(self) -> Dict[str, np.ndarray]:
+        """priority mode: score, visits, last ([M]) and state ([8]) on the host; one sync"""
+        self._need_priority("stats")
+        packed = torch.cat([self._stats[k].view(torch.int32) for k in OE.POOL_STATS + ("state",)]).cpu().numpy()
+        M = self.S
+        return {"score": packed[:M].view(f32).copy(), "visits": packed[M:2 * M].copy(), "last": packed[2 * M:3 * M].copy(),
+                "state": packed[3 * M:].copy()}
 
     def to_scenes(self) -> Optional[Scenes]:
         """the pinned and the filled slots as a host Scenes (the ring fills from its first slot on); None while there is none"""
@@ -286,11 +397,19 @@ class ScenePool:
         d = {k: v.cpu().numpy() for k, v in self.dev.items()}
         d["state"] = self.state.cpu().numpy()
         d["pinned"] = int(self.P)
+        if self.priority:
+            d["stats"] = {k: self._stats[k].cpu().numpy() for k in OE.POOL_STATS}
         return d
 
     def load_state_dict(self, d: dict) -> None:
         if int(d.get("pinned", -1)) != self.P or any(k not in d or tuple(d[k].shape) != tuple(v.shape) for k, v in self.dev.items()):
             raise ValueError("ScenePool: the stored pool does not fit this one (capacity, pinned scenes or env differ)")
+        if ("stats" in d) != self.priority:
+            raise ValueError(f"ScenePool: the stored pool is {'a priority pool' if 'stats' in d else 'a plain ring'}, this one is "
+                             f"{'a priority pool' if self.priority else 'a plain ring'}: the two modes do not load each other")
         for k, v in self.dev.items():
             v.copy_(torch.from_numpy(np.ascontiguousarray(d[k], f32)))
         self.state.copy_(torch.from_numpy(np.ascontiguousarray(d["state"], np.int32)))
+        if self.priority:
+            for k in OE.POOL_STATS:
+                self._stats[k].copy_(torch.from_numpy(np.ascontiguousarray(d["stats"][k], f32 if k == "score" else np.int32)))

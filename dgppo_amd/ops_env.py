@@ -342,9 +342,8 @@ def scene_start(cfg: N.EnvCfg, scenes_dev: Dict[str, torch.Tensor], scene_ids, s
         materialize(cfg, st, graph)
 
 
-def _scene_mix_checked(cfg: N.EnvCfg, scenes_dev, scene_of, seeds, jitter, st: State, flags, n_fallback):
-    """every refusal of scene_mix -> (S, jitter, scene_of as int32 on the host); launches nothing"""
-    fn = "scene_mix"
+def _scene_mix_operands(cfg: N.EnvCfg, scenes_dev, seeds, jitter, st: State, flags, n_fallback, fn: str = "scene_mix"):
+    """every refusal of scene_mix but those of scene_of -> (S, jitter); launches nothing"""
     if cfg.is_vmas:
         raise ValueError(f"{fn}: VMASReverseTransport has no scene entry point")
     B = int(st.agent.shape[0])
@@ -364,6 +363,18 @@ def _scene_mix_checked(cfg: N.EnvCfg, scenes_dev, scene_of, seeds, jitter, st: S
     if seeds is None:
         raise ValueError(f"{fn}: seeds are required")
     N.expect_shape(seeds, (B,), "seeds")
+    if flags is not None:
+        N.expect_shape(flags, (B,), "flags")
+    if n_fallback is not None:
+        N.expect_shape(n_fallback, (1,), "n_fallback")
+    return S, jitter
+
+
+def _scene_mix_checked(cfg: N.EnvCfg, scenes_dev, scene_of, seeds, jitter, st: State, flags, n_fallback):
+    """every refusal of scene_mix -> (S, jitter, scene_of as int32 on the host); launches nothing"""
+    fn = "scene_mix"
+    S, jitter = _scene_mix_operands(cfg, scenes_dev, seeds, jitter, st, flags, n_fallback)
+    B = int(st.agent.shape[0])
     if scene_of is None:
         raise ValueError(f"{fn}: scene_of is required")
     of = np.asarray(scene_of.cpu() if torch.is_tensor(scene_of) else scene_of)
@@ -371,15 +382,12 @@ def _scene_mix_checked(cfg: N.EnvCfg, scenes_dev, scene_of, seeds, jitter, st: S
         raise ValueError(f"{fn}: scene_of must be {B} ints (got shape {of.shape}, dtype {of.dtype})")
     if B and int(of.max()) >= S:
         raise ValueError(f"{fn}: scene_of outside [-inf, {S})")
-    if flags is not None:
-        N.expect_shape(flags, (B,), "flags")
-    if n_fallback is not None:
-        N.expect_shape(n_fallback, (1,), "n_fallback")
     return S, jitter, np.ascontiguousarray(np.maximum(of.astype(np.int64), -1), np.int32)
 
 
-def _scene_mix_launch(cfg: N.EnvCfg, scenes_dev, S: int, of: np.ndarray, seeds, jitter: float, st: State, flags, n_fallback):
-    of_dev = torch.from_numpy(of).to(st.agent.device)
+def _scene_mix_launch(cfg: N.EnvCfg, scenes_dev, S: int, of, seeds, jitter: float, st: State, flags, n_fallback):
+    """of: the checked host array, or a device int32 tensor that is trusted to be in range (scene_pool_draw wrote it)"""
+    of_dev = of if torch.is_tensor(of) else torch.from_numpy(of).to(st.agent.device)
     rc = N.lib().dgppo_env_scene_mix(
         C.byref(cfg), N.ptr(scenes_dev["agent"], name="scenes_dev.agent"), N.ptr(scenes_dev["goal"], name="scenes_dev.goal"),
         N.ptr(scenes_dev.get("obst") if cfg.n_obs > 0 else None, name="scenes_dev.obst"), S, N.ptr(of_dev, torch.int32, "scene_of"),
@@ -409,6 +417,24 @@ def mixed_start(cfg: N.EnvCfg, seeds: torch.Tensor, st: State, scenes_dev: Dict[
     S, jitter, of = _scene_mix_checked(cfg, scenes_dev, scene_of, seeds, jitter, st, None, n_fallback)
     env_reset(cfg, seeds, st.agent, st.goal, st.obst, n_failed)
     _scene_mix_launch(cfg, scenes_dev, S, of, seeds, jitter, st, None, n_fallback)
+    if "hits" in st.step:
+        sense(cfg, st, graph)
+    elif graph is not None:
+        materialize(cfg, st, graph)
+
+
+def mixed_start_drawn(cfg: N.EnvCfg, seeds: torch.Tensor, st: State, scenes_dev: Dict[str, torch.Tensor], scene_of: torch.Tensor,
+                      jitter: float, flags=None, n_failed=None, n_fallback=None, graph: Optional[Dict[str, torch.Tensor]] = None):
+    """mixed_start with the scene_of that scene_pool_draw wrote: a device int32 [B] tensor, trusted to be in range, so nothing is
+    copied to the host and nothing waits for the device.  flags [B] int32 (optional) receives the bits of the envs scene_of names
+    (scene_pool_score reads them)."""
+    fn = "mixed_start_drawn"
+    S, jitter = _scene_mix_operands(cfg, scenes_dev, seeds, jitter, st, flags, n_fallback, fn)
+    if not (torch.is_tensor(scene_of) and scene_of.is_cuda and scene_of.dtype == torch.int32):
+        raise ValueError(f"{fn}: scene_of must be the device int32 tensor of scene_pool_draw (scene_mix takes host lists)")
+    N.expect_shape(scene_of, (int(st.agent.shape[0]),), "scene_of")
+    env_reset(cfg, seeds, st.agent, st.goal, st.obst, n_failed)
+    _scene_mix_launch(cfg, scenes_dev, S, scene_of, seeds, jitter, st, flags, n_fallback)
     if "hits" in st.step:
         sense(cfg, st, graph)
     elif graph is not None:
@@ -506,6 +532,117 @@ def scene_pool_push(cfg: N.EnvCfg, mined: Dict[str, torch.Tensor], pool: Dict[st
         N.ptr(pool["goal"], name="pool.goal"), N.ptr(pool["obst"] if obst else None, name="pool.obst"), M, fixed,
         N.ptr(state, i32, "state"), N.ptr(slot_of, i32, "slot_of"), B, N.stream_ptr())
     N.check(rc, "dgppo_env_scene_pool_push")
+
+
+# ---- the pool by priority (csrc/env_scene_pool.hip) ---------------------------------------------------------------------------
+POOL_MAX_M, POOL_MAX_AGE = 65536, 1024
+POOL_STATS = ("score", "visits", "last")
+
+
+def alloc_pool_stats(M: int, device) -> Dict[str, torch.Tensor]:
+    """the per-slot statistics of a pool of M slots, as a new pool has them (every score 0.5, no visit, last step 0), the int32 [8]
+    state, and the scratch of the three entry points: tally int32 [2 M] (zero between calls), cum int64 [M], order int32 [M]"""
+    i32 = torch.int32
+    return {"score": torch.full((M,), 0.5, device=device), "visits": torch.zeros(M, dtype=i32, device=device),
+            "last": torch.zeros(M, dtype=i32, device=device), "state": torch.zeros(8, dtype=i32, device=device),
+            "tally": torch.zeros(2 * M, dtype=i32, device=device), "cum": torch.empty(M, dtype=torch.int64, device=device),
+            "order": torch.empty(M, dtype=i32, device=device)}
+
+
+def _check_pool_stats(fn: str, stats: Dict[str, torch.Tensor], M: int):
+    if not 1 <= M <= POOL_MAX_M:
+        raise ValueError(f"{fn}: M must be in [1, {POOL_MAX_M}] (got {M})")
+    for k in POOL_STATS + ("cum", "order"):
+        N.expect_shape(stats[k], (M,), f"stats.{k}")
+    N.expect_shape(stats["tally"], (2 * M,), "stats.tally")
+    N.expect_shape(stats["state"], (8,), "stats.state")
+
+
+def scene_pool_score(cfg: N.EnvCfg, scene_of, mix_flags, first, stats: Dict[str, torch.Tensor], beta: float, step: int):
+    """dgppo_env_scene_pool_score: what the replays of a rollout did — scene_of [B] from scene_pool_draw, mix_flags [B] from the
+    rollout's scene mix, first [B] from scene_mine of its record, all device int32 — folded into stats (alloc_pool_stats):
+    score, visits, last of every replayed slot, state[6] = replays, state[7] = failed replays.  Two launches, no sync."""
+    fn = "scene_pool_score"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no scene entry point")
+    M, B = int(stats["score"].shape[0]), int(scene_of.shape[0])
+    _check_pool_stats(fn, stats, M)
+    beta = float(beta)
+    if not 0.0 < beta <= 1.0:
+        raise ValueError(f"{fn}: beta must be in (0, 1] (got {beta})")
+    N.expect_shape(mix_flags, (B,), "mix_flags")
+    N.expect_shape(first, (B,), "first")
+    i32 = torch.int32
+    rc = N.lib().dgppo_env_scene_pool_score(
+        C.byref(cfg), N.ptr(scene_of, i32, "scene_of"), N.ptr(mix_flags, i32, "mix_flags"), N.ptr(first, i32, "first"),
+        N.ptr(stats["score"], name="stats.score"), N.ptr(stats["visits"], i32, "stats.visits"), N.ptr(stats["last"], i32, "stats.last"),
+        N.ptr(stats["tally"], i32, "stats.tally"), M, beta, int(step), N.ptr(stats["state"], i32, "stats.state"), B, N.stream_ptr())
+    N.check(rc, "dgppo_env_scene_pool_score")
+
+
+def scene_pool_draw(cfg: N.EnvCfg, stats: Dict[str, torch.Tensor], fixed: int, age_cap: int, step: int, draw_seed: int, n_total: int,
+                    n_scene: int, lo: int, scene_of: torch.Tensor):
+    """dgppo_env_scene_pool_draw: scene_of (device int32 [B]) of the global envs lo .. lo + B - 1 of a batch of n_total envs of
+    which n_scene start in a slot: the scene envs are those of env.scenes.mix_assignment, each draws a live slot in proportion
+    to q(score) * min(1 + max(step - last, 0), age_cap); every other env, and every env while no slot is live, gets -1.  One
+    launch, no sync.  Every refusal is raised before anything is launched."""
+    fn = "scene_pool_draw"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no scene entry point")
+    M, B = int(stats["score"].shape[0]), int(scene_of.shape[0])
+    _check_pool_stats(fn, stats, M)
+    fixed, age_cap, step, n_total, n_scene, lo = (int(v) for v in (fixed, age_cap, step, n_total, n_scene, lo))
+    if not 0 <= fixed < M:
+        raise ValueError(f"{fn}: fixed must be in [0, M) (got {fixed}, M {M})")
+    if not 1 <= age_cap <= POOL_MAX_AGE:
+        raise ValueError(f"{fn}: age_cap must be in [1, {POOL_MAX_AGE}] (got {age_cap})")
+    if not (1 <= n_total < 2 ** 31 and 0 <= n_scene <= n_total):
+        raise ValueError(f"{fn}: need 1 <= n_total < 2^31 and 0 <= n_scene <= n_total (got n_total {n_total}, n_scene {n_scene})")
+    if not (0 <= lo and lo + B <= n_total):
+        raise ValueError(f"{fn}: the window [{lo}, {lo + B}) lies outside the batch of {n_total}")
+    i32 = torch.int32
+    rc = N.lib().dgppo_env_scene_pool_draw(
+        C.byref(cfg), N.ptr(stats["score"], name="stats.score"), N.ptr(stats["last"], i32, "stats.last"),
+        N.ptr(stats["state"], i32, "stats.state"), M, fixed, age_cap, step, int(draw_seed) & (2 ** 64 - 1), n_total, n_scene, lo,
+        N.ptr(stats["cum"], torch.int64, "stats.cum"), N.ptr(scene_of, i32, "scene_of"), B, N.stream_ptr())
+    N.check(rc, "dgppo_env_scene_pool_draw")
+
+
+def scene_pool_push_evict(cfg: N.EnvCfg, mined: Dict[str, torch.Tensor], pool: Dict[str, torch.Tensor], fixed: int,
+                          stats: Dict[str, torch.Tensor], min_visits: int, evict_w: float, step: int, slot_of=None):
+    """dgppo_env_scene_pool_push_evict: scene_pool_push with eviction by priority: the taken envs of `mined` go to the empty ring
+    slots first, then over the filled ones with visits >= min_visits and w(score) <= evict_w, in ring order from head; the rest
+    are dropped.  A written slot restarts at score 0.5, no visit, last = step; stats["state"] (int32 [8]) is advanced.  One launch,
+    no sync.  Every refusal is raised before anything is launched."""
+    fn = "scene_pool_push_evict"
+    if cfg.is_vmas:
+        raise ValueError(f"{fn}: VMASReverseTransport has no scene entry point")
+    shapes = scene_template_shapes(cfg)
+    B, M = int(mined["first"].shape[0]), int(pool["agent"].shape[0])
+    fixed, min_visits, evict_w = int(fixed), int(min_visits), float(evict_w)
+    _check_pool_stats(fn, stats, M)
+    if not 0 <= fixed < M:
+        raise ValueError(f"{fn}: fixed must be in [0, M) (got {fixed}, M {M})")
+    if min_visits < 0:
+        raise ValueError(f"{fn}: min_visits must be >= 0 (got {min_visits})")
+    if not 0.0 <= evict_w <= 1.0:
+        raise ValueError(f"{fn}: evict_w must be in [0, 1] (got {evict_w})")
+    N.expect_shape(mined["flags"], (B,), "mined.flags")
+    for k, s in shapes.items():
+        N.expect_shape(mined[k], (B,) + s, f"mined.{k}")
+        N.expect_shape(pool[k], (M,) + s, f"pool.{k}")
+    if slot_of is not None:
+        N.expect_shape(slot_of, (B,), "slot_of")
+    i32, obst = torch.int32, cfg.n_obs > 0
+    rc = N.lib().dgppo_env_scene_pool_push_evict(
+        C.byref(cfg), N.ptr(mined["first"], i32, "mined.first"), N.ptr(mined["flags"], i32, "mined.flags"),
+        N.ptr(mined["agent"], name="mined.agent"), N.ptr(mined["goal"], name="mined.goal"),
+        N.ptr(mined["obst"] if obst else None, name="mined.obst"), N.ptr(pool["agent"], name="pool.agent"),
+        N.ptr(pool["goal"], name="pool.goal"), N.ptr(pool["obst"] if obst else None, name="pool.obst"),
+        N.ptr(stats["score"], name="stats.score"), N.ptr(stats["visits"], i32, "stats.visits"), N.ptr(stats["last"], i32, "stats.last"),
+        N.ptr(stats["order"], i32, "stats.order"), M, fixed, min_visits, evict_w, int(step), N.ptr(stats["state"], i32, "stats.state"),
+        N.ptr(slot_of, i32, "slot_of"), B, N.stream_ptr())
+    N.check(rc, "dgppo_env_scene_pool_push_evict")
 
 
 def step(cfg: N.EnvCfg, st: State, action, nst: State, reward, cost, graph: Optional[Dict[str, torch.Tensor]] = None):

@@ -19,7 +19,10 @@ also rolls each scene once.
 Mined scenes (not in the reference): `Trainer(..., mine_scenes=M, mine_back=K, scene_frac=P)` keeps a device-resident pool of M
 scenes (env.scenes.ScenePool; `scenes`, if given, pinned in its first slots), starts the share P of every batch in it, and after
 every collect pushes the states K steps before the rollout's failures into its ring.  One rank only; the pool is part of the
-state a stopped run resumes from, and every save also writes it as `{log_dir}/scenes/{step}.npz`."""
+state a stopped run resumes from, and every save also writes it as `{log_dir}/scenes/{step}.npz`.
+`scene_priority=True` (needs mine_scenes) makes that a pool by priority (ScenePool(priority=True), csrc/env_scene_pool.hip): every
+iteration draws the scene envs' slots on the device in proportion to 4 s (1 - s) of the slot's failure score s and to its
+staleness, collects, mines, folds what the replays did into the scores, and pushes with eviction of solved and hopeless slots."""
 from __future__ import annotations
 
 import json
@@ -29,7 +32,7 @@ from time import time
 import numpy as np
 import torch
 
-from ..env.scenes import ScenePool, mix_assignment
+from ..env.scenes import ScenePool, mix_assignment, write_npz
 from ..utils import checkpoint as CK
 
 KEEP_STATES = 2          # state files kept under {log_dir}/resume: the newest and the one before it
@@ -69,7 +72,8 @@ class _Logger:
 class Trainer:
     def __init__(self, env, env_test, algo, gamma: float, n_env_train: int, n_env_test: int, log_dir: str, seed: int,
                  params: dict, save_log: bool = True, rank: int = 0, world: int = 1, resume: bool = False, scenes=None,
-                 scene_frac: float = 0.0, scene_jitter: float = 0.0, mine_scenes: int = 0, mine_back: int = 8):
+                 scene_frac: float = 0.0, scene_jitter: float = 0.0, mine_scenes: int = 0, mine_back: int = 8,
+                 scene_priority: bool = False):
         self.env, self.env_test, self.algo, self.gamma = env, env_test, algo, gamma
         self.n_env_train, self.n_env_test, self.log_dir, self.seed = n_env_train, n_env_test, log_dir, seed
         self.rank, self.world = int(rank), int(world)
@@ -102,13 +106,15 @@ class Trainer:
         self.scenes, self.scene_jitter = scenes, float(scene_jitter)
         # mining: the pool takes the place of the scenes in every collect; the given scenes are its pinned slots
         self.pool, self.mine_back = None, int(mine_back)
+        if scene_priority and int(mine_scenes) == 0:
+            raise ValueError("Trainer: scene_priority needs mine_scenes: it is a mode of the pool of mined scenes")
         if int(mine_scenes) != 0:
             if self.world > 1:
                 raise ValueError("Trainer: mine_scenes runs on one rank: every rank would keep a pool of its own failures and the "
                                  "ranks' windows would no longer be what one device runs")
             if self.mine_back < 0:
                 raise ValueError(f"Trainer: mine_back must be >= 0 (got {mine_back})")
-            self.pool = ScenePool(env, int(mine_scenes), pinned=scenes)
+            self.pool = ScenePool(env, int(mine_scenes), pinned=scenes, priority=bool(scene_priority), draw_seed=int(seed))
         source = self.pool if self.pool is not None else scenes
         self.n_scene = scene_count(scene_frac, n_env_train) if source is not None else 0
         if source is None and (float(scene_frac) != 0.0 or self.scene_jitter != 0.0):
@@ -134,7 +140,12 @@ class Trainer:
         sc = self.pool.to_scenes()
         if sc is not None:
             os.makedirs(os.path.join(self.log_dir, "scenes"), exist_ok=True)
-            sc.save(os.path.join(self.log_dir, "scenes", f"{step}.npz"))
+            path = os.path.join(self.log_dir, "scenes", f"{step}.npz")
+            if not self.pool.priority:
+                return sc.save(path)
+            st = self.pool.stats()         # a priority pool: the statistics of the saved slots as extra arrays (read_npz ignores them)
+            write_npz(path, sc.env_id, sc.num_agents, sc.rows["agent"], sc.rows["goal"], sc.rows.get("obst"), sc.obst_key, sc.names,
+                      extra={k: st[k][:sc.S] for k in ("score", "visits", "last")})
 
     def _save_state(self, step: int):
         CK.save_state(self.state_dict(step), os.path.join(self.resume_dir, f"{step}.pkl"))
@@ -233,10 +244,17 @@ class Trainer:
             source = self.pool if self.pool is not None else self.scenes
             if source is None:
                 rollouts = self.algo.collect(None, keys[lo:hi])
+            elif self.pool is not None and self.pool.priority:      # draw, collect, mine, score, evicting push: all on the device
+                drawn = self.pool.draw(self.n_env_train, self.n_scene, step, lo, hi)
+                rollouts = self.algo.collect(None, keys[lo:hi], scenes=self.pool, jitter=self.scene_jitter, scene_of=self.pool.drawn(drawn))
+                record = self.algo.rollout_record(rollouts)
+                mined = self.pool.score_from(record, drawn, self.pool.mix_flags(hi - lo), step, self.mine_back, 1e-6)
+                self.pool.push_from(record, self.mine_back, 1e-6, step=step, mined=mined)
             else:
                 scene_of = mix_assignment(self.n_env_train, self.n_scene, source.S, step, lo, hi)
                 rollouts = self.algo.collect(None, keys[lo:hi], scenes=source, jitter=self.scene_jitter, scene_of=scene_of)
-            if self.pool is not None:      # the envs that started in scenes included: a jittered scene that still fails is a failure
+            if self.pool is not None and not self.pool.priority:
+                # the envs that started in scenes included: a jittered scene that still fails is a failure
                 self.pool.push_from(self.algo.rollout_record(rollouts), self.mine_back, 1e-6)
             update_info = self.algo.update(rollouts, step)                      # global values on every rank (Engine.info)
             if self.logger is not None:

@@ -282,6 +282,64 @@ int32_t dgppo_env_scene_pool_push(const dgppo_env_cfg* cfg, const int32_t* first
                                   const float* goal_t, const float* obst_t, float* pool_agent, float* pool_goal,
                                   float* pool_obst, int32_t M, int32_t fixed, int32_t* state, int32_t* slot_of, int32_t B,
                                   void* stream);
+/* ---- the pool by priority (csrc/env_scene_pool.hip): per-slot statistics, all DEVICE arrays of length M <= 65536
+ *   score  float [M]   the EMA of the failed fraction of the slot's replays; 0.5 for a newly written and for a pinned slot
+ *   visits int32 [M]   replays since the slot was written
+ *   last   int32 [M]   the training step of the slot's last replay or write (pinned slots start at 0)
+ *   state  int32 [8]   head, filled, pushed_total, taken_last (as above), evicted_last, dropped_last (the last push),
+ *                      replays_last, replay_fails_last (the last score call)
+ * One priority serves the draw and the push; in fp32, every operation a single IEEE operation in this order:
+ *   w(s) = (4.0f * s) * (1.0f - s); a NaN or a value below 0 gives 0, a value above 1 gives 1
+ *   q(s) = (uint32)(w(s) * 65535.0f) + 1, truncated: in [1, 65536]
+ *
+ * What the replays of a rollout did, folded into the statistics.
+ *   scene_of, mix_flags [B]   the slot every env was assigned (dgppo_env_scene_pool_draw) and its bits from dgppo_env_scene_mix;
+ *                             mix_flags[b] is not read where scene_of[b] < 0
+ *   first [B]                 from dgppo_env_scene_mine of the same rollout
+ *   tally int32 [2 M]         scratch, zero on entry and zero again on return
+ *   beta in (0, 1], step
+ * For slot m, r counts the envs b with scene_of[b] == m && mix_flags[b] == 0 (an env that fell back ran a sampled episode and is
+ * no replay) and f those of them with first[b] >= 0.  Where r > 0: y = (float)f / (float)r, score[m] = score[m] + beta * (y -
+ * score[m]), visits[m] += r, last[m] = step; where r == 0 slot m is untouched.  state[6] and state[7] receive the sums of r and f.
+ * The counts are integers, summed by integer atomics (order-free); the float fold is one lane per slot.  Two launches.
+ * Refused on the host with an error that names dgppo_env_scene_pool_score: an invalid cfg, VMASReverseTransport, B < 0, M outside
+ * [1, 65536], beta outside (0, 1], NULL operands (the three [B] operands may be NULL at B == 0, which counts no replay).    */
+int32_t dgppo_env_scene_pool_score(const dgppo_env_cfg* cfg, const int32_t* scene_of, const int32_t* mix_flags, const int32_t* first,
+                                   float* score, int32_t* visits, int32_t* last, int32_t* tally, int32_t M, float beta, int32_t step,
+                                   int32_t* state, int32_t B, void* stream);
+/* The slot of every env of the window lo .. lo + B - 1 of a global batch of n_total envs of which n_scene are scene envs, drawn in
+ * proportion to priority times staleness.
+ *   scene_of [B] out   global env g = lo + b is a scene env iff (g + 1) n_scene / n_total > g n_scene / n_total (64-bit integer
+ *                      division), and then has the ordinal k = g n_scene / n_total; every other env gets -1
+ *   cum uint64 [M]     scratch: the inclusive prefix sums of Q
+ * Slot m is live iff m < fixed or m < fixed + state[1].  Q[m] = live ? (uint64)q(score[m]) * min(1 + max(step - last[m], 0),
+ * age_cap) : 0, total = sum of Q.  With total == 0 every scene env gets -1.  Otherwise scene env k takes Philox4x32-10 of counter
+ * (k, step, 0, 0) and key (lo32, hi32 of draw_seed), forms u = (word0 << 32) | word1 and t = the high 64 bits of u * total, and
+ * gets the smallest m whose inclusive prefix sum of Q exceeds t: a slot with Q == 0, an empty one included, is never drawn.
+ * Integer arithmetic throughout.  One workgroup: the prefix sum in chunks of the block size with a carry, one binary search per env.
+ * Refused on the host with an error that names dgppo_env_scene_pool_draw: an invalid cfg, VMASReverseTransport, B < 0, M outside
+ * [1, 65536], fixed outside [0, M), age_cap outside [1, 1024], n_total outside [1, 2^31), n_scene outside [0, n_total], a window
+ * outside the batch, NULL operands.  B == 0 returns 0.                                                                      */
+int32_t dgppo_env_scene_pool_draw(const dgppo_env_cfg* cfg, const float* score, const int32_t* last, const int32_t* state, int32_t M,
+                                  int32_t fixed, int32_t age_cap, int32_t step, uint64_t draw_seed, int64_t n_total, int64_t n_scene,
+                                  int64_t lo, uint64_t* cum, int32_t* scene_of, int32_t B, void* stream);
+/* dgppo_env_scene_pool_push with eviction by priority in place of the ring's "oldest first": the operands of that entry point, the
+ * statistics, min_visits >= 0, evict_w in [0, 1], step, the [8] state and order int32 [M], scratch.
+ * The taken envs and their ranks are as there.  The ranks go first to the empty ring positions filled, filled + 1, ..., then to the
+ * evictable filled ring positions in ring order from head — position p < filled (slot m = fixed + p) is evictable iff visits[m] >=
+ * min_visits && w(score[m]) <= evict_w, judged before anything is written — and the ranks beyond that are dropped.  A written slot
+ * gets the rows word for word, score = 0.5, visits = 0, last = step.  head moves to one past the last evicted position and stays
+ * when only empties were written; filled grows by the empties written; pushed_total grows by the slots written; taken_last,
+ * evicted_last and dropped_last are set as named; state[6], state[7] are not touched.  One workgroup, two ballot-and-prefix
+ * compactions (ring positions, envs); no atomic decides a slot: two runs give the same pool and statistics word for word.
+ * Refused on the host with an error that names dgppo_env_scene_pool_push_evict: what dgppo_env_scene_pool_push refuses, M > 65536,
+ * min_visits < 0, evict_w outside [0, 1], NULL statistics or order.  B == 0 is a push of nothing, and its [B] operands may be
+ * NULL.                                                                                                                     */
+int32_t dgppo_env_scene_pool_push_evict(const dgppo_env_cfg* cfg, const int32_t* first, const int32_t* flags, const float* agent_t,
+                                        const float* goal_t, const float* obst_t, float* pool_agent, float* pool_goal,
+                                        float* pool_obst, float* score, int32_t* visits, int32_t* last, int32_t* order, int32_t M,
+                                        int32_t fixed, int32_t min_visits, float evict_w, int32_t step, int32_t* state,
+                                        int32_t* slot_of, int32_t B, void* stream);
 
 /* ---- VMASReverseTransport (dgppo/env/vmas/vmas_reverse_transport.py) ------------------------------------------
  * n agents (discs of radius 0.03) push a hollow 0.6 x 0.6 box of mass 10 towards a goal past 3 disc obstacles.  The record

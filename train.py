@@ -34,6 +34,10 @@ FLAGS = [
     # steps before a rollout's first unsafe step); the share --scene-frac of every batch starts there, the scenes of --scenes FILE
     # are pinned in its first slots (README "Mining failure scenes")
     (("--mine-scenes",), "int", 0), (("--mine-back",), "int", 8),
+    # not in the reference: the pool by priority: slots are drawn in proportion to 4 s (1 - s) of their failure score s and to their
+    # staleness, empty slots never, and a push evicts solved and hopeless slots instead of the oldest (README "Mining failure scenes")
+    # (--mine-priority is the same flag under the family name of the pool's other flags)
+    (("--scene-priority", "--mine-priority"), "flag", False),
     # not in the reference: a share P of every training batch starts in the designed scenes of FILE (env.Scenes.save), moved by
     # up to J, the rest at the sampled reset; every evaluation also rolls each scene once (README "Training on scenes")
     (("--scenes",), "str", None), (("--scene-frac",), "float", 0.0), (("--scene-jitter",), "float", 0.0),
@@ -45,7 +49,7 @@ FLAGS = [
 # flags a resumed run may give differently: where it logs and what it is called play no part in the computation
 _RESUME_FREE = ("resume", "log_dir", "name", "debug")
 # flags newer than full-state checkpoints: a stopped run that does not record them ran without them, at their defaults
-_RESUME_LATER = ("scenes", "scene_frac", "scene_jitter", "mine_scenes", "mine_back")
+_RESUME_LATER = ("scenes", "scene_frac", "scene_jitter", "mine_scenes", "mine_back", "scene_priority")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -60,8 +64,13 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def _long(names) -> str:
+    """the flag's first long name: what argparse derives the attribute from, and what messages call it"""
+    return next(n for n in names if n.startswith("--"))
+
+
 def _dest(names) -> str:
-    return names[-1].lstrip("-").replace("-", "_")
+    return _long(names).lstrip("-").replace("-", "_")
 
 
 def _flags_to_store(a) -> dict:
@@ -80,9 +89,9 @@ def check_resume_flags(a, stored: dict) -> None:
         if k in _RESUME_LATER:
             stored = {k: default, **stored}
         if k not in stored:
-            diff.append(f"{names[-1]} (not recorded by the stopped run)")
+            diff.append(f"{_long(names)} (not recorded by the stopped run)")
         elif stored[k] != getattr(a, k):
-            diff.append(f"{names[-1]} ({stored[k]!r} in the stopped run, {getattr(a, k)!r} now)")
+            diff.append(f"{_long(names)} ({stored[k]!r} in the stopped run, {getattr(a, k)!r} now)")
     if diff:
         raise SystemExit("train.py --resume: these flags differ from the stopped run's: " + ", ".join(diff))
 
@@ -103,6 +112,8 @@ def check_resume(a) -> None:
 def check_mining(a) -> None:
     """--mine-scenes / --mine-back; needs no GPU.  SystemExit naming the flag at fault"""
     if a.mine_scenes == 0:
+        if a.scene_priority:
+            raise SystemExit("train.py: --scene-priority needs --mine-scenes: it is a mode of the pool of mined scenes")
         if a.mine_back != 8:
             raise SystemExit("train.py: --mine-back needs --mine-scenes: it says how many steps before a failure the mined scene starts")
         return
@@ -110,6 +121,8 @@ def check_mining(a) -> None:
         raise SystemExit(f"train.py: --mine-scenes must be >= 1, the capacity of the pool (got {a.mine_scenes})")
     if a.mine_back < 0:
         raise SystemExit(f"train.py: --mine-back must be >= 0 (got {a.mine_back})")
+    if a.scene_priority and a.mine_scenes > 65536:
+        raise SystemExit(f"train.py: --scene-priority takes a pool of at most 65536 scenes (got --mine-scenes {a.mine_scenes})")
     if a.scene_frac == 0.0:
         raise SystemExit("train.py: --mine-scenes needs --scene-frac: the share of every batch that starts in the pool")
     if a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -244,7 +257,8 @@ def train(a):
     trainer = Trainer(env=env, env_test=env_test, algo=algo, gamma=0.99, log_dir=log_dir, n_env_train=a.n_env_train,
                       n_env_test=a.n_env_test, seed=a.seed, params=schedule, save_log=write, rank=rank, world=world,
                       resume=a.resume is not None, scenes=scenes, scene_frac=a.scene_frac, scene_jitter=a.scene_jitter,
-                      **({} if a.mine_scenes == 0 else {"mine_scenes": a.mine_scenes, "mine_back": a.mine_back}))
+                      **({} if a.mine_scenes == 0 else {"mine_scenes": a.mine_scenes, "mine_back": a.mine_back}),
+                      **({"scene_priority": True} if a.scene_priority else {}))
     if write and a.resume is None:   # plain mappings (the reference dumps the argparse.Namespace object itself; test.py reads both)
         with open(f"{log_dir}/config.yaml", "w") as f:
             yaml.safe_dump(_flags_to_store(a), f)
