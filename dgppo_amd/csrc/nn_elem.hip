@@ -189,12 +189,7 @@ __device__ inline size_t gru_row(const GruArgs& a, int s, int tau) {
   return ((size_t)grp * a.T + tau) * a.n_inner + i;
 }
 __device__ inline float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-// GRU gate non-linearities on the hardware transcendental units: exp through v_exp_f32 (scaled by log2 e), the quotient
-// through v_rcp_f32; absolute error ~1e-7 on outputs in [-1, 1], far inside the 1e-5 parity tolerance, at ~1/4 of the
-// VALU instructions of expf / tanhf / IEEE division (the gate math was ~70 instructions per element).
-__device__ inline float gate_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ inline float gate_tanh(float x) { return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)), -1.0f); }
-
+// (gate_sigmoid / gate_tanh and the forward gate arithmetic gru_gate_fwd: nn_gru.h)
 
 #define GRU_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
@@ -313,11 +308,8 @@ __global__ void __launch_bounds__(256) gru_fwd_kernel(GruArgs a) {
         for (int r = 0; r < 4; ++r) {
           const int rl = rt * 16 + lq * 4 + r;
           const float hp = hs_cur[rl * GRU_HL + c];
-          const float rg = gate_sigmoid(g[rt][r][0] + acc[rt][0][r]);
-          const float zg = gate_sigmoid(g[rt][r][1] + acc[rt][1][r]);
-          const float hn = acc[rt][2][r] + bn;
-          const float ng = gate_tanh(g[rt][r][2] + rg * hn);
-          const float hnew = (1.0f - zg) * ng + zg * hp;
+          const GruGateFwd gg = gru_gate_fwd(g[rt][r][0], g[rt][r][1], g[rt][r][2], acc[rt][0][r], acc[rt][1][r], acc[rt][2][r], bn, hp, RTW == 2);
+          const float rg = gg.r, zg = gg.z, hn = gg.hn, ng = gg.n, hnew = gg.h;
           hs_nxt[rl * GRU_HL + c] = hnew;
           if (ok[rt][r]) {
             const size_t row = (size_t)(row0[rt][r] + tau * a.n_inner);
@@ -476,8 +468,7 @@ static int32_t gru_fwd_launch(GruArgs a, hipStream_t stream) {
   const int n_seq = a.n_seq;
   if (n_seq == 0) return 0;
   DGPPO_REQUIRE(a.gi && a.Wh && a.bhn && a.hs, "gru_fwd: NULL operand");
-  // 32-sequence tiles when there are enough of them to fill the device, otherwise 16 (half the MFMA chain per step)
-  if (cdiv(n_seq, 32) >= 512) {
+  if (gru_fwd_big_tiles(n_seq)) {            // (nn_gru.h: the two instances round h' differently)
     const size_t smem = sizeof(float) * 2 * 32 * GRU_HL;
     static thread_local int cap = 0;
     if (cap == 0) cap = gru_resident(reinterpret_cast<const void*>(&gru_fwd_kernel<2>), smem);

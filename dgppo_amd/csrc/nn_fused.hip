@@ -8,6 +8,7 @@
 #include <type_traits>
 #include "common.h"
 #include "nn_ln.h"
+#include "nn_gru.h"
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 #define FZ_H 64            // hidden width of every layer in the chain
@@ -232,27 +233,32 @@ __global__ void __launch_bounds__(64 * RW_WAVES) mlp_gi_fwd_rw_kernel(MlpGiArgs 
       // is one trip to L2 per iteration)
     static_assert(RW_WAVES == 16, "the staging below assumes 1024 threads");
     const float4 v1 = reinterpret_cast<const float4*>(a.W1)[tid], v2 = reinterpret_cast<const float4*>(a.W2)[tid];
-    float4 vi[3];
+    const bool want_gi = a.gi != nullptr;        // without gi (the caller forms it: dgppo_gi_gru1_head_fwd) Wi is not staged
+    float4 vi[3] = {};
+    if (want_gi) {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) vi[j] = reinterpret_cast<const float4*>(a.Wi)[j * 1024 + tid];
+      for (int j = 0; j < 3; ++j) vi[j] = reinterpret_cast<const float4*>(a.Wi)[j * 1024 + tid];
+    }
     {
       const int k = tid >> 4, c = (tid & 15) * 4;
       float* d1 = sW1 + k * RW_WL + c; float* d2 = sW2 + k * RW_WL + c;
       d1[0] = v1.x; d1[1] = v1.y; d1[2] = v1.z; d1[3] = v1.w;
       d2[0] = v2.x; d2[1] = v2.y; d2[2] = v2.z; d2[3] = v2.w;
     }
+    if (want_gi) {
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int q = j * 1024 + tid, k = q / 48, c = (q - k * 48) * 4;
-      float* d = sWi + k * RW_WIL + c;
-      d[0] = vi[j].x; d[1] = vi[j].y; d[2] = vi[j].z; d[3] = vi[j].w;
+      for (int j = 0; j < 3; ++j) {
+        const int q = j * 1024 + tid, k = q / 48, c = (q - k * 48) * 4;
+        float* d = sWi + k * RW_WIL + c;
+        d[0] = vi[j].x; d[1] = vi[j].y; d[2] = vi[j].z; d[3] = vi[j].w;
+      }
     }
   }
   if (tid < 64) {
     sP[tid] = a.b1[tid]; sP[64 + tid] = a.g1[tid]; sP[128 + tid] = a.be1[tid];
     sP[192 + tid] = a.b2[tid]; sP[256 + tid] = a.g2[tid]; sP[320 + tid] = a.be2[tid];
   }
-  if (tid < 192) sP[384 + tid] = a.bi[tid];
+  if (tid < 192 && a.gi != nullptr) sP[384 + tid] = a.bi[tid];
   __syncthreads();
   const int n_tiles = (a.M + 15) >> 4;
   const bool save = a.p1 != nullptr;
@@ -335,6 +341,14 @@ __global__ void __launch_bounds__(64 * RW_WAVES) mlp_gi_fwd_rw_kernel(MlpGiArgs 
     fetch(tile);
     layer(sW1, sP, a.p1, a.y1, a.st1, row0);
     layer(sW2, sP + 192, a.p2, a.y2, a.st2, row0);
+    if (!save && a.y2 != nullptr) {   // y2 alone (no gi): from the A operand, 16 bytes per lane
+      if (row0 + li < a.M) {
+        float4* yp = reinterpret_cast<float4*>(a.y2 + (size_t)(row0 + li) * FZ_H + lq * 16);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) yp[j] = make_float4(A[4 * j], A[4 * j + 1], A[4 * j + 2], A[4 * j + 3]);
+      }
+    }
+    if (a.gi == nullptr) continue;
     // gate projection: 12 column tiles in two halves (24 accumulator registers at a time)
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
@@ -1197,14 +1211,20 @@ extern "C" int32_t dgppo_mlp_gi_fwd(const float* X, int32_t ldx, const float* W1
                                     const float* Wi, const float* bi, float* p1, float* y1, float* st1, float* p2, float* y2,
                                     float* st2, float* gi, int32_t M, void* stream) {
   DGPPO_REQUIRE(M >= 0 && ldx >= FZ_H, "mlp_gi_fwd: bad shape M=%d ldx=%d", M, ldx);
-  DGPPO_REQUIRE(X && W1 && b1 && g1 && be1 && W2 && b2 && g2 && be2 && Wi && bi && gi, "mlp_gi_fwd: NULL operand");
-  const bool save = p1 || y1 || st1 || p2 || y2 || st2;
+  DGPPO_REQUIRE(X && W1 && b1 && g1 && be1 && W2 && b2 && g2 && be2 && Wi && bi, "mlp_gi_fwd: NULL operand");
+  // gi == NULL: the trunk alone, y2 is the result (dgppo_gi_gru1_head_fwd forms the gate inputs from it); then y2 may be given
+  // without the other saves
+  const bool save = p1 || y1 || st1 || p2 || st2 || (gi && y2);
   DGPPO_REQUIRE(!save || (p1 && y1 && st1 && p2 && y2 && st2), "mlp_gi_fwd: the saved activations are all-or-none");
+  DGPPO_REQUIRE(gi || y2, "mlp_gi_fwd: neither gi nor y2 to write");
+  const bool rw = (ldx & 3) == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W1) |
+                                      reinterpret_cast<uintptr_t>(W2) | reinterpret_cast<uintptr_t>(Wi)) & 15) == 0;
+  DGPPO_REQUIRE(gi || (rw && (reinterpret_cast<uintptr_t>(y2) & 15) == 0),
+                "mlp_gi_fwd: gi == NULL needs 16-byte aligned X, W1, W2, Wi, y2 and ldx a multiple of 4");
   if (M == 0) return 0;
   MlpGiArgs a{X, ldx, M, W1, b1, g1, be1, W2, b2, g2, be2, Wi, bi, p1, y1, st1, p2, y2, st2, gi};
   // rows per wave, weights in LDS (one 16-wave workgroup per CU): needs 16-byte addressable input rows
-  if ((ldx & 3) == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W1) | reinterpret_cast<uintptr_t>(W2) |
-                          reinterpret_cast<uintptr_t>(Wi)) & 15) == 0) {
+  if (rw) {
     static thread_local int cus = 0;
     if (cus == 0) {
       int dev = 0;
@@ -1255,12 +1275,7 @@ struct GruHeadArgs {
   float *hs, *hprev, *gates, *u, *out;    // hs [M,64]; hprev [M,64] / gates [M,256] / u [M,64] saved for training or NULL
   int M, n_out;
 };
-// GRU gate non-linearities on the hardware transcendental units: exp through v_exp_f32 (scaled by log2 e), the quotient
-// through v_rcp_f32; absolute error ~1e-7 on outputs in [-1, 1], far inside the 1e-5 parity tolerance, at ~1/4 of the
-// VALU instructions of expf / tanhf / IEEE division (the gate math was ~70 instructions per element).
-__device__ inline float gate_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ inline float gate_tanh(float x) { return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)), -1.0f); }
-
+// (gate_sigmoid / gate_tanh: nn_gru.h)
 
 template <bool TWO>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) gru1_head_fwd_kernel(GruHeadArgs a) {
@@ -1615,6 +1630,241 @@ extern "C" int32_t dgppo_gru1_head_fwd(const float* gi, const float* Wh, const f
   const int grid = tiles < cap[two] ? tiles : cap[two];
   if (two) hipLaunchKernelGGL(gru1_head_fwd_kernel<true>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(gru1_head_fwd_kernel<false>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
+  DGPPO_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- gate projection + one GRU step + value head, rows per WAVE: the tail of the constraint-value net's T = 1 passes --------------
+//   gi = y2 Wi + bi  (never leaves registers),  h' = GRU(gi, h0),  out = h' W1 + b1  [n_out <= 16]
+// (flax GRUCell, dgppo/nn/rnn.py:14-30, and the value Dense, dgppo/algo/module/value.py:41,76, on the rows of one step.)
+// It replaces the gate projection of mlp_gi_fwd_rw_kernel, gru_fwd_kernel at T = 1 and the head's dense_fwd_kernel, and with them
+// the 768-byte gi row written once and read once, and (inference) the hs row nobody reads.  With T = 1 the step is row-local, so a
+// WAVE owns 16 rows from y2 to out as in gru1_head_fwd_rw_kernel; no barrier after the weights are staged.
+// LDS: Wi and Wh [64][193] (98 816 B), W1 [64][17] (4 352 B), biases (1 088 B), one 16 x 68 tile per wave (4 352 B): 12 waves
+// = 156 480 B of the 160 KB (16 waves would need 173 888 B); one workgroup per CU, three waves per SIMD (<= 170 VGPRs).
+// Arithmetic, so that hs and gates keep the bits of the launches replaced:
+//   gi : summed from zero in the permuted k order of mlp_gi_fwd_rw_kernel (a lane's 16 k-values are 16 consecutive columns of its
+//        y2 row; step j of lane group lq contracts k = lq * 16 + j), then + bi;
+//   gh : summed from zero in the natural k order of gru_fwd_kernel (step kk contracts k = kk * 4 + lq).  The A fragments of that
+//        order come from the wave's tile (h0 rows written row-major, read back one float per step); Wh is staged with its rows
+//        permuted (row k at (k & 3) * 16 + (k >> 2)) so that both B fragments are read at [lq * 16 + step]: 64 different banks;
+//   gates: gru_gate_fwd (nn_gru.h).
+// The tile then holds h0 in the C/D layout for the update, which puts h' in its place (same lane, same element), and h' goes back
+// out as the head's A operand and as 16-byte stores of hs.
+// Every row operand of tile t + 1 is requested before tile t computes; with ids, the id of tile t + 2 as well.
+#define GG_WAVES 12
+#define GG_W1L 17
+#define GG_BIAS 272                                 // bi (192) | bhn (64) | b1 (16)
+#define GG_LDS_FLOATS (2 * 64 * RW_WIL + 64 * GG_W1L + GG_BIAS + GG_WAVES * 16 * RW_YL)
+static_assert(GG_LDS_FLOATS * sizeof(float) <= 160 * 1024, "gi_gru1_head_fwd_kernel: LDS");
+struct GiGruHeadArgs {
+  const float *y2, *Wi, *bi, *Wh, *bhn, *W1, *b1;   // y2 [M,64], Wi / Wh [64,192], bi [192], bhn [64], W1 [64,n_out], b1 [n_out]
+  const float* h0;                                  // NULL (zeros), dense [M,64], blocked (h0_rpb > 0) or mapped (h0_map.n_inner.d > 0)
+  float *out, *hs, *gates;                          // out [M, ldo]; hs [M,64] / gates [M,256] or NULL
+  int M, n_out, ldo;
+  int h0_rpb;
+  long h0_bstride;
+  GruH0Map h0_map;
+  bool big_tiles;                                   // gru_fwd_big_tiles(M): the rounding of h' gru_fwd_kernel has at this row count
+};
+
+__global__ void __launch_bounds__(64 * GG_WAVES) gi_gru1_head_fwd_kernel(GiGruHeadArgs a) {
+  extern __shared__ float sm[];
+  float* sWi = sm;                                  // [64][193]
+  float* sWh = sWi + 64 * RW_WIL;                   // [64][193], rows permuted
+  float* sW1 = sWh + 64 * RW_WIL;                   // [64][17], columns >= n_out zero
+  float* sB = sW1 + 64 * GG_W1L;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, lq = lane >> 4;
+  float* sT = sB + GG_BIAS + w * (16 * RW_YL);      // wave-private tile
+  {   // 96 KB of weights: eight 16-byte loads per thread, all requested before the first LDS write
+    static_assert(GG_WAVES == 12, "the staging below assumes 768 threads");
+    float4 vi[4], vh[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      vi[j] = reinterpret_cast<const float4*>(a.Wi)[j * 768 + tid];
+      vh[j] = reinterpret_cast<const float4*>(a.Wh)[j * 768 + tid];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int q = j * 768 + tid, k = q / 48, c = (q - k * 48) * 4;
+      float* di = sWi + k * RW_WIL + c;
+      float* dh = sWh + ((k & 3) * 16 + (k >> 2)) * RW_WIL + c;
+      di[0] = vi[j].x; di[1] = vi[j].y; di[2] = vi[j].z; di[3] = vi[j].w;
+      dh[0] = vh[j].x; dh[1] = vh[j].y; dh[2] = vh[j].z; dh[3] = vh[j].w;
+    }
+    for (int i = tid; i < 64 * 16; i += 64 * GG_WAVES) {
+      const int k = i >> 4, c = i & 15;
+      sW1[k * GG_W1L + c] = (c < a.n_out) ? a.W1[k * a.n_out + c] : 0.0f;
+    }
+    if (tid < 192) sB[tid] = a.bi[tid];
+    if (tid < 64) sB[192 + tid] = a.bhn[tid];
+    if (tid < 16) sB[256 + tid] = (tid < a.n_out) ? a.b1[tid] : 0.0f;
+  }
+  __syncthreads();
+  const int n_tiles = (a.M + 15) >> 4, step = gridDim.x * GG_WAVES;
+  const bool has_h0 = a.h0 != nullptr, mapped = has_h0 && a.h0_map.n_inner.d > 0, by_id = mapped && a.h0_map.ids != nullptr;
+  auto seq_of = [&](int tile) {                     // this lane's row of the tile in the A layout, clamped for loads
+    const int s = tile * 16 + li;
+    return s < a.M ? s : a.M - 1;
+  };
+  auto request_id = [&](int tile) { return a.h0_map.ids[gru_h0_map_cell(a.h0_map, seq_of(tile)).e]; };
+  float nY[16], nH[16];                             // the next tile's y2 and h0 rows: row li, columns lq * 16 .. + 15
+  auto request = [&](int tile, int id) {
+    const int s = seq_of(tile);
+    const float4* py = reinterpret_cast<const float4*>(a.y2 + (size_t)s * FZ_H + lq * 16);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { const float4 v = py[j]; nY[4 * j] = v.x; nY[4 * j + 1] = v.y; nY[4 * j + 2] = v.z; nY[4 * j + 3] = v.w; }
+    if (has_h0) {
+      const float* hp = a.h0 + (size_t)s * FZ_H;
+      if (mapped) {
+        const GruH0Cell cell = gru_h0_map_cell(a.h0_map, s);
+        hp = gru_h0_map_cell_row(a.h0, a.h0_map, cell, by_id ? (long)id : (long)cell.e);
+      } else if (a.h0_rpb > 0) {
+        const int b = s / a.h0_rpb;
+        hp = a.h0 + (size_t)b * a.h0_bstride + (size_t)(s - b * a.h0_rpb) * FZ_H;
+      }
+      const float4* ph = reinterpret_cast<const float4*>(hp + lq * 16);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { const float4 v = ph[j]; nH[4 * j] = v.x; nH[4 * j + 1] = v.y; nH[4 * j + 2] = v.z; nH[4 * j + 3] = v.w; }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) nH[j] = 0.0f;
+    }
+  };
+  int tile = w * gridDim.x + blockIdx.x;            // consecutive tiles on different CUs
+  int id_n = 0;                                     // with ids: the env of the NEXT request's row
+  if (tile < n_tiles) {
+    if (by_id) id_n = request_id(tile);
+    request(tile, id_n);
+    if (by_id && tile + step < n_tiles) id_n = request_id(tile + step);
+  }
+  for (; tile < n_tiles; tile += step) {
+    const int row0 = tile * 16, nxt = tile + step;
+    float Y[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) Y[j] = nY[j];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      *reinterpret_cast<float4*>(sT + li * RW_YL + lq * 16 + 4 * j) = make_float4(nH[4 * j], nH[4 * j + 1], nH[4 * j + 2], nH[4 * j + 3]);
+    if (nxt < n_tiles) {
+      request(nxt, id_n);
+      if (by_id && nxt + step < n_tiles) id_n = request_id(nxt + step);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    float Hk[16];                                   // h0 in the A layout of the natural k order
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) Hk[kk] = sT[li * RW_YL + kk * 4 + lq];
+    // hidden column group ct: gate tiles ct, ct + 4, ct + 8 of gi and of gh, 96 MFMAs
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+      f32x4 gi[3], gh[3];
+#pragma unroll
+      for (int t = 0; t < 3; ++t) { gi[t] = f32x4{0.f, 0.f, 0.f, 0.f}; gh[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+      float bq[2][2][6];                            // two k-steps per group, double-buffered (see mlp_gi_fwd_rw_kernel)
+      auto ldb = [&](int buf, int g) {
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+          const int o = (lq * 16 + g * 2 + kk) * RW_WIL + ct * 16 + li;
+#pragma unroll
+          for (int t = 0; t < 3; ++t) { bq[buf][kk][t] = sWi[o + t * 64]; bq[buf][kk][3 + t] = sWh[o + t * 64]; }
+        }
+      };
+      ldb(0, 0);
+#pragma unroll
+      for (int g = 0; g < 8; ++g) {
+        if (g + 1 < 8) ldb((g + 1) & 1, g + 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int t = 0; t < 3; ++t) {
+            gi[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(Y[g * 2 + kk], bq[g & 1][kk][t], gi[t], 0, 0, 0);
+            gh[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(Hk[g * 2 + kk], bq[g & 1][kk][3 + t], gh[t], 0, 0, 0);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      const int col = ct * 16 + li;
+      const float bir = sB[col], biz = sB[64 + col], bin = sB[128 + col], bn = sB[192 + col];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float* tp = sT + (lq * 4 + r) * RW_YL + col;
+        const GruGateFwd gg = gru_gate_fwd(gi[0][r] + bir, gi[1][r] + biz, gi[2][r] + bin, gh[0][r], gh[1][r], gh[2][r], bn, *tp, a.big_tiles);
+        *tp = gg.h;
+        const int row = row0 + lq * 4 + r;
+        if (a.gates != nullptr && row < a.M) {
+          float* gs = a.gates + (size_t)row * 256 + col;
+          gs[0] = gg.r; gs[64] = gg.z; gs[128] = gg.n; gs[192] = gg.hn;
+        }
+      }
+    }
+    // h' as the head's A operand (permuted contraction) and, 16 bytes per lane, as hs
+    float Hn[16];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float4 v = *reinterpret_cast<const float4*>(sT + li * RW_YL + lq * 16 + 4 * j);
+      Hn[4 * j] = v.x; Hn[4 * j + 1] = v.y; Hn[4 * j + 2] = v.z; Hn[4 * j + 3] = v.w;
+      if (a.hs != nullptr && row0 + li < a.M) reinterpret_cast<float4*>(a.hs + (size_t)(row0 + li) * FZ_H + lq * 16)[j] = v;
+    }
+    f32x4 ao = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) ao = __builtin_amdgcn_mfma_f32_16x16x4f32(Hn[kk], sW1[(lq * 16 + kk) * GG_W1L + li], ao, 0, 0, 0);
+    const float b = sB[256 + li];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = row0 + lq * 4 + r;
+      if (row < a.M && li < a.n_out) a.out[(size_t)row * a.ldo + li] = ao[r] + b;
+    }
+  }
+}
+
+extern "C" int32_t dgppo_gi_gru1_head_fwd(const float* y2, const float* Wi, const float* bi, const float* Wh, const float* bhn,
+                                          const float* W1, const float* b1, const float* h0, int32_t h0_form,
+                                          int32_t h0_rows_per_block, int64_t h0_block_stride, const int32_t* ids, int32_t n_env,
+                                          int32_t n_time, int32_t n_inner, int64_t env_stride, int64_t time_stride, float* out,
+                                          int32_t ldo, float* hs, float* gates, int32_t M, int32_t n_out, void* stream) {
+  DGPPO_REQUIRE(M >= 0 && n_out >= 1 && n_out <= 16 && ldo >= n_out, "gi_gru1_head_fwd: bad shape M=%d n_out=%d ldo=%d", M, n_out, ldo);
+  DGPPO_REQUIRE(y2 && Wi && bi && Wh && bhn && W1 && b1 && out, "gi_gru1_head_fwd: NULL operand");
+  DGPPO_REQUIRE(((reinterpret_cast<uintptr_t>(y2) | reinterpret_cast<uintptr_t>(Wi) | reinterpret_cast<uintptr_t>(Wh) |
+                  reinterpret_cast<uintptr_t>(hs) | reinterpret_cast<uintptr_t>(h0)) & 15) == 0,
+                "gi_gru1_head_fwd: y2, Wi, Wh, h0 and hs must be 16-byte aligned");
+  GiGruHeadArgs a{};
+  a.y2 = y2; a.Wi = Wi; a.bi = bi; a.Wh = Wh; a.bhn = bhn; a.W1 = W1; a.b1 = b1; a.h0 = h0;
+  a.out = out; a.hs = hs; a.gates = gates; a.M = M; a.n_out = n_out; a.ldo = ldo;
+  a.big_tiles = gru_fwd_big_tiles(M);
+  if (h0_form == DGPPO_H0_BLOCKS) {
+    DGPPO_REQUIRE(h0 != nullptr, "gi_gru1_head_fwd: blocked h0 is NULL");
+    DGPPO_REQUIRE(h0_rows_per_block >= 1, "gi_gru1_head_fwd: rows_per_block must be >= 1 (got %d)", h0_rows_per_block);
+    DGPPO_REQUIRE(h0_block_stride >= (int64_t)h0_rows_per_block * FZ_H && h0_block_stride % 4 == 0,
+                  "gi_gru1_head_fwd: block_stride must be a multiple of 4 and >= rows_per_block * 64");
+    a.h0_rpb = h0_rows_per_block; a.h0_bstride = (long)h0_block_stride;
+  } else if (h0_form == DGPPO_H0_MAP) {
+    DGPPO_REQUIRE(h0 != nullptr, "gi_gru1_head_fwd: mapped h0 is NULL");
+    DGPPO_REQUIRE(n_env >= 1 && n_time >= 1 && n_inner >= 1, "gi_gru1_head_fwd: bad sizes n_env=%d n_time=%d n_inner=%d", n_env,
+                  n_time, n_inner);
+    DGPPO_REQUIRE(env_stride % 4 == 0 && time_stride % 4 == 0 && env_stride >= 0 && time_stride >= 0,
+                  "gi_gru1_head_fwd: env_stride and time_stride must be non-negative multiples of 4 floats");
+    DGPPO_REQUIRE((int64_t)M <= (int64_t)n_env * n_time * n_inner, "gi_gru1_head_fwd: the map holds fewer than M = %d carries", M);
+    a.h0_map = gru_h0_map(ids, (long)env_stride, (long)time_stride, n_inner, n_time);
+  } else {
+    DGPPO_REQUIRE(h0_form == DGPPO_H0_DENSE, "gi_gru1_head_fwd: unknown h0 form %d", h0_form);
+  }
+  if (M == 0) return 0;
+  static thread_local int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+  }
+  const size_t smem = sizeof(float) * GG_LDS_FLOATS;
+  static thread_local bool attr = false;
+  if (!attr) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gi_gru1_head_fwd_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    DGPPO_REQUIRE(e == hipSuccess, "gi_gru1_head_fwd: cannot reserve %zu bytes of LDS per workgroup: %s", smem, hipGetErrorString(e));
+    attr = true;
+  }
+  const int tiles16 = (M + 15) / 16;
+  hipLaunchKernelGGL(gi_gru1_head_fwd_kernel, dim3(tiles16 < cus ? tiles16 : cus), dim3(64 * GG_WAVES), smem, (hipStream_t)stream, a);
   DGPPO_LAUNCH_CHECK();
   return 0;
 }

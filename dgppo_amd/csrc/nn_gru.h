@@ -23,6 +23,43 @@ __device__ __forceinline__ GruGateGrad gru_gate_grad(float d, float hp, float rg
   return o;
 }
 
+// GRU gate non-linearities on the hardware transcendental units: exp through v_exp_f32 (scaled by log2 e), the quotient
+// through v_rcp_f32; absolute error ~1e-7 on outputs in [-1, 1], far inside the 1e-5 parity tolerance, at ~1/4 of the
+// VALU instructions of expf / tanhf / IEEE division (the gate math was ~70 instructions per element).
+__device__ inline float gate_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ inline float gate_tanh(float x) { return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)), -1.0f); }
+
+// Forward of one GRU element from its gate inputs g = gi (x Wi + bi, already rounded to fp32) and the hidden products
+// a = h Wh summed from zero: the arithmetic of gru_fwd_kernel (nn_elem.hip), which the one-step kernel of nn_fused.hip that
+// forms gi itself repeats so that hs and gates keep their bits.  Contraction mode: off, with the two fused multiply-adds
+// written out.  They are the ones the compiler chose for gru_fwd_kernel while it was left to contract freely: n's argument in
+// one rounding, and h' = (1 - z) n + z h with ONE of the two products rounded first — (1 - z) n in the 32-sequence-tile
+// instance, z h in the 16-sequence-tile instance.  Both stay as they were: big_tiles says which instance the launch rule
+// (gru_fwd_big_tiles) picks for the row count, and the one-step kernel follows the same rule.  (Left free, the same
+// expressions came out of the one-step kernel as two packed products and an add: a third set of bits.)
+struct GruGateFwd {
+  float r, z, n, hn, h;     // the saved gates r | z | n | hn_lin and h'
+};
+
+__device__ __forceinline__ GruGateFwd gru_gate_fwd(float g_r, float g_z, float g_n, float a_r, float a_z, float a_n, float bn,
+                                                   float hp, bool big_tiles) {
+#pragma clang fp contract(off)
+  GruGateFwd o;
+  o.r = gate_sigmoid(g_r + a_r);
+  o.z = gate_sigmoid(g_z + a_z);
+  o.hn = a_n + bn;
+  o.n = gate_tanh(__fmaf_rn(o.hn, o.r, g_n));
+  const float zc = 1.0f - o.z;
+  o.h = big_tiles ? __fmaf_rn(hp, o.z, zc * o.n) : __fmaf_rn(zc, o.n, o.z * hp);
+  return o;
+}
+
+// 32-sequence tiles when there are enough of them to fill the device, otherwise 16 (half the MFMA chain per step)
+// This rule is part of the numerical contract, not only a launch heuristic: it decides the rounding of h' (above) in
+// gru_fwd_kernel and in gi_gru1_head_fwd_kernel alike.  Moving the threshold moves the bits of every pass whose row count
+// changes sides; tests/test_gi_gru1_head_gpu.py holds the two kernels to each other on both sides of it (16 352 / 16 353).
+static inline bool gru_fwd_big_tiles(int n_seq) { return (n_seq + 31) / 32 >= 512; }
+
 // 0.0f + du, as an add that is really executed (IEEE: -0.0 -> +0.0)
 __device__ __forceinline__ float gru_zero_carry(float du) { return __fadd_rn(0.0f, du); }
 
@@ -69,6 +106,23 @@ struct GruH0Map {
 
 static inline GruH0Map gru_h0_map(const int* ids, long env_stride, long time_stride, int n_inner, int n_time) {
   return GruH0Map{ids, env_stride, time_stride, gru_fast_div(n_inner), gru_fast_div(n_time)};
+}
+
+// The same address in two steps, for a kernel that requests ids[e] a tile before it needs the row: the env slot e of
+// sequence s and the offset of its cell inside the env's record, then the row from the env the id named.
+struct GruH0Cell {
+  unsigned e;
+  long off;
+};
+
+__device__ __forceinline__ GruH0Cell gru_h0_map_cell(const GruH0Map& m, int s) {
+  const unsigned c = gru_div((unsigned)s, m.n_inner), ag = (unsigned)s - c * (unsigned)m.n_inner.d;
+  const unsigned e = gru_div(c, m.n_time), t = c - e * (unsigned)m.n_time.d;
+  return GruH0Cell{e, (long)t * m.time_stride + (long)ag * 64};
+}
+
+__device__ __forceinline__ const float* gru_h0_map_cell_row(const float* base, const GruH0Map& m, const GruH0Cell& cell, long env) {
+  return base + env * m.env_stride + cell.off;
 }
 
 __device__ __forceinline__ const float* gru_h0_map_row(const float* base, const GruH0Map& m, int s) {

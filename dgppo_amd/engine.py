@@ -569,8 +569,9 @@ class Engine:
                 h0_all[:, :T].copy_(self._vh_carry(ro, e0, Eb))
                 h0_all[:, T].copy_(hstar.view(Eb, n, HC)[..., :H])
                 h0 = h0_all.view(-1, H)
-            act = self.Vh.forward(feats, n_seq=Eb * (T + 1) * n, T=1, h0=h0, tag="pre", train=False)
-            Vh_buf[e0:e0 + Eb].copy_(act["v"].view(Eb, T + 1, n, nh))
+            # the head writes the block's values where the targets read them
+            self.Vh.forward(feats, n_seq=Eb * (T + 1) * n, T=1, h0=h0, tag="pre", train=False,
+                            v_out=Vh_buf[e0:e0 + Eb].view(Eb * (T + 1) * n, nh))
             if restore:
                 ro._rnn_all[T, e0:e0 + Eb].copy_(ro._rnn_all[T + 1, e0:e0 + Eb])
         return Vl_buf, Vh_buf

@@ -200,16 +200,20 @@ class Net:
     """One network = flat params + flat grads + prepared GNN weights + forward/backward over a batch of graphs."""
 
     def __init__(self, kind: str, cfg: N.EnvCfg, gnn_layers: int, n_out: int, device, grads: Optional[torch.Tensor] = None,
-                 rnn: str = "gru", rnn_layers: int = 1, lean_attn0: bool = True):
+                 rnn: str = "gru", rnn_layers: int = 1, lean_attn0: bool = True, gi_in_step: bool = True):
         """grads: optional caller-owned flat gradient buffer (a slice of the engine's [g_policy | g_Vl | g_Vh | scalars]
         buffer, so that the data-parallel update all-reduces ALL gradients with one collective).
         rnn / rnn_layers: "gru" x L stacked cells (dgppo/nn/rnn.py:14-30; the carry of a row is [L * 64]) or "none".
         lean_attn0: the first layer's attention reads no edge features and saves no weights where the features allow it
         (GraphFeats.edges_from_rows) and the C ABI has such kernels (dgppo_attn_rows_supported); False keeps the general entry
-        points (tests, A/B measurements)."""
+        points (tests, A/B measurements).
+        gi_in_step: a value net's one-step inference pass from a given carry (T = 1, train=False: Vh's pre-pass, landscapes,
+        shield) forms the GRU gate inputs inside the step kernel, which also applies the head (dgppo_gi_gru1_head_fwd): neither
+        gi nor hs in memory; False keeps the three launches (tests, A/B measurements)."""
         assert kind in ("policy", "Vl", "Vh", "Vhg")
         self.kind, self.cfg, self.gnn_layers, self.n_out, self.device = kind, cfg, gnn_layers, n_out, device
         self.rnn, self.rnn_layers = rnn, (rnn_layers if rnn != "none" else 0)
+        self.gi_in_step = bool(gi_in_step)
         self.lean_attn0 = bool(lean_attn0) and K.attn_rows_supported(cfg, input_width(cfg), H_HEADS)
         # packed carry of one row: GRU [h_0 | h_1 | ...]; LSTM [c_0 | h_0 | c_1 | h_1 | ...] (the reference stacks (c, h) as
         # carries 0 and 1 of a layer, rnn.py:23-24); without a cell 64 zeros pass through
@@ -289,8 +293,10 @@ class Net:
 
     # ---- forward ---------------------------------------------------------------------------------------------------
     def forward(self, feats: GraphFeats, n_seq: int, T: int, h0: Optional[torch.Tensor], tag: str = "f",
-                hs_out: Optional[torch.Tensor] = None, train: bool = True, qt0: Optional[torch.Tensor] = None):
+                hs_out: Optional[torch.Tensor] = None, train: bool = True, qt0: Optional[torch.Tensor] = None,
+                v_out: Optional[torch.Tensor] = None):
         """Trunk + GRU + output Dense(s).  Graphs are ordered (group, time): G = (n_seq / n_inner) * T.
+        v_out: where a value net's head writes ([Rh, n_out], rows may be strided); the arena otherwise.
         qt0: the layer-0 queries Xa Mcat0 + cvec0 [G * n, H * Fp] where the caller already holds them (the one-launch rollout
         step emits them with the features); the layer-0 Dense is then skipped.
         Returns a dict of activations (views into this net's arena, valid until the next forward with the same tag)."""
@@ -352,7 +358,18 @@ class Net:
             xcat.view(G, n, 2 * OUT_DIM)[:, :, OUT_DIM:].copy_(pooled.view(G, 1, OUT_DIM).expand(G, n, OUT_DIM))
             x = xcat
         act["Rh"], act["n_inner"], act["mlp_in"] = Rh, n_inner, x
-        gi = A.get(f"{tag}.gi", Rh, 3 * HID)
+        # one step of a value net from a given carry: the step kernel forms gi from y2 and applies the head, where the library
+        # takes the operands (16-byte addressable rows); the trunk then stops at y2
+        # Inference only so far: the training form (hs and gates written) is faster per call too (182 -> 136 us at 131 072 rows),
+        # but the update trace, whole-iteration runs and output comparison of profiles/README.md, Round 13, were taken with the
+        # inference use alone, so the minibatch pass keeps its three launches until that protocol is run with it switched on
+        gi_step = (self.gi_in_step and not train and self.kind in ("Vl", "Vh") and self.rnn == "gru" and self.rnn_layers == 1
+                   and T == 1 and h0 is not None and x.is_cuda)
+        if gi_step:
+            y2 = A.get(f"{tag}.y2", Rh, HID)
+            hs = hs_out                                   # (written only where the caller wants the carry)
+            gi_step = K.mlp_y2_ok(x) and K.gi_gru1_head_ok(y2, h0, hs) and (v_out is None or v_out.stride(-1) == 1)
+        gi = None if gi_step else A.get(f"{tag}.gi", Rh, 3 * HID)
         if self.kind == "Vhg" or self.rnn != "gru":
             # 128-wide first Dense: the separate Dense / LayerNorm+ReLU kernels (the fused trunk kernel is 64-wide)
             sv = {nm: A.get(f"{tag}.{nm}", Rh, w) for nm, w in (("p1", HID), ("y1", HID), ("st1", 2), ("p2", HID), ("y2", HID), ("st2", 2))}
@@ -370,6 +387,8 @@ class Net:
                 saves = tuple(A.get(f"{tag}.{nm}{i}", Rh, w) for i in (1, 2) for nm, w in (("p", HID), ("y", HID), ("st", 2)))
                 for i in (1, 2):
                     act[f"p{i}"], act[f"y{i}"], act[f"st{i}"] = saves[3 * (i - 1):3 * i]
+            elif gi_step:
+                saves = (None, None, None, None, y2, None)
             K.mlp_gi_fwd(x, self.p("mlp.W1"), self.p("mlp.b1"), self.p("mlp.g1"), self.p("mlp.be1"), self.p("mlp.W2"),
                          self.p("mlp.b2"), self.p("mlp.g2"), self.p("mlp.be2"), self.p("gru.Wi"), self.p("gru.bi"), gi, saves)
         assert n_seq * T == Rh, (n_seq, T, Rh)
@@ -389,7 +408,8 @@ class Net:
         act["gi"] = gi
         simple = (self.rnn == "gru" and L == 1)           # the reference default: every fused kernel applies
         if simple:
-            hs = hs_out if hs_out is not None else A.get(f"{tag}.hs", Rh, HID)
+            if not gi_step:                               # (the step kernel of gi_step writes no hs that nobody asked for)
+                hs = hs_out if hs_out is not None else A.get(f"{tag}.hs", Rh, HID)
             # one step from a given carry: h before the step IS h0, which the backward reads in place of a saved copy
             hprev_is_h0 = train and T == 1 and h0 is not None and self.kind != "policy"
             hprev = A.get(f"{tag}.hprev", Rh, HID) if (train and not hprev_is_h0) else None
@@ -397,10 +417,15 @@ class Net:
             feat = hs
             act["hs"], act["hprev"], act["gates"] = hs, hprev, gates
         # one GRU step: the step and the head Dense(s) are row-local -> fused kernel.  Measured (MI355X): policy rollout
-        # shape 23.5 vs 34.2 us; for the one-layer value heads at pre-pass sizes the plain GRU kernel + Dense is faster
-        # (261 vs 350 us at 524 288 rows), so those keep the separate kernels.
+        # shape 23.5 vs 34.2 us.  For the one-layer value heads the step + head kernel that READS gi (gru1_head_fwd) was slower
+        # than the plain GRU kernel + Dense at pre-pass sizes (350 vs 261 us at 524 288 rows), so a value pass that does not take
+        # gi_step above (which forms gi itself and so saves its round trip through memory) keeps the separate kernels.
         fused_tail = (simple and T == 1 and self.kind == "policy")
-        if simple and not fused_tail:
+        if gi_step:
+            v = v_out if v_out is not None else A.get(f"{tag}.v", Rh, self.n_out)
+            K.gi_gru1_head_fwd(y2, self.p("gru.Wi"), self.p("gru.bi"), self.p("gru.Wh"), self.p("gru.bhn"), h0,
+                               self.p("head.Wo"), self.p("head.bo"), v, hs, None)
+        elif simple and not fused_tail:
             if h0_blocks:
                 K.gru_fwd_h0_blocks(gi, self.p("gru.Wh"), self.p("gru.bhn"), h0, hs, hprev, gates, n_seq, T, n_inner)
             elif h0_map:
@@ -478,8 +503,10 @@ class Net:
                 K.dense_fwd(feat, self.p("head.Ws"), self.p("head.bs"), u)
                 K.dense_fwd(u, self.p("head.Wms"), self.p("head.bms"), ms)
             act["u"], act["ms"] = u, ms
+        elif gi_step:
+            act["v"] = v
         else:
-            v = A.get(f"{tag}.v", Rh, self.n_out)
+            v = v_out if v_out is not None else A.get(f"{tag}.v", Rh, self.n_out)
             K.dense_fwd(feat, self.p("head.Wo"), self.p("head.bo"), v)
             act["v"] = v
         return act

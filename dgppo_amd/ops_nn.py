@@ -56,20 +56,23 @@ def dense_fwd(X, W, bias, Y, act: int = 0, accumulate: bool = False, trans_w: bo
 
 
 def mlp_gi_fwd(X, W1, b1, g1, be1, W2, b2, g2, be2, Wi, bi, gi, saves=None):
-    """gi = relu(LN(relu(LN(X W1 + b1)) W2 + b2)) Wi + bi in one kernel; saves = (p1, y1, st1, p2, y2, st2) or None."""
+    """gi = relu(LN(relu(LN(X W1 + b1)) W2 + b2)) Wi + bi in one kernel; saves = (p1, y1, st1, p2, y2, st2) or None.
+    gi None: the trunk alone (its y2 is the result, for gi_gru1_head_fwd); saves may then be (None, None, None, None, y2, None)."""
     xp, ldx, M, K = _mat(X, "X")
     if K != 64:
         raise ValueError(f"mlp_gi_fwd: X must be [M, 64], got {tuple(X.shape)}")
     for t, shp, nm in ((W1, (64, 64), "W1"), (W2, (64, 64), "W2"), (Wi, (64, 192), "Wi"), (b1, (64,), "b1"), (g1, (64,), "g1"),
-                       (be1, (64,), "be1"), (b2, (64,), "b2"), (g2, (64,), "g2"), (be2, (64,), "be2"), (bi, (192,), "bi"),
-                       (gi, (M, 192), "gi")):
+                       (be1, (64,), "be1"), (b2, (64,), "b2"), (g2, (64,), "g2"), (be2, (64,), "be2"), (bi, (192,), "bi")):
         N.expect_shape(t, shp, nm)
+    if gi is not None:
+        N.expect_shape(gi, (M, 192), "gi")
     sv = [None] * 6
     if saves is not None:
         for t, shp, nm in zip(saves, ((M, 64), (M, 64), (M, 2), (M, 64), (M, 64), (M, 2)), ("p1", "y1", "st1", "p2", "y2", "st2")):
-            N.expect_shape(t, shp, nm)
+            if t is not None:
+                N.expect_shape(t, shp, nm)
         sv = list(saves)
-    FLOPS[0] += 2.0 * M * (64 * 64 * 2 + 64 * 192)
+    FLOPS[0] += 2.0 * M * (64 * 64 * 2 + (64 * 192 if gi is not None else 0))
     rc = N.lib().dgppo_mlp_gi_fwd(xp, ldx, _p(W1), _p(b1), _p(g1), _p(be1), _p(W2), _p(b2), _p(g2), _p(be2), _p(Wi), _p(bi),
                                   *[_p(t) for t in sv], _p(gi), M, N.stream_ptr())
     N.check(rc, "dgppo_mlp_gi_fwd")
@@ -967,6 +970,62 @@ def gru_fwd_h0_map(gi, Wh, bhn, h0: H0Map, hs, hprev, gates, n_seq, T, n_inner):
     rc = N.lib().dgppo_gru_fwd_h0_map(_p(gi), _p(Wh), _p(bhn), base, ids, n_env, n_time, C.c_int64(h0.env_stride),
                                       C.c_int64(h0.time_stride), _p(hs), _p(hprev), _p(gates), n_seq, n_inner, N.stream_ptr())
     N.check(rc, "dgppo_gru_fwd_h0_map")
+
+
+def mlp_y2_ok(X) -> bool:
+    """mlp_gi_fwd(gi=None) serves X: 16-byte addressable rows (the library refuses the others; the parameters of a Net are
+    aligned by its layout and checked again there)"""
+    return X.is_cuda and X.data_ptr() % 16 == 0 and (X.shape[0] <= 1 or X.stride(0) % 4 == 0)
+
+
+def gi_gru1_head_ok(y2, h0, hs=None) -> bool:
+    """the operands dgppo_gi_gru1_head_fwd accepts: y2 / hs / the base of h0 16-byte aligned, the strides of a blocked or
+    mapped h0 multiples of 4 floats (what the library checks: it refuses the others, the separate launches serve them)"""
+    def al(t):
+        return t is None or (t.is_cuda and t.data_ptr() % 16 == 0)
+    if isinstance(h0, H0Blocks):
+        ok = al(h0.base) and h0.block_stride % 4 == 0
+    elif isinstance(h0, H0Map):
+        ok = al(h0.base) and h0.env_stride % 4 == 0 and h0.time_stride % 4 == 0
+    else:
+        ok = al(h0)
+    return bool(ok and y2.is_cuda and al(y2) and al(hs))
+
+
+def gi_gru1_head_fwd(y2, Wi, bi, Wh, bhn, h0, W1, b1, out, hs=None, gates=None):
+    """gi = y2 Wi + bi (kept on chip), one GRU step from h0 and the value head out = h' W1 + b1 in one launch
+    (dgppo_gi_gru1_head_fwd).  h0: None (zeros), [M, 64], H0Blocks or H0Map; out [M, n_out <= 16] may be a row-strided view;
+    hs [M, 64] / gates [M, 256] are written where given."""
+    M = y2.shape[0]
+    op, ldo, Mo, n_out = _mat(out, "out")
+    N.expect_shape(y2, (M, 64), "y2"); N.expect_shape(Wi, (64, 192), "Wi"); N.expect_shape(bi, (192,), "bi")
+    N.expect_shape(Wh, (64, 192), "Wh"); N.expect_shape(bhn, (64,), "bhn")
+    N.expect_shape(W1, (64, n_out), "W1"); N.expect_shape(b1, (n_out,), "b1")
+    if Mo != M:
+        raise ValueError(f"gi_gru1_head_fwd: out {tuple(out.shape)} does not match y2 {tuple(y2.shape)}")
+    for t, shp, nm in ((hs, (M, 64), "hs"), (gates, (M, 256), "gates")):
+        if t is not None:
+            N.expect_shape(t, shp, nm)
+    form, base, ids = 0, None, None                  # DGPPO_H0_DENSE / _BLOCKS / _MAP
+    rpb = bstride = n_env = n_time = n_inner = es = ts = 0
+    if isinstance(h0, H0Blocks):
+        if M > h0.n_seq:
+            raise ValueError(f"h0: {h0.n_blocks} blocks of {h0.rows_per_block} rows hold fewer than M = {M} carries")
+        form, base, rpb, bstride = 1, C.c_void_p(h0.base.data_ptr()), h0.rows_per_block, h0.block_stride
+    elif isinstance(h0, H0Map):
+        if M > h0.n_seq:
+            raise ValueError(f"h0: the map holds {h0.n_seq} carries, fewer than M = {M}")
+        base, ids, n_env, n_time = h0._args()
+        form, n_inner, es, ts = 2, h0.n_inner, h0.env_stride, h0.time_stride
+    else:
+        if h0 is not None:
+            N.expect_shape(h0, (M, 64), "h0")
+        base = _p(h0, "h0")
+    FLOPS[0] += 2.0 * M * (2 * 64 * 192 + 64 * n_out)
+    rc = N.lib().dgppo_gi_gru1_head_fwd(_p(y2), _p(Wi), _p(bi), _p(Wh), _p(bhn), _p(W1), _p(b1), base, form, rpb,
+                                        C.c_int64(bstride), ids, n_env, n_time, n_inner, C.c_int64(es), C.c_int64(ts), op, ldo,
+                                        _p(hs), _p(gates), M, n_out, N.stream_ptr())
+    N.check(rc, "dgppo_gi_gru1_head_fwd")
 
 
 class GatherDesc(C.Structure):

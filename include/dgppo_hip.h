@@ -415,7 +415,10 @@ int32_t dgppo_dense_bwd_w(const float* X, int32_t ldx, const float* dY, int32_t 
  * value.py:58-80) in one launch: y1 = relu(LN(X W1 + b1)), y2 = relu(LN(y1 W2 + b2)) (MLP of dgppo/nn/mlp.py:17-29, hidden
  * 64, LayerNorm scale g / bias be, eps 1e-6), gi = y2 Wi + bi [M,192] (the input half of flax GRUCell, dgppo/nn/rnn.py:14-30,
  * gates r|z|n).  X [M, >= 64] with leading dimension ldx.  p1/y1/st1/p2/y2/st2 (pre-LN [M,64], post-ReLU [M,64], LN
- * statistics [M,2] per layer) are what the backward needs: all six or none (inference).                          */
+ * statistics [M,2] per layer) are what the backward needs: all six or none (inference).  gi == NULL: the gate projection is
+ * skipped and y2 is the result (dgppo_gi_gru1_head_fwd forms gi from it); y2 may then be given without the other five, and is
+ * bit for bit the y2 of the call with gi.  That form needs 16-byte aligned X, W1, W2, Wi, y2 and ldx a multiple of 4 (refused
+ * otherwise).                                                                                                      */
 int32_t dgppo_mlp_gi_fwd(const float* X, int32_t ldx, const float* W1, const float* b1, const float* g1, const float* be1,
                          const float* W2, const float* b2, const float* g2, const float* be2, const float* Wi,
                          const float* bi, float* p1, float* y1, float* st1, float* p2, float* y2, float* st2, float* gi,
@@ -501,6 +504,26 @@ int32_t dgppo_head_bwd(const float* feat, int32_t ldf, const float* u, const flo
 int32_t dgppo_gru1_head_fwd(const float* gi, const float* Wh, const float* bhn, const float* h0, const float* W1,
                             const float* b1, const float* W2, const float* b2, float* hs, float* hprev, float* gates,
                             float* u, float* out, int32_t M, int32_t n_out, void* stream);
+/* The tail of a value net's one-step (T = 1) pass from the trunk's output, in one launch: gi = y2 Wi + bi (the input half of
+ * flax GRUCell, dgppo/nn/rnn.py:14-30; it stays on the CU), h' = GRUCell(gi, h0), out [M, ldo >= n_out] = h' W1 + b1 (the value
+ * Dense, dgppo/algo/module/value.py:41,76; n_out <= 16).  y2 [M,64] is what dgppo_mlp_gi_fwd writes with gi == NULL.  hs [M,64]
+ * (h') and gates [M,256] (r|z|n|hn_lin) are written where given: they are bit for bit those of dgppo_mlp_gi_fwd (with gi) +
+ * dgppo_gru_fwd at T = 1 with hprev = h0; out sums over k in another order than dgppo_dense_fwd (fp32 rounding of a reordered
+ * 64-term sum).  h0 by h0_form:
+ *   DGPPO_H0_DENSE   h0 [M,64], or NULL for zeros;
+ *   DGPPO_H0_BLOCKS  row m at h0 + (m / h0_rows_per_block) * h0_block_stride + (m % h0_rows_per_block) * 64 (dgppo_gru_fwd_h0_blocks);
+ *   DGPPO_H0_MAP     row m through the map of dgppo_gru_fwd_h0_map (ids, n_env, n_time, n_inner, env_stride, time_stride).
+ * The arguments of the other forms are ignored.  y2, Wi, Wh, h0 and hs must be 16-byte aligned and the strides multiples of 4
+ * floats, otherwise the call is refused (the three separate launches serve such operands).  Rows >= M are neither read into a
+ * result nor written.                                                                                                        */
+#define DGPPO_H0_DENSE 0
+#define DGPPO_H0_BLOCKS 1
+#define DGPPO_H0_MAP 2
+int32_t dgppo_gi_gru1_head_fwd(const float* y2, const float* Wi, const float* bi, const float* Wh, const float* bhn,
+                               const float* W1, const float* b1, const float* h0, int32_t h0_form, int32_t h0_rows_per_block,
+                               int64_t h0_block_stride, const int32_t* ids, int32_t n_env, int32_t n_time, int32_t n_inner,
+                               int64_t env_stride, int64_t time_stride, float* out, int32_t ldo, float* hs, float* gates,
+                               int32_t M, int32_t n_out, void* stream);
 /* Scratch for dgppo_dense_bwd_w's two-stage reduction (per-workgroup partial sums, then one reduce kernel): the caller
  * owns it, like every other buffer (16-byte aligned device memory, reusable by consecutive calls on one stream).  The
  * returned size lets every workgroup keep its own slab (the MFMA kernels write one per CU, the narrow-K kernel up to

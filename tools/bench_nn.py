@@ -160,6 +160,49 @@ if which in ("all", "h0map"):
                iters=50, bytes_=4.0 * Mp * 320)
         timeit(f"pre-pass gru_fwd M={Mp}: time-major map", lambda: K.gru_fwd_h0_map(gip, Wh, bh, pmap, hsp, None, None, Mp, 1, nm),
                iters=50, bytes_=4.0 * Mp * 320)
+if which in ("all", "gistep"):
+    # Vh's one-step tail from the trunk's input rows to the values: the three launches (mlp_gi_fwd with gi, gru_fwd_h0_map,
+    # dense_fwd) against the pair (mlp_gi_fwd without gi, gi_gru1_head_fwd; only where the library has it: the same script times
+    # an older library).  Pre-pass form: 4 227 072 rows (4096 envs x 129 steps x 8 agents), mapped h0 without ids, nothing saved.
+    # Training form: 131 072 rows (128 envs by ids x 128 steps x 8), the six saves, hs and gates written.  Step form: 32 768
+    # rows (4096 envs x 8, one step: the shield's and the landscapes' size), dense h0, nothing saved.  The trunk of each form is
+    # also timed alone, with and without its gate projection.  Three repeats, alternating
+    Bm, Tm, nm, Em, nh = 4096, 128, 8, 128, 2
+    tm = torch.randn(Tm + 2, Bm, nm, 64, device=dev) * 0.5
+    g_ = torch.Generator(device="cpu").manual_seed(2)
+    rnd = lambda *s, k=1.0: (k * torch.randn(*s, generator=g_)).to(dev)
+    P = [rnd(64, 64, k=0.2), rnd(64, k=0.1), 1.0 + rnd(64, k=0.1), rnd(64, k=0.1), rnd(64, 64, k=0.2), rnd(64, k=0.1),
+         1.0 + rnd(64, k=0.1), rnd(64, k=0.1), rnd(64, 192, k=0.2), rnd(192, k=0.1)]
+    Wh, bh, Wo, bo = rnd(64, 192, k=0.2), rnd(64, k=0.1), rnd(64, nh, k=0.3), rnd(nh, k=0.1)
+    has_pair = hasattr(N.lib(), "dgppo_gi_gru1_head_fwd")
+    ids = torch.randperm(Bm, device=dev)[:Em].to(torch.int32)
+    for label, M, hmap, train in (("pre-pass", Bm * (Tm + 1) * nm, K.H0Map(tm[0], tm.stride(1), tm.stride(0), Tm + 1, nm, Bm, n_env_src=Bm), False),
+                                  ("minibatch", Em * Tm * nm, K.H0Map(tm[1], tm.stride(1), tm.stride(0), Tm, nm, Em, ids=ids, n_env_src=Bm), True),
+                                  ("step", Bm * nm, tm[3].reshape(Bm * nm, 64), False)):
+        X = torch.randn(M, 64, device=dev).relu_()
+        gi = torch.empty(M, 192, device=dev); hs = torch.empty(M, 64, device=dev); v = torch.empty(M, nh, device=dev)
+        y2 = torch.empty(M, 64, device=dev)
+        sv = tuple(torch.empty(M, w, device=dev) for w in (64, 64, 2, 64, 64, 2)) if train else None
+        gt = torch.empty(M, 256, device=dev) if train else None
+
+        def three():
+            K.mlp_gi_fwd(X, *P, gi, sv)
+            if isinstance(hmap, K.H0Map):
+                K.gru_fwd_h0_map(gi, Wh, bh, hmap, hs, None, gt, M, 1, nm)
+            else:
+                K.gru_fwd(gi, Wh, bh, hmap, hs, None, gt, M, 1, nm)
+            K.dense_fwd(hs, Wo, bo, v)
+
+        def pair():
+            K.mlp_gi_fwd(X, *P, None, sv if train else (None, None, None, None, y2, None))
+            K.gi_gru1_head_fwd(sv[4] if train else y2, P[8], P[9], Wh, bh, hmap, Wo, bo, v, hs if train else None, gt)
+        for rep in range(3):
+            timeit(f"Vh {label} tail M={M}: three launches", three, iters=20)
+            if has_pair:
+                timeit(f"Vh {label} tail M={M}: pair", pair, iters=20)
+            timeit(f"Vh {label} trunk M={M}: with gi", lambda: K.mlp_gi_fwd(X, *P, gi, sv), iters=20)
+            if has_pair:
+                timeit(f"Vh {label} trunk M={M}: y2 only", lambda: K.mlp_gi_fwd(X, *P, None, sv if train else (None, None, None, None, y2, None)), iters=20)
 if which in ("all", "featlayout"):
     # dgppo_graph_feats reading the env-major record [B, T+1, ...] against the time-major one [T+1, B, ...] (env and time stride
     # swapped): the minibatch form (128 envs by ids x 128 steps = 16 384 graphs) and the pre-pass form (4096 envs x 129 steps =
